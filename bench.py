@@ -13,7 +13,9 @@ overlap of the gases' g points and the merged g-point map (:1452-1483).
 Metric = wavenumber-points/s = nwav * (ngas + N_pass) / t, N_pass = the passes over the spectrum the searches swept on the
 device (the reference's counter total_comp_cost, find_g_points.cpp:320, also counts the requests the memo of interval
 errors answered; reported beside it).  Ranks run independent jobs (weak scaling, no data-path collective); rank 0 prints ONE
-JSON line.  Beside the headline, on one GPU: the same job gas after gas, and round 3's single-gas step (`single_gas`).
+JSON line.  A plain run sets up, warms up, times the steps and prints that line; with --full, beside the headline, on one
+GPU: the same job gas after gas, round 3's single-gas step (`single_gas`), the optimiser and shortwave legs, the end-to-end
+tool chains and the CPU baseline.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 
 --config 1 (default)  BASELINE configs[1], the configuration the metric is quoted on: as above.
 --config 3            BASELINE configs[3]: ONE find_g_points job over the 13 narrow longwave bands (test/config.h:141-142)
@@ -85,6 +87,12 @@ def parse():
     ap.add_argument("--cpu-gases", type=int, default=3)
     # no device work at all: rendezvous (gloo), the one all-reduce, the JSON line.  For the CPU test of the launcher.
     ap.add_argument("--dry-run", action="store_true")
+    # everything beside the headline (CPU baselines, the gas-after-gas and single-gas legs, the PCIe figure, the optimiser and
+    # shortwave legs, the end-to-end tool chains, the strong-scaling leg): off by default, so that a plain run sets up, warms
+    # up, times the steps and prints the result line
+    ap.add_argument("--full", action="store_true")
+    # after the timed steps: what the last timed step computed, as DIR/<name>.npy (float32 / float64, at most 64 MB in all)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None)
     args = ap.parse_args()
     if args.nwav is None:
         args.nwav = 3_300_000 if args.config == 2 else 7_200_000
@@ -415,7 +423,7 @@ def lut_opt_cpu_baseline(model, scenes, cfg, evaluations=10):
             "seconds_per_evaluation": dt, "cost_at_start": J_rt + J_b}
 
 
-def lut_opt_bench(ctx, iterations, sharded=False, rank=0, world=1, sw=False, cpu=False):
+def lut_opt_bench(ctx, iterations, sharded=False, rank=0, world=1, sw=False, cpu=False, outputs=None):
     """Second half of the headline metric: LUT-optimisation iterations/s (solve_adept.cpp:295-299 logs one
     line per L-BFGS iteration).  Synthetic CKD model with the shapes of configs[4]: ng = 64, 6 x 53 (T, p)
     grid, H2O look-up table with 12 mole fractions (nx ~ 3e5), 8 scenarios x 50 columns x 54 layers."""
@@ -462,6 +470,8 @@ def lut_opt_bench(ctx, iterations, sharded=False, rank=0, world=1, sw=False, cpu
     t0 = time.perf_counter()
     res = opt.minimize(max_iterations=iterations, convergence_criterion=0.0, bounded=True)
     dt = time.perf_counter() - t0
+    if outputs is not None:                                  # what the minimisation hands its caller
+        outputs.update(x=res["x"], summary=np.array([res["cost"], res["gradient_norm"], res["iterations"], res["status"]], dtype=np.float64))
     n_eval = 0
     t1 = time.perf_counter()
     for _ in range(20):
@@ -501,6 +511,46 @@ def lut_opt_bench(ctx, iterations, sharded=False, rank=0, world=1, sw=False, cpu
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 20          # per-wavenumber arrays longer than this are written as a fixed, seeded sample of this many points
+
+
+def dump_arrays(path, arrays):
+    """Write {name: array} as path/<name>.npy: integers and float32 as float32 (exact below 2^24), the rest as float64."""
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = a.astype(np.float32 if a.dtype in (np.float32, np.int32, np.int16, np.int8, np.uint8, np.bool_) else np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the limit of %d" % (total, DUMP_LIMIT_BYTES))
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def find_g_outputs(res, nwav):
+    """The arrays a caller of pipeline.find_g_points_resident receives on rank 0: the per-gas tables of the g points, the
+    overlap of the gases' g points and the merged g-point map.  The per-wavenumber maps (nwav int32 each) are sampled at the
+    same DUMP_SAMPLE seeded positions, written as `sample_index`."""
+    import torch
+    arrays = {"summary": np.array([res["ng"], res.get("n_unassigned", -1), res["cost_sum"], res["comp_cost_sum"], res["points"]],
+                                  dtype=np.float64),
+              "band_number": np.asarray(res["band_number"])}
+    idx = None
+    if "g_point" in res:
+        idx = np.arange(nwav) if nwav <= DUMP_SAMPLE else np.sort(np.random.default_rng(20261016).choice(nwav, DUMP_SAMPLE, replace=False))
+        arrays["sample_index"] = idx.astype(np.float64)
+        idx_d = torch.as_tensor(idx, device=res["g_point"].device)
+        arrays["g_point"] = res["g_point"][idx_d].cpu().numpy()
+    for gi, g in enumerate(res["gases"]):
+        for k in ("n_g_points", "band_number", "rank1", "rank2", "error", "sorting_variable", "status", "comp_cost", "g_min", "g_max"):
+            arrays["%s_%s" % (g["name"], k)] = np.asarray(g[k], dtype=np.float64)
+        if idx is not None:
+            arrays["%s_g_point" % g["name"]] = res["gas_g_point"][gi][idx_d].cpu().numpy()
+    return arrays
+
+
 def find_g_main(args, ctx, dist, rank, world, barrier, use_dist):
     """configs[1] (default; weak scaling: every rank its own single-gas, single-band job) and configs[3] (one 13-band,
     8-gas job dealt to the ranks; strong scaling): warm-up, K timed steps between barriers, ONE all-reduce of
@@ -511,6 +561,7 @@ def find_g_main(args, ctx, dist, rank, world, barrier, use_dist):
     nwav, nlay = args.nwav, args.nlay
     info = {}
     extra = {}
+    last_res = [None]                         # config 1: the result dict of the latest job step
     if args.config in (2, 3):
         step3, info, extra = (config3_bench if args.config == 3 else config2_bench)(args, ctx, dist, rank, world)
         od = None
@@ -526,6 +577,7 @@ def find_g_main(args, ctx, dist, rank, world, barrier, use_dist):
 
         def job_step(side_by_side):
             res = job.run(args.tolerance, args.tolerance_tolerance, args.max_iterations, gases_side_by_side=side_by_side)
+            last_res[0] = res
             info.update(ng=res["ng"], ng_per_gas=[int(sum(g["n_g_points"])) for g in res["gases"]],
                         status=[int(g["status"][0]) for g in res["gases"]], comp_cost=res["comp_cost_sum"], cost_sum=res["cost_sum"],
                         n_unassigned=res["n_unassigned"], phase_seconds=res["phase_seconds"],
@@ -553,6 +605,9 @@ def find_g_main(args, ctx, dist, rank, world, barrier, use_dist):
     # the single collective of the path: max elapsed, total passes, total final cost (RCCL over xGMI)
     from ecckd_amd import shard
     dt, passes, total_cost, ranks_seen = shard.reduce_scalars(dt, passes, info.get("cost_sum", 0.0), device=dev, count=True)
+    if args.dump_outputs and rank == 0:
+        dump_arrays(args.dump_outputs, find_g_outputs(info if args.config in (2, 3) else last_res[0], nwav))
+    last_res[0] = None
 
     gw_calls, gw_ms, gw_pts = ctx.profile_get("find_g_gases")          # the windows in which the gases' searches ran side by side
 
@@ -565,7 +620,7 @@ def find_g_main(args, ctx, dist, rank, world, barrier, use_dist):
     h2d_ms = None
     gas_after_gas = None
     single_gas = None
-    if rank == 0 and world == 1 and args.config == 1:
+    if args.full and rank == 0 and world == 1 and args.config == 1:
         try:
             any_od = next(iter(job.od.values()))
             host_od = torch.empty((nlay, nwav), dtype=torch.float32).pin_memory()
@@ -581,7 +636,7 @@ def find_g_main(args, ctx, dist, rank, world, barrier, use_dist):
         except RuntimeError:
             h2d_ms = None
         head_info = dict(info)
-    if rank == 0 and world == 1 and args.config == 1 and not args.no_gas_after_gas:
+    if args.full and rank == 0 and world == 1 and args.config == 1 and not args.no_gas_after_gas:
         ctx.profile_enable(max(1, args.profile_stride))
         barrier()
         t1 = time.perf_counter()
@@ -606,7 +661,7 @@ def find_g_main(args, ctx, dist, rank, world, barrier, use_dist):
                          "frac_per_launch": sq_pts * bpp / max(sq_ms * 1e-3, 1e-12) / 1e9 / HBM_PEAK_GBS,
                          "note": "the same job with the reference's gas loop (find_g_points.cpp:655): merge, reorder, prepare, search, "
                                  "release, one gas after the other on one stream; every sweep launch has the device to itself"}
-    if rank == 0 and world == 1 and args.config == 1 and not args.no_single_gas:
+    if args.full and rank == 0 and world == 1 and args.config == 1 and not args.no_single_gas:
         job.close()
         torch.cuda.empty_cache()
         p1, wn_h, dwn_h, od1, bg1 = make_inputs(torch, nwav, nlay, syn.SEED_BASE + 1, device=dev, spectra=args.spectra, nlines=args.nlines)
@@ -800,12 +855,12 @@ def find_g_main(args, ctx, dist, rank, world, barrier, use_dist):
                                              "overlapped; the tools' reader streams a gas's files while the previous gas is prepared"}
         if lut_sharded is not None:
             out["lut_opt"] = lut_sharded
-        elif world == 1 and not args.no_lut_opt and args.config == 1:
+        elif args.full and world == 1 and not args.no_lut_opt and args.config == 1:
             out["lut_opt"] = lut_opt_bench(ctx, args.lut_opt_iterations, cpu=not args.no_cpu)
             out["lut_opt"]["shortwave"] = lut_opt_bench(ctx, args.lut_opt_iterations, sw=True)
-        if world == 1 and not args.no_sw and args.config == 1:
+        if args.full and world == 1 and not args.no_sw and args.config == 1:
             out["sw_find_g"] = sw_find_g_bench(ctx)
-        if world == 1 and not args.no_e2e and args.config == 1:
+        if args.full and world == 1 and not args.no_e2e and args.config == 1:
             # the end-to-end number north_star asks for: the do_all_lw chain with the tools as fresh child processes at the
             # headline size against the CPU oracle chain (tools/e2e_bench.py); a failure there must not cost the headline line
             try:
@@ -825,7 +880,7 @@ def find_g_main(args, ctx, dist, rank, world, barrier, use_dist):
             except Exception as exc:                                      # noqa: BLE001
                 import traceback
                 out["tools_fsck_job"] = {"error": repr(exc), "traceback": traceback.format_exc()[-1500:]}
-        if world == 1 and not args.no_cpu and args.config == 1:
+        if args.full and world == 1 and not args.no_cpu and args.config == 1:
             cb = cpu_baseline(args, args.cpu_sample, nlay, syn.SEED_BASE + 1, args.tolerance, args.tolerance_tolerance,
                               args.max_iterations, ctx)
             out["cpu_baseline"] = {"value": cb["points"] / cb["seconds"], "unit": "wavenumber-points/s",
@@ -854,15 +909,18 @@ def config4_main(args, ctx, dist, rank, world, barrier):
     sharded = dist is not None
     res = {}
     t = {}
+    outputs = {}
     for name, sw in (("longwave", False), ("shortwave", True)):
         barrier()
         t0 = time.perf_counter()
         res[name] = lut_opt_bench(ctx, args.lut_opt_iterations, sharded=sharded, rank=rank, world=world, sw=sw,
-                                  cpu=(rank == 0 and not args.no_cpu))
+                                  cpu=(args.full and rank == 0 and not args.no_cpu), outputs=outputs.setdefault(name, {}))
         barrier()
         t[name] = time.perf_counter() - t0
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_arrays(args.dump_outputs, {"%s_%s" % (name, k): v for name, o in outputs.items() for k, v in o.items()})
     its = sum(r["iterations"] for r in res.values())
     secs = sum(r["iterations"] / r["iters_per_s"] for r in res.values())
     return {"metric": "LUT-opt iterations/s", "value": its / secs, "unit": "iterations/s", "n_gpus": world, "steps": 1, "warmup": 0,
@@ -972,12 +1030,13 @@ def main():
         out = config4_main(args, ctx, dist, rank, world, barrier)
     else:
         out = find_g_main(args, ctx, dist, rank, world, barrier, use_dist)
-        strong = args.strong_leg if args.strong_leg is not None else world > 1
+        strong = args.strong_leg if args.strong_leg is not None else (args.full and world > 1)
         if args.config == 1 and strong:
             # the strong-scaling leg north_star describes: ONE configs[3] job (13 bands x 8 gases) dealt to all the ranks
             import copy
             a3 = copy.copy(args)
             a3.config = 3
+            a3.dump_outputs = None                 # the outputs are the headline job's
             torch.cuda.empty_cache()
             leg = find_g_main(a3, ctx, dist, rank, world, barrier, use_dist)
             if rank == 0:

@@ -1,6 +1,6 @@
 """The NetCDF classic reader / writer (file parts of rows a1, a9, a21) against an independent implementation
 (scipy.io.netcdf_file) in both directions, and on the reference's own classic data file
-(data/mie_droplet_scattering.nc, read in place when the reference tree is present)."""
+(data/mie_droplet_scattering.nc, cut to 10 x 40 points by tests/golden/make_nc_fixture.py)."""
 import os
 
 import numpy as np
@@ -9,16 +9,14 @@ from scipy.io import netcdf_file
 
 from ecckd_amd import ncio, EcckdError
 
-# the reference's own NetCDF-classic data file, read where it lies (not copied into the repo); absent on the GPU box
-GOLDEN = "/root/reference/data/mie_droplet_scattering.nc"
-needs_reference = pytest.mark.skipif(not os.path.exists(GOLDEN), reason="reference tree not present")
+# the reference's own NetCDF-classic data file, a fixture of the suite
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mie_droplet_scattering.nc")
 
 
-@needs_reference
 def test_reads_the_reference_data_file():
     ref = netcdf_file(GOLDEN, "r", mmap=False)
     with ncio.NcFile(GOLDEN) as f:
-        assert f.dim("effective_radius") == 50 and f.dim("wavenumber") == 396
+        assert f.dim("effective_radius") == 10 and f.dim("wavenumber") == 40
         for name, v in ref.variables.items():
             t, shape = f.var_info(name)
             assert shape == v.shape and t == 5                     # all FLOAT

@@ -7,10 +7,10 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/${tag}_profiles; mkdir -p $out
 quiet="--no-cpu --no-lut-opt --no-sw --no-e2e"
 # per-kernel totals of the headline step
-rocprofv3 --kernel-trace --stats -d $out/ks -o ks --output-format csv -- python3 bench.py --steps 2 --warmup 1 $quiet > $out/ks_bench.json 2> $out/ks.err
+rocprofv3 --kernel-trace --stats -d $out/ks -o ks --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 $quiet > $out/ks_bench.json 2> $out/ks.err
 # the same with the side-by-side steps only: the UNION of the time in which a sweep launch was executing (the launches of the six
 # streams overlap: launches x average duration is not the device time of the sweep) and its bytes over that time
-rocprofv3 --kernel-trace -d $out/kt -o kt --output-format csv -- python3 bench.py --steps 2 --warmup 1 $quiet --no-gas-after-gas --no-single-gas > $out/kt_bench.json 2> $out/kt.err
+rocprofv3 --kernel-trace -d $out/kt -o kt --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 $quiet --no-gas-after-gas --no-single-gas > $out/kt_bench.json 2> $out/kt.err
 python3 - > $out/sweep_union.json 2>> $out/kt.err <<PYEOF
 import json, subprocess, glob
 line = json.loads(open("$out/kt_bench.json").read().strip().splitlines()[-1])
@@ -23,16 +23,16 @@ u["bench_line_roofline"] = {k: rl[k] for k in ("achieved", "frac", "avg_launch_m
 print(json.dumps(u, indent=1))
 PYEOF
 # the same job gas after gas ONLY (no overlap of launches): the per-kernel averages a reader can price with bytes per launch
-rocprofv3 --kernel-trace --stats -d $out/ksq -o ksq --output-format csv -- python3 bench.py --steps 2 --warmup 1 $quiet --gases-side-by-side 1 --no-gas-after-gas --no-single-gas > $out/ksq_bench.json 2> $out/ksq.err
+rocprofv3 --kernel-trace --stats -d $out/ksq -o ksq --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 $quiet --gases-side-by-side 1 --no-gas-after-gas --no-single-gas > $out/ksq_bench.json 2> $out/ksq.err
 cp $out/ksq/ksq_kernel_stats.csv $out/kernel_stats_gas_after_gas.csv 2>/dev/null
 # HBM bytes of the dominant kernel: separate --pmc passes, kernel trace only beside them
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $c -d $out/pmc_$c -o p --output-format csv -- python3 bench.py --steps 1 --warmup 0 $quiet --no-gas-after-gas --no-single-gas > $out/pmc_$c.json 2> $out/pmc_$c.err
+  rocprofv3 --kernel-trace --pmc $c -d $out/pmc_$c -o p --output-format csv -- python3 bench.py --full --steps 1 --warmup 0 $quiet --no-gas-after-gas --no-single-gas > $out/pmc_$c.json 2> $out/pmc_$c.err
 done
 python3 tools/traffic_json.py k_rt_lw_bb_mirror $out/pmc_FETCH_SIZE/p_counter_collection.csv $out/pmc_WRITE_SIZE/p_counter_collection.csv $out/pmc_FETCH_SIZE.json > $out/traffic_k_rt_lw_bb.json
 # the bench line as the driver runs it; its `traffic` comes from profiles/<tag>_traffic_k_rt_lw_bb.json: this build's, just measured
 cp $out/traffic_k_rt_lw_bb.json profiles/${tag}_traffic_k_rt_lw_bb.json
-python3 bench.py > $out/bench.json 2> $out/bench.err
+python3 bench.py --full > $out/bench.json 2> $out/bench.err
 # K6 (g-point averaging) and K2 / K7: timings, then the SQ counters and HBM bytes of K6
 python3 tools/k267_probe.py > $out/k267_probe.json 2> $out/k267.err
 # ... and the kernels' own durations (K2's probe figure includes its call's constants upload and flag read-back)
@@ -56,7 +56,7 @@ done
 # one step's kernel trace)
 python3 tools/sweep_probe.py > $out/sweep_probe.json 2> $out/sp.err
 ECCKD_BG64=1 python3 tools/sweep_probe.py > $out/sweep_probe_double_rows.json 2>> $out/sp.err
-rocprofv3 --kernel-trace -d $out/bb -o bb --output-format rocpd -- python3 bench.py --steps 1 --warmup 0 $quiet > /dev/null 2> $out/bb.err
+rocprofv3 --kernel-trace -d $out/bb -o bb --output-format rocpd -- python3 bench.py --full --steps 1 --warmup 0 $quiet > /dev/null 2> $out/bb.err
 python3 tools/batch_breakdown.py $(ls $out/bb/*.db | head -1) > $out/batch_breakdown.txt 2>> $out/bb.err
 # the searches of the six prepared gases: gas after gas / side by side; the job by the tools on files
 python3 tools/gases_probe.py --widths 1,6,3,1 --out $out/gases_probe.json > $out/gases_probe.log 2>&1
@@ -69,7 +69,7 @@ grep -E "k_sort|k_iota|Name" $out/sortks/s_kernel_stats.csv > $out/sort_kernel_s
 # the other configurations
 python3 bench.py --config 2 --steps 3 > $out/bench_config2.json 2> $out/c2.err
 python3 bench.py --config 3 --steps 2 > $out/bench_config3.json 2> $out/c3.err
-python3 bench.py --config 4 > $out/bench_config4.json 2> $out/c4.err
+python3 bench.py --full --config 4 > $out/bench_config4.json 2> $out/c4.err
 # gpurun returns at most 64 MiB: keep the summaries, drop the raw traces they were computed from
 cp $out/ks/ks_kernel_stats.csv $out/kernel_stats.csv 2>/dev/null
 rm -rf $out/ks $out/ksq $out/k267ks $out/optks $out/opt_FETCH_SIZE $out/opt_WRITE_SIZE $out/kt $out/pmc_FETCH_SIZE $out/pmc_WRITE_SIZE $out/k6_*/ $out/bb
