@@ -1250,3 +1250,43 @@ def inflate(ctx, streams, out_bytes):
                                 status.ctypes.data_as(C.POINTER(C.c_int))))
     ends = np.concatenate([[0], np.cumsum(want)]).astype(np.int64)
     return [out[ends[k]:ends[k + 1]].tobytes() for k in range(n)], status[:n]
+
+
+def cloud_sorting_variable(ctx, cloud_wavenumber, ssa, asymmetry, wavenumber, out=None):
+    """reorder_cloud_spectrum.cpp:111-123: the optically thick absorptance of one size bin (ssa[nknot], asymmetry[nknot] on the
+    Mie grid cloud_wavenumber[nknot]) interpolated onto `wavenumber` (float64 device tensor) -> float64 device tensor."""
+    torch = _torch()
+    x = np.ascontiguousarray(cloud_wavenumber, dtype=np.float64)
+    s = np.ascontiguousarray(ssa, dtype=np.float64)
+    g = np.ascontiguousarray(asymmetry, dtype=np.float64)
+    if s.size != x.size or g.size != x.size:
+        raise EcckdError(_lib.PARAMETER_ERROR, "cloud_sorting_variable: ssa, asymmetry and wavenumber differ in length")
+    if out is None:
+        out = torch.empty(wavenumber.numel(), dtype=torch.float64, device=ctx.device)
+    ctx.fence_from_torch()
+    check(ctx.lib.ecckd_cloud_sorting_variable_dev(ctx.handle, x.size, _hptr(x), _hptr(s), _hptr(g), wavenumber.numel(),
+                                                   _dptr(wavenumber), _dptr(out)))
+    return out
+
+
+def cloud_partition(ctx, ssi, rank, sorting_variable, band_begin, band_end, max_reflectance_range=0.26, capacity=4096):
+    """find_g_points.cpp:586-636: the g points of the cloud pseudo-gas, ssi / rank (int32) / sorting_variable device tensors
+    in wavenumber order, band_begin / band_end the first / last index of every band.
+    -> dict(n_g_points, band_number, rank1, rank2, error, median) as numpy arrays."""
+    bb = np.ascontiguousarray(band_begin, dtype=np.int64)
+    be = np.ascontiguousarray(band_end, dtype=np.int64)
+    nband = bb.size
+    ngb = np.zeros(nband, dtype=np.int32)
+    ng = C.c_int()
+    band = np.zeros(capacity, dtype=np.int32)
+    r1 = np.zeros(capacity, dtype=np.int64)
+    r2 = np.zeros(capacity, dtype=np.int64)
+    err = np.zeros(capacity)
+    med = np.zeros(capacity)
+    ctx.fence_from_torch()
+    check(ctx.lib.ecckd_cloud_partition_dev(ctx.handle, ssi.numel(), _dptr(ssi), _dptr(rank), _dptr(sorting_variable), nband,
+                                            _hptr(bb, C.c_int64), _hptr(be, C.c_int64), float(max_reflectance_range), capacity,
+                                            _hptr(ngb, C.c_int), C.byref(ng), _hptr(band, C.c_int), _hptr(r1, C.c_int64),
+                                            _hptr(r2, C.c_int64), _hptr(err), _hptr(med)))
+    n = ng.value
+    return dict(n_g_points=ngb, band_number=band[:n], rank1=r1[:n], rank2=r2[:n], error=err[:n], median=med[:n])

@@ -1,9 +1,11 @@
 // find_g_points [key=value ...] [file.cfg]
 //
-// Drop-in for the reference executable of the same name (src/ecckd/find_g_points.cpp:407-1664, without the
-// cloud pseudo-gas of :541-652, which the shipped configurations leave commented out): for every gas in
+// Drop-in for the reference executable of the same name (src/ecckd/find_g_points.cpp:407-1664): for every gas in
 // `gases` and every band of its reordering file, partition the reordered spectrum into g points whose heating-
 // rate error is within `heating_rate_tolerance`, then overlap the gases' g points and write the g-points file.
+// In the shortwave, `cloud <name>` adds the cloud pseudo-gas of :541-652 (<name>.reordering_input from
+// reorder_cloud_spectrum, <name>.max_reflectance_range): bands split into g points of equal solar energy along the cloud's
+// ordering (ecckd_cloud_partition_dev), the first constituent of the overlap.
 // Keys (:443-523, :655-771): output, ssi, iprofile, heating_rate_tolerance, tolerance_tolerance, max_iterations,
 // averaging_method, flux_weight, min_pressure, max_no_rayleigh_wavenumber, gases, prepend_path, append_path,
 // log_level; per gas <gas>.input / scaling / conc, <gas>.background_input / _scaling / _conc, reordering_input,
@@ -165,7 +167,10 @@ int main(int argc, char** argv) {
     } else {
       LOG("Assuming longwave spectral region (ssi not provided)\n");
     }
-    if (config.exist("cloud")) fail(ECCKD_PARAMETER_ERROR, "The cloud pseudo-gas is not supported by this tool");
+    // the cloud pseudo-gas (:543-652): shortwave only; its g points are found by process 0 once the gases' searches are in
+    std::string cloud_str;
+    const bool have_cloud = config.read(cloud_str, "cloud");
+    if (have_cloud && !do_sw) fail(ECCKD_PARAMETER_ERROR, "Don't yet know how to sort cloud properties in the longwave");
     int iprofile = 0;
     config.read(iprofile, "iprofile");
     std::vector<double> tolerance_in;
@@ -618,9 +623,57 @@ int main(int argc, char** argv) {
       by_task[(size_t)br.gas * nband + br.band] = &br;
     }
     double final_cost = 0.0;
-    std::vector<GasResult> gases(ngas);
+    // the cloud, if any, is the first constituent (:650, :1448-1451): first in constituent_id, the overlap and n_gases
+    const int c0 = have_cloud ? 1 : 0, nconst = ngas + c0;
+    std::vector<GasResult> gases(nconst);
+    if (have_cloud) {
+      GasResult& res = gases[0];
+      res.molecule = cloud_str;
+      LOG("*** FINDING G POINTS FOR %s\n", cloud_str.c_str());
+      double max_reflectance_range = 0.26;
+      config.read(max_reflectance_range, "max_reflectance_range", cloud_str.c_str());
+      // the cloud's ordering file (:552-565); it sets the bands of nothing else: those of the gases stay in place
+      const std::vector<double> bb1 = band_bound1, bb2 = band_bound2, wn_now = wavenumber;
+      const int nband_gases = nband;
+      const size_t nwav_gases = nwav;
+      Ordering co;
+      read_ordering(cloud_str, co);
+      const int nband_cloud = nband;
+      const size_t nwav_cloud = nwav;
+      band_bound1 = bb1; band_bound2 = bb2; wavenumber = wn_now; nband = nband_gases; nwav = nwav_gases;
+      // (the reference does not check this)
+      if (nwav_cloud != nwav || ssi.size() != nwav || nband_cloud != nband)
+        fail(ECCKD_PARAMETER_ERROR, "The ordering of %s has %zu wavenumbers in %d bands, the gases %zu in %d (ssi %zu)", cloud_str.c_str(),
+             nwav_cloud, nband_cloud, nwav, nband, ssi.size());
+      DevBuf d_ssi_c, d_sv_c;
+      d_ssi_c.upload(dev, ssi);
+      d_sv_c.upload(dev, co.sorting_variable);
+      co.d_rank.upload(dev, co.rank);
+      const int cloud_capacity = 4096;
+      std::vector<int> band_number(cloud_capacity), ngb(nband);
+      std::vector<int64_t> r1(cloud_capacity), r2(cloud_capacity);
+      std::vector<double> err(cloud_capacity), med(cloud_capacity);
+      int ngc = 0;
+      ck(ecckd_cloud_partition_dev(dev.ctx(), nwav, d_ssi_c.as<double>(), co.d_rank.as<int32_t>(), d_sv_c.as<double>(), nband,
+                                   co.ibegin.data(), co.iend.data(), max_reflectance_range, cloud_capacity, ngb.data(), &ngc,
+                                   band_number.data(), r1.data(), r2.data(), err.data(), med.data()));
+      res.n_g_points = ngb;
+      res.band_number.assign(band_number.begin(), band_number.begin() + ngc);
+      res.rank1.assign(r1.begin(), r1.begin() + ngc);
+      res.rank2.assign(r2.begin(), r2.begin() + ngc);
+      res.error.assign(err.begin(), err.begin() + ngc);
+      res.sorting_variable.assign(med.begin(), med.begin() + ngc);
+      for (int k = 0; k < ngc; ++k)
+        LOG("  Band %d, g point %d: ranks %lld-%lld, sorting variable range %g\n", res.band_number[k], k, (long long)res.rank1[k],
+            (long long)res.rank2[k], res.error[k]);
+      std::vector<int32_t> gr1(res.rank1.begin(), res.rank1.end()), gr2(res.rank2.begin(), res.rank2.end());
+      res.d_g_point.alloc(dev, nwav * sizeof(int32_t));
+      ck(ecckd_gas_g_point_dev(dev.ctx(), nwav, co.d_rank.as<int32_t>(), ngc, gr1.data(), gr2.data(), res.d_g_point.as<int32_t>()));
+      ck(ecckd_synchronize(dev.ctx()));
+      LOG("\n");
+    }
     for (int gi = 0; gi < ngas; ++gi) {
-      GasResult& res = gases[gi];
+      GasResult& res = gases[c0 + gi];
       res.molecule = gas_list[gi];
       std::vector<int32_t>& rank = order_rank[gi];
       for (int b = 0; b < nband; ++b) {
@@ -664,19 +717,19 @@ int main(int argc, char** argv) {
       capacity += (int)g.rank1.size();
     }
     int ng = 0;
-    std::vector<int> band_number(capacity), g_min((size_t)ngas * capacity), g_max((size_t)ngas * capacity);
-    ck(ecckd_overlap_g_points(ngas, nband, n_g_points.data(), gas_offset.data(), sorting_all.data(), capacity, &ng, band_number.data(),
+    std::vector<int> band_number(capacity), g_min((size_t)nconst * capacity), g_max((size_t)nconst * capacity);
+    ck(ecckd_overlap_g_points(nconst, nband, n_g_points.data(), gas_offset.data(), sorting_all.data(), capacity, &ng, band_number.data(),
                               g_min.data(), g_max.data()));
     band_number.resize(ng);
     std::vector<const int32_t*> d_gp;
-    for (int k = 0; k < ngas; ++k) {
+    for (int k = 0; k < nconst; ++k) {
       gases[k].g_min.assign(g_min.begin() + (size_t)k * capacity, g_min.begin() + (size_t)k * capacity + ng);
       gases[k].g_max.assign(g_max.begin() + (size_t)k * capacity, g_max.begin() + (size_t)k * capacity + ng);
       d_gp.push_back(gases[k].d_g_point.as<int32_t>());
     }
     DevBuf d_g_point(dev, nwav * sizeof(int32_t));
     int64_t n_unassigned = 0;
-    ck(ecckd_merge_g_points_dev(dev.ctx(), nwav, ngas, d_gp.data(), ng, capacity, g_min.data(), g_max.data(), d_g_point.as<int32_t>(),
+    ck(ecckd_merge_g_points_dev(dev.ctx(), nwav, nconst, d_gp.data(), ng, capacity, g_min.data(), g_max.data(), d_g_point.as<int32_t>(),
                                 &n_unassigned));
     std::vector<int32_t> g_point = d_g_point.download<int32_t>();
     if (n_unassigned > 0) WARN("%lld wavenumbers are not assigned to a g point", (long long)n_unassigned);
@@ -722,7 +775,7 @@ int main(int argc, char** argv) {
     file.att(history_line(argc, argv), "history");
     file.att(config.str(), "config");
     file.end_define();
-    file.write("n_gases", {(double)ngas});
+    file.write("n_gases", {(double)nconst});
     file.write("wavenumber1_band", band_bound1);
     file.write("wavenumber2_band", band_bound2);
     file.write_as_double("band_number", band_number);

@@ -302,6 +302,71 @@ def reorder_spectrum(ctx, input_path, output_path, band_bound1, band_bound2, ipr
     return dict(spectrum=s, key=key, column_optical_depth=col, band_number=iband, rank=rank)
 
 
+def reorder_cloud_spectrum(ctx, input_path, wavenumber_input, output_path, isize, band_bound1=None, band_bound2=None, config_str="",
+                           history=None):
+    """reorder_cloud_spectrum.cpp:31-201: the optically thick absorptance of size bin `isize` of a Mie scattering file on the grid
+    of `wavenumber_input`, ranked per band, written as the reordering file of the cloud pseudo-gas.  Returns the order dict."""
+    import torch
+    with ncio.NcFile(wavenumber_input) as f:
+        wn = f.read("wavenumber")
+    with ncio.NcFile(input_path) as f:
+        cloud_wn = f.read("wavenumber")
+        nsize = f.var_info("single_scattering_albedo")[1][0]
+        if not 0 <= isize < nsize:
+            raise EcckdError(PARAMETER_ERROR, "isize = %d is outside the %d size bins of %s" % (isize, nsize, input_path))
+        ssa = f.read("single_scattering_albedo", isize)
+        asymmetry = f.read("asymmetry_factor", isize)
+    d_wn = torch.as_tensor(wn, device=ctx.device)
+    dwn = api.derive_d_wavenumber(ctx, d_wn).cpu().numpy()                                                  # :86-92
+    if band_bound1 is None:                                                                                 # :132-137
+        band_bound1, band_bound2 = [max(0.0, wn[0] - dwn[0])], [wn[-1] + dwn[-1]]
+    band_bound1, band_bound2 = np.array(band_bound1, dtype=np.float64), np.array(band_bound2, dtype=np.float64)
+    key = api.cloud_sorting_variable(ctx, cloud_wn, ssa, asymmetry, d_wn)
+    iband, bb, be = api.band_ranges(wn, band_bound1, band_bound2)
+    if np.any(bb > be):
+        raise EcckdError(PARAMETER_ERROR, "reorder_cloud_spectrum: band %d contains no wavenumbers" % int(np.nonzero(bb > be)[0][0]))
+    rank, _ = api.stable_argsort_bands(ctx, key, bb, be, want_ordered=False)
+    key, rank = key.cpu().numpy(), rank.cpu().numpy()
+    band_bound1[0], band_bound2[-1] = max(wn[0], band_bound1[0]), min(wn[-1], band_bound2[-1])              # :156-161
+    ncio.write_order(output_path, band_bound1, band_bound2, wn, dwn, iband, rank, key, None, molecule="cloud", config_str=config_str,
+                     history=history)
+    return dict(wavenumber=wn, d_wavenumber=dwn, sorting_variable=key, band_number=iband, rank=rank,
+                wavenumber1_band=band_bound1, wavenumber2_band=band_bound2)
+
+
+def cloud_g_points(ctx, cloud, ssi, nwav=None, nband=None):
+    """find_g_points.cpp:543-652: the single-gas g points of the cloud pseudo-gas.
+    cloud: dict(name, reordering_input, max_reflectance_range=0.26).  nwav / nband: those of the gases, checked."""
+    import torch
+    order = ncio.read_order(cloud["reordering_input"])
+    iband = order["band_number"]
+    nb = order["wavenumber1_band"].size
+    if (nwav is not None and iband.size != nwav) or (nband is not None and nb != nband) or len(ssi) != iband.size:
+        raise EcckdError(PARAMETER_ERROR, "The ordering of %s has %d wavenumbers in %d bands, the gases %s in %s" %
+                         (cloud["name"], iband.size, nb, nwav, nband))
+    bb, be = _band_index_ranges(iband, nb)
+    dev = ctx.device
+    rank = torch.as_tensor(order["rank"], device=dev)
+    res = api.cloud_partition(ctx, torch.as_tensor(np.asarray(ssi, dtype=np.float64), device=dev), rank,
+                              torch.as_tensor(order["sorting_variable"], device=dev), bb, be,
+                              cloud.get("max_reflectance_range", 0.26))
+    gp = api.gas_g_point(ctx, rank, res["rank1"], res["rank2"])
+    out = dict(name=cloud["name"], n_g_points=[int(v) for v in res["n_g_points"]], band_number=[int(v) for v in res["band_number"]],
+               rank1=[int(v) for v in res["rank1"]], rank2=[int(v) for v in res["rank2"]], error=[float(v) for v in res["error"]],
+               sorting_variable=[float(v) for v in res["median"]], status=[], comp_cost=[])
+    return out, gp
+
+
+def _band_index_ranges(iband, nband):
+    """First / last index of every band of a band_number array (-1, -1 for an empty band)."""
+    bb, be = np.full(nband, -1, dtype=np.int64), np.full(nband, -1, dtype=np.int64)
+    for b in range(nband):
+        idx = np.nonzero(iband == b)[0]
+        if idx.size:
+            bb[b], be[b] = idx[0], idx[-1]
+    return bb, be
+
+
 def reorder_single_band_sharded(ctx, pressure_hl, wn, dwn, od, threshold_optical_depth=0.5, group=None):
     """reorder_spectrum of ONE longwave band (the fsck structure) with the key sweep split by wavenumber range over the processes
     of `group`: every process runs K1 on its own whole-tile range of the resident spectrum, the keys and column
@@ -464,7 +529,7 @@ def _per_gas_tables(names, nband, by_task):
 def find_g_points(ctx, gases, band_bound1, band_bound2, heating_rate_tolerance, output_path=None, averaging_method="transmission",
                   flux_weight=0.02, min_pressure=0.0, tolerance_tolerance=0.02, max_iterations=60, iprofile=0, ssi=None,
                   max_no_rayleigh_wavenumber=10000.0, reference_albedo=0.15, cos_sza=0.5, sequential_bands=False,
-                  rank=None, world_size=None, group=None):
+                  rank=None, world_size=None, group=None, cloud=None):
     """The main loop of find_g_points.cpp:655-1660 over classic files (shortwave when `ssi[nwav]` is given: solar weights,
     reference albedo 0.15 below max_no_rayleigh_wavenumber (:469, :522, :757-761, :921-923), REFERENCE_COS_SZA = 0.5,
     per-gas min_scaling / max_scaling (:661-667)): per gas the merged background, the gas
@@ -480,8 +545,13 @@ def find_g_points(ctx, gases, band_bound1, band_bound2, heating_rate_tolerance, 
     exchanged while searching.  The per-band results (a few numbers per g point) are gathered on rank 0, which does what
     follows the gas loop in the reference (:1452-1660: overlap, merged map, file); ONE all-reduce combines the final cost
     (sum of the g points' errors) and the work counters.  Returns the result dict on rank 0, a summary elsewhere; both hold
-    `cost_sum` and `comp_cost_sum`, identical on every rank.  The g points do not depend on the number of processes."""
+    `cost_sum` and `comp_cost_sum`, identical on every rank.  The g points do not depend on the number of processes.
+
+    cloud: None, or (shortwave only) dict(name, reordering_input, max_reflectance_range=0.26): the cloud pseudo-gas of :543-652,
+    partitioned by rank 0 after the gases' searches and the first constituent of the overlap (:1448-1451)."""
     import torch
+    if cloud is not None and ssi is None:
+        raise EcckdError(PARAMETER_ERROR, "Don't yet know how to sort cloud properties in the longwave")
     dev = ctx.device
     nband = len(band_bound1)
     ngas = len(gases)
@@ -555,6 +625,11 @@ def find_g_points(ctx, gases, band_bound1, band_bound2, heating_rate_tolerance, 
         gp = api.gas_g_point(ctx, torch.as_tensor(order["rank"], device=dev), out["rank1"], out["rank2"])
         out["g_point"] = gp.cpu().numpy()
         gas_gp.append(gp)
+    if cloud is not None:
+        out, gp = cloud_g_points(ctx, cloud, ssi, nwav=len(wn), nband=nband)
+        out["g_point"] = gp.cpu().numpy()
+        per_gas.insert(0, out)
+        gas_gp.insert(0, gp)
     ng, band_number, g_min, g_max = api.overlap_g_points([g["n_g_points"] for g in per_gas],
                                                          [np.asarray(g["sorting_variable"]) for g in per_gas])
     g_point, n_unassigned = api.merge_g_points(ctx, gas_gp, g_min, g_max)

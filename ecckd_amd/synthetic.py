@@ -205,6 +205,22 @@ def solar_spectral_irradiance(wavenumber, d_wavenumber, tsi=1361.0, t_sun=5777.0
     return b * (tsi / b.sum())
 
 
+def mie_table(seed, nknot=400, nsize=4, lo=200.0, hi=52000.0):
+    """A smooth seeded stand-in for a Mie droplet scattering table (the variables reorder_cloud_spectrum reads): wavenumber[nknot]
+    ascending on a log grid, single_scattering_albedo and asymmetry_factor [nsize][nknot] as FLOAT values (as stored)."""
+    rng = np.random.default_rng(seed)
+    wn = np.geomspace(lo, hi, nknot)
+    x = np.log(wn / lo) / np.log(hi / lo)
+    ssa = np.empty((nsize, nknot))
+    g = np.empty((nsize, nknot))
+    for k in range(nsize):
+        ph = rng.uniform(0, 2 * np.pi, 3)
+        absorb = 10.0 ** (-6.0 + 5.0 * (1 - x) ** 2 + 0.8 * np.sin(9 * x + ph[0]) + 0.4 * np.sin(23 * x + ph[1]) + 0.3 * k)
+        ssa[k] = 1.0 - np.minimum(absorb, 0.5)
+        g[k] = 0.75 + 0.08 * x + 0.05 * np.sin(7 * x + ph[2])
+    return wn, ssa.astype(np.float32).astype(np.float64), g.astype(np.float32).astype(np.float64)
+
+
 # reference test/config.h:141-150 band definitions (cm-1) used by the parity cases
 LW_NARROW_BANDS = (
     np.array([0, 350, 500, 630, 700, 820, 980, 1080, 1180, 1390, 1480, 1800, 2080], dtype=np.float64),

@@ -768,6 +768,34 @@ int ecckd_merge_g_points_dev(ecckd_ctx* ctx, size_t nwav, int ngas,
                              const int* h_g_min, const int* h_g_max, int32_t* d_g_point,
                              int64_t* h_n_unassigned);
 
+/* ---- the cloud pseudo-gas (shortwave) ------------------------------------------
+ * ecckd_cloud_sorting_variable_dev replaces reorder_cloud_spectrum.cpp:111-123: the absorptance
+ * of an optically thick cloud, 1-(1-a)/(1+a) with a = sqrt((1-ssa_de)/(1-ssa_de*asymmetry_de)),
+ * ssa_de = ssa*(1-g*g)/(1-ssa*g*g) and asymmetry_de = 1/(1+g) as the reference writes it, on the
+ * Mie grid h_cloud_wavenumber[nknot] (strictly ascending, else ECCKD_PARAMETER_ERROR) from one
+ * size bin h_ssa[nknot], h_asymmetry[nknot]; then adept::interp onto d_wavenumber[nwav] (linear,
+ * extrapolated linearly outside the knots) -> d_sorting_variable[nwav].  Every operation is
+ * rounded on its own: the keys equal a plain double-precision restatement bit for bit.  The
+ * per-band stable sort of :150-188 is ecckd_stable_argsort_bands_dev.
+ * ecckd_cloud_partition_dev replaces find_g_points.cpp:586-636 (the equal-solar-energy branch):
+ * per band [h_band_begin[b], h_band_end[b]] (ascending, non-empty), ng_b = int((max-min of
+ * the sorting variable)/max_reflectance_range) + 1 g points, each the rank range over which the
+ * running sum of d_ssi in rank order (d_rank from the ordering file) lies in [jg*d, (jg+1)*d),
+ * d = band irradiance*(1+1e-8)/ng_b.  Outputs h_n_g_points[nband], *h_ng and per g point (up to
+ * capacity) h_band_number, h_rank1, h_rank2, h_error (max - min of the sorting variable) and
+ * h_median (-2 + its unweighted mean).  The running sum is a blocked fp64 scan (fixed order, no
+ * atomics), so a point can change g point only where the sum is within rounding of a boundary.
+ * ECCKD_PARAMETER_ERROR for ssi < 0 anywhere or a rank outside its band; ECCKD_PROCESSING_ERROR
+ * for a g point that holds no wavenumber (the reference takes minval of an empty set there). */
+int ecckd_cloud_sorting_variable_dev(ecckd_ctx* ctx, int nknot, const double* h_cloud_wavenumber,
+                                     const double* h_ssa, const double* h_asymmetry, size_t nwav,
+                                     const double* d_wavenumber, double* d_sorting_variable);
+int ecckd_cloud_partition_dev(ecckd_ctx* ctx, size_t nwav, const double* d_ssi, const int32_t* d_rank,
+                              const double* d_sorting_variable, int nband, const int64_t* h_band_begin,
+                              const int64_t* h_band_end, double max_reflectance_range, int capacity,
+                              int* h_n_g_points, int* h_ng, int* h_band_number, int64_t* h_rank1,
+                              int64_t* h_rank2, double* h_error, double* h_median);
+
 #ifdef __cplusplus
 }
 #endif
