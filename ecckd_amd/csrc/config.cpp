@@ -444,9 +444,9 @@ int ecckd_cfg_from_args(int argc, const char* const* argv, ecckd_cfg** out) {
     if (rc != ECCKD_OK) { delete c; return ECCKD_CANNOT_OPEN_MANDATORY_FILE; }
     c->file_name = argv[ifile];
     if (c->have_section) {
-      const int rc2 = ecckd::fail(ECCKD_CANNOT_OPEN_MANDATORY_FILE, "Section \"%s\" unterminated by \\end", c->section.c_str());
+      const int code = ecckd::fail(ECCKD_CANNOT_OPEN_MANDATORY_FILE, "Section \"%s\" unterminated by \\end", c->section.c_str());
       delete c;
-      return rc2;
+      return code;
     }
   }
   c->register_args(argc, argv);

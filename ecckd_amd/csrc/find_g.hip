@@ -2017,12 +2017,11 @@ int gas_ensure_work(ecckd_gas* g, size_t dev_bytes, size_t pinned_bytes) {
   if (dev_bytes > g->work_bytes) {
     if (g->work) {
       ECCKD_HIP_CHECK(hipStreamSynchronize(g->eval_stream()));
-      ecckd::dev_release(g->ctx, g->work);
-      g->work = nullptr;
+      g->give_back(g->work);
       g->work_bytes = 0;
     }
     size_t want = ecckd_align_up(dev_bytes * 2, 1 << 20);
-    ECCKD_HIP_CHECK(ecckd::dev_malloc(g->ctx, &g->work, want));
+    ECCKD_HIP_CHECK(g->alloc(&g->work, want));
     g->work_bytes = want;
   }
   // the pinned staging area belongs to the context (one caller per context at a time) or to the lane the gas was lent
@@ -2042,29 +2041,276 @@ void gas_free(ecckd_gas* g) {
   if (!g) return;
   ecckd_ctx* ctx = g->ctx;
   if (ctx) (void)hipStreamSynchronize(ctx->stream);
-  auto fr = [ctx](void* p) { if (p) ecckd::dev_release(ctx, p); };
-  if (g->owns_planck) fr(g->planck_hl);
-  fr(g->ssi); fr(g->tf); fr(g->tg); fr(g->hr_low); fr(g->hr_high); fr(g->fx);
-  fr(g->bg_od); fr(g->bg_pair); fr(g->w1); fr(g->w2); fr(g->cnt); fr(g->hr); fr(g->fds); fr(g->fut);
-  fr(g->wn_sorted); fr(g->dwn_sorted); fr(g->ireorder); fr((void*)g->rows); fr(g->tile_sums); fr(g->super_sums);
-  fr(g->lev); fr(g->work);
+  for (void* b : g->blocks) ecckd::dev_release(ctx, b);
   delete g;
 }
+
+// A gas under construction: whatever leaves the constructor early (ECCKD_HIP_CHECK, ECCKD_REQUIRE) frees it on the way out.
+struct GasDeleter { void operator()(ecckd_gas* g) const { gas_free(g); } };
+typedef std::unique_ptr<ecckd_gas, GasDeleter> GasPtr;
 
 // The DOUBLE rows of the background optical depths.  A longwave gas whose background is FLOAT holds the FLOAT pairs only
 // (ecckd_gas_create_lw); the rows are made from them when something asks: ecckd_gas_view, the run-time-nlay sweep.
 static int gas_bg_rows(ecckd_gas* g) {
   if (g->bg_od || !g->bg_pair) return ECCKD_OK;
   ecckd_ctx* ctx = g->ctx;
-  const hipError_t e = ecckd::dev_malloc(ctx, (void**)&g->bg_od, (size_t)g->nlay * g->n * sizeof(double));
-  if (e != hipSuccess) return ecckd::fail(e == hipErrorOutOfMemory ? ECCKD_OUT_OF_MEMORY : ECCKD_UNEXPECTED_EXCEPTION,
-                                          "background rows: %s", hipGetErrorString(e));
+  ECCKD_HIP_CHECK(g->alloc(&g->bg_od, (size_t)g->nlay * g->n * sizeof(double)));
   hipLaunchKernelGGL(k_unpack_bg32, dim3((unsigned)((g->n + 255) / 256)), dim3(256), 0, ctx->stream, g->nlay / 2, g->n,
                      (const float_x2_store*)g->bg_pair, g->bg_od);
   ECCKD_HIP_CHECK(hipGetLastError());
   ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return ECCKD_OK;
 }
+
+// ---------------------------------------------------------------------------
+// The steps of gas construction that the longwave and the shortwave gas share.
+
+// Temporaries of the column-staged preparation (54 layers of FLOAT optical depths).  Whatever is still held when the
+// constructor returns (error paths included) goes back to the context's cache once the stream has drained.
+struct Temps {
+  ecckd_ctx* ctx;
+  void *od_col = nullptr, *bg_col = nullptr;   // the columns of the target and the background, in rank order (scatter_columns)
+  void* wave_part = nullptr;                   // per-wave row sums left by K4, combined into the tile sums (gas_sum_rows)
+  void drop(void*& q) {                        // the caller has synchronised the stream
+    if (q) ecckd::dev_release(ctx, q);
+    q = nullptr;
+  }
+  void drop_all() { drop(od_col); drop(bg_col); drop(wave_part); }
+  ~Temps() {
+    if (!od_col && !bg_col && !wave_part) return;
+    (void)hipStreamSynchronize(ctx->stream);
+    drop_all();
+  }
+};
+
+// `who`: the entry point's name in front of every message.  arrays: none of the entry point's mandatory arrays is NULL.
+// h_temperature_hl: NULL in the shortwave.
+static int gas_check_args(const char* who, ecckd_ctx* ctx, ecckd_gas** out, int nlay, size_t nwav, bool arrays, int od_type,
+                          bool has_bg, int bg_type, size_t src_stride, int averaging_method, int last_method,
+                          const double* h_pressure_hl, const double* h_temperature_hl) {
+  ECCKD_REQUIRE(ctx && out, "%s: NULL ctx/out", who);
+  *out = nullptr;
+  ECCKD_REQUIRE(nlay > 0 && nwav > 0, "%s: empty problem (nlay=%d, nwav=%zu)", who, nlay, nwav);
+  ECCKD_REQUIRE(nwav < (size_t)0x7fffffff, "%s: nwav exceeds int32 rank range", who);
+  ECCKD_REQUIRE(arrays, "%s: NULL array argument", who);
+  ECCKD_REQUIRE(od_type == ECCKD_F32 || od_type == ECCKD_F64, "%s: od_type must be 4 or 8", who);
+  ECCKD_REQUIRE(!has_bg || bg_type == ECCKD_F32 || bg_type == ECCKD_F64, "%s: bg_type must be 4 or 8", who);
+  ECCKD_REQUIRE(src_stride >= nwav, "%s: src_stride < nwav", who);
+  // find_g_points.cpp:1146-1149: unknown averaging method is a PARAMETER_ERROR
+  ECCKD_REQUIRE(averaging_method >= ECCKD_AVG_LINEAR && averaging_method <= last_method,
+                "Averaging method %d not understood", averaging_method);
+  for (int i = 0; i <= nlay; ++i)
+    ECCKD_REQUIRE(h_pressure_hl[i] > 0.0 && (!h_temperature_hl || h_temperature_hl[i] > 0.0) &&
+                      (i == 0 || h_pressure_hl[i] > h_pressure_hl[i - 1]),
+                  "%s: pressure_hl must be positive and increasing%s", who, h_temperature_hl ? ", temperature_hl positive" : "");
+  return ECCKD_OK;
+}
+
+static GasPtr gas_new(ecckd_ctx* ctx, int do_sw, int averaging_method, int nlay, size_t nwav, double flux_weight,
+                      const double* h_pressure_hl) {
+  GasPtr g(new ecckd_gas());
+  g->ctx = ctx;
+  g->do_sw = do_sw;
+  g->method = averaging_method;
+  g->nlay = nlay;
+  g->n = nwav;
+  g->flux_weight = flux_weight;
+  g->h_pressure_hl.assign(h_pressure_hl, h_pressure_hl + nlay + 1);
+  return g;
+}
+
+// Per-level constants on the device, g->lev: hk[nhl] (longwave: h/k over the temperature; shortwave: unused) | conv[nlay] |
+// layer_weight[nlay] | two int flags, zero.  Returns once they are there.
+static int gas_layer_constants(ecckd_gas* g, const double* h_temperature_hl, double min_pressure) {
+  const int nlay = g->nlay;
+  const size_t nhl = nlay + 1;
+  const std::vector<double>& p = g->h_pressure_hl;
+  std::vector<double> lev(nhl + 2 * nlay + 1, 0.0);
+  const double hk = 6.62606896e-34 / 1.3806504e-23;
+  if (h_temperature_hl)
+    for (size_t i = 0; i < nhl; ++i) lev[i] = hk / h_temperature_hl[i];
+  g->h_layer_weight.resize(nlay);
+  // find_g_points.cpp:1093-1099
+  double s = 0.0;
+  for (int l = 0; l < nlay; ++l) {
+    lev[nhl + l] = -(ECCKD_ACCEL_GRAVITY / ECCKD_SPECIFIC_HEAT_AIR) / (p[l + 1] - p[l]);
+    double lw = std::sqrt(p[l + 1]) - std::sqrt(p[l]);
+    double pfl = 0.5 * (p[l + 1] + p[l]);
+    if (pfl < min_pressure) lw = 0.0;
+    g->h_layer_weight[l] = lw;
+  }
+  for (int l = 0; l < nlay; ++l) s += g->h_layer_weight[l];
+  for (int l = 0; l < nlay; ++l) {
+    g->h_layer_weight[l] /= s;
+    lev[nhl + nlay + l] = g->h_layer_weight[l];
+  }
+  ECCKD_HIP_CHECK(g->alloc(&g->lev, lev.size() * sizeof(double)));
+  ECCKD_HIP_CHECK(hipMemcpyAsync(g->lev, lev.data(), lev.size() * sizeof(double), hipMemcpyHostToDevice, g->ctx->stream));
+  ECCKD_HIP_CHECK(hipStreamSynchronize(g->ctx->stream));
+  return ECCKD_OK;
+}
+
+// d_ireorder = the inverse of d_rank, which must be a permutation: every slot of ireorder written exactly once.  Checked on
+// the device BEFORE anything dereferences ireorder.  d_flag: an int on the device that the stream has zeroed.
+static int invert_rank(ecckd_ctx* ctx, const char* who, size_t nwav, const int32_t* d_rank, int32_t* d_ireorder, int* d_flag) {
+  const unsigned eblocks = (unsigned)((nwav + 255) / 256);
+  ECCKD_HIP_CHECK(hipMemsetAsync(d_ireorder, 0xFF, nwav * sizeof(int32_t), ctx->stream));
+  hipLaunchKernelGGL(k_invert_rank, dim3(eblocks), dim3(256), 0, ctx->stream, nwav, d_rank, d_ireorder, d_flag);
+  hipLaunchKernelGGL(k_check_perm, dim3(eblocks), dim3(256), 0, ctx->stream, nwav, d_ireorder, d_flag);
+  int flag = 0;
+  ECCKD_HIP_CHECK(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  ECCKD_REQUIRE(flag == 0, "%s: rank is not a permutation of 0..nwav-1", who);
+  return ECCKD_OK;
+}
+
+// The 54-layer columns of the FLOAT target spectrum and of the background (if any) scattered into rank order, in PARTS runs
+// of 54 / PARTS layers, [PARTS][ncol][54 / PARTS] with ncol = nwav rounded up to 64: K4 stages them through LDS.
+template <int PARTS>
+static int scatter_columns(Temps& temps, size_t nwav, size_t src_stride, const int32_t* d_rank, const void* d_od,
+                           const void* d_bg_od, bool bg32) {
+  ecckd_ctx* ctx = temps.ctx;
+  const unsigned tblocks = (unsigned)((nwav + 63) / 64);
+  const size_t ncol = (size_t)tblocks * 64;
+  ECCKD_HIP_CHECK(ecckd::dev_malloc(ctx, &temps.od_col, ncol * 54 * sizeof(float)));
+  if (d_bg_od) ECCKD_HIP_CHECK(ecckd::dev_malloc(ctx, &temps.bg_col, ncol * 54 * (bg32 ? sizeof(float) : sizeof(double))));
+  hipLaunchKernelGGL((k_scatter_column_halves<54, float, PARTS>), dim3(tblocks), dim3(256), 0, ctx->stream, nwav, ncol, src_stride,
+                     d_rank, (const float*)d_od, (float*)temps.od_col);
+  if (d_bg_od && bg32)
+    hipLaunchKernelGGL((k_scatter_column_halves<54, float, PARTS>), dim3(tblocks), dim3(256), 0, ctx->stream, nwav, ncol, src_stride,
+                       d_rank, (const float*)d_bg_od, (float*)temps.bg_col);
+  else if (d_bg_od)
+    hipLaunchKernelGGL((k_scatter_column_halves<54, double, PARTS>), dim3(tblocks), dim3(256), 0, ctx->stream, nwav, ncol, src_stride,
+                       d_rank, (const double*)d_bg_od, (double*)temps.bg_col);
+  return ECCKD_OK;
+}
+
+// Which summable rows a gas has, in the order of RowMap's members.
+static RowMap make_row_map(int nlay, bool is_log, bool is_tt) {
+  RowMap R;
+  int next = 0;
+  R.A = next; next += nlay;
+  R.B = next; next += nlay;
+  if (is_log) { R.N = next; next += nlay; }
+  R.H = next; next += nlay;
+  R.FDS = next++;
+  R.FUT = next++;
+  if (is_tt) {
+    R.TF = next; next += nlay;
+    R.TG = next; next += nlay;
+    R.HL = next; next += nlay;
+    R.HH = next; next += nlay;
+    R.FDSL = next++; R.FUTL = next++; R.FDSH = next++; R.FUTH = next++;
+  }
+  R.total = next;
+  return R;
+}
+
+// The rows of g->rm -> device table -> tile sums -> super sums.  denom + l * denom_stride: the denominator of the fit of
+// layer l where the method is not the logarithmic one.  The tile sums come from the per-wave sums that the column-staged
+// preparation left in temps.wave_part, if any.  sync: wait for the tile sums and give every temporary back.
+static int gas_sum_rows(ecckd_gas* g, const double* denom, size_t denom_stride, Temps& temps, bool sync) {
+  ecckd_ctx* ctx = g->ctx;
+  const RowMap& R = g->rm;
+  const size_t nwav = g->n;
+  std::vector<const double*> rows(g->nrows);
+  for (int l = 0; l < g->nlay; ++l) {
+    rows[R.A + l] = g->w1 + (size_t)l * nwav;
+    rows[R.B + l] = R.N >= 0 ? g->w2 + (size_t)l * nwav : denom + (size_t)l * denom_stride;
+    if (R.N >= 0) rows[R.N + l] = g->cnt + (size_t)l * nwav;
+    rows[R.H + l] = g->hr + (size_t)l * nwav;
+    if (R.TF >= 0) {
+      rows[R.TF + l] = g->tf + (size_t)l * nwav;
+      rows[R.TG + l] = g->tg + (size_t)l * nwav;
+      rows[R.HL + l] = g->hr_low + (size_t)l * nwav;
+      rows[R.HH + l] = g->hr_high + (size_t)l * nwav;
+    }
+  }
+  rows[R.FDS] = g->fds;
+  rows[R.FUT] = g->fut;
+  if (R.TF >= 0) {
+    rows[R.FDSL] = g->fx;
+    rows[R.FUTL] = g->fx + nwav;
+    rows[R.FDSH] = g->fx + 2 * nwav;
+    rows[R.FUTH] = g->fx + 3 * nwav;
+  }
+  ECCKD_HIP_CHECK(g->alloc(&g->rows, rows.size() * sizeof(double*)));
+  ECCKD_HIP_CHECK(hipMemcpyAsync((void*)g->rows, rows.data(), rows.size() * sizeof(double*), hipMemcpyHostToDevice, ctx->stream));
+  ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  g->ntiles = (nwav + TILE - 1) / TILE;
+  ECCKD_HIP_CHECK(g->alloc(&g->tile_sums, (size_t)g->nrows * g->ntiles * sizeof(double)));
+  if (temps.wave_part) {
+    static_assert(TILE == 256, "a tile is four 64-point groups");
+    hipLaunchKernelGGL(k_combine_wave_sums, dim3((unsigned)((g->ntiles + 255) / 256), (unsigned)g->nrows), dim3(256), 0, ctx->stream,
+                       g->nrows, (nwav + 63) / 64, g->ntiles, (const double*)temps.wave_part, g->tile_sums);
+  } else {
+    hipLaunchKernelGGL(k_tile_sums, dim3((unsigned)g->ntiles), dim3(TILE), 0, ctx->stream, g->nrows, nwav, g->ntiles,
+                       (const double* const*)g->rows, g->tile_sums);
+  }
+  ECCKD_HIP_CHECK(hipGetLastError());
+  if (sync) {
+    ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    temps.drop_all();
+  }
+  g->nsuper = (g->ntiles + SUPER - 1) / SUPER;
+  ECCKD_HIP_CHECK(g->alloc(&g->super_sums, (size_t)g->nrows * g->nsuper * sizeof(double)));
+  hipLaunchKernelGGL(k_super_sums, dim3((unsigned)g->nsuper, (unsigned)g->nrows), dim3(256), 0, ctx->stream, g->ntiles, g->nsuper,
+                     (const double*)g->tile_sums, g->super_sums);
+  ECCKD_HIP_CHECK(hipGetLastError());
+  return ECCKD_OK;
+}
+
+// ---------------------------------------------------------------------------
+// What the entry points that take interval bounds share.
+
+// The interval [b1, b2] (fractions) of the band of npoints points that starts at sorted index ibegin: index mapping and
+// error paths of CkdEquipartition::calc_error (find_g_points.cpp:282-320).  The chunking is the sweep's to fill in.
+static int make_interval(const ecckd_gas* g, size_t ibegin, size_t npoints, double b1, double b2, double albedo, Interval& iv) {
+  ECCKD_REQUIRE(npoints > 0 && ibegin + npoints <= g->n,
+                "ecckd_calc_error_batch: band [%zu,%zu) outside the spectrum (%zu points)", ibegin, ibegin + npoints, g->n);
+  long long i1 = (long long)std::ceil(b1 * (double)(npoints - 1));
+  long long i2 = (long long)std::floor(b2 * (double)(npoints - 1));
+  if (i1 < 0 || i2 >= (long long)npoints || !(b1 == b1) || !(b2 == b2))
+    return ecckd::fail(ECCKD_PROCESSING_ERROR,
+                       "requested bounds %.17g-%.17g corresponding to indices %lld-%lld outside valid range 0-%zu",
+                       b1, b2, i1, i2, npoints - 1);
+  if (b2 < b1) return ecckd::fail(ECCKD_PROCESSING_ERROR, "requested bounds out of order: %.17g-%.17g", b1, b2);
+  if (i2 + 1 < i1) return ecckd::fail(ECCKD_PROCESSING_ERROR, "requested indices out of order: %lld-%lld", i1, i2);
+  if (i2 < i1) i2 = i1;
+  iv.i1 = (long long)ibegin + i1;
+  iv.i2 = (long long)ibegin + i2;
+  iv.chunk0 = 0;
+  iv.chunk_pts = 0;
+  iv.npoints = (long long)npoints;
+  iv.albedo = albedo;
+  return ECCKD_OK;
+}
+
+// what an interval's error depends on (gas.hpp); the longwave knows no albedo
+static IntervalKey interval_key(const ecckd_gas* g, const Interval& iv) {
+  IntervalKey key;
+  key.i1 = iv.i1;
+  key.i2 = iv.i2;
+  key.albedo_bits = 0;
+  if (g->do_sw) std::memcpy(&key.albedo_bits, &iv.albedo, sizeof(double));
+  return key;
+}
+
+// The device work buffer of a batch of n intervals: intervals | sums[n][nrows] | od_fit[2][n][nlay] |
+// partial[2][nchunks][2 nhl] (x2: both fits of the dual shortwave sweep).  The pinned buffer starts with the intervals too.
+struct WorkLayout {
+  size_t iv_bytes, sums_bytes, fit_bytes, part_bytes;
+  WorkLayout(int n, int nrows, int nlay, long long nchunks)
+      : iv_bytes(ecckd_align_up((size_t)n * sizeof(Interval), 256)),
+        sums_bytes(ecckd_align_up((size_t)n * nrows * sizeof(double), 256)),
+        fit_bytes(ecckd_align_up((size_t)2 * n * nlay * sizeof(double), 256)),
+        part_bytes(ecckd_align_up((size_t)2 * nchunks * 2 * (nlay + 1) * sizeof(double), 256)) {}
+  size_t dev_bytes() const { return iv_bytes + sums_bytes + fit_bytes + part_bytes; }
+  Interval* iv(void* work) const { return (Interval*)work; }
+  double* sums(void* work) const { return (double*)((char*)work + iv_bytes); }
+  double* fit(void* work) const { return (double*)((char*)work + iv_bytes + sums_bytes); }
+  double* part(void* work) const { return (double*)((char*)work + iv_bytes + sums_bytes + fit_bytes); }
+};
 
 }  // namespace
 
@@ -2076,126 +2322,56 @@ int ecckd_gas_create_lw(ecckd_ctx* ctx, int nlay, size_t nwav, const double* h_p
                         int bg_type, const void* d_od, int od_type, size_t src_stride,
                         int averaging_method, double flux_weight, double min_pressure,
                         const double* d_planck_hl_reuse, ecckd_gas** out) {
-  ECCKD_REQUIRE(ctx && out, "ecckd_gas_create_lw: NULL ctx/out");
-  *out = nullptr;
-  ECCKD_REQUIRE(nlay > 0 && nwav > 0, "ecckd_gas_create_lw: empty problem (nlay=%d, nwav=%zu)", nlay, nwav);
-  ECCKD_REQUIRE(nwav < (size_t)0x7fffffff, "ecckd_gas_create_lw: nwav exceeds int32 rank range");
-  ECCKD_REQUIRE(h_pressure_hl && h_temperature_hl && d_wavenumber && d_d_wavenumber && d_rank && d_od,
-                "ecckd_gas_create_lw: NULL array argument");
-  ECCKD_REQUIRE(od_type == ECCKD_F32 || od_type == ECCKD_F64, "ecckd_gas_create_lw: od_type must be 4 or 8");
-  ECCKD_REQUIRE(!d_bg_od || bg_type == ECCKD_F32 || bg_type == ECCKD_F64, "ecckd_gas_create_lw: bg_type must be 4 or 8");
-  ECCKD_REQUIRE(src_stride >= nwav, "ecckd_gas_create_lw: src_stride < nwav");
-  // find_g_points.cpp:1146-1149: unknown averaging method is a PARAMETER_ERROR;
-  // total-transmission is shortwave-only (fit_optical_depth_lw has no such branch, :101-104)
-  ECCKD_REQUIRE(averaging_method >= ECCKD_AVG_LINEAR && averaging_method <= ECCKD_AVG_LOGARITHMIC,
-                "Averaging method %d not understood", averaging_method);
-  for (int i = 0; i <= nlay; ++i)
-    ECCKD_REQUIRE(h_pressure_hl[i] > 0.0 && h_temperature_hl[i] > 0.0 && (i == 0 || h_pressure_hl[i] > h_pressure_hl[i - 1]),
-                  "ecckd_gas_create_lw: pressure_hl must be positive and increasing, temperature_hl positive");
+  static const char who[] = "ecckd_gas_create_lw";
+  // total-transmission is shortwave-only (fit_optical_depth_lw has no such branch, find_g_points.cpp:101-104)
+  ECCKD_CHECK(gas_check_args(who, ctx, out, nlay, nwav,
+                             h_pressure_hl && h_temperature_hl && d_wavenumber && d_d_wavenumber && d_rank && d_od, od_type,
+                             d_bg_od != nullptr, bg_type, src_stride, averaging_method, ECCKD_AVG_LOGARITHMIC, h_pressure_hl,
+                             h_temperature_hl));
   ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
   if ((size_t)nlay * 64 * sizeof(double) > 160 * 1024)
     return ecckd::fail(ECCKD_PARAMETER_ERROR, "ecckd_gas_create_lw: nlay = %d exceeds the supported maximum (320)", nlay);
 
-  ecckd_gas* g = new ecckd_gas();
-  g->ctx = ctx;
-  g->do_sw = 0;
-  g->method = averaging_method;
-  g->nlay = nlay;
-  g->n = nwav;
-  g->flux_weight = flux_weight;
-  g->h_pressure_hl.assign(h_pressure_hl, h_pressure_hl + nlay + 1);
+  GasPtr gas = gas_new(ctx, 0, averaging_method, nlay, nwav, flux_weight, h_pressure_hl);
+  ecckd_gas* const g = gas.get();
   const bool is_log = averaging_method == ECCKD_AVG_LOGARITHMIC;
   const size_t nhl = nlay + 1;
-  int rc = ECCKD_OK;
-#define GTRY(expr)                                                                       \
-  do {                                                                                   \
-    hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess) {                                                              \
-      rc = ecckd::fail(_e == hipErrorOutOfMemory ? ECCKD_OUT_OF_MEMORY : ECCKD_UNEXPECTED_EXCEPTION, \
-                       "%s failed: %s", #expr, hipGetErrorString(_e));                   \
-      gas_free(g);                                                                       \
-      return rc;                                                                         \
-    }                                                                                    \
-  } while (0)
   const size_t mat = (size_t)nlay * nwav * sizeof(double);
-  if (d_planck_hl_reuse) {
-    g->planck_hl = const_cast<double*>(d_planck_hl_reuse);
-    g->owns_planck = false;
-  } else {
-    GTRY(ecckd::dev_malloc(ctx, (void**)&g->planck_hl, nhl * nwav * sizeof(double)));
-  }
+  if (d_planck_hl_reuse) g->planck_hl = const_cast<double*>(d_planck_hl_reuse);   // not recorded: its owner frees it
+  else ECCKD_HIP_CHECK(g->alloc(&g->planck_hl, nhl * nwav * sizeof(double)));
   // The background rows.  FLOAT pairs for the sweep (k_rt_lw_bb_mirror<.., true>) whenever every value is a float: with a
   // FLOAT background (or none) on the 54-layer path K4 writes them itself INSTEAD of the DOUBLE rows (which are then made on
   // demand only, gas_bg_rows: 3.1 GB less to write and to hold per gas at 7.2e6 points); otherwise the DOUBLE rows are
   // written and k_pack_bg32 tries to pack them below.  ECCKD_BG64: DOUBLE rows only.
   const bool want_pairs = (nlay == 54 || nlay == 30) && std::getenv("ECCKD_BG64") == nullptr;
   const bool pairs_in_k4 = want_pairs && nlay == 54 && od_type == ECCKD_F32 && !is_log && (!d_bg_od || bg_type == ECCKD_F32);
-  if (want_pairs) GTRY(ecckd::dev_malloc(ctx, (void**)&g->bg_pair, (size_t)(nlay / 2) * nwav * 2 * sizeof(float)));
-  if (!pairs_in_k4) GTRY(ecckd::dev_malloc(ctx, (void**)&g->bg_od, mat));
-  GTRY(ecckd::dev_malloc(ctx, (void**)&g->w1, mat));
+  if (want_pairs) ECCKD_HIP_CHECK(g->alloc(&g->bg_pair, (size_t)(nlay / 2) * nwav * 2 * sizeof(float)));
+  if (!pairs_in_k4) ECCKD_HIP_CHECK(g->alloc(&g->bg_od, mat));
+  ECCKD_HIP_CHECK(g->alloc(&g->w1, mat));
   if (is_log) {
-    GTRY(ecckd::dev_malloc(ctx, (void**)&g->w2, mat));
-    GTRY(ecckd::dev_malloc(ctx, (void**)&g->cnt, mat));
+    ECCKD_HIP_CHECK(g->alloc(&g->w2, mat));
+    ECCKD_HIP_CHECK(g->alloc(&g->cnt, mat));
   }
-  GTRY(ecckd::dev_malloc(ctx, (void**)&g->hr, mat));
-  GTRY(ecckd::dev_malloc(ctx, (void**)&g->fds, nwav * sizeof(double)));
-  GTRY(ecckd::dev_malloc(ctx, (void**)&g->fut, nwav * sizeof(double)));
-  GTRY(ecckd::dev_malloc(ctx, (void**)&g->wn_sorted, nwav * sizeof(double)));
-  GTRY(ecckd::dev_malloc(ctx, (void**)&g->dwn_sorted, nwav * sizeof(double)));
-  GTRY(ecckd::dev_malloc(ctx, (void**)&g->ireorder, nwav * sizeof(int32_t)));
-
-  // per-level constants: hk[nhl] | conv[nlay] | layer_weight[nlay] | flag
-  std::vector<double> lev(nhl + 2 * nlay + 1, 0.0);
-  const double hk = 6.62606896e-34 / 1.3806504e-23;
-  for (size_t i = 0; i < nhl; ++i) lev[i] = hk / h_temperature_hl[i];
-  g->h_layer_weight.resize(nlay);
-  {
-    // find_g_points.cpp:1093-1099
-    double s = 0.0;
-    for (int l = 0; l < nlay; ++l) {
-      lev[nhl + l] = -(ECCKD_ACCEL_GRAVITY / ECCKD_SPECIFIC_HEAT_AIR) / (h_pressure_hl[l + 1] - h_pressure_hl[l]);
-      double lw = std::sqrt(h_pressure_hl[l + 1]) - std::sqrt(h_pressure_hl[l]);
-      double pfl = 0.5 * (h_pressure_hl[l + 1] + h_pressure_hl[l]);
-      if (pfl < min_pressure) lw = 0.0;
-      g->h_layer_weight[l] = lw;
-    }
-    for (int l = 0; l < nlay; ++l) s += g->h_layer_weight[l];
-    for (int l = 0; l < nlay; ++l) {
-      g->h_layer_weight[l] /= s;
-      lev[nhl + nlay + l] = g->h_layer_weight[l];
-    }
-  }
-  GTRY(ecckd::dev_malloc(ctx, (void**)&g->lev, lev.size() * sizeof(double)));
-  GTRY(hipMemcpyAsync(g->lev, lev.data(), lev.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  GTRY(hipStreamSynchronize(ctx->stream));
+  ECCKD_HIP_CHECK(g->alloc(&g->hr, mat));
+  ECCKD_HIP_CHECK(g->alloc(&g->fds, nwav * sizeof(double)));
+  ECCKD_HIP_CHECK(g->alloc(&g->fut, nwav * sizeof(double)));
+  ECCKD_HIP_CHECK(g->alloc(&g->wn_sorted, nwav * sizeof(double)));
+  ECCKD_HIP_CHECK(g->alloc(&g->dwn_sorted, nwav * sizeof(double)));
+  ECCKD_HIP_CHECK(g->alloc(&g->ireorder, nwav * sizeof(int32_t)));
+  ECCKD_CHECK(gas_layer_constants(g, h_temperature_hl, min_pressure));
+  const double* hkd = g->lev;
+  const double* convd = g->lev + nhl;
   int* d_flag = (int*)(g->lev + nhl + 2 * nlay);
-
-  const unsigned eblocks = (unsigned)((nwav + 255) / 256);
-  // rank must be a permutation: every slot of ireorder written exactly once.  Checked on the
-  // device BEFORE the gather kernel dereferences ireorder.
-  GTRY(hipMemsetAsync(g->ireorder, 0xFF, nwav * sizeof(int32_t), ctx->stream));
-  hipLaunchKernelGGL(k_invert_rank, dim3(eblocks), dim3(256), 0, ctx->stream, nwav, d_rank, g->ireorder, d_flag);
-  hipLaunchKernelGGL(k_check_perm, dim3(eblocks), dim3(256), 0, ctx->stream, nwav, g->ireorder, d_flag);
-  {
-    int flag0 = 0;
-    GTRY(hipMemcpyAsync(&flag0, d_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    GTRY(hipStreamSynchronize(ctx->stream));
-    if (flag0) {
-      gas_free(g);
-      return ecckd::fail(ECCKD_PARAMETER_ERROR, "ecckd_gas_create_lw: rank is not a permutation of 0..nwav-1");
-    }
-  }
+  ECCKD_CHECK(invert_rank(ctx, who, nwav, d_rank, g->ireorder, d_flag));
 
   int threads = PREP_THREADS;
   while ((size_t)nlay * threads * sizeof(double) > 160 * 1024 && threads > 64) threads /= 2;
   const size_t lds = (size_t)nlay * threads * sizeof(double);
   const unsigned pblocks = (unsigned)((nwav + threads - 1) / threads);
-  const double* hkd = g->lev;
-  const double* convd = g->lev + nhl;
 #define LAUNCH_PREP(BG, OD)                                                                                   \
   do {                                                                                                        \
-    GTRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gas_prep_lw<BG, OD>),                            \
-                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                        \
+    ECCKD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gas_prep_lw<BG, OD>),                 \
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));             \
     hipLaunchKernelGGL((k_gas_prep_lw<BG, OD>), dim3(pblocks), dim3(threads), lds, ctx->stream, nlay, nwav,   \
                        src_stride, averaging_method, g->ireorder, hkd, convd, d_wavenumber, d_d_wavenumber,   \
                        (const BG*)d_bg_od, (const OD*)d_od, d_planck_hl_reuse, g->wn_sorted, g->dwn_sorted,   \
@@ -2205,129 +2381,49 @@ int ecckd_gas_create_lw(ecckd_ctx* ctx, int nlay, size_t nwav, const double* h_p
   // fast path: 54 layers, FLOAT target spectrum (as stored in the CKDMIP files), FLOAT or DOUBLE (merged) background,
   // with or without the Planck matrix of an earlier gas, no log metric
   const bool fast = nlay == 54 && od_type == ECCKD_F32 && !is_log;
-  // temporaries of the fast path; whatever is still held when the function returns (error paths included) goes back to
-  // the context's cache once the stream has drained
-  struct Temps {
-    ecckd_ctx* ctx;
-    void* p[3] = {nullptr, nullptr, nullptr};
-    void drop(void*& q) {
-      for (void*& r : p)
-        if (r && r == q) { ecckd::dev_release(ctx, r); r = nullptr; }
-      q = nullptr;
-    }
-    ~Temps() {
-      bool any = false;
-      for (void* r : p) any = any || r;
-      if (!any) return;
-      (void)hipStreamSynchronize(ctx->stream);
-      for (void* r : p) if (r) ecckd::dev_release(ctx, r);
-    }
-  } temps{ctx};
-  void*& od_col_v = temps.p[0];
-  void*& bg_col = temps.p[1];
-  void*& wave_part_v = temps.p[2];   // per-wave row sums left by K4, combined into the tile sums below
-  size_t nw64 = 0;
+  Temps temps{ctx};
   if (fast) {
-    const size_t bg_elem = bg32 ? sizeof(float) : sizeof(double);
-    nw64 = (nwav + 63) / 64;
-    const size_t ncol = nw64 * 64;             // the columns in two runs of 27 layers, [2][ncol][27], staged through LDS by K4
-    GTRY(ecckd::dev_malloc(ctx, &od_col_v, ncol * 54 * sizeof(float)));
-    if (d_bg_od) GTRY(ecckd::dev_malloc(ctx, &bg_col, ncol * 54 * bg_elem));
-    float* od_col = (float*)od_col_v;
-    const unsigned tblocks = (unsigned)((nwav + 63) / 64);
-    hipLaunchKernelGGL((k_scatter_column_halves<54, float, 2>), dim3(tblocks), dim3(256), 0, ctx->stream, nwav, ncol, src_stride,
-                       d_rank, (const float*)d_od, od_col);
-    if (d_bg_od && bg32)
-      hipLaunchKernelGGL((k_scatter_column_halves<54, float, 2>), dim3(tblocks), dim3(256), 0, ctx->stream, nwav, ncol, src_stride,
-                         d_rank, (const float*)d_bg_od, (float*)bg_col);
-    else if (d_bg_od)
-      hipLaunchKernelGGL((k_scatter_column_halves<54, double, 2>), dim3(tblocks), dim3(256), 0, ctx->stream, nwav, ncol, src_stride,
-                         d_rank, (const double*)d_bg_od, (double*)bg_col);
+    // the columns in two runs of 27 layers
+    ECCKD_CHECK(scatter_columns<2>(temps, nwav, src_stride, d_rank, d_od, d_bg_od, bg32));
+    const size_t nw64 = (nwav + 63) / 64;
     const unsigned fblocks = (unsigned)((nwav + 127) / 128);
-    GTRY(ecckd::dev_malloc(ctx, &wave_part_v, (size_t)(3 * 54 + 2) * nw64 * sizeof(double)));
-    double* wave_part = (double*)wave_part_v;
+    ECCKD_HIP_CHECK(ecckd::dev_malloc(ctx, &temps.wave_part, (size_t)(3 * 54 + 2) * nw64 * sizeof(double)));
 #define LAUNCH_MIRROR(BG, REUSE)                                                                                              \
   hipLaunchKernelGGL((k_gas_prep_lw_mirror<54, BG, float, REUSE>), dim3(fblocks), dim3(PREP_THREADS), 0, ctx->stream, nwav,    \
-                     averaging_method, g->ireorder, hkd, convd, d_wavenumber, d_d_wavenumber, (const BG*)bg_col,               \
-                     (const float*)od_col, d_planck_hl_reuse, g->wn_sorted, g->dwn_sorted, g->planck_hl, g->bg_od, g->w1,      \
-                     g->hr, g->fds, g->fut, wave_part, nw64, pairs_in_k4 ? (float_x2_store*)g->bg_pair : nullptr)
+                     averaging_method, g->ireorder, hkd, convd, d_wavenumber, d_d_wavenumber, (const BG*)temps.bg_col,         \
+                     (const float*)temps.od_col, d_planck_hl_reuse, g->wn_sorted, g->dwn_sorted, g->planck_hl, g->bg_od,       \
+                     g->w1, g->hr, g->fds, g->fut, (double*)temps.wave_part, nw64,                                             \
+                     pairs_in_k4 ? (float_x2_store*)g->bg_pair : nullptr)
     if (bg32 || !d_bg_od) { if (d_planck_hl_reuse) LAUNCH_MIRROR(float, true); else LAUNCH_MIRROR(float, false); }
     else { if (d_planck_hl_reuse) LAUNCH_MIRROR(double, true); else LAUNCH_MIRROR(double, false); }
 #undef LAUNCH_MIRROR
-    GTRY(hipGetLastError());
-    GTRY(hipStreamSynchronize(ctx->stream));
-    temps.drop(od_col_v);
-    temps.drop(bg_col);
+    ECCKD_HIP_CHECK(hipGetLastError());
+    ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    temps.drop(temps.od_col);
+    temps.drop(temps.bg_col);
   } else if (bg32 && od_type == ECCKD_F32) LAUNCH_PREP(float, float);
   else if (bg32) LAUNCH_PREP(float, double);
   else if (od_type == ECCKD_F32) LAUNCH_PREP(double, float);
   else LAUNCH_PREP(double, double);
 #undef LAUNCH_PREP
-  GTRY(hipGetLastError());
+  ECCKD_HIP_CHECK(hipGetLastError());
 
-  // row table + tile sums
-  RowMap R;
-  R.A = 0;
-  R.B = nlay;
-  if (is_log) R.N = 2 * nlay;
-  R.H = (is_log ? 3 : 2) * nlay;
-  R.FDS = R.H + nlay;
-  R.FUT = R.FDS + 1;
-  R.total = R.FUT + 1;
-  g->rm = R;
-  g->nrows = R.total;
-  std::vector<const double*> rows(g->nrows);
-  for (int l = 0; l < nlay; ++l) {
-    rows[R.A + l] = g->w1 + (size_t)l * nwav;
-    // denominator of the fit: planck_hl(l+1) (find_g_points.cpp:62), or for the
-    // logarithmic method planck_hl(l) masked by metric > 0 (:87)
-    rows[R.B + l] = is_log ? g->w2 + (size_t)l * nwav : g->planck_hl + (size_t)(l + 1) * nwav;
-    if (is_log) rows[R.N + l] = g->cnt + (size_t)l * nwav;
-    rows[R.H + l] = g->hr + (size_t)l * nwav;
-  }
-  rows[R.FDS] = g->fds;
-  rows[R.FUT] = g->fut;
-  GTRY(ecckd::dev_malloc(ctx, (void**)&g->rows, rows.size() * sizeof(double*)));
-  GTRY(hipMemcpyAsync((void*)g->rows, rows.data(), rows.size() * sizeof(double*), hipMemcpyHostToDevice, ctx->stream));
-  GTRY(hipStreamSynchronize(ctx->stream));
-  g->ntiles = (nwav + TILE - 1) / TILE;
-  GTRY(ecckd::dev_malloc(ctx, (void**)&g->tile_sums, (size_t)g->nrows * g->ntiles * sizeof(double)));
-  if (wave_part_v) {
-    static_assert(TILE == 256, "a tile is four 64-point groups");
-    hipLaunchKernelGGL(k_combine_wave_sums, dim3((unsigned)((g->ntiles + 255) / 256), (unsigned)g->nrows), dim3(256), 0, ctx->stream,
-                       g->nrows, nw64, g->ntiles, (const double*)wave_part_v, g->tile_sums);
-    GTRY(hipGetLastError());
-    GTRY(hipStreamSynchronize(ctx->stream));
-    temps.drop(wave_part_v);
-  } else {
-    hipLaunchKernelGGL(k_tile_sums, dim3((unsigned)g->ntiles), dim3(TILE), 0, ctx->stream, g->nrows, nwav, g->ntiles,
-                       (const double* const*)g->rows, g->tile_sums);
-  }
-  GTRY(hipGetLastError());
-  g->nsuper = (g->ntiles + SUPER - 1) / SUPER;
-  GTRY(ecckd::dev_malloc(ctx, (void**)&g->super_sums, (size_t)g->nrows * g->nsuper * sizeof(double)));
-  hipLaunchKernelGGL(k_super_sums, dim3((unsigned)g->nsuper, (unsigned)g->nrows), dim3(256), 0, ctx->stream, g->ntiles, g->nsuper,
-                     (const double*)g->tile_sums, g->super_sums);
-  GTRY(hipGetLastError());
+  g->rm = make_row_map(nlay, is_log, false);
+  g->nrows = g->rm.total;
+  // denominator of the fit: planck_hl(l+1) (find_g_points.cpp:62), or for the logarithmic method planck_hl(l) masked by
+  // metric > 0 (:87), which K4 has left in w2.  The per-wave sums go back as soon as they are combined.
+  ECCKD_CHECK(gas_sum_rows(g, g->planck_hl + nwav, nwav, temps, temps.wave_part != nullptr));
   // FLOAT pairs from the DOUBLE rows where K4 has not written them itself: kept if every value is a float
   if (want_pairs && !pairs_in_k4) {
-    hipLaunchKernelGGL(k_pack_bg32, dim3(eblocks), dim3(256), 0, ctx->stream, nlay / 2, nwav, (const double*)g->bg_od,
-                       (float_x2_store*)g->bg_pair, d_flag + 1);
-    GTRY(hipGetLastError());
+    hipLaunchKernelGGL(k_pack_bg32, dim3((unsigned)((nwav + 255) / 256)), dim3(256), 0, ctx->stream, nlay / 2, nwav,
+                       (const double*)g->bg_od, (float_x2_store*)g->bg_pair, d_flag + 1);
+    ECCKD_HIP_CHECK(hipGetLastError());
   }
-  int flag[2] = {0, 0};
-  GTRY(hipMemcpyAsync(flag, d_flag, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  GTRY(hipStreamSynchronize(ctx->stream));
-#undef GTRY
-  if (flag[0]) {
-    gas_free(g);
-    return ecckd::fail(ECCKD_PARAMETER_ERROR, "ecckd_gas_create_lw: rank is not a permutation of 0..nwav-1");
-  }
-  if (want_pairs && !pairs_in_k4 && flag[1]) {          // a DOUBLE background with values between the floats: the DOUBLE rows serve
-    ecckd::dev_release(ctx, g->bg_pair);
-    g->bg_pair = nullptr;
-  }
-  *out = g;
+  int not_float = 0;
+  ECCKD_HIP_CHECK(hipMemcpyAsync(&not_float, d_flag + 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  if (want_pairs && !pairs_in_k4 && not_float) g->give_back(g->bg_pair);   // a DOUBLE background with values between the floats: the DOUBLE rows serve
+  *out = gas.release();
   return ECCKD_OK;
 }
 
@@ -2354,16 +2450,9 @@ int ecckd_planck_hl_sorted_dev(ecckd_ctx* ctx, int nlay, size_t nwav, const doub
   int32_t* d_ireorder = (int32_t*)((char*)ctx->scratch + hk_bytes + flag_bytes);
   ECCKD_HIP_CHECK(hipMemcpyAsync(d_hk, hk.data(), nhl * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   ECCKD_HIP_CHECK(hipMemsetAsync(d_flag, 0, sizeof(int), ctx->stream));
-  ECCKD_HIP_CHECK(hipMemsetAsync(d_ireorder, 0xFF, nwav * sizeof(int32_t), ctx->stream));
-  const unsigned eblocks = (unsigned)((nwav + 255) / 256);
-  hipLaunchKernelGGL(k_invert_rank, dim3(eblocks), dim3(256), 0, ctx->stream, nwav, d_rank, d_ireorder, d_flag);
-  hipLaunchKernelGGL(k_check_perm, dim3(eblocks), dim3(256), 0, ctx->stream, nwav, d_ireorder, d_flag);
-  int flag = 0;
-  ECCKD_HIP_CHECK(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // also: hk is a local
-  ECCKD_REQUIRE(flag == 0, "ecckd_planck_hl_sorted_dev: rank is not a permutation of 0..nwav-1");
-  hipLaunchKernelGGL(k_planck_sorted, dim3(eblocks), dim3(256), 0, ctx->stream, nhl, nwav, d_ireorder, d_hk, d_wavenumber,
-                     d_d_wavenumber, d_planck_hl);
+  ECCKD_CHECK(invert_rank(ctx, "ecckd_planck_hl_sorted_dev", nwav, d_rank, d_ireorder, d_flag));   // its wait also: hk is a local
+  hipLaunchKernelGGL(k_planck_sorted, dim3((unsigned)((nwav + 255) / 256)), dim3(256), 0, ctx->stream, nhl, nwav, d_ireorder, d_hk,
+                     d_wavenumber, d_d_wavenumber, d_planck_hl);
   ECCKD_HIP_CHECK(hipGetLastError());
   ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return ECCKD_OK;
@@ -2379,120 +2468,42 @@ int ecckd_gas_create_sw(ecckd_ctx* ctx, int nlay, size_t nwav, const double* h_p
                         size_t src_stride, int averaging_method, double flux_weight,
                         double min_pressure, double cos_sza, double min_scaling, double max_scaling,
                         ecckd_gas** out) {
-  ECCKD_REQUIRE(ctx && out, "ecckd_gas_create_sw: NULL ctx/out");
-  *out = nullptr;
-  ECCKD_REQUIRE(nlay > 0 && nwav > 0, "ecckd_gas_create_sw: empty problem (nlay=%d, nwav=%zu)", nlay, nwav);
-  ECCKD_REQUIRE(nwav < (size_t)0x7fffffff, "ecckd_gas_create_sw: nwav exceeds int32 rank range");
-  ECCKD_REQUIRE(h_pressure_hl && d_ssi && d_rank && d_od, "ecckd_gas_create_sw: NULL array argument");
-  ECCKD_REQUIRE(od_type == ECCKD_F32 || od_type == ECCKD_F64, "ecckd_gas_create_sw: od_type must be 4 or 8");
-  ECCKD_REQUIRE(!d_bg_od || bg_type == ECCKD_F32 || bg_type == ECCKD_F64, "ecckd_gas_create_sw: bg_type must be 4 or 8");
-  ECCKD_REQUIRE(src_stride >= nwav, "ecckd_gas_create_sw: src_stride < nwav");
-  ECCKD_REQUIRE(averaging_method >= ECCKD_AVG_LINEAR && averaging_method <= ECCKD_AVG_TOTAL_TRANSMISSION,
-                "Averaging method %d not understood", averaging_method);
+  static const char who[] = "ecckd_gas_create_sw";
+  ECCKD_CHECK(gas_check_args(who, ctx, out, nlay, nwav, h_pressure_hl && d_ssi && d_rank && d_od, od_type, d_bg_od != nullptr,
+                             bg_type, src_stride, averaging_method, ECCKD_AVG_TOTAL_TRANSMISSION, h_pressure_hl, nullptr));
   ECCKD_REQUIRE(cos_sza > 0.0, "ecckd_gas_create_sw: cos_sza must be positive");
-  for (int i = 0; i <= nlay; ++i)
-    ECCKD_REQUIRE(h_pressure_hl[i] > 0.0 && (i == 0 || h_pressure_hl[i] > h_pressure_hl[i - 1]),
-                  "ecckd_gas_create_sw: pressure_hl must be positive and increasing");
   ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
 
-  ecckd_gas* g = new ecckd_gas();
-  g->ctx = ctx;
-  g->do_sw = 1;
-  g->method = averaging_method;
-  g->nlay = nlay;
-  g->n = nwav;
-  g->flux_weight = flux_weight;
+  GasPtr gas = gas_new(ctx, 1, averaging_method, nlay, nwav, flux_weight, h_pressure_hl);
+  ecckd_gas* const g = gas.get();
   g->cos_sza = cos_sza;
   g->min_scaling = min_scaling;
   g->max_scaling = max_scaling;
-  g->owns_planck = true;
-  g->h_pressure_hl.assign(h_pressure_hl, h_pressure_hl + nlay + 1);
   const bool is_log = averaging_method == ECCKD_AVG_LOGARITHMIC;
   const bool is_tt = averaging_method == ECCKD_AVG_TOTAL_TRANSMISSION;
   const size_t nhl = nlay + 1;
-  int rc = ECCKD_OK;
-#define GTRY(expr)                                                                       \
-  do {                                                                                   \
-    hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess) {                                                              \
-      rc = ecckd::fail(_e == hipErrorOutOfMemory ? ECCKD_OUT_OF_MEMORY : ECCKD_UNEXPECTED_EXCEPTION, \
-                       "%s failed: %s", #expr, hipGetErrorString(_e));                   \
-      gas_free(g);                                                                       \
-      return rc;                                                                         \
-    }                                                                                    \
-  } while (0)
   const size_t mat = (size_t)nlay * nwav * sizeof(double);
-  GTRY(ecckd::dev_malloc(ctx, (void**)&g->ssi, nwav * sizeof(double)));
-  GTRY(ecckd::dev_malloc(ctx, (void**)&g->bg_od, mat));
-  GTRY(ecckd::dev_malloc(ctx, (void**)&g->w1, mat));
+  ECCKD_HIP_CHECK(g->alloc(&g->ssi, nwav * sizeof(double)));
+  ECCKD_HIP_CHECK(g->alloc(&g->bg_od, mat));
+  ECCKD_HIP_CHECK(g->alloc(&g->w1, mat));
   if (is_log) {
-    GTRY(ecckd::dev_malloc(ctx, (void**)&g->w2, mat));
-    GTRY(ecckd::dev_malloc(ctx, (void**)&g->cnt, mat));
+    ECCKD_HIP_CHECK(g->alloc(&g->w2, mat));
+    ECCKD_HIP_CHECK(g->alloc(&g->cnt, mat));
   }
-  GTRY(ecckd::dev_malloc(ctx, (void**)&g->hr, mat));
-  GTRY(ecckd::dev_malloc(ctx, (void**)&g->fds, nwav * sizeof(double)));
-  GTRY(ecckd::dev_malloc(ctx, (void**)&g->fut, nwav * sizeof(double)));
+  ECCKD_HIP_CHECK(g->alloc(&g->hr, mat));
+  ECCKD_HIP_CHECK(g->alloc(&g->fds, nwav * sizeof(double)));
+  ECCKD_HIP_CHECK(g->alloc(&g->fut, nwav * sizeof(double)));
   if (is_tt) {
-    GTRY(ecckd::dev_malloc(ctx, (void**)&g->tf, mat));
-    GTRY(ecckd::dev_malloc(ctx, (void**)&g->tg, mat));
-    GTRY(ecckd::dev_malloc(ctx, (void**)&g->hr_low, mat));
-    GTRY(ecckd::dev_malloc(ctx, (void**)&g->hr_high, mat));
-    GTRY(ecckd::dev_malloc(ctx, (void**)&g->fx, 4 * nwav * sizeof(double)));
+    ECCKD_HIP_CHECK(g->alloc(&g->tf, mat));
+    ECCKD_HIP_CHECK(g->alloc(&g->tg, mat));
+    ECCKD_HIP_CHECK(g->alloc(&g->hr_low, mat));
+    ECCKD_HIP_CHECK(g->alloc(&g->hr_high, mat));
+    ECCKD_HIP_CHECK(g->alloc(&g->fx, 4 * nwav * sizeof(double)));
   }
-  GTRY(ecckd::dev_malloc(ctx, (void**)&g->ireorder, nwav * sizeof(int32_t)));
-
-  // per-level constants: (unused hk)[nhl] | conv[nlay] | layer_weight[nlay] | flag
-  std::vector<double> lev(nhl + 2 * nlay + 1, 0.0);
-  g->h_layer_weight.resize(nlay);
-  {
-    double sw = 0.0;
-    for (int l = 0; l < nlay; ++l) {
-      lev[nhl + l] = -(ECCKD_ACCEL_GRAVITY / ECCKD_SPECIFIC_HEAT_AIR) / (h_pressure_hl[l + 1] - h_pressure_hl[l]);
-      double lw = std::sqrt(h_pressure_hl[l + 1]) - std::sqrt(h_pressure_hl[l]);
-      double pfl = 0.5 * (h_pressure_hl[l + 1] + h_pressure_hl[l]);
-      if (pfl < min_pressure) lw = 0.0;
-      g->h_layer_weight[l] = lw;
-    }
-    for (int l = 0; l < nlay; ++l) sw += g->h_layer_weight[l];
-    for (int l = 0; l < nlay; ++l) {
-      g->h_layer_weight[l] /= sw;
-      lev[nhl + nlay + l] = g->h_layer_weight[l];
-    }
-  }
-  GTRY(ecckd::dev_malloc(ctx, (void**)&g->lev, lev.size() * sizeof(double)));
-  GTRY(hipMemcpyAsync(g->lev, lev.data(), lev.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  GTRY(hipStreamSynchronize(ctx->stream));
-  int* d_flag = (int*)(g->lev + nhl + 2 * nlay);
-
-  const unsigned eblocks = (unsigned)((nwav + 255) / 256);
-  GTRY(hipMemsetAsync(g->ireorder, 0xFF, nwav * sizeof(int32_t), ctx->stream));
-  hipLaunchKernelGGL(k_invert_rank, dim3(eblocks), dim3(256), 0, ctx->stream, nwav, d_rank, g->ireorder, d_flag);
-  hipLaunchKernelGGL(k_check_perm, dim3(eblocks), dim3(256), 0, ctx->stream, nwav, g->ireorder, d_flag);
-  {
-    int flag0 = 0;
-    GTRY(hipMemcpyAsync(&flag0, d_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    GTRY(hipStreamSynchronize(ctx->stream));
-    if (flag0) {
-      gas_free(g);
-      return ecckd::fail(ECCKD_PARAMETER_ERROR, "ecckd_gas_create_sw: rank is not a permutation of 0..nwav-1");
-    }
-  }
-  RowMap R;
-  int next = 0;
-  R.A = next; next += nlay;
-  R.B = next; next += nlay;   // rows of ssi (masked by metric > 0 for the logarithmic method)
-  if (is_log) { R.N = next; next += nlay; }
-  R.H = next; next += nlay;
-  R.FDS = next++;
-  R.FUT = next++;
-  if (is_tt) {
-    R.TF = next; next += nlay;
-    R.TG = next; next += nlay;
-    R.HL = next; next += nlay;
-    R.HH = next; next += nlay;
-    R.FDSL = next++; R.FUTL = next++; R.FDSH = next++; R.FUTH = next++;
-  }
-  R.total = next;
+  ECCKD_HIP_CHECK(g->alloc(&g->ireorder, nwav * sizeof(int32_t)));
+  ECCKD_CHECK(gas_layer_constants(g, nullptr, min_pressure));
+  ECCKD_CHECK(invert_rank(ctx, who, nwav, d_rank, g->ireorder, (int*)(g->lev + nhl + 2 * nlay)));
+  const RowMap R = make_row_map(nlay, is_log, is_tt);   // B: rows of ssi (masked by metric > 0 for the logarithmic method)
   g->rm = R;
   g->nrows = R.total;
 
@@ -2501,102 +2512,36 @@ int ecckd_gas_create_sw(ecckd_ctx* ctx, int nlay, size_t nwav, const double* h_p
   // 54 layers of FLOAT optical depths (the CKDMIP spectra): the columns are scattered into rank order first, staged through
   // LDS by the preparation, and the row sums are taken from registers (ECCKD_SW_PREP_GATHER: the general, gathering kernel)
   const bool cols = nlay == 54 && od_type == ECCKD_F32 && std::getenv("ECCKD_SW_PREP_GATHER") == nullptr;
-  void *od_col = nullptr, *bg_col = nullptr, *wave_part = nullptr;
-  auto drop_temps = [&]() {
-    if (od_col) ecckd::dev_release(ctx, od_col);
-    if (bg_col) ecckd::dev_release(ctx, bg_col);
-    if (wave_part) ecckd::dev_release(ctx, wave_part);
-    od_col = bg_col = wave_part = nullptr;
-  };
-  const size_t nw64 = (nwav + 63) / 64;
-#define LAUNCH_PREP_SW(BG, OD, BGP, ODP)                                                                          \
+  Temps temps{ctx};
+#define LAUNCH_PREP_SW(BG, OD)                                                                                    \
   hipLaunchKernelGGL((k_gas_prep_sw<BG, OD>), dim3(pblocks), dim3(PREP_THREADS), 0, ctx->stream, nlay, nwav,       \
                      src_stride, averaging_method, cos_sza, min_scaling, max_scaling, g->ireorder,                 \
-                     g->lev + nhl, d_ssi, d_albedo, (const BG*)(BGP), (const OD*)(ODP), g->ssi, g->bg_od,          \
+                     g->lev + nhl, d_ssi, d_albedo, (const BG*)d_bg_od, (const OD*)d_od, g->ssi, g->bg_od,         \
                      g->w1, g->w2, g->cnt, g->hr, g->fds, g->fut, g->tf, g->tg, g->hr_low, g->hr_high, g->fx)
   if (cols) {
-    const unsigned tblocks = (unsigned)((nwav + 63) / 64);
-    const size_t npad = nw64 * 64;          // the columns in runs of 18 layers, [3][npad][18], staged through LDS by the kernel
-    int rc2 = ecckd::dev_malloc(ctx, &od_col, npad * 54 * sizeof(float));
-    if (rc2 == ECCKD_OK && d_bg_od) rc2 = ecckd::dev_malloc(ctx, &bg_col, npad * 54 * (bg32 ? sizeof(float) : sizeof(double)));
-    if (rc2 == ECCKD_OK) rc2 = ecckd::dev_malloc(ctx, &wave_part, (size_t)g->nrows * nw64 * sizeof(double));
-    if (rc2 != ECCKD_OK) { drop_temps(); gas_free(g); return rc2; }
-    hipLaunchKernelGGL((k_scatter_column_halves<54, float, SW_STAGE_PARTS>), dim3(tblocks), dim3(256), 0, ctx->stream, nwav, npad, src_stride, d_rank,
-                       (const float*)d_od, (float*)od_col);
-    if (d_bg_od && bg32)
-      hipLaunchKernelGGL((k_scatter_column_halves<54, float, SW_STAGE_PARTS>), dim3(tblocks), dim3(256), 0, ctx->stream, nwav, npad, src_stride,
-                         d_rank, (const float*)d_bg_od, (float*)bg_col);
-    else if (d_bg_od)
-      hipLaunchKernelGGL((k_scatter_column_halves<54, double, SW_STAGE_PARTS>), dim3(tblocks), dim3(256), 0, ctx->stream, nwav, npad, src_stride,
-                         d_rank, (const double*)d_bg_od, (double*)bg_col);
+    // the columns in runs of 18 layers
+    ECCKD_CHECK(scatter_columns<SW_STAGE_PARTS>(temps, nwav, src_stride, d_rank, d_od, d_bg_od, bg32));
+    const size_t nw64 = (nwav + 63) / 64, npad = nw64 * 64;
+    ECCKD_HIP_CHECK(ecckd::dev_malloc(ctx, &temps.wave_part, (size_t)g->nrows * nw64 * sizeof(double)));
 #define LAUNCH_PREP_SW_STAGED(BG)                                                                                                     \
   hipLaunchKernelGGL((k_gas_prep_sw_staged<SW_STAGE_PARTS, BG>), dim3(pblocks), dim3(PREP_THREADS), 0, ctx->stream, nwav, npad,        \
-                     averaging_method, cos_sza, min_scaling, max_scaling, g->ireorder, g->lev + nhl, d_ssi, d_albedo, (const BG*)bg_col, \
-                     (const float*)od_col, g->ssi, g->bg_od, g->w1, g->w2, g->cnt, g->hr, g->fds, g->fut, g->tf, g->tg, g->hr_low,      \
-                     g->hr_high, g->fx, R, (double*)wave_part, nw64)
+                     averaging_method, cos_sza, min_scaling, max_scaling, g->ireorder, g->lev + nhl, d_ssi, d_albedo,                  \
+                     (const BG*)temps.bg_col, (const float*)temps.od_col, g->ssi, g->bg_od, g->w1, g->w2, g->cnt, g->hr, g->fds,       \
+                     g->fut, g->tf, g->tg, g->hr_low, g->hr_high, g->fx, R, (double*)temps.wave_part, nw64)
     if (bg32 || !d_bg_od) LAUNCH_PREP_SW_STAGED(float); else LAUNCH_PREP_SW_STAGED(double);
 #undef LAUNCH_PREP_SW_STAGED
   }
-  else if (bg32 && od_type == ECCKD_F32) LAUNCH_PREP_SW(float, float, d_bg_od, d_od);
-  else if (bg32) LAUNCH_PREP_SW(float, double, d_bg_od, d_od);
-  else if (od_type == ECCKD_F32) LAUNCH_PREP_SW(double, float, d_bg_od, d_od);
-  else LAUNCH_PREP_SW(double, double, d_bg_od, d_od);
+  else if (bg32 && od_type == ECCKD_F32) LAUNCH_PREP_SW(float, float);
+  else if (bg32) LAUNCH_PREP_SW(float, double);
+  else if (od_type == ECCKD_F32) LAUNCH_PREP_SW(double, float);
+  else LAUNCH_PREP_SW(double, double);
 #undef LAUNCH_PREP_SW
-  {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); drop_temps(); GTRY(e); }
-  }
+  ECCKD_HIP_CHECK(hipGetLastError());
 
-  std::vector<const double*> rows(g->nrows);
-  for (int l = 0; l < nlay; ++l) {
-    rows[R.A + l] = g->w1 + (size_t)l * nwav;
-    rows[R.B + l] = is_log ? g->w2 + (size_t)l * nwav : g->ssi;
-    if (is_log) rows[R.N + l] = g->cnt + (size_t)l * nwav;
-    rows[R.H + l] = g->hr + (size_t)l * nwav;
-    if (is_tt) {
-      rows[R.TF + l] = g->tf + (size_t)l * nwav;
-      rows[R.TG + l] = g->tg + (size_t)l * nwav;
-      rows[R.HL + l] = g->hr_low + (size_t)l * nwav;
-      rows[R.HH + l] = g->hr_high + (size_t)l * nwav;
-    }
-  }
-  rows[R.FDS] = g->fds;
-  rows[R.FUT] = g->fut;
-  if (is_tt) {
-    rows[R.FDSL] = g->fx;
-    rows[R.FUTL] = g->fx + nwav;
-    rows[R.FDSH] = g->fx + 2 * nwav;
-    rows[R.FUTH] = g->fx + 3 * nwav;
-  }
-  GTRY(ecckd::dev_malloc(ctx, (void**)&g->rows, rows.size() * sizeof(double*)));
-  GTRY(hipMemcpyAsync((void*)g->rows, rows.data(), rows.size() * sizeof(double*), hipMemcpyHostToDevice, ctx->stream));
-  GTRY(hipStreamSynchronize(ctx->stream));
-  g->ntiles = (nwav + TILE - 1) / TILE;
-  {
-    const int rc3 = ecckd::dev_malloc(ctx, (void**)&g->tile_sums, (size_t)g->nrows * g->ntiles * sizeof(double));
-    if (rc3 != ECCKD_OK) { (void)hipStreamSynchronize(ctx->stream); drop_temps(); gas_free(g); return rc3; }
-  }
-  if (wave_part) {
-    hipLaunchKernelGGL(k_combine_wave_sums, dim3((unsigned)((g->ntiles + 255) / 256), (unsigned)g->nrows), dim3(256), 0, ctx->stream,
-                       g->nrows, nw64, g->ntiles, (const double*)wave_part, g->tile_sums);
-  } else {
-    hipLaunchKernelGGL(k_tile_sums, dim3((unsigned)g->ntiles), dim3(TILE), 0, ctx->stream, g->nrows, nwav, g->ntiles,
-                       (const double* const*)g->rows, g->tile_sums);
-  }
-  {
-    const hipError_t e = hipGetLastError();
-    (void)hipStreamSynchronize(ctx->stream);
-    drop_temps();
-    GTRY(e);
-  }
-  g->nsuper = (g->ntiles + SUPER - 1) / SUPER;
-  GTRY(ecckd::dev_malloc(ctx, (void**)&g->super_sums, (size_t)g->nrows * g->nsuper * sizeof(double)));
-  hipLaunchKernelGGL(k_super_sums, dim3((unsigned)g->nsuper, (unsigned)g->nrows), dim3(256), 0, ctx->stream, g->ntiles, g->nsuper,
-                     (const double*)g->tile_sums, g->super_sums);
-  GTRY(hipGetLastError());
-  GTRY(hipStreamSynchronize(ctx->stream));
-#undef GTRY
-  *out = g;
+  // the three temporaries go back together, once the tile sums are there
+  ECCKD_CHECK(gas_sum_rows(g, g->ssi, 0, temps, true));
+  ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  *out = gas.release();
   return ECCKD_OK;
 }
 
@@ -2657,32 +2602,16 @@ double ecckd_gas_comp_cost(ecckd_gas* gas, int reset) {
 int ecckd_fit_optical_depth(ecckd_gas* g, size_t ibegin, size_t npoints, int n, const double* bound1,
                             const double* bound2, double* h_od_fit) {
   ECCKD_REQUIRE(g && n > 0 && bound1 && bound2 && h_od_fit, "ecckd_fit_optical_depth: bad argument");
-  ECCKD_REQUIRE(npoints > 0 && ibegin + npoints <= g->n, "ecckd_fit_optical_depth: band outside the spectrum");
   ecckd_ctx* ctx = g->ctx;
   ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
   const int nlay = g->nlay;
   std::vector<Interval> iv(n);
-  for (int k = 0; k < n; ++k) {
-    long long i1 = (long long)std::ceil(bound1[k] * (double)(npoints - 1));
-    long long i2 = (long long)std::floor(bound2[k] * (double)(npoints - 1));
-    if (i1 < 0 || i2 >= (long long)npoints || i2 + 1 < i1 || bound2[k] < bound1[k])
-      return ecckd::fail(ECCKD_PROCESSING_ERROR, "ecckd_fit_optical_depth: bad bounds %.17g-%.17g", bound1[k], bound2[k]);
-    if (i2 < i1) i2 = i1;
-    iv[k].i1 = (long long)ibegin + i1;
-    iv[k].i2 = (long long)ibegin + i2;
-    iv[k].chunk0 = k;
-    iv[k].chunk_pts = 0;   // no sweep in this call
-    iv[k].npoints = (long long)npoints;
-    iv[k].albedo = 0.0;
-  }
-  const size_t iv_bytes = ecckd_align_up((size_t)n * sizeof(Interval), 256);
-  const size_t sums_bytes = ecckd_align_up((size_t)n * g->nrows * sizeof(double), 256);
-  const size_t fit_bytes = ecckd_align_up((size_t)2 * n * nlay * sizeof(double), 256);
-  ECCKD_CHECK(gas_ensure_work(g, iv_bytes + sums_bytes + fit_bytes, iv_bytes + fit_bytes));
-  char* w = (char*)g->work;
-  Interval* d_iv = (Interval*)w; w += iv_bytes;
-  double* d_sums = (double*)w; w += sums_bytes;
-  double* d_fit = (double*)w;
+  for (int k = 0; k < n; ++k) ECCKD_CHECK(make_interval(g, ibegin, npoints, bound1[k], bound2[k], 0.0, iv[k]));
+  const WorkLayout L(n, g->nrows, nlay, 0);   // no sweep in this call
+  ECCKD_CHECK(gas_ensure_work(g, L.dev_bytes(), L.iv_bytes + L.fit_bytes));
+  Interval* d_iv = L.iv(g->work);
+  double* d_sums = L.sums(g->work);
+  double* d_fit = L.fit(g->work);
   std::memcpy(g->pinned, iv.data(), (size_t)n * sizeof(Interval));
   ECCKD_HIP_CHECK(hipMemcpyAsync(d_iv, g->pinned, (size_t)n * sizeof(Interval), hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(k_interval_sums, dim3(g->nrows, n), dim3(256), 0, ctx->stream, IntervalArgs(), g->nrows, g->ntiles, g->nsuper, d_iv, 0,
@@ -2695,7 +2624,7 @@ int ecckd_fit_optical_depth(ecckd_gas* g, size_t ibegin, size_t npoints, int n, 
     hipLaunchKernelGGL(k_fit_lw, dim3(n), dim3(128), 0, ctx->stream, nlay, g->method, g->rm, d_iv, d_sums, d_fit);
   }
   ECCKD_HIP_CHECK(hipGetLastError());
-  double* h = (double*)((char*)g->pinned + iv_bytes);
+  double* h = (double*)((char*)g->pinned + L.iv_bytes);
   ECCKD_HIP_CHECK(hipMemcpyAsync(h, d_fit, (size_t)n * nlay * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   std::memcpy(h_od_fit, h, (size_t)n * nlay * sizeof(double));
@@ -2710,13 +2639,28 @@ int ecckd_calc_error_batch(ecckd_gas* g, size_t ibegin, size_t npoints, int n, c
   return ecckd_calc_error_multi(g, n, ib.data(), np.data(), nullptr, bound1, bound2, error);
 }
 
-// ECCKD_TURNAROUND_LOG=1: where the host's time between two batches of a search goes (printed when the process ends)
+// ECCKD_TURNAROUND_LOG=1: where the host's time between two batches of a longwave search goes (printed when the process ends)
 struct TurnaroundLog {
+  typedef std::chrono::steady_clock::time_point time_point;
   bool on = std::getenv("ECCKD_TURNAROUND_LOG") != nullptr;
-  std::chrono::steady_clock::time_point seen;
+  time_point seen;
   bool have_seen = false;
   double to_entry = 0, to_first = 0, to_last = 0, wait = 0;
   long long n = 0;
+  time_point now() const { return on ? std::chrono::steady_clock::now() : time_point(); }
+  // a batch entered at t_entry, whose first and last launch were issued at t_first and t_last, has delivered its errors
+  void delivered(time_point t_entry, time_point t_first, time_point t_last) {
+    const time_point t = std::chrono::steady_clock::now();
+    if (have_seen && std::chrono::duration<double>(t_entry - seen).count() < 500e-6) {   // not the pause between two searches
+      to_entry += std::chrono::duration<double>(t_entry - seen).count();
+      to_first += std::chrono::duration<double>(t_first - seen).count();
+      to_last += std::chrono::duration<double>(t_last - seen).count();
+      wait += std::chrono::duration<double>(t - t_last).count();
+      n += 1;
+    }
+    seen = t;
+    have_seen = true;
+  }
   ~TurnaroundLog() {
     if (on && n)
       std::fprintf(stderr, "search batches %lld: errors seen -> next evaluation entered %.2f us, -> first launch issued %.2f us, -> last launch "
@@ -2725,22 +2669,153 @@ struct TurnaroundLog {
 };
 static TurnaroundLog g_turn;
 
+// HIP events round the sweep launches of every profile_stride-th batch (ecckd_profile_enable), on the lane of the evaluation:
+// the context's own events and counters, or the ones this gas was lent (ecckd_find_g_gases).
+struct SweepTimer {
+  hipEvent_t ev0, ev1;
+  ecckd_lane_stat& stat;
+  double units;
+  bool timed;
+  SweepTimer(ecckd_gas* g, double total_pts)
+      : ev0(g->lane ? g->lane->pev0 : g->ctx->pev0), ev1(g->lane ? g->lane->pev1 : g->ctx->pev1),
+        stat(g->lane ? (g->do_sw ? g->lane->stat_rt_sw : g->lane->stat_rt_lw) : (g->do_sw ? g->ctx->stat_rt_sw : g->ctx->stat_rt_lw)),
+        units(total_pts) {
+    const ecckd_ctx* ctx = g->ctx;
+    long long& profile_seq = g->lane ? g->lane->profile_seq : g->ctx->profile_seq;
+    timed = ctx->profile && (profile_seq++ % ctx->profile_stride) == 0;
+    if (ctx->profile) { stat.all_calls += 1; stat.all_units += units; }
+  }
+  int begin(hipStream_t stream) const {
+    if (timed) ECCKD_HIP_CHECK(hipEventRecord(ev0, stream));
+    return ECCKD_OK;
+  }
+  int end(hipStream_t stream) const {
+    if (timed) ECCKD_HIP_CHECK(hipEventRecord(ev1, stream));
+    return ECCKD_OK;
+  }
+  // after the errors have arrived (the cost kernel behind ev1 has delivered): the sweep's time into the counters and *ms
+  int finish(float* ms) {
+    if (!timed) return ECCKD_OK;
+    ECCKD_HIP_CHECK(hipEventSynchronize(ev1));
+    ECCKD_HIP_CHECK(hipEventElapsedTime(ms, ev0, ev1));
+    stat.ms += *ms;
+    stat.units += units;
+    stat.calls += 1;
+    return ECCKD_OK;
+  }
+};
+
+// A batch of intervals on its way through the launch train: what eval_intervals has laid out for the sweeps.
+struct Batch {
+  int n;                       // intervals
+  long long total_pts, nchunks, target_blocks;
+  bool fast_path;              // the compile-time-nlay sweeps
+  int use_ka;                  // the interval table travels in the first kernel's arguments
+  hipStream_t stream;
+  Interval* d_iv;
+  double *d_sums, *d_fit, *d_part;
+  double* h_err_dev;           // device alias of the pinned error slots
+  size_t cost_lds;
+  TurnaroundLog::time_point t_first;
+};
+
+// CkdEquipartition::calc_error, longwave (find_g_points.cpp:322-340): sums and fit, sweep, cost
+static int sweep_lw(ecckd_gas* g, Batch& b, const IntervalArgs& ka, const SweepTimer& timer) {
+  const int nlay = g->nlay, nhl = nlay + 1, n = b.n;
+  const hipStream_t stream = b.stream;
+  LwRowBases lw_rows;
+  lw_rows.w1 = g->w1; lw_rows.w2 = g->w2; lw_rows.cnt = g->cnt; lw_rows.planck_hl = g->planck_hl; lw_rows.hr = g->hr;
+  lw_rows.fds = g->fds; lw_rows.fut = g->fut; lw_rows.n = g->n; lw_rows.is_log = g->method == ECCKD_AVG_LOGARITHMIC;
+  hipLaunchKernelGGL(k_interval_sums_fit_lw, dim3(nlay + (g->rm.total - g->rm.H), n), dim3(256), 0, stream, ka, nlay, g->method,
+                     g->rm, g->ntiles, g->nsuper, b.d_iv, b.use_ka, b.d_iv, lw_rows, g->tile_sums, g->super_sums,
+                     b.d_sums, b.d_fit);
+  b.t_first = g_turn.now();
+  ECCKD_CHECK(timer.begin(stream));
+#define ECCKD_LW_MIRROR(NL, P32)                                                                                          \
+  hipLaunchKernelGGL((k_rt_lw_bb_mirror<NL, P32>), dim3(mirror_grid), dim3(RT_THREADS), 0, stream, g->n, n, b.nchunks, b.d_iv, \
+                     g->planck_hl, g->bg_od, (const float_x2*)g->bg_pair, b.d_fit, b.d_part)
+  // a block per chunk.  (ECCKD_RT_PERSISTENT: one resident round of blocks, each taking every mirror_grid-th chunk - measured
+  // SLOWER on a partition of unequal intervals, 1 069 against 1 015 us per pass of 38 intervals over 7.2e6 points, equal on
+  // equal intervals: the hardware's block dispatcher balances chunks of one to three tiles better than a fixed deal.)
+  static const bool persistent = std::getenv("ECCKD_RT_PERSISTENT") != nullptr;
+  const unsigned mirror_grid = (unsigned)(persistent ? std::min<long long>(b.nchunks, b.target_blocks) : b.nchunks);
+  if (b.fast_path && nlay == 54) {
+    if (g->bg_pair) ECCKD_LW_MIRROR(54, true); else ECCKD_LW_MIRROR(54, false);
+  } else if (b.fast_path && nlay == 30) {
+    if (g->bg_pair) ECCKD_LW_MIRROR(30, true); else ECCKD_LW_MIRROR(30, false);
+#undef ECCKD_LW_MIRROR
+  } else {
+    ECCKD_CHECK(gas_bg_rows(g));
+    const size_t rt_lds = (size_t)(4 * 2 * nhl + nlay) * sizeof(double);
+    hipLaunchKernelGGL(k_rt_lw_bb, dim3((unsigned)b.nchunks), dim3(RT_THREADS), rt_lds, stream, nlay, g->n,
+                       n, b.d_iv, g->planck_hl, g->bg_od, b.d_fit, b.d_part);
+  }
+  ECCKD_CHECK(timer.end(stream));
+  hipLaunchKernelGGL(k_cost_lw, dim3(n), dim3(1024), b.cost_lds, stream, nlay, g->rm, b.d_iv,
+                     b.nchunks, b.d_part, b.d_sums, g->lev + nhl, g->lev + nhl + nlay, g->flux_weight, b.h_err_dev);
+  return ECCKD_OK;
+}
+
+// CkdEquipartition::calc_error, shortwave branches (find_g_points.cpp:341-402): sums, fit, sweep(s), cost
+static int sweep_sw(ecckd_gas* g, Batch& b, const IntervalArgs& ka, const SweepTimer& timer) {
+  const int nlay = g->nlay, nhl = nlay + 1, n = b.n;
+  const hipStream_t stream = b.stream;
+  Interval* const d_iv = b.d_iv;
+  double* const d_fit = b.d_fit;
+  const long long nchunks = b.nchunks;
+  const bool is_tt = g->method == ECCKD_AVG_TOTAL_TRANSMISSION;
+  const RowMap& R = g->rm;
+  hipLaunchKernelGGL(k_interval_sums, dim3(g->nrows, n), dim3(256), 0, stream, ka, g->nrows, g->ntiles, g->nsuper, d_iv, b.use_ka,
+                     d_iv, (const double* const*)g->rows, g->tile_sums, g->super_sums, b.d_sums);
+  hipLaunchKernelGGL(k_fit_sw, dim3(n), dim3(128), nlay * sizeof(double), stream, nlay, g->method, R, n,
+                     g->min_scaling, g->max_scaling, d_iv, b.d_sums, d_fit);
+  const size_t rt_lds_sw = (size_t)(4 * 2 * nhl + nlay) * sizeof(double);
+  const int npass = is_tt ? 2 : 1;
+  // total-transmission evaluates the interval with the fit scaled by min_scaling and by max_scaling (:374-386; never equal
+  // in the reference: min <= 0.5, max >= 2.5, :666-667): one launch that fetches the column once and sweeps it with both
+  // fits (the compile-time-nlay kernels).  At the reference's cos_sza = 0.5 the direct and the reflected beam see the same
+  // transmittance exp(-2 tau), bit for bit: the kernels then keep it from the way down (SAME).
+  const bool dual = is_tt && b.fast_path;
+  const size_t part_stride = (size_t)nchunks * 2 * nhl;
+  static const bool no_same = std::getenv("ECCKD_SW_NO_SAME") != nullptr;   // A/B knob
+  const bool same_exp = g->cos_sza == 0.5 && !no_same;
+  ECCKD_CHECK(timer.begin(stream));
+  for (int pass = 0; pass < (dual ? 1 : npass); ++pass) {
+    double* part = b.d_part + (size_t)pass * part_stride;
+#define ECCKD_SW_SWEEP(NL, NF, SM, FIT)                                                                                         \
+  hipLaunchKernelGGL((k_rt_sw_bb_fast<NL, NF, SM>), dim3((unsigned)nchunks), dim3(RT_THREADS), 0, stream, g->n, n, \
+                     d_iv, g->cos_sza, g->ssi, g->bg_od, FIT, part)
+    const double* fit1 = d_fit + (size_t)pass * n * nlay;
+    if (!b.fast_path)
+      hipLaunchKernelGGL(k_rt_sw_bb, dim3((unsigned)nchunks), dim3(RT_THREADS), rt_lds_sw, stream, nlay, g->n,
+                         n, d_iv, g->cos_sza, g->ssi, g->bg_od, fit1, part);
+    else if (nlay == 54 && dual) { if (same_exp) ECCKD_SW_SWEEP(54, 2, true, d_fit); else ECCKD_SW_SWEEP(54, 2, false, d_fit); }
+    else if (nlay == 30 && dual) { if (same_exp) ECCKD_SW_SWEEP(30, 2, true, d_fit); else ECCKD_SW_SWEEP(30, 2, false, d_fit); }
+    else if (nlay == 54) { if (same_exp) ECCKD_SW_SWEEP(54, 1, true, fit1); else ECCKD_SW_SWEEP(54, 1, false, fit1); }
+    else if (nlay == 30) { if (same_exp) ECCKD_SW_SWEEP(30, 1, true, fit1); else ECCKD_SW_SWEEP(30, 1, false, fit1); }
+#undef ECCKD_SW_SWEEP
+  }
+  ECCKD_CHECK(timer.end(stream));
+  // both evaluations in one launch; the errors go straight into the pinned host buffer (a few bytes over PCIe)
+  SwTruthRows rows;
+  rows.rH[0] = is_tt ? R.HL : R.H;      rows.rH[1] = R.HH;
+  rows.rFDS[0] = is_tt ? R.FDSL : R.FDS; rows.rFDS[1] = R.FDSH;
+  rows.rFUT[0] = is_tt ? R.FUTL : R.FUT; rows.rFUT[1] = R.FUTH;
+  hipLaunchKernelGGL(k_cost_sw, dim3(n, npass), dim3(1024), b.cost_lds, stream, nlay, R.total, rows, d_iv, nchunks,
+                     b.d_part, part_stride, b.d_sums, g->lev + nhl, g->lev + nhl + nlay, g->flux_weight, g->cos_sza, b.h_err_dev);
+  return ECCKD_OK;
+}
+
 // Errors of the intervals iv[0..n) (first / last sorted index and albedo filled in) on the device -> error[0..n).
 static int eval_intervals(ecckd_gas* g, std::vector<Interval>& iv, double* error) {
-  const auto t_entry = g_turn.on ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
-  std::chrono::steady_clock::time_point t_first, t_last;
-  const int n = (int)iv.size();
+  const TurnaroundLog::time_point t_entry = g_turn.now();
   ecckd_ctx* ctx = g->ctx;
-  // the lane of this evaluation: the context's own stream, events and counters, or the ones this gas was lent (ecckd_find_g_gases)
-  ecckd_lane* const lane = g->lane;
-  const hipStream_t stream = g->eval_stream();
-  hipEvent_t const pev0 = lane ? lane->pev0 : ctx->pev0, pev1 = lane ? lane->pev1 : ctx->pev1;
-  long long& profile_seq = lane ? lane->profile_seq : ctx->profile_seq;
-  ecckd_lane_stat& stat_rt_lw = lane ? lane->stat_rt_lw : ctx->stat_rt_lw;
-  ecckd_lane_stat& stat_rt_sw = lane ? lane->stat_rt_sw : ctx->stat_rt_sw;
   const int nlay = g->nlay, nhl = nlay + 1;
-  long long total_pts = 0;
-  for (int k = 0; k < n; ++k) total_pts += iv[k].i2 - iv[k].i1 + 1;
+  Batch b;
+  const int n = b.n = (int)iv.size();
+  b.stream = g->eval_stream();
+  b.total_pts = 0;
+  for (int k = 0; k < n; ++k) b.total_pts += iv[k].i2 - iv[k].i1 + 1;
 
   // Chunking.  Every interval is cut into chunks of ITS OWN size: the smallest multiple of what one block iteration covers
   // (the longwave mirror kernel: two wave pairs = 128 points; the other sweeps: 256) with which the interval fills at most
@@ -2750,181 +2825,70 @@ static int eval_intervals(ecckd_gas* g, std::vector<Interval>& iv, double* error
   // other bands' intervals (ecckd_calc_error_multi).  A batch of n intervals launches up to n rounds of small blocks; the
   // hardware's block dispatcher balances them.
   // ECCKD_RT_GENERIC (read per call): the run-time-nlay sweeps instead of the compile-time ones, for cross-checks at full size
-  const bool fast_path = (nlay == 54 || nlay == 30) && std::getenv("ECCKD_RT_GENERIC") == nullptr;
+  b.fast_path = (nlay == 54 || nlay == 30) && std::getenv("ECCKD_RT_GENERIC") == nullptr;
   // mirror path: 3 resident blocks per CU (3 waves/SIMD); the two-fit shortwave sweep holds 2
   static const int rt_bpc = std::getenv("ECCKD_RT_BPC") ? std::max(1, std::atoi(std::getenv("ECCKD_RT_BPC"))) : 3;   // tuning knob
   static const int sw2_bpc = std::getenv("ECCKD_SW2_BPC") ? std::max(1, std::atoi(std::getenv("ECCKD_SW2_BPC"))) : 2;   // tuning knob
-  const bool sw_two_fits = g->do_sw && g->method == ECCKD_AVG_TOTAL_TRANSMISSION && fast_path;
-  const long long target_blocks = (long long)ctx->num_cu * (sw_two_fits ? sw2_bpc : fast_path ? rt_bpc : 8);
-  const long long gran = (!g->do_sw && fast_path) ? RT_THREADS / 2 : RT_THREADS;
-  long long nchunks = 0;
+  const bool is_tt = g->do_sw && g->method == ECCKD_AVG_TOTAL_TRANSMISSION;
+  b.target_blocks = (long long)ctx->num_cu * (is_tt && b.fast_path ? sw2_bpc : b.fast_path ? rt_bpc : 8);
+  const long long gran = (!g->do_sw && b.fast_path) ? RT_THREADS / 2 : RT_THREADS;
+  b.nchunks = 0;
   for (int k = 0; k < n; ++k) {
     const long long len = iv[k].i2 - iv[k].i1 + 1;
-    iv[k].chunk_pts = interval_chunk_pts(len, target_blocks, gran);
-    iv[k].chunk0 = nchunks;
-    nchunks += (len + iv[k].chunk_pts - 1) / iv[k].chunk_pts;
+    iv[k].chunk_pts = interval_chunk_pts(len, b.target_blocks, gran);
+    iv[k].chunk0 = b.nchunks;
+    b.nchunks += (len + iv[k].chunk_pts - 1) / iv[k].chunk_pts;
   }
-  ECCKD_REQUIRE(nchunks < 0x7fffffffLL, "ecckd_calc_error_batch: %lld chunks in one batch", nchunks);
+  ECCKD_REQUIRE(b.nchunks < 0x7fffffffLL, "ecckd_calc_error_batch: %lld chunks in one batch", b.nchunks);
+  b.cost_lds = (size_t)(COST_GROUPS * 2 * nhl + 2 * nhl + nlay) * sizeof(double);
+  ECCKD_REQUIRE(b.target_blocks <= 32 * COST_GROUPS && b.cost_lds <= 64 * 1024, "ecckd_calc_error_batch: %lld chunks per interval / %d layers exceed the cost kernel's room",
+                b.target_blocks, nlay);
 
-  // device work layout: intervals | sums[n][nrows] | od_fit[2][n][nlay] | partial[nchunks][2nhl] | err[2][n]
-  const size_t iv_bytes = ecckd_align_up((size_t)n * sizeof(Interval), 256);
-  const size_t sums_bytes = ecckd_align_up((size_t)n * g->nrows * sizeof(double), 256);
-  const size_t fit_bytes = ecckd_align_up((size_t)2 * n * nlay * sizeof(double), 256);
-  const size_t part_bytes = ecckd_align_up((size_t)2 * nchunks * 2 * nhl * sizeof(double), 256);   // x2: both fits of the dual shortwave sweep
+  // The errors are written straight into the pinned host buffer by the last kernel (a few bytes over PCIe): no device-to-host
+  // copy in the stream.  err_bytes count in the device request too: it sizes the block the context's cache later hands on.
+  const WorkLayout L(n, g->nrows, nlay, b.nchunks);
   const size_t err_bytes = ecckd_align_up((size_t)2 * n * sizeof(double), 256);
-  ECCKD_CHECK(gas_ensure_work(g, iv_bytes + sums_bytes + fit_bytes + part_bytes + err_bytes, iv_bytes + err_bytes));
-  char* w = (char*)g->work;
-  Interval* d_iv = (Interval*)w; w += iv_bytes;
-  double* d_sums = (double*)w; w += sums_bytes;
-  double* d_fit = (double*)w; w += fit_bytes;
-  double* d_part = (double*)w; w += part_bytes;
-  (void)err_bytes;   // the errors are written into the pinned host buffer
+  ECCKD_CHECK(gas_ensure_work(g, L.dev_bytes() + err_bytes, L.iv_bytes + err_bytes));
+  b.d_iv = L.iv(g->work);
+  b.d_sums = L.sums(g->work);
+  b.d_fit = L.fit(g->work);
+  b.d_part = L.part(g->work);
   Interval* h_iv = (Interval*)g->pinned;
-  double* h_err = (double*)((char*)g->pinned + iv_bytes);
-  // the errors are written straight into the pinned host buffer by the last kernel (a few bytes over PCIe): no
-  // device-to-host copy in the stream
+  double* h_err = (double*)((char*)g->pinned + L.iv_bytes);
   if (g->pinned_dev_of != g->pinned) {        // the device alias of the pinned buffer, looked up once per (re)allocation
     ECCKD_HIP_CHECK(hipHostGetDevicePointer((void**)&g->pinned_dev, g->pinned, 0));
     g->pinned_dev_of = g->pinned;
   }
-  double* h_err_dev = (double*)((char*)g->pinned_dev + iv_bytes);
-  const int nslots = (g->do_sw && g->method == ECCKD_AVG_TOTAL_TRANSMISSION) ? 2 * n : n;
+  b.h_err_dev = (double*)((char*)g->pinned_dev + L.iv_bytes);
+  const int nslots = is_tt ? 2 * n : n;
   mark_pending(h_err, nslots);
   static const bool no_karg = std::getenv("ECCKD_NO_KARG") != nullptr;   // A/B knob: always copy the interval table
-  const int use_ka = (n <= KARG_MAX && !no_karg) ? 1 : 0;
+  b.use_ka = (n <= KARG_MAX && !no_karg) ? 1 : 0;
   IntervalArgs ka;
-  if (use_ka) {
+  if (b.use_ka) {
     for (int k = 0; k < KARG_MAX; ++k) ka.iv[k] = iv[k < n ? k : n - 1];
   } else {
     std::memset(&ka, 0, sizeof ka);
     std::memcpy(h_iv, iv.data(), (size_t)n * sizeof(Interval));
-    ECCKD_HIP_CHECK(hipMemcpyAsync(d_iv, h_iv, (size_t)n * sizeof(Interval), hipMemcpyHostToDevice, stream));
+    ECCKD_HIP_CHECK(hipMemcpyAsync(b.d_iv, h_iv, (size_t)n * sizeof(Interval), hipMemcpyHostToDevice, b.stream));
   }
 
-  LwRowBases lw_rows;
-  lw_rows.w1 = g->w1; lw_rows.w2 = g->w2; lw_rows.cnt = g->cnt; lw_rows.planck_hl = g->planck_hl; lw_rows.hr = g->hr;
-  lw_rows.fds = g->fds; lw_rows.fut = g->fut; lw_rows.n = g->n; lw_rows.is_log = g->method == ECCKD_AVG_LOGARITHMIC;
-  if (!g->do_sw)
-    hipLaunchKernelGGL(k_interval_sums_fit_lw, dim3(nlay + (g->rm.total - g->rm.H), n), dim3(256), 0, stream, ka, nlay, g->method,
-                       g->rm, g->ntiles, g->nsuper, d_iv, use_ka, d_iv, lw_rows, g->tile_sums, g->super_sums,
-                       d_sums, d_fit);
-  else
-    hipLaunchKernelGGL(k_interval_sums, dim3(g->nrows, n), dim3(256), 0, stream, ka, g->nrows, g->ntiles, g->nsuper, d_iv, use_ka,
-                       d_iv, (const double* const*)g->rows, g->tile_sums, g->super_sums, d_sums);
-  if (g->do_sw) {
-    // CkdEquipartition::calc_error, shortwave branches (find_g_points.cpp:341-402)
-    const bool is_tt = g->method == ECCKD_AVG_TOTAL_TRANSMISSION;
-    const RowMap& R = g->rm;
-    hipLaunchKernelGGL(k_fit_sw, dim3(n), dim3(128), nlay * sizeof(double), stream, nlay, g->method, R, n,
-                       g->min_scaling, g->max_scaling, d_iv, d_sums, d_fit);
-    const size_t rt_lds_sw = (size_t)(4 * 2 * nhl + nlay) * sizeof(double);
-    const size_t cost_lds_sw = (size_t)(COST_GROUPS * 2 * nhl + 2 * nhl + nlay) * sizeof(double);
-    ECCKD_REQUIRE(target_blocks <= 32 * COST_GROUPS && cost_lds_sw <= 64 * 1024, "ecckd_calc_error_batch: %lld chunks per interval / %d layers exceed the cost kernel's room",
-                  target_blocks, nlay);
-    const int npass = is_tt ? 2 : 1;
-    // total-transmission evaluates the interval with the fit scaled by min_scaling and by max_scaling (:374-386; never equal
-    // in the reference: min <= 0.5, max >= 2.5, :666-667): one launch that fetches the column once and sweeps it with both
-    // fits (the compile-time-nlay kernels).  At the reference's cos_sza = 0.5 the direct and the reflected beam see the same
-    // transmittance exp(-2 tau), bit for bit: the kernels then keep it from the way down (SAME).
-    const bool dual = is_tt && fast_path;
-    const size_t part_stride = (size_t)nchunks * 2 * nhl;
-    static const bool no_same = std::getenv("ECCKD_SW_NO_SAME") != nullptr;   // A/B knob
-    const bool same_exp = g->cos_sza == 0.5 && !no_same;
-    // HIP events round the sweep launches of every profile_stride-th batch (ecckd_profile_enable), as for the longwave sweep
-    const bool timed_sw = ctx->profile && (profile_seq++ % ctx->profile_stride) == 0;
-    if (ctx->profile) { stat_rt_sw.all_calls += 1; stat_rt_sw.all_units += (double)total_pts; }
-    if (timed_sw) ECCKD_HIP_CHECK(hipEventRecord(pev0, stream));
-    for (int pass = 0; pass < (dual ? 1 : npass); ++pass) {
-      double* part = d_part + (size_t)pass * part_stride;
-#define ECCKD_SW_SWEEP(NL, NF, SM, FIT)                                                                                         \
-  hipLaunchKernelGGL((k_rt_sw_bb_fast<NL, NF, SM>), dim3((unsigned)nchunks), dim3(RT_THREADS), 0, stream, g->n, n, \
-                     d_iv, g->cos_sza, g->ssi, g->bg_od, FIT, part)
-      const double* fit1 = d_fit + (size_t)pass * n * nlay;
-      if (!fast_path)
-        hipLaunchKernelGGL(k_rt_sw_bb, dim3((unsigned)nchunks), dim3(RT_THREADS), rt_lds_sw, stream, nlay, g->n,
-                           n, d_iv, g->cos_sza, g->ssi, g->bg_od, fit1, part);
-      else if (nlay == 54 && dual) { if (same_exp) ECCKD_SW_SWEEP(54, 2, true, d_fit); else ECCKD_SW_SWEEP(54, 2, false, d_fit); }
-      else if (nlay == 30 && dual) { if (same_exp) ECCKD_SW_SWEEP(30, 2, true, d_fit); else ECCKD_SW_SWEEP(30, 2, false, d_fit); }
-      else if (nlay == 54) { if (same_exp) ECCKD_SW_SWEEP(54, 1, true, fit1); else ECCKD_SW_SWEEP(54, 1, false, fit1); }
-      else if (nlay == 30) { if (same_exp) ECCKD_SW_SWEEP(30, 1, true, fit1); else ECCKD_SW_SWEEP(30, 1, false, fit1); }
-#undef ECCKD_SW_SWEEP
-    }
-    if (timed_sw) ECCKD_HIP_CHECK(hipEventRecord(pev1, stream));
-    // both evaluations in one launch; the errors go straight into the pinned host buffer (a few bytes over PCIe)
-    SwTruthRows rows;
-    rows.rH[0] = is_tt ? R.HL : R.H;      rows.rH[1] = R.HH;
-    rows.rFDS[0] = is_tt ? R.FDSL : R.FDS; rows.rFDS[1] = R.FDSH;
-    rows.rFUT[0] = is_tt ? R.FUTL : R.FUT; rows.rFUT[1] = R.FUTH;
-    hipLaunchKernelGGL(k_cost_sw, dim3(n, npass), dim3(1024), cost_lds_sw, stream, nlay, R.total, rows, d_iv, nchunks,
-                       d_part, part_stride, d_sums, g->lev + nhl, g->lev + nhl + nlay, g->flux_weight, g->cos_sza, h_err_dev);
-    ECCKD_HIP_CHECK(hipGetLastError());
-    ECCKD_CHECK(wait_for_slots(stream, h_err, nslots));
-    for (int k = 0; k < n; ++k) error[k] = is_tt ? 0.5 * (h_err[k] + h_err[n + k]) : h_err[k];  // :386
-    if (timed_sw) {
-      float ms = 0.f;
-      ECCKD_HIP_CHECK(hipEventSynchronize(pev1));
-      ECCKD_HIP_CHECK(hipEventElapsedTime(&ms, pev0, pev1));
-      stat_rt_sw.ms += ms;
-      stat_rt_sw.units += (double)total_pts;
-      stat_rt_sw.calls += 1;
-    }
-    return ECCKD_OK;
-  }
-  if (g_turn.on) t_first = std::chrono::steady_clock::now();
-  const size_t rt_lds = (size_t)(4 * 2 * nhl + nlay) * sizeof(double);
-  const bool timed = ctx->profile && (profile_seq++ % ctx->profile_stride) == 0;
-  if (ctx->profile) { stat_rt_lw.all_calls += 1; stat_rt_lw.all_units += (double)total_pts; }
-  if (timed) ECCKD_HIP_CHECK(hipEventRecord(pev0, stream));
-#define ECCKD_LW_MIRROR(NL, P32)                                                                                          \
-  hipLaunchKernelGGL((k_rt_lw_bb_mirror<NL, P32>), dim3(mirror_grid), dim3(RT_THREADS), 0, stream, g->n, n, nchunks, d_iv,     \
-                     g->planck_hl, g->bg_od, (const float_x2*)g->bg_pair, d_fit, d_part)
-  // a block per chunk.  (ECCKD_RT_PERSISTENT: one resident round of blocks, each taking every mirror_grid-th chunk - measured
-  // SLOWER on a partition of unequal intervals, 1 069 against 1 015 us per pass of 38 intervals over 7.2e6 points, equal on
-  // equal intervals: the hardware's block dispatcher balances chunks of one to three tiles better than a fixed deal.)
-  static const bool persistent = std::getenv("ECCKD_RT_PERSISTENT") != nullptr;
-  const unsigned mirror_grid = (unsigned)(persistent ? std::min<long long>(nchunks, target_blocks) : nchunks);
-  if (fast_path && nlay == 54) {
-    if (g->bg_pair) ECCKD_LW_MIRROR(54, true); else ECCKD_LW_MIRROR(54, false);
-  } else if (fast_path && nlay == 30) {
-    if (g->bg_pair) ECCKD_LW_MIRROR(30, true); else ECCKD_LW_MIRROR(30, false);
-#undef ECCKD_LW_MIRROR
-  } else {
-    ECCKD_CHECK(gas_bg_rows(g));
-    hipLaunchKernelGGL(k_rt_lw_bb, dim3((unsigned)nchunks), dim3(RT_THREADS), rt_lds, stream, nlay, g->n,
-                       n, d_iv, g->planck_hl, g->bg_od, d_fit, d_part);
-  }
-  if (timed) ECCKD_HIP_CHECK(hipEventRecord(pev1, stream));
-  const size_t cost_lds = (size_t)(COST_GROUPS * 2 * nhl + 2 * nhl + nlay) * sizeof(double);
-  ECCKD_REQUIRE(target_blocks <= 32 * COST_GROUPS && cost_lds <= 64 * 1024, "ecckd_calc_error_batch: %lld chunks per interval / %d layers exceed the cost kernel's room",
-                target_blocks, nlay);
-  hipLaunchKernelGGL(k_cost_lw, dim3(n), dim3(1024), cost_lds, stream, nlay, g->rm, d_iv,
-                     nchunks, d_part, d_sums, g->lev + nhl, g->lev + nhl + nlay, g->flux_weight, h_err_dev);
+  SweepTimer timer(g, (double)b.total_pts);
+  ECCKD_CHECK(g->do_sw ? sweep_sw(g, b, ka, timer) : sweep_lw(g, b, ka, timer));
   ECCKD_HIP_CHECK(hipGetLastError());
-  if (g_turn.on) t_last = std::chrono::steady_clock::now();
-  ECCKD_CHECK(wait_for_slots(stream, h_err, nslots));
-  if (g_turn.on) {
-    const auto now = std::chrono::steady_clock::now();
-    if (g_turn.have_seen && std::chrono::duration<double>(t_entry - g_turn.seen).count() < 500e-6) {   // not the pause between two searches
-      g_turn.to_entry += std::chrono::duration<double>(t_entry - g_turn.seen).count();
-      g_turn.to_first += std::chrono::duration<double>(t_first - g_turn.seen).count();
-      g_turn.to_last += std::chrono::duration<double>(t_last - g_turn.seen).count();
-      g_turn.wait += std::chrono::duration<double>(now - t_last).count();
-      g_turn.n += 1;
-    }
-    g_turn.seen = now;
-    g_turn.have_seen = true;
-  }
-  std::memcpy(error, h_err, (size_t)n * sizeof(double));
-  if (timed) {
-    float ms = 0.f;
-    ECCKD_HIP_CHECK(hipEventSynchronize(pev1));    // long past: the cost kernel behind it has delivered
-    ECCKD_HIP_CHECK(hipEventElapsedTime(&ms, pev0, pev1));
-    stat_rt_lw.ms += ms;
-    stat_rt_lw.units += (double)total_pts;
-    stat_rt_lw.calls += 1;
-    // ECCKD_SWEEP_LOG=<file>: one line per sweep launch (intervals, points, chunks, ms) for tools/sweep_sizes.py
+  const TurnaroundLog::time_point t_last = g_turn.now();
+  ECCKD_CHECK(wait_for_slots(b.stream, h_err, nslots));
+  if (g_turn.on && !g->do_sw) g_turn.delivered(t_entry, b.t_first, t_last);
+  if (is_tt)
+    for (int k = 0; k < n; ++k) error[k] = 0.5 * (h_err[k] + h_err[n + k]);  // find_g_points.cpp:386
+  else
+    std::memcpy(error, h_err, (size_t)n * sizeof(double));
+  float ms = 0.f;
+  ECCKD_CHECK(timer.finish(&ms));
+  if (timer.timed && !g->do_sw) {
+    // ECCKD_SWEEP_LOG=<file>: one line per longwave sweep launch (intervals, points, chunks, ms) for tools/sweep_sizes.py
     static FILE* sweep_log = std::getenv("ECCKD_SWEEP_LOG") ? std::fopen(std::getenv("ECCKD_SWEEP_LOG"), "a") : nullptr;
-    if (sweep_log) std::fprintf(sweep_log, "%d %lld %lld %.6f\n", n, total_pts, nchunks, (double)ms);
+    if (sweep_log) std::fprintf(sweep_log, "%d %lld %lld %.6f\n", n, b.total_pts, b.nchunks, (double)ms);
   }
   return ECCKD_OK;
 }
@@ -2939,29 +2903,9 @@ int ecckd_calc_error_multi(ecckd_gas* g, int n, const size_t* ibegin_k, const si
   ecckd_ctx* ctx = g->ctx;
   ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
 
-  // index mapping and error paths of CkdEquipartition::calc_error (find_g_points.cpp:282-320)
   std::vector<Interval> iv(n);
-  for (int k = 0; k < n; ++k) {
-    const size_t ibegin = ibegin_k[k], npoints = npoints_k[k];
-    ECCKD_REQUIRE(npoints > 0 && ibegin + npoints <= g->n,
-                  "ecckd_calc_error_batch: band [%zu,%zu) outside the spectrum (%zu points)", ibegin, ibegin + npoints, g->n);
-    const double b1 = bound1[k], b2 = bound2[k];
-    long long i1 = (long long)std::ceil(b1 * (double)(npoints - 1));
-    long long i2 = (long long)std::floor(b2 * (double)(npoints - 1));
-    if (i1 < 0 || i2 >= (long long)npoints || !(b1 == b1) || !(b2 == b2))
-      return ecckd::fail(ECCKD_PROCESSING_ERROR,
-                         "requested bounds %.17g-%.17g corresponding to indices %lld-%lld outside valid range 0-%zu",
-                         b1, b2, i1, i2, npoints - 1);
-    if (b2 < b1) return ecckd::fail(ECCKD_PROCESSING_ERROR, "requested bounds out of order: %.17g-%.17g", b1, b2);
-    if (i2 + 1 < i1) return ecckd::fail(ECCKD_PROCESSING_ERROR, "requested indices out of order: %lld-%lld", i1, i2);
-    if (i2 < i1) i2 = i1;
-    iv[k].i1 = (long long)ibegin + i1;
-    iv[k].i2 = (long long)ibegin + i2;
-    iv[k].chunk0 = 0;
-    iv[k].chunk_pts = 0;
-    iv[k].npoints = (long long)npoints;
-    iv[k].albedo = albedo_k ? albedo_k[k] : g->surf_albedo;
-  }
+  for (int k = 0; k < n; ++k)
+    ECCKD_CHECK(make_interval(g, ibegin_k[k], npoints_k[k], bound1[k], bound2[k], albedo_k ? albedo_k[k] : g->surf_albedo, iv[k]));
   for (int k = 0; k < n; ++k) g->total_comp_cost += bound2[k] - bound1[k];  // :320: the reference's counter counts every request
 
   // The memo: only intervals not seen before (and once each) go to the device.  ECCKD_NO_ERROR_MEMO (read per call): every
@@ -2972,10 +2916,7 @@ int ecckd_calc_error_multi(ecckd_gas* g, int n, const size_t* ibegin_k, const si
   std::vector<int> slot(n, -1);            // index into todo, or -1: served from the memo
   std::unordered_map<IntervalKey, int, IntervalKeyHash> in_batch;
   for (int k = 0; k < n; ++k) {
-    IntervalKey key;
-    key.i1 = iv[k].i1; key.i2 = iv[k].i2;
-    std::memcpy(&key.albedo_bits, &iv[k].albedo, sizeof(double));
-    if (!g->do_sw) key.albedo_bits = 0;
+    const IntervalKey key = interval_key(g, iv[k]);
     const double len = (double)(iv[k].i2 - iv[k].i1 + 1);
     g->memo_requests += 1;
     g->points_requested += len;
@@ -2996,13 +2937,7 @@ int ecckd_calc_error_multi(ecckd_gas* g, int n, const size_t* ibegin_k, const si
   for (int k = 0; k < n; ++k)
     if (slot[k] >= 0) error[k] = fresh[slot[k]];
   if (use_memo)
-    for (size_t t = 0; t < todo.size(); ++t) {
-      IntervalKey key;
-      key.i1 = todo[t].i1; key.i2 = todo[t].i2;
-      std::memcpy(&key.albedo_bits, &todo[t].albedo, sizeof(double));
-      if (!g->do_sw) key.albedo_bits = 0;
-      g->error_memo.emplace(key, fresh[t]);
-    }
+    for (size_t t = 0; t < todo.size(); ++t) g->error_memo.emplace(interval_key(g, todo[t]), fresh[t]);
   return ECCKD_OK;
 }
 

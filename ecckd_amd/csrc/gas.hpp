@@ -3,6 +3,7 @@
 #include "common.hpp"
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <unordered_map>
 #include <vector>
 
@@ -60,8 +61,7 @@ struct ecckd_gas {
   long long memo_requests = 0, memo_hits = 0;
   double points_requested = 0.0, points_evaluated = 0.0;
   // device arrays, all in sorted order
-  double* planck_hl = nullptr;  // [nlay+1][n]
-  bool owns_planck = true;
+  double* planck_hl = nullptr;  // [nlay+1][n]  its own, or the matrix of an earlier gas (then not among `blocks`)
   double* bg_od = nullptr;      // [nlay][n]
   float* bg_pair = nullptr;     // [nlay/2][n][2]  longwave, only if every background value is a float: layers 2p, 2p+1 of a point side by side
   double* w1 = nullptr;         // [nlay][n]  metric * weight          (log: log(metric)*weight)
@@ -106,5 +106,20 @@ struct ecckd_gas {
   // ecckd_find_g_gases lends one per gas for the length of the call
   ecckd_lane* lane = nullptr;
   hipStream_t eval_stream() const { return lane ? lane->stream : ctx->stream; }
+  // Every device block of this gas comes from alloc(), which records it; gas_free (find_g.hip) releases what is recorded,
+  // give_back() one block early.  The named members above are views for the launch sites.
+  std::vector<void*> blocks;
+  template <typename T> hipError_t alloc(T** p, size_t bytes) {
+    void* v = nullptr;
+    const hipError_t e = ecckd::dev_malloc(ctx, &v, bytes);
+    if (e == hipSuccess) blocks.push_back(v);
+    *p = (T*)v;
+    return e;
+  }
+  template <typename T> void give_back(T*& p) {
+    for (void*& b : blocks)
+      if (b && b == (void*)p) { ecckd::dev_release(ctx, b); b = blocks.back(); blocks.pop_back(); break; }
+    p = nullptr;
+  }
 };
 

@@ -399,9 +399,9 @@ int ecckd_nc_close(ecckd_nc* f) {
   int rc = ECCKD_OK;
   if (f->netcdf4) {
     if (f->defining) rc = ecckd::fail(ECCKD_PROCESSING_ERROR, "%s closed while still in define mode", f->path.c_str());
-    const int rc2 = ecckd::h5w_close(f->h5w);
+    const int close_rc = ecckd::h5w_close(f->h5w);
     delete f;
-    return rc != ECCKD_OK ? rc : rc2;
+    return rc != ECCKD_OK ? rc : close_rc;
   }
   if (f->writing && f->defining) rc = ecckd::fail(ECCKD_PROCESSING_ERROR, "%s closed while still in define mode", f->path.c_str());
   if (f->fp && std::fclose(f->fp) != 0) rc = ecckd::fail(ECCKD_PROCESSING_ERROR, "error closing %s", f->path.c_str());
