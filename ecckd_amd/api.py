@@ -1053,6 +1053,25 @@ def lbl_band_fluxes_lw(ctx, temperature_hl, wavenumber, d_wavenumber, optical_de
     return dn, up
 
 
+def lbl_spectral_fluxes_lw(ctx, temperature_hl, wavenumber, d_wavenumber, optical_depth):
+    """Line-by-line longwave spectral fluxes of one column (lw_spectra.cpp:222-237): device tensors in ->
+    (flux_dn, flux_up) FLOAT device tensors (nlay+1, nwav), (bb_dn, bb_up) host arrays (nlay+1,) summed in double."""
+    t = _f64c(temperature_hl)
+    nlay = t.size - 1
+    torch = _torch()
+    nwav = optical_depth.shape[1]
+    dn = torch.empty((nlay + 1, nwav), dtype=torch.float32, device=ctx.device)
+    up = torch.empty((nlay + 1, nwav), dtype=torch.float32, device=ctx.device)
+    bdn, bup = np.empty(nlay + 1), np.empty(nlay + 1)
+    stride = optical_depth.stride(0) if nlay > 1 else nwav
+    ctx.fence_from_torch()
+    check(ctx.lib.ecckd_lbl_spectral_fluxes_lw(ctx.handle, nlay, nwav, _hptr(t), _dptr(wavenumber), _dptr(d_wavenumber),
+                                               _dptr(optical_depth), _od_type(optical_depth), stride, _dptr(dn), _dptr(up),
+                                               nwav, _hptr(bdn), _hptr(bup)))
+    ctx.synchronize()
+    return dn, up, bdn, bup
+
+
 def gauss_legendre_01(n):
     """Nodes (ascending) and weights of the n-point Gauss-Legendre rule on (0, 1) (host only)."""
     from . import _lib
@@ -1159,6 +1178,19 @@ class GPointMap:
         check(self.lib.ecckd_gmap_sum_rows(self.handle, rows.shape[0], _dptr(rows), _od_type(rows), rows.stride(0),
                                            _hptr(out)))
         return out
+
+    def lbl_fluxes_lw(self, temperature_hl, optical_depth):
+        """Line-by-line longwave fluxes of one column per g point, fused (lw_spectra.cpp:222-257): device tensor optical_depth
+        (nlay, nwav) -> (flux_dn, flux_up) each (nlay+1, ng), (bb_dn, bb_up) each (nlay+1,): the sums over ALL wavenumbers."""
+        t = _f64c(temperature_hl)
+        nlay = t.size - 1
+        dn, up = np.empty((nlay + 1, self.ng)), np.empty((nlay + 1, self.ng))
+        bdn, bup = np.empty(nlay + 1), np.empty(nlay + 1)
+        stride = optical_depth.stride(0) if nlay > 1 else self.nwav
+        self.ctx.fence_from_torch()
+        check(self.lib.ecckd_lbl_gpoint_fluxes_lw(self.handle, nlay, _hptr(t), _dptr(optical_depth), _od_type(optical_depth),
+                                                  stride, _hptr(dn), _hptr(up), _hptr(bdn), _hptr(bup)))
+        return dn, up, bdn, bup
 
     def erythemal_spectrum(self):
         """sqrt(erythemal action spectrum) per g point, 5777 K Planck weighted (lbl_fluxes.cpp:198-230)."""

@@ -17,6 +17,7 @@
 // an (nlay, nwav) matrix: 8 B/point/layer of HBM traffic traded for one exp.
 #include "common.hpp"
 #include "fastmath.hpp"
+#include "gmap.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -52,7 +53,7 @@ __device__ __forceinline__ double wave_max(double v) {
   return v;
 }
 
-struct Chunk { long long p0, p1; int g; int pad; };
+using Chunk = ecckd::GmapChunk;
 
 __global__ void __launch_bounds__(256)
 k_gmap_keys(size_t n, const int32_t* __restrict__ g_point, int ng, double* __restrict__ key, int* __restrict__ counts,
@@ -415,30 +416,12 @@ k_width_totals(int ng, int nint, const int* __restrict__ seg_chunk0, const doubl
 
 }  // namespace
 
-struct ecckd_gmap {
-  ecckd_ctx* ctx = nullptr;
-  size_t n = 0;          // wavenumbers
-  size_t nassigned = 0;  // with g >= 0
-  int ng = 0;
-  int32_t* order = nullptr;   // [n] original index of each sorted position
-  double* wn_s = nullptr;     // [n]
-  double* dwn_s = nullptr;    // [n]
-  std::vector<long long> seg_begin;  // [ng+1] in sorted positions
-  std::vector<Chunk> chunks;
-  std::vector<int> seg_chunk0;       // [ng+1]
-  Chunk* d_chunks = nullptr;
-  int* d_seg_chunk0 = nullptr;
-  long long* d_seg_count = nullptr;
-  long long* d_seg_begin = nullptr;
-  void* work = nullptr;
-  size_t work_bytes = 0;
-};
-
 namespace {
 void gmap_free(ecckd_gmap* m) {
   if (!m) return;
   if (m->ctx) (void)hipStreamSynchronize(m->ctx->stream);
-  void* ptrs[] = {m->order, m->wn_s, m->dwn_s, m->d_chunks, m->d_seg_chunk0, m->d_seg_count, m->d_seg_begin, m->work};
+  void* ptrs[] = {m->order, m->wn_s, m->dwn_s, m->d_chunks, m->d_seg_chunk0, m->d_seg_count, m->d_seg_begin, m->work,
+                  m->nat_g, m->nat_wn, m->nat_dwn};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete m;
@@ -450,7 +433,52 @@ int gmap_work(ecckd_gmap* m, size_t bytes) {
   m->work_bytes = bytes;
   return ECCKD_OK;
 }
+// the map back in wavenumber order: sorted position i holds wavenumber order[i]; its g point is the segment i lies in
+__global__ void __launch_bounds__(256)
+k_gmap_unsort(size_t n, size_t nassigned, int ng, const long long* __restrict__ seg_begin, const int32_t* __restrict__ order,
+              const double* __restrict__ wn_s, const double* __restrict__ dwn_s, int32_t* __restrict__ g_point,
+              double* __restrict__ wn, double* __restrict__ dwn) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int g = -1;
+  if (i < nassigned) {
+    int lo = 0, hi = ng;                       // the last g with seg_begin[g] <= i (empty g points share their begin with the next)
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (seg_begin[mid] <= (long long)i) lo = mid; else hi = mid; }
+    g = lo;
+  }
+  const size_t j = (size_t)order[i];
+  g_point[j] = g;
+  wn[j] = wn_s[i];
+  dwn[j] = dwn_s[i];
+}
 }  // namespace
+
+int ecckd::gmap_natural(ecckd_gmap* m, const int32_t** d_g_point, const double** d_wavenumber, const double** d_d_wavenumber) {
+  if (!m->nat_g) {
+    ecckd_ctx* ctx = m->ctx;
+    ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
+    // allocated into locals and published together: a failure on the way leaves the map as it was
+    int32_t* g = nullptr; double* wn = nullptr; double* dwn = nullptr;
+    hipError_t e = hipMalloc((void**)&g, m->n * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&wn, m->n * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&dwn, m->n * sizeof(double));
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(k_gmap_unsort, dim3((unsigned)((m->n + 255) / 256)), dim3(256), 0, ctx->stream, m->n, m->nassigned, m->ng,
+                         m->d_seg_begin, m->order, m->wn_s, m->dwn_s, g, wn, dwn);
+      e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+      if (g) (void)hipFree(g);
+      if (wn) (void)hipFree(wn);
+      if (dwn) (void)hipFree(dwn);
+      return ecckd::fail(e == hipErrorOutOfMemory ? ECCKD_OUT_OF_MEMORY : ECCKD_UNEXPECTED_EXCEPTION,
+                         "the g-point map in wavenumber order: %s", hipGetErrorString(e));
+    }
+    m->nat_g = g; m->nat_wn = wn; m->nat_dwn = dwn;
+  }
+  *d_g_point = m->nat_g; *d_wavenumber = m->nat_wn; *d_d_wavenumber = m->nat_dwn;
+  return ECCKD_OK;
+}
 
 extern "C" {
 

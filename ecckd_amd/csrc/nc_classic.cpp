@@ -18,6 +18,7 @@
 #include "nc_hdf5.hpp"
 #include "nc_classic.hpp"
 
+#include <sys/stat.h>
 #include <algorithm>
 #include <cctype>
 #include <cstdint>
@@ -329,7 +330,7 @@ void put_atts(std::vector<unsigned char>& b, int version, const std::vector<Att>
 }
 std::vector<unsigned char> build_header(const ecckd_nc* f) {
   std::vector<unsigned char> b = {'C', 'D', 'F', (unsigned char)f->version};
-  put_count(b, f->version, 0);   // numrecs: no record variables are written
+  put_count(b, f->version, f->numrecs);   // 0 until a record is written (ecckd_nc_write_slice_double rewrites this field)
   if (f->dims.empty()) { put_u32(b, 0); put_count(b, f->version, 0); }
   else {
     put_u32(b, TAG_DIM);
@@ -623,7 +624,11 @@ int ecckd_nc_create(const char* path, ecckd_nc** out) {
 }
 
 int ecckd_nc_def_dim(ecckd_nc* f, const char* name, size_t len, int* dimid) {
-  ECCKD_REQUIRE(f && f->defining && name && len > 0, "ecckd_nc_def_dim: bad argument (record dimensions are not written)");
+  ECCKD_REQUIRE(f && f->defining && name, "ecckd_nc_def_dim: bad argument");
+  // len = 0: the unlimited (record) dimension; the classic format has at most one
+  if (len == 0) {
+    for (const Dim& e : f->dims) ECCKD_REQUIRE(e.len != 0, "ecckd_nc_def_dim: a second unlimited dimension (\"%s\")", name);
+  }
   Dim d;
   d.name = name;
   d.len = len;
@@ -639,8 +644,10 @@ int ecckd_nc_def_var(ecckd_nc* f, const char* name, int nc_type, int ndims, cons
   v.type = nc_type;
   for (int k = 0; k < ndims; ++k) {
     ECCKD_REQUIRE(dimids[k] >= 0 && dimids[k] < (int)f->dims.size(), "ecckd_nc_def_var: bad dimension id %d", dimids[k]);
+    ECCKD_REQUIRE(k == 0 || f->dims[dimids[k]].len != 0, "ecckd_nc_def_var: the unlimited dimension must be the slowest of \"%s\"", name);
     v.dimids.push_back(dimids[k]);
   }
+  v.record = ndims > 0 && f->dims[dimids[0]].len == 0;
   f->vars.push_back(v);
   if (varid) *varid = (int)f->vars.size() - 1;
   return ECCKD_OK;
@@ -718,13 +725,14 @@ int ecckd_nc_enddef(ecckd_nc* f) {
     f->defining = false;
     return ECCKD_OK;
   }
-  // sizes first: they decide the format variant (CDF-1: every offset < 2 GiB; CDF-2: every variable < 4 GiB; else CDF-5)
+  // sizes first: they decide the format variant (CDF-1: every offset < 2 GiB - the record variables begin inside the first record,
+  // so one whole record counts; CDF-2: every variable / record of a variable < 4 GiB; else CDF-5)
   uint64_t data_bytes = 0, max_var = 0;
   for (Var& v : f->vars) {
     uint64_t nel = 1;
-    for (int id : v.dimids) nel *= f->dims[id].len;
+    for (size_t k = v.record ? 1 : 0; k < v.dimids.size(); ++k) nel *= f->dims[v.dimids[k]].len;   // a record variable: one record
     v.vsize = pad4(nel * type_size(v.type));
-    data_bytes += v.vsize;
+    data_bytes += v.vsize;          // fixed-size data and ONE record: every `begin` of the header lies below their sum
     max_var = std::max(max_var, v.vsize);
   }
   bool big_dim = false;
@@ -736,7 +744,21 @@ int ecckd_nc_enddef(ecckd_nc* f) {
     if (version == 2 && max_var < ((uint64_t)1 << 32) - 4 && !big_dim) break;
   }
   uint64_t off = build_header(f).size();
-  for (Var& v : f->vars) { v.begin = off; off += v.vsize; }
+  for (Var& v : f->vars) if (!v.record) { v.begin = off; off += v.vsize; }
+  // the record variables follow the fixed-size ones: record r of variable v at v.begin + r * recsize, recsize = the sum of the
+  // record variables' (padded) sizes; a single record variable is stored without padding between its records
+  size_t nrecvar = 0;
+  for (const Var& v : f->vars) nrecvar += v.record ? 1 : 0;
+  f->recsize = 0;
+  uint64_t rec_off = off;
+  for (Var& v : f->vars) if (v.record) {
+    v.begin = rec_off;
+    uint64_t one = v.vsize;
+    if (nrecvar == 1) { one = type_size(v.type); for (size_t k = 1; k < v.dimids.size(); ++k) one *= f->dims[v.dimids[k]].len; }
+    rec_off += one;
+    f->recsize += one;
+  }
+  f->numrecs = 0;
   const std::vector<unsigned char> hdr = build_header(f);
   if (std::fwrite(hdr.data(), 1, hdr.size(), f->fp) != hdr.size()) return ecckd::fail(ECCKD_PROCESSING_ERROR, "%s: header write failed", f->path.c_str());
   // reserve the data section so that unwritten variables read back as zeros
@@ -793,6 +815,31 @@ int write_values(ecckd_nc* f, const Var& v, const char* name, uint64_t at, const
   if (!ok) return ecckd::fail(ECCKD_PROCESSING_ERROR, "%s: short write of \"%s\"", f->path.c_str(), name);
   return ECCKD_OK;
 }
+// record `rec` of a record variable; numrecs (header bytes 4..) follows the highest record written, and the file is extended to
+// whole records so that the other record variables of a new record read back as zeros until they are written
+int write_record(ecckd_nc* f, const Var& v, const char* name, size_t rec, const double* data, size_t count) {
+  uint64_t per = 1;
+  for (size_t k = 1; k < v.dimids.size(); ++k) per *= f->dims[v.dimids[k]].len;
+  ECCKD_REQUIRE(count == per, "ecckd_nc_write_slice_double: \"%s\" has %llu values per record, %zu given", name, (unsigned long long)per, count);
+  ECCKD_REQUIRE(f->version == 5 || rec < 0xFFFFFFFFull, "ecckd_nc_write_slice_double: record %zu does not fit the format", rec);
+  ECCKD_CHECK(write_values(f, v, name, v.begin + (uint64_t)rec * f->recsize, data, count));
+  if (rec + 1 > f->numrecs) {
+    f->numrecs = rec + 1;
+    uint64_t first = UINT64_MAX;
+    for (const Var& o : f->vars) if (o.record) first = std::min(first, o.begin);
+    const uint64_t end = first + f->numrecs * f->recsize;
+    const int fd = ::fileno(f->fp);
+    struct stat st;
+    unsigned char be[8];
+    const size_t nb = f->version == 5 ? 8 : 4;
+    for (size_t i = 0; i < nb; ++i) be[i] = (unsigned char)(f->numrecs >> (8 * (nb - 1 - i)));
+    const unsigned char zero = 0;
+    if (::fstat(fd, &st) != 0 || ((uint64_t)st.st_size < end && ::pwrite(fd, &zero, 1, (off_t)(end - 1)) != 1) ||
+        ::pwrite(fd, be, nb, 4) != (ssize_t)nb)
+      return ecckd::fail(ECCKD_PROCESSING_ERROR, "%s: cannot extend to %llu records", f->path.c_str(), (unsigned long long)f->numrecs);
+  }
+  return ECCKD_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -803,23 +850,26 @@ int ecckd_nc_write_double(ecckd_nc* f, const char* name, const double* data, siz
   if (!v) return ecckd::fail(ECCKD_PARAMETER_ERROR, "%s: no variable \"%s\"", f->path.c_str(), name);
   uint64_t nel = 1;
   for (int id : v->dimids) nel *= f->dims[id].len;
+  ECCKD_REQUIRE(!v->record, "ecckd_nc_write_double: \"%s\" is a record variable (write it record by record)", name);
   ECCKD_REQUIRE(count == nel, "ecckd_nc_write_double: \"%s\" has %llu elements, %zu given", name, (unsigned long long)nel, count);
   if (f->netcdf4) return ecckd::h5w_write(f->h5w, (int)(v - f->vars.data()), -1, data, count);
   return write_values(f, *v, name, v->begin, data, count);
 }
 
-// one index of the slowest dimension of a (fixed-size) variable: what lets a tool write a (column, level, wavenumber)
+// one index of the slowest dimension of a variable (for a record variable: one record; a record past the last one extends the
+// record count, and the records in between read back as zeros): what lets a tool write a (column, level, wavenumber)
 // matrix column by column without holding all columns
 int ecckd_nc_write_slice_double(ecckd_nc* f, const char* name, size_t slice, const double* data, size_t count) {
   ECCKD_REQUIRE(f && f->writing && !f->defining && name && data, "ecckd_nc_write_slice_double: bad argument or still in define mode");
   const Var* v = f->find(name);
   if (!v) return ecckd::fail(ECCKD_PARAMETER_ERROR, "%s: no variable \"%s\"", f->path.c_str(), name);
-  ECCKD_REQUIRE(!v->dimids.empty() && !v->record, "ecckd_nc_write_slice_double: \"%s\" is a scalar or a record variable", name);
+  ECCKD_REQUIRE(!v->dimids.empty(), "ecckd_nc_write_slice_double: \"%s\" is a scalar", name);
   uint64_t per = 1;
   for (size_t k = 1; k < v->dimids.size(); ++k) per *= f->dims[v->dimids[k]].len;
-  ECCKD_REQUIRE(slice < f->dims[v->dimids[0]].len && count == per, "ecckd_nc_write_slice_double: \"%s\" slice %zu / %zu values do not fit",
+  ECCKD_REQUIRE((v->record || slice < f->dims[v->dimids[0]].len) && count == per, "ecckd_nc_write_slice_double: \"%s\" slice %zu / %zu values do not fit",
                 name, slice, count);
   if (f->netcdf4) return ecckd::h5w_write(f->h5w, (int)(v - f->vars.data()), (long long)slice, data, count);
+  if (v->record) return write_record(f, *v, name, slice, data, count);
   return write_values(f, *v, name, v->begin + (uint64_t)slice * per * type_size(v->type), data, count);
 }
 

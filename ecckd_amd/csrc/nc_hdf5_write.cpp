@@ -74,6 +74,7 @@ struct WApi {
   herr_t (*H5Aclose)(hid_t);
   int (*H5Zfilter_avail)(int);
   herr_t (*H5Dwrite_chunk)(hid_t, hid_t, unsigned, const hsize_t*, size_t, const void*) = nullptr;   // 1.10.3 on
+  herr_t (*H5Dset_extent)(hid_t, const hsize_t*) = nullptr;   // the unlimited dimension
   int (*z_compress2)(unsigned char*, unsigned long*, const unsigned char*, unsigned long, int) = nullptr;
   unsigned long (*z_compressBound)(unsigned long) = nullptr;
   herr_t (*H5DSset_scale)(hid_t, const char*);
@@ -137,6 +138,7 @@ WApi& wapi() {
     if (!ids) return;
     if (a.H5Zfilter_avail(1) <= 0) { a.why = "this HDF5 library has no deflate filter"; return; }
     a.H5Dwrite_chunk = reinterpret_cast<decltype(a.H5Dwrite_chunk)>(dlsym(a.lib, "H5Dwrite_chunk"));
+    a.H5Dset_extent = reinterpret_cast<decltype(a.H5Dset_extent)>(dlsym(a.lib, "H5Dset_extent"));
     for (const char* zn : {"libz.so.1", "libz.so", "/opt/conda/lib/libz.so.1"}) {
       if (void* z = dlopen(zn, RTLD_NOW | RTLD_LOCAL)) {
         a.z_compress2 = reinterpret_cast<decltype(a.z_compress2)>(dlsym(z, "compress2"));
@@ -152,6 +154,8 @@ WApi& wapi() {
 
 enum { NC_BYTE = 1, NC_CHAR = 2, NC_SHORT = 3, NC_INT = 4, NC_FLOAT = 5, NC_DOUBLE = 6, NC_UBYTE = 7 };
 constexpr hsize_t kChunkValues = (hsize_t)1 << 18;      // values per chunk of a deflated variable (along its last dimension)
+constexpr hsize_t kUnlimited = ~(hsize_t)0;              // H5S_UNLIMITED
+constexpr hsize_t kRecordChunkBytes = (hsize_t)1 << 26; // a record variable that is not deflated: chunks of at most 64 MB
 
 size_t file_type_size(int nc_type) {
   switch (nc_type) {
@@ -234,6 +238,11 @@ struct H5Writer {
   std::vector<hid_t> dimonly_ids;
   std::vector<H5WVar> vars;
   std::vector<H5WDim> dims;
+  // the unlimited dimension (a dimension of length 0, at most one, the slowest of its variables): its present length, the
+  // index of its scale dataset in dimonly_ids (-1: a coordinate variable is the scale)
+  int unlimited = -1;
+  hsize_t numrecs = 0;
+  hid_t unlimited_scale = -1;
   // deflated variables on their way through the worker threads (queue_deflated_chunks)
   struct Chunk {
     int var = 0;
@@ -273,6 +282,8 @@ int h5w_create(const char* path, const std::vector<H5WDim>& dims, const std::vec
   w->vars = vars;
   w->dims = dims;
   int rc = ECCKD_OK;
+  for (size_t k = 0; k < dims.size(); ++k) if (dims[k].len == 0) w->unlimited = (int)k;
+  if (w->unlimited >= 0 && !a.H5Dset_extent) { h5w_close(w); return fail(ECCKD_PROCESSING_ERROR, "%s: this HDF5 library cannot extend a dataset (H5Dset_extent)", path); }
   // the coordinate variable of a dimension: the 1-D variable of its name over it
   std::vector<int> coord(dims.size(), -1);
   for (size_t v = 0; v < vars.size(); ++v)
@@ -282,11 +293,25 @@ int h5w_create(const char* path, const std::vector<H5WDim>& dims, const std::vec
     const H5WVar& var = vars[v];
     const int nd = (int)var.dimids.size();
     hsize_t shape[32], chunk[32];
-    for (int k = 0; k < nd; ++k) { shape[k] = dims[var.dimids[k]].len; chunk[k] = 1; }
-    const hid_t space = nd == 0 ? a.H5Screate(0) : a.H5Screate_simple(nd, shape, nullptr);
+    hsize_t maxshape[32];
+    for (int k = 0; k < nd; ++k) { shape[k] = dims[var.dimids[k]].len; maxshape[k] = shape[k]; chunk[k] = 1; }
+    // a record variable: no records yet, unlimited along the slowest dimension, chunked (the library lays out nothing else
+    // that can grow) - one record per chunk, cut along the faster dimensions where a record is larger than kRecordChunkBytes
+    const bool record = nd > 0 && dims[var.dimids[0]].len == 0;
+    if (record) maxshape[0] = kUnlimited;
+    const hid_t space = nd == 0 ? a.H5Screate(0) : a.H5Screate_simple(nd, shape, record ? maxshape : nullptr);
     const hid_t dcpl = a.H5Pcreate(a.p_dataset_create);
     a.H5Pset_attr_creation_order(dcpl, order);
-    if (var.deflate && nd > 0) {
+    if (record && !(var.deflate && nd > 1)) {
+      hsize_t bytes = file_type_size(var.nc_type);
+      for (int k = nd - 1; k >= 1; --k) {
+        const hsize_t room = std::max<hsize_t>(1, kRecordChunkBytes / bytes);
+        chunk[k] = std::min<hsize_t>(shape[k], room);
+        bytes *= chunk[k];
+      }
+      a.H5Pset_chunk(dcpl, nd, chunk);
+      if (var.deflate) { a.H5Pset_shuffle(dcpl); a.H5Pset_deflate(dcpl, 2); }
+    } else if (var.deflate && nd > 0) {
       chunk[nd - 1] = shape[nd - 1] < kChunkValues ? shape[nd - 1] : kChunkValues;
       a.H5Pset_chunk(dcpl, nd, chunk);
       a.H5Pset_shuffle(dcpl);
@@ -316,15 +341,17 @@ int h5w_create(const char* path, const std::vector<H5WDim>& dims, const std::vec
       if (a.H5DSset_scale(scale[k], dims[k].name.c_str()) < 0) rc = fail(ECCKD_PROCESSING_ERROR, "%s: dimension scale \"%s\"", path, dims[k].name.c_str());
     } else {
       const hsize_t len = dims[k].len;
-      const hid_t space = a.H5Screate_simple(1, &len, nullptr);
+      const hid_t space = a.H5Screate_simple(1, &len, len == 0 ? &kUnlimited : nullptr);
       const hid_t dcpl = a.H5Pcreate(a.p_dataset_create);
       a.H5Pset_attr_creation_order(dcpl, order);
+      if (len == 0) { const hsize_t one_k = 1024; a.H5Pset_chunk(dcpl, 1, &one_k); }
       const hid_t d = a.H5Dcreate2(file, dims[k].name.c_str(), a.t_f32be, space, 0, dcpl, 0);
       a.H5Pclose(dcpl);
       a.H5Sclose(space);
       if (d < 0) { rc = fail(ECCKD_PROCESSING_ERROR, "%s: dimension \"%s\" could not be created", path, dims[k].name.c_str()); break; }
       w->dimonly_ids.push_back(d);
       scale[k] = d;
+      if (len == 0) w->unlimited_scale = d;
       char name[96];
       std::snprintf(name, sizeof name, "This is a netCDF dimension but not a netCDF variable.%10d", (int)len);
       if (a.H5DSset_scale(d, name) < 0) rc = fail(ECCKD_PROCESSING_ERROR, "%s: dimension scale \"%s\"", path, dims[k].name.c_str());
@@ -455,6 +482,7 @@ int queue_deflated_chunks(WApi& a, H5Writer* w, int varindex, size_t row0, const
     size_t row = row0 + c / per_row;
     for (int k = nd - 2; k >= 0; --k) {
       const size_t len = w->dims[var.dimids[k]].len;
+      if (len == 0) { ch.offset[k] = row; break; }      // the unlimited dimension (k = 0): the record itself
       ch.offset[k] = row % len;
       row /= len;
     }
@@ -485,7 +513,26 @@ int h5w_write(H5Writer* w, int varindex, long long slice, const double* data, si
   const hid_t d = w->var_ids[varindex];
   const int nd = (int)var.dimids.size();
   herr_t e;
-  if (var.deflate && nd > 0) {
+  const bool record = nd > 0 && w->dims[var.dimids[0]].len == 0;
+  if (record) {
+    // one record; a record past the last one extends every record variable and the dimension's scale (unwritten chunks read
+    // back as the fill value, zero)
+    if (slice < 0) return fail(ECCKD_PARAMETER_ERROR, "%s: \"%s\" is a record variable (write it record by record)", w->path.c_str(), var.name.c_str());
+    if ((hsize_t)slice + 1 > w->numrecs) {
+      w->numrecs = (hsize_t)slice + 1;
+      for (size_t v = 0; v < w->vars.size(); ++v) {
+        const H5WVar& o = w->vars[v];
+        if (o.dimids.empty() || o.dimids[0] != w->unlimited) continue;
+        hsize_t ext[32];
+        for (size_t k = 0; k < o.dimids.size(); ++k) ext[k] = w->dims[o.dimids[k]].len;
+        ext[0] = w->numrecs;
+        if (a.H5Dset_extent(w->var_ids[v], ext) < 0) return fail(ECCKD_PROCESSING_ERROR, "%s: \"%s\" could not be extended to %llu records", w->path.c_str(), o.name.c_str(), w->numrecs);
+      }
+      if (w->unlimited_scale >= 0 && a.H5Dset_extent(w->unlimited_scale, &w->numrecs) < 0)
+        return fail(ECCKD_PROCESSING_ERROR, "%s: the unlimited dimension could not be extended", w->path.c_str());
+    }
+  }
+  if (var.deflate && nd > (record ? 1 : 0)) {
     size_t rows_per_slice = 1;
     for (int k = 1; k + 1 < nd; ++k) rows_per_slice *= w->dims[var.dimids[k]].len;
     const int rc = queue_deflated_chunks(a, w, varindex, slice < 0 || nd == 1 ? 0 : (size_t)slice * rows_per_slice, data, count);
@@ -508,6 +555,7 @@ int h5w_write(H5Writer* w, int varindex, long long slice, const double* data, si
   } else {
     hsize_t shape[32], start[32], cnt[32];
     for (int k = 0; k < nd; ++k) { shape[k] = w->dims[var.dimids[k]].len; start[k] = 0; cnt[k] = shape[k]; }
+    if (record) shape[0] = w->numrecs;
     start[0] = (hsize_t)slice;
     cnt[0] = 1;
     const hid_t fsp = a.H5Screate_simple(nd, shape, nullptr);

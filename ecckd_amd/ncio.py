@@ -580,3 +580,80 @@ def read_g_points(path):
                     wavenumber=f.read("wavenumber"), wavenumber1_band=f.read("wavenumber1_band"),
                     wavenumber2_band=f.read("wavenumber2_band"),
                     solar_irradiance=f.read("solar_irradiance") if f.exist("solar_irradiance") else None)
+
+
+def write_merged_spectra(path, m, config_str="", history=None):
+    """The file of merge_spectra (merge_spectra.cpp:84-156): `m` as pipeline.merge_spectra returns it."""
+    ncol, nlay, nwav = m["optical_depth"].shape
+    w = NcWriter(path)
+    for name, n in (("column", ncol), ("level", nlay), ("half_level", nlay + 1), ("wavenumber", nwav)):
+        w.define_dimension(name, n)
+    for name, long_name, units in (("pressure_hl", "Pressure at half levels", "Pa"), ("temperature_hl", "Temperature at half levels", "K")):
+        w.define_variable(name, "float", "column", "half_level")
+        w.write_attribute("long_name", long_name, var=name)
+        w.write_attribute("units", units, var=name)
+    w.define_variable("wavenumber", "double", "wavenumber")
+    w.deflate_variable("wavenumber")
+    w.write_attribute("long_name", "Wavenumber", var="wavenumber")
+    w.write_attribute("units", "cm-1", var="wavenumber")
+    w.define_variable("optical_depth", "float", "column", "level", "wavenumber")
+    w.deflate_variable("optical_depth")
+    w.write_attribute("long_name", "Layer optical depth", var="optical_depth")
+    w.write_attribute("title", "Merged spectral optical depth profiles of " + m["molecules"].upper().replace(",", ", "))
+    w.write_attribute("molecule", "hybrid:" + m["molecules"])
+    w.write_attribute("history", history or "")
+    w.write_attribute("config", config_str)
+    w.end_define_mode()
+    w.write("wavenumber", m["wavenumber"])
+    for c in range(ncol):
+        w.write_slice("pressure_hl", c, m["pressure_hl"][c])
+        w.write_slice("temperature_hl", c, m["temperature_hl"][c])
+        w.write_slice("optical_depth", c, m["optical_depth"][c])
+    w.close()
+
+
+def write_lw_spectra(path, s, config_str="", history=None):
+    """The file of lw_spectra (lw_spectra.cpp:127-261): `s` as pipeline.lw_spectra returns it; `column` unlimited."""
+    nrec, nlay = s["optical_depth"].shape[:2]
+    have_g = s["ng"] > 0
+    spec = "g_point" if have_g else "wavenumber"
+    w = NcWriter(path)
+    w.define_dimension("column", 0)
+    w.define_dimension("level", nlay)
+    w.define_dimension("half_level", nlay + 1)
+    w.define_dimension(spec, s["optical_depth"].shape[2])
+    w.define_dimension("gas", s["vmr_fl"].shape[1])
+
+    def var(name, dims, long_name, units=None):
+        w.define_variable(name, "float", *dims)
+        w.write_attribute("long_name", long_name, var=name)
+        if units:
+            w.write_attribute("units", units, var=name)
+    var("pressure_hl", ("column", "half_level"), "Pressure at half levels", "Pa")
+    var("temperature_hl", ("column", "half_level"), "Temperature at half levels", "K")
+    if not have_g:
+        w.define_variable("wavenumber", "double", "wavenumber")
+        w.deflate_variable("wavenumber")
+        w.write_attribute("long_name", "Wavenumber", var="wavenumber")
+        w.write_attribute("units", "cm-1", var="wavenumber")
+    var("vmr_fl", ("column", "gas", "level"), "Volume mixing ratio", "mol mol-1")
+    w.write_attribute("comment", 'The gases are listed in the global attribute "molecules".', var="vmr_fl")
+    var("flux_dn_lw", ("column", "half_level"), "Upwelling longwave flux", "W m-2")           # (sic, lw_spectra.cpp:169)
+    var("flux_up_lw", ("column", "half_level"), "Upwelling longwave flux", "W m-2")
+    w.define_variable("optical_depth", "float", "column", "level", spec)
+    if not have_g:
+        w.deflate_variable("optical_depth")
+    w.write_attribute("long_name", "Layer optical depth", var="optical_depth")
+    var("spectral_flux_dn_lw", ("column", "half_level", spec), "Downwelling longwave spectral flux", "W m-2")
+    var("spectral_flux_up_lw", ("column", "half_level", spec), "Upwelling longwave spectral flux", "W m-2")
+    w.write_attribute("history", history or "")
+    w.write_attribute("molecules", s["molecules"])
+    w.write_attribute("config", config_str)
+    w.end_define_mode()
+    if not have_g:
+        w.write("wavenumber", s["wavenumber"])
+    for r in range(nrec):
+        for name in ("pressure_hl", "temperature_hl", "vmr_fl", "flux_dn_lw", "flux_up_lw", "optical_depth", "spectral_flux_dn_lw",
+                     "spectral_flux_up_lw"):
+            w.write_slice(name, r, s[name][r])
+    w.close()

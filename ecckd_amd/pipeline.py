@@ -819,3 +819,104 @@ def _max_to_root(t, world_size, group=None):
 def _is_nccl(group=None):
     import torch.distributed as dist
     return dist.is_available() and dist.is_initialized() and dist.get_backend(group) == "nccl"
+
+
+def _read_merged_spectrum(ctx, inputs, scaling, conc, icol):
+    """read_merged_spectrum.cpp:20-185 as cli/tool.hpp::read_merged_spectrum does it (without a concentration file): every
+    file's optical depths to the device as stored, scaling rules on the host, sum on the device.  A single unscaled input
+    stays as stored (FLOAT).  -> (first spectrum dict, molecules, device optical depths, vmr rows)"""
+    import torch
+    first, molecules, merged, vmr = None, "", None, []
+    for ibg, path in enumerate(inputs):
+        s = ncio.read_spectrum(path, icol)
+        sc = scaling[ibg] if scaling is not None and ibg < len(scaling) else -1.0
+        cc = conc[ibg] if conc is not None and ibg < len(conc) else -1.0
+        if ibg == 0:
+            first, molecules = s, s["molecule"] or ""
+        else:
+            molecules += " " + (s["molecule"] or "")
+        sp, vrow = api.merge_scaling(first["pressure_hl"], sc, cc, s["reference_surface_vmr"], s["vmr_fl"])
+        vmr.append(vrow)
+        od = _to_device(s["optical_depth"], ctx.device)
+        if len(inputs) == 1 and np.all(sp == 1.0):
+            merged = od
+        else:
+            merged = api.merge_spectrum(ctx, od, sp, merged)
+    ctx.synchronize()
+    return first, molecules, merged, np.array(vmr)
+
+
+def merge_spectra(ctx, inputs, output_path=None, scaling=None, conc=None, config_str="", history=None):
+    """merge_spectra.cpp:27-170: the spectra of several gases merged column by column, as bin/merge_spectra does it.
+    -> dict(pressure_hl, temperature_hl (ncol, nlay+1), wavenumber, optical_depth (ncol, nlay, nwav) as the file's FLOATs,
+    molecules); written to output_path when given."""
+    out = {"pressure_hl": [], "temperature_hl": [], "optical_depth": []}
+    icol, ncol = 0, 1
+    while icol < ncol:
+        first, molecules, merged, _ = _read_merged_spectrum(ctx, inputs, scaling, conc, icol)
+        ncol = first["ncol"]
+        out["pressure_hl"].append(first["pressure_hl"])
+        out["temperature_hl"].append(first["temperature_hl"])
+        out["optical_depth"].append(merged.cpu().numpy().astype(np.float32))
+        out["wavenumber"], out["molecules"] = first["wavenumber_cm_1"], molecules
+        icol += 1
+    for k in ("pressure_hl", "temperature_hl", "optical_depth"):
+        out[k] = np.stack(out[k])
+    if output_path is not None:
+        ncio.write_merged_spectra(output_path, out, config_str=config_str, history=history)
+    return out
+
+
+def lw_spectra(ctx, inputs, output_path=None, scaling=None, conc=None, g_point=None, iprofile=None, config_str="", history=None):
+    """lw_spectra.cpp:31-275 as bin/lw_spectra does it: per column the merged spectrum, then either the spectral fluxes
+    (ecckd_lbl_spectral_fluxes_lw) or, with g_point (one value per wavenumber, -1 = none), the fluxes per g point
+    (ecckd_lbl_gpoint_fluxes_lw) and the optical depth averaged by transmission with the Planck weight at the pressure-weighted
+    full-level temperature (ecckd_average_to_gpoints, reference_surface_vmr = 0).  Arrays are returned in double as the library
+    gives them (the tool's file holds their FLOAT casts): dict of (nrec, ...) arrays; written to output_path when given."""
+    import torch
+    names = ("pressure_hl", "temperature_hl", "vmr_fl", "flux_dn_lw", "flux_up_lw", "optical_depth", "spectral_flux_dn_lw",
+             "spectral_flux_up_lw")
+    out = {k: [] for k in names}
+    have_g = g_point is not None
+    ng = int(np.max(g_point)) + 1 if have_g else -1
+    icol = iprofile if iprofile is not None else 0
+    ncol, gm, d_wn, d_dwn = 10000, None, None, None
+    while icol < ncol:
+        first, molecules, od, vmr = _read_merged_spectrum(ctx, inputs, scaling, conc, icol)
+        ncol = first["ncol"]
+        p, t = first["pressure_hl"], first["temperature_hl"]
+        if d_wn is None:
+            d_wn = torch.as_tensor(first["wavenumber_cm_1"], device=ctx.device)
+            d_dwn = torch.as_tensor(first["d_wavenumber_cm_1"], device=ctx.device)
+            if have_g:
+                gm = api.GPointMap(ctx, torch.as_tensor(np.ascontiguousarray(g_point, dtype=np.int32), device=ctx.device), ng, d_wn, d_dwn)
+            out["wavenumber"], out["molecules"] = first["wavenumber_cm_1"], molecules.replace(",", " ")
+        out["pressure_hl"].append(p)
+        out["temperature_hl"].append(t)
+        out["vmr_fl"].append(vmr)
+        if not have_g:
+            sdn, sup, bdn, bup = api.lbl_spectral_fluxes_lw(ctx, t, d_wn, d_dwn, od)
+            out["optical_depth"].append(od.cpu().numpy().astype(np.float64))
+            out["spectral_flux_dn_lw"].append(sdn.cpu().numpy().astype(np.float64))
+            out["spectral_flux_up_lw"].append(sup.cpu().numpy().astype(np.float64))
+        else:
+            dn, up, bdn, bup = gm.lbl_fluxes_lw(t, od)
+            p_fl = 0.5 * (p[:-1] + p[1:])
+            t_fl = 0.5 * (t[:-1] * p[:-1] + t[1:] * p[1:]) / p_fl                              # :242-244
+            od_g, _, _ = gm.average_optical_depth(p, od, "transmission", 0.0, temperature_fl=t_fl)
+            out["optical_depth"].append(od_g)
+            out["spectral_flux_dn_lw"].append(dn)
+            out["spectral_flux_up_lw"].append(up)
+        out["flux_dn_lw"].append(bdn)
+        out["flux_up_lw"].append(bup)
+        if iprofile is not None:
+            break
+        icol += 1
+    if gm is not None:
+        gm.close()
+    for k in names:
+        out[k] = np.stack(out[k])
+    out["ng"] = ng
+    if output_path is not None:
+        ncio.write_lw_spectra(output_path, out, config_str=config_str, history=history)
+    return out

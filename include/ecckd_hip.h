@@ -510,7 +510,11 @@ int ecckd_nc_deflate_var(ecckd_nc* file, const char* name);
 int ecckd_nc_is_netcdf4(ecckd_nc* file, int* is_netcdf4);
 int ecckd_nc_enddef(ecckd_nc* file);
 int ecckd_nc_write_double(ecckd_nc* file, const char* name, const double* data, size_t count);
-/* one index of the slowest dimension of a fixed-size variable (count = the elements below that dimension) */
+/* one index of the slowest dimension of a variable (count = the elements below that dimension).  A dimension defined with
+ * length 0 is the unlimited (record) dimension of a classic file - at most one, the slowest dimension of its variables; such
+ * variables are written record by record through this call, a record past the last one extends the record count (records in
+ * between and the other record variables of a new record read back as zeros).  In NetCDF-4 output the same calls make chunked
+ * datasets with an unlimited first dimension that are extended record by record. */
 int ecckd_nc_write_slice_double(ecckd_nc* file, const char* name, size_t slice, const double* data, size_t count);
 /* write_order (write_order.cpp:24-143): same variables, external types and attributes; `history` is the
  * line OutputDataFile::append_history would add (may be NULL); column_optical_depth may be NULL (:88). */
@@ -739,6 +743,24 @@ int ecckd_average_to_gpoints(ecckd_gmap* gmap, int nlay, const double* h_pressur
 /* h_sums[nrows][ng] = sum over the wavenumbers of each g point of d_rows[r][.] (scale_lut.cpp:119-124) */
 int ecckd_gmap_sum_rows(ecckd_gmap* gmap, int nrows, const void* d_rows, int rows_type, size_t row_stride,
                         double* h_sums);
+/* Line-by-line longwave fluxes of one column resolved per g point (lw_spectra.cpp:222-257): planck_function
+ * (planck_function.cpp:22-54) + radiative_transfer_lw (radiative_transfer_lw.cpp:27-60, unit surface emissivity, surface
+ * Planck function at temperature_hl(end), diffusivity 1.66 - the arithmetic of ecckd_lbl_band_fluxes_lw) and, in the same pass
+ * over the optical depths, h_flux_*[nlay+1][ng] = the sum of the spectral flux at each half level over the wavenumbers of each
+ * g point (exactly 0 for a g point without wavenumbers); h_bb_*[nlay+1] (may be NULL) = the sum over ALL wavenumbers, those
+ * with g_point = -1 included.  No (nlay+1) x nwav flux matrix is formed.  Bitwise reproducible.  The per-block accumulator
+ * (2 (nlay+1) x g points of doubles in 42 KB of LDS) bounds both entry points: nlay above 1 343 is refused with
+ * PARAMETER_ERROR, and a map with more g points than fit (47 at nlay = 54) is swept in ceil((ng + 1) / columns) launches, each
+ * repeating the radiative transfer. */
+int ecckd_lbl_gpoint_fluxes_lw(ecckd_gmap* gmap, int nlay, const double* h_temperature_hl, const void* d_od, int od_type,
+                               size_t od_stride, double* h_flux_dn, double* h_flux_up, double* h_bb_dn, double* h_bb_up);
+/* The same kernel's other output: the spectral fluxes themselves, d_flux_dn / d_flux_up[nlay+1][flux_stride] FLOAT device
+ * rows (what lw_spectra writes without g points, lw_spectra.cpp:236-237), and the broadband sums h_bb_*[nlay+1] (may be
+ * NULL) of the DOUBLE fluxes. */
+int ecckd_lbl_spectral_fluxes_lw(ecckd_ctx* ctx, int nlay, size_t nwav, const double* h_temperature_hl,
+                                 const double* d_wavenumber, const double* d_d_wavenumber, const void* d_od, int od_type,
+                                 size_t od_stride, float* d_flux_dn, float* d_flux_up, size_t flux_stride, double* h_bb_dn,
+                                 double* h_bb_up);
 /* LblFluxes::read, lbl_fluxes.cpp:198-230: the square root of the erythemal action spectrum (Webb et al.
  * 2011) averaged over each g point with a 5777 K Planck weight, h_erythemal[ng]; NaN for an empty g point
  * (0/0 as in the reference). */
