@@ -1103,6 +1103,26 @@ def lbl_band_fluxes_sw(ctx, cos_sza, ssi, optical_depth, band_begin, band_end, a
     return dn, up
 
 
+def lbl_spectral_fluxes_sw(ctx, cos_sza, ssi, optical_depth, albedo=None):
+    """Line-by-line shortwave spectral fluxes of one column for every solar zenith angle of cos_sza (a scalar is one angle):
+    device tensors ssi (nwav,), optical_depth (nlay, nwav), albedo (nwav,) or None (no upwelling sweep) ->
+    (flux_dn_direct, flux_up) FLOAT device tensors (nsza, nlay+1, nwav), (bb_dn, bb_up) host arrays (nsza, nlay+1) summed in
+    double."""
+    mu = _f64c(np.atleast_1d(cos_sza))
+    nlay, nwav = optical_depth.shape
+    torch = _torch()
+    dn = torch.empty((mu.size, nlay + 1, nwav), dtype=torch.float32, device=ctx.device)
+    up = torch.empty((mu.size, nlay + 1, nwav), dtype=torch.float32, device=ctx.device)
+    bdn, bup = np.empty((mu.size, nlay + 1)), np.empty((mu.size, nlay + 1))
+    stride = optical_depth.stride(0) if nlay > 1 else nwav
+    ctx.fence_from_torch()
+    check(ctx.lib.ecckd_lbl_spectral_fluxes_sw(ctx.handle, nlay, nwav, mu.size, _hptr(mu), _dptr(ssi),
+                                               _dptr(albedo) if albedo is not None else None, _dptr(optical_depth),
+                                               _od_type(optical_depth), stride, _dptr(dn), _dptr(up), nwav, _hptr(bdn), _hptr(bup)))
+    ctx.synchronize()
+    return dn, up, bdn, bup
+
+
 def scale_lut(ctx, model, flux_sums, pressure_hl, temperature_hl, vmr_fl, gas_present, mu0):
     """scale_lut.cpp:117-189 + CkdModel::scale_optical_depth for one reference profile.  `flux_sums` (nz+1, ng)
     from GPointMap.sum_rows of the LBL direct spectral flux.  -> (list of scaled molar_abs arrays, scaling[nz, ng])."""
@@ -1190,6 +1210,21 @@ class GPointMap:
         self.ctx.fence_from_torch()
         check(self.lib.ecckd_lbl_gpoint_fluxes_lw(self.handle, nlay, _hptr(t), _dptr(optical_depth), _od_type(optical_depth),
                                                   stride, _hptr(dn), _hptr(up), _hptr(bdn), _hptr(bup)))
+        return dn, up, bdn, bup
+
+    def lbl_fluxes_sw(self, cos_sza, ssi, optical_depth, albedo=None):
+        """Line-by-line shortwave fluxes of one column per g point, fused, for every solar zenith angle of cos_sza (a scalar is
+        one angle): device tensors ssi (nwav,), optical_depth (nlay, nwav), albedo (nwav,) or None (no upwelling sweep) ->
+        (flux_dn_direct, flux_up) each (nsza, nlay+1, ng), (bb_dn, bb_up) each (nsza, nlay+1): the sums over ALL wavenumbers."""
+        mu = _f64c(np.atleast_1d(cos_sza))
+        nlay = optical_depth.shape[0]
+        dn, up = np.empty((mu.size, nlay + 1, self.ng)), np.empty((mu.size, nlay + 1, self.ng))
+        bdn, bup = np.empty((mu.size, nlay + 1)), np.empty((mu.size, nlay + 1))
+        stride = optical_depth.stride(0) if nlay > 1 else self.nwav
+        self.ctx.fence_from_torch()
+        check(self.lib.ecckd_lbl_gpoint_fluxes_sw(self.handle, nlay, mu.size, _hptr(mu), _dptr(ssi),
+                                                  _dptr(albedo) if albedo is not None else None, _dptr(optical_depth),
+                                                  _od_type(optical_depth), stride, _hptr(dn), _hptr(up), _hptr(bdn), _hptr(bup)))
         return dn, up, bdn, bup
 
     def erythemal_spectrum(self):

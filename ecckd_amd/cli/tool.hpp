@@ -298,6 +298,9 @@ class NcOut {
   void write_slice(const std::string& name, size_t slice, const std::vector<double>& v) {
     ck(ecckd_nc_write_slice_double(f_, name.c_str(), slice, v.data(), v.size()));
   }
+  void write_subslice(const std::string& name, size_t slice, size_t sub, const std::vector<double>& v) {
+    ck(ecckd_nc_write_subslice_double(f_, name.c_str(), slice, sub, v.data(), v.size()));
+  }
   template <class T>
   void write_as_double(const std::string& name, const std::vector<T>& v) {
     std::vector<double> d(v.begin(), v.end());

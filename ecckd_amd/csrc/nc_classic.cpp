@@ -817,12 +817,13 @@ int write_values(ecckd_nc* f, const Var& v, const char* name, uint64_t at, const
 }
 // record `rec` of a record variable; numrecs (header bytes 4..) follows the highest record written, and the file is extended to
 // whole records so that the other record variables of a new record read back as zeros until they are written
-int write_record(ecckd_nc* f, const Var& v, const char* name, size_t rec, const double* data, size_t count) {
+// (`first`: the first of the record's values that `data` holds - a part of a record, ecckd_nc_write_subslice_double)
+int write_record(ecckd_nc* f, const Var& v, const char* name, size_t rec, const double* data, size_t count, uint64_t first = 0) {
   uint64_t per = 1;
   for (size_t k = 1; k < v.dimids.size(); ++k) per *= f->dims[v.dimids[k]].len;
-  ECCKD_REQUIRE(count == per, "ecckd_nc_write_slice_double: \"%s\" has %llu values per record, %zu given", name, (unsigned long long)per, count);
+  ECCKD_REQUIRE(first + count <= per, "ecckd_nc_write_slice_double: \"%s\" has %llu values per record, %zu given", name, (unsigned long long)per, count);
   ECCKD_REQUIRE(f->version == 5 || rec < 0xFFFFFFFFull, "ecckd_nc_write_slice_double: record %zu does not fit the format", rec);
-  ECCKD_CHECK(write_values(f, v, name, v.begin + (uint64_t)rec * f->recsize, data, count));
+  ECCKD_CHECK(write_values(f, v, name, v.begin + (uint64_t)rec * f->recsize + first * type_size(v.type), data, count));
   if (rec + 1 > f->numrecs) {
     f->numrecs = rec + 1;
     uint64_t first = UINT64_MAX;
@@ -871,6 +872,23 @@ int ecckd_nc_write_slice_double(ecckd_nc* f, const char* name, size_t slice, con
   if (f->netcdf4) return ecckd::h5w_write(f->h5w, (int)(v - f->vars.data()), (long long)slice, data, count);
   if (v->record) return write_record(f, *v, name, slice, data, count);
   return write_values(f, *v, name, v->begin + (uint64_t)slice * per * type_size(v->type), data, count);
+}
+
+// one index of the slowest TWO dimensions: what lets a tool write a (column, angle, level, wavenumber) record angle by angle
+// without holding the record.  Not for a variable that is deflated in a NetCDF-4 file (its chunks are compressed whole).
+int ecckd_nc_write_subslice_double(ecckd_nc* f, const char* name, size_t slice, size_t sub, const double* data, size_t count) {
+  ECCKD_REQUIRE(f && f->writing && !f->defining && name && data, "ecckd_nc_write_subslice_double: bad argument or still in define mode");
+  const Var* v = f->find(name);
+  if (!v) return ecckd::fail(ECCKD_PARAMETER_ERROR, "%s: no variable \"%s\"", f->path.c_str(), name);
+  ECCKD_REQUIRE(v->dimids.size() >= 2, "ecckd_nc_write_subslice_double: \"%s\" has fewer than two dimensions", name);
+  uint64_t per = 1;
+  for (size_t k = 2; k < v->dimids.size(); ++k) per *= f->dims[v->dimids[k]].len;
+  const uint64_t nsub = f->dims[v->dimids[1]].len;
+  ECCKD_REQUIRE((v->record || slice < f->dims[v->dimids[0]].len) && sub < nsub && count == per,
+                "ecckd_nc_write_subslice_double: \"%s\" slice %zu, %zu / %zu values do not fit", name, slice, sub, count);
+  if (f->netcdf4) return ecckd::h5w_write(f->h5w, (int)(v - f->vars.data()), (long long)slice, data, count, (long long)sub);
+  if (v->record) return write_record(f, *v, name, slice, data, count, (uint64_t)sub * per);
+  return write_values(f, *v, name, v->begin + ((uint64_t)slice * nsub + sub) * per * type_size(v->type), data, count);
 }
 
 

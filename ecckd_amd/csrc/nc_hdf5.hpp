@@ -45,7 +45,8 @@ struct H5Writer;
 bool h5w_available(const char** why);
 int h5w_create(const char* path, const std::vector<H5WDim>& dims, const std::vector<H5WVar>& vars, const std::vector<H5WAtt>& gatts,
                H5Writer** out);
-int h5w_write(H5Writer* w, int varindex, long long slice /* < 0: the whole variable */, const double* data, size_t count);
+int h5w_write(H5Writer* w, int varindex, long long slice /* < 0: the whole variable */, const double* data, size_t count,
+              long long sub = -1 /* >= 0: with `slice`, one index of the second dimension too (not for deflated variables) */);
 int h5w_close(H5Writer* w);
 
 }  // namespace ecckd

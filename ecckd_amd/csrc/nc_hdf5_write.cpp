@@ -507,9 +507,11 @@ int queue_deflated_chunks(WApi& a, H5Writer* w, int varindex, size_t row0, const
 }
 }  // namespace
 
-int h5w_write(H5Writer* w, int varindex, long long slice, const double* data, size_t count) {
+int h5w_write(H5Writer* w, int varindex, long long slice, const double* data, size_t count, long long sub) {
   WApi& a = wapi();
   const H5WVar& var = w->vars[varindex];
+  if (sub >= 0 && (var.deflate || slice < 0 || var.dimids.size() < 2))
+    return fail(ECCKD_PARAMETER_ERROR, "%s: \"%s\" cannot be written in parts of a slice", w->path.c_str(), var.name.c_str());
   const hid_t d = w->var_ids[varindex];
   const int nd = (int)var.dimids.size();
   herr_t e;
@@ -558,6 +560,7 @@ int h5w_write(H5Writer* w, int varindex, long long slice, const double* data, si
     if (record) shape[0] = w->numrecs;
     start[0] = (hsize_t)slice;
     cnt[0] = 1;
+    if (sub >= 0) { start[1] = (hsize_t)sub; cnt[1] = 1; }
     const hid_t fsp = a.H5Screate_simple(nd, shape, nullptr);
     a.H5Sselect_hyperslab(fsp, 0 /* H5S_SELECT_SET */, start, nullptr, cnt, nullptr);
     const hsize_t n = count;

@@ -153,6 +153,12 @@ class NcWriter:
         d = np.ascontiguousarray(data, dtype=np.float64)
         check(self.lib.ecckd_nc_write_slice_double(self.handle, _b(name), int(index), d.ctypes.data_as(C.POINTER(C.c_double)), d.size))
 
+    def write_subslice(self, name, index, sub, data):
+        """One index of the variable's slowest two dimensions (ecckd_nc_write_subslice_double)."""
+        d = np.ascontiguousarray(data, dtype=np.float64)
+        check(self.lib.ecckd_nc_write_subslice_double(self.handle, _b(name), int(index), int(sub),
+                                                      d.ctypes.data_as(C.POINTER(C.c_double)), d.size))
+
     def close(self):
         if getattr(self, "handle", None):
             h, self.handle = self.handle, None
@@ -656,4 +662,67 @@ def write_lw_spectra(path, s, config_str="", history=None):
         for name in ("pressure_hl", "temperature_hl", "vmr_fl", "flux_dn_lw", "flux_up_lw", "optical_depth", "spectral_flux_dn_lw",
                      "spectral_flux_up_lw"):
             w.write_slice(name, r, s[name][r])
+    w.close()
+
+
+def write_sw_spectra(path, s, config_str="", history=None):
+    """The file of sw_spectra (cli/sw_spectra.cpp): `s` as pipeline.sw_spectra returns it; `column` unlimited."""
+    nrec, nlay = s["optical_depth"].shape[:2]
+    have_g = s["ng"] > 0
+    have_t = "temperature_hl" in s
+    spec = "g_point" if have_g else "wavenumber"
+    w = NcWriter(path)
+    w.define_dimension("column", 0)
+    w.define_dimension("mu0", s["mu0"].size)
+    w.define_dimension("level", nlay)
+    w.define_dimension("half_level", nlay + 1)
+    w.define_dimension(spec, s["optical_depth"].shape[2])
+    w.define_dimension("gas", s["vmr_fl"].shape[1])
+
+    def var(name, dims, long_name, units=None):
+        w.define_variable(name, "float", *dims)
+        w.write_attribute("long_name", long_name, var=name)
+        if units:
+            w.write_attribute("units", units, var=name)
+    var("mu0", ("mu0",), "Cosine of solar zenith angle", "1")
+    var("pressure_hl", ("column", "half_level"), "Pressure at half levels", "Pa")
+    if have_t:
+        var("temperature_hl", ("column", "half_level"), "Temperature at half levels", "K")
+    if not have_g:
+        w.define_variable("wavenumber", "double", "wavenumber")
+        w.deflate_variable("wavenumber")
+        w.write_attribute("long_name", "Wavenumber", var="wavenumber")
+        w.write_attribute("units", "cm-1", var="wavenumber")
+    else:
+        var("solar_irradiance", ("g_point",), "Solar irradiance across each g point", "W m-2")
+    var("vmr_fl", ("column", "gas", "level"), "Volume mixing ratio", "mol mol-1")
+    w.write_attribute("comment", 'The gases are listed in the global attribute "molecules".', var="vmr_fl")
+    var("flux_dn_direct_sw", ("column", "mu0", "half_level"), "Downwelling direct shortwave flux", "W m-2")
+    var("flux_up_sw", ("column", "mu0", "half_level"), "Upwelling shortwave flux", "W m-2")
+    w.define_variable("optical_depth", "float", "column", "level", spec)
+    if not have_g:
+        w.deflate_variable("optical_depth")
+    w.write_attribute("long_name", "Layer optical depth", var="optical_depth")
+    var("spectral_flux_dn_direct_sw", ("column", "mu0", "half_level", spec),
+        "Downwelling direct shortwave flux per g point" if have_g else "Downwelling direct shortwave spectral flux", "W m-2")
+    var("spectral_flux_up_sw", ("column", "mu0", "half_level", spec),
+        "Upwelling shortwave flux per g point" if have_g else "Upwelling shortwave spectral flux", "W m-2")
+    w.write_attribute("history", history or "")
+    w.write_attribute("molecules", s["molecules"])
+    w.write_attribute("config", config_str)
+    w.end_define_mode()
+    w.write("mu0", s["mu0"])
+    if not have_g:
+        w.write("wavenumber", s["wavenumber"])
+    else:
+        w.write("solar_irradiance", s["solar_irradiance"])
+    names = ["pressure_hl"] + (["temperature_hl"] if have_t else []) + ["vmr_fl", "flux_dn_direct_sw", "flux_up_sw", "optical_depth",
+                                                                        "spectral_flux_dn_direct_sw", "spectral_flux_up_sw"]
+    for r in range(nrec):
+        for name in names:
+            if not have_g and name.startswith("spectral_flux"):      # angle by angle, as the tool
+                for a in range(s["mu0"].size):
+                    w.write_subslice(name, r, a, s[name][r, a])
+            else:
+                w.write_slice(name, r, s[name][r])
     w.close()

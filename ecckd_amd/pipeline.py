@@ -920,3 +920,80 @@ def lw_spectra(ctx, inputs, output_path=None, scaling=None, conc=None, g_point=N
     if output_path is not None:
         ncio.write_lw_spectra(output_path, out, config_str=config_str, history=history)
     return out
+
+
+def sw_spectra(ctx, inputs, ssi, output_path=None, scaling=None, conc=None, g_point=None, iprofile=None, cos_sza=(0.5,),
+               surface_albedo=0.15, config_str="", history=None):
+    """bin/sw_spectra as the tool does it: per column the merged spectrum, then either the spectral fluxes one angle at a time
+    (ecckd_lbl_spectral_fluxes_sw) or, with g_point (one value per wavenumber, -1 = none), the fluxes per g point for all
+    angles in one call (ecckd_lbl_gpoint_fluxes_sw) and the optical depth averaged by transmission with the `ssi` weight
+    (ecckd_average_to_gpoints, reference_surface_vmr = 0).  `ssi`: solar spectral irradiance per wavenumber (host array).
+    Arrays are returned in double as the library gives them (the tool's file holds their FLOAT casts): dict of (nrec, ...)
+    arrays; written to output_path when given."""
+    import torch
+    names = ["pressure_hl", "temperature_hl", "vmr_fl", "flux_dn_direct_sw", "flux_up_sw", "optical_depth",
+             "spectral_flux_dn_direct_sw", "spectral_flux_up_sw"]
+    out = {k: [] for k in names}
+    mu0 = np.atleast_1d(np.asarray(cos_sza, dtype=np.float64))
+    if not (1 <= mu0.size <= 8) or np.any(~((mu0 > 0.0) & (mu0 <= 1.0))):
+        raise EcckdError(PARAMETER_ERROR, "cos_sza must hold 1 to 8 numbers in (0, 1]")
+    have_g = g_point is not None
+    ng = int(np.max(g_point)) + 1 if have_g else -1
+    if have_g and ng < 1:
+        raise EcckdError(PARAMETER_ERROR, "g_point assigns no wavenumber to a g point")
+    icol = iprofile if iprofile is not None else 0
+    ncol, gm, d_ssi, d_albedo = 10000, None, None, None
+    while icol < ncol:
+        first, molecules, od, vmr = _read_merged_spectrum(ctx, inputs, scaling, conc, icol)
+        ncol = first["ncol"]
+        p, t = first["pressure_hl"], first["temperature_hl"]
+        if d_ssi is None:
+            nwav = first["wavenumber_cm_1"].size
+            if np.size(ssi) != nwav or (have_g and np.size(g_point) != nwav):
+                raise EcckdError(PARAMETER_ERROR, "ssi / g_point do not have one value per wavenumber")
+            d_ssi = torch.as_tensor(np.ascontiguousarray(ssi, dtype=np.float64), device=ctx.device)
+            d_albedo = torch.full((nwav,), float(surface_albedo), dtype=torch.float64, device=ctx.device)
+            if have_g:
+                d_wn = torch.as_tensor(first["wavenumber_cm_1"], device=ctx.device)
+                d_dwn = torch.as_tensor(first["d_wavenumber_cm_1"], device=ctx.device)
+                gm = api.GPointMap(ctx, torch.as_tensor(np.ascontiguousarray(g_point, dtype=np.int32), device=ctx.device), ng, d_wn, d_dwn)
+                out["solar_irradiance"] = gm.sum_rows(d_ssi[None, :])[0]
+            out["wavenumber"], out["molecules"] = first["wavenumber_cm_1"], molecules.replace(",", " ")
+        out["pressure_hl"].append(p)
+        if t is not None:
+            out["temperature_hl"].append(t)
+        out["vmr_fl"].append(vmr)
+        if not have_g:
+            sdn, sup, bdn, bup = [], [], [], []
+            for mu in mu0:                                                                     # one angle at a time, as the tool
+                a, b, c, d = api.lbl_spectral_fluxes_sw(ctx, mu, d_ssi, od, d_albedo)
+                sdn.append(a[0].cpu().numpy().astype(np.float64))
+                sup.append(b[0].cpu().numpy().astype(np.float64))
+                bdn.append(c[0])
+                bup.append(d[0])
+            bdn, bup = np.stack(bdn), np.stack(bup)
+            out["optical_depth"].append(od.cpu().numpy().astype(np.float64))
+            out["spectral_flux_dn_direct_sw"].append(np.stack(sdn))
+            out["spectral_flux_up_sw"].append(np.stack(sup))
+        else:
+            dn, up, bdn, bup = gm.lbl_fluxes_sw(mu0, d_ssi, od, d_albedo)
+            od_g, _, _ = gm.average_optical_depth(p, od, "transmission", 0.0, ssi=d_ssi)
+            out["optical_depth"].append(od_g)
+            out["spectral_flux_dn_direct_sw"].append(dn)
+            out["spectral_flux_up_sw"].append(up)
+        out["flux_dn_direct_sw"].append(bdn)
+        out["flux_up_sw"].append(bup)
+        if iprofile is not None:
+            break
+        icol += 1
+    if gm is not None:
+        gm.close()
+    if not out["temperature_hl"]:
+        del out["temperature_hl"]
+        names.remove("temperature_hl")
+    for k in names:
+        out[k] = np.stack(out[k])
+    out["ng"], out["mu0"] = ng, mu0
+    if output_path is not None:
+        ncio.write_sw_spectra(output_path, out, config_str=config_str, history=history)
+    return out

@@ -516,6 +516,9 @@ int ecckd_nc_write_double(ecckd_nc* file, const char* name, const double* data, 
  * between and the other record variables of a new record read back as zeros).  In NetCDF-4 output the same calls make chunked
  * datasets with an unlimited first dimension that are extended record by record. */
 int ecckd_nc_write_slice_double(ecckd_nc* file, const char* name, size_t slice, const double* data, size_t count);
+/* One index of the slowest TWO dimensions (`count` = the product of the others): a (column, angle, level, wavenumber) record
+ * angle by angle.  Refused for a variable that is deflated in NetCDF-4 output. */
+int ecckd_nc_write_subslice_double(ecckd_nc* file, const char* name, size_t slice, size_t sub, const double* data, size_t count);
 /* write_order (write_order.cpp:24-143): same variables, external types and attributes; `history` is the
  * line OutputDataFile::append_history would add (may be NULL); column_optical_depth may be NULL (:88). */
 int ecckd_write_order_file(const char* path, const char* molecule, const char* config_str, const char* history, int nband,
@@ -761,6 +764,25 @@ int ecckd_lbl_spectral_fluxes_lw(ecckd_ctx* ctx, int nlay, size_t nwav, const do
                                  const double* d_wavenumber, const double* d_d_wavenumber, const void* d_od, int od_type,
                                  size_t od_stride, float* d_flux_dn, float* d_flux_up, size_t flux_stride, double* h_bb_dn,
                                  double* h_bb_up);
+/* Line-by-line shortwave fluxes of one column resolved per g point, for nsza (1..8) solar zenith angles in one call:
+ * radiative_transfer_direct_sw / _norayleigh_sw (radiative_transfer_sw.cpp:26-77, the arithmetic of ecckd_lbl_band_fluxes_sw) and,
+ * in the same pass over the optical depths, h_flux_*[nsza][nlay+1][ng] = the sum of the spectral flux at each half level over
+ * the wavenumbers of each g point (exactly 0 for a g point without wavenumbers); h_bb_*[nsza][nlay+1] (may be NULL) = the sum over
+ * ALL wavenumbers, those with g_point = -1 included.  d_albedo[nwav] is the surface albedo per wavenumber; NULL: no upwelling
+ * sweep, h_flux_up and h_bb_up exactly 0.  exp(-2 tau) of the upwelling sweep is evaluated once for all angles of a launch;
+ * angle s of a call has the bits of a single-angle call with h_cos_sza[s].  Bitwise reproducible.  The per-block accumulator
+ * (angles x 2 (nlay+1) x columns of doubles in 58 KB of LDS) is filled in several launches where it does not fit: angles are
+ * split first, then g points (ng = 32 at nlay = 54, five angles: 3 launches).  PARAMETER_ERROR: nsza outside 1..8, a cos_sza
+ * outside (0, 1], nlay above 1 855. */
+int ecckd_lbl_gpoint_fluxes_sw(ecckd_gmap* gmap, int nlay, int nsza, const double* h_cos_sza, const double* d_ssi,
+                               const double* d_albedo, const void* d_od, int od_type, size_t od_stride, double* h_flux_dn_direct,
+                               double* h_flux_up, double* h_bb_dn, double* h_bb_up);
+/* The same kernel's other output: the spectral fluxes themselves, d_flux_dn_direct / d_flux_up[nsza][nlay+1][flux_stride] FLOAT
+ * device rows (d_flux_up all 0 without an albedo), and the broadband sums h_bb_*[nsza][nlay+1] (may be NULL) of the DOUBLE
+ * fluxes. */
+int ecckd_lbl_spectral_fluxes_sw(ecckd_ctx* ctx, int nlay, size_t nwav, int nsza, const double* h_cos_sza, const double* d_ssi,
+                                 const double* d_albedo, const void* d_od, int od_type, size_t od_stride, float* d_flux_dn_direct,
+                                 float* d_flux_up, size_t flux_stride, double* h_bb_dn, double* h_bb_up);
 /* LblFluxes::read, lbl_fluxes.cpp:198-230: the square root of the erythemal action spectrum (Webb et al.
  * 2011) averaged over each g point with a 5777 K Planck weight, h_erythemal[ng]; NaN for an empty g point
  * (0/0 as in the reference). */
