@@ -1103,6 +1103,87 @@ def lbl_band_fluxes_sw(ctx, cos_sza, ssi, optical_depth, band_begin, band_end, a
     return dn, up
 
 
+def lbl_scenarios_slots(shortwave, nlay):
+    """Slots (longwave: scenarios; shortwave: scenario-angle pairs) one launch of the scenario kernels carries at nlay layers."""
+    return int(_lib.load_library().ecckd_lbl_scenarios_slots(int(bool(shortwave)), int(nlay)))
+
+
+def _scenario_args(optical_depths, scales):
+    """The gas table of the scenario calls: (ngas, nlay, nwav, pointer array, type array, stride array, scale table)."""
+    ods = list(optical_depths)
+    if not ods:
+        raise ValueError("optical_depths is empty")
+    nlay, nwav = ods[0].shape
+    for od in ods:
+        if tuple(od.shape) != (nlay, nwav) or od.stride(1) != 1:
+            raise ValueError("every optical depth must be a (nlay, nwav) device tensor with contiguous rows")
+    ngas = len(ods)
+    sc = np.asarray(scales, dtype=np.float64)
+    if sc.ndim == 2:
+        sc = np.repeat(sc[:, :, None], nlay, axis=2)
+    if sc.ndim != 3 or sc.shape[1:] != (ngas, nlay):
+        raise ValueError(f"scales must be (nscen, {ngas}) or (nscen, {ngas}, {nlay}), got {sc.shape}")
+    sc = np.ascontiguousarray(sc)
+    ptrs = (C.c_void_p * ngas)(*[od.data_ptr() for od in ods])
+    types = (C.c_int * ngas)(*[_od_type(od) for od in ods])
+    strides = (C.c_size_t * ngas)(*[od.stride(0) if nlay > 1 else nwav for od in ods])
+    return ngas, nlay, nwav, ptrs, types, strides, sc
+
+
+def lbl_band_fluxes_lw_scenarios(ctx, temperature_hl, wavenumber, d_wavenumber, optical_depths, scales, band_begin, band_end,
+                                 boundary=False, nangle=0):
+    """lbl_band_fluxes_lw of many scenarios from one read of the gases' spectra: optical_depths a list of device tensors
+    (nlay, nwav), float32 or float64 per gas; scales (nscen, ngas, nlay), or (nscen, ngas) for one factor per gas; scenario s
+    is computed on sum_g optical_depths[g] * scales[s, g] (the bits of merge_spectrum gas after gas) -> (flux_dn, flux_up),
+    each (nscen, nband, nlay+1); boundary=True: also the spectral boundary fluxes, device tensors (nscen, nwav)."""
+    t = _f64c(temperature_hl)
+    ngas, nlay, nwav, ptrs, types, strides, sc = _scenario_args(optical_depths, scales)
+    if t.size != nlay + 1:
+        raise ValueError("temperature_hl must have nlay + 1 values")
+    nscen = sc.shape[0]
+    b0 = np.ascontiguousarray(band_begin, dtype=np.int64)
+    b1 = np.ascontiguousarray(band_end, dtype=np.int64)
+    dn, up = np.empty((nscen, b0.size, nlay + 1)), np.empty((nscen, b0.size, nlay + 1))
+    torch = _torch()
+    sdn = torch.empty((nscen, nwav), dtype=torch.float64, device=ctx.device) if boundary else None
+    tup = torch.empty((nscen, nwav), dtype=torch.float64, device=ctx.device) if boundary else None
+    ctx.fence_from_torch()
+    check(ctx.lib.ecckd_lbl_band_fluxes_lw_scenarios(ctx.handle, int(nangle), nlay, nwav, _hptr(t), _dptr(wavenumber),
+                                                     _dptr(d_wavenumber), ngas, ptrs, types, strides, nscen, _hptr(sc), b0.size,
+                                                     _hptr(b0, C.c_int64), _hptr(b1, C.c_int64), _hptr(dn), _hptr(up),
+                                                     _dptr(sdn) if boundary else None, _dptr(tup) if boundary else None))
+    if boundary:
+        ctx.synchronize()
+        return dn, up, sdn, tup
+    return dn, up
+
+
+def lbl_band_fluxes_sw_scenarios(ctx, cos_sza, ssi, optical_depths, scales, band_begin, band_end, albedo=None, boundary=False):
+    """lbl_band_fluxes_sw of many scenarios and every solar zenith angle of cos_sza (a scalar is one angle) from one read of
+    the gases' spectra (optical_depths and scales as lbl_band_fluxes_lw_scenarios) -> (flux_dn_direct, flux_up), each
+    (nscen, nsza, nband, nlay+1); boundary=True: also the spectral boundary fluxes, device tensors (nscen, nsza, nwav)."""
+    mu = _f64c(np.atleast_1d(cos_sza))
+    ngas, nlay, nwav, ptrs, types, strides, sc = _scenario_args(optical_depths, scales)
+    nscen = sc.shape[0]
+    b0 = np.ascontiguousarray(band_begin, dtype=np.int64)
+    b1 = np.ascontiguousarray(band_end, dtype=np.int64)
+    shape = (nscen, mu.size, b0.size, nlay + 1)
+    dn, up = np.empty(shape), np.empty(shape)
+    torch = _torch()
+    sdn = torch.empty((nscen, mu.size, nwav), dtype=torch.float64, device=ctx.device) if boundary else None
+    tup = torch.empty((nscen, mu.size, nwav), dtype=torch.float64, device=ctx.device) if boundary else None
+    ctx.fence_from_torch()
+    check(ctx.lib.ecckd_lbl_band_fluxes_sw_scenarios(ctx.handle, nlay, nwav, mu.size, _hptr(mu), _dptr(ssi),
+                                                     _dptr(albedo) if albedo is not None else None, ngas, ptrs, types, strides,
+                                                     nscen, _hptr(sc), b0.size, _hptr(b0, C.c_int64), _hptr(b1, C.c_int64),
+                                                     _hptr(dn), _hptr(up), _dptr(sdn) if boundary else None,
+                                                     _dptr(tup) if boundary else None))
+    if boundary:
+        ctx.synchronize()
+        return dn, up, sdn, tup
+    return dn, up
+
+
 def lbl_spectral_fluxes_sw(ctx, cos_sza, ssi, optical_depth, albedo=None):
     """Line-by-line shortwave spectral fluxes of one column for every solar zenith angle of cos_sza (a scalar is one angle):
     device tensors ssi (nwav,), optical_depth (nlay, nwav), albedo (nwav,) or None (no upwelling sweep) ->

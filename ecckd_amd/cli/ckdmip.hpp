@@ -4,6 +4,7 @@
 //
 // ckdmip_{lw,sw} [--config file.nam] [--scenario name] [--merge-only] [--column-range a b] [--ssi file]
 //                {[--scale s | --conc c | --const c] spectrum-file}... [--ckd optical-depth-file] --output file
+// ckdmip_{lw,sw} [--config file.nam] [--column-range a b] [--ssi file] --scenarios table spectrum-file...
 //
 //   --merge-only   test/merge_well_mixed_lw.sh:28-31, :46-49, :60-63 (merge_well_mixed_sw.sh:35-81): the optical depths of
 //                  several gas files added up, each scaled as requested, written as one spectrum file that read_spectrum /
@@ -19,6 +20,15 @@
 //                  (LblFluxes::mask_rayleigh_up);
 //   --ckd file     test/run_ckd_lw.sh:133-137, test/run_ckd_sw.sh:125-128: radiative transfer on the g-point optical depths
 //                  that run_ckd wrote, fluxes per column.
+//   --scenarios FILE   the loop of test/run_lw_lbl_evaluation.sh:286-323 / test/run_sw_lbl_evaluation.sh:70-260 - one call per
+//                  scenario, the scenarios differing in one scaling per gas file - as ONE call: FILE is a text table (`#` starts a
+//                  comment, blank lines are skipped), one line per scenario,  NAME OUTPUT SPEC_1 ... SPEC_n,  exactly one SPEC per
+//                  spectrum file of the command line in command-line order, a SPEC one of  asis  scale=S  conc=C  const=C  with
+//                  the meanings of --scale / --conc / --const below.  Every gas file is read once per column and stays on the
+//                  device; all scenarios (shortwave: and all zenith angles) are computed from that one read
+//                  (ecckd_lbl_band_fluxes_lw_scenarios / _sw_scenarios), and every OUTPUT is the file the default mode would
+//                  have written with `--scenario NAME --output OUTPUT` and the line's scalings.  Not with --merge-only, --ckd,
+//                  --output, --scenario or a per-file --scale / --conc / --const.
 // A file may be preceded by  --scale s  (optical depth times s),  --conc c  (scaled so that the file's reference surface
 // mole fraction becomes c)  or  --const c  (a mole fraction c at every level: each level scaled by c / its own).
 // Namelist (&longwave_config / &shortwave_config): band_wavenumber1 / band_wavenumber2, nspectralstride (1 only), nangle (0:
@@ -32,6 +42,7 @@
 #include <algorithm>
 #include <cctype>
 #include <fstream>
+#include <memory>
 #include <sstream>
 
 #include "tool.hpp"
@@ -116,13 +127,132 @@ Namelist read_namelist(const std::string& path) {
   return nl;
 }
 
+// One line of a --scenarios table: the scenario's name, its output file and one GasArg (path empty) per spectrum file
+struct ScenarioRow {
+  std::string name, output;
+  std::vector<GasArg> specs;
+};
+
+std::vector<ScenarioRow> read_scenarios(const std::string& path, size_t ngas) {
+  std::ifstream in(path);
+  if (!in) fail(ECCKD_PARAMETER_ERROR, "Cannot open scenario table %s", path.c_str());
+  std::vector<ScenarioRow> rows;
+  std::string line;
+  int lineno = 0;
+  while (std::getline(in, line)) {
+    ++lineno;
+    const size_t c = line.find('#');
+    if (c != std::string::npos) line.erase(c);
+    std::istringstream ss(line);
+    std::vector<std::string> tok;
+    for (std::string t; ss >> t;) tok.push_back(t);
+    if (tok.empty()) continue;
+    if (tok.size() != 2 + ngas)
+      fail(ECCKD_PARAMETER_ERROR, "%s:%d: %zu scaling spec(s) for %zu spectrum file(s) (NAME OUTPUT and one spec per file)", path.c_str(),
+           lineno, tok.size() >= 2 ? tok.size() - 2 : (size_t)0, ngas);
+    ScenarioRow row;
+    row.name = tok[0]; row.output = tok[1];
+    for (size_t g = 0; g < ngas; ++g) {
+      const std::string& t = tok[2 + g];
+      GasArg a;
+      const size_t eq = t.find('=');
+      const std::string key = t.substr(0, eq);
+      if (t == "asis") a.mode = GasArg::NONE;
+      else if (eq != std::string::npos && key == "scale") a.mode = GasArg::SCALE;
+      else if (eq != std::string::npos && key == "conc") a.mode = GasArg::CONC;
+      else if (eq != std::string::npos && key == "const") a.mode = GasArg::CONST;
+      else fail(ECCKD_PARAMETER_ERROR, "%s:%d: unknown scaling spec \"%s\" (asis, scale=S, conc=C or const=C)", path.c_str(), lineno, t.c_str());
+      if (a.mode != GasArg::NONE) {
+        const std::string v = t.substr(eq + 1);
+        char* end = nullptr;
+        a.value = std::strtod(v.c_str(), &end);
+        if (v.empty() || *end) fail(ECCKD_PARAMETER_ERROR, "%s:%d: unknown scaling spec \"%s\" (no number after '=')", path.c_str(), lineno, t.c_str());
+      }
+      row.specs.push_back(a);
+    }
+    for (const ScenarioRow& r : rows)
+      if (r.output == row.output) fail(ECCKD_PARAMETER_ERROR, "%s:%d: duplicate output file \"%s\"", path.c_str(), lineno, row.output.c_str());
+    rows.push_back(row);
+  }
+  if (rows.empty()) fail(ECCKD_PARAMETER_ERROR, "Scenario table %s is empty", path.c_str());
+  return rows;
+}
+
+// The scaling profile of one gas file in one column and the mole fractions the output reports for it
+void gas_scaling(const GasArg& g, const std::string& path, int nlay, const std::vector<double>& pressure_hl, double ref,
+                 const std::vector<double>& vmr, std::vector<double>& profile, std::vector<double>& vmr_out) {
+  profile.assign(nlay, 1.0); vmr_out.assign(nlay, -1.0);
+  if (g.mode == GasArg::SCALE) {
+    for (int l = 0; l < nlay; ++l) { profile[l] = g.value; vmr_out[l] = vmr[l] >= 0.0 ? vmr[l] * g.value : -1.0; }
+  } else if (g.mode == GasArg::CONC) {
+    ck(ecckd_merge_scaling(nlay, pressure_hl.data(), -1.0, g.value, ref, vmr.data(), 0, nullptr, nullptr, profile.data(), vmr_out.data()));
+  } else if (g.mode == GasArg::CONST) {
+    for (int l = 0; l < nlay; ++l) {
+      if (!(vmr[l] > 0.0)) fail(ECCKD_PARAMETER_ERROR, "--const needs mole_fraction_fl in %s", path.c_str());
+      profile[l] = g.value / vmr[l];
+      vmr_out[l] = g.value;
+    }
+  } else {
+    vmr_out = vmr;
+  }
+}
+
+// The dimensions and variables of a flux file after pressure_hl / temperature_hl (what LblFluxes::read expects, lbl_fluxes.cpp:60-133)
+void define_flux_variables(NcOut& out, bool sw, size_t ngas, int nmu, int nband, size_t nwav, const std::string& ids, bool boundary) {
+  if (sw) {
+    out.dim("gas", ngas); out.dim("mu0", nmu); out.dim("band_sw", nband);
+    out.var("mole_fraction_fl", NC_FLOAT_T, {"column", "gas", "level"}, "Mole fraction at full levels", "1");
+    out.var("mu0", NC_FLOAT_T, {"mu0"}, "Cosine of solar zenith angle", "1");
+    out.var("flux_up_sw", NC_FLOAT_T, {"column", "mu0", "half_level"}, "Upwelling shortwave flux", "W m-2");
+    out.var("flux_dn_sw", NC_FLOAT_T, {"column", "mu0", "half_level"}, "Downwelling shortwave flux", "W m-2");
+    out.var("flux_dn_direct_sw", NC_FLOAT_T, {"column", "mu0", "half_level"}, "Downwelling direct shortwave flux", "W m-2");
+    out.var("band_wavenumber1_sw", NC_FLOAT_T, {"band_sw"}, "Lower bound wavenumber for shortwave band", "cm-1");
+    out.var("band_wavenumber2_sw", NC_FLOAT_T, {"band_sw"}, "Upper bound wavenumber for shortwave band", "cm-1");
+    out.var("band_flux_up_sw", NC_FLOAT_T, {"column", "mu0", "half_level", "band_sw"}, "Upwelling shortwave flux in bands", "W m-2");
+    out.var("band_flux_dn_direct_sw", NC_FLOAT_T, {"column", "mu0", "half_level", "band_sw"}, "Downwelling direct shortwave flux in bands", "W m-2");
+    out.att(ids, "constituent_id");
+    if (boundary) {     // what LblFluxes::read maps to g points (lbl_fluxes.cpp:183-246)
+      out.dim("wavenumber", nwav);
+      out.var("wavenumber", NC_DOUBLE_T, {"wavenumber"}, "Wavenumber", "cm-1");
+      out.var("spectral_flux_dn_direct_surf_sw", NC_FLOAT_T, {"column", "mu0", "wavenumber"}, "Spectral direct shortwave flux at the surface", "W m-2");
+      out.var("spectral_flux_up_toa_sw", NC_FLOAT_T, {"column", "mu0", "wavenumber"}, "Spectral upwelling shortwave flux at top of atmosphere", "W m-2");
+    }
+  } else {
+    out.dim("gas", ngas); out.dim("band_lw", nband);
+    out.var("mole_fraction_fl", NC_FLOAT_T, {"column", "gas", "level"}, "Mole fraction at full levels", "1");
+    out.var("flux_up_lw", NC_FLOAT_T, {"column", "half_level"}, "Upwelling longwave flux", "W m-2");
+    out.var("flux_dn_lw", NC_FLOAT_T, {"column", "half_level"}, "Downwelling longwave flux", "W m-2");
+    out.var("band_wavenumber1_lw", NC_FLOAT_T, {"band_lw"}, "Lower bound wavenumber for longwave band", "cm-1");
+    out.var("band_wavenumber2_lw", NC_FLOAT_T, {"band_lw"}, "Upper bound wavenumber for longwave band", "cm-1");
+    out.var("band_flux_up_lw", NC_FLOAT_T, {"column", "half_level", "band_lw"}, "Upwelling longwave flux in bands", "W m-2");
+    out.var("band_flux_dn_lw", NC_FLOAT_T, {"column", "half_level", "band_lw"}, "Downwelling longwave flux in bands", "W m-2");
+    out.att(ids, "constituent_id");
+    if (boundary) {     // lbl_fluxes.cpp:301-325
+      out.dim("wavenumber", nwav);
+      out.var("wavenumber", NC_DOUBLE_T, {"wavenumber"}, "Wavenumber", "cm-1");
+      out.var("spectral_flux_dn_surf_lw", NC_FLOAT_T, {"column", "wavenumber"}, "Spectral downwelling longwave flux at the surface", "W m-2");
+      out.var("spectral_flux_up_toa_lw", NC_FLOAT_T, {"column", "wavenumber"}, "Spectral upwelling longwave flux at top of atmosphere", "W m-2");
+    }
+  }
+}
+
+// [band][level] fluxes -> (half_level, band) and the sums over the bands
+void bands_to_file_order(int nband, size_t nhl, const double* b, double* t /* [nhl][nband] */, double* sum /* [nhl] */) {
+  for (size_t i = 0; i < nhl; ++i) sum[i] = 0.0;
+  for (int k = 0; k < nband; ++k)
+    for (size_t i = 0; i < nhl; ++i) {
+      t[i * nband + k] = b[(size_t)k * nhl + i];
+      sum[i] += b[(size_t)k * nhl + i];
+    }
+}
+
 }  // namespace
 
 inline int ckdmip_main(int argc, char** argv, bool sw) {
   try {
     std::vector<GasArg> gases;
-    std::string config_file, scenario, output, ckd_file, ssi_file;
-    bool merge_only = false;
+    std::string config_file, scenario, output, ckd_file, ssi_file, scenarios_file;
+    bool merge_only = false, per_file_scaling = false;
     long col_a = -1, col_b = -1;
     GasArg pending;
     for (int i = 1; i < argc; ++i) {
@@ -134,14 +264,22 @@ inline int ckdmip_main(int argc, char** argv, bool sw) {
       else if (a == "--ckd") { need(1); ckd_file = argv[++i]; }
       else if (a == "--ssi") { need(1); ssi_file = argv[++i]; }
       else if (a == "--merge-only") merge_only = true;
+      else if (a == "--scenarios") { need(1); scenarios_file = argv[++i]; }
       else if (a == "--column-range") { need(2); col_a = std::atol(argv[++i]); col_b = std::atol(argv[++i]); }
-      else if (a == "--scale") { need(1); pending.mode = GasArg::SCALE; pending.value = std::atof(argv[++i]); }
-      else if (a == "--conc") { need(1); pending.mode = GasArg::CONC; pending.value = std::atof(argv[++i]); }
-      else if (a == "--const") { need(1); pending.mode = GasArg::CONST; pending.value = std::atof(argv[++i]); }
+      else if (a == "--scale") { need(1); pending.mode = GasArg::SCALE; pending.value = std::atof(argv[++i]); per_file_scaling = true; }
+      else if (a == "--conc") { need(1); pending.mode = GasArg::CONC; pending.value = std::atof(argv[++i]); per_file_scaling = true; }
+      else if (a == "--const") { need(1); pending.mode = GasArg::CONST; pending.value = std::atof(argv[++i]); per_file_scaling = true; }
       else if (a.rfind("--", 0) == 0) fail(ECCKD_PARAMETER_ERROR, "Argument \"%s\" not understood", a.c_str());
       else { pending.path = a; gases.push_back(pending); pending = GasArg(); }
     }
-    if (output.empty()) fail(ECCKD_PARAMETER_ERROR, "\"--output\" file not specified");
+    std::vector<ScenarioRow> table;              // --scenarios: every check of the table before a device is opened
+    if (!scenarios_file.empty()) {
+      const char* with = merge_only ? "--merge-only" : !ckd_file.empty() ? "--ckd" : !output.empty() ? "--output" : !scenario.empty() ? "--scenario"
+                         : per_file_scaling ? "a per-file --scale, --conc or --const" : nullptr;
+      if (with) fail(ECCKD_PARAMETER_ERROR, "\"--scenarios\" cannot be combined with %s (names, outputs and scalings come from the table)", with);
+      if (gases.empty()) fail(ECCKD_PARAMETER_ERROR, "No spectrum files given");
+      table = read_scenarios(scenarios_file, gases.size());
+    } else if (output.empty()) fail(ECCKD_PARAMETER_ERROR, "\"--output\" file not specified");
     Namelist nl;
     if (!config_file.empty()) nl = read_namelist(config_file);
     if (nl.nspectralstride != 1) fail(ECCKD_PARAMETER_ERROR, "nspectralstride = %d is not supported (1 only)", nl.nspectralstride);
@@ -239,7 +377,8 @@ inline int ckdmip_main(int argc, char** argv, bool sw) {
     LOG("%d gas file(s), %d column(s), %d layers, %zu spectral points\n", (int)gases.size(), ncol, nlay, nwav);
 
     Device dev;
-    DevBuf d_merged(dev, (size_t)nlay * nwav * sizeof(double));
+    DevBuf d_merged;
+    if (table.empty()) d_merged.alloc(dev, (size_t)nlay * nwav * sizeof(double));
     DevBuf d_wn, d_dwn;
     d_wn.upload(dev, first.wavenumber_cm_1);
     d_dwn.upload(dev, first.d_wavenumber_cm_1);
@@ -276,6 +415,113 @@ inline int ckdmip_main(int argc, char** argv, bool sw) {
       ck(ecckd_band_ranges(nwav, first.wavenumber_cm_1.data(), nband, nl.band1.data(), nl.band2.data(), nullptr, bbegin.data(), bend.data()));
     }
 
+    // ---------------------------------------------------------------------------------------------------------------
+    if (!table.empty()) {   // every scenario of the table from one read of the gas files per column
+      const size_t nscen = table.size(), ngas = gases.size(), nhl = (size_t)nlay + 1;
+      std::vector<std::unique_ptr<NcOut>> outs;
+      for (const ScenarioRow& row : table) {
+        outs.emplace_back(new NcOut(row.output));
+        NcOut& o = *outs.back();
+        o.dim("column", ncol); o.dim("half_level", nlay + 1); o.dim("level", nlay);
+        o.var("pressure_hl", NC_FLOAT_T, {"column", "half_level"}, "Pressure at half levels", "Pa");
+        o.var("temperature_hl", NC_FLOAT_T, {"column", "half_level"}, "Temperature at half levels", "K");
+        define_flux_variables(o, sw, ngas, nmu, nband, nwav, ids, nl.boundary_fluxes);
+        o.att(row.name, "scenario");
+        o.att(history, "history");
+        o.end_define();
+        if (sw) { o.write("band_wavenumber1_sw", nl.band1); o.write("band_wavenumber2_sw", nl.band2); o.write("mu0", mu0); }
+        else { o.write("band_wavenumber1_lw", nl.band1); o.write("band_wavenumber2_lw", nl.band2); }
+        if (nl.boundary_fluxes) o.write("wavenumber", first.wavenumber_cm_1);
+      }
+      const size_t nslot = sw ? nscen * nmu : nscen;            // rows of fluxes: (scenario[, angle])
+      const int ngroup = sw ? std::min(8, nmu) : 1;              // angles per call: the entry takes up to 8
+      DevBuf d_sdn, d_tup;
+      if (nl.boundary_fluxes) { d_sdn.alloc(dev, nscen * ngroup * nwav * sizeof(double)); d_tup.alloc(dev, nscen * ngroup * nwav * sizeof(double)); }
+      double* const p_sdn = nl.boundary_fluxes ? d_sdn.as<double>() : nullptr;
+      double* const p_tup = nl.boundary_fluxes ? d_tup.as<double>() : nullptr;
+      for (int c = c0; c <= c1; ++c) {
+        const Spectrum col = c == 0 ? first : read_spectrum(gases[0].path, c, false);
+        std::vector<DevOd> ods;                                  // the gases side by side on the device, read once
+        std::vector<const void*> od_ptr;
+        std::vector<int> od_type;
+        std::vector<size_t> od_stride(ngas, nwav);
+        std::vector<double> scale(nscen * ngas * nlay), vmr_all(nscen * ngas * nlay);   // [scenario][gas][level]
+        for (size_t ig = 0; ig < ngas; ++ig) {
+          NcIn f(gases[ig].path);
+          double ref = -1.0;
+          std::vector<double> vmr, profile, vmr_out;
+          std::string mol;
+          read_od_meta(f, c, nlay, ref, vmr, mol);
+          for (size_t s = 0; s < nscen; ++s) {
+            gas_scaling(table[s].specs[ig], gases[ig].path, nlay, col.pressure_hl, ref, vmr, profile, vmr_out);
+            std::copy(profile.begin(), profile.end(), scale.begin() + (s * ngas + ig) * nlay);
+            std::copy(vmr_out.begin(), vmr_out.end(), vmr_all.begin() + (s * ngas + ig) * nlay);
+          }
+          ods.push_back(read_od_dev(dev, f, c, nlay, nwav));
+          od_ptr.push_back(ods.back().buf.ptr());
+          od_type.push_back(ods.back().type);
+        }
+        ck(ecckd_synchronize(dev.ctx()));
+        std::vector<double> bdn(nslot * nband * nhl), bup(nslot * nband * nhl);
+        std::vector<double> all_dn, all_up;                      // [slot][wavenumber] boundary fluxes of this column
+        if (nl.boundary_fluxes) { all_dn.resize(nslot * nwav); all_up.resize(nslot * nwav); }
+        if (sw) {
+          for (int m0 = 0; m0 < nmu; m0 += ngroup) {             // [scenario][angle] rows per group of angles
+            const size_t nm = (size_t)std::min(ngroup, nmu - m0);
+            std::vector<double> gdn(nscen * nm * nband * nhl), gup(gdn.size());
+            ck(ecckd_lbl_band_fluxes_sw_scenarios(dev.ctx(), nlay, nwav, (int)nm, mu0.data() + m0, d_ssi.as<double>(), d_albedo.as<double>(), (int)ngas,
+                                                  od_ptr.data(), od_type.data(), od_stride.data(), (int)nscen, scale.data(), nband, bbegin.data(),
+                                                  bend.data(), gdn.data(), gup.data(), p_sdn, p_tup));
+            std::vector<double> a, b;
+            if (nl.boundary_fluxes) { a = d_sdn.download<double>(); b = d_tup.download<double>(); }
+            for (size_t s = 0; s < nscen; ++s) {
+              const size_t n = nm * nband * nhl, to = (s * nmu + m0) * nband * nhl;
+              std::copy(gdn.begin() + s * n, gdn.begin() + (s + 1) * n, bdn.begin() + to);
+              std::copy(gup.begin() + s * n, gup.begin() + (s + 1) * n, bup.begin() + to);
+              if (nl.boundary_fluxes) {
+                std::copy(a.begin() + s * nm * nwav, a.begin() + (s + 1) * nm * nwav, all_dn.begin() + (s * nmu + m0) * nwav);
+                std::copy(b.begin() + s * nm * nwav, b.begin() + (s + 1) * nm * nwav, all_up.begin() + (s * nmu + m0) * nwav);
+              }
+            }
+          }
+        } else {
+          if (col.temperature_hl.empty()) fail(ECCKD_PARAMETER_ERROR, "temperature_hl missing from %s", gases[0].path.c_str());
+          ck(ecckd_lbl_band_fluxes_lw_scenarios(dev.ctx(), nl.nangle, nlay, nwav, col.temperature_hl.data(), d_wn.as<double>(), d_dwn.as<double>(),
+                                                (int)ngas, od_ptr.data(), od_type.data(), od_stride.data(), (int)nscen, scale.data(), nband,
+                                                bbegin.data(), bend.data(), bdn.data(), bup.data(), p_sdn, p_tup));
+          if (nl.boundary_fluxes) { all_dn = d_sdn.download<double>(); all_up = d_tup.download<double>(); }
+        }
+        const size_t oc = (size_t)(c - c0), per = sw ? (size_t)nmu : 1;   // rows per scenario
+        std::vector<double> tdn(per * nhl * nband), tup(per * nhl * nband), sdn(per * nhl), sup(per * nhl);
+        for (size_t s = 0; s < nscen; ++s) {
+          NcOut& o = *outs[s];
+          o.write_slice("pressure_hl", oc, col.pressure_hl);
+          if (!col.temperature_hl.empty()) o.write_slice("temperature_hl", oc, col.temperature_hl);
+          for (size_t m = 0; m < per; ++m) {
+            bands_to_file_order(nband, nhl, &bdn[(s * per + m) * nband * nhl], &tdn[m * nhl * nband], &sdn[m * nhl]);
+            bands_to_file_order(nband, nhl, &bup[(s * per + m) * nband * nhl], &tup[m * nhl * nband], &sup[m * nhl]);
+          }
+          o.write_slice("mole_fraction_fl", oc, std::vector<double>(vmr_all.begin() + s * ngas * nlay, vmr_all.begin() + (s + 1) * ngas * nlay));
+          if (sw) {
+            o.write_slice("band_flux_dn_direct_sw", oc, tdn); o.write_slice("band_flux_up_sw", oc, tup);
+            o.write_slice("flux_dn_direct_sw", oc, sdn); o.write_slice("flux_dn_sw", oc, sdn); o.write_slice("flux_up_sw", oc, sup);
+          } else {
+            o.write_slice("band_flux_dn_lw", oc, tdn); o.write_slice("band_flux_up_lw", oc, tup);
+            o.write_slice("flux_dn_lw", oc, sdn); o.write_slice("flux_up_lw", oc, sup);
+          }
+          if (nl.boundary_fluxes) {
+            const std::vector<double> a(all_dn.begin() + s * per * nwav, all_dn.begin() + (s + 1) * per * nwav);
+            const std::vector<double> b(all_up.begin() + s * per * nwav, all_up.begin() + (s + 1) * per * nwav);
+            o.write_slice(sw ? "spectral_flux_dn_direct_surf_sw" : "spectral_flux_dn_surf_lw", oc, a);
+            o.write_slice(sw ? "spectral_flux_up_toa_sw" : "spectral_flux_up_toa_lw", oc, b);
+          }
+        }
+        LOG("  column %d done (%zu scenarios)\n", c + 1, nscen);
+      }
+      for (auto& o : outs) o->close();
+      return done(0);
+    }
+
     NcOut out(output);
     out.dim("column", ncol); out.dim("half_level", nlay + 1); out.dim("level", nlay);
     out.var("pressure_hl", NC_FLOAT_T, {"column", "half_level"}, "Pressure at half levels", "Pa");
@@ -286,40 +532,8 @@ inline int ckdmip_main(int argc, char** argv, bool sw) {
       out.var("optical_depth", NC_FLOAT_T, {"column", "level", "wavenumber"}, "Layer optical depth");
       out.att(ids, "molecules");
       out.att("composite", "constituent_id");
-    } else if (sw) {
-      out.dim("gas", gases.size()); out.dim("mu0", nmu); out.dim("band_sw", nband);
-      out.var("mole_fraction_fl", NC_FLOAT_T, {"column", "gas", "level"}, "Mole fraction at full levels", "1");
-      out.var("mu0", NC_FLOAT_T, {"mu0"}, "Cosine of solar zenith angle", "1");
-      out.var("flux_up_sw", NC_FLOAT_T, {"column", "mu0", "half_level"}, "Upwelling shortwave flux", "W m-2");
-      out.var("flux_dn_sw", NC_FLOAT_T, {"column", "mu0", "half_level"}, "Downwelling shortwave flux", "W m-2");
-      out.var("flux_dn_direct_sw", NC_FLOAT_T, {"column", "mu0", "half_level"}, "Downwelling direct shortwave flux", "W m-2");
-      out.var("band_wavenumber1_sw", NC_FLOAT_T, {"band_sw"}, "Lower bound wavenumber for shortwave band", "cm-1");
-      out.var("band_wavenumber2_sw", NC_FLOAT_T, {"band_sw"}, "Upper bound wavenumber for shortwave band", "cm-1");
-      out.var("band_flux_up_sw", NC_FLOAT_T, {"column", "mu0", "half_level", "band_sw"}, "Upwelling shortwave flux in bands", "W m-2");
-      out.var("band_flux_dn_direct_sw", NC_FLOAT_T, {"column", "mu0", "half_level", "band_sw"}, "Downwelling direct shortwave flux in bands", "W m-2");
-      out.att(ids, "constituent_id");
-      if (nl.boundary_fluxes) {     // what LblFluxes::read maps to g points (lbl_fluxes.cpp:183-246)
-        out.dim("wavenumber", nwav);
-        out.var("wavenumber", NC_DOUBLE_T, {"wavenumber"}, "Wavenumber", "cm-1");
-        out.var("spectral_flux_dn_direct_surf_sw", NC_FLOAT_T, {"column", "mu0", "wavenumber"}, "Spectral direct shortwave flux at the surface", "W m-2");
-        out.var("spectral_flux_up_toa_sw", NC_FLOAT_T, {"column", "mu0", "wavenumber"}, "Spectral upwelling shortwave flux at top of atmosphere", "W m-2");
-      }
     } else {
-      out.dim("gas", gases.size()); out.dim("band_lw", nband);
-      out.var("mole_fraction_fl", NC_FLOAT_T, {"column", "gas", "level"}, "Mole fraction at full levels", "1");
-      out.var("flux_up_lw", NC_FLOAT_T, {"column", "half_level"}, "Upwelling longwave flux", "W m-2");
-      out.var("flux_dn_lw", NC_FLOAT_T, {"column", "half_level"}, "Downwelling longwave flux", "W m-2");
-      out.var("band_wavenumber1_lw", NC_FLOAT_T, {"band_lw"}, "Lower bound wavenumber for longwave band", "cm-1");
-      out.var("band_wavenumber2_lw", NC_FLOAT_T, {"band_lw"}, "Upper bound wavenumber for longwave band", "cm-1");
-      out.var("band_flux_up_lw", NC_FLOAT_T, {"column", "half_level", "band_lw"}, "Upwelling longwave flux in bands", "W m-2");
-      out.var("band_flux_dn_lw", NC_FLOAT_T, {"column", "half_level", "band_lw"}, "Downwelling longwave flux in bands", "W m-2");
-      out.att(ids, "constituent_id");
-      if (nl.boundary_fluxes) {     // lbl_fluxes.cpp:301-325
-        out.dim("wavenumber", nwav);
-        out.var("wavenumber", NC_DOUBLE_T, {"wavenumber"}, "Wavenumber", "cm-1");
-        out.var("spectral_flux_dn_surf_lw", NC_FLOAT_T, {"column", "wavenumber"}, "Spectral downwelling longwave flux at the surface", "W m-2");
-        out.var("spectral_flux_up_toa_lw", NC_FLOAT_T, {"column", "wavenumber"}, "Spectral upwelling longwave flux at top of atmosphere", "W m-2");
-      }
+      define_flux_variables(out, sw, gases.size(), nmu, nband, nwav, ids, nl.boundary_fluxes);
     }
     if (!scenario.empty()) out.att(scenario, "scenario");
     out.att(history, "history");
@@ -346,20 +560,8 @@ inline int ckdmip_main(int argc, char** argv, bool sw) {
         std::vector<double> vmr;
         std::string mol;
         read_od_meta(f, c, nlay, ref, vmr, mol);
-        std::vector<double> profile(nlay, 1.0), vmr_out(nlay, -1.0);
-        if (g.mode == GasArg::SCALE) {
-          for (int l = 0; l < nlay; ++l) { profile[l] = g.value; vmr_out[l] = vmr[l] >= 0.0 ? vmr[l] * g.value : -1.0; }
-        } else if (g.mode == GasArg::CONC) {
-          ck(ecckd_merge_scaling(nlay, col.pressure_hl.data(), -1.0, g.value, ref, vmr.data(), 0, nullptr, nullptr, profile.data(), vmr_out.data()));
-        } else if (g.mode == GasArg::CONST) {
-          for (int l = 0; l < nlay; ++l) {
-            if (!(vmr[l] > 0.0)) fail(ECCKD_PARAMETER_ERROR, "--const needs mole_fraction_fl in %s", g.path.c_str());
-            profile[l] = g.value / vmr[l];
-            vmr_out[l] = g.value;
-          }
-        } else {
-          vmr_out = vmr;
-        }
+        std::vector<double> profile, vmr_out;
+        gas_scaling(g, g.path, nlay, col.pressure_hl, ref, vmr, profile, vmr_out);
         vmr_all.insert(vmr_all.end(), vmr_out.begin(), vmr_out.end());
         DevOd od = read_od_dev(dev, f, c, nlay, nwav);
         ck(ecckd_merge_spectrum_dev(dev.ctx(), nlay, nwav, od.buf.ptr(), od.type, nwav, profile.data(), ig == 0 ? 1 : 0,

@@ -458,6 +458,37 @@ int ecckd_lbl_band_fluxes_sw_ex(ecckd_ctx* ctx, int nlay, size_t nwav, double co
                                 const int64_t* h_band_begin, const int64_t* h_band_end, double* h_flux_dn_direct,
                                 double* h_flux_up, double* d_surf_dn_direct, double* d_toa_up);
 
+/* The band fluxes of one column for nscen SCENARIOS from one read of the gases' spectra: the loop of
+ * test/run_lw_lbl_evaluation.sh:286-323 / test/run_sw_lbl_evaluation.sh:70-260 (one call of the CKDMIP tool per scenario, a
+ * scenario differing from the next in one scaling per gas file) as one call.  d_od[ngas]: the gases' device matrices
+ * [nlay][od_stride[g]], od_type[g] ECCKD_F32 or ECCKD_F64 per gas, 1 <= ngas <= 16; h_scale[nscen][ngas][nlay]: the scaling
+ * profiles (ecckd_merge_scaling).  Scenario s is computed on tau = sum_g od_g * scale[s][g][level], product and sum rounded
+ * separately in gas order - bit for bit the DOUBLE matrix ngas calls of ecckd_merge_spectrum_dev leave (read_merged_spectrum.cpp:
+ * 152-166), which is formed in registers and never written - with the arithmetic of ecckd_lbl_band_fluxes_lw_angles (nangle
+ * 0..16) / ecckd_lbl_band_fluxes_sw_ex (nsza = 1..8 solar zenith angles at once, every cos_sza in (0, 1]; d_albedo NULL: no
+ * upwelling sweep, h_flux_up all zero).  Results: h_flux_dn / h_flux_up [nscen][nband][nlay+1] (shortwave:
+ * [nscen][nsza][nband][nlay+1]); d_surf_dn / d_toa_up: NULL or device arrays [nscen][nwav] (shortwave [nscen][nsza][nwav]), the
+ * spectral boundary fluxes as the _ex / _angles calls write them.  Scenario s (and angle a) of a call has the bits of that
+ * scenario (and angle) computed by a call of its own.
+ * A launch carries T "slots" (longwave: scenarios; shortwave: scenario-angle pairs), T = ecckd_lbl_scenarios_slots(shortwave,
+ * nlay) = min(8, 43008 / (64 (nlay+1))) longwave, min(16, 59392 / (64 (nlay+1))) shortwave: the 4 x T x 2 (nlay+1) doubles
+ * of a block's LDS accumulator within 42 KB / 58 KB.  T = 0 - nlay > 671 longwave, > 927 shortwave - is a PARAMETER_ERROR.
+ * More slots than T run as several launches, each reading the gas rows again: scenarios are split first (evenly over
+ * ceil(nscen / T) launches; shortwave: min(T, 16) / nsza scenarios with all their angles per launch), the angles of one
+ * scenario only where nsza > T. */
+int ecckd_lbl_band_fluxes_lw_scenarios(ecckd_ctx* ctx, int nangle, int nlay, size_t nwav, const double* h_temperature_hl,
+                                       const double* d_wavenumber, const double* d_d_wavenumber, int ngas, const void* const* d_od,
+                                       const int* od_type, const size_t* od_stride, int nscen, const double* h_scale, int nband,
+                                       const int64_t* h_band_begin, const int64_t* h_band_end, double* h_flux_dn, double* h_flux_up,
+                                       double* d_surf_dn, double* d_toa_up);
+int ecckd_lbl_band_fluxes_sw_scenarios(ecckd_ctx* ctx, int nlay, size_t nwav, int nsza, const double* h_cos_sza, const double* d_ssi,
+                                       const double* d_albedo, int ngas, const void* const* d_od, const int* od_type,
+                                       const size_t* od_stride, int nscen, const double* h_scale, int nband,
+                                       const int64_t* h_band_begin, const int64_t* h_band_end, double* h_flux_dn_direct,
+                                       double* h_flux_up, double* d_surf_dn_direct, double* d_toa_up);
+/* Slots per launch of the two calls above at nlay layers (0: more layers than the accumulator holds; no device needed). */
+int ecckd_lbl_scenarios_slots(int shortwave, int nlay);
+
 /* ---- NetCDF classic files (file parts of a1, a9, a21) ----------------------------
  * A self-contained reader / writer for the classic on-disk formats CDF-1, CDF-2 (64-bit offset)
  * and CDF-5 (64-bit data): what the reference reads / writes for *.nc, *.cdf names
