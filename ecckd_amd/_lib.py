@@ -244,6 +244,12 @@ SIGNATURES = {
     "ecckd_find_g_gases_begin": (C.c_int, [C.c_double, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "ecckd_find_g_gases_add": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ecckd_find_g_gases_wait": (C.c_int, [C.c_void_p]),
+    "ecckd_target_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, _c_double_p, C.POINTER(C.c_int),
+                                      C.POINTER(C.c_int), C.POINTER(C.c_int), _c_double_p, C.POINTER(C.c_int), C.c_int]),
+    "ecckd_find_g_gases_target": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.c_int,
+                                            _c_double_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _c_double_p, C.POINTER(C.c_int),
+                                            _c_double_p, C.POINTER(C.c_int), C.c_int]),
+    "ecckd_find_g_gases_target_observe": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ecckd_opt_set_allreduce": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "ecckd_cfg_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "ecckd_cfg_from_args": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]),
@@ -321,6 +327,8 @@ class OptConfig(C.Structure):
 
 TRACE_FN = C.CFUNCTYPE(None, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p)
 ERROR_FN = C.CFUNCTYPE(C.c_int, C.c_int, _c_double_p, _c_double_p, _c_double_p, C.c_void_p)
+COUNT_FN = C.CFUNCTYPE(C.c_int, C.c_double, C.POINTER(C.c_int), C.c_void_p)                  # ecckd_count_fn
+TARGET_TRIAL_FN = C.CFUNCTYPE(None, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p)   # ecckd_target_trial_fn
 EVALUATOR_FN = C.CFUNCTYPE(C.c_int, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p)   # ecckd_evaluator_fn
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_int, C.c_double, C.c_double, C.c_void_p)                 # ecckd_progress_fn
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)   # ecckd_allreduce_fn

@@ -554,6 +554,37 @@ class GasLW:
         return out
 
 
+def _gas_request(gas, ibegin, iend, heating_rate_tolerance, options, capacity, keep):
+    """One ecckd_gas_search (arguments as Gas.find_g_bands_ex) -> (the struct, its output arrays); what the struct points to
+    is appended to `keep`."""
+    nband = len(ibegin)
+    ib = np.ascontiguousarray(ibegin, dtype=np.uint64)
+    ie = np.ascontiguousarray(iend, dtype=np.uint64)
+    tol = np.ascontiguousarray(np.broadcast_to(np.asarray(heating_rate_tolerance, dtype=np.float64), (nband,)))
+    opts = (_lib.BandOptions * nband)()
+    for j in range(nband):
+        opts[j] = gas._band_options(keep, **((options[j] if options else None) or {}))
+    b = np.zeros((nband, capacity + 1)); e = np.zeros((nband, capacity))
+    r1 = np.zeros((nband, capacity), dtype=np.int64); r2 = np.zeros((nband, capacity), dtype=np.int64)
+    ng = np.zeros(nband, dtype=np.int32); st = np.zeros(nband, dtype=np.int32); cc = np.zeros(nband)
+    q = _lib.GasSearch()
+    q.gas, q.nband = gas.handle, nband
+    q.ibegin, q.iend = ib.ctypes.data_as(C.POINTER(C.c_size_t)), ie.ctypes.data_as(C.POINTER(C.c_size_t))
+    q.heating_rate_tolerance, q.opt = _hptr(tol), C.cast(opts, C.c_void_p)
+    q.ng, q.bounds, q.error = ng.ctypes.data_as(C.POINTER(C.c_int)), _hptr(b), _hptr(e)
+    q.rank1, q.rank2 = r1.ctypes.data_as(C.POINTER(C.c_int64)), r2.ctypes.data_as(C.POINTER(C.c_int64))
+    q.capacity, q.status, q.comp_cost = capacity, st.ctypes.data_as(C.POINTER(C.c_int)), _hptr(cc)
+    keep += [ib, ie, tol, opts, gas]
+    return q, (nband, b, e, r1, r2, ng, st, cc)
+
+
+def _gas_results(out):
+    """The per-band result dicts of one gas from the output arrays of _gas_request."""
+    nband, b, e, r1, r2, ng, st, cc = out
+    return [dict(status=int(st[j]), bounds=b[j, :ng[j] + 1].copy(), error=e[j, :ng[j]].copy(), rank1=r1[j, :ng[j]].copy(),
+                 rank2=r2[j, :ng[j]].copy(), comp_cost=float(cc[j])) for j in range(nband)]
+
+
 class GasSearchJob:
     """The band searches of several prepared gases side by side on one device (ecckd_find_g_gases_begin / _add / _wait: one host
     thread and one HIP stream per gas, every gas the launch trains it runs alone).  add() starts a gas's search at once and
@@ -571,35 +602,16 @@ class GasSearchJob:
 
     def add(self, gas, ibegin, iend, heating_rate_tolerance, options=None):
         """Start the search of the bands [ibegin[k], iend[k]] of `gas` (arguments as Gas.find_g_bands_ex)."""
-        capacity = self.capacity
-        nband = len(ibegin)
-        ib = np.ascontiguousarray(ibegin, dtype=np.uint64)
-        ie = np.ascontiguousarray(iend, dtype=np.uint64)
-        tol = np.ascontiguousarray(np.broadcast_to(np.asarray(heating_rate_tolerance, dtype=np.float64), (nband,)))
-        opts = (_lib.BandOptions * nband)()
-        for j in range(nband):
-            opts[j] = gas._band_options(self._keep, **((options[j] if options else None) or {}))
-        b = np.zeros((nband, capacity + 1)); e = np.zeros((nband, capacity))
-        r1 = np.zeros((nband, capacity), dtype=np.int64); r2 = np.zeros((nband, capacity), dtype=np.int64)
-        ng = np.zeros(nband, dtype=np.int32); st = np.zeros(nband, dtype=np.int32); cc = np.zeros(nband)
-        q = _lib.GasSearch()
-        q.gas, q.nband = gas.handle, nband
-        q.ibegin, q.iend = ib.ctypes.data_as(C.POINTER(C.c_size_t)), ie.ctypes.data_as(C.POINTER(C.c_size_t))
-        q.heating_rate_tolerance, q.opt = _hptr(tol), C.cast(opts, C.c_void_p)
-        q.ng, q.bounds, q.error = ng.ctypes.data_as(C.POINTER(C.c_int)), _hptr(b), _hptr(e)
-        q.rank1, q.rank2 = r1.ctypes.data_as(C.POINTER(C.c_int64)), r2.ctypes.data_as(C.POINTER(C.c_int64))
-        q.capacity, q.status, q.comp_cost = capacity, st.ctypes.data_as(C.POINTER(C.c_int)), _hptr(cc)
-        self._keep += [ib, ie, tol, opts, q, gas]
-        self._out.append((nband, b, e, r1, r2, ng, st, cc))
+        q, out = _gas_request(gas, ibegin, iend, heating_rate_tolerance, options, self.capacity, self._keep)
+        self._keep.append(q)
+        self._out.append(out)
         gas.ctx.fence_from_torch()
         check(self.lib.ecckd_find_g_gases_add(self.handle, C.byref(q)))
 
     def wait(self):
         h, self.handle = self.handle, None
         check(self.lib.ecckd_find_g_gases_wait(h))
-        res = [[dict(status=int(st[j]), bounds=b[j, :ng[j] + 1].copy(), error=e[j, :ng[j]].copy(), rank1=r1[j, :ng[j]].copy(),
-                     rank2=r2[j, :ng[j]].copy(), comp_cost=float(cc[j])) for j in range(nband)]
-               for nband, b, e, r1, r2, ng, st, cc in self._out]
+        res = [_gas_results(out) for out in self._out]
         self._keep, self._out = [], []
         return res
 
@@ -630,6 +642,79 @@ def find_g_gases(gases, requests, tolerance_tolerance=0.02, max_iterations=60, m
             pass
         raise first_error
     return job.wait()
+
+
+TARGET_STATUS = {0: "target hit", 1: "resolution reached", 2: "maximum number of trials reached", 3: "target out of reach"}
+
+
+def target_search(fn, target, resolution=1e-3, max_trials=40, capacity=None):
+    """The tolerance scaling s at which the step function fn(s) -> number of g points gives `target` (ecckd_target_search:
+    s = 1, bracketing by factors of two within [2^-20, 2^20], geometric bisection; see include/ecckd_hip.h).
+    -> dict(scaling, ng, status, trials=[(scaling, ng), ...]); status 0 hit, 1 resolution, 2 max_trials, 3 out of reach.
+    An exception in fn ends the search with PROCESSING_ERROR."""
+    lib = _lib.load_library()
+    cb = None
+    if fn is not None:
+        def count(s, ng, _user):
+            try:
+                ng[0] = int(fn(s))
+                return 0
+            except EcckdError as exc:
+                return exc.code or _lib.PROCESSING_ERROR
+            except Exception:  # noqa: BLE001
+                import traceback
+                traceback.print_exc()
+                return _lib.PROCESSING_ERROR
+        cb = _lib.COUNT_FN(count)
+    capacity = max(int(max_trials), 1) if capacity is None else int(capacity)
+    ts, tn = np.zeros(max(capacity, 1)), np.zeros(max(capacity, 1), dtype=np.int32)
+    scaling, ng, st, nt = C.c_double(), C.c_int(), C.c_int(), C.c_int()
+    check(lib.ecckd_target_search(C.cast(cb, C.c_void_p) if cb is not None else None, None, int(target), float(resolution),
+                                  int(max_trials), C.byref(scaling), C.byref(ng), C.byref(st), C.byref(nt), _hptr(ts),
+                                  tn.ctypes.data_as(C.POINTER(C.c_int)), capacity))
+    return dict(scaling=scaling.value, ng=ng.value, status=st.value,
+                trials=[(float(ts[i]), int(tn[i])) for i in range(nt.value)])
+
+
+def find_g_gases_target(gases, requests, ng_offset, target, resolution=1e-3, max_trials=40, tolerance_tolerance=0.02,
+                        max_iterations=60, max_concurrent=0, capacity=1024, trial_capacity=None, on_trial=None):
+    """The searches of find_g_gases at the tolerance scaling that gives `target` g points in total (ecckd_find_g_gases_target):
+    every trial multiplies the requests' tolerances by one factor, searches the gases as prepared (their memos of interval errors
+    carry over from trial to trial) and counts ng_offset + the g points of all gases and bands.
+    on_trial(trial, scaling, ng_total, ng_per_gas): called after every trial.
+    -> (per gas the list of per-band result dicts at the chosen scaling,
+        dict(scaling, ng, status, tolerance_used=[per gas the tolerances of its bands], trials=[(scaling, ng), ...]))."""
+    lib = _lib.load_library()
+    ngas = len(gases)
+    keep, outs = [], []
+    reqs = (_lib.GasSearch * max(ngas, 1))()
+    for k, (gas, r) in enumerate(zip(gases, requests)):
+        reqs[k], out = _gas_request(gas, r["ibegin"], r["iend"], r["heating_rate_tolerance"], r.get("options"), capacity, keep)
+        outs.append(out)
+    nbands = [out[0] for out in outs]
+    trial_capacity = max(int(max_trials), 1) + 1 if trial_capacity is None else int(trial_capacity)
+    ts, tn = np.zeros(max(trial_capacity, 1)), np.zeros(max(trial_capacity, 1), dtype=np.int32)
+    used = np.zeros(max(sum(nbands), 1))
+    scaling, ng, st, nt = C.c_double(), C.c_int(), C.c_int(), C.c_int()
+    observer = None
+    if on_trial is not None:
+        observer = _lib.TARGET_TRIAL_FN(lambda i, s, n, m, per_gas, _u: on_trial(i, s, n, [per_gas[k] for k in range(m)]))
+        check(lib.ecckd_find_g_gases_target_observe(C.cast(observer, C.c_void_p), None))
+    for gas in gases:
+        gas.ctx.fence_from_torch()
+    try:
+        check(lib.ecckd_find_g_gases_target(ngas, C.cast(reqs, C.c_void_p), int(ng_offset), int(target), float(resolution),
+                                            int(max_trials), float(tolerance_tolerance), int(max_iterations), int(max_concurrent),
+                                            C.byref(scaling), C.byref(ng), C.byref(st), _hptr(used), C.byref(nt), _hptr(ts),
+                                            tn.ctypes.data_as(C.POINTER(C.c_int)), trial_capacity))
+    finally:
+        if observer is not None:
+            lib.ecckd_find_g_gases_target_observe(None, None)
+    offs = np.concatenate([[0], np.cumsum(nbands)]).astype(int)
+    info = dict(scaling=scaling.value, ng=ng.value, status=st.value,
+                tolerance_used=[used[offs[k]:offs[k + 1]].copy() for k in range(ngas)],
+                trials=[(float(ts[i]), int(tn[i])) for i in range(nt.value)])
+    return [_gas_results(out) for out in outs], info
 
 
 def regroup_rank_by_wavenumber(ctx, wavenumber, rank, rank_lo, rank_hi, wn_bound):

@@ -11,6 +11,16 @@
 // log_level; per gas <gas>.input / scaling / conc, <gas>.background_input / _scaling / _conc, reordering_input,
 // min_scaling, max_scaling, g_split + subband_wavenumber_boundary, base_split, base_wavenumber_boundary,
 // min_g_points, max_g_points.
+// Extension keys for asking for a NUMBER of g points instead of a tolerance (the reference's scripts keep hand-found tables of
+// the tolerance per g-point count, test/do_all_lw.sh:44-65): target_g_points = n switches the mode on: every gas is read and
+// prepared first and stays resident, then ONE call (ecckd_find_g_gases_target) searches the gases again and again with all
+// tolerances multiplied by one factor - heating_rate_tolerance is the first guess and fixes the ratio between the bands - until
+// the overlap of the gases has n g points; target_resolution (1e-3: the factor is not refined below this relative width) and
+// target_max_trials (40) bound the search; target_exact = 1 makes a search that does not hit n exactly a PROCESSING_ERROR that
+// writes no file.  The g-points file then also holds target_g_points, target_search_status (0 hit, 1 resolution reached,
+// 2 trials spent, 3 out of reach), heating_rate_tolerance_scaling, heating_rate_tolerance(band) - the tolerances used, with
+// which a plain run gives the same file - and the trials, target_trial_scaling / target_trial_n_g_points(target_trial).
+// Not with WORLD_SIZE > 1, cloud, sequential_bands or a base_wavenumber_boundary inside a band (PARAMETER_ERROR).
 // All nwav-sized work runs on the GPU through include/ecckd_hip.h; this file is the driver around it.
 //
 // Several processes, one per GPU (RANK / WORLD_SIZE / LOCAL_RANK from the launcher, e.g. torchrun --no-python): the (gas, band)
@@ -192,6 +202,36 @@ int main(int argc, char** argv) {
 
     const int world = std::max(1, env_int("WORLD_SIZE", 1)), my_rank = env_int("RANK", 0);
     if (my_rank < 0 || my_rank >= world) fail(ECCKD_PARAMETER_ERROR, "RANK=%d outside WORLD_SIZE=%d", my_rank, world);
+    // ---- target_g_points: the tolerance is searched for (see the head of this file) ----
+    int target_g_points = 0, target_max_trials = 40;
+    double target_resolution = 1.0e-3;
+    bool target_exact = false;
+    const bool target_mode = config.read(target_g_points, "target_g_points");
+    config.read(target_resolution, "target_resolution");
+    config.read(target_max_trials, "target_max_trials");
+    config.read(target_exact, "target_exact");
+    if (target_mode) {
+      // refused here, before the device starts and before any other process is waited for
+      bool one_band_at_a_time = false;
+      config.read(one_band_at_a_time, "sequential_bands");
+      if (world > 1) fail(ECCKD_PARAMETER_ERROR, "target_g_points needs all gases in one process (WORLD_SIZE=%d): a trial would need an all-reduce", world);
+      if (have_cloud) fail(ECCKD_PARAMETER_ERROR, "target_g_points cannot be combined with cloud");
+      if (one_band_at_a_time) fail(ECCKD_PARAMETER_ERROR, "target_g_points cannot be combined with sequential_bands");
+      if (target_g_points < 1) fail(ECCKD_PARAMETER_ERROR, "target_g_points = %d, must be at least 1", target_g_points);
+      for (const std::string& gas_str : config.read_list("gases")) {
+        std::vector<double> boundary;
+        std::string reordering_input;
+        if (!config.read(boundary, "base_wavenumber_boundary", gas_str.c_str()) || boundary.empty()) continue;
+        if (!config.read(reordering_input, "reordering_input", gas_str.c_str())) fail(ECCKD_PARAMETER_ERROR, "No reordering_input found");
+        NcIn f(paths.find(reordering_input));
+        const std::vector<double> b1 = f.read("wavenumber1_band"), b2 = f.read("wavenumber2_band");
+        for (size_t b = 0; b < b1.size() && b < b2.size(); ++b)
+          for (double w : boundary)
+            if (w > b1[b] && w < b2[b])
+              fail(ECCKD_PARAMETER_ERROR, "target_g_points: %s.base_wavenumber_boundary %g lies inside band %zu: that split re-ranks the "
+                   "spectrum during the search, so the gas cannot be searched more than once", gas_str.c_str(), w, b);
+      }
+    }
     const uint64_t run_id = run_identity(config, world);
     if (world > 1) {
       // before anything that can fail (device start-up, the gas list, the files): never a stale part or marker of an earlier
@@ -379,7 +419,7 @@ int main(int argc, char** argv) {
 
       // all gases of the run stay resident until their searches are over: when the device runs short (3 x nlay + 8 rows of
       // doubles per gas, and the spectra it is made from while it is prepared), the searches in flight are finished first
-      if (!pending.empty() && nwav > 0) {
+      if (!pending.empty() && nwav > 0 && !target_mode) {   // (a target search needs every gas resident: it fails rather than flush)
         size_t free_b = 0, total_b = 0;
         const double need = 6.0 * 60.0 * 8.0 * (double)nwav;
         ck(ecckd_mem_info(dev.ctx(), &free_b, &total_b));
@@ -586,11 +626,58 @@ int main(int argc, char** argv) {
         rq.opt = gj.opts.data(); rq.ng = gj.ngs.data(); rq.bounds = gj.bounds.data(); rq.error = gj.error.data();
         rq.rank1 = gj.r1.data(); rq.rank2 = gj.r2.data(); rq.capacity = band_capacity; rq.status = gj.statuses.data();
         rq.comp_cost = gj.comp_costs.data();
-        if (!search_job) ck(ecckd_find_g_gases_begin(tolerance_tolerance, max_iterations, gases_side_by_side, &search_job));
-        ck(ecckd_find_g_gases_add(search_job, &rq));
-        if (gases_side_by_side == 1) flush();
+        if (!target_mode) {
+          if (!search_job) ck(ecckd_find_g_gases_begin(tolerance_tolerance, max_iterations, gases_side_by_side, &search_job));
+          ck(ecckd_find_g_gases_add(search_job, &rq));
+          if (gases_side_by_side == 1) flush();
+        }                                   // (target_g_points: searched below, once every gas is prepared)
       }
       LOG("\n");
+    }
+    // ---- target_g_points: all gases are prepared and resident; one blocking call searches them, trial after trial ----
+    int target_status = 0, target_ng = 0;
+    double target_scaling = 1.0;
+    std::vector<double> target_tolerance, target_trial_scaling;
+    std::vector<int> target_trial_ng;
+    if (target_mode) {
+      LOG("*** SEARCHING FOR THE TOLERANCE SCALING THAT GIVES %d G POINTS\n", target_g_points);
+      std::vector<ecckd_gas_search> reqs;
+      for (GasJob& gj : pending) reqs.push_back(gj.req);
+      const int capacity = std::max(1, target_max_trials) + 1;
+      int ntrial = 0;
+      target_tolerance.assign((size_t)ngas * nband, 0.0);
+      target_trial_scaling.assign(capacity, 0.0);
+      target_trial_ng.assign(capacity, 0);
+      struct Names { const std::vector<std::string>* gas; } names{&gas_list};
+      ck(ecckd_find_g_gases_target_observe(
+          [](int trial, double scaling, int ng_total, int n, const int* ng_per_gas, void* user) {
+            std::string per_gas;
+            for (int k = 0; k < n; ++k) per_gas += " " + (*static_cast<Names*>(user)->gas)[k] + " " + std::to_string(ng_per_gas[k]);
+            LOG("  Trial %d: scaling %.17g: %d g points (%s )\n", trial, scaling, ng_total, per_gas.c_str());
+          },
+          &names));
+      const int rc = ecckd_find_g_gases_target((int)reqs.size(), reqs.data(), nband * (1 - ngas), target_g_points, target_resolution,
+                                               target_max_trials, tolerance_tolerance, max_iterations, gases_side_by_side, &target_scaling,
+                                               &target_ng, &target_status, target_tolerance.data(), &ntrial, target_trial_scaling.data(),
+                                               target_trial_ng.data(), capacity);
+      ecckd_find_g_gases_target_observe(nullptr, nullptr);
+      ck(rc);
+      target_trial_scaling.resize(ntrial);
+      target_trial_ng.resize(ntrial);
+      target_tolerance.resize(nband);         // every gas has the same tolerances: those of the first
+      static const char* const outcome[] = {"the target was hit", "the scaling is resolved and the count steps over the target",
+                                            "the trials are spent", "the target is out of reach"};
+      LOG("  %d trials: %d g points at scaling %.17g (%s)\n", ntrial, target_ng, target_scaling, outcome[target_status & 3]);
+      std::string used;
+      for (double t : target_tolerance) {
+        char buf[40];
+        std::snprintf(buf, sizeof buf, " %.17g", t);
+        used += buf;
+      }
+      LOG("  heating_rate_tolerance used:%s\n\n", used.c_str());
+      if (target_exact && target_status != 0)
+        fail(ECCKD_PROCESSING_ERROR, "target_exact: no tolerance scaling gives %d g points (nearest: %d at scaling %.17g, search status %d)",
+             target_g_points, target_ng, target_scaling, target_status);
     }
     flush();
     if (first_lw_gas) ck(ecckd_gas_destroy(first_lw_gas));
@@ -762,6 +849,15 @@ int main(int argc, char** argv) {
       file.var(m + "_g_min", NC_INT_T, {"g_point"}, "First single-gas g point contributing to each merged g point");
       file.var(m + "_g_max", NC_INT_T, {"g_point"}, "Last single-gas g point contributing to each merged g point");
     }
+    if (target_mode) {
+      file.dim("target_trial", target_trial_scaling.size());
+      file.var("target_g_points", NC_INT_T, {}, "Number of g points asked for");
+      file.var("target_search_status", NC_INT_T, {}, "Outcome of the search for the tolerance scaling (0 target hit, 1 resolution reached, 2 trials spent, 3 out of reach)");
+      file.var("heating_rate_tolerance_scaling", NC_DOUBLE_T, {}, "Factor applied to the configured heating-rate tolerance");
+      file.var("heating_rate_tolerance", NC_DOUBLE_T, {"band"}, "Heating-rate tolerance used in each band", "K d-1");
+      file.var("target_trial_scaling", NC_DOUBLE_T, {"target_trial"}, "Tolerance scaling of each trial");
+      file.var("target_trial_n_g_points", NC_INT_T, {"target_trial"}, "Total number of g points of each trial");
+    }
     file.var("wavenumber", NC_DOUBLE_T, {"wavenumber"}, "Wavenumber", "cm-1");
     file.var("g_point", NC_SHORT_T, {"wavenumber"}, "G point of each wavenumber");
     file.deflate("g_point");                                               // find_g_points.cpp:1580
@@ -798,6 +894,14 @@ int main(int argc, char** argv) {
       file.write_as_double(m + "_g_min", g.g_min);
       file.write_as_double(m + "_g_max", g.g_max);
       file.write_as_double(m + "_g_point", g.d_g_point.download<int32_t>());
+    }
+    if (target_mode) {
+      file.write("target_g_points", {(double)target_g_points});
+      file.write("target_search_status", {(double)target_status});
+      file.write("heating_rate_tolerance_scaling", {target_scaling});
+      file.write("heating_rate_tolerance", target_tolerance);
+      file.write("target_trial_scaling", target_trial_scaling);
+      file.write_as_double("target_trial_n_g_points", target_trial_ng);
     }
     file.write("wavenumber", wavenumber);
     file.write_as_double("g_point", g_point);

@@ -527,9 +527,11 @@ def subtract_lbl_fluxes(scene, source):
 # ---- g-points file (find_g_points.cpp:1487-1660) ------------------------------------------------------------
 
 def write_g_points(path, band_bound1, band_bound2, band_number, gases, wavenumber, g_point, solar_irradiance=None,
-                   config_str="", history=None):
+                   config_str="", history=None, target=None):
     """gases: list of dict(name, n_g_points[nband], band_number, rank1, rank2, error, sorting_variable, g_min, g_max,
-    g_point[nwav]) as SingleGasData holds them."""
+    g_point[nwav]) as SingleGasData holds them.
+    target: None, or what a search for a number of g points adds to the file (find_g_points target_g_points=n):
+    dict(target_g_points, status, scaling, tolerance_used[nband], trials=[(scaling, ng), ...])."""
     w = NcWriter(path)
     ng = len(band_number)
     w.define_dimension("band", len(band_bound1))
@@ -553,6 +555,14 @@ def write_g_points(path, band_bound1, band_bound2, band_number, gases, wavenumbe
         w.define_variable(m + "_sorting_variable", "float", d)
         w.define_variable(m + "_g_min", "int", "g_point")
         w.define_variable(m + "_g_max", "int", "g_point")
+    if target is not None:
+        w.define_dimension("target_trial", len(target["trials"]))
+        w.define_variable("target_g_points", "int")
+        w.define_variable("target_search_status", "int")
+        w.define_variable("heating_rate_tolerance_scaling", "double")
+        w.define_variable("heating_rate_tolerance", "double", "band")
+        w.define_variable("target_trial_scaling", "double", "target_trial")
+        w.define_variable("target_trial_n_g_points", "int", "target_trial")
     w.define_variable("wavenumber", "double", "wavenumber")
     w.define_variable("g_point", "short", "wavenumber")
     w.deflate_variable("g_point")                                          # find_g_points.cpp:1580
@@ -574,6 +584,13 @@ def write_g_points(path, band_bound1, band_bound2, band_number, gases, wavenumbe
         m = g["name"]
         for k in ("n_g_points", "band_number", "rank1", "rank2", "error", "sorting_variable", "g_min", "g_max", "g_point"):
             w.write(m + "_" + k, g[k])
+    if target is not None:
+        w.write("target_g_points", [int(target["target_g_points"])])
+        w.write("target_search_status", [int(target["status"])])
+        w.write("heating_rate_tolerance_scaling", [float(target["scaling"])])
+        w.write("heating_rate_tolerance", np.asarray(target["tolerance_used"], dtype=np.float64))
+        w.write("target_trial_scaling", np.asarray([t[0] for t in target["trials"]], dtype=np.float64))
+        w.write("target_trial_n_g_points", np.asarray([t[1] for t in target["trials"]], dtype=np.int32))
     w.write("wavenumber", wavenumber)
     w.write("g_point", g_point)
     w.close()

@@ -529,7 +529,8 @@ def _per_gas_tables(names, nband, by_task):
 def find_g_points(ctx, gases, band_bound1, band_bound2, heating_rate_tolerance, output_path=None, averaging_method="transmission",
                   flux_weight=0.02, min_pressure=0.0, tolerance_tolerance=0.02, max_iterations=60, iprofile=0, ssi=None,
                   max_no_rayleigh_wavenumber=10000.0, reference_albedo=0.15, cos_sza=0.5, sequential_bands=False,
-                  rank=None, world_size=None, group=None, cloud=None):
+                  rank=None, world_size=None, group=None, cloud=None, target_g_points=None, target_resolution=1e-3,
+                  target_max_trials=40, target_exact=False):
     """The main loop of find_g_points.cpp:655-1660 over classic files (shortwave when `ssi[nwav]` is given: solar weights,
     reference albedo 0.15 below max_no_rayleigh_wavenumber (:469, :522, :757-761, :921-923), REFERENCE_COS_SZA = 0.5,
     per-gas min_scaling / max_scaling (:661-667)): per gas the merged background, the gas
@@ -548,7 +549,15 @@ def find_g_points(ctx, gases, band_bound1, band_bound2, heating_rate_tolerance, 
     `cost_sum` and `comp_cost_sum`, identical on every rank.  The g points do not depend on the number of processes.
 
     cloud: None, or (shortwave only) dict(name, reordering_input, max_reflectance_range=0.26): the cloud pseudo-gas of :543-652,
-    partitioned by rank 0 after the gases' searches and the first constituent of the overlap (:1448-1451)."""
+    partitioned by rank 0 after the gases' searches and the first constituent of the overlap (:1448-1451).
+
+    target_g_points: None, or the number of g points wanted (the tool's target_g_points key).  heating_rate_tolerance is then the
+    first guess and fixes the ratio between the bands: every gas is prepared first and stays resident, and one call
+    (api.find_g_gases_target) searches all of them again and again with the tolerances multiplied by one factor until the
+    overlap has that many g points (target_resolution, target_max_trials: the bounds of that search; target_exact: a search
+    that does not hit the number exactly raises PROCESSING_ERROR and writes nothing).  The result gains
+    `target` = dict(target_g_points, scaling, ng, status, tolerance_used[nband], trials) and the file the tool's extra variables.
+    One process only, and neither cloud nor sequential_bands (PARAMETER_ERROR)."""
     import torch
     if cloud is not None and ssi is None:
         raise EcckdError(PARAMETER_ERROR, "Don't yet know how to sort cloud properties in the longwave")
@@ -556,6 +565,17 @@ def find_g_points(ctx, gases, band_bound1, band_bound2, heating_rate_tolerance, 
     nband = len(band_bound1)
     ngas = len(gases)
     rank, world_size, tasks, mine, my_bands = _deal(ngas, nband, rank, world_size, group)
+    target_mode = target_g_points is not None
+    if target_mode:
+        if world_size > 1:
+            raise EcckdError(PARAMETER_ERROR, "target_g_points needs all gases in one process: a trial would need an all-reduce")
+        if cloud is not None:
+            raise EcckdError(PARAMETER_ERROR, "target_g_points cannot be combined with cloud")
+        if sequential_bands:
+            raise EcckdError(PARAMETER_ERROR, "target_g_points cannot be combined with sequential_bands")
+        if int(target_g_points) < 1:
+            raise EcckdError(PARAMETER_ERROR, "target_g_points = %d, must be at least 1" % int(target_g_points))
+    prepared = []                  # target_g_points: (gas index, g, gas handle, sorting variable sorted, band albedo)
     tol = np.broadcast_to(np.asarray(heating_rate_tolerance, dtype=np.float64), (nband,))           # :762-771
     first_lw_gas = None
     planck_first = None            # the first gas's Planck matrix where this process does not prepare the first gas itself
@@ -602,6 +622,13 @@ def find_g_points(ctx, gases, band_bound1, band_bound2, heating_rate_tolerance, 
             sw = dict(ssi=torch.as_tensor(np.asarray(ssi, dtype=np.float64), device=dev), cos_sza=cos_sza,
                       band_albedo=np.where(no_ray, reference_albedo, 0.0),                            # :756-760
                       albedo=torch.as_tensor(np.where(wn < wn_limit, reference_albedo, 0.0), device=dev))   # :921-923
+        if target_mode:
+            # prepared and kept resident; searched below, once every gas is prepared
+            gas, sv_sorted, band_albedo = _prepare_gas(ctx, g, averaging_method, flux_weight, min_pressure, reuse, sw)
+            prepared.append((gi, g, gas, sv_sorted, band_albedo))
+            if ssi is None and gi == 0:
+                first_lw_gas = gas
+            continue
         gas, res = _search_gas(ctx, g, my_bands[gi], tol, tolerance_tolerance, max_iterations, averaging_method, flux_weight,
                                min_pressure, sequential_bands, reuse, sw)
         local += [(gi, b, r) for b, r in res]
@@ -609,6 +636,24 @@ def find_g_points(ctx, gases, band_bound1, band_bound2, heating_rate_tolerance, 
             first_lw_gas = gas
         else:
             gas.close()
+    target = None
+    if target_mode:
+        reqs = [_band_requests(g, my_bands[gi], tol, band_albedo) for gi, g, _, _, band_albedo in prepared]
+        try:
+            found, info = api.find_g_gases_target([p[2] for p in prepared], reqs, nband * (1 - ngas), int(target_g_points),
+                                                  target_resolution, target_max_trials, tolerance_tolerance, max_iterations)
+            if target_exact and info["status"] != 0:
+                raise EcckdError(PROCESSING_ERROR, "target_exact: no tolerance scaling gives %d g points (nearest: %d at scaling %.17g, "
+                                 "search status %d)" % (int(target_g_points), info["ng"], info["scaling"], info["status"]))
+            for (gi, g, gas, sv_sorted, _), band_res in zip(prepared, found):
+                local += [(gi, b, r) for b, r in _finish_gas(gas, g, my_bands[gi], band_res, sv_sorted)]
+        finally:
+            for _, _, gas, _, _ in prepared:
+                if gas is not first_lw_gas:
+                    gas.close()
+        # every gas has the same tolerances: those of the first
+        target = dict(target_g_points=int(target_g_points), scaling=info["scaling"], ng=info["ng"], status=info["status"],
+                      tolerance_used=info["tolerance_used"][0], trials=info["trials"])
     if first_lw_gas is not None:
         first_lw_gas.close()
     planck_first = None
@@ -637,8 +682,10 @@ def find_g_points(ctx, gases, band_bound1, band_bound2, heating_rate_tolerance, 
         g["g_min"], g["g_max"] = g_min[k], g_max[k]
     result = dict(ng=ng, band_number=band_number, g_point=g_point.cpu().numpy(), n_unassigned=n_unassigned, gases=per_gas,
                   wavenumber=wn, cost_sum=cost_sum, comp_cost_sum=comp_sum, rank=0, tasks=mine)
+    if target is not None:
+        result["target"] = target
     if output_path is not None:
-        ncio.write_g_points(output_path, band_bound1, band_bound2, band_number, per_gas, wn, result["g_point"])
+        ncio.write_g_points(output_path, band_bound1, band_bound2, band_number, per_gas, wn, result["g_point"], target=target)
     return result
 
 

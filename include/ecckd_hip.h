@@ -392,6 +392,44 @@ int ecckd_find_g_gases_begin(double tolerance_tolerance, int max_iterations, int
 int ecckd_find_g_gases_add(ecckd_gas_search_job* job, ecckd_gas_search* req);
 int ecckd_find_g_gases_wait(ecckd_gas_search_job* job);
 
+/* ---- the tolerance that yields a wanted number of g points ---------------------
+ * The reference takes heating_rate_tolerance and reports the number of g points; its scripts keep hand-found tables of the
+ * tolerance per g-point count (test/do_all_lw.sh:44-65).  Here the count is the input.  fn(s) = the total number of g points
+ * when every band's configured tolerance is multiplied by s (non-zero return aborts, and is returned).  The search, host code
+ * (csrc/target_search.cpp):
+ *   1. s = 1; 2. bracket the target: double s while fn(s) > target, halve it while fn(s) < target, within [2^-20, 2^20];
+ *   3. bisect geometrically, mid = sqrt(lo * hi), lo the scaling with ng > target and hi the one with ng < target;
+ *   4. without an exact hit the answer is the trial with the smallest |ng - target|, among equals the one with
+ *      ng < target, then the larger scaling.
+ * status: 0 the target was hit; 1 hi / lo <= 1 + resolution (the count steps over the target there: both neighbours are in
+ * the trial list); 2 max_trials trials spent (those of the bracketing included); 3 the bracket did not close within
+ * [2^-20, 2^20] (the target is out of reach).  fn need not be monotone.  Every trial is recorded in order as
+ * (trial_scaling[i], trial_ng[i]), i < *ntrial <= capacity; a trial beyond capacity: PARAMETER_ERROR (as are target_ng < 1,
+ * resolution <= 0, max_trials < 1, fn == NULL). */
+typedef int (*ecckd_count_fn)(double scaling, int* ng, void* user);   /* non-zero aborts */
+int ecckd_target_search(ecckd_count_fn fn, void* user, int target_ng, double resolution, int max_trials,
+                        double* scaling, int* ng, int* status,
+                        int* ntrial, double* trial_scaling, int* trial_ng, int capacity);
+/* The same over the searches of prepared gases: a trial copies the requests, sets every band's tolerance to
+ * scaling * req[k].heating_rate_tolerance[b] (one multiplication; its result is the double reported in h_tolerance_used),
+ * runs ecckd_find_g_gases as it stands and counts ng_offset + sum of ng[k][b] (the overlap of the gases gives
+ * sum over bands of (1 - ngas + sum over gases of n_g_points), single_gas_data.cpp:30-38: ng_offset = nband * (1 - ngas)).
+ * The gases stay as prepared and keep their memos of interval errors from trial to trial, so a trial sweeps only intervals no
+ * earlier trial asked for, and takes the decisions of a plain run at its tolerances bit for bit.  The caller's tolerance arrays
+ * are not written.  On return the requests' outputs are those of the chosen scaling: if that was not the last trial run it is
+ * searched once more, from the memos.  A trial whose searches fail ends the call with that code.  A request with
+ * opt.nbase_wn_bound > 2 is refused (PARAMETER_ERROR) before anything runs: that split re-ranks the spectrum during a search. */
+int ecckd_find_g_gases_target(int ngas, ecckd_gas_search* req, int ng_offset, int target_ng,
+                              double resolution, int max_trials,
+                              double tolerance_tolerance, int max_iterations, int max_concurrent,
+                              double* scaling, int* ng_total, int* status,
+                              double* h_tolerance_used /* [sum of nband] in request order */,
+                              int* ntrial, double* trial_scaling, int* trial_ng, int capacity);
+/* Progress hook of ecckd_find_g_gases_target for the calling thread: fn is called after every trial (0-based, in order) with
+ * its scaling, total and the g points of every gas (ng_per_gas[ngas], summed over the gas's bands).  fn = NULL switches it off. */
+typedef void (*ecckd_target_trial_fn)(int trial, double scaling, int ng_total, int ngas, const int* ng_per_gas, void* user);
+int ecckd_find_g_gases_target_observe(ecckd_target_trial_fn fn, void* user);
+
 /* calc_median_sorting_variable (find_g_points.cpp:35-49) for n g points: the sorting variable
  * at the point where the cumulative weight (LW: surface Planck function, SW: solar irradiance,
  * :1404-1409) first reaches half of the interval's total.  d_sorting_variable_sorted[n points]
