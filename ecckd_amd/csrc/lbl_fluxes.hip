@@ -4,10 +4,10 @@
 //   longwave:  planck_function (planck_function.cpp:22-54) + radiative_transfer_lw (radiative_transfer_lw.cpp:27-60,
 //              unit surface emissivity, surface Planck function at temperature_hl(end)), fluxes summed per band;
 //   shortwave: radiative_transfer_direct_sw / _norayleigh_sw (radiative_transfer_sw.cpp:26-77).
-// One thread per wavenumber; per half level the fluxes of a block are reduced wave -> block in a fixed order and
-// written as chunk partials, which the host adds in chunk order (bitwise reproducible).
+// One thread per wavenumber, its transfer that of lbl_rt.hpp; per half level the fluxes of a block are reduced wave -> block
+// in a fixed order and written as chunk partials, which the host adds in chunk order (bitwise reproducible).
 #include "common.hpp"
-#include "fastmath.hpp"
+#include "lbl_rt.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -15,32 +15,13 @@
 
 namespace {
 
-constexpr int LBL_THREADS = 256;
-__device__ constexpr double kPlanckH = 6.62606896e-34;
-__device__ constexpr double kLightC = 2.99792458e8;
-__device__ constexpr double kPi = 3.14159265358979323846;
-
-struct BandChunk { long long i1, i2; int band; int pad; };
-
-// The zenith angles of the longwave fluxes.  n = 1 with sec = 1.66, weight = 1: the classic two-stream form the reference
-// itself uses (radiative_transfer_lw.cpp:27-60, LW_DIFFUSIVITY).  n = nangle > 0: Gauss-Legendre quadrature in mu = cos(zenith
-// angle) over one hemisphere, flux = sum_k 2 w_k mu_k L(mu_k), each L(mu_k) the same no-scattering recurrence with the slant
-// path tau / mu_k in place of 1.66 tau (CKDMIP's `nangle`, Hogan & Matricardi 2020, GMD 13, 6501-6521, section 3.2: "N angles
-// per hemisphere").  The CKDMIP tool is not among the reference's sources: its node set is unpinned, see DESIGN.md.
-constexpr int LBL_MAX_ANGLES = 16;
-struct Angles { int n; double sec[LBL_MAX_ANGLES]; double weight[LBL_MAX_ANGLES]; };
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;  // valid in lane 0
-}
+using namespace ecckd::lbl;
 
 // LDS: acc[4][2*nhl]
 template <typename OdT>
 __global__ void __launch_bounds__(LBL_THREADS)
-k_lbl_fluxes_lw(int nang, const double* __restrict__ ang /*[nang] secants, [nang] weights*/, int nlay, size_t od_stride, const BandChunk* __restrict__ chunks, const double* __restrict__ hk,
-                const double* __restrict__ wn, const double* __restrict__ dwn, const OdT* __restrict__ od,
+k_lbl_fluxes_lw(int nang, const double* __restrict__ ang /*[nang] secants, [nang] weights*/, int nlay, size_t od_stride,
+                const BandChunk* __restrict__ chunks, const double* __restrict__ hk, const double* __restrict__ wn, const double* __restrict__ dwn, const OdT* __restrict__ od,
                 double* __restrict__ partial, double* __restrict__ surf_dn /* [nwav] or NULL */,
                 double* __restrict__ toa_up /* [nwav] or NULL */) {
   extern __shared__ double s_acc[];
@@ -54,45 +35,34 @@ k_lbl_fluxes_lw(int nang, const double* __restrict__ ang /*[nang] secants, [nang
   const long long i = c.i1 + tid;
   const bool live = i <= c.i2;
   const size_t j = live ? (size_t)i : (size_t)c.i2;
-  const double inv_cm_2_Hz = 100.0 * kLightC;
-  const double freq = wn[j] * inv_cm_2_Hz;
-  const double pref = live ? (dwn[j] * 2.0 * kPlanckH * inv_cm_2_Hz * kPi / (kLightC * kLightC)) * (freq * freq * freq) : 0.0;
-  auto planck = [&](int level) { return ecckd::div_fast(pref, ecckd::exp_fast(freq * hk[level]) - 1.0); };
+  const double freq = wn_to_freq(wn[j]);
+  const double pref = live ? planck_pref(dwn[j], freq) : 0.0;
   double surf_acc = 0.0, toa_acc = 0.0;
   for (int a = 0; a < nang; ++a) {
     const double sec = ang[a], wgt = ang[nang + a];          // (uniform: scalar loads)
     const double rsec = 1.0 / sec;
-    auto layer = [&](int l, double& eps, double& fac) {
-      const double tau = (double)od[(size_t)l * od_stride + j];
-      eps = 1.0 - ecckd::exp_fast(-sec * tau);
-      fac = (eps > 1.0e-5) ? 1.0 - ecckd::div_fast(eps * rsec, tau) : 0.5 * eps;   // :41-43
-    };
+    auto layer = [&](int l, double& eps, double& fac) { lw_layer(sec, rsec, (double)od[(size_t)l * od_stride + j], eps, fac); };
     // down sweep from zero at the top of the atmosphere (:45-50); dead lanes carry pref = 0 -> all fluxes 0
     double flux = 0.0;
-    double b_prev = planck(0);
+    double b_prev = planck(pref, freq, hk[0]);
     for (int l = 0; l < nlay; ++l) {
       double eps, fac;
       layer(l, eps, fac);
-      const double b_next = planck(l + 1);
-      flux = flux * (1.0 - eps) + b_prev * (eps - fac) + b_next * fac;
-      const double s = wave_sum(wgt * flux);
-      if (lane == 0) acc_dn[l + 1] += s;
+      const double b_next = planck(pref, freq, hk[l + 1]);
+      flux = lw_step(flux, eps, fac, b_prev, b_next);
+      wave_add(&acc_dn[l + 1], lane, wgt * flux);
       b_prev = b_next;
     }
     surf_acc += wgt * flux;                         // the spectral flux at the boundary (do_write_spectral_boundary_fluxes)
     // surface: emissivity 1, Planck function at temperature_hl(end) (:52-53)
-    flux = b_prev * 1.0 + (1.0 - 1.0) * flux;
-    {
-      const double s = wave_sum(wgt * flux);
-      if (lane == 0) acc_up[nlay] += s;
-    }
+    flux = lw_surface(flux, b_prev);
+    wave_add(&acc_up[nlay], lane, wgt * flux);
     for (int l = nlay - 1; l >= 0; --l) {                                    // :55-59
       double eps, fac;
       layer(l, eps, fac);
-      const double b_l = planck(l);
-      flux = flux * (1.0 - eps) + b_prev * (eps - fac) + b_l * fac;
-      const double s = wave_sum(wgt * flux);
-      if (lane == 0) acc_up[l] += s;
+      const double b_l = planck(pref, freq, hk[l]);
+      flux = lw_step(flux, eps, fac, b_prev, b_l);
+      wave_add(&acc_up[l], lane, wgt * flux);
       b_prev = b_l;
     }
     toa_acc += wgt * flux;
@@ -101,7 +71,7 @@ k_lbl_fluxes_lw(int nang, const double* __restrict__ ang /*[nang] secants, [nang
   if (toa_up && live) toa_up[j] = toa_acc;
   __syncthreads();
   for (int t = tid; t < 2 * nhl; t += LBL_THREADS)
-    partial[(size_t)blockIdx.x * 2 * nhl + t] = ((s_acc[t] + s_acc[2 * nhl + t]) + s_acc[4 * nhl + t]) + s_acc[6 * nhl + t];
+    partial[(size_t)blockIdx.x * 2 * nhl + t] = add_waves(s_acc, 2 * nhl, t);
 }
 
 template <typename OdT>
@@ -123,33 +93,25 @@ k_lbl_fluxes_sw(int nlay, size_t od_stride, const BandChunk* __restrict__ chunks
   const size_t j = live ? (size_t)i : (size_t)c.i2;
   const double minus_sec_sza = -1.0 / cos_sza;
   double flux = live ? cos_sza * ssi[j] : 0.0;                              // radiative_transfer_sw.cpp:39
-  {
-    const double s = wave_sum(flux);
-    if (lane == 0) acc_dn[0] += s;
-  }
+  wave_add(&acc_dn[0], lane, flux);
   for (int l = 0; l < nlay; ++l) {
     flux = flux * exp(minus_sec_sza * (double)od[(size_t)l * od_stride + j]);
-    const double s = wave_sum(flux);
-    if (lane == 0) acc_dn[l + 1] += s;
+    wave_add(&acc_dn[l + 1], lane, flux);
   }
   if (surf_dn && live) surf_dn[j] = flux;
   if (toa_up && live && !albedo) toa_up[j] = 0.0;
   if (albedo) {                                                             // :70-76
     flux = flux * albedo[j];
-    {
-      const double s = wave_sum(flux);
-      if (lane == 0) acc_up[nlay] += s;
-    }
+    wave_add(&acc_up[nlay], lane, flux);
     for (int l = nlay - 1; l >= 0; --l) {
       flux = flux * exp(-2.0 * (double)od[(size_t)l * od_stride + j]);
-      const double s = wave_sum(flux);
-      if (lane == 0) acc_up[l] += s;
+      wave_add(&acc_up[l], lane, flux);
     }
     if (toa_up && live) toa_up[j] = flux;
   }
   __syncthreads();
   for (int t = tid; t < 2 * nhl; t += LBL_THREADS)
-    partial[(size_t)blockIdx.x * 2 * nhl + t] = ((s_acc[t] + s_acc[2 * nhl + t]) + s_acc[4 * nhl + t]) + s_acc[6 * nhl + t];
+    partial[(size_t)blockIdx.x * 2 * nhl + t] = add_waves(s_acc, 2 * nhl, t);
 }
 
 // Fluxes of (level, g point) matrices - what run_ckd leaves for a flux evaluation (test/run_ckd_lw.sh:133-137: optical depth and
@@ -205,22 +167,6 @@ k_rt_sw_gpoints(int ncol, int nlay, int ng, double mu0, double albedo, const dou
   f = f * albedo;
   fu[(size_t)nlay * ng] = f;
   for (int l = nlay - 1; l >= 0; --l) { f = f * exp(-2.0 * tau[(size_t)l * ng]); fu[(size_t)l * ng] = f; }
-}
-
-struct Buf {
-  void* p = nullptr;
-  ~Buf() { if (p) (void)hipFree(p); }
-};
-
-int make_chunks(size_t nwav, int nband, const int64_t* b0, const int64_t* b1, std::vector<BandChunk>& chunks) {
-  for (int b = 0; b < nband; ++b) {
-    if (b1[b] < b0[b]) continue;                       // empty band
-    ECCKD_REQUIRE(b0[b] >= 0 && (size_t)b1[b] < nwav, "band %d range [%lld,%lld] outside the spectrum", b, (long long)b0[b],
-                  (long long)b1[b]);
-    for (long long i = b0[b]; i <= b1[b]; i += LBL_THREADS)
-      chunks.push_back(BandChunk{i, std::min<long long>(i + LBL_THREADS - 1, b1[b]), b, 0});
-  }
-  return ECCKD_OK;
 }
 
 int combine(ecckd_ctx* ctx, int nlay, int nband, const std::vector<BandChunk>& chunks, const double* d_partial,
@@ -289,51 +235,37 @@ int ecckd_lbl_band_fluxes_lw_angles(ecckd_ctx* ctx, int nangle, int nlay, size_t
                                     const double* d_wavenumber, const double* d_d_wavenumber, const void* d_od, int od_type,
                                     size_t od_stride, int nband, const int64_t* h_band_begin, const int64_t* h_band_end,
                                     double* h_flux_dn, double* h_flux_up, double* d_surf_dn, double* d_toa_up) {
-  ECCKD_REQUIRE(nangle >= 0 && nangle <= LBL_MAX_ANGLES, "ecckd_lbl_band_fluxes_lw: nangle = %d outside 0..%d", nangle, LBL_MAX_ANGLES);
-  Angles ang{};
-  if (nangle == 0) {
-    ang.n = 1; ang.sec[0] = ECCKD_LW_DIFFUSIVITY; ang.weight[0] = 1.0;
-  } else {
-    double mu[LBL_MAX_ANGLES], w[LBL_MAX_ANGLES];
-    ECCKD_CHECK(ecckd_gauss_legendre_01(nangle, mu, w));
-    ang.n = nangle;
-    for (int a = 0; a < nangle; ++a) { ang.sec[a] = 1.0 / mu[a]; ang.weight[a] = 2.0 * w[a] * mu[a]; }
-  }
+  const char* who = "ecckd_lbl_band_fluxes_lw";
+  int nang = 0;
+  std::vector<double> sec_wgt;
+  ECCKD_CHECK(lw_angle_table(who, nangle, &nang, sec_wgt));
   ECCKD_REQUIRE(ctx && nlay > 0 && h_temperature_hl && d_wavenumber && d_d_wavenumber && d_od && nband > 0 && h_band_begin &&
                 h_band_end && h_flux_dn && h_flux_up, "ecckd_lbl_band_fluxes_lw: bad argument");
-  ECCKD_REQUIRE(od_type == ECCKD_F32 || od_type == ECCKD_F64, "ecckd_lbl_band_fluxes_lw: od_type must be 4 or 8");
-  ECCKD_REQUIRE(od_stride >= nwav, "ecckd_lbl_band_fluxes_lw: od_stride (%zu) < nwav (%zu)", od_stride, nwav);
+  ECCKD_CHECK(check_od(who, od_type, od_stride, nwav));
   ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
   const int nhl = nlay + 1;
   std::vector<BandChunk> chunks;
-  ECCKD_CHECK(make_chunks(nwav, nband, h_band_begin, h_band_end, chunks));
+  ECCKD_CHECK(make_chunks(nullptr, nwav, nband, h_band_begin, h_band_end, chunks));
   // wavenumbers outside every band carry no flux
   if (d_surf_dn) ECCKD_HIP_CHECK(hipMemsetAsync(d_surf_dn, 0, nwav * sizeof(double), ctx->stream));
   if (d_toa_up) ECCKD_HIP_CHECK(hipMemsetAsync(d_toa_up, 0, nwav * sizeof(double), ctx->stream));
-  std::vector<double> hk(nhl);
-  for (int i = 0; i < nhl; ++i) {
-    ECCKD_REQUIRE(h_temperature_hl[i] > 0.0, "ecckd_lbl_band_fluxes_lw: temperature_hl must be positive");
-    hk[i] = (6.62606896e-34 / 1.3806504e-23) / h_temperature_hl[i];
-  }
+  std::vector<double> hk;
+  ECCKD_CHECK(make_hk(who, nhl, h_temperature_hl, hk));
+  hk.insert(hk.end(), sec_wgt.begin(), sec_wgt.end());   // one upload: hk[nhl], then the angles
   Buf d_chunks, d_hk, d_part;
   if (!chunks.empty()) {
     ECCKD_HIP_CHECK(hipMalloc(&d_chunks.p, chunks.size() * sizeof(BandChunk)));
-    ECCKD_HIP_CHECK(hipMalloc(&d_hk.p, (nhl + 2 * LBL_MAX_ANGLES) * sizeof(double)));
+    ECCKD_HIP_CHECK(hipMalloc(&d_hk.p, hk.size() * sizeof(double)));
     ECCKD_HIP_CHECK(hipMalloc(&d_part.p, chunks.size() * 2 * nhl * sizeof(double)));
     ECCKD_CHECK(ecckd_h2d(ctx, d_chunks.p, chunks.data(), chunks.size() * sizeof(BandChunk)));
-    for (int a = 0; a < ang.n; ++a) hk.push_back(ang.sec[a]);
-    for (int a = 0; a < ang.n; ++a) hk.push_back(ang.weight[a]);
     ECCKD_CHECK(ecckd_h2d(ctx, d_hk.p, hk.data(), hk.size() * sizeof(double)));
-    const double* d_ang = (const double*)d_hk.p + nhl;
     const size_t lds = (size_t)4 * 2 * nhl * sizeof(double);
-    if (od_type == ECCKD_F32)
-      hipLaunchKernelGGL(k_lbl_fluxes_lw<float>, dim3((unsigned)chunks.size()), dim3(LBL_THREADS), lds, ctx->stream, ang.n, d_ang, nlay,
-                         od_stride, (const BandChunk*)d_chunks.p, (const double*)d_hk.p, d_wavenumber, d_d_wavenumber,
-                         (const float*)d_od, (double*)d_part.p, d_surf_dn, d_toa_up);
-    else
-      hipLaunchKernelGGL(k_lbl_fluxes_lw<double>, dim3((unsigned)chunks.size()), dim3(LBL_THREADS), lds, ctx->stream, ang.n, d_ang, nlay,
-                         od_stride, (const BandChunk*)d_chunks.p, (const double*)d_hk.p, d_wavenumber, d_d_wavenumber,
-                         (const double*)d_od, (double*)d_part.p, d_surf_dn, d_toa_up);
+    with_od_type(od_type, [&](auto t) {
+      using OdT = decltype(t);
+      hipLaunchKernelGGL(k_lbl_fluxes_lw<OdT>, dim3((unsigned)chunks.size()), dim3(LBL_THREADS), lds, ctx->stream, nang,
+                         (const double*)d_hk.p + nhl, nlay, od_stride, (const BandChunk*)d_chunks.p, (const double*)d_hk.p,
+                         d_wavenumber, d_d_wavenumber, (const OdT*)d_od, (double*)d_part.p, d_surf_dn, d_toa_up);
+    });
     ECCKD_HIP_CHECK(hipGetLastError());
   }
   return combine(ctx, nlay, nband, chunks, (const double*)d_part.p, h_flux_dn, h_flux_up);
@@ -355,12 +287,11 @@ int ecckd_lbl_band_fluxes_sw_ex(ecckd_ctx* ctx, int nlay, size_t nwav, double co
   ECCKD_REQUIRE(ctx && nlay > 0 && d_ssi && d_od && nband > 0 && h_band_begin && h_band_end && h_flux_dn_direct,
                 "ecckd_lbl_band_fluxes_sw: bad argument");
   ECCKD_REQUIRE(cos_sza > 0.0, "ecckd_lbl_band_fluxes_sw: cos_sza must be positive");
-  ECCKD_REQUIRE(od_type == ECCKD_F32 || od_type == ECCKD_F64, "ecckd_lbl_band_fluxes_sw: od_type must be 4 or 8");
-  ECCKD_REQUIRE(od_stride >= nwav, "ecckd_lbl_band_fluxes_sw: od_stride (%zu) < nwav (%zu)", od_stride, nwav);
+  ECCKD_CHECK(check_od("ecckd_lbl_band_fluxes_sw", od_type, od_stride, nwav));
   ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
   const int nhl = nlay + 1;
   std::vector<BandChunk> chunks;
-  ECCKD_CHECK(make_chunks(nwav, nband, h_band_begin, h_band_end, chunks));
+  ECCKD_CHECK(make_chunks(nullptr, nwav, nband, h_band_begin, h_band_end, chunks));
   if (d_surf_dn) ECCKD_HIP_CHECK(hipMemsetAsync(d_surf_dn, 0, nwav * sizeof(double), ctx->stream));
   if (d_toa_up) ECCKD_HIP_CHECK(hipMemsetAsync(d_toa_up, 0, nwav * sizeof(double), ctx->stream));
   Buf d_chunks, d_part;
@@ -369,14 +300,12 @@ int ecckd_lbl_band_fluxes_sw_ex(ecckd_ctx* ctx, int nlay, size_t nwav, double co
     ECCKD_HIP_CHECK(hipMalloc(&d_part.p, chunks.size() * 2 * nhl * sizeof(double)));
     ECCKD_CHECK(ecckd_h2d(ctx, d_chunks.p, chunks.data(), chunks.size() * sizeof(BandChunk)));
     const size_t lds = (size_t)4 * 2 * nhl * sizeof(double);
-    if (od_type == ECCKD_F32)
-      hipLaunchKernelGGL(k_lbl_fluxes_sw<float>, dim3((unsigned)chunks.size()), dim3(LBL_THREADS), lds, ctx->stream, nlay,
-                         od_stride, (const BandChunk*)d_chunks.p, cos_sza, d_ssi, d_albedo, (const float*)d_od, (double*)d_part.p,
-                         d_surf_dn, d_toa_up);
-    else
-      hipLaunchKernelGGL(k_lbl_fluxes_sw<double>, dim3((unsigned)chunks.size()), dim3(LBL_THREADS), lds, ctx->stream, nlay,
-                         od_stride, (const BandChunk*)d_chunks.p, cos_sza, d_ssi, d_albedo, (const double*)d_od, (double*)d_part.p,
-                         d_surf_dn, d_toa_up);
+    with_od_type(od_type, [&](auto t) {
+      using OdT = decltype(t);
+      hipLaunchKernelGGL(k_lbl_fluxes_sw<OdT>, dim3((unsigned)chunks.size()), dim3(LBL_THREADS), lds, ctx->stream, nlay, od_stride,
+                         (const BandChunk*)d_chunks.p, cos_sza, d_ssi, d_albedo, (const OdT*)d_od, (double*)d_part.p, d_surf_dn,
+                         d_toa_up);
+    });
     ECCKD_HIP_CHECK(hipGetLastError());
   }
   return combine(ctx, nlay, nband, chunks, (const double*)d_part.p, h_flux_dn_direct, h_flux_up);
@@ -390,14 +319,9 @@ int ecckd_rt_lw_gpoints(ecckd_ctx* ctx, int nangle, int ncol, int nlay, int ng, 
   ECCKD_REQUIRE(ctx && ncol > 0 && nlay > 0 && ng > 0 && h_planck_hl && h_od && h_flux_dn && h_flux_up, "ecckd_rt_lw_gpoints: bad argument");
   ECCKD_REQUIRE(nangle >= 0 && nangle <= LBL_MAX_ANGLES, "ecckd_rt_lw_gpoints: nangle %d outside 0..%d", nangle, LBL_MAX_ANGLES);
   ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
-  const int nsec = nangle == 0 ? 1 : nangle;
-  std::vector<double> sw(2 * (size_t)nsec);
-  if (nangle == 0) { sw[0] = ECCKD_LW_DIFFUSIVITY; sw[1] = 1.0; }
-  else {
-    std::vector<double> mu(nangle), w(nangle);
-    ECCKD_CHECK(ecckd_gauss_legendre_01(nangle, mu.data(), w.data()));
-    for (int a = 0; a < nangle; ++a) { sw[a] = 1.0 / mu[a]; sw[nsec + a] = 2.0 * w[a] * mu[a]; }
-  }
+  int nsec = 0;
+  std::vector<double> sw;
+  ECCKD_CHECK(lw_angle_table("ecckd_rt_lw_gpoints", nangle, &nsec, sw));
   const size_t nl = (size_t)ncol * nlay * ng, nh = (size_t)ncol * (nlay + 1) * ng;
   const size_t b_sw = ecckd_align_up(sw.size() * sizeof(double), 256), b_l = ecckd_align_up(nl * sizeof(double), 256),
                b_h = ecckd_align_up(nh * sizeof(double), 256);

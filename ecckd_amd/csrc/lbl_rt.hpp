@@ -1,0 +1,163 @@
+// lbl_rt.hpp - the no-scattering transfer of ONE wavenumber, written once for the line-by-line kernels (lbl_fluxes.hip,
+// lbl_gpoint_fluxes.hip, lbl_gpoint_fluxes_sw.hip, lbl_scenarios.hip), and the host plumbing they share.  DESIGN.md and the
+// tests compare these kernels with each other, bit for bit where they can: one source text keeps an edit from reaching only
+// one of them.  The files are compiled with the default contraction, so an expression here keeps its form and operand order;
+// a reordered one can fuse differently and change bits.
+//
+// Longwave: planck_function (planck_function.cpp:22-54) and radiative_transfer_lw (radiative_transfer_lw.cpp:27-60) with
+// unit surface emissivity along the slant path sec * tau:
+//   freq = wn_to_freq(wn);  pref = planck_pref(d_wn, freq);  B(level) = planck(pref, freq, hk[level]), hk = (h / k) / T
+//   per layer   lw_layer(sec, 1 / sec, tau, eps, fac)                                          (:41-43)
+//   down, up    flux = lw_step(flux, eps, fac, B(level left), B(level reached))                (:45-50, :55-59)
+//   surface     flux = lw_surface(flux, B(surface))                                            (:52-53)
+// Shortwave: radiative_transfer_direct_sw / _norayleigh_sw (radiative_transfer_sw.cpp:26-77).  Its steps are single
+// products and stay written out where they are used, always in this form, with the IEEE exp and not exp_fast:
+//   top         flux = cos_sza * ssi                                                           (:39)
+//   down        flux = flux * exp(minus_sec_sza * tau),  minus_sec_sza = -1.0 / cos_sza        (:45-50)
+//   surface     flux = flux * albedo                                                           (:70)
+//   up          flux = flux * exp(-2.0 * tau)                                                  (:72-76)
+// The tuned kernels of find_g.hip, optimize.hip, create_lut.hip and reorder.hip keep their own SGPR-pinned variants.
+#pragma once
+
+#include "common.hpp"
+#include "fastmath.hpp"
+
+#include <algorithm>
+#include <vector>
+
+namespace ecckd {
+namespace lbl {
+
+constexpr int LBL_THREADS = 256;     // threads of a block = wavenumbers of a BandChunk
+constexpr int LBL_MAX_ANGLES = 16;   // longwave zenith angles per hemisphere
+constexpr int LBL_MAX_SZA = 8;       // solar zenith angles of one call
+
+// ---------------------------------------------------------------------------------------------------------------- device
+__device__ constexpr double kPlanckH = 6.62606896e-34;
+__device__ constexpr double kLightC = 2.99792458e8;
+__device__ constexpr double kPi = 3.14159265358979323846;
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;  // valid in lane 0
+}
+
+// the sum of v over the wave, added to *acc by lane 0: one writer per wave's accumulator
+__device__ __forceinline__ void wave_add(double* acc, int lane, double v) {
+  const double s = wave_sum(v);
+  if (lane == 0) *acc += s;
+}
+
+// the four waves' accumulators s[w * n + t], added in a fixed order
+__device__ __forceinline__ double add_waves(const double* s, int n, int t) {
+  return ((s[t] + s[n + t]) + s[2 * n + t]) + s[3 * n + t];
+}
+
+__device__ __forceinline__ double wn_to_freq(double wn) {
+  const double inv_cm_2_Hz = 100.0 * kLightC;
+  return wn * inv_cm_2_Hz;
+}
+
+__device__ __forceinline__ double planck_pref(double dwn, double freq) {
+  const double inv_cm_2_Hz = 100.0 * kLightC;
+  return (dwn * 2.0 * kPlanckH * inv_cm_2_Hz * kPi / (kLightC * kLightC)) * (freq * freq * freq);
+}
+
+__device__ __forceinline__ double planck(double pref, double freq, double hk_level) {
+  return div_fast(pref, exp_fast(freq * hk_level) - 1.0);
+}
+
+__device__ __forceinline__ void lw_layer(double sec, double rsec, double tau, double& eps, double& fac) {
+  eps = 1.0 - exp_fast(-sec * tau);
+  fac = (eps > 1.0e-5) ? 1.0 - div_fast(eps * rsec, tau) : 0.5 * eps;
+}
+
+__device__ __forceinline__ double lw_step(double flux, double eps, double fac, double b_prev, double b) {
+  return flux * (1.0 - eps) + b_prev * (eps - fac) + b * fac;
+}
+
+// emissivity 1: the reference's emissivity * B + (1 - emissivity) * flux, kept as it stands
+__device__ __forceinline__ double lw_surface(double flux, double b_surf) {
+  return b_surf * 1.0 + (1.0 - 1.0) * flux;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ host
+constexpr double kPlanckOverBoltzmann = 6.62606896e-34 / 1.3806504e-23;
+
+struct BandChunk { long long i1, i2; int band; int pad; };
+
+struct Buf {
+  void* p = nullptr;
+  ~Buf() { if (p) (void)hipFree(p); }
+};
+
+// hk[level] = (h / k) / temperature_hl[level]
+inline int make_hk(const char* who, int nhl, const double* h_temperature_hl, std::vector<double>& hk) {
+  hk.resize(nhl);
+  for (int i = 0; i < nhl; ++i) {
+    ECCKD_REQUIRE(h_temperature_hl[i] > 0.0, "%s: temperature_hl must be positive", who);
+    hk[i] = kPlanckOverBoltzmann / h_temperature_hl[i];
+  }
+  return ECCKD_OK;
+}
+
+// one chunk per LBL_THREADS wavenumbers of a band, in wavenumber order; `who` (or NULL) prefixes the message
+inline int make_chunks(const char* who, size_t nwav, int nband, const int64_t* b0, const int64_t* b1, std::vector<BandChunk>& chunks) {
+  for (int b = 0; b < nband; ++b) {
+    if (b1[b] < b0[b]) continue;                       // empty band
+    ECCKD_REQUIRE(b0[b] >= 0 && (size_t)b1[b] < nwav, "%s%sband %d range [%lld,%lld] outside the spectrum", who ? who : "",
+                  who ? ": " : "", b, (long long)b0[b], (long long)b1[b]);
+    for (long long i = b0[b]; i <= b1[b]; i += LBL_THREADS)
+      chunks.push_back(BandChunk{i, std::min<long long>(i + LBL_THREADS - 1, b1[b]), b, 0});
+  }
+  return ECCKD_OK;
+}
+
+// The zenith angles of the longwave fluxes: sec_wgt = [nang] secants, then [nang] weights.  nangle = 0: one angle with
+// sec = 1.66, weight = 1, the classic two-stream form the reference itself uses (radiative_transfer_lw.cpp:27-60,
+// LW_DIFFUSIVITY).  nangle > 0: Gauss-Legendre quadrature in mu = cos(zenith angle) over one hemisphere, flux = sum_k 2 w_k
+// mu_k L(mu_k), each L(mu_k) the same no-scattering recurrence with the slant path tau / mu_k in place of 1.66 tau (CKDMIP's
+// `nangle`, Hogan & Matricardi 2020, GMD 13, 6501-6521, section 3.2: "N angles per hemisphere").  The CKDMIP tool is not
+// among the reference's sources: its node set is unpinned, see DESIGN.md.
+inline int lw_angle_table(const char* who, int nangle, int* nang, std::vector<double>& sec_wgt) {
+  ECCKD_REQUIRE(nangle >= 0 && nangle <= LBL_MAX_ANGLES, "%s: nangle = %d outside 0..%d", who, nangle, LBL_MAX_ANGLES);
+  *nang = nangle == 0 ? 1 : nangle;
+  sec_wgt.assign(2 * (size_t)*nang, 0.0);
+  if (nangle == 0) { sec_wgt[0] = ECCKD_LW_DIFFUSIVITY; sec_wgt[1] = 1.0; }
+  else {
+    double mu[LBL_MAX_ANGLES], w[LBL_MAX_ANGLES];
+    ECCKD_CHECK(ecckd_gauss_legendre_01(nangle, mu, w));
+    for (int a = 0; a < nangle; ++a) { sec_wgt[a] = 1.0 / mu[a]; sec_wgt[nangle + a] = 2.0 * w[a] * mu[a]; }
+  }
+  return ECCKD_OK;
+}
+
+// The solar zenith angles of a shortwave call, checked: h_ang = [LBL_MAX_SZA] cos_sza (1.0 beyond nsza), then
+// [LBL_MAX_SZA] -1.0 / cos_sza, divided on the host (IEEE, as on the device).
+inline int sw_angle_table(const char* who, int nsza, const double* h_cos_sza, double (&h_ang)[2 * LBL_MAX_SZA]) {
+  ECCKD_REQUIRE(nsza >= 1 && nsza <= LBL_MAX_SZA, "%s: nsza (%d) must be between 1 and %d", who, nsza, LBL_MAX_SZA);
+  for (int s = 0; s < nsza; ++s)
+    ECCKD_REQUIRE(h_cos_sza[s] > 0.0 && h_cos_sza[s] <= 1.0, "%s: cos_sza[%d] = %g is not in (0, 1]", who, s, h_cos_sza[s]);
+  for (int s = 0; s < LBL_MAX_SZA; ++s) {
+    h_ang[s] = s < nsza ? h_cos_sza[s] : 1.0;
+    h_ang[LBL_MAX_SZA + s] = -1.0 / h_ang[s];
+  }
+  return ECCKD_OK;
+}
+
+inline int check_od(const char* who, int od_type, size_t od_stride, size_t nwav) {
+  ECCKD_REQUIRE(od_type == ECCKD_F32 || od_type == ECCKD_F64, "%s: od_type must be 4 or 8", who);
+  ECCKD_REQUIRE(od_stride >= nwav, "%s: od_stride (%zu) < nwav (%zu)", who, od_stride, nwav);
+  return ECCKD_OK;
+}
+
+// f(OdT()) with OdT = float or double, as a checked od_type says
+template <typename F>
+auto with_od_type(int od_type, F&& f) {
+  if (od_type == ECCKD_F32) return f(float());
+  return f(double());
+}
+
+}  // namespace lbl
+}  // namespace ecckd

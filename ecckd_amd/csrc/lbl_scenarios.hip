@@ -3,7 +3,7 @@
 // the scenarios differing in one scaling per gas file) as one call.  The arithmetic per scenario is that of the single-scenario
 // path: the merged optical depth of k_merge (merge.hip:36-38: product and sum rounded separately, in gas order - bit for bit the
 // DOUBLE matrix ecckd_merge_spectrum_dev would leave in HBM, which is never written here) under the recurrences of
-// k_lbl_fluxes_lw / k_lbl_fluxes_sw (lbl_fluxes.hip), expression by expression.
+// k_lbl_fluxes_lw / k_lbl_fluxes_sw (lbl_fluxes.hip): the same functions and steps of lbl_rt.hpp.
 //
 // Shape.  One thread per wavenumber, 256-thread blocks over the BandChunk list of lbl_fluxes.hip.  A SLOT is what owns one row
 // of fluxes: a scenario in the longwave kernel, a (scenario, solar zenith angle) pair in the shortwave one.  A launch carries up
@@ -22,15 +22,16 @@
 // Tiling.  LDS per block: 4 waves x T slots x 2 nhl doubles = 64 T (nlay + 1) bytes, held within the budgets the g-point
 // kernels use for their accumulators (LS_LW_LDS = 42 KB longwave, LS_SW_LDS = 58 KB shortwave), and T is capped by what the
 // kernels keep in registers without scratch (LS_LW_SLOTS = 8 scenarios; LS_SW_SLOTS = 16 scenario-angles):
-//   longwave:  T = min(8, 43008 / (64 (nlay+1)))      8 up to 83 layers;  nlay <= 671, above that PARAMETER_ERROR
-//   shortwave: T = min(16, 59392 / (64 (nlay+1)))    16 up to 57 layers;  nlay <= 927, above that PARAMETER_ERROR
+//   longwave:  T = min(8, GF_ACC_BYTES / (64 (nlay+1)))    8 up to 83 layers;  nlay <= 671, above that PARAMETER_ERROR
+//   shortwave: T = min(16, SF_ACC_BYTES / (64 (nlay+1)))  16 up to 57 layers;  nlay <= 927, above that PARAMETER_ERROR
 // More slots than T: ceil(slots / T) launches, each reading the gas rows again.  Scenarios are split first: the longwave
 // scenarios go evenly over ceil(nscen / T) launches; the shortwave launch takes all nsza angles and S = min(T / nsza,
 // 16 / nsza) scenarios (nsza = 5: 3 scenarios, 15 slots), the scenarios evenly over ceil(nscen / S) launches.  Only where one
 // scenario's angles exceed T (nsza > T: more than 114 layers) the angles are split too, evenly over ceil(nsza / T) launches of
 // one scenario.  The shortwave kernel is instantiated per number of angles of a launch (1..8), so that fluxes stay in registers.
 #include "common.hpp"
-#include "fastmath.hpp"
+#include "gpoint_bin.hpp"
+#include "lbl_rt.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -38,19 +39,14 @@
 
 namespace {
 
-constexpr int LS_THREADS = 256;
+using namespace ecckd::lbl;
+
 constexpr int LS_MAX_GAS = 16;
-constexpr int LS_MAX_ANGLES = 16;                  // longwave zenith angles (LBL_MAX_ANGLES of lbl_fluxes.hip)
-constexpr int LS_MAX_SZA = 8;                      // SF_MAX_SZA of lbl_gpoint_fluxes_sw.hip
 constexpr int LS_LW_SLOTS = 8;
 constexpr int LS_SW_SLOTS = 16;
-constexpr size_t LS_LW_LDS = 43008;                // GF_ACC_BYTES of lbl_gpoint_fluxes.hip
-constexpr size_t LS_SW_LDS = 59392;                // SF_ACC_BYTES of lbl_gpoint_fluxes_sw.hip
-__device__ constexpr double kPlanckH = 6.62606896e-34;
-__device__ constexpr double kLightC = 2.99792458e8;
-__device__ constexpr double kPi = 3.14159265358979323846;
-
-struct BandChunk { long long i1, i2; int band; int pad; };
+constexpr size_t LS_LW_LDS = GF_ACC_BYTES;         // 43008: the accumulator budgets of the g-point kernels (gpoint_bin.hpp)
+constexpr size_t LS_SW_LDS = SF_ACC_BYTES;         // 59392
+static_assert(LS_LW_LDS == 43008 && LS_SW_LDS == 59392, "the slot counts of ecckd_lbl_scenarios_slots follow from these");
 
 // the gases' rows, by value in the kernel arguments: indexed with the (uniform) gas counter, so scalar loads
 struct GasRows {
@@ -58,12 +54,6 @@ struct GasRows {
   unsigned long long stride[LS_MAX_GAS];
   int type[LS_MAX_GAS];
 };
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;  // valid in lane 0
-}
 
 // tau[s] = sum over the gases, in gas order, of od_g * scale[s][g][l] (k_merge, merge.hip:36-38), s < ns
 template <int S>
@@ -84,7 +74,7 @@ __device__ __forceinline__ void merged_tau(const GasRows& gr, int ngas, int nlay
 }
 
 // LDS: acc[4][ns][2*nhl]
-__global__ void __launch_bounds__(LS_THREADS)
+__global__ void __launch_bounds__(LBL_THREADS)
 k_lbl_scenarios_lw(int nang, const double* __restrict__ ang /*[nang] secants, [nang] weights*/, int nlay, int ngas, GasRows gr, int ns,
                    const double* __restrict__ scale /* [ns][ngas][nlay]: the scenarios of this launch */,
                    const BandChunk* __restrict__ chunks, const double* __restrict__ hk, const double* __restrict__ wn,
@@ -97,42 +87,35 @@ k_lbl_scenarios_lw(int nang, const double* __restrict__ ang /*[nang] secants, [n
   const BandChunk c = chunks[blockIdx.x];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nrow = ns * 2 * nhl;
-  for (int t = tid; t < 4 * nrow; t += LS_THREADS) s_acc[t] = 0.0;
+  for (int t = tid; t < 4 * nrow; t += LBL_THREADS) s_acc[t] = 0.0;
   __syncthreads();
   double* acc = s_acc + wave * nrow;               // slot s: down at acc[s * 2 * nhl + level], up nhl further on
   const long long i = c.i1 + tid;
   const bool live = i <= c.i2;
   const size_t j = live ? (size_t)i : (size_t)c.i2;
-  const double inv_cm_2_Hz = 100.0 * kLightC;
-  const double freq = wn[j] * inv_cm_2_Hz;
-  const double pref = live ? (dwn[j] * 2.0 * kPlanckH * inv_cm_2_Hz * kPi / (kLightC * kLightC)) * (freq * freq * freq) : 0.0;
-  auto planck = [&](int level) { return ecckd::div_fast(pref, ecckd::exp_fast(freq * hk[level]) - 1.0); };
+  const double freq = wn_to_freq(wn[j]);
+  const double pref = live ? planck_pref(dwn[j], freq) : 0.0;
   double surf_acc[S], toa_acc[S];
 #pragma unroll
   for (int s = 0; s < S; ++s) { surf_acc[s] = 0.0; toa_acc[s] = 0.0; }
   for (int a = 0; a < nang; ++a) {
     const double sec = ang[a], wgt = ang[nang + a];          // (uniform: scalar loads)
     const double rsec = 1.0 / sec;
-    auto layer = [&](double tau, double& eps, double& fac) {
-      eps = 1.0 - ecckd::exp_fast(-sec * tau);
-      fac = (eps > 1.0e-5) ? 1.0 - ecckd::div_fast(eps * rsec, tau) : 0.5 * eps;   // radiative_transfer_lw.cpp:41-43
-    };
     double flux[S], tau[S];
 #pragma unroll
     for (int s = 0; s < S; ++s) { flux[s] = 0.0; tau[s] = 0.0; }
     // down sweep from zero at the top of the atmosphere (:45-50); dead lanes carry pref = 0 -> all fluxes 0
-    double b_prev = planck(0);
+    double b_prev = planck(pref, freq, hk[0]);
     for (int l = 0; l < nlay; ++l) {
       merged_tau<S>(gr, ngas, nlay, l, j, ns, scale, tau);
-      const double b_next = planck(l + 1);                   // once per level for every scenario of the launch
+      const double b_next = planck(pref, freq, hk[l + 1]);                   // once per level for every scenario of the launch
 #pragma unroll
       for (int s = 0; s < S; ++s)
         if (s < ns) {
           double eps, fac;
-          layer(tau[s], eps, fac);
-          flux[s] = flux[s] * (1.0 - eps) + b_prev * (eps - fac) + b_next * fac;
-          const double sum = wave_sum(wgt * flux[s]);
-          if (lane == 0) acc[s * 2 * nhl + l + 1] += sum;
+          lw_layer(sec, rsec, tau[s], eps, fac);
+          flux[s] = lw_step(flux[s], eps, fac, b_prev, b_next);
+          wave_add(&acc[s * 2 * nhl + l + 1], lane, wgt * flux[s]);
         }
       b_prev = b_next;
     }
@@ -141,21 +124,19 @@ k_lbl_scenarios_lw(int nang, const double* __restrict__ ang /*[nang] secants, [n
     for (int s = 0; s < S; ++s)
       if (s < ns) {
         surf_acc[s] += wgt * flux[s];
-        flux[s] = b_prev * 1.0 + (1.0 - 1.0) * flux[s];
-        const double sum = wave_sum(wgt * flux[s]);
-        if (lane == 0) acc[s * 2 * nhl + nhl + nlay] += sum;
+        flux[s] = lw_surface(flux[s], b_prev);
+        wave_add(&acc[s * 2 * nhl + nhl + nlay], lane, wgt * flux[s]);
       }
     for (int l = nlay - 1; l >= 0; --l) {                                    // :55-59
       merged_tau<S>(gr, ngas, nlay, l, j, ns, scale, tau);
-      const double b_l = planck(l);
+      const double b_l = planck(pref, freq, hk[l]);
 #pragma unroll
       for (int s = 0; s < S; ++s)
         if (s < ns) {
           double eps, fac;
-          layer(tau[s], eps, fac);
-          flux[s] = flux[s] * (1.0 - eps) + b_prev * (eps - fac) + b_l * fac;
-          const double sum = wave_sum(wgt * flux[s]);
-          if (lane == 0) acc[s * 2 * nhl + nhl + l] += sum;
+          lw_layer(sec, rsec, tau[s], eps, fac);
+          flux[s] = lw_step(flux[s], eps, fac, b_prev, b_l);
+          wave_add(&acc[s * 2 * nhl + nhl + l], lane, wgt * flux[s]);
         }
       b_prev = b_l;
     }
@@ -169,13 +150,13 @@ k_lbl_scenarios_lw(int nang, const double* __restrict__ ang /*[nang] secants, [n
       if (toa_up) toa_up[(size_t)s * nwav + j] = toa_acc[s];
     }
   __syncthreads();
-  for (int t = tid; t < nrow; t += LS_THREADS)
-    partial[(size_t)blockIdx.x * nrow + t] = ((s_acc[t] + s_acc[nrow + t]) + s_acc[2 * nrow + t]) + s_acc[3 * nrow + t];
+  for (int t = tid; t < nrow; t += LBL_THREADS)
+    partial[(size_t)blockIdx.x * nrow + t] = add_waves(s_acc, nrow, t);
 }
 
 // A angles per launch (compile time), up to LS_SW_SLOTS / A scenarios.  LDS: acc[4][ns][A][2*nhl]
 template <int A>
-__global__ void __launch_bounds__(LS_THREADS)
+__global__ void __launch_bounds__(LBL_THREADS)
 k_lbl_scenarios_sw(int nlay, int ngas, GasRows gr, int ns, const double* __restrict__ scale /* [ns][ngas][nlay] */,
                    const BandChunk* __restrict__ chunks, const double* __restrict__ cos_sza /* [A] */,
                    const double* __restrict__ minus_sec_sza /* [A]: -1.0 / cos_sza */, const double* __restrict__ ssi,
@@ -188,7 +169,7 @@ k_lbl_scenarios_sw(int nlay, int ngas, GasRows gr, int ns, const double* __restr
   const BandChunk c = chunks[blockIdx.x];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nrow = ns * A * 2 * nhl;
-  for (int t = tid; t < 4 * nrow; t += LS_THREADS) s_acc[t] = 0.0;
+  for (int t = tid; t < 4 * nrow; t += LBL_THREADS) s_acc[t] = 0.0;
   __syncthreads();
   double* acc = s_acc + wave * nrow;               // slot (s, a): down at acc[(s * A + a) * 2 * nhl + level], up nhl further on
   const long long i = c.i1 + tid;
@@ -205,10 +186,7 @@ k_lbl_scenarios_sw(int nlay, int ngas, GasRows gr, int ns, const double* __restr
 #pragma unroll
     for (int a = 0; a < A; ++a) {
       flux[s][a] = live ? mu[a] * ssi_j : 0.0;                               // radiative_transfer_sw.cpp:39
-      if (s < ns) {
-        const double sum = wave_sum(flux[s][a]);
-        if (lane == 0) acc[(s * A + a) * 2 * nhl] += sum;
-      }
+      if (s < ns) wave_add(&acc[(s * A + a) * 2 * nhl], lane, flux[s][a]);
     }
   }
   for (int l = 0; l < nlay; ++l) {
@@ -219,8 +197,7 @@ k_lbl_scenarios_sw(int nlay, int ngas, GasRows gr, int ns, const double* __restr
 #pragma unroll
         for (int a = 0; a < A; ++a) {
           flux[s][a] = flux[s][a] * exp(msec[a] * tau[s]);
-          const double sum = wave_sum(flux[s][a]);
-          if (lane == 0) acc[(s * A + a) * 2 * nhl + l + 1] += sum;
+          wave_add(&acc[(s * A + a) * 2 * nhl + l + 1], lane, flux[s][a]);
         }
       }
   }
@@ -241,8 +218,7 @@ k_lbl_scenarios_sw(int nlay, int ngas, GasRows gr, int ns, const double* __restr
 #pragma unroll
         for (int a = 0; a < A; ++a) {
           flux[s][a] = flux[s][a] * alb;
-          const double sum = wave_sum(flux[s][a]);
-          if (lane == 0) acc[(s * A + a) * 2 * nhl + nhl + nlay] += sum;
+          wave_add(&acc[(s * A + a) * 2 * nhl + nhl + nlay], lane, flux[s][a]);
         }
       }
     for (int l = nlay - 1; l >= 0; --l) {
@@ -254,8 +230,7 @@ k_lbl_scenarios_sw(int nlay, int ngas, GasRows gr, int ns, const double* __restr
 #pragma unroll
           for (int a = 0; a < A; ++a) {
             flux[s][a] = flux[s][a] * t2;
-            const double sum = wave_sum(flux[s][a]);
-            if (lane == 0) acc[(s * A + a) * 2 * nhl + nhl + l] += sum;
+            wave_add(&acc[(s * A + a) * 2 * nhl + nhl + l], lane, flux[s][a]);
           }
         }
     }
@@ -269,24 +244,8 @@ k_lbl_scenarios_sw(int nlay, int ngas, GasRows gr, int ns, const double* __restr
     }
   }
   __syncthreads();
-  for (int t = tid; t < nrow; t += LS_THREADS)
-    partial[(size_t)blockIdx.x * nrow + t] = ((s_acc[t] + s_acc[nrow + t]) + s_acc[2 * nrow + t]) + s_acc[3 * nrow + t];
-}
-
-struct Buf {
-  void* p = nullptr;
-  ~Buf() { if (p) (void)hipFree(p); }
-};
-
-int make_chunks(const char* who, size_t nwav, int nband, const int64_t* b0, const int64_t* b1, std::vector<BandChunk>& chunks) {
-  for (int b = 0; b < nband; ++b) {
-    if (b1[b] < b0[b]) continue;                       // empty band
-    ECCKD_REQUIRE(b0[b] >= 0 && (size_t)b1[b] < nwav, "%s: band %d range [%lld,%lld] outside the spectrum", who, b, (long long)b0[b],
-                  (long long)b1[b]);
-    for (long long i = b0[b]; i <= b1[b]; i += LS_THREADS)
-      chunks.push_back(BandChunk{i, std::min<long long>(i + LS_THREADS - 1, b1[b]), b, 0});
-  }
-  return ECCKD_OK;
+  for (int t = tid; t < nrow; t += LBL_THREADS)
+    partial[(size_t)blockIdx.x * nrow + t] = add_waves(s_acc, nrow, t);
 }
 
 // slots per launch: what the LDS budget holds, capped by what the kernel keeps in registers (see the header); 0: nlay too large
@@ -326,7 +285,7 @@ void launch_sw(ecckd_ctx* ctx, unsigned nblk, size_t lds, int nlay, int ngas, co
                const BandChunk* d_chunks, const double* d_mu, const double* d_msec, const double* d_ssi, const double* d_albedo,
                double* d_part, double* surf, double* toa, size_t scen_stride, size_t nwav) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_lbl_scenarios_sw<A>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LS_SW_LDS);
-  hipLaunchKernelGGL(k_lbl_scenarios_sw<A>, dim3(nblk), dim3(LS_THREADS), lds, ctx->stream, nlay, ngas, gr, ns, d_scale, d_chunks, d_mu,
+  hipLaunchKernelGGL(k_lbl_scenarios_sw<A>, dim3(nblk), dim3(LBL_THREADS), lds, ctx->stream, nlay, ngas, gr, ns, d_scale, d_chunks, d_mu,
                      d_msec, d_ssi, d_albedo, d_part, surf, toa, scen_stride, nwav);
 }
 
@@ -344,7 +303,9 @@ int ecckd_lbl_band_fluxes_lw_scenarios(ecckd_ctx* ctx, int nangle, int nlay, siz
                                        const int64_t* h_band_begin, const int64_t* h_band_end, double* h_flux_dn, double* h_flux_up,
                                        double* d_surf_dn, double* d_toa_up) {
   const char* who = "ecckd_lbl_band_fluxes_lw_scenarios";
-  ECCKD_REQUIRE(nangle >= 0 && nangle <= LS_MAX_ANGLES, "%s: nangle = %d outside 0..%d", who, nangle, LS_MAX_ANGLES);
+  int nang = 0;
+  std::vector<double> sec_wgt;
+  ECCKD_CHECK(lw_angle_table(who, nangle, &nang, sec_wgt));
   ECCKD_REQUIRE(ctx && nlay > 0 && h_temperature_hl && d_wavenumber && d_d_wavenumber && nband > 0 && h_band_begin && h_band_end &&
                 h_flux_dn && h_flux_up, "%s: bad argument", who);
   GasRows gr;
@@ -353,20 +314,9 @@ int ecckd_lbl_band_fluxes_lw_scenarios(ecckd_ctx* ctx, int nangle, int nlay, siz
   ECCKD_REQUIRE(T >= 1, "%s: %d layers are more than the block's accumulator holds (at most %d)", who, nlay,
                 (int)(LS_LW_LDS / 64) - 1);
   const int nhl = nlay + 1;
-  std::vector<double> hk(nhl);
-  for (int i = 0; i < nhl; ++i) {
-    ECCKD_REQUIRE(h_temperature_hl[i] > 0.0, "%s: temperature_hl must be positive", who);
-    hk[i] = (6.62606896e-34 / 1.3806504e-23) / h_temperature_hl[i];
-  }
-  int nang = 1;
-  if (nangle == 0) { hk.push_back(ECCKD_LW_DIFFUSIVITY); hk.push_back(1.0); }
-  else {
-    double mu[LS_MAX_ANGLES], w[LS_MAX_ANGLES];
-    ECCKD_CHECK(ecckd_gauss_legendre_01(nangle, mu, w));
-    nang = nangle;
-    for (int a = 0; a < nangle; ++a) hk.push_back(1.0 / mu[a]);
-    for (int a = 0; a < nangle; ++a) hk.push_back(2.0 * w[a] * mu[a]);
-  }
+  std::vector<double> hk;
+  ECCKD_CHECK(make_hk(who, nhl, h_temperature_hl, hk));
+  hk.insert(hk.end(), sec_wgt.begin(), sec_wgt.end());   // one upload: hk[nhl], then the angles
   ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
   std::vector<BandChunk> chunks;
   ECCKD_CHECK(make_chunks(who, nwav, nband, h_band_begin, h_band_end, chunks));
@@ -392,7 +342,7 @@ int ecckd_lbl_band_fluxes_lw_scenarios(ecckd_ctx* ctx, int nangle, int nlay, siz
   for (int s0 = 0; s0 < nscen; s0 += per) {
     const int ns = std::min(per, nscen - s0);
     const size_t lds = (size_t)4 * ns * 2 * nhl * sizeof(double);
-    hipLaunchKernelGGL(k_lbl_scenarios_lw, dim3((unsigned)chunks.size()), dim3(LS_THREADS), lds, ctx->stream, nang,
+    hipLaunchKernelGGL(k_lbl_scenarios_lw, dim3((unsigned)chunks.size()), dim3(LBL_THREADS), lds, ctx->stream, nang,
                        (const double*)d_hk.p + nhl, nlay, ngas, gr, ns, (const double*)d_scale.p + (size_t)s0 * ngas * nlay,
                        (const BandChunk*)d_chunks.p, (const double*)d_hk.p, d_wavenumber, d_d_wavenumber, (double*)d_part.p,
                        d_surf_dn ? d_surf_dn + (size_t)s0 * nwav : nullptr, d_toa_up ? d_toa_up + (size_t)s0 * nwav : nullptr, nwav);
@@ -414,9 +364,8 @@ int ecckd_lbl_band_fluxes_sw_scenarios(ecckd_ctx* ctx, int nlay, size_t nwav, in
   const char* who = "ecckd_lbl_band_fluxes_sw_scenarios";
   ECCKD_REQUIRE(ctx && nlay > 0 && h_cos_sza && d_ssi && nband > 0 && h_band_begin && h_band_end && h_flux_dn_direct && h_flux_up,
                 "%s: bad argument", who);
-  ECCKD_REQUIRE(nsza >= 1 && nsza <= LS_MAX_SZA, "%s: nsza (%d) must be between 1 and %d", who, nsza, LS_MAX_SZA);
-  for (int a = 0; a < nsza; ++a)
-    ECCKD_REQUIRE(h_cos_sza[a] > 0.0 && h_cos_sza[a] <= 1.0, "%s: cos_sza[%d] = %g is not in (0, 1]", who, a, h_cos_sza[a]);
+  double h_ang[2 * LBL_MAX_SZA];
+  ECCKD_CHECK(sw_angle_table(who, nsza, h_cos_sza, h_ang));
   GasRows gr;
   ECCKD_CHECK(check_gases(who, ngas, d_od, od_type, od_stride, nwav, nscen, h_scale, gr));
   const int T = slots_per_launch(true, nlay);
@@ -442,11 +391,6 @@ int ecckd_lbl_band_fluxes_sw_scenarios(ecckd_ctx* ctx, int nlay, size_t nwav, in
     const int nl = (nsza + T - 1) / T;
     ang_per = (nsza + nl - 1) / nl;
   }
-  double h_ang[2 * LS_MAX_SZA];                    // cos_sza, then -1.0 / cos_sza: divided on the host (IEEE, as on the device)
-  for (int a = 0; a < LS_MAX_SZA; ++a) {
-    h_ang[a] = a < nsza ? h_cos_sza[a] : 1.0;
-    h_ang[LS_MAX_SZA + a] = -1.0 / h_ang[a];
-  }
   const size_t nscale = (size_t)nscen * ngas * nlay;
   Buf d_chunks, d_ang, d_scale, d_part;
   ECCKD_HIP_CHECK(hipMalloc(&d_chunks.p, chunks.size() * sizeof(BandChunk)));
@@ -468,7 +412,7 @@ int ecckd_lbl_band_fluxes_sw_scenarios(ecckd_ctx* ctx, int nlay, size_t nwav, in
       double* surf = d_surf_dn_direct ? d_surf_dn_direct + first : nullptr;
       double* toa = d_toa_up ? d_toa_up + first : nullptr;
       const double* d_mu = (const double*)d_ang.p + a0;
-      const double* d_msec = (const double*)d_ang.p + LS_MAX_SZA + a0;
+      const double* d_msec = (const double*)d_ang.p + LBL_MAX_SZA + a0;
       const double* d_sc = (const double*)d_scale.p + (size_t)s0 * ngas * nlay;
 #define LS_SW(A)                                                                                                           \
   case A:                                                                                                                  \
