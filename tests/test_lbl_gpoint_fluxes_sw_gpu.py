@@ -195,8 +195,8 @@ def test_band_kernel_consistency(ctx, nlay, nwav, nband, nsza, dtype):
     gm = _gmap(ctx, g, nband, wn, dwn)
     dn, up, bdn, bup = gm.lbl_fluxes_sw(mu, d_ssi, d_od, d_alb)
     gm.close()
-    # the constants of csrc/lbl_gpoint_fluxes_sw.hip: SF_THREADS = 256 points per tile, SF_TARGET_BLOCKS = 2048,
-    # SF_SEGLEN = 8 ranks per piece, SF_SEG = 32 segments per tile
+    # the constants of csrc/gpoint_bin.hpp: GB_THREADS = 256 points per tile, GB_TARGET_BLOCKS = 2048,
+    # GB_SEGLEN = 8 ranks per piece, GB_SEG = 32 segments per tile
     ntiles = -(-nwav // 256)
     tiles_per_block = max(1, -(-ntiles // 2048))
     nblocks = -(-ntiles // tiles_per_block)
