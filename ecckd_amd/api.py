@@ -1188,6 +1188,51 @@ def lbl_band_fluxes_sw(ctx, cos_sza, ssi, optical_depth, band_begin, band_end, a
     return dn, up
 
 
+def lbl_band_fluxes_sw_rayleigh(ctx, cos_sza, ssi, optical_depth, rayleigh_optical_depth, band_begin, band_end, albedo=None,
+                                boundary=False):
+    """Line-by-line shortwave fluxes with Rayleigh scattering (two-stream, ecckd_lbl_band_fluxes_sw_rayleigh) for every solar
+    zenith angle of cos_sza (a scalar is one angle, 8 at most): device tensors ssi (nwav,), optical_depth (absorption) and
+    rayleigh_optical_depth (nlay, nwav), each float32 or float64, albedo (nwav,) or None (albedo 0) ->
+    (flux_dn_direct, flux_dn, flux_up), each (nsza, nband, nlay+1), flux_dn direct plus diffuse; boundary=True: also the
+    spectral direct and total downwelling fluxes at the surface and the upwelling one at the top, device tensors (nsza, nwav)."""
+    mu = _f64c(np.atleast_1d(cos_sza))
+    nlay, nwav = optical_depth.shape
+    if tuple(rayleigh_optical_depth.shape) != (nlay, nwav):
+        raise ValueError("optical_depth and rayleigh_optical_depth must have one shape (nlay, nwav)")
+    b0 = np.ascontiguousarray(band_begin, dtype=np.int64)
+    b1 = np.ascontiguousarray(band_end, dtype=np.int64)
+    shape = (mu.size, b0.size, nlay + 1)
+    direct, dn, up = np.empty(shape), np.empty(shape), np.empty(shape)
+    torch = _torch()
+    bnd = [torch.empty((mu.size, nwav), dtype=torch.float64, device=ctx.device) if boundary else None for _ in range(3)]
+    stride = lambda od: od.stride(0) if nlay > 1 else nwav
+    ctx.fence_from_torch()
+    check(ctx.lib.ecckd_lbl_band_fluxes_sw_rayleigh(ctx.handle, nlay, nwav, mu.size, _hptr(mu), _dptr(ssi),
+                                                    _dptr(albedo) if albedo is not None else None, _dptr(optical_depth),
+                                                    _od_type(optical_depth), stride(optical_depth), _dptr(rayleigh_optical_depth),
+                                                    _od_type(rayleigh_optical_depth), stride(rayleigh_optical_depth), b0.size,
+                                                    _hptr(b0, C.c_int64), _hptr(b1, C.c_int64), _hptr(direct), _hptr(dn), _hptr(up),
+                                                    *[_dptr(b) if boundary else None for b in bnd]))
+    if boundary:
+        ctx.synchronize()
+        return (direct, dn, up, *bnd)
+    return direct, dn, up
+
+
+def rt_sw_gpoints_rayleigh(ctx, cos_sza, albedo, incoming, optical_depth, rayleigh_optical_depth):
+    """Shortwave fluxes per g point with Rayleigh scattering from what run_ckd wrote (ecckd_rt_sw_gpoints_rayleigh): host
+    arrays incoming (ncol, ng), optical_depth (absorption) and rayleigh_optical_depth (ncol, nlay, ng), scalars cos_sza and
+    albedo -> (flux_dn_direct, flux_dn, flux_up), each (ncol, nlay+1, ng), flux_dn direct plus diffuse."""
+    od, ray, inc = _f64c(optical_depth), _f64c(rayleigh_optical_depth), _f64c(incoming)
+    if od.ndim != 3 or ray.shape != od.shape or inc.shape != (od.shape[0], od.shape[2]):
+        raise ValueError("optical depths must be (ncol, nlay, ng) and incoming (ncol, ng)")
+    ncol, nlay, ng = od.shape
+    direct, dn, up = np.empty((ncol, nlay + 1, ng)), np.empty((ncol, nlay + 1, ng)), np.empty((ncol, nlay + 1, ng))
+    check(ctx.lib.ecckd_rt_sw_gpoints_rayleigh(ctx.handle, ncol, nlay, ng, float(cos_sza), float(albedo), _hptr(inc), _hptr(od),
+                                               _hptr(ray), _hptr(direct), _hptr(dn), _hptr(up)))
+    return direct, dn, up
+
+
 def lbl_scenarios_slots(shortwave, nlay):
     """Slots (longwave: scenarios; shortwave: scenario-angle pairs) one launch of the scenario kernels carries at nlay layers."""
     return int(_lib.load_library().ecckd_lbl_scenarios_slots(int(bool(shortwave)), int(nlay)))

@@ -1,9 +1,11 @@
 // ckdmip.hpp - bin/ckdmip_lw and bin/ckdmip_sw: stand-ins for the EXTERNAL CKDMIP tools that the reference's scripts call (they are
-// not part of ecCKD; test/config.h:32-35), restricted to what those scripts use and to the no-scattering radiative transfer
-// the reference itself contains.
+// not part of ecCKD; test/config.h:32-35), restricted to what those scripts use and, unless ckdmip_sw is asked to scatter
+// (--rayleigh, --rayleigh-scattering), to the no-scattering radiative transfer the reference itself contains.
 //
 // ckdmip_{lw,sw} [--config file.nam] [--scenario name] [--merge-only] [--column-range a b] [--ssi file]
 //                {[--scale s | --conc c | --const c] spectrum-file}... [--ckd optical-depth-file] --output file
+// ckdmip_sw      ... [--rayleigh rayleigh-spectrum-file] spectrum-file... --output file
+// ckdmip_sw      ... --ckd optical-depth-file --rayleigh-scattering --output file
 // ckdmip_{lw,sw} [--config file.nam] [--column-range a b] [--ssi file] --scenarios table spectrum-file...
 //
 //   --merge-only   test/merge_well_mixed_lw.sh:28-31, :46-49, :60-63 (merge_well_mixed_sw.sh:35-81): the optical depths of
@@ -18,7 +20,18 @@
 //                  absorber, as the reference's own forward model treats Rayleigh scattering (solve_adept.cpp:34) - the real
 //                  tool scatters, which is why the reference masks the upwelling fluxes it cannot represent
 //                  (LblFluxes::mask_rayleigh_up);
-//   --ckd file     test/run_ckd_lw.sh:133-137, test/run_ckd_sw.sh:125-128: radiative transfer on the g-point optical depths
+//   --rayleigh FILE   (ckdmip_sw, default mode) the spectrum whose optical depth SCATTERS: read and streamed like a gas file,
+//                  unscaled, and not one of the gases of the output; the other files remain the absorbers.  The fluxes are
+//                  those of the two-stream transfer with Rayleigh scattering (ecckd_lbl_band_fluxes_sw_rayleigh: ecRad's
+//                  shortwave two-stream coefficients at asymmetry 0, Meador & Weaver's layer solution, the adding method,
+//                  a Lambertian surface of albedo surf_albedo).  The output keeps its variables - flux_dn_sw now the true
+//                  total, flux_up_sw and band_flux_up_sw with the scattered light - and gains band_flux_dn_sw, with
+//                  do_write_spectral_boundary_fluxes spectral_flux_dn_surf_sw (direct plus diffuse), and the global
+//                  attribute rayleigh_scattering = "two-stream".  The real tool's arithmetic is not among the reference's
+//                  sources: agreement with it node for node is unpinned;
+//   --rayleigh-scattering   (ckdmip_sw --ckd) rayleigh_optical_depth of the file scatters (ecckd_rt_sw_gpoints_rayleigh)
+//                  instead of absorbing; the file must hold it.  flux_dn_sw is the true total, spectral_flux_dn_sw is added,
+//                  and the same global attribute.  Neither switch goes with --merge-only or --scenarios, or with ckdmip_lw;//   --ckd file     test/run_ckd_lw.sh:133-137, test/run_ckd_sw.sh:125-128: radiative transfer on the g-point optical depths
 //                  that run_ckd wrote, fluxes per column.
 //   --scenarios FILE   the loop of test/run_lw_lbl_evaluation.sh:286-323 / test/run_sw_lbl_evaluation.sh:70-260 - one call per
 //                  scenario, the scenarios differing in one scaling per gas file - as ONE call: FILE is a text table (`#` starts a
@@ -198,7 +211,8 @@ void gas_scaling(const GasArg& g, const std::string& path, int nlay, const std::
 }
 
 // The dimensions and variables of a flux file after pressure_hl / temperature_hl (what LblFluxes::read expects, lbl_fluxes.cpp:60-133)
-void define_flux_variables(NcOut& out, bool sw, size_t ngas, int nmu, int nband, size_t nwav, const std::string& ids, bool boundary) {
+void define_flux_variables(NcOut& out, bool sw, size_t ngas, int nmu, int nband, size_t nwav, const std::string& ids, bool boundary,
+                           bool rayleigh = false) {
   if (sw) {
     out.dim("gas", ngas); out.dim("mu0", nmu); out.dim("band_sw", nband);
     out.var("mole_fraction_fl", NC_FLOAT_T, {"column", "gas", "level"}, "Mole fraction at full levels", "1");
@@ -210,12 +224,15 @@ void define_flux_variables(NcOut& out, bool sw, size_t ngas, int nmu, int nband,
     out.var("band_wavenumber2_sw", NC_FLOAT_T, {"band_sw"}, "Upper bound wavenumber for shortwave band", "cm-1");
     out.var("band_flux_up_sw", NC_FLOAT_T, {"column", "mu0", "half_level", "band_sw"}, "Upwelling shortwave flux in bands", "W m-2");
     out.var("band_flux_dn_direct_sw", NC_FLOAT_T, {"column", "mu0", "half_level", "band_sw"}, "Downwelling direct shortwave flux in bands", "W m-2");
+    if (rayleigh) out.var("band_flux_dn_sw", NC_FLOAT_T, {"column", "mu0", "half_level", "band_sw"}, "Downwelling shortwave flux in bands", "W m-2");
     out.att(ids, "constituent_id");
+    if (rayleigh) out.att("two-stream", "rayleigh_scattering");
     if (boundary) {     // what LblFluxes::read maps to g points (lbl_fluxes.cpp:183-246)
       out.dim("wavenumber", nwav);
       out.var("wavenumber", NC_DOUBLE_T, {"wavenumber"}, "Wavenumber", "cm-1");
       out.var("spectral_flux_dn_direct_surf_sw", NC_FLOAT_T, {"column", "mu0", "wavenumber"}, "Spectral direct shortwave flux at the surface", "W m-2");
       out.var("spectral_flux_up_toa_sw", NC_FLOAT_T, {"column", "mu0", "wavenumber"}, "Spectral upwelling shortwave flux at top of atmosphere", "W m-2");
+      if (rayleigh) out.var("spectral_flux_dn_surf_sw", NC_FLOAT_T, {"column", "mu0", "wavenumber"}, "Spectral shortwave flux at the surface", "W m-2");
     }
   } else {
     out.dim("gas", ngas); out.dim("band_lw", nband);
@@ -251,8 +268,8 @@ void bands_to_file_order(int nband, size_t nhl, const double* b, double* t /* [n
 inline int ckdmip_main(int argc, char** argv, bool sw) {
   try {
     std::vector<GasArg> gases;
-    std::string config_file, scenario, output, ckd_file, ssi_file, scenarios_file;
-    bool merge_only = false, per_file_scaling = false;
+    std::string config_file, scenario, output, ckd_file, ssi_file, scenarios_file, rayleigh_file;
+    bool merge_only = false, per_file_scaling = false, rayleigh_scattering = false;
     long col_a = -1, col_b = -1;
     GasArg pending;
     for (int i = 1; i < argc; ++i) {
@@ -265,12 +282,23 @@ inline int ckdmip_main(int argc, char** argv, bool sw) {
       else if (a == "--ssi") { need(1); ssi_file = argv[++i]; }
       else if (a == "--merge-only") merge_only = true;
       else if (a == "--scenarios") { need(1); scenarios_file = argv[++i]; }
+      else if (a == "--rayleigh") { need(1); rayleigh_file = argv[++i]; }
+      else if (a == "--rayleigh-scattering") rayleigh_scattering = true;
       else if (a == "--column-range") { need(2); col_a = std::atol(argv[++i]); col_b = std::atol(argv[++i]); }
       else if (a == "--scale") { need(1); pending.mode = GasArg::SCALE; pending.value = std::atof(argv[++i]); per_file_scaling = true; }
       else if (a == "--conc") { need(1); pending.mode = GasArg::CONC; pending.value = std::atof(argv[++i]); per_file_scaling = true; }
       else if (a == "--const") { need(1); pending.mode = GasArg::CONST; pending.value = std::atof(argv[++i]); per_file_scaling = true; }
       else if (a.rfind("--", 0) == 0) fail(ECCKD_PARAMETER_ERROR, "Argument \"%s\" not understood", a.c_str());
       else { pending.path = a; gases.push_back(pending); pending = GasArg(); }
+    }
+    if (!rayleigh_file.empty() || rayleigh_scattering) {     // scattering is opt-in, shortwave only, one column set per call
+      const char* sw_switch = !rayleigh_file.empty() ? "--rayleigh" : "--rayleigh-scattering";
+      const char* with = !sw ? "the longwave tool" : merge_only ? "--merge-only" : !scenarios_file.empty() ? "--scenarios" : nullptr;
+      if (with) fail(ECCKD_PARAMETER_ERROR, "\"%s\" cannot be combined with %s", sw_switch, with);
+      if (!rayleigh_file.empty() && !ckd_file.empty())
+        fail(ECCKD_PARAMETER_ERROR, "\"--rayleigh\" names a spectrum file of the default mode; with --ckd use --rayleigh-scattering");
+      if (rayleigh_scattering && ckd_file.empty())
+        fail(ECCKD_PARAMETER_ERROR, "\"--rayleigh-scattering\" needs --ckd; in the default mode name the spectrum with --rayleigh");
     }
     std::vector<ScenarioRow> table;              // --scenarios: every check of the table before a device is opened
     if (!scenarios_file.empty()) {
@@ -299,6 +327,9 @@ inline int ckdmip_main(int argc, char** argv, bool sw) {
         std::vector<double> mu0 = nl.mu0;
         if (mu0.empty()) mu0 = {0.5};
         const int nmu = (int)mu0.size();
+        const bool have_ray = f.exist("rayleigh_optical_depth");
+        if (rayleigh_scattering && !have_ray)
+          fail(ECCKD_PARAMETER_ERROR, "\"--rayleigh-scattering\": %s holds no rayleigh_optical_depth", ckd_file.c_str());
         NcOut out(output);
         out.dim("column", ncol); out.dim("mu0", nmu); out.dim("half_level", nlay + 1); out.dim("g_point", ng);
         out.var("pressure_hl", NC_FLOAT_T, {"column", "half_level"}, "Pressure at half levels", "Pa");
@@ -308,13 +339,34 @@ inline int ckdmip_main(int argc, char** argv, bool sw) {
         out.var("flux_dn_direct_sw", NC_FLOAT_T, {"column", "mu0", "half_level"}, "Downwelling direct shortwave flux", "W m-2");
         out.var("spectral_flux_up_sw", NC_FLOAT_T, {"column", "mu0", "half_level", "g_point"}, "Upwelling shortwave flux per g point", "W m-2");
         out.var("spectral_flux_dn_direct_sw", NC_FLOAT_T, {"column", "mu0", "half_level", "g_point"}, "Downwelling direct shortwave flux per g point", "W m-2");
+        if (rayleigh_scattering)
+          out.var("spectral_flux_dn_sw", NC_FLOAT_T, {"column", "mu0", "half_level", "g_point"}, "Downwelling shortwave flux per g point", "W m-2");
         if (!scenario.empty()) out.att(scenario, "scenario");
         out.att(history, "history");
+        if (rayleigh_scattering) out.att("two-stream", "rayleigh_scattering");
         out.end_define();
         out.write("mu0", mu0);
         const size_t nhg = (size_t)(nlay + 1) * ng;
-        const bool have_ray = f.exist("rayleigh_optical_depth");
-        for (int c = 0; c < ncol; ++c) {
+        if (rayleigh_scattering) for (int c = 0; c < ncol; ++c) {  // two-stream per g point, on the device (ecckd_rt_sw_gpoints_rayleigh)
+          const std::vector<double> od = f.read("optical_depth", c), ray = f.read("rayleigh_optical_depth", c), incoming = f.read("incoming_sw", c);
+          std::vector<double> dir_all(nmu * nhg), dn_all(nmu * nhg), up_all(nmu * nhg);
+          std::vector<double> bdir((size_t)nmu * (nlay + 1), 0.0), bdn(bdir), bup(bdir);
+          for (int m = 0; m < nmu; ++m) {
+            ck(ecckd_rt_sw_gpoints_rayleigh(dev.ctx(), 1, nlay, ng, mu0[m], nl.surf_albedo, incoming.data(), od.data(), ray.data(), &dir_all[m * nhg],
+                                            &dn_all[m * nhg], &up_all[m * nhg]));
+            for (int i = 0; i <= nlay; ++i)
+              for (int g = 0; g < ng; ++g) {
+                bdir[(size_t)m * (nlay + 1) + i] += dir_all[m * nhg + (size_t)i * ng + g];
+                bdn[(size_t)m * (nlay + 1) + i] += dn_all[m * nhg + (size_t)i * ng + g];
+                bup[(size_t)m * (nlay + 1) + i] += up_all[m * nhg + (size_t)i * ng + g];
+              }
+          }
+          out.write_slice("pressure_hl", c, f.read("pressure_hl", c));
+          out.write_slice("flux_dn_direct_sw", c, bdir); out.write_slice("flux_dn_sw", c, bdn); out.write_slice("flux_up_sw", c, bup);
+          out.write_slice("spectral_flux_dn_direct_sw", c, dir_all); out.write_slice("spectral_flux_dn_sw", c, dn_all);
+          out.write_slice("spectral_flux_up_sw", c, up_all);
+        }
+        else for (int c = 0; c < ncol; ++c) {
           std::vector<double> od = f.read("optical_depth", c);
           if (have_ray) {                       // one more absorber, as in the reference's forward model (solve_adept.cpp:34)
             const std::vector<double> ray = f.read("rayleigh_optical_depth", c);
@@ -533,7 +585,7 @@ inline int ckdmip_main(int argc, char** argv, bool sw) {
       out.att(ids, "molecules");
       out.att("composite", "constituent_id");
     } else {
-      define_flux_variables(out, sw, gases.size(), nmu, nband, nwav, ids, nl.boundary_fluxes);
+      define_flux_variables(out, sw, gases.size(), nmu, nband, nwav, ids, nl.boundary_fluxes, !rayleigh_file.empty());
     }
     if (!scenario.empty()) out.att(scenario, "scenario");
     out.att(history, "history");
@@ -549,6 +601,10 @@ inline int ckdmip_main(int argc, char** argv, bool sw) {
     }
     double* const p_bnd_dn = nl.boundary_fluxes && !merge_only ? d_bnd_dn.as<double>() : nullptr;
     double* const p_bnd_up = nl.boundary_fluxes && !merge_only ? d_bnd_up.as<double>() : nullptr;
+    const int ngroup = std::min(8, std::max(nmu, 1));          // --rayleigh: angles per call, the entry takes up to 8
+    DevBuf d_ray_dir, d_ray_dn, d_ray_up;                      // their boundary fluxes, [angle][wavenumber]
+    if (!rayleigh_file.empty() && nl.boundary_fluxes)
+      for (DevBuf* b : {&d_ray_dir, &d_ray_dn, &d_ray_up}) b->alloc(dev, (size_t)ngroup * nwav * sizeof(double));
 
     for (int c = c0; c <= c1; ++c) {
       const Spectrum col = c == 0 ? first : read_spectrum(gases[0].path, c, false);
@@ -573,6 +629,41 @@ inline int ckdmip_main(int argc, char** argv, bool sw) {
       if (!col.temperature_hl.empty()) out.write_slice("temperature_hl", oc, col.temperature_hl);
       if (merge_only) {
         out.write_slice("optical_depth", oc, d_merged.download<double>());
+      } else if (sw && !rayleigh_file.empty()) {   // the absorbers merged above, the Rayleigh spectrum beside them: two-stream
+        const size_t nhl = (size_t)nlay + 1;
+        NcIn fr(rayleigh_file);
+        const DevOd ray = read_od_dev(dev, fr, c, nlay, nwav);
+        ck(ecckd_synchronize(dev.ctx()));
+        std::vector<double> tdir((size_t)nmu * nhl * nband), tdn(tdir.size()), tup(tdir.size()), sdir((size_t)nmu * nhl), sdn(sdir.size()), sup(sdir.size());
+        std::vector<double> all_dir, all_dn, all_up;     // (mu0, wavenumber) boundary fluxes of this column
+        const bool bnd = nl.boundary_fluxes;
+        for (int m0 = 0; m0 < nmu; m0 += ngroup) {
+          const int nm = std::min(ngroup, nmu - m0);
+          std::vector<double> gdir((size_t)nm * nband * nhl), gdn(gdir.size()), gup(gdir.size());
+          ck(ecckd_lbl_band_fluxes_sw_rayleigh(dev.ctx(), nlay, nwav, nm, mu0.data() + m0, d_ssi.as<double>(), d_albedo.as<double>(), d_merged.ptr(),
+                                               ECCKD_F64, nwav, ray.buf.ptr(), ray.type, nwav, nband, bbegin.data(), bend.data(), gdir.data(),
+                                               gdn.data(), gup.data(), bnd ? d_ray_dir.as<double>() : nullptr, bnd ? d_ray_dn.as<double>() : nullptr,
+                                               bnd ? d_ray_up.as<double>() : nullptr));
+          if (bnd) {
+            const std::vector<double> a = d_ray_dir.download<double>(), b = d_ray_dn.download<double>(), u = d_ray_up.download<double>();
+            all_dir.insert(all_dir.end(), a.begin(), a.begin() + (size_t)nm * nwav);
+            all_dn.insert(all_dn.end(), b.begin(), b.begin() + (size_t)nm * nwav);
+            all_up.insert(all_up.end(), u.begin(), u.begin() + (size_t)nm * nwav);
+          }
+          for (int m = 0; m < nm; ++m) {
+            const size_t from = (size_t)m * nband * nhl, to = (size_t)(m0 + m);
+            bands_to_file_order(nband, nhl, &gdir[from], &tdir[to * nhl * nband], &sdir[to * nhl]);
+            bands_to_file_order(nband, nhl, &gdn[from], &tdn[to * nhl * nband], &sdn[to * nhl]);
+            bands_to_file_order(nband, nhl, &gup[from], &tup[to * nhl * nband], &sup[to * nhl]);
+          }
+        }
+        out.write_slice("mole_fraction_fl", oc, vmr_all);
+        out.write_slice("band_flux_dn_direct_sw", oc, tdir); out.write_slice("band_flux_dn_sw", oc, tdn); out.write_slice("band_flux_up_sw", oc, tup);
+        out.write_slice("flux_dn_direct_sw", oc, sdir); out.write_slice("flux_dn_sw", oc, sdn); out.write_slice("flux_up_sw", oc, sup);
+        if (bnd) {
+          out.write_slice("spectral_flux_dn_direct_surf_sw", oc, all_dir); out.write_slice("spectral_flux_dn_surf_sw", oc, all_dn);
+          out.write_slice("spectral_flux_up_toa_sw", oc, all_up);
+        }
       } else if (sw) {
         const size_t nhl = (size_t)nlay + 1;
         std::vector<double> tdn((size_t)nmu * nhl * nband), tup((size_t)nmu * nhl * nband), sdn((size_t)nmu * nhl, 0.0), sup((size_t)nmu * nhl, 0.0);

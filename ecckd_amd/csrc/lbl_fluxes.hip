@@ -169,6 +169,45 @@ k_rt_sw_gpoints(int ncol, int nlay, int ng, double mu0, double albedo, const dou
   for (int l = nlay - 1; l >= 0; --l) { f = f * exp(-2.0 * tau[(size_t)l * ng]); fu[(size_t)l * ng] = f; }
 }
 
+// k_rt_sw_gpoints with Rayleigh scattering: the two-stream transfer of lbl_rt.hpp per (column, g point).  The three output
+// matrices hold the per-level state between the sweeps - D in `direct`, the albedo A below each level in `dn`, the source S in
+// `up` - each element written and read by its own thread only, and leave holding the fluxes (dn: direct plus diffuse).
+__global__ void __launch_bounds__(256)
+k_rt_sw_gpoints_rayleigh(int ncol, int nlay, int ng, double mu0, double minus_sec_sza, double albedo, const double* __restrict__ incoming /*[ncol][ng]*/,
+                         const double* __restrict__ od, const double* __restrict__ od_ray, double* direct, double* dn, double* up) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)ncol * ng) return;
+  const size_t c = t / ng, g = t % ng;
+  const double* tau_abs = od + c * (size_t)nlay * ng + g;
+  const double* tau_ray = od_ray + c * (size_t)nlay * ng + g;
+  double* fdir = direct + c * (size_t)(nlay + 1) * ng + g;
+  double* fd = dn + c * (size_t)(nlay + 1) * ng + g;
+  double* fu = up + c * (size_t)(nlay + 1) * ng + g;
+  double f = mu0 * incoming[c * ng + g];
+  fdir[0] = f;
+  for (int l = 0; l < nlay; ++l) {
+    f = f * exp(minus_sec_sza * (tau_abs[(size_t)l * ng] + tau_ray[(size_t)l * ng]));
+    fdir[(size_t)(l + 1) * ng] = f;
+  }
+  double a = albedo, src = albedo * f;
+  fd[(size_t)nlay * ng] = a;
+  fu[(size_t)nlay * ng] = src;
+  for (int l = nlay - 1; l >= 0; --l) {
+    const RayleighLayer L = rayleigh_layer(tau_abs[(size_t)l * ng], tau_ray[(size_t)l * ng], mu0, minus_sec_sza);
+    rayleigh_up(L, fdir[(size_t)l * ng], a, src, a, src);
+    fd[(size_t)l * ng] = a;
+    fu[(size_t)l * ng] = src;
+  }
+  double diffuse = 0.0, flux_up = src;
+  fd[0] = diffuse + fdir[0];
+  for (int l = 0; l < nlay; ++l) {
+    const RayleighLayer L = rayleigh_layer(tau_abs[(size_t)l * ng], tau_ray[(size_t)l * ng], mu0, minus_sec_sza);
+    rayleigh_down(L, fdir[(size_t)l * ng], fd[(size_t)(l + 1) * ng], fu[(size_t)(l + 1) * ng], diffuse, diffuse, flux_up);
+    fd[(size_t)(l + 1) * ng] = diffuse + fdir[(size_t)(l + 1) * ng];
+    fu[(size_t)(l + 1) * ng] = flux_up;
+  }
+}
+
 int combine(ecckd_ctx* ctx, int nlay, int nband, const std::vector<BandChunk>& chunks, const double* d_partial,
             double* h_flux_dn, double* h_flux_up) {
   const int nhl = nlay + 1;
@@ -363,6 +402,39 @@ int ecckd_rt_sw_gpoints(ecckd_ctx* ctx, int ncol, int nlay, int ng, double cos_s
   hipLaunchKernelGGL(k_rt_sw_gpoints, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, ctx->stream, ncol, nlay, ng, cos_sza, albedo, d_in,
                      d_od, d_dn, d_up);
   ECCKD_HIP_CHECK(hipGetLastError());
+  ECCKD_HIP_CHECK(hipMemcpyAsync(h_flux_dn, d_dn, nh * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  ECCKD_HIP_CHECK(hipMemcpyAsync(h_flux_up, d_up, nh * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return ECCKD_OK;
+}
+
+int ecckd_rt_sw_gpoints_rayleigh(ecckd_ctx* ctx, int ncol, int nlay, int ng, double cos_sza, double albedo, const double* h_incoming,
+                                 const double* h_od, const double* h_od_rayleigh, double* h_flux_dn_direct, double* h_flux_dn,
+                                 double* h_flux_up) {
+  const char* who = "ecckd_rt_sw_gpoints_rayleigh";
+  ECCKD_REQUIRE(ctx && ncol > 0 && nlay > 0 && ng > 0 && h_incoming && h_od && h_od_rayleigh && h_flux_dn_direct && h_flux_dn && h_flux_up,
+                "%s: bad argument", who);
+  double h_ang[2 * LBL_MAX_SZA];
+  ECCKD_CHECK(sw_angle_table(who, 1, &cos_sza, h_ang));
+  ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
+  const size_t nl = (size_t)ncol * nlay * ng, nh = (size_t)ncol * (nlay + 1) * ng, ni = (size_t)ncol * ng;
+  const size_t b_i = ecckd_align_up(ni * sizeof(double), 256), b_l = ecckd_align_up(nl * sizeof(double), 256),
+               b_h = ecckd_align_up(nh * sizeof(double), 256);
+  ECCKD_CHECK(ecckd::ensure_scratch(ctx, b_i + 2 * b_l + 3 * b_h));
+  char* q = (char*)ctx->scratch;
+  double* d_in = (double*)q; q += b_i;
+  double* d_od = (double*)q; q += b_l;
+  double* d_ray = (double*)q; q += b_l;
+  double* d_dir = (double*)q; q += b_h;
+  double* d_dn = (double*)q; q += b_h;
+  double* d_up = (double*)q;
+  ECCKD_HIP_CHECK(hipMemcpyAsync(d_in, h_incoming, ni * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  ECCKD_HIP_CHECK(hipMemcpyAsync(d_od, h_od, nl * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  ECCKD_HIP_CHECK(hipMemcpyAsync(d_ray, h_od_rayleigh, nl * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(k_rt_sw_gpoints_rayleigh, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, ctx->stream, ncol, nlay, ng, h_ang[0],
+                     h_ang[LBL_MAX_SZA], albedo, d_in, d_od, d_ray, d_dir, d_dn, d_up);
+  ECCKD_HIP_CHECK(hipGetLastError());
+  ECCKD_HIP_CHECK(hipMemcpyAsync(h_flux_dn_direct, d_dir, nh * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   ECCKD_HIP_CHECK(hipMemcpyAsync(h_flux_dn, d_dn, nh * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   ECCKD_HIP_CHECK(hipMemcpyAsync(h_flux_up, d_up, nh * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));

@@ -1,0 +1,189 @@
+// lbl_fluxes_sw_rayleigh.hip - line-by-line shortwave band fluxes of one column with Rayleigh scattering: the two-stream
+// transfer of lbl_rt.hpp (rayleigh_layer, rayleigh_up, rayleigh_down) per wavenumber, which the reference does not contain
+// (it masks the upwelling fluxes it cannot represent, LblFluxes::mask_rayleigh_up); the external CKDMIP shortwave tool scatters
+// by the rayleigh_optical_depth that run_ckd writes apart for it (run_ckd.cpp:166-192).
+//
+// One thread per wavenumber of a BandChunk, nsza = 1..8 solar zenith angles per launch, angle after angle.  The adding method
+// runs up the column and then down it, so a thread needs per level what the other sweep left: the direct flux D (written by
+// the first sweep down, the chain of k_lbl_fluxes_sw), and the albedo A and source S below each level (written by the sweep
+// up).  That is 3 (nlay + 1) doubles per thread for the angle in hand - 1.3 KB at 54 layers, too much for registers and, at
+// 256 threads, for the LDS a block should take - so it lives in a device workspace [block][slot][level][thread]: a thread
+// writes and later reads only its own element, every access coalesced, no barrier needed.  The layer terms are computed again
+// in each sweep from the two optical depths rather than stored (two exp, a sqrt and three divisions against five more
+// doubles per level written and read).  The grid is bounded (RAYLEIGH_BLOCKS_PER_CU blocks per compute unit, or
+// ECCKD_RAYLEIGH_GRID blocks) and its blocks loop over the chunks, so the workspace is sized by the grid, not by nwav.
+// Per level the fluxes of a block are reduced wave -> block in the fixed order of k_lbl_fluxes_sw and written as chunk
+// partials per angle, which the host adds in chunk order (bitwise reproducible, and an angle's bits do not depend on the
+// angles computed with it).
+#include "common.hpp"
+#include "lbl_rt.hpp"
+
+#include <cstdlib>
+#include <vector>
+
+namespace {
+
+using namespace ecckd::lbl;
+
+constexpr int RAYLEIGH_BLOCKS_PER_CU = 3;     // the waves per SIMD its registers allow
+constexpr int RAYLEIGH_SLOTS = 3;        // D, A, S per level
+constexpr int RAYLEIGH_FLUXES = 3;       // direct, total down, up per level
+
+// LDS: acc[4][3][nhl]; ws: [gridDim.x][3][nhl][LBL_THREADS]; partial: [nchunk][nsza][3][nhl]
+template <typename AbsT, typename RayT>
+__global__ void __launch_bounds__(LBL_THREADS)
+k_lbl_fluxes_sw_rayleigh(int nlay, int nsza, int nchunk, size_t nwav, size_t abs_stride, size_t ray_stride,
+                         const BandChunk* __restrict__ chunks, const double* __restrict__ ang /* sw_angle_table */,
+                         const double* __restrict__ ssi, const double* __restrict__ albedo /* per wavenumber or NULL */,
+                         const AbsT* __restrict__ od_abs, const RayT* __restrict__ od_ray, double* ws, double* __restrict__ partial,
+                         double* __restrict__ surf_dn_direct /* [nsza][nwav] or NULL */, double* __restrict__ surf_dn /* same */,
+                         double* __restrict__ toa_up /* same */) {
+  extern __shared__ double s_acc[];
+  const int nhl = nlay + 1;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  double* acc_dir = s_acc + wave * RAYLEIGH_FLUXES * nhl;
+  double* acc_dn = acc_dir + nhl;
+  double* acc_up = acc_dn + nhl;
+  double* my = ws + (size_t)blockIdx.x * RAYLEIGH_SLOTS * nhl * LBL_THREADS + tid;
+  double* w_d = my;                                        // element (slot, level) of this thread: [(slot * nhl + level) * LBL_THREADS]
+  double* w_a = my + (size_t)nhl * LBL_THREADS;
+  double* w_s = my + (size_t)2 * nhl * LBL_THREADS;
+  for (int ci = blockIdx.x; ci < nchunk; ci += gridDim.x) {
+    const BandChunk c = chunks[ci];
+    const long long i = c.i1 + tid;
+    const bool live = i <= c.i2;
+    const size_t j = live ? (size_t)i : (size_t)c.i2;
+    const double inc = ssi[j];
+    const double alb = albedo ? albedo[j] : 0.0;
+    auto layer = [&](int l, double mu0, double minus_sec_sza) {
+      return rayleigh_layer((double)od_abs[(size_t)l * abs_stride + j], (double)od_ray[(size_t)l * ray_stride + j], mu0, minus_sec_sza);
+    };
+    for (int s = 0; s < nsza; ++s) {
+      const double cos_sza = ang[s], minus_sec_sza = ang[LBL_MAX_SZA + s];     // (uniform: scalar loads)
+      for (int t = tid; t < 4 * RAYLEIGH_FLUXES * nhl; t += LBL_THREADS) s_acc[t] = 0.0;
+      __syncthreads();
+      // the direct beam, as k_lbl_fluxes_sw on tau_abs + tau_ray; dead lanes carry no flux at all
+      double flux = live ? cos_sza * inc : 0.0;
+      w_d[0] = flux;
+      for (int l = 0; l < nlay; ++l) {
+        const double tau = (double)od_abs[(size_t)l * abs_stride + j] + (double)od_ray[(size_t)l * ray_stride + j];
+        flux = flux * exp(minus_sec_sza * tau);
+        w_d[(size_t)(l + 1) * LBL_THREADS] = flux;
+      }
+      if (surf_dn_direct && live) surf_dn_direct[(size_t)s * nwav + j] = flux;
+      const double d_surf = flux;
+      // up: the albedo and the source below every level
+      double a = alb, src = alb * flux;
+      w_a[(size_t)nlay * LBL_THREADS] = a;
+      w_s[(size_t)nlay * LBL_THREADS] = src;
+      for (int l = nlay - 1; l >= 0; --l) {
+        const RayleighLayer L = layer(l, cos_sza, minus_sec_sza);
+        rayleigh_up(L, w_d[(size_t)l * LBL_THREADS], a, src, a, src);
+        w_a[(size_t)l * LBL_THREADS] = a;
+        w_s[(size_t)l * LBL_THREADS] = src;
+      }
+      // down: the diffuse and the upwelling flux at every level.  The direct flux is summed here, from the value the first sweep
+      // stored, and not where it is computed: there the product flux * exp() would fuse into the first addition of the wave's sum,
+      // and direct and total would differ in the last bit where nothing scatters.
+      double dn = 0.0, up = src;
+      double d_top = w_d[0];
+      wave_add(&acc_dir[0], lane, d_top);
+      wave_add(&acc_dn[0], lane, dn + d_top);
+      wave_add(&acc_up[0], lane, up);
+      if (toa_up && live) toa_up[(size_t)s * nwav + j] = up;
+      for (int l = 0; l < nlay; ++l) {
+        const RayleighLayer L = layer(l, cos_sza, minus_sec_sza);
+        rayleigh_down(L, d_top, w_a[(size_t)(l + 1) * LBL_THREADS], w_s[(size_t)(l + 1) * LBL_THREADS], dn, dn, up);
+        d_top = w_d[(size_t)(l + 1) * LBL_THREADS];
+        wave_add(&acc_dir[l + 1], lane, d_top);
+        wave_add(&acc_dn[l + 1], lane, dn + d_top);
+        wave_add(&acc_up[l + 1], lane, up);
+      }
+      if (surf_dn && live) surf_dn[(size_t)s * nwav + j] = dn + d_surf;
+      __syncthreads();
+      for (int t = tid; t < RAYLEIGH_FLUXES * nhl; t += LBL_THREADS)
+        partial[((size_t)ci * nsza + s) * RAYLEIGH_FLUXES * nhl + t] = add_waves(s_acc, RAYLEIGH_FLUXES * nhl, t);
+      __syncthreads();
+    }
+  }
+}
+
+// blocks of the launch: every chunk its own up to the bound, ECCKD_RAYLEIGH_GRID (>= 1) in place of the bound
+size_t rayleigh_grid(const ecckd_ctx* ctx, size_t nchunk) {
+  size_t cap = (size_t)std::max(ctx->num_cu, 1) * RAYLEIGH_BLOCKS_PER_CU;
+  if (const char* e = std::getenv("ECCKD_RAYLEIGH_GRID")) {
+    const long v = std::atol(e);
+    if (v >= 1) cap = (size_t)v;
+  }
+  return std::min(nchunk, cap);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ecckd_lbl_band_fluxes_sw_rayleigh(ecckd_ctx* ctx, int nlay, size_t nwav, int nsza, const double* h_cos_sza, const double* d_ssi,
+                                      const double* d_albedo, const void* d_od_abs, int abs_type, size_t abs_stride,
+                                      const void* d_od_ray, int ray_type, size_t ray_stride, int nband, const int64_t* h_band_begin,
+                                      const int64_t* h_band_end, double* h_flux_dn_direct, double* h_flux_dn, double* h_flux_up,
+                                      double* d_surf_dn_direct, double* d_surf_dn, double* d_toa_up) {
+  const char* who = "ecckd_lbl_band_fluxes_sw_rayleigh";
+  ECCKD_REQUIRE(ctx && nlay > 0 && h_cos_sza && d_ssi && d_od_abs && d_od_ray && nband > 0 && h_band_begin && h_band_end &&
+                h_flux_dn_direct && h_flux_dn && h_flux_up, "%s: bad argument", who);
+  double h_ang[2 * LBL_MAX_SZA];
+  ECCKD_CHECK(sw_angle_table(who, nsza, h_cos_sza, h_ang));
+  ECCKD_CHECK(check_od(who, abs_type, abs_stride, nwav));
+  ECCKD_CHECK(check_od(who, ray_type, ray_stride, nwav));
+  const size_t nhl = (size_t)nlay + 1;
+  const size_t lds = (size_t)4 * RAYLEIGH_FLUXES * nhl * sizeof(double);
+  ECCKD_REQUIRE(lds <= 64 * 1024, "%s: nlay = %d needs %zu bytes of LDS for the level sums (64 KB at most)", who, nlay, lds);
+  ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
+  std::vector<BandChunk> chunks;
+  ECCKD_CHECK(make_chunks(who, nwav, nband, h_band_begin, h_band_end, chunks));
+  // wavenumbers outside every band carry no flux
+  for (double* p : {d_surf_dn_direct, d_surf_dn, d_toa_up})
+    if (p) ECCKD_HIP_CHECK(hipMemsetAsync(p, 0, (size_t)nsza * nwav * sizeof(double), ctx->stream));
+  const size_t nslab = (size_t)nsza * nband * nhl;
+  std::fill(h_flux_dn_direct, h_flux_dn_direct + nslab, 0.0);
+  std::fill(h_flux_dn, h_flux_dn + nslab, 0.0);
+  std::fill(h_flux_up, h_flux_up + nslab, 0.0);
+  if (chunks.empty()) return ECCKD_OK;
+  const size_t nchunk = chunks.size(), grid = rayleigh_grid(ctx, nchunk);
+  const size_t npart = nchunk * nsza * RAYLEIGH_FLUXES * nhl;
+  const size_t b_ang = ecckd_align_up(sizeof(h_ang), 256), b_chunks = ecckd_align_up(nchunk * sizeof(BandChunk), 256),
+               b_part = ecckd_align_up(npart * sizeof(double), 256),
+               b_ws = grid * RAYLEIGH_SLOTS * nhl * LBL_THREADS * sizeof(double);
+  ECCKD_CHECK(ecckd::ensure_scratch(ctx, b_ang + b_chunks + b_part + b_ws));
+  char* q = (char*)ctx->scratch;
+  double* d_ang = (double*)q; q += b_ang;
+  BandChunk* d_chunks = (BandChunk*)q; q += b_chunks;
+  double* d_part = (double*)q; q += b_part;
+  double* d_ws = (double*)q;
+  ECCKD_HIP_CHECK(hipMemcpyAsync(d_ang, h_ang, sizeof(h_ang), hipMemcpyHostToDevice, ctx->stream));
+  ECCKD_CHECK(ecckd_h2d(ctx, d_chunks, chunks.data(), nchunk * sizeof(BandChunk)));
+  with_od_type(abs_type, [&](auto ta) {
+    with_od_type(ray_type, [&](auto tr) {
+      using AbsT = decltype(ta);
+      using RayT = decltype(tr);
+      hipLaunchKernelGGL((k_lbl_fluxes_sw_rayleigh<AbsT, RayT>), dim3((unsigned)grid), dim3(LBL_THREADS), lds, ctx->stream, nlay, nsza,
+                         (int)nchunk, nwav, abs_stride, ray_stride, (const BandChunk*)d_chunks, (const double*)d_ang, d_ssi, d_albedo,
+                         (const AbsT*)d_od_abs, (const RayT*)d_od_ray, d_ws, d_part, d_surf_dn_direct, d_surf_dn, d_toa_up);
+    });
+  });
+  ECCKD_HIP_CHECK(hipGetLastError());
+  std::vector<double> part(npart);
+  ECCKD_CHECK(ecckd_d2h(ctx, part.data(), d_part, npart * sizeof(double)));
+  for (size_t c = 0; c < nchunk; ++c)                  // chunk order = wavenumber order within each band
+    for (int s = 0; s < nsza; ++s) {
+      const double* p = &part[(c * nsza + s) * RAYLEIGH_FLUXES * nhl];
+      const size_t to = ((size_t)s * nband + chunks[c].band) * nhl;
+      for (size_t i = 0; i < nhl; ++i) {
+        h_flux_dn_direct[to + i] += p[i];
+        h_flux_dn[to + i] += p[nhl + i];
+        h_flux_up[to + i] += p[2 * nhl + i];
+      }
+    }
+  return ECCKD_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,6 @@
-// lbl_rt.hpp - the no-scattering transfer of ONE wavenumber, written once for the line-by-line kernels (lbl_fluxes.hip,
-// lbl_gpoint_fluxes.hip, lbl_gpoint_fluxes_sw.hip, lbl_scenarios.hip), and the host plumbing they share.  DESIGN.md and the
+// lbl_rt.hpp - the transfer of ONE wavenumber, written once for the line-by-line kernels (lbl_fluxes.hip,
+// lbl_gpoint_fluxes.hip, lbl_gpoint_fluxes_sw.hip, lbl_scenarios.hip: no scattering; lbl_fluxes_sw_rayleigh.hip and
+// k_rt_sw_gpoints_rayleigh of lbl_fluxes.hip: Rayleigh scattering), and the host plumbing they share.  DESIGN.md and the
 // tests compare these kernels with each other, bit for bit where they can: one source text keeps an edit from reaching only
 // one of them.  The files are compiled with the default contraction, so an expression here keeps its form and operand order;
 // a reordered one can fuse differently and change bits.
@@ -16,6 +17,15 @@
 //   down        flux = flux * exp(minus_sec_sza * tau),  minus_sec_sza = -1.0 / cos_sza        (:45-50)
 //   surface     flux = flux * albedo                                                           (:70)
 //   up          flux = flux * exp(-2.0 * tau)                                                  (:72-76)
+// Shortwave with Rayleigh scattering (not in the reference: the external CKDMIP tool scatters by rayleigh_optical_depth, its
+// arithmetic is unpinned): the two-stream equations at asymmetry 0 with ecRad's shortwave coefficients
+// (Zdunkowski PIFM: g1 = 2 - 1.25 w, g2 = 0.75 w, g3 = g4 = 0.5), Meador & Weaver's (1980) closed form per layer and the
+// adding method over the column; tests/rayleigh_ref.py restates it.  The direct beam is the chain above on tau_abs + tau_ray.
+//   per layer   rayleigh_layer(tau_abs, tau_ray, mu0, minus_sec_sza) -> R, T, Tdir, Rdir, Tdd per unit direct flux at its top
+//   surface     A = albedo, S = albedo * D(surface)
+//   up          rayleigh_up(layer, D(top), A below, S below) -> A, S at the layer's top
+//   top         up = S, diffuse down = 0
+//   down        rayleigh_down(layer, D(top), A below, S below, diffuse down at the top) -> diffuse down, up at its base
 // The tuned kernels of find_g.hip, optimize.hip, create_lut.hip and reorder.hip keep their own SGPR-pinned variants.
 #pragma once
 
@@ -80,6 +90,78 @@ __device__ __forceinline__ double lw_step(double flux, double eps, double fac, d
 // emissivity 1: the reference's emissivity * B + (1 - emissivity) * flux, kept as it stands
 __device__ __forceinline__ double lw_surface(double flux, double b_surf) {
   return b_surf * 1.0 + (1.0 - 1.0) * flux;
+}
+
+// The layer terms of the Rayleigh two-stream transfer per unit direct flux D at the layer's top: diffuse reflectance R and
+// transmittance T, direct transmittance Tdir, and the parts of the direct beam that leave the layer upwards (Rdir) and
+// downwards (Tdd) as diffuse light.
+struct RayleighLayer { double R, T, Tdir, Rdir, Tdd; };
+
+constexpr double RAYLEIGH_RESONANCE_H = 1.0e-4;
+
+// Rdir and Tdd of the closed form before their clamps, with mu0 and tdir = exp(-tau / mu0) in every place they occur
+__device__ __forceinline__ void rayleigh_direct(double w, double k, double e, double e2, double f, double a1, double a2, double mu0,
+                                                double tdir, double& rdir, double& tdd) {
+  const double g3 = 0.5, g4 = 0.5;
+  const double km = k * mu0;
+  const double f2 = w * f / (1.0 - km * km);
+  rdir = f2 * ((1.0 - km) * (a2 + k * g3) - (1.0 + km) * (a2 - k * g3) * e2 - 2.0 * k * e * (g3 - a2 * mu0) * tdir);
+  tdd = f2 * (2.0 * k * e * (g4 + a1 * mu0) - tdir * ((1.0 + km) * (a1 + k * g4) - (1.0 - km) * (a1 - k * g4) * e2));
+}
+
+// The closed form divides by 1 - (k mu0)^2, and k -> 2 as w -> 0: the resonance k mu0 = 1 sits on mu0 = 0.5 for every weakly
+// scattering layer.  Within |1 - k mu0| < h the direct terms are therefore evaluated at mu0 = (1 -+ 2h) / k, each with its own
+// Tdir, and interpolated linearly to mu0 (R, T and Tdir do not depend on the shift); w = 0 is a branch of its own, the
+// no-scattering path with the diffuse transmittance exp(-2 tau).
+__device__ __forceinline__ RayleighLayer rayleigh_layer(double tau_abs, double tau_ray, double mu0, double minus_sec_sza) {
+  RayleighLayer L;
+  const double tau = tau_abs + tau_ray;
+  L.Tdir = exp(minus_sec_sza * tau);
+  if (!(tau_ray > 0.0 && tau > 0.0)) {
+    L.R = 0.0; L.T = exp(-2.0 * tau); L.Rdir = 0.0; L.Tdd = 0.0;
+    return L;
+  }
+  const double g3 = 0.5, g4 = 0.5;
+  const double w = tau_ray / tau;
+  const double g1 = 2.0 - 1.25 * w, g2 = 0.75 * w;
+  const double a1 = g1 * g4 + g2 * g3;
+  const double a2 = g1 * g3 + g2 * g4;
+  const double k = sqrt(fmax((g1 - g2) * (g1 + g2), 1e-12));
+  const double e = exp(-k * tau);
+  const double e2 = e * e;
+  const double f = 1.0 / (k + g1 + (k - g1) * e2);
+  L.R = g2 * (1.0 - e2) * f;
+  L.T = 2.0 * k * e * f;
+  double rdir, tdd;
+  if (fabs(1.0 - k * mu0) < RAYLEIGH_RESONANCE_H) {
+    const double mu_a = (1.0 - 2.0 * RAYLEIGH_RESONANCE_H) / k, mu_b = (1.0 + 2.0 * RAYLEIGH_RESONANCE_H) / k;
+    double ra, ta, rb, tb;
+    rayleigh_direct(w, k, e, e2, f, a1, a2, mu_a, exp((-1.0 / mu_a) * tau), ra, ta);
+    rayleigh_direct(w, k, e, e2, f, a1, a2, mu_b, exp((-1.0 / mu_b) * tau), rb, tb);
+    const double x = (mu0 - mu_a) / (mu_b - mu_a);
+    rdir = ra + (rb - ra) * x;
+    tdd = ta + (tb - ta) * x;
+  } else {
+    rayleigh_direct(w, k, e, e2, f, a1, a2, mu0, L.Tdir, rdir, tdd);
+  }
+  L.Rdir = fmin(fmax(rdir, 0.0), 1.0 - L.Tdir);
+  L.Tdd = fmin(fmax(tdd, 0.0), 1.0 - L.Tdir - L.Rdir);
+  return L;
+}
+
+// adding, upwards: the albedo A and the source S (the upwelling flux the direct beam alone causes) seen from the layer's top
+__device__ __forceinline__ void rayleigh_up(const RayleighLayer& L, double d_top, double a_below, double s_below, double& a, double& s) {
+  const double inv = 1.0 / (1.0 - a_below * L.R);
+  a = L.R + L.T * L.T * a_below * inv;
+  s = L.Rdir * d_top + L.T * (s_below + a_below * L.Tdd * d_top) * inv;
+}
+
+// adding, downwards: the diffuse downwelling and the upwelling flux at the layer's base from the diffuse one at its top
+__device__ __forceinline__ void rayleigh_down(const RayleighLayer& L, double d_top, double a_below, double s_below, double dn_top,
+                                              double& dn, double& up) {
+  const double inv = 1.0 / (1.0 - a_below * L.R);
+  dn = (L.T * dn_top + L.R * s_below + L.Tdd * d_top) * inv;
+  up = a_below * dn + s_below;
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host

@@ -496,6 +496,31 @@ int ecckd_lbl_band_fluxes_sw_ex(ecckd_ctx* ctx, int nlay, size_t nwav, double co
                                 const int64_t* h_band_begin, const int64_t* h_band_end, double* h_flux_dn_direct,
                                 double* h_flux_up, double* d_surf_dn_direct, double* d_toa_up);
 
+/* Shortwave band fluxes of one column WITH Rayleigh scattering, nsza = 1..8 solar zenith angles (every cos_sza in (0, 1]) per
+ * call: per wavenumber and layer tau = od_abs + od_ray (each ECCKD_F32 or ECCKD_F64, converted to double and added once),
+ * single-scattering albedo w = od_ray / tau, and the two-stream equations at asymmetry 0 with ecRad's shortwave coefficients
+ * (Zdunkowski PIFM: g1 = 2 - 1.25 w, g2 = 0.75 w, g3 = g4 = 0.5), solved by Meador & Weaver's (1980) closed form per layer and
+ * the adding method over the column, above a Lambertian surface (d_albedo[nwav], the same for direct and diffuse light; NULL:
+ * albedo 0).  The reference has no such transfer (it masks the fluxes it cannot represent, LblFluxes::mask_rayleigh_up); the
+ * external CKDMIP tool, which is not among its sources, scatters by the rayleigh_optical_depth run_ckd writes apart
+ * (run_ckd.cpp:166-192): node-for-node agreement with that tool is unpinned.  Where od_ray = 0 this is the
+ * arithmetic of ecckd_lbl_band_fluxes_sw_ex, and the direct beam has that call's bits on tau throughout.
+ * Results: h_flux_dn_direct, h_flux_dn (direct plus diffuse), h_flux_up [nsza][nband][nlay+1]; d_surf_dn_direct, d_surf_dn
+ * (direct plus diffuse), d_toa_up: NULL or device arrays [nsza][nwav], zero outside the bands.  An angle of a call has the
+ * bits of that angle computed by a call of its own.  Per-level state lives in the context's scratch: 3 (nlay+1) doubles per
+ * thread of a bounded grid (3 blocks per compute unit; ECCKD_RAYLEIGH_GRID = N blocks instead). */
+int ecckd_lbl_band_fluxes_sw_rayleigh(ecckd_ctx* ctx, int nlay, size_t nwav, int nsza, const double* h_cos_sza, const double* d_ssi,
+                                      const double* d_albedo, const void* d_od_abs, int abs_type, size_t abs_stride,
+                                      const void* d_od_ray, int ray_type, size_t ray_stride, int nband, const int64_t* h_band_begin,
+                                      const int64_t* h_band_end, double* h_flux_dn_direct, double* h_flux_dn, double* h_flux_up,
+                                      double* d_surf_dn_direct, double* d_surf_dn, double* d_toa_up);
+/* ecckd_rt_sw_gpoints with the same scattering transfer: h_od (absorption) and h_od_rayleigh [ncol][nlay][ng] as run_ckd
+ * writes optical_depth and rayleigh_optical_depth; h_flux_dn_direct, h_flux_dn (direct plus diffuse), h_flux_up
+ * [ncol][nlay+1][ng]. */
+int ecckd_rt_sw_gpoints_rayleigh(ecckd_ctx* ctx, int ncol, int nlay, int ng, double cos_sza, double albedo, const double* h_incoming,
+                                 const double* h_od, const double* h_od_rayleigh, double* h_flux_dn_direct, double* h_flux_dn,
+                                 double* h_flux_up);
+
 /* The band fluxes of one column for nscen SCENARIOS from one read of the gases' spectra: the loop of
  * test/run_lw_lbl_evaluation.sh:286-323 / test/run_sw_lbl_evaluation.sh:70-260 (one call of the CKDMIP tool per scenario, a
  * scenario differing from the next in one scaling per gas file) as one call.  d_od[ngas]: the gases' device matrices
