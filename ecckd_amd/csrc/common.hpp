@@ -89,6 +89,17 @@ void streamer_delete(ecckd_ctx* ctx);               // nc_stream.hip
 // Cores THIS process may count on (context.hip): the affinity mask, capped by the cgroup's CPU quota, divided by the processes
 // the launcher started on this node (LOCAL_WORLD_SIZE: one process per GPU); ECCKD_HOST_CORES overrides.  At least 1.
 int host_cores();
+bool host_oversubscribed();     // find_g_band.hip: more spinning search / batcher threads than cores (they then yield while waiting)
+
+// Results the host needs at once (the errors of a batch of intervals, the cost of a trial point, the dot products of the
+// L-BFGS update) arrive in pinned, host-coherent memory, written by the last kernel of the train that produces them.  Waiting
+// for them with hipStreamSynchronize costs a wake-up through the runtime per wait, and a search is hundreds of dependent
+// batches (equipartition.cpp:638-805: one interval per call), an optimisation two waits per iteration; the host instead marks
+// the n slots as pending - a NaN payload no arithmetic produces - and watches them (context.hip).  slots_wait looks now and
+// then whether the stream has drained or died without delivering (`what` names the results in the message), yields the core
+// while host_oversubscribed(), and with ECCKD_NO_POLL set (an A/B knob) synchronises the stream and checks the delivery.
+void slots_mark_pending(double* h, int n);
+int slots_wait(hipStream_t stream, const double* h, int n, const char* what);
 
 }  // namespace ecckd
 

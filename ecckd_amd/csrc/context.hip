@@ -1,6 +1,8 @@
 // context.hip - context lifetime, device memory helpers, stream timing and the
 // error channel of the C ABI (include/ecckd_hip.h).
 #include "common.hpp"
+#include <atomic>
+#include <immintrin.h>
 #include <map>
 #include <unordered_map>
 #include <cstdlib>
@@ -214,9 +216,47 @@ int ensure_pinned(ecckd_ctx* ctx, size_t bytes) {
     ctx->pinned_bytes = 0;
   }
   size_t want = ecckd_align_up(bytes * 2, 4096);
-  // host-coherent: results that a kernel writes here are visible to the host while the stream is still running (wait_for_slots)
+  // host-coherent: results that a kernel writes here are visible to the host while the stream is still running (slots_wait)
   ECCKD_HIP_CHECK(hipHostMalloc(&ctx->pinned, want, hipHostMallocMapped | hipHostMallocCoherent));
   ctx->pinned_bytes = want;
+  return ECCKD_OK;
+}
+
+constexpr unsigned long long kSlotPending = 0x7ff4dead5eed0001ULL;   // not the canonical quiet NaN, the only one sqrt() and the sums give
+
+void slots_mark_pending(double* h, int n) {
+  volatile unsigned long long* s = reinterpret_cast<volatile unsigned long long*>(h);
+  for (int k = 0; k < n; ++k) s[k] = kSlotPending;
+  std::atomic_thread_fence(std::memory_order_release);
+}
+
+int slots_wait(hipStream_t stream, const double* h, int n, const char* what) {
+  static const bool no_poll = std::getenv("ECCKD_NO_POLL") != nullptr;
+  const volatile unsigned long long* s = reinterpret_cast<const volatile unsigned long long*>(h);
+  auto all_there = [&] {
+    for (int k = 0; k < n; ++k)
+      if (s[k] == kSlotPending) return false;
+    return true;
+  };
+  if (no_poll) {
+    ECCKD_HIP_CHECK(hipStreamSynchronize(stream));
+    return all_there() ? ECCKD_OK : fail(ECCKD_UNEXPECTED_EXCEPTION, "%s were not delivered by the device", what);
+  }
+  for (unsigned spins = 1;; ++spins) {
+    if (all_there()) break;
+    if ((spins & 0x3fff) == 0) {
+      // now and then: has the stream drained (or died) without delivering?  An idle stream has made all its writes visible.
+      const hipError_t q = hipStreamQuery(stream);
+      if (q == hipSuccess) {
+        if (all_there()) break;
+        return fail(ECCKD_UNEXPECTED_EXCEPTION, "%s were not delivered by the device", what);
+      }
+      if (q != hipErrorNotReady)
+        return fail(ECCKD_UNEXPECTED_EXCEPTION, "device failure while waiting for %s: %s", what, hipGetErrorString(q));
+    }
+    if ((spins & 0x3f) == 0 && host_oversubscribed()) std::this_thread::yield(); else _mm_pause();
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
   return ECCKD_OK;
 }
 

@@ -16,7 +16,7 @@
 // The Planck weights are recomputed from (T, wavenumber) on the fly instead of being read from
 // an (nlay, nwav) matrix: 8 B/point/layer of HBM traffic traded for one exp.
 #include "common.hpp"
-#include "fastmath.hpp"
+#include "rt_device.hpp"
 #include "gmap.hpp"
 
 #include <cmath>
@@ -30,29 +30,10 @@ constexpr int GA_THREADS = 256;
 constexpr int GA_PPT = 8;                       // points per thread (halves the cross-lane reductions per point)
 constexpr int GA_CHUNK = GA_THREADS * GA_PPT;   // sorted positions per block
 
-__device__ constexpr double kPlanckH = 6.62606896e-34;
-__device__ constexpr double kLightC = 2.99792458e8;
-__device__ constexpr double kPi = 3.14159265358979323846;
-
 // averaging-method codes of the ABI (ECCKD_AVG_*)
 constexpr int M_LINEAR = 0, M_TRANS = 1, M_TRANS2 = 2, M_SQRT = 3, M_LOG = 4, M_TRANS3 = 6, M_TRANS10 = 7, M_HYBRID = 8;
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_down(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
-  return v;
-}
-
+using ecckd::wave_sum; using ecckd::wave_min; using ecckd::wave_max;   // rt_device.hpp
 using Chunk = ecckd::GmapChunk;
 
 __global__ void __launch_bounds__(256)
@@ -85,37 +66,10 @@ k_gmap_check(size_t nassigned, const int32_t* __restrict__ order, const int32_t*
   if (g_point[order[i]] == g_point[order[i + 1]] && !(wn_s[i + 1] >= wn_s[i])) atomicOr(flag, 2);
 }
 
-// Several per-lane values reduced over the wave TOGETHER: at lane distance 32 a lane hands over one half of its values and
-// combines what it receives with the half it keeps, at distance 16 a half of those, ... - NV + NV/2 + ... exchanges instead of
-// six per value (every exchange is an LDS crossbar operation that all the waves of a CU queue for).  Lane l ends up with the
-// wave's result of value bitreverse6(l).  A fixed tree: bitwise reproducible.
-template <int USED, typename Op>
-__device__ __forceinline__ void fold_level(double* v, bool upper, int mask, Op op) {
-  constexpr int NEXT = (USED + 1) / 2;
-#pragma unroll
-  for (int i = 0; i < NEXT; ++i) {
-    const double a = v[2 * i];
-    const double b = (2 * i + 1 < USED) ? v[2 * i + 1] : a;      // (odd tail: the same value from both halves)
-    const double send = upper ? a : b;
-    const double keep = upper ? b : a;
-    v[i] = op(keep, __shfl_xor(send, mask, 64));
-  }
-}
-template <int NV, typename Op>
-__device__ __forceinline__ void fold_wave(double (&v)[NV], int lane, Op op) {
-  constexpr int U1 = (NV + 1) / 2, U2 = (U1 + 1) / 2, U3 = (U2 + 1) / 2, U4 = (U3 + 1) / 2, U5 = (U4 + 1) / 2;
-  fold_level<NV>(v, (lane & 32) != 0, 32, op);
-  fold_level<U1>(v, (lane & 16) != 0, 16, op);
-  fold_level<U2>(v, (lane & 8) != 0, 8, op);
-  fold_level<U3>(v, (lane & 4) != 0, 4, op);
-  fold_level<U4>(v, (lane & 2) != 0, 2, op);
-  fold_level<U5>(v, (lane & 1) != 0, 1, op);
-}
-
 // K6a.  partial[chunk][layer][6] = { num, den, den_nz, cnt_nz, min, max }.  Per layer and point: the Planck weight at the
 // layer's temperature (planck_function.cpp:48-50) and the averaged quantity of the layer's method
 // (average_optical_depth.cpp:43-133) - the same two exp per layer and point as K1, with the same < 1 ulp exp / division
-// (fastmath.hpp) instead of the library's -; the six per-layer sums of a wave are folded together (above), the waves' results
+// (fastmath.hpp) instead of the library's -; the six per-layer sums of a wave are folded together (fold_wave, rt_device.hpp), the waves' results
 // wait in LDS and are combined in wave order once, after the last layer: no barrier inside the layer loop.
 // dynamic LDS: [nlay][6][GA_THREADS / 64]
 template <typename OdT>
@@ -139,9 +93,8 @@ k_gavg_partial(int nlay, size_t od_stride, const Chunk* __restrict__ chunks, con
     jj[p] = (size_t)order[ii];
     if (hk) {
       // planck_function.cpp:48-50
-      const double inv_cm_2_Hz = 100.0 * kLightC;
-      freq[p] = wn_s[ii] * inv_cm_2_Hz;
-      pref[p] = (dwn_s[ii] * 2.0 * kPlanckH * inv_cm_2_Hz * kPi / (kLightC * kLightC)) * (freq[p] * freq[p] * freq[p]);
+      freq[p] = ecckd::wn_to_freq(wn_s[ii]);
+      pref[p] = ecckd::planck_pref(dwn_s[ii], freq[p]);
     } else {
       freq[p] = 0.0;
       pref[p] = ssi[jj[p]];
@@ -161,7 +114,7 @@ k_gavg_partial(int nlay, size_t od_stride, const Chunk* __restrict__ chunks, con
 #pragma unroll
     for (int p = 0; p < GA_PPT; ++p) {
       if (!live[p]) continue;
-      const double w = hk ? ecckd::div_fast(pref[p], ecckd::exp_fast(freq[p] * hkl) - 1.0) : pref[p];
+      const double w = hk ? ecckd::planck(pref[p], freq[p], hkl) : pref[p];
       sums[1] += w;
       mm[0] = fmin(mm[0], o[p]);
       mm[1] = fmin(mm[1], -o[p]);
@@ -170,8 +123,8 @@ k_gavg_partial(int nlay, size_t od_stride, const Chunk* __restrict__ chunks, con
       else if (lm == M_SQRT) sums[0] += sqrt(o[p]) * w;
       else if (o[p] > 0.0) { sums[0] += log(o[p]) * w; sums[2] += w; sums[3] += 1.0; }      // logarithmic
     }
-    fold_wave<4>(sums, lane, [](double a, double b) { return a + b; });
-    fold_wave<2>(mm, lane, [](double a, double b) { return fmin(a, b); });
+    ecckd::fold_wave<4, false>(sums, lane, [](double a, double b) { return a + b; });
+    ecckd::fold_wave<2, false>(mm, lane, [](double a, double b) { return fmin(a, b); });
     if (kk < 4) s_part[((size_t)l * 6 + kk) * NW + wave] = sums[0];
     if (kk < 2) s_part[((size_t)l * 6 + 4 + kk) * NW + wave] = kk == 0 ? mm[0] : -mm[0];
   }
@@ -254,9 +207,8 @@ k_planck_lut_partial(int nlut, const Chunk* __restrict__ chunks, const double* _
     const long long i = c.p0 + (long long)p * GA_THREADS + tid;
     const bool live = i <= c.p1;
     const size_t ii = live ? (size_t)i : (size_t)c.p1;
-    const double inv_cm_2_Hz = 100.0 * kLightC;
-    freq[p] = wn_s[ii] * inv_cm_2_Hz;
-    pref[p] = live ? (dwn_s[ii] * 2.0 * kPlanckH * inv_cm_2_Hz * kPi / (kLightC * kLightC)) * (freq[p] * freq[p] * freq[p]) : 0.0;
+    freq[p] = ecckd::wn_to_freq(wn_s[ii]);
+    pref[p] = live ? ecckd::planck_pref(dwn_s[ii], freq[p]) : 0.0;
   }
   // (1.66e9 Planck evaluations for 231 temperatures x 7.2e6 points: 2.2 ms, ~60 % of the fp64 issue rate; the < 1 ulp exp and
   // division of fastmath.hpp with the waves' sums parked in LDS - no barrier in the loop - measured 2.4 ms: left as it was)
@@ -337,10 +289,9 @@ k_erythemal_partial(const Chunk* __restrict__ chunks, const double* __restrict__
     if (wavelength_nm > 328.0 && wavelength_nm <= 400.0) ery = pow(10.0, 0.015 * (140.0 - wavelength_nm));
     ery = sqrt(ery);
     // planck_function(5777 K), planck_function.cpp:22-54
-    const double inv_cm_2_Hz = 100.0 * kLightC;
-    const double freq = wn * inv_cm_2_Hz;
-    const double pref = (dwn_s[i] * 2.0 * kPlanckH * inv_cm_2_Hz * kPi / (kLightC * kLightC)) * (freq * freq * freq);
-    const double pl = pref / (exp((6.62606896e-34 / 1.3806504e-23) * (freq / 5777.0)) - 1.0);
+    const double freq = ecckd::wn_to_freq(wn);
+    const double pref = ecckd::planck_pref(dwn_s[i], freq);
+    const double pl = pref / (exp(ecckd::kPlanckOverBoltzmann * (freq / 5777.0)) - 1.0);
     num += ery * pl;
     den += pl;
   }
@@ -588,7 +539,7 @@ int ecckd_average_to_gpoints(ecckd_gmap* m, int nlay, const double* h_pressure_h
   std::vector<int> lm(nlay, averaging_method);
   for (int l = 0; l < nlay; ++l) {
     dp[l] = h_pressure_hl[l + 1] - h_pressure_hl[l];
-    if (h_temperature_fl) hk[l] = (6.62606896e-34 / 1.3806504e-23) / h_temperature_fl[l];
+    if (h_temperature_fl) hk[l] = ecckd::kPlanckOverBoltzmann / h_temperature_fl[l];
     if (averaging_method == M_HYBRID) {
       // :101-126: logarithmic where pressure_fl > 100 hPa, transmission-3 above
       const double pfl = 0.5 * (h_pressure_hl[l] + h_pressure_hl[l + 1]);
@@ -670,7 +621,7 @@ int ecckd_planck_lut(ecckd_gmap* m, int nlut, const double* h_temperature_lut, d
   std::vector<double> hk(nlut);
   for (int i = 0; i < nlut; ++i) {
     ECCKD_REQUIRE(h_temperature_lut[i] > 0.0, "ecckd_planck_lut: temperatures must be positive");
-    hk[i] = (6.62606896e-34 / 1.3806504e-23) / h_temperature_lut[i];
+    hk[i] = ecckd::kPlanckOverBoltzmann / h_temperature_lut[i];
   }
   const size_t part_bytes = ecckd_align_up(std::max<size_t>(nchunk, 1) * nlut * sizeof(double), 256);
   const size_t out_bytes = ecckd_align_up((size_t)nlut * ng * sizeof(double), 256);

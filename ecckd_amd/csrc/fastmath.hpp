@@ -4,11 +4,10 @@
 
 namespace ecckd {
 
-// exp(y), any sign.  Cody-Waite reduction y = k ln2 + r, |r| <= ln2/2, degree-12 Taylor/Horner
-// in FMA, scaled with v_ldexp_f64.  < 1 ulp over the finite range; below -745 flushes to 0,
-// above 709 overflows to +inf like libm.
-__device__ __forceinline__ double exp_fast(double y) {
-  const double kf = __builtin_rint(y * 1.4426950408889634074);
+// What exp_fast and exp_nonpos share: the Cody-Waite reduction y = kf ln2 + r, |r| <= ln2/2, and the degree-12
+// Taylor/Horner polynomial of r in FMA.
+__device__ __forceinline__ double exp_reduced(double y, double& kf) {
+  kf = __builtin_rint(y * 1.4426950408889634074);
   double r = __builtin_fma(kf, -6.93147180369123816490e-01, y);
   r = __builtin_fma(kf, -1.90821492927058770002e-10, r);
   double p = 2.08767569878680989792e-09;                 // 1/12!
@@ -23,8 +22,24 @@ __device__ __forceinline__ double exp_fast(double y) {
   p = __builtin_fma(p, r, 1.66666666666666666667e-01);   // 1/3!
   p = __builtin_fma(p, r, 0.5);
   p = __builtin_fma(p, r, 1.0);
-  p = __builtin_fma(p, r, 1.0);
+  return __builtin_fma(p, r, 1.0);
+}
+
+// exp(y), any sign: the polynomial scaled with v_ldexp_f64.  < 1 ulp over the finite range; below -745 flushes to 0,
+// above 709 overflows to +inf like libm.
+__device__ __forceinline__ double exp_fast(double y) {
+  double kf;
+  const double p = exp_reduced(y, kf);
   const int k = (int)fmin(fmax(kf, -1100.0), 1100.0);
+  return __builtin_amdgcn_ldexp(p, k);
+}
+
+// exp(y) for y <= 0 only (emissivity: eps = 1 - exp(-D * od)): exp_fast with the exponent clamped from below alone, one
+// instruction less.  < 1 ulp on [-745, 0], below -745 flushes to 0; not for positive arguments.
+__device__ __forceinline__ double exp_nonpos(double y) {
+  double kf;
+  const double p = exp_reduced(y, kf);
+  const int k = (int)fmax(kf, -1100.0);
   return __builtin_amdgcn_ldexp(p, k);
 }
 

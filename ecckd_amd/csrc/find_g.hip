@@ -23,7 +23,7 @@
 // fixed order (bitwise reproducible; no float atomics).
 #include "common.hpp"
 #include "partition_search.hpp"
-#include "fastmath.hpp"
+#include "rt_device.hpp"
 
 #include <atomic>
 #include <cmath>
@@ -53,18 +53,11 @@ typedef float_x2 float_x2_store;
 constexpr int RT_THREADS = 256;    // K5c block
 constexpr int PREP_THREADS = 256;  // K4 block
 
-__device__ constexpr double kPlanckH = 6.62606896e-34;
-__device__ constexpr double kLightC = 2.99792458e8;
-__device__ constexpr double kPi = 3.14159265358979323846;
 __device__ constexpr double kD = ECCKD_LW_DIFFUSIVITY;
 
 // ---------------------------------------------------------------------------
-// deterministic reductions
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;  // valid in lane 0
-}
+// deterministic reductions (wave_sum: rt_device.hpp)
+using ecckd::wave_sum;
 
 // sum over a 256-thread block; result valid in thread 0.  s4 = 4 doubles of LDS.
 __device__ __forceinline__ double block_sum_256(double v, double* s4) {
@@ -123,11 +116,9 @@ k_planck_sorted(int nhl, size_t n, const int32_t* __restrict__ ireorder, const d
   if (i >= n) return;
   const size_t j = (size_t)ireorder[i];
   const double w = wn[j], dw = dwn[j];
-  const double inv_cm_2_Hz = 100.0 * kLightC;
-  const double freq = w * inv_cm_2_Hz;
-  const double pref = (dw * 2.0 * kPlanckH * inv_cm_2_Hz * kPi / (kLightC * kLightC)) * (freq * freq * freq);
-  for (int lev = 0; lev < nhl; ++lev)
-    planck_hl[(size_t)lev * n + i] = ecckd::div_fast(pref, ecckd::exp_fast(freq * hk[lev]) - 1.0);
+  const double freq = ecckd::wn_to_freq(w);
+  const double pref = ecckd::planck_pref(dw, freq);
+  for (int lev = 0; lev < nhl; ++lev) planck_hl[(size_t)lev * n + i] = ecckd::planck(pref, freq, hk[lev]);
 }
 
 __device__ __forceinline__ double metric_of(int method, double od) {
@@ -165,12 +156,11 @@ k_gas_prep_lw(int nlay, size_t n, size_t src_stride, int method,
   const double w = wn[j], dw = dwn[j];
   wn_sorted[i] = w;
   dwn_sorted[i] = dw;
-  const double inv_cm_2_Hz = 100.0 * kLightC;
-  const double freq = w * inv_cm_2_Hz;
-  const double pref = (dw * 2.0 * kPlanckH * inv_cm_2_Hz * kPi / (kLightC * kLightC)) * (freq * freq * freq);
+  const double freq = ecckd::wn_to_freq(w);
+  const double pref = ecckd::planck_pref(dw, freq);
   auto planck_at = [&](int lev) -> double {
     if (planck_reuse) return planck_reuse[(size_t)lev * n + i];
-    return ecckd::div_fast(pref, ecckd::exp_fast(freq * hk[lev]) - 1.0);
+    return ecckd::planck(pref, freq, hk[lev]);
   };
 
   double b_prev = planck_at(0);
@@ -196,10 +186,10 @@ k_gas_prep_lw(int nlay, size_t n, size_t src_stride, int method,
     const double od = odv[q];
     const double tau = bg + od;  // find_g_points.cpp:993
     // radiative_transfer_lw.cpp:41-43
-    const double eps = 1.0 - ecckd::exp_fast(-kD * tau);
-    const double fac = (eps > 1.0e-5) ? 1.0 - ecckd::div_fast(eps * (1.0 / kD), tau) : 0.5 * eps;
+    double eps, fac;
+    ecckd::lw_layer(kD, 1.0 / kD, tau, eps, fac);
     const double b_next = planck_reuse ? plv[q] : planck_at(l + 1);
-    const double dn_next = dn * (1.0 - eps) + b_prev * (eps - fac) + b_next * fac;
+    const double dn_next = ecckd::lw_step(dn, eps, fac, b_prev, b_next);
     s_col[l * bs + tid] = dn_next - dn;
     const size_t o = (size_t)l * n + i;
     bg_od[o] = bg;
@@ -221,7 +211,7 @@ k_gas_prep_lw(int nlay, size_t n, size_t src_stride, int method,
   }
   fds[i] = dn;  // flux_dn(end,__), find_g_points.cpp:1045
   // surface: emissivity 1, surf_planck = planck at temperature_hl(end) (:976-978, :987-988)
-  double up = b_prev * 1.0 + (1.0 - 1.0) * dn;
+  double up = ecckd::lw_surface(dn, b_prev);
   for (int l0 = nlay - 1; l0 >= 0; l0 -= CH) {
   double bgv[CH], odv[CH], plv[CH];
 #pragma unroll
@@ -236,10 +226,10 @@ k_gas_prep_lw(int nlay, size_t n, size_t src_stride, int method,
     const int l = l0 - q;
     if (l < 0) break;
     const double tau = bgv[q] + odv[q];
-    const double eps = 1.0 - ecckd::exp_fast(-kD * tau);
-    const double fac = (eps > 1.0e-5) ? 1.0 - ecckd::div_fast(eps * (1.0 / kD), tau) : 0.5 * eps;
+    double eps, fac;
+    ecckd::lw_layer(kD, 1.0 / kD, tau, eps, fac);
     const double b_l = planck_reuse ? plv[q] : planck_at(l);
-    const double up_l = up * (1.0 - eps) + b_prev * (eps - fac) + b_l * fac;
+    const double up_l = ecckd::lw_step(up, eps, fac, b_prev, b_l);
     // heating_rate.h:47-48
     hr[(size_t)l * n + i] = conv[l] * (s_col[l * bs + tid] - up + up_l);
     up = up_l;
@@ -324,9 +314,8 @@ k_gas_prep_lw_mirror(size_t n, int method, const int32_t* __restrict__ ireorder,
   const size_t j = (size_t)ireorder[ii];
   const double w = wn[j], dw = dwn[j];
   if (live && half == 0) { wn_sorted[i] = w; dwn_sorted[i] = dw; }
-  const double inv_cm_2_Hz = 100.0 * kLightC;
-  const double freq = w * inv_cm_2_Hz;
-  const double pref = (dw * 2.0 * kPlanckH * inv_cm_2_Hz * kPi / (kLightC * kLightC)) * (freq * freq * freq);
+  const double freq = ecckd::wn_to_freq(w);
+  const double pref = ecckd::planck_pref(dw, freq);
   const BgT* bgc = bg_col && !STAGED ? bg_col + ii * NLAY : nullptr;
   const OdT* odc = od_col + (STAGED ? 0 : ii * NLAY);
   const size_t wid = (size_t)blockIdx.x * 2 + pair;          // index of this pair's 64 points among the 64-point groups
@@ -750,33 +739,8 @@ k_fit_lw(int nlay, int method, RowMap R, const Interval* __restrict__ iv,
   const double* s = sums + (size_t)k * R.total;
   for (int l = threadIdx.x; l < nlay; l += blockDim.x) {
     const double a = s[R.A + l], b = s[R.B + l];
-    double fit;
-    switch (method) {
-      case ECCKD_AVG_LINEAR:
-        fit = a / b;
-        break;
-      case ECCKD_AVG_TRANSMISSION:  // find_g_points.cpp:64-68
-        fit = fabs(-log(1.0 - fmin(0.9999999999999999, a / b)) / kD);
-        break;
-      case ECCKD_AVG_TRANSMISSION_2:
-        fit = fabs(-log(1.0 - fmin(0.9999999999999999, a / b)) / (kD * 2.0));
-        break;
-      case ECCKD_AVG_SQUARE_ROOT: {
-        const double v = a / b;
-        fit = v * v;
-        break;
-      }
-      case ECCKD_AVG_LOGARITHMIC: {  // find_g_points.cpp:79-99
-        const double nnz = s[R.N + l];
-        const double ntot = (double)(iv[k].i2 - iv[k].i1 + 1);
-        if (nnz == ntot) fit = exp(a / b);
-        else if (nnz == 0.0) fit = 0.0;
-        else fit = exp(a / b) * (nnz / ntot);
-        break;
-      }
-      default:
-        fit = nan("");
-    }
+    const double nnz = method == ECCKD_AVG_LOGARITHMIC ? s[R.N + l] : 0.0;
+    const double fit = fit_lw_layer(method, a, b, nnz, (double)(iv[k].i2 - iv[k].i1 + 1));
     od_fit[(size_t)k * nlay + l] = fit;
   }
 }
@@ -868,47 +832,6 @@ k_rt_lw_bb(int nlay, size_t n, int nint, const Interval* __restrict__ iv,
 }
 
 
-// ---------------------------------------------------------------------------
-// fp64 helpers for the hot loops.
-//
-// exp(y) for y <= 0 (emissivity: eps = 1 - exp(-D*od)).  Cody-Waite reduction
-// y = k ln2 + r, |r| <= ln2/2, degree-12 Taylor/Horner in FMA, scaled with
-// ldexp.  Max error < 1 ulp on [-745, 0]; arguments below -745 flush to 0.
-__device__ __forceinline__ double exp_nonpos(double y) {
-  const double kf = __builtin_rint(y * 1.4426950408889634074);
-  double r = __builtin_fma(kf, -6.93147180369123816490e-01, y);
-  r = __builtin_fma(kf, -1.90821492927058770002e-10, r);
-  double p = 2.08767569878680989792e-09;            // 1/12!
-  p = __builtin_fma(p, r, 2.50521083854417187751e-08);  // 1/11!
-  p = __builtin_fma(p, r, 2.75573192239858906526e-07);  // 1/10!
-  p = __builtin_fma(p, r, 2.75573192239858906526e-06);  // 1/9!
-  p = __builtin_fma(p, r, 2.48015873015873015873e-05);  // 1/8!
-  p = __builtin_fma(p, r, 1.98412698412698412698e-04);  // 1/7!
-  p = __builtin_fma(p, r, 1.38888888888888888889e-03);  // 1/6!
-  p = __builtin_fma(p, r, 8.33333333333333333333e-03);  // 1/5!
-  p = __builtin_fma(p, r, 4.16666666666666666667e-02);  // 1/4!
-  p = __builtin_fma(p, r, 1.66666666666666666667e-01);  // 1/3!
-  p = __builtin_fma(p, r, 0.5);
-  p = __builtin_fma(p, r, 1.0);
-  p = __builtin_fma(p, r, 1.0);
-  const int k = (int)fmax(kf, -1100.0);
-  return __builtin_amdgcn_ldexp(p, k);
-}
-
-// a / b for b well inside the normal range: v_rcp_f64 seed + 2 Newton steps + 1 residual
-// correction (relative error < 1 ulp).
-__device__ __forceinline__ double fast_div(double a, double b) {
-  double y = __builtin_amdgcn_rcp(b);
-  double e = __builtin_fma(-b, y, 1.0);
-  y = __builtin_fma(y, e, y);
-  e = __builtin_fma(-b, y, 1.0);
-  y = __builtin_fma(y, e, y);
-  double q = a * y;
-  const double res = __builtin_fma(-b, q, a);
-  return __builtin_fma(res, y, q);
-}
-
-
 // Emissivity and factor of TWO layers at once with the two dependency chains interleaved in
 // the source: at 2 waves/SIMD the fp64 FMA latency is not covered by other waves, so the
 // instruction-level parallelism has to be in the stream itself (radiative_transfer_lw.cpp:114-119).
@@ -956,8 +879,8 @@ __device__ __forceinline__ void eps_fac_pair(double od0, double od1, double& eps
 // Emissivity and factor of one layer (the tail of an odd-length half column).
 __device__ __forceinline__ void eps_fac_one(double od, double& eps, double& fac) {
   constexpr double TE = 1.0e-5;
-  eps = 1.0 - exp_nonpos(-kD * od);
-  fac = fmax(1.0 - (1.0 / kD) * fast_div(fmax(eps, TE), fmax(od, TE / kD)), 0.5 * TE);
+  eps = 1.0 - ecckd::exp_nonpos(-kD * od);
+  fac = fmax(1.0 - (1.0 / kD) * ecckd::div_fast(fmax(eps, TE), fmax(od, TE / kD)), 0.5 * TE);
 }
 
 // The background optical depths of a longwave gas as FLOAT pairs: out[p][i] = (bg_od[2p][i], bg_od[2p+1][i]).  A value that
@@ -1964,48 +1887,6 @@ k_cost_sw(int nlay, int ntotal, SwTruthRows rows, const Interval* __restrict__ i
   }
 }
 
-// The errors of a batch arrive in pinned, host-coherent memory, written by the last kernel of the train.  Waiting for them
-// with hipStreamSynchronize costs a wake-up through the runtime per batch, and a search is hundreds of dependent batches
-// (equipartition.cpp:638-805: one interval per call); the host instead marks the slots as pending and watches them.
-// A pattern no result can have: the kernels end in sqrt(), whose only NaN is the canonical quiet one.
-constexpr unsigned long long kPendingBits = 0x7ff4dead5eed0001ULL;
-
-void mark_pending(double* h_slots, int count) {
-  volatile unsigned long long* s = reinterpret_cast<volatile unsigned long long*>(h_slots);
-  for (int k = 0; k < count; ++k) s[k] = kPendingBits;
-  std::atomic_thread_fence(std::memory_order_release);
-}
-
-int wait_for_slots(hipStream_t stream, const double* h_slots, int count) {
-  static const bool no_poll = std::getenv("ECCKD_NO_POLL") != nullptr;   // A/B knob: wait through the runtime
-  if (no_poll) {
-    ECCKD_HIP_CHECK(hipStreamSynchronize(stream));
-    return ECCKD_OK;
-  }
-  const volatile unsigned long long* s = reinterpret_cast<const volatile unsigned long long*>(h_slots);
-  auto all_there = [&] {
-    for (int k = 0; k < count; ++k)
-      if (s[k] == kPendingBits) return false;
-    return true;
-  };
-  for (unsigned spins = 1;; ++spins) {
-    if (all_there()) break;
-    if ((spins & 0x3fff) == 0) {
-      // now and then: has the stream drained (or died) without delivering?  An idle stream has made all its writes visible.
-      const hipError_t q = hipStreamQuery(stream);
-      if (q == hipSuccess) {
-        if (all_there()) break;
-        return ecckd::fail(ECCKD_UNEXPECTED_EXCEPTION, "interval errors were not delivered by the device");
-      }
-      if (q != hipErrorNotReady)
-        return ecckd::fail(ECCKD_UNEXPECTED_EXCEPTION, "device failure while waiting for interval errors: %s", hipGetErrorString(q));
-    }
-    if ((spins & 0x3f) == 0 && ecckd::host_oversubscribed()) std::this_thread::yield(); else _mm_pause();
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
-  return ECCKD_OK;
-}
-
 // Chunk size of an interval of `len` points: the smallest multiple of `gran` that covers it with at most `blocks` chunks.
 long long interval_chunk_pts(long long len, long long blocks, long long gran) {
   long long c = (len + blocks - 1) / blocks;
@@ -2126,9 +2007,8 @@ static int gas_layer_constants(ecckd_gas* g, const double* h_temperature_hl, dou
   const size_t nhl = nlay + 1;
   const std::vector<double>& p = g->h_pressure_hl;
   std::vector<double> lev(nhl + 2 * nlay + 1, 0.0);
-  const double hk = 6.62606896e-34 / 1.3806504e-23;
   if (h_temperature_hl)
-    for (size_t i = 0; i < nhl; ++i) lev[i] = hk / h_temperature_hl[i];
+    for (size_t i = 0; i < nhl; ++i) lev[i] = ecckd::kPlanckOverBoltzmann / h_temperature_hl[i];
   g->h_layer_weight.resize(nlay);
   // find_g_points.cpp:1093-1099
   double s = 0.0;
@@ -2438,11 +2318,8 @@ int ecckd_planck_hl_sorted_dev(ecckd_ctx* ctx, int nlay, size_t nwav, const doub
   ECCKD_REQUIRE(nlay > 0 && nwav > 0 && nwav < (size_t)0x7fffffff, "ecckd_planck_hl_sorted_dev: bad size (nlay=%d, nwav=%zu)", nlay, nwav);
   ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
   const int nhl = nlay + 1;
-  std::vector<double> hk(nhl);
-  for (int i = 0; i < nhl; ++i) {
-    ECCKD_REQUIRE(h_temperature_hl[i] > 0.0, "ecckd_planck_hl_sorted_dev: temperature_hl must be positive");
-    hk[i] = (6.62606896e-34 / 1.3806504e-23) / h_temperature_hl[i];
-  }
+  std::vector<double> hk;
+  ECCKD_CHECK(ecckd::make_hk("ecckd_planck_hl_sorted_dev", nhl, h_temperature_hl, hk));
   const size_t hk_bytes = ecckd_align_up(nhl * sizeof(double), 256), flag_bytes = 256;
   ECCKD_CHECK(ecckd::ensure_scratch(ctx, hk_bytes + flag_bytes + nwav * sizeof(int32_t)));
   double* d_hk = (double*)ctx->scratch;
@@ -2861,7 +2738,7 @@ static int eval_intervals(ecckd_gas* g, std::vector<Interval>& iv, double* error
   }
   b.h_err_dev = (double*)((char*)g->pinned_dev + L.iv_bytes);
   const int nslots = is_tt ? 2 * n : n;
-  mark_pending(h_err, nslots);
+  ecckd::slots_mark_pending(h_err, nslots);
   static const bool no_karg = std::getenv("ECCKD_NO_KARG") != nullptr;   // A/B knob: always copy the interval table
   b.use_ka = (n <= KARG_MAX && !no_karg) ? 1 : 0;
   IntervalArgs ka;
@@ -2877,7 +2754,7 @@ static int eval_intervals(ecckd_gas* g, std::vector<Interval>& iv, double* error
   ECCKD_CHECK(g->do_sw ? sweep_sw(g, b, ka, timer) : sweep_lw(g, b, ka, timer));
   ECCKD_HIP_CHECK(hipGetLastError());
   const TurnaroundLog::time_point t_last = g_turn.now();
-  ECCKD_CHECK(wait_for_slots(b.stream, h_err, nslots));
+  ECCKD_CHECK(ecckd::slots_wait(b.stream, h_err, nslots, "interval errors"));
   if (g_turn.on && !g->do_sw) g_turn.delivered(t_entry, b.t_first, t_last);
   if (is_tt)
     for (int k = 0; k < n; ++k) error[k] = 0.5 * (h_err[k] + h_err[n + k]);  // find_g_points.cpp:386

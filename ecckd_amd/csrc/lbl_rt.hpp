@@ -2,8 +2,8 @@
 // lbl_gpoint_fluxes.hip, lbl_gpoint_fluxes_sw.hip, lbl_scenarios.hip: no scattering; lbl_fluxes_sw_rayleigh.hip and
 // k_rt_sw_gpoints_rayleigh of lbl_fluxes.hip: Rayleigh scattering), and the host plumbing they share.  DESIGN.md and the
 // tests compare these kernels with each other, bit for bit where they can: one source text keeps an edit from reaching only
-// one of them.  The files are compiled with the default contraction, so an expression here keeps its form and operand order;
-// a reordered one can fuse differently and change bits.
+// one of them.  The files are compiled with the default contraction, so an expression here and in rt_device.hpp keeps its form
+// and operand order; a reordered one can fuse differently and change bits.
 //
 // Longwave: planck_function (planck_function.cpp:22-54) and radiative_transfer_lw (radiative_transfer_lw.cpp:27-60) with
 // unit surface emissivity along the slant path sec * tau:
@@ -26,11 +26,12 @@
 //   up          rayleigh_up(layer, D(top), A below, S below) -> A, S at the layer's top
 //   top         up = S, diffuse down = 0
 //   down        rayleigh_down(layer, D(top), A below, S below, diffuse down at the top) -> diffuse down, up at its base
-// The tuned kernels of find_g.hip, optimize.hip, create_lut.hip and reorder.hip keep their own SGPR-pinned variants.
+// The constants, reductions, Planck function and longwave steps live in rt_device.hpp, which the tuned kernels of find_g.hip,
+// optimize.hip, create_lut.hip and reorder.hip include too; of their own they keep only the SGPR-pinned and pairwise
+// interleaved variants (k_rt_lw_bb, eps_fac_pair), whose arithmetic differs.
 #pragma once
 
-#include "common.hpp"
-#include "fastmath.hpp"
+#include "rt_device.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -43,54 +44,11 @@ constexpr int LBL_MAX_ANGLES = 16;   // longwave zenith angles per hemisphere
 constexpr int LBL_MAX_SZA = 8;       // solar zenith angles of one call
 
 // ---------------------------------------------------------------------------------------------------------------- device
-__device__ constexpr double kPlanckH = 6.62606896e-34;
-__device__ constexpr double kLightC = 2.99792458e8;
-__device__ constexpr double kPi = 3.14159265358979323846;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;  // valid in lane 0
-}
-
-// the sum of v over the wave, added to *acc by lane 0: one writer per wave's accumulator
-__device__ __forceinline__ void wave_add(double* acc, int lane, double v) {
-  const double s = wave_sum(v);
-  if (lane == 0) *acc += s;
-}
-
-// the four waves' accumulators s[w * n + t], added in a fixed order
-__device__ __forceinline__ double add_waves(const double* s, int n, int t) {
-  return ((s[t] + s[n + t]) + s[2 * n + t]) + s[3 * n + t];
-}
-
-__device__ __forceinline__ double wn_to_freq(double wn) {
-  const double inv_cm_2_Hz = 100.0 * kLightC;
-  return wn * inv_cm_2_Hz;
-}
-
-__device__ __forceinline__ double planck_pref(double dwn, double freq) {
-  const double inv_cm_2_Hz = 100.0 * kLightC;
-  return (dwn * 2.0 * kPlanckH * inv_cm_2_Hz * kPi / (kLightC * kLightC)) * (freq * freq * freq);
-}
-
-__device__ __forceinline__ double planck(double pref, double freq, double hk_level) {
-  return div_fast(pref, exp_fast(freq * hk_level) - 1.0);
-}
-
-__device__ __forceinline__ void lw_layer(double sec, double rsec, double tau, double& eps, double& fac) {
-  eps = 1.0 - exp_fast(-sec * tau);
-  fac = (eps > 1.0e-5) ? 1.0 - div_fast(eps * rsec, tau) : 0.5 * eps;
-}
-
-__device__ __forceinline__ double lw_step(double flux, double eps, double fac, double b_prev, double b) {
-  return flux * (1.0 - eps) + b_prev * (eps - fac) + b * fac;
-}
-
-// emissivity 1: the reference's emissivity * B + (1 - emissivity) * flux, kept as it stands
-__device__ __forceinline__ double lw_surface(double flux, double b_surf) {
-  return b_surf * 1.0 + (1.0 - 1.0) * flux;
-}
+// constants, wave reductions, Planck function and longwave layer step: rt_device.hpp, shared with the tuned kernels
+using ecckd::kPlanckH; using ecckd::kLightC; using ecckd::kPi;
+using ecckd::wave_sum; using ecckd::wave_add; using ecckd::add_waves;
+using ecckd::wn_to_freq; using ecckd::planck_pref; using ecckd::planck;
+using ecckd::lw_layer; using ecckd::lw_step; using ecckd::lw_surface;
 
 // The layer terms of the Rayleigh two-stream transfer per unit direct flux D at the layer's top: diffuse reflectance R and
 // transmittance T, direct transmittance Tdir, and the parts of the direct beam that leave the layer upwards (Rdir) and
@@ -165,7 +123,7 @@ __device__ __forceinline__ void rayleigh_down(const RayleighLayer& L, double d_t
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
-constexpr double kPlanckOverBoltzmann = 6.62606896e-34 / 1.3806504e-23;
+using ecckd::kPlanckOverBoltzmann; using ecckd::make_hk;   // rt_device.hpp
 
 struct BandChunk { long long i1, i2; int band; int pad; };
 
@@ -173,16 +131,6 @@ struct Buf {
   void* p = nullptr;
   ~Buf() { if (p) (void)hipFree(p); }
 };
-
-// hk[level] = (h / k) / temperature_hl[level]
-inline int make_hk(const char* who, int nhl, const double* h_temperature_hl, std::vector<double>& hk) {
-  hk.resize(nhl);
-  for (int i = 0; i < nhl; ++i) {
-    ECCKD_REQUIRE(h_temperature_hl[i] > 0.0, "%s: temperature_hl must be positive", who);
-    hk[i] = kPlanckOverBoltzmann / h_temperature_hl[i];
-  }
-  return ECCKD_OK;
-}
 
 // one chunk per LBL_THREADS wavenumbers of a band, in wavenumber order; `who` (or NULL) prefixes the message
 inline int make_chunks(const char* who, size_t nwav, int nband, const int64_t* b0, const int64_t* b1, std::vector<BandChunk>& chunks) {

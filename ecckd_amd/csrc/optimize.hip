@@ -31,7 +31,7 @@
 // the metric is iterations per second.
 #include "common.hpp"
 #include <chrono>
-#include "fastmath.hpp"
+#include "rt_device.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -74,6 +74,8 @@ Tri ar1_inverse(int n, double rho) {
 
 __device__ __forceinline__ double block_reduce_sum(double v, double* s_red) {
   // fixed-order reduction over a block of up to 1024 threads; result valid in every thread
+  // wave_sum (rt_device.hpp) written out, here and in k_opt_gradient_finish and k_opt_sum_cost: with the call the compiler
+  // orders the instructions of these kernels differently, and their code stays what was measured
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1096,11 +1098,7 @@ constexpr int VEC_THREADS = 1024;  // ONE element per thread at nx ~ 3e5: every 
 constexpr int VEC_WAVES = VEC_THREADS / 64;
 constexpr int FIN_THREADS = 256;   // k_lb_finish
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
+using ecckd::wave_sum;   // rt_device.hpp
 
 // the nblk (<= 512) partials of one reduction, summed by every caller in the same order (blockDim >= 256)
 __device__ __forceinline__ double sum_partials(const double* __restrict__ part, int nblk, double* s_tmp /*[4]*/) {
@@ -1117,36 +1115,23 @@ __device__ __forceinline__ double sum_partials(const double* __restrict__ part, 
   return ((s_tmp[0] + s_tmp[1]) + s_tmp[2]) + s_tmp[3];
 }
 
-// NACC per-thread accumulators -> one partial per (accumulator, block).  Within a wave the NACC sums are taken TOGETHER: at the
-// exchange over lane distance 32 a lane passes on one half of its values and adds what it receives to the half it keeps, at
-// distance 16 a half of those, ... - NACC + NACC/2 + ... exchanges in all instead of 6 per value (every exchange is an LDS
-// crossbar operation that all the waves of a CU queue for: the plain form cost the update kernel more than its memory traffic).
-// Lane l ends up with the wave's sum of accumulator bitreverse6(l).  Same tree for every value, fixed: bitwise reproducible.
-template <int USED>
-__device__ __forceinline__ void fold_level(double* v, bool upper, int mask) {
-  constexpr int NEXT = (USED + 1) / 2;
-#pragma unroll
-  for (int i = 0; i < NEXT; ++i) {
-    const double a = v[2 * i];
-    const double b = (2 * i + 1 < USED) ? v[2 * i + 1] : 0.0;
-    const double send = upper ? a : b;
-    double keep = upper ? b : a;
-    keep += __shfl_xor(send, mask, 64);
-    v[i] = keep;
-  }
-}
-
+// NACC per-thread accumulators -> one partial per (accumulator, block).  Within a wave the NACC sums are taken TOGETHER
+// (fold_wave, rt_device.hpp: the plain form, six exchanges per value, cost the update kernel more than its memory traffic);
+// lane l ends up with the wave's sum of accumulator bitreverse6(l).
 template <int NACC>
 __device__ __forceinline__ void write_partials(double (&acc)[NACC], int nused, double* __restrict__ part, double* s_all /*[NACC][VEC_WAVES]*/) {
   static_assert(NACC <= 64, "one value per lane at the end");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // the levels of fold_wave (rt_device.hpp) written out: through fold_wave itself the compiler orders k_lb_update and
+  // k_lb_direction differently, and their code stays what was measured
   constexpr int U1 = (NACC + 1) / 2, U2 = (U1 + 1) / 2, U3 = (U2 + 1) / 2, U4 = (U3 + 1) / 2, U5 = (U4 + 1) / 2;
-  fold_level<NACC>(acc, (lane & 32) != 0, 32);
-  fold_level<U1>(acc, (lane & 16) != 0, 16);
-  fold_level<U2>(acc, (lane & 8) != 0, 8);
-  fold_level<U3>(acc, (lane & 4) != 0, 4);
-  fold_level<U4>(acc, (lane & 2) != 0, 2);
-  fold_level<U5>(acc, (lane & 1) != 0, 1);
+  auto add = [](double a, double b) { return a + b; };
+  ecckd::fold_level<NACC, true>(acc, (lane & 32) != 0, 32, add);
+  ecckd::fold_level<U1, true>(acc, (lane & 16) != 0, 16, add);
+  ecckd::fold_level<U2, true>(acc, (lane & 8) != 0, 8, add);
+  ecckd::fold_level<U3, true>(acc, (lane & 4) != 0, 4, add);
+  ecckd::fold_level<U4, true>(acc, (lane & 2) != 0, 2, add);
+  ecckd::fold_level<U5, true>(acc, (lane & 1) != 0, 1, add);
   const int kk = (int)(__brev((unsigned)lane) >> 26);           // the accumulator this lane now holds
   if (kk < NACC) s_all[kk * VEC_WAVES + wave] = acc[0];
   __syncthreads();
@@ -2013,47 +1998,9 @@ int ecckd_opt_initial_state(ecckd_opt* o, double* h_x, double* h_x_min, double* 
 
 // CkdOptimizable::calc_cost_function_gradient (solve_adept.cpp:240-292).
 // cost and gradient at the DEVICE state d_x -> d_grad; J on the host (one stream sync).
-// Results the host needs at once (the cost of a trial point, the dot products of the L-BFGS update) arrive in pinned,
-// host-coherent slots written by the last kernel that produces them; the host marks the slots as pending and watches them
-// instead of queueing a copy and synchronising the stream - two waits per iteration, each a PCIe write away from the kernel's
-// end (the same scheme as the interval errors of find_g.hip).  kOptPending: a NaN payload no arithmetic produces.
-constexpr unsigned long long kOptPending = 0x7ff4dead0b5e55edULL;
-
-static void opt_mark_pending(double* h_slots, int count) {
-  volatile unsigned long long* s = reinterpret_cast<volatile unsigned long long*>(h_slots);
-  for (int k = 0; k < count; ++k) s[k] = kOptPending;
-  std::atomic_thread_fence(std::memory_order_release);
-}
-
-static int opt_wait_slots(ecckd_ctx* ctx, const double* h_slots, int count) {
-  static const bool no_poll = std::getenv("ECCKD_NO_POLL") != nullptr;   // A/B knob: wait through the runtime
-  const volatile unsigned long long* s = reinterpret_cast<const volatile unsigned long long*>(h_slots);
-  auto all_there = [&] {
-    for (int k = 0; k < count; ++k)
-      if (s[k] == kOptPending) return false;
-    return true;
-  };
-  if (no_poll) {
-    ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return all_there() ? ECCKD_OK : ecckd::fail(ECCKD_UNEXPECTED_EXCEPTION, "ecckd_opt: results were not delivered by the device");
-  }
-  for (unsigned spins = 1;; ++spins) {
-    if (all_there()) break;
-    if ((spins & 0x3fff) == 0) {
-      const hipError_t q = hipStreamQuery(ctx->stream);       // drained (or dead) without delivering?
-      if (q == hipSuccess) {
-        if (all_there()) break;
-        return ecckd::fail(ECCKD_UNEXPECTED_EXCEPTION, "ecckd_opt: results were not delivered by the device");
-      }
-      if (q != hipErrorNotReady)
-        return ecckd::fail(ECCKD_UNEXPECTED_EXCEPTION, "ecckd_opt: device failure while waiting for results: %s", hipGetErrorString(q));
-    }
-    _mm_pause();
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
-  return ECCKD_OK;
-}
-
+// Results the host needs at once (the cost of a trial point, the dot products of the L-BFGS update) arrive in pinned slots
+// that the host watches (slots_mark_pending / slots_wait, common.hpp): two waits per iteration, each a PCIe write away from
+// the kernel's end.
 static int opt_launch_forward(ecckd_opt* o) {
   ecckd_ctx* ctx = o->ctx;
   const int nlay = o->nlay, nhl = nlay + 1, ng = o->ng, nband = o->nband;
@@ -2153,11 +2100,11 @@ static int opt_cost_grad_dev(ecckd_opt* o, const double* d_x, double* d_grad, do
   // the cost: profiles, then the prior's node terms, summed on the device in a fixed order and delivered to the host's slot
   // (and, for the profile-sharded all-reduce, into the slot behind the gradient: ONE collective of nx + 1 doubles)
   double* h_cost = o->h_pin + 70;
-  opt_mark_pending(h_cost, 1);
+  ecckd::slots_mark_pending(h_cost, 1);
   hipLaunchKernelGGL(k_opt_sum_cost, dim3(1), dim3(256), 0, ctx->stream, o->d_jcol, o->ncol, o->d_jb, o->nnode_active * (size_t)o->grad_nchunk, prior ? 1 : 0,
                      o->d_pin + 70, reduce ? d_grad + o->nx : nullptr);
   ECCKD_HIP_CHECK(hipGetLastError());
-  ECCKD_CHECK(opt_wait_slots(ctx, h_cost, 1));
+  ECCKD_CHECK(ecckd::slots_wait(ctx->stream, h_cost, 1, "ecckd_opt: results"));
   if (timed) {
     // "radiative transfer": look-up, penalty, two sweeps, cost and their adjoint; "a-priori": the gradient kernel, which
     // gathers the adjoint back onto the coefficients and adds the prior term (the reference times the prior alone there)
@@ -2315,7 +2262,7 @@ int ecckd_opt_minimize(ecckd_opt* o, int max_iterations, double convergence_crit
     LbSlots none;
     none.n = 0;
     for (int a = 0; a < M; ++a) none.slot[a] = 0;
-    opt_mark_pending(h_rb, NPART);
+    ecckd::slots_mark_pending(h_rb, NPART);
     hipLaunchKernelGGL(k_lb_update, vb, vt, 0, ctx->stream, n, none, -1, x, x, g, g, bmin, bmax, o->d_q, o->d_S, o->d_Y, part_a);
     hipLaunchKernelGGL(k_lb_finish, dim3(NPART), dim3(FIN_THREADS), 0, ctx->stream, part_a, nblk, sc);
     ECCKD_HIP_CHECK(hipGetLastError());
@@ -2323,7 +2270,7 @@ int ecckd_opt_minimize(ecckd_opt* o, int max_iterations, double convergence_crit
   for (it = 0; it <= max_iterations; ++it) {
     // |q|^2, S^T q, Y^T q at the current point (the pending pair included, as the newest) and the pending pair's own dots:
     // launched at the end of the previous iteration (k_lb_update), awaited here
-    ECCKD_CHECK(opt_wait_slots(ctx, h_rb, NPART));
+    ECCKD_CHECK(ecckd::slots_wait(ctx->stream, h_rb, NPART, "ecckd_opt: results"));
     int npairs = hist;           // pairs that enter this direction
     if (pending) {
       const double* rp = h_rb + 1 + 2 * M;   // s.y, y.y, s.Y_a, S_a.y, y.Y_a for a < hist
@@ -2385,12 +2332,12 @@ int ecckd_opt_minimize(ecckd_opt* o, int max_iterations, double convergence_crit
       }
       hipLaunchKernelGGL(k_lb_direction, vb, vt, 0, ctx->stream, n, sd, cf, o->d_q, o->d_S, o->d_Y, g, o->d_dir, part_dg);
       // the trial point (and its coefficients) with the step chosen on the device, then the cost there; one wait for both
-      opt_mark_pending(h_step, 3);
+      ecckd::slots_mark_pending(h_step, 3);
       hipLaunchKernelGGL(k_lb_step, vb, vt, 0, ctx->stream, n, -1.0, npairs == 0 ? 1 : 0, max_step, 1.0, part_dg,
                          part_dd, x, o->d_dir, bmin, bmax, xn, o->d_k, sc_step);
       ECCKD_HIP_CHECK(hipGetLastError());
       ECCKD_CHECK(opt_cost_grad_dev(o, xn, gn, &Jn, true));
-      ECCKD_CHECK(opt_wait_slots(ctx, h_step, 3));
+      ECCKD_CHECK(ecckd::slots_wait(ctx->stream, h_step, 3, "ecckd_opt: results"));
       step = h_step[0];
       dg = h_step[2];
       if (!(dg < 0.0)) {
@@ -2442,7 +2389,7 @@ int ecckd_opt_minimize(ecckd_opt* o, int max_iterations, double convergence_crit
     LbSlots sp;
     sp.n = hist;
     for (int a = 0; a < M; ++a) sp.slot[a] = a < hist ? ord[a] : 0;
-    opt_mark_pending(h_rb, NPART);
+    ecckd::slots_mark_pending(h_rb, NPART);
     hipLaunchKernelGGL(k_lb_update, vb, vt, 0, ctx->stream, n, sp, pend_slot, x, xn, g, gn, bmin, bmax, o->d_q, o->d_S, o->d_Y, part_a);
     hipLaunchKernelGGL(k_lb_finish, dim3(NPART), dim3(FIN_THREADS), 0, ctx->stream, part_a, nblk, sc);
     ECCKD_HIP_CHECK(hipGetLastError());

@@ -17,7 +17,7 @@
 // the per-layer net-flux increments of the down sweep in LDS, so HBM traffic
 // is the algorithmic minimum: nlay*sizeof(od) + 16 B read, 16 B written.
 #include "common.hpp"
-#include "fastmath.hpp"
+#include "rt_device.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -38,11 +38,6 @@ struct LevelLayout {
   __host__ __device__ int phhl() const { return 4 * nlay + 1; }
   __host__ __device__ int total() const { return 5 * nlay + 2; }
 };
-
-// planck_function.cpp:29-33
-__device__ constexpr double kPlanckH = 6.62606896e-34;
-__device__ constexpr double kLightC = 2.99792458e8;
-__device__ constexpr double kPi = 3.14159265358979323846;
 
 // K1.  LW sorting key.  Dynamic LDS: double[nlay][blockDim.x] holding the
 // down-sweep flux increments dn[l+1]-dn[l], then the clamped heating rates.
@@ -65,13 +60,11 @@ k_reorder_key_lw(int nlay, size_t nwav, size_t od_stride, const double* __restri
   const double* phhl = lev + L.phhl();
 
   // planck_function.cpp:48-50, same operation order
-  const double inv_cm_2_Hz = 100.0 * kLightC;
-  const double freq = wn[j] * inv_cm_2_Hz;
-  const double pref = (dwn[j] * 2.0 * kPlanckH * inv_cm_2_Hz * kPi / (kLightC * kLightC)) *
-                      (freq * freq * freq);
+  const double freq = ecckd::wn_to_freq(wn[j]);
+  const double pref = ecckd::planck_pref(dwn[j], freq);
 
   // ---- down sweep (radiative_transfer_lw.cpp:45-50) ----
-  double b_prev = ecckd::div_fast(pref, ecckd::exp_fast(freq * hk[0]) - 1.0);
+  double b_prev = ecckd::planck(pref, freq, hk[0]);
   double dn = 0.0;
   double col = 0.0;
   double thr_height = 0.0;
@@ -79,11 +72,10 @@ k_reorder_key_lw(int nlay, size_t nwav, size_t od_stride, const double* __restri
   const OdT* odp = od + j;
   for (int l = 0; l < nlay; ++l) {
     const double tau = (double)odp[(size_t)l * od_stride];
-    const double eps = 1.0 - ecckd::exp_fast(-ECCKD_LW_DIFFUSIVITY * tau);
-    // :42-43  factor = eps > 1e-5 ? 1 - eps*(1/D)/tau : 0.5*eps
-    const double fac = (eps > 1.0e-5) ? 1.0 - ecckd::div_fast(eps * (1.0 / ECCKD_LW_DIFFUSIVITY), tau) : 0.5 * eps;
-    const double b_next = ecckd::div_fast(pref, ecckd::exp_fast(freq * hk[l + 1]) - 1.0);
-    const double dn_next = dn * (1.0 - eps) + b_prev * (eps - fac) + b_next * fac;
+    double eps, fac;   // :41-43
+    ecckd::lw_layer(ECCKD_LW_DIFFUSIVITY, 1.0 / ECCKD_LW_DIFFUSIVITY, tau, eps, fac);
+    const double b_next = ecckd::planck(pref, freq, hk[l + 1]);
+    const double dn_next = ecckd::lw_step(dn, eps, fac, b_prev, b_next);
     s_col[l * bs + tid] = dn_next - dn;
     // reorder_spectrum.cpp:199-222 (threshold height; in LW only its throw is observable)
     const double next_col = col + tau;
@@ -100,13 +92,13 @@ k_reorder_key_lw(int nlay, size_t nwav, size_t od_stride, const double* __restri
   // ---- surface (:52-53, emissivity 1) and up sweep (:55-59) ----
   // surf_planck is planck at temperature_hl(end) (reorder_spectrum.cpp:130-131)
   // = b_prev; with surf_emissivity = 1 the reflected term is 0*dn.
-  double up = b_prev * 1.0 + (1.0 - 1.0) * dn;
+  double up = ecckd::lw_surface(dn, b_prev);
   for (int l = nlay - 1; l >= 0; --l) {
     const double tau = (double)odp[(size_t)l * od_stride];
-    const double eps = 1.0 - ecckd::exp_fast(-ECCKD_LW_DIFFUSIVITY * tau);
-    const double fac = (eps > 1.0e-5) ? 1.0 - ecckd::div_fast(eps * (1.0 / ECCKD_LW_DIFFUSIVITY), tau) : 0.5 * eps;
-    const double b_l = ecckd::div_fast(pref, ecckd::exp_fast(freq * hk[l]) - 1.0);
-    const double up_l = up * (1.0 - eps) + b_prev * (eps - fac) + b_l * fac;
+    double eps, fac;
+    ecckd::lw_layer(ECCKD_LW_DIFFUSIVITY, 1.0 / ECCKD_LW_DIFFUSIVITY, tau, eps, fac);
+    const double b_l = ecckd::planck(pref, freq, hk[l]);
+    const double up_l = ecckd::lw_step(up, eps, fac, b_prev, b_l);
     // heating_rate.h:47-48: conv * (dn[l+1]-dn[l]-up[l+1]+up[l]), left to right
     double hr = conv[l] * (s_col[l * bs + tid] - up + up_l);
     // reorder_spectrum.cpp:175: only cooling
@@ -148,10 +140,8 @@ k_reorder_key_lw_fast(size_t nwav, size_t od_stride, const double* __restrict__ 
   const double* dh = lev + L.dh();
   const double* dhph = lev + L.dhph();
   const double* phhl = lev + L.phhl();
-  const double inv_cm_2_Hz = 100.0 * kLightC;
-  const double freq = wn[j] * inv_cm_2_Hz;
-  const double pref = (dwn[j] * 2.0 * kPlanckH * inv_cm_2_Hz * kPi / (kLightC * kLightC)) *
-                      (freq * freq * freq);
+  const double freq = ecckd::wn_to_freq(wn[j]);
+  const double pref = ecckd::planck_pref(dwn[j], freq);
   const ecckd::ExpConsts ek = ecckd::exp_consts();
   const double neg_d = ecckd::sgpr_pin(-ECCKD_LW_DIFFUSIVITY), inv_d = ecckd::sgpr_pin(1.0 / ECCKD_LW_DIFFUSIVITY);
   const double thin = ecckd::sgpr_pin(1.0e-5);
@@ -190,7 +180,7 @@ k_reorder_key_lw_fast(size_t nwav, size_t od_stride, const double* __restrict__ 
     b_prev = b_next;
   }
   if (col > thr && thr_height > 30.0) atomicOr(err_flag, 1);
-  double up = b_prev * 1.0 + (1.0 - 1.0) * dn;
+  double up = ecckd::lw_surface(dn, b_prev);
 #pragma unroll
   for (int l = NLAY - 1; l >= 0; --l) {
     const double up_l = up * (1.0 - ee[l]) + ss[l];
@@ -252,9 +242,8 @@ int upload_level_consts(ecckd_ctx* ctx, int nlay, const double* p_hl, const doub
   const LevelLayout L{nlay};
   const int n = L.total();
   std::vector<double> h(n, 0.0);
-  const double hk = 6.62606896e-34 / 1.3806504e-23;  // h/k, planck_function.cpp:29-31
   for (int i = 0; i <= nlay; ++i) {
-    h[L.hk() + i] = t_hl ? hk / t_hl[i] : 0.0;
+    h[L.hk() + i] = t_hl ? ecckd::kPlanckOverBoltzmann / t_hl[i] : 0.0;
     h[L.phhl() + i] = std::log(p_hl[nlay]) - std::log(p_hl[i]);  // reorder_spectrum.cpp:196
   }
   for (int l = 0; l < nlay; ++l) {

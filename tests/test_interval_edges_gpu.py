@@ -465,7 +465,8 @@ def test_fits_match_exact_sums_of_the_resident_rows(gases, nlay, method):
     """a. ecckd_fit_optical_depth of every listed interval against the gas's own rows summed exactly: what is left is the
     re-association of the sum hierarchy and one log.  That entry point launches the unfused pair k_interval_sums + k_fit_lw
     (always with a copied interval table); the fused k_interval_sums_fit_lw of the error path calls the same
-    interval_row_acc and is pinned by the error tests.  Largest observed multiples of the derived bound on an MI355X:
+    interval_row_acc and the same fit_lw_layer - the fit arithmetic is one function for both - and is pinned by the error
+    tests.  Largest observed multiples of the derived bound on an MI355X:
     0.500 for the transmission methods (thin layers: half an ulp of 1 - a / b; 0.055 where a / b >= 0.1), 0.033 square-root,
     0.057 linear ("Interval edges")."""
     gas = gases.lw(nlay, method)
