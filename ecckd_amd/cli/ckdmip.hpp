@@ -263,459 +263,446 @@ void bands_to_file_order(int nband, size_t nhl, const double* b, double* t /* [n
     }
 }
 
-}  // namespace
+// [nrow][ng] fluxes -> the sum over the g points of every row, g ascending
+std::vector<double> sum_over_g_points(const std::vector<double>& f, size_t nrow, int ng) {
+  std::vector<double> sum(nrow, 0.0);
+  for (size_t r = 0; r < nrow; ++r)
+    for (int g = 0; g < ng; ++g) sum[r] += f[r * ng + g];
+  return sum;
+}
 
-inline int ckdmip_main(int argc, char** argv, bool sw) {
-  try {
-    std::vector<GasArg> gases;
-    std::string config_file, scenario, output, ckd_file, ssi_file, scenarios_file, rayleigh_file;
-    bool merge_only = false, per_file_scaling = false, rayleigh_scattering = false;
-    long col_a = -1, col_b = -1;
-    GasArg pending;
-    for (int i = 1; i < argc; ++i) {
-      const std::string a = argv[i];
-      auto need = [&](int n) { if (i + n >= argc) fail(ECCKD_PARAMETER_ERROR, "%s needs %d argument(s)", a.c_str(), n); };
-      if (a == "--config") { need(1); config_file = argv[++i]; }
-      else if (a == "--scenario") { need(1); scenario = argv[++i]; }
-      else if (a == "--output") { need(1); output = argv[++i]; }
-      else if (a == "--ckd") { need(1); ckd_file = argv[++i]; }
-      else if (a == "--ssi") { need(1); ssi_file = argv[++i]; }
-      else if (a == "--merge-only") merge_only = true;
-      else if (a == "--scenarios") { need(1); scenarios_file = argv[++i]; }
-      else if (a == "--rayleigh") { need(1); rayleigh_file = argv[++i]; }
-      else if (a == "--rayleigh-scattering") rayleigh_scattering = true;
-      else if (a == "--column-range") { need(2); col_a = std::atol(argv[++i]); col_b = std::atol(argv[++i]); }
-      else if (a == "--scale") { need(1); pending.mode = GasArg::SCALE; pending.value = std::atof(argv[++i]); per_file_scaling = true; }
-      else if (a == "--conc") { need(1); pending.mode = GasArg::CONC; pending.value = std::atof(argv[++i]); per_file_scaling = true; }
-      else if (a == "--const") { need(1); pending.mode = GasArg::CONST; pending.value = std::atof(argv[++i]); per_file_scaling = true; }
-      else if (a.rfind("--", 0) == 0) fail(ECCKD_PARAMETER_ERROR, "Argument \"%s\" not understood", a.c_str());
-      else { pending.path = a; gases.push_back(pending); pending = GasArg(); }
+// The command line, checked as far as it can be without a file of spectra or a device
+struct Args {
+  bool sw = false;
+  std::vector<GasArg> gases;
+  std::string config_file, scenario, output, ckd_file, ssi_file, scenarios_file, rayleigh_file, history;
+  bool merge_only = false, per_file_scaling = false, rayleigh_scattering = false;
+  long col_a = -1, col_b = -1;
+  std::vector<ScenarioRow> table;              // --scenarios
+  Namelist nl;
+};
+
+Args parse_args(int argc, char** argv, bool sw) {
+  Args p;
+  p.sw = sw;
+  GasArg pending;
+  for (int i = 1; i < argc; ++i) {
+    const std::string a = argv[i];
+    auto need = [&](int n) { if (i + n >= argc) fail(ECCKD_PARAMETER_ERROR, "%s needs %d argument(s)", a.c_str(), n); };
+    auto scaling = [&](int mode) { need(1); pending.mode = (decltype(pending.mode))mode; pending.value = std::atof(argv[++i]); p.per_file_scaling = true; };
+    if (a == "--config") { need(1); p.config_file = argv[++i]; }
+    else if (a == "--scenario") { need(1); p.scenario = argv[++i]; }
+    else if (a == "--output") { need(1); p.output = argv[++i]; }
+    else if (a == "--ckd") { need(1); p.ckd_file = argv[++i]; }
+    else if (a == "--ssi") { need(1); p.ssi_file = argv[++i]; }
+    else if (a == "--merge-only") p.merge_only = true;
+    else if (a == "--scenarios") { need(1); p.scenarios_file = argv[++i]; }
+    else if (a == "--rayleigh") { need(1); p.rayleigh_file = argv[++i]; }
+    else if (a == "--rayleigh-scattering") p.rayleigh_scattering = true;
+    else if (a == "--column-range") { need(2); p.col_a = std::atol(argv[++i]); p.col_b = std::atol(argv[++i]); }
+    else if (a == "--scale") scaling(GasArg::SCALE);
+    else if (a == "--conc") scaling(GasArg::CONC);
+    else if (a == "--const") scaling(GasArg::CONST);
+    else if (a.rfind("--", 0) == 0) fail(ECCKD_PARAMETER_ERROR, "Argument \"%s\" not understood", a.c_str());
+    else { pending.path = a; p.gases.push_back(pending); pending = GasArg(); }
+  }
+  if (!p.rayleigh_file.empty() || p.rayleigh_scattering) {     // scattering is opt-in, shortwave only, one column set per call
+    const char* sw_switch = !p.rayleigh_file.empty() ? "--rayleigh" : "--rayleigh-scattering";
+    const char* with = !sw ? "the longwave tool" : p.merge_only ? "--merge-only" : !p.scenarios_file.empty() ? "--scenarios" : nullptr;
+    if (with) fail(ECCKD_PARAMETER_ERROR, "\"%s\" cannot be combined with %s", sw_switch, with);
+    if (!p.rayleigh_file.empty() && !p.ckd_file.empty())
+      fail(ECCKD_PARAMETER_ERROR, "\"--rayleigh\" names a spectrum file of the default mode; with --ckd use --rayleigh-scattering");
+    if (p.rayleigh_scattering && p.ckd_file.empty())
+      fail(ECCKD_PARAMETER_ERROR, "\"--rayleigh-scattering\" needs --ckd; in the default mode name the spectrum with --rayleigh");
+  }
+  if (!p.scenarios_file.empty()) {             // every check of the table before a device is opened
+    const char* with = p.merge_only ? "--merge-only" : !p.ckd_file.empty() ? "--ckd" : !p.output.empty() ? "--output" : !p.scenario.empty() ? "--scenario"
+                       : p.per_file_scaling ? "a per-file --scale, --conc or --const" : nullptr;
+    if (with) fail(ECCKD_PARAMETER_ERROR, "\"--scenarios\" cannot be combined with %s (names, outputs and scalings come from the table)", with);
+    if (p.gases.empty()) fail(ECCKD_PARAMETER_ERROR, "No spectrum files given");
+    p.table = read_scenarios(p.scenarios_file, p.gases.size());
+  } else if (p.output.empty()) fail(ECCKD_PARAMETER_ERROR, "\"--output\" file not specified");
+  if (!p.config_file.empty()) p.nl = read_namelist(p.config_file);
+  if (p.nl.nspectralstride != 1) fail(ECCKD_PARAMETER_ERROR, "nspectralstride = %d is not supported (1 only)", p.nl.nspectralstride);
+  if (p.nl.nangle < 0 || p.nl.nangle > 16) fail(ECCKD_PARAMETER_ERROR, "nangle = %d outside 0..16", p.nl.nangle);
+  if (sw && p.nl.nangle != 0) WARN("nangle = %d has no meaning for the direct solar beam: ignored", p.nl.nangle);
+  p.history = history_line(argc, argv);
+  return p;
+}
+
+// ---- --ckd: radiative transfer on a CKD model's optical depths (test/run_ckd_lw.sh:133-137, test/run_ckd_sw.sh:125-128) ----
+// The output's header: per column (shortwave: and angle) and half level the fluxes, broadband and per g point
+void define_ckd_output(NcOut& out, const Args& a, int ncol, int nmu, int nlay, int ng) {
+  const bool sw = a.sw, scattering = a.rayleigh_scattering;
+  const std::string x = sw ? "_sw" : "_lw", X = sw ? " shortwave flux" : " longwave flux";
+  out.dim("column", ncol);
+  if (sw) out.dim("mu0", nmu);
+  out.dim("half_level", nlay + 1); out.dim("g_point", ng);
+  std::vector<std::string> hl = {"column", "half_level"};
+  if (sw) hl.insert(hl.begin() + 1, "mu0");
+  std::vector<std::string> hl_g = hl;
+  hl_g.push_back("g_point");
+  auto flux = [&](const std::string& name, const std::vector<std::string>& dims, const std::string& long_name) {
+    out.var(name + x, NC_FLOAT_T, dims, long_name.c_str(), "W m-2");
+  };
+  out.var("pressure_hl", NC_FLOAT_T, {"column", "half_level"}, "Pressure at half levels", "Pa");
+  if (sw) out.var("mu0", NC_FLOAT_T, {"mu0"}, "Cosine of solar zenith angle", "1");
+  flux("flux_up", hl, "Upwelling" + X);
+  flux("flux_dn", hl, "Downwelling" + X);
+  if (sw) flux("flux_dn_direct", hl, "Downwelling direct" + X);
+  flux("spectral_flux_up", hl_g, "Upwelling" + X + " per g point");
+  if (sw) flux("spectral_flux_dn_direct", hl_g, "Downwelling direct" + X + " per g point");
+  if (!sw || scattering) flux("spectral_flux_dn", hl_g, "Downwelling" + X + " per g point");
+  if (!a.scenario.empty()) out.att(a.scenario, "scenario");
+  out.att(a.history, "history");
+  if (scattering) out.att("two-stream", "rayleigh_scattering");
+  out.end_define();
+}
+
+// Fluxes [row][half_level][g_point], a row per angle (longwave: one row).  Shortwave: flux 0 is the direct beam, which is the
+// whole downwelling flux too unless the Rayleigh optical depth scatters; the last flux is the upwelling one.
+int mode_ckd(const Args& a) {
+  const bool sw = a.sw, scattering = a.rayleigh_scattering;
+  const Namelist& nl = a.nl;
+  Device dev;
+  NcIn f(a.ckd_file);
+  const std::vector<size_t> sh = f.shape("optical_depth");
+  if (sh.size() != 3) fail(ECCKD_PARAMETER_ERROR, "optical_depth in %s is not (column, level, g_point)", a.ckd_file.c_str());
+  const int ncol = (int)sh[0], nlay = (int)sh[1], ng = (int)sh[2];
+  std::vector<double> mu0 = nl.mu0;
+  bool have_ray = false;
+  if (sw) {
+    if (!f.exist("incoming_sw")) fail(ECCKD_PARAMETER_ERROR, "%s holds no incoming_sw: not a shortwave optical-depth file", a.ckd_file.c_str());
+    if (mu0.empty()) mu0 = {0.5};
+    have_ray = f.exist("rayleigh_optical_depth");
+    if (scattering && !have_ray)
+      fail(ECCKD_PARAMETER_ERROR, "\"--rayleigh-scattering\": %s holds no rayleigh_optical_depth", a.ckd_file.c_str());
+  } else if (!f.exist("planck_hl")) {
+    fail(ECCKD_PARAMETER_ERROR, "%s holds no planck_hl: not a longwave optical-depth file", a.ckd_file.c_str());
+  }
+  const int nrow = sw ? (int)mu0.size() : 1, nflux = scattering ? 3 : 2, dn = scattering ? 1 : 0, up = nflux - 1;
+  NcOut out(a.output);
+  define_ckd_output(out, a, ncol, nrow, nlay, ng);
+  if (sw) out.write("mu0", mu0);
+  const size_t nhg = (size_t)(nlay + 1) * ng;
+  const std::string x = sw ? "_sw" : "_lw";
+  for (int c = 0; c < ncol; ++c) {
+    std::vector<double> od = f.read("optical_depth", c), ray, flux[3];
+    for (int k = 0; k < nflux; ++k) flux[k].resize(nrow * nhg);
+    if (have_ray) ray = f.read("rayleigh_optical_depth", c);
+    if (have_ray && !scattering)                // one more absorber, as in the reference's forward model (solve_adept.cpp:34)
+      for (size_t i = 0; i < od.size(); ++i) od[i] += ray[i];
+    const std::vector<double> source = f.read(sw ? "incoming_sw" : "planck_hl", c);
+    for (int m = 0; m < nrow; ++m) {            // per g point, on the device
+      if (scattering)                           // two-stream
+        ck(ecckd_rt_sw_gpoints_rayleigh(dev.ctx(), 1, nlay, ng, mu0[m], nl.surf_albedo, source.data(), od.data(), ray.data(), &flux[0][m * nhg],
+                                        &flux[1][m * nhg], &flux[2][m * nhg]));
+      else if (sw)                              // radiative_transfer_sw.cpp:45-77
+        ck(ecckd_rt_sw_gpoints(dev.ctx(), 1, nlay, ng, mu0[m], nl.surf_albedo, source.data(), od.data(), &flux[0][m * nhg], &flux[1][m * nhg]));
+      else                                      // radiative_transfer_lw.cpp:27-60 (two-stream or nangle Gauss-Legendre angles)
+        ck(ecckd_rt_lw_gpoints(dev.ctx(), nl.nangle, 1, nlay, ng, source.data(), od.data(), flux[0].data(), flux[1].data()));
     }
-    if (!rayleigh_file.empty() || rayleigh_scattering) {     // scattering is opt-in, shortwave only, one column set per call
-      const char* sw_switch = !rayleigh_file.empty() ? "--rayleigh" : "--rayleigh-scattering";
-      const char* with = !sw ? "the longwave tool" : merge_only ? "--merge-only" : !scenarios_file.empty() ? "--scenarios" : nullptr;
-      if (with) fail(ECCKD_PARAMETER_ERROR, "\"%s\" cannot be combined with %s", sw_switch, with);
-      if (!rayleigh_file.empty() && !ckd_file.empty())
-        fail(ECCKD_PARAMETER_ERROR, "\"--rayleigh\" names a spectrum file of the default mode; with --ckd use --rayleigh-scattering");
-      if (rayleigh_scattering && ckd_file.empty())
-        fail(ECCKD_PARAMETER_ERROR, "\"--rayleigh-scattering\" needs --ckd; in the default mode name the spectrum with --rayleigh");
-    }
-    std::vector<ScenarioRow> table;              // --scenarios: every check of the table before a device is opened
-    if (!scenarios_file.empty()) {
-      const char* with = merge_only ? "--merge-only" : !ckd_file.empty() ? "--ckd" : !output.empty() ? "--output" : !scenario.empty() ? "--scenario"
-                         : per_file_scaling ? "a per-file --scale, --conc or --const" : nullptr;
-      if (with) fail(ECCKD_PARAMETER_ERROR, "\"--scenarios\" cannot be combined with %s (names, outputs and scalings come from the table)", with);
-      if (gases.empty()) fail(ECCKD_PARAMETER_ERROR, "No spectrum files given");
-      table = read_scenarios(scenarios_file, gases.size());
-    } else if (output.empty()) fail(ECCKD_PARAMETER_ERROR, "\"--output\" file not specified");
-    Namelist nl;
-    if (!config_file.empty()) nl = read_namelist(config_file);
-    if (nl.nspectralstride != 1) fail(ECCKD_PARAMETER_ERROR, "nspectralstride = %d is not supported (1 only)", nl.nspectralstride);
-    if (nl.nangle < 0 || nl.nangle > 16) fail(ECCKD_PARAMETER_ERROR, "nangle = %d outside 0..16", nl.nangle);
-    if (sw && nl.nangle != 0) WARN("nangle = %d has no meaning for the direct solar beam: ignored", nl.nangle);
-    const std::string history = history_line(argc, argv);
+    const size_t nsum = (size_t)nrow * (nlay + 1);
+    out.write_slice("pressure_hl", c, f.read("pressure_hl", c));
+    if (sw) out.write_slice("flux_dn_direct_sw", c, sum_over_g_points(flux[0], nsum, ng));
+    out.write_slice("flux_dn" + x, c, sum_over_g_points(flux[dn], nsum, ng));
+    out.write_slice("flux_up" + x, c, sum_over_g_points(flux[up], nsum, ng));
+    if (sw) out.write_slice("spectral_flux_dn_direct_sw", c, flux[0]);
+    if (!sw || scattering) out.write_slice("spectral_flux_dn" + x, c, flux[dn]);
+    out.write_slice("spectral_flux_up" + x, c, flux[up]);
+  }
+  out.close();
+  return done(0);
+}
 
-    // ---------------------------------------------------------------------------------------------------------------
-    if (!ckd_file.empty()) {   // radiative transfer on a CKD model's optical depths (test/run_ckd_lw.sh:133-137)
-      Device dev;
-      NcIn f(ckd_file);
-      const std::vector<size_t> sh = f.shape("optical_depth");
-      if (sh.size() != 3) fail(ECCKD_PARAMETER_ERROR, "optical_depth in %s is not (column, level, g_point)", ckd_file.c_str());
-      const int ncol = (int)sh[0], nlay = (int)sh[1], ng = (int)sh[2];
-      if (sw) {
-        if (!f.exist("incoming_sw")) fail(ECCKD_PARAMETER_ERROR, "%s holds no incoming_sw: not a shortwave optical-depth file", ckd_file.c_str());
-        std::vector<double> mu0 = nl.mu0;
-        if (mu0.empty()) mu0 = {0.5};
-        const int nmu = (int)mu0.size();
-        const bool have_ray = f.exist("rayleigh_optical_depth");
-        if (rayleigh_scattering && !have_ray)
-          fail(ECCKD_PARAMETER_ERROR, "\"--rayleigh-scattering\": %s holds no rayleigh_optical_depth", ckd_file.c_str());
-        NcOut out(output);
-        out.dim("column", ncol); out.dim("mu0", nmu); out.dim("half_level", nlay + 1); out.dim("g_point", ng);
-        out.var("pressure_hl", NC_FLOAT_T, {"column", "half_level"}, "Pressure at half levels", "Pa");
-        out.var("mu0", NC_FLOAT_T, {"mu0"}, "Cosine of solar zenith angle", "1");
-        out.var("flux_up_sw", NC_FLOAT_T, {"column", "mu0", "half_level"}, "Upwelling shortwave flux", "W m-2");
-        out.var("flux_dn_sw", NC_FLOAT_T, {"column", "mu0", "half_level"}, "Downwelling shortwave flux", "W m-2");
-        out.var("flux_dn_direct_sw", NC_FLOAT_T, {"column", "mu0", "half_level"}, "Downwelling direct shortwave flux", "W m-2");
-        out.var("spectral_flux_up_sw", NC_FLOAT_T, {"column", "mu0", "half_level", "g_point"}, "Upwelling shortwave flux per g point", "W m-2");
-        out.var("spectral_flux_dn_direct_sw", NC_FLOAT_T, {"column", "mu0", "half_level", "g_point"}, "Downwelling direct shortwave flux per g point", "W m-2");
-        if (rayleigh_scattering)
-          out.var("spectral_flux_dn_sw", NC_FLOAT_T, {"column", "mu0", "half_level", "g_point"}, "Downwelling shortwave flux per g point", "W m-2");
-        if (!scenario.empty()) out.att(scenario, "scenario");
-        out.att(history, "history");
-        if (rayleigh_scattering) out.att("two-stream", "rayleigh_scattering");
-        out.end_define();
-        out.write("mu0", mu0);
-        const size_t nhg = (size_t)(nlay + 1) * ng;
-        if (rayleigh_scattering) for (int c = 0; c < ncol; ++c) {  // two-stream per g point, on the device (ecckd_rt_sw_gpoints_rayleigh)
-          const std::vector<double> od = f.read("optical_depth", c), ray = f.read("rayleigh_optical_depth", c), incoming = f.read("incoming_sw", c);
-          std::vector<double> dir_all(nmu * nhg), dn_all(nmu * nhg), up_all(nmu * nhg);
-          std::vector<double> bdir((size_t)nmu * (nlay + 1), 0.0), bdn(bdir), bup(bdir);
-          for (int m = 0; m < nmu; ++m) {
-            ck(ecckd_rt_sw_gpoints_rayleigh(dev.ctx(), 1, nlay, ng, mu0[m], nl.surf_albedo, incoming.data(), od.data(), ray.data(), &dir_all[m * nhg],
-                                            &dn_all[m * nhg], &up_all[m * nhg]));
-            for (int i = 0; i <= nlay; ++i)
-              for (int g = 0; g < ng; ++g) {
-                bdir[(size_t)m * (nlay + 1) + i] += dir_all[m * nhg + (size_t)i * ng + g];
-                bdn[(size_t)m * (nlay + 1) + i] += dn_all[m * nhg + (size_t)i * ng + g];
-                bup[(size_t)m * (nlay + 1) + i] += up_all[m * nhg + (size_t)i * ng + g];
-              }
-          }
-          out.write_slice("pressure_hl", c, f.read("pressure_hl", c));
-          out.write_slice("flux_dn_direct_sw", c, bdir); out.write_slice("flux_dn_sw", c, bdn); out.write_slice("flux_up_sw", c, bup);
-          out.write_slice("spectral_flux_dn_direct_sw", c, dir_all); out.write_slice("spectral_flux_dn_sw", c, dn_all);
-          out.write_slice("spectral_flux_up_sw", c, up_all);
-        }
-        else for (int c = 0; c < ncol; ++c) {
-          std::vector<double> od = f.read("optical_depth", c);
-          if (have_ray) {                       // one more absorber, as in the reference's forward model (solve_adept.cpp:34)
-            const std::vector<double> ray = f.read("rayleigh_optical_depth", c);
-            for (size_t i = 0; i < od.size(); ++i) od[i] += ray[i];
-          }
-          const std::vector<double> incoming = f.read("incoming_sw", c);
-          std::vector<double> dn_all(nmu * nhg), up_all(nmu * nhg), bdn((size_t)nmu * (nlay + 1), 0.0), bup((size_t)nmu * (nlay + 1), 0.0);
-          for (int m = 0; m < nmu; ++m) {
-            // radiative_transfer_sw.cpp:45-77 per g point, on the device (ecckd_rt_sw_gpoints)
-            ck(ecckd_rt_sw_gpoints(dev.ctx(), 1, nlay, ng, mu0[m], nl.surf_albedo, incoming.data(), od.data(), &dn_all[m * nhg], &up_all[m * nhg]));
-            for (int i = 0; i <= nlay; ++i)
-              for (int g = 0; g < ng; ++g) {
-                bdn[(size_t)m * (nlay + 1) + i] += dn_all[m * nhg + (size_t)i * ng + g];
-                bup[(size_t)m * (nlay + 1) + i] += up_all[m * nhg + (size_t)i * ng + g];
-              }
-          }
-          out.write_slice("pressure_hl", c, f.read("pressure_hl", c));
-          out.write_slice("flux_dn_direct_sw", c, bdn); out.write_slice("flux_dn_sw", c, bdn); out.write_slice("flux_up_sw", c, bup);
-          out.write_slice("spectral_flux_dn_direct_sw", c, dn_all); out.write_slice("spectral_flux_up_sw", c, up_all);
-        }
-        out.close();
-        return done(0);
-      }
-      if (!f.exist("planck_hl")) fail(ECCKD_PARAMETER_ERROR, "%s holds no planck_hl: not a longwave optical-depth file", ckd_file.c_str());
-      NcOut out(output);
-      out.dim("column", ncol); out.dim("half_level", nlay + 1); out.dim("g_point", ng);
-      out.var("pressure_hl", NC_FLOAT_T, {"column", "half_level"}, "Pressure at half levels", "Pa");
-      out.var("flux_up_lw", NC_FLOAT_T, {"column", "half_level"}, "Upwelling longwave flux", "W m-2");
-      out.var("flux_dn_lw", NC_FLOAT_T, {"column", "half_level"}, "Downwelling longwave flux", "W m-2");
-      out.var("spectral_flux_up_lw", NC_FLOAT_T, {"column", "half_level", "g_point"}, "Upwelling longwave flux per g point", "W m-2");
-      out.var("spectral_flux_dn_lw", NC_FLOAT_T, {"column", "half_level", "g_point"}, "Downwelling longwave flux per g point", "W m-2");
-      if (!scenario.empty()) out.att(scenario, "scenario");
-      out.att(history, "history");
-      out.end_define();
-      const size_t nhg = (size_t)(nlay + 1) * ng;
-      for (int c = 0; c < ncol; ++c) {
-        const std::vector<double> od = f.read("optical_depth", c), planck = f.read("planck_hl", c);
-        std::vector<double> dn(nhg), up(nhg), bdn(nlay + 1, 0.0), bup(nlay + 1, 0.0);
-        // radiative_transfer_lw.cpp:27-60 per g point (two-stream or nangle Gauss-Legendre angles), on the device
-        ck(ecckd_rt_lw_gpoints(dev.ctx(), nl.nangle, 1, nlay, ng, planck.data(), od.data(), dn.data(), up.data()));
-        for (int i = 0; i <= nlay; ++i)
-          for (int g = 0; g < ng; ++g) { bdn[i] += dn[(size_t)i * ng + g]; bup[i] += up[(size_t)i * ng + g]; }
-        out.write_slice("pressure_hl", c, f.read("pressure_hl", c));
-        out.write_slice("flux_dn_lw", c, bdn); out.write_slice("flux_up_lw", c, bup);
-        out.write_slice("spectral_flux_dn_lw", c, dn); out.write_slice("spectral_flux_up_lw", c, up);
-      }
-      out.close();
-      return done(0);
-    }
+// ---- the modes that read files of spectra ----
+// Grids and profiles from the first file (every other file must share them) and the columns asked for: no device needed
+struct Grid {
+  Spectrum first;
+  int nlay = 0, c0 = 0, c1 = 0, ncol = 0;
+  size_t nwav = 0;
+};
 
-    if (gases.empty()) fail(ECCKD_PARAMETER_ERROR, "No spectrum files given");
-    // ---- grids and profiles from the first file; every other file must share them ----
-    Spectrum first = read_spectrum(gases[0].path, 0, false);
-    const int nlay = first.nlay, ncol_file = first.ncol;
-    const size_t nwav = first.nwav;
-    int c0 = 0, c1 = ncol_file - 1;
-    if (col_a >= 1) { c0 = (int)col_a - 1; c1 = std::min<long>(col_b, ncol_file) - 1; }   // 1-based, inclusive, like the Fortran tool
-    const int ncol = c1 - c0 + 1;
-    if (ncol <= 0) fail(ECCKD_PARAMETER_ERROR, "Empty column range");
-    LOG("%d gas file(s), %d column(s), %d layers, %zu spectral points\n", (int)gases.size(), ncol, nlay, nwav);
+Grid read_grid(const Args& a) {
+  Grid g;
+  g.first = read_spectrum(a.gases[0].path, 0, false);
+  g.nlay = g.first.nlay; g.nwav = g.first.nwav;
+  g.c1 = g.first.ncol - 1;
+  if (a.col_a >= 1) { g.c0 = (int)a.col_a - 1; g.c1 = std::min<long>(a.col_b, g.first.ncol) - 1; }   // 1-based, inclusive, like the Fortran tool
+  g.ncol = g.c1 - g.c0 + 1;
+  if (g.ncol <= 0) fail(ECCKD_PARAMETER_ERROR, "Empty column range");
+  LOG("%d gas file(s), %d column(s), %d layers, %zu spectral points\n", (int)a.gases.size(), g.ncol, g.nlay, g.nwav);
+  return g;
+}
 
-    Device dev;
-    DevBuf d_merged;
-    if (table.empty()) d_merged.alloc(dev, (size_t)nlay * nwav * sizeof(double));
-    DevBuf d_wn, d_dwn;
-    d_wn.upload(dev, first.wavenumber_cm_1);
-    d_dwn.upload(dev, first.d_wavenumber_cm_1);
-    DevBuf d_ssi, d_albedo;
-    std::vector<double> mu0 = nl.mu0;
-    if (sw && !merge_only) {
-      if (ssi_file.empty()) fail(ECCKD_PARAMETER_ERROR, "\"--ssi\" file not specified");
-      NcIn fs(ssi_file);
+// ... and what they keep on the device or take from the namelist
+struct Spectra {
+  const Grid g;
+  Device dev;
+  DevBuf d_wn, d_dwn, d_ssi, d_albedo;
+  std::vector<double> mu0;
+  int nmu = 0, nband = 0;
+  std::string ids;
+  std::vector<int64_t> bbegin, bend;           // bands of the namelist -> wavenumber index ranges
+
+  explicit Spectra(const Args& a) : g(read_grid(a)) {
+    const Namelist& nl = a.nl;
+    d_wn.upload(dev, g.first.wavenumber_cm_1);
+    d_dwn.upload(dev, g.first.d_wavenumber_cm_1);
+    mu0 = nl.mu0;
+    if (a.sw && !a.merge_only) {
+      if (a.ssi_file.empty()) fail(ECCKD_PARAMETER_ERROR, "\"--ssi\" file not specified");
+      NcIn fs(a.ssi_file);
       const std::vector<double> ssi = fs.read("solar_spectral_irradiance");
-      if (ssi.size() != nwav) fail(ECCKD_PARAMETER_ERROR, "solar_spectral_irradiance has %zu points, the spectra %zu", ssi.size(), nwav);
+      if (ssi.size() != g.nwav) fail(ECCKD_PARAMETER_ERROR, "solar_spectral_irradiance has %zu points, the spectra %zu", ssi.size(), g.nwav);
       d_ssi.upload(dev, ssi);
-      d_albedo.upload(dev, std::vector<double>(nwav, nl.surf_albedo));
+      d_albedo.upload(dev, std::vector<double>(g.nwav, nl.surf_albedo));
       if (mu0.empty()) fail(ECCKD_PARAMETER_ERROR, "cos_solar_zenith_angle missing from the namelist");
     }
-    const int nmu = (int)mu0.size();
-    std::string ids;
-    std::vector<std::string> molecules;
-    for (const GasArg& g : gases) {
-      NcIn f(g.path);
+    nmu = (int)mu0.size();
+    for (const GasArg& gas : a.gases) {
+      NcIn f(gas.path);
       std::string m;
       if (!f.att_text("constituent_id", m)) f.att_text("molecules", m);
-      molecules.push_back(m.substr(0, m.find(' ')));
-      ids += (ids.empty() ? "" : " ") + molecules.back();
+      ids += (ids.empty() ? "" : " ") + m.substr(0, m.find(' '));
     }
-
-    // bands of the namelist -> wavenumber index ranges
-    std::vector<int64_t> bbegin, bend;
-    int nband = 0;
-    if (!merge_only) {
+    if (!a.merge_only) {
       if (nl.band1.empty() || nl.band1.size() != nl.band2.size())
         fail(ECCKD_PARAMETER_ERROR, "band_wavenumber1 / band_wavenumber2 missing from the namelist");
       nband = (int)nl.band1.size();
       bbegin.resize(nband); bend.resize(nband);
-      ck(ecckd_band_ranges(nwav, first.wavenumber_cm_1.data(), nband, nl.band1.data(), nl.band2.data(), nullptr, bbegin.data(), bend.data()));
+      ck(ecckd_band_ranges(g.nwav, g.first.wavenumber_cm_1.data(), nband, nl.band1.data(), nl.band2.data(), nullptr, bbegin.data(), bend.data()));
     }
+  }
+};
 
-    // ---------------------------------------------------------------------------------------------------------------
-    if (!table.empty()) {   // every scenario of the table from one read of the gas files per column
-      const size_t nscen = table.size(), ngas = gases.size(), nhl = (size_t)nlay + 1;
-      std::vector<std::unique_ptr<NcOut>> outs;
-      for (const ScenarioRow& row : table) {
-        outs.emplace_back(new NcOut(row.output));
-        NcOut& o = *outs.back();
-        o.dim("column", ncol); o.dim("half_level", nlay + 1); o.dim("level", nlay);
-        o.var("pressure_hl", NC_FLOAT_T, {"column", "half_level"}, "Pressure at half levels", "Pa");
-        o.var("temperature_hl", NC_FLOAT_T, {"column", "half_level"}, "Temperature at half levels", "K");
-        define_flux_variables(o, sw, ngas, nmu, nband, nwav, ids, nl.boundary_fluxes);
-        o.att(row.name, "scenario");
-        o.att(history, "history");
-        o.end_define();
-        if (sw) { o.write("band_wavenumber1_sw", nl.band1); o.write("band_wavenumber2_sw", nl.band2); o.write("mu0", mu0); }
-        else { o.write("band_wavenumber1_lw", nl.band1); o.write("band_wavenumber2_lw", nl.band2); }
-        if (nl.boundary_fluxes) o.write("wavenumber", first.wavenumber_cm_1);
+// A flux file as far as the column dimension, the profiles and define_flux_variables go, and its coordinate variables
+void define_flux_file(NcOut& o, const Args& a, const Spectra& s, const std::string& scenario, bool rayleigh) {
+  o.dim("column", s.g.ncol); o.dim("half_level", s.g.nlay + 1); o.dim("level", s.g.nlay);
+  o.var("pressure_hl", NC_FLOAT_T, {"column", "half_level"}, "Pressure at half levels", "Pa");
+  o.var("temperature_hl", NC_FLOAT_T, {"column", "half_level"}, "Temperature at half levels", "K");
+  if (a.merge_only) {
+    o.dim("wavenumber", s.g.nwav);
+    o.var("wavenumber", NC_DOUBLE_T, {"wavenumber"}, "Wavenumber", "cm-1");
+    o.var("optical_depth", NC_FLOAT_T, {"column", "level", "wavenumber"}, "Layer optical depth");
+    o.att(s.ids, "molecules");
+    o.att("composite", "constituent_id");
+  } else {
+    define_flux_variables(o, a.sw, a.gases.size(), s.nmu, s.nband, s.g.nwav, s.ids, a.nl.boundary_fluxes, rayleigh);
+  }
+  if (!scenario.empty()) o.att(scenario, "scenario");
+  o.att(a.history, "history");
+  o.end_define();
+  if (!a.merge_only) {
+    const std::string x = a.sw ? "_sw" : "_lw";
+    o.write("band_wavenumber1" + x, a.nl.band1); o.write("band_wavenumber2" + x, a.nl.band2);
+    if (a.sw) o.write("mu0", s.mu0);
+  }
+  if (a.merge_only || a.nl.boundary_fluxes) o.write("wavenumber", s.g.first.wavenumber_cm_1);
+}
+
+// ---- --scenarios: every scenario of the table from one read of the gas files per column ----
+int mode_scenarios(const Args& a, Spectra& s) {
+  const Namelist& nl = a.nl;
+  const bool sw = a.sw;
+  const Device& dev = s.dev;
+  const int nlay = s.g.nlay, nband = s.nband, nmu = s.nmu;
+  const size_t nwav = s.g.nwav, nscen = a.table.size(), ngas = a.gases.size(), nhl = (size_t)nlay + 1;
+  std::vector<std::unique_ptr<NcOut>> outs;
+  for (const ScenarioRow& row : a.table) {
+    outs.emplace_back(new NcOut(row.output));
+    define_flux_file(*outs.back(), a, s, row.name, false);
+  }
+  const size_t nslot = sw ? nscen * nmu : nscen;            // rows of fluxes: (scenario[, angle])
+  const int ngroup = sw ? std::min(8, nmu) : 1;              // angles per call: the entry takes up to 8
+  DevBuf d_sdn, d_tup;
+  if (nl.boundary_fluxes) { d_sdn.alloc(dev, nscen * ngroup * nwav * sizeof(double)); d_tup.alloc(dev, nscen * ngroup * nwav * sizeof(double)); }
+  double* const p_sdn = nl.boundary_fluxes ? d_sdn.as<double>() : nullptr;
+  double* const p_tup = nl.boundary_fluxes ? d_tup.as<double>() : nullptr;
+  for (int c = s.g.c0; c <= s.g.c1; ++c) {
+    const Spectrum col = c == 0 ? s.g.first : read_spectrum(a.gases[0].path, c, false);
+    std::vector<DevOd> ods;                                  // the gases side by side on the device, read once
+    std::vector<const void*> od_ptr;
+    std::vector<int> od_type;
+    std::vector<size_t> od_stride(ngas, nwav);
+    std::vector<double> scale(nscen * ngas * nlay), vmr_all(nscen * ngas * nlay);   // [scenario][gas][level]
+    for (size_t ig = 0; ig < ngas; ++ig) {
+      NcIn f(a.gases[ig].path);
+      double ref = -1.0;
+      std::vector<double> vmr, profile, vmr_out;
+      std::string mol;
+      read_od_meta(f, c, nlay, ref, vmr, mol);
+      for (size_t k = 0; k < nscen; ++k) {
+        gas_scaling(a.table[k].specs[ig], a.gases[ig].path, nlay, col.pressure_hl, ref, vmr, profile, vmr_out);
+        std::copy(profile.begin(), profile.end(), scale.begin() + (k * ngas + ig) * nlay);
+        std::copy(vmr_out.begin(), vmr_out.end(), vmr_all.begin() + (k * ngas + ig) * nlay);
       }
-      const size_t nslot = sw ? nscen * nmu : nscen;            // rows of fluxes: (scenario[, angle])
-      const int ngroup = sw ? std::min(8, nmu) : 1;              // angles per call: the entry takes up to 8
-      DevBuf d_sdn, d_tup;
-      if (nl.boundary_fluxes) { d_sdn.alloc(dev, nscen * ngroup * nwav * sizeof(double)); d_tup.alloc(dev, nscen * ngroup * nwav * sizeof(double)); }
-      double* const p_sdn = nl.boundary_fluxes ? d_sdn.as<double>() : nullptr;
-      double* const p_tup = nl.boundary_fluxes ? d_tup.as<double>() : nullptr;
-      for (int c = c0; c <= c1; ++c) {
-        const Spectrum col = c == 0 ? first : read_spectrum(gases[0].path, c, false);
-        std::vector<DevOd> ods;                                  // the gases side by side on the device, read once
-        std::vector<const void*> od_ptr;
-        std::vector<int> od_type;
-        std::vector<size_t> od_stride(ngas, nwav);
-        std::vector<double> scale(nscen * ngas * nlay), vmr_all(nscen * ngas * nlay);   // [scenario][gas][level]
-        for (size_t ig = 0; ig < ngas; ++ig) {
-          NcIn f(gases[ig].path);
-          double ref = -1.0;
-          std::vector<double> vmr, profile, vmr_out;
-          std::string mol;
-          read_od_meta(f, c, nlay, ref, vmr, mol);
-          for (size_t s = 0; s < nscen; ++s) {
-            gas_scaling(table[s].specs[ig], gases[ig].path, nlay, col.pressure_hl, ref, vmr, profile, vmr_out);
-            std::copy(profile.begin(), profile.end(), scale.begin() + (s * ngas + ig) * nlay);
-            std::copy(vmr_out.begin(), vmr_out.end(), vmr_all.begin() + (s * ngas + ig) * nlay);
-          }
-          ods.push_back(read_od_dev(dev, f, c, nlay, nwav));
-          od_ptr.push_back(ods.back().buf.ptr());
-          od_type.push_back(ods.back().type);
-        }
-        ck(ecckd_synchronize(dev.ctx()));
-        std::vector<double> bdn(nslot * nband * nhl), bup(nslot * nband * nhl);
-        std::vector<double> all_dn, all_up;                      // [slot][wavenumber] boundary fluxes of this column
-        if (nl.boundary_fluxes) { all_dn.resize(nslot * nwav); all_up.resize(nslot * nwav); }
-        if (sw) {
-          for (int m0 = 0; m0 < nmu; m0 += ngroup) {             // [scenario][angle] rows per group of angles
-            const size_t nm = (size_t)std::min(ngroup, nmu - m0);
-            std::vector<double> gdn(nscen * nm * nband * nhl), gup(gdn.size());
-            ck(ecckd_lbl_band_fluxes_sw_scenarios(dev.ctx(), nlay, nwav, (int)nm, mu0.data() + m0, d_ssi.as<double>(), d_albedo.as<double>(), (int)ngas,
-                                                  od_ptr.data(), od_type.data(), od_stride.data(), (int)nscen, scale.data(), nband, bbegin.data(),
-                                                  bend.data(), gdn.data(), gup.data(), p_sdn, p_tup));
-            std::vector<double> a, b;
-            if (nl.boundary_fluxes) { a = d_sdn.download<double>(); b = d_tup.download<double>(); }
-            for (size_t s = 0; s < nscen; ++s) {
-              const size_t n = nm * nband * nhl, to = (s * nmu + m0) * nband * nhl;
-              std::copy(gdn.begin() + s * n, gdn.begin() + (s + 1) * n, bdn.begin() + to);
-              std::copy(gup.begin() + s * n, gup.begin() + (s + 1) * n, bup.begin() + to);
-              if (nl.boundary_fluxes) {
-                std::copy(a.begin() + s * nm * nwav, a.begin() + (s + 1) * nm * nwav, all_dn.begin() + (s * nmu + m0) * nwav);
-                std::copy(b.begin() + s * nm * nwav, b.begin() + (s + 1) * nm * nwav, all_up.begin() + (s * nmu + m0) * nwav);
-              }
-            }
-          }
-        } else {
-          if (col.temperature_hl.empty()) fail(ECCKD_PARAMETER_ERROR, "temperature_hl missing from %s", gases[0].path.c_str());
-          ck(ecckd_lbl_band_fluxes_lw_scenarios(dev.ctx(), nl.nangle, nlay, nwav, col.temperature_hl.data(), d_wn.as<double>(), d_dwn.as<double>(),
-                                                (int)ngas, od_ptr.data(), od_type.data(), od_stride.data(), (int)nscen, scale.data(), nband,
-                                                bbegin.data(), bend.data(), bdn.data(), bup.data(), p_sdn, p_tup));
-          if (nl.boundary_fluxes) { all_dn = d_sdn.download<double>(); all_up = d_tup.download<double>(); }
-        }
-        const size_t oc = (size_t)(c - c0), per = sw ? (size_t)nmu : 1;   // rows per scenario
-        std::vector<double> tdn(per * nhl * nband), tup(per * nhl * nband), sdn(per * nhl), sup(per * nhl);
-        for (size_t s = 0; s < nscen; ++s) {
-          NcOut& o = *outs[s];
-          o.write_slice("pressure_hl", oc, col.pressure_hl);
-          if (!col.temperature_hl.empty()) o.write_slice("temperature_hl", oc, col.temperature_hl);
-          for (size_t m = 0; m < per; ++m) {
-            bands_to_file_order(nband, nhl, &bdn[(s * per + m) * nband * nhl], &tdn[m * nhl * nband], &sdn[m * nhl]);
-            bands_to_file_order(nband, nhl, &bup[(s * per + m) * nband * nhl], &tup[m * nhl * nband], &sup[m * nhl]);
-          }
-          o.write_slice("mole_fraction_fl", oc, std::vector<double>(vmr_all.begin() + s * ngas * nlay, vmr_all.begin() + (s + 1) * ngas * nlay));
-          if (sw) {
-            o.write_slice("band_flux_dn_direct_sw", oc, tdn); o.write_slice("band_flux_up_sw", oc, tup);
-            o.write_slice("flux_dn_direct_sw", oc, sdn); o.write_slice("flux_dn_sw", oc, sdn); o.write_slice("flux_up_sw", oc, sup);
-          } else {
-            o.write_slice("band_flux_dn_lw", oc, tdn); o.write_slice("band_flux_up_lw", oc, tup);
-            o.write_slice("flux_dn_lw", oc, sdn); o.write_slice("flux_up_lw", oc, sup);
-          }
+      ods.push_back(read_od_dev(dev, f, c, nlay, nwav));
+      od_ptr.push_back(ods.back().buf.ptr());
+      od_type.push_back(ods.back().type);
+    }
+    ck(ecckd_synchronize(dev.ctx()));
+    std::vector<double> bdn(nslot * nband * nhl), bup(nslot * nband * nhl);
+    std::vector<double> all_dn, all_up;                      // [slot][wavenumber] boundary fluxes of this column
+    if (nl.boundary_fluxes) { all_dn.resize(nslot * nwav); all_up.resize(nslot * nwav); }
+    if (sw) {
+      for (int m0 = 0; m0 < nmu; m0 += ngroup) {             // [scenario][angle] rows per group of angles
+        const size_t nm = (size_t)std::min(ngroup, nmu - m0);
+        std::vector<double> gdn(nscen * nm * nband * nhl), gup(gdn.size());
+        ck(ecckd_lbl_band_fluxes_sw_scenarios(dev.ctx(), nlay, nwav, (int)nm, s.mu0.data() + m0, s.d_ssi.as<double>(), s.d_albedo.as<double>(),
+                                              (int)ngas, od_ptr.data(), od_type.data(), od_stride.data(), (int)nscen, scale.data(), nband,
+                                              s.bbegin.data(), s.bend.data(), gdn.data(), gup.data(), p_sdn, p_tup));
+        std::vector<double> sd, tu;
+        if (nl.boundary_fluxes) { sd = d_sdn.download<double>(); tu = d_tup.download<double>(); }
+        for (size_t k = 0; k < nscen; ++k) {
+          const size_t n = nm * nband * nhl, to = (k * nmu + m0) * nband * nhl;
+          std::copy(gdn.begin() + k * n, gdn.begin() + (k + 1) * n, bdn.begin() + to);
+          std::copy(gup.begin() + k * n, gup.begin() + (k + 1) * n, bup.begin() + to);
           if (nl.boundary_fluxes) {
-            const std::vector<double> a(all_dn.begin() + s * per * nwav, all_dn.begin() + (s + 1) * per * nwav);
-            const std::vector<double> b(all_up.begin() + s * per * nwav, all_up.begin() + (s + 1) * per * nwav);
-            o.write_slice(sw ? "spectral_flux_dn_direct_surf_sw" : "spectral_flux_dn_surf_lw", oc, a);
-            o.write_slice(sw ? "spectral_flux_up_toa_sw" : "spectral_flux_up_toa_lw", oc, b);
+            std::copy(sd.begin() + k * nm * nwav, sd.begin() + (k + 1) * nm * nwav, all_dn.begin() + (k * nmu + m0) * nwav);
+            std::copy(tu.begin() + k * nm * nwav, tu.begin() + (k + 1) * nm * nwav, all_up.begin() + (k * nmu + m0) * nwav);
           }
         }
-        LOG("  column %d done (%zu scenarios)\n", c + 1, nscen);
       }
-      for (auto& o : outs) o->close();
-      return done(0);
-    }
-
-    NcOut out(output);
-    out.dim("column", ncol); out.dim("half_level", nlay + 1); out.dim("level", nlay);
-    out.var("pressure_hl", NC_FLOAT_T, {"column", "half_level"}, "Pressure at half levels", "Pa");
-    out.var("temperature_hl", NC_FLOAT_T, {"column", "half_level"}, "Temperature at half levels", "K");
-    if (merge_only) {
-      out.dim("wavenumber", nwav);
-      out.var("wavenumber", NC_DOUBLE_T, {"wavenumber"}, "Wavenumber", "cm-1");
-      out.var("optical_depth", NC_FLOAT_T, {"column", "level", "wavenumber"}, "Layer optical depth");
-      out.att(ids, "molecules");
-      out.att("composite", "constituent_id");
     } else {
-      define_flux_variables(out, sw, gases.size(), nmu, nband, nwav, ids, nl.boundary_fluxes, !rayleigh_file.empty());
+      if (col.temperature_hl.empty()) fail(ECCKD_PARAMETER_ERROR, "temperature_hl missing from %s", a.gases[0].path.c_str());
+      ck(ecckd_lbl_band_fluxes_lw_scenarios(dev.ctx(), nl.nangle, nlay, nwav, col.temperature_hl.data(), s.d_wn.as<double>(), s.d_dwn.as<double>(),
+                                            (int)ngas, od_ptr.data(), od_type.data(), od_stride.data(), (int)nscen, scale.data(), nband,
+                                            s.bbegin.data(), s.bend.data(), bdn.data(), bup.data(), p_sdn, p_tup));
+      if (nl.boundary_fluxes) { all_dn = d_sdn.download<double>(); all_up = d_tup.download<double>(); }
     }
-    if (!scenario.empty()) out.att(scenario, "scenario");
-    out.att(history, "history");
-    out.end_define();
-    if (merge_only) out.write("wavenumber", first.wavenumber_cm_1);
-    else if (sw) { out.write("band_wavenumber1_sw", nl.band1); out.write("band_wavenumber2_sw", nl.band2); out.write("mu0", mu0); }
-    else { out.write("band_wavenumber1_lw", nl.band1); out.write("band_wavenumber2_lw", nl.band2); }
-    DevBuf d_bnd_dn, d_bnd_up;
-    if (!merge_only && nl.boundary_fluxes) {
-      out.write("wavenumber", first.wavenumber_cm_1);
-      d_bnd_dn.alloc(dev, nwav * sizeof(double));
-      d_bnd_up.alloc(dev, nwav * sizeof(double));
+    const size_t oc = (size_t)(c - s.g.c0), per = sw ? (size_t)nmu : 1;   // rows per scenario
+    std::vector<double> tdn(per * nhl * nband), tup(per * nhl * nband), sdn(per * nhl), sup(per * nhl);
+    const std::string x = sw ? "_sw" : "_lw";
+    for (size_t k = 0; k < nscen; ++k) {
+      NcOut& o = *outs[k];
+      o.write_slice("pressure_hl", oc, col.pressure_hl);
+      if (!col.temperature_hl.empty()) o.write_slice("temperature_hl", oc, col.temperature_hl);
+      for (size_t m = 0; m < per; ++m) {
+        bands_to_file_order(nband, nhl, &bdn[(k * per + m) * nband * nhl], &tdn[m * nhl * nband], &sdn[m * nhl]);
+        bands_to_file_order(nband, nhl, &bup[(k * per + m) * nband * nhl], &tup[m * nhl * nband], &sup[m * nhl]);
+      }
+      o.write_slice("mole_fraction_fl", oc, std::vector<double>(vmr_all.begin() + k * ngas * nlay, vmr_all.begin() + (k + 1) * ngas * nlay));
+      o.write_slice(sw ? "band_flux_dn_direct_sw" : "band_flux_dn_lw", oc, tdn); o.write_slice("band_flux_up" + x, oc, tup);
+      if (sw) o.write_slice("flux_dn_direct_sw", oc, sdn);
+      o.write_slice("flux_dn" + x, oc, sdn); o.write_slice("flux_up" + x, oc, sup);
+      if (nl.boundary_fluxes) {
+        const std::vector<double> sd(all_dn.begin() + k * per * nwav, all_dn.begin() + (k + 1) * per * nwav);
+        const std::vector<double> tu(all_up.begin() + k * per * nwav, all_up.begin() + (k + 1) * per * nwav);
+        o.write_slice(sw ? "spectral_flux_dn_direct_surf_sw" : "spectral_flux_dn_surf_lw", oc, sd);
+        o.write_slice("spectral_flux_up_toa" + x, oc, tu);
+      }
     }
-    double* const p_bnd_dn = nl.boundary_fluxes && !merge_only ? d_bnd_dn.as<double>() : nullptr;
-    double* const p_bnd_up = nl.boundary_fluxes && !merge_only ? d_bnd_up.as<double>() : nullptr;
-    const int ngroup = std::min(8, std::max(nmu, 1));          // --rayleigh: angles per call, the entry takes up to 8
-    DevBuf d_ray_dir, d_ray_dn, d_ray_up;                      // their boundary fluxes, [angle][wavenumber]
-    if (!rayleigh_file.empty() && nl.boundary_fluxes)
-      for (DevBuf* b : {&d_ray_dir, &d_ray_dn, &d_ray_up}) b->alloc(dev, (size_t)ngroup * nwav * sizeof(double));
+    LOG("  column %d done (%zu scenarios)\n", c + 1, nscen);
+  }
+  for (auto& o : outs) o->close();
+  return done(0);
+}
 
-    for (int c = c0; c <= c1; ++c) {
-      const Spectrum col = c == 0 ? first : read_spectrum(gases[0].path, c, false);
-      std::vector<double> vmr_all;   // [gas][level]
-      for (size_t ig = 0; ig < gases.size(); ++ig) {
-        const GasArg& g = gases[ig];
-        NcIn f(g.path);
-        double ref = -1.0;
-        std::vector<double> vmr;
-        std::string mol;
-        read_od_meta(f, c, nlay, ref, vmr, mol);
-        std::vector<double> profile, vmr_out;
-        gas_scaling(g, g.path, nlay, col.pressure_hl, ref, vmr, profile, vmr_out);
-        vmr_all.insert(vmr_all.end(), vmr_out.begin(), vmr_out.end());
-        DevOd od = read_od_dev(dev, f, c, nlay, nwav);
-        ck(ecckd_merge_spectrum_dev(dev.ctx(), nlay, nwav, od.buf.ptr(), od.type, nwav, profile.data(), ig == 0 ? 1 : 0,
-                                    d_merged.as<double>(), nwav));
-        ck(ecckd_synchronize(dev.ctx()));
-      }
-      const size_t oc = (size_t)(c - c0);
-      out.write_slice("pressure_hl", oc, col.pressure_hl);
-      if (!col.temperature_hl.empty()) out.write_slice("temperature_hl", oc, col.temperature_hl);
-      if (merge_only) {
-        out.write_slice("optical_depth", oc, d_merged.download<double>());
-      } else if (sw && !rayleigh_file.empty()) {   // the absorbers merged above, the Rayleigh spectrum beside them: two-stream
-        const size_t nhl = (size_t)nlay + 1;
-        NcIn fr(rayleigh_file);
-        const DevOd ray = read_od_dev(dev, fr, c, nlay, nwav);
-        ck(ecckd_synchronize(dev.ctx()));
-        std::vector<double> tdir((size_t)nmu * nhl * nband), tdn(tdir.size()), tup(tdir.size()), sdir((size_t)nmu * nhl), sdn(sdir.size()), sup(sdir.size());
-        std::vector<double> all_dir, all_dn, all_up;     // (mu0, wavenumber) boundary fluxes of this column
-        const bool bnd = nl.boundary_fluxes;
-        for (int m0 = 0; m0 < nmu; m0 += ngroup) {
-          const int nm = std::min(ngroup, nmu - m0);
-          std::vector<double> gdir((size_t)nm * nband * nhl), gdn(gdir.size()), gup(gdir.size());
-          ck(ecckd_lbl_band_fluxes_sw_rayleigh(dev.ctx(), nlay, nwav, nm, mu0.data() + m0, d_ssi.as<double>(), d_albedo.as<double>(), d_merged.ptr(),
-                                               ECCKD_F64, nwav, ray.buf.ptr(), ray.type, nwav, nband, bbegin.data(), bend.data(), gdir.data(),
-                                               gdn.data(), gup.data(), bnd ? d_ray_dir.as<double>() : nullptr, bnd ? d_ray_dn.as<double>() : nullptr,
-                                               bnd ? d_ray_up.as<double>() : nullptr));
-          if (bnd) {
-            const std::vector<double> a = d_ray_dir.download<double>(), b = d_ray_dn.download<double>(), u = d_ray_up.download<double>();
-            all_dir.insert(all_dir.end(), a.begin(), a.begin() + (size_t)nm * nwav);
-            all_dn.insert(all_dn.end(), b.begin(), b.begin() + (size_t)nm * nwav);
-            all_up.insert(all_up.end(), u.begin(), u.begin() + (size_t)nm * nwav);
-          }
-          for (int m = 0; m < nm; ++m) {
-            const size_t from = (size_t)m * nband * nhl, to = (size_t)(m0 + m);
-            bands_to_file_order(nband, nhl, &gdir[from], &tdir[to * nhl * nband], &sdir[to * nhl]);
-            bands_to_file_order(nband, nhl, &gdn[from], &tdn[to * nhl * nband], &sdn[to * nhl]);
-            bands_to_file_order(nband, nhl, &gup[from], &tup[to * nhl * nband], &sup[to * nhl]);
-          }
-        }
-        out.write_slice("mole_fraction_fl", oc, vmr_all);
-        out.write_slice("band_flux_dn_direct_sw", oc, tdir); out.write_slice("band_flux_dn_sw", oc, tdn); out.write_slice("band_flux_up_sw", oc, tup);
-        out.write_slice("flux_dn_direct_sw", oc, sdir); out.write_slice("flux_dn_sw", oc, sdn); out.write_slice("flux_up_sw", oc, sup);
-        if (bnd) {
-          out.write_slice("spectral_flux_dn_direct_surf_sw", oc, all_dir); out.write_slice("spectral_flux_dn_surf_sw", oc, all_dn);
-          out.write_slice("spectral_flux_up_toa_sw", oc, all_up);
-        }
-      } else if (sw) {
-        const size_t nhl = (size_t)nlay + 1;
-        std::vector<double> tdn((size_t)nmu * nhl * nband), tup((size_t)nmu * nhl * nband), sdn((size_t)nmu * nhl, 0.0), sup((size_t)nmu * nhl, 0.0);
-        std::vector<double> bdn((size_t)nband * nhl), bup((size_t)nband * nhl);
-        std::vector<double> all_dn, all_up;     // (mu0, wavenumber) boundary fluxes of this column
-        for (int m = 0; m < nmu; ++m) {
-          ck(ecckd_lbl_band_fluxes_sw_ex(dev.ctx(), nlay, nwav, mu0[m], d_ssi.as<double>(), d_albedo.as<double>(), d_merged.ptr(), ECCKD_F64, nwav,
-                                         nband, bbegin.data(), bend.data(), bdn.data(), bup.data(), p_bnd_dn, p_bnd_up));
-          if (p_bnd_dn) {
-            const std::vector<double> a = d_bnd_dn.download<double>(), b = d_bnd_up.download<double>();
-            all_dn.insert(all_dn.end(), a.begin(), a.end());
-            all_up.insert(all_up.end(), b.begin(), b.end());
-          }
-          for (int b = 0; b < nband; ++b)
-            for (size_t i = 0; i < nhl; ++i) {
-              tdn[((size_t)m * nhl + i) * nband + b] = bdn[(size_t)b * nhl + i];
-              tup[((size_t)m * nhl + i) * nband + b] = bup[(size_t)b * nhl + i];
-              sdn[(size_t)m * nhl + i] += bdn[(size_t)b * nhl + i];
-              sup[(size_t)m * nhl + i] += bup[(size_t)b * nhl + i];
-            }
-        }
-        out.write_slice("mole_fraction_fl", oc, vmr_all);
-        out.write_slice("band_flux_dn_direct_sw", oc, tdn); out.write_slice("band_flux_up_sw", oc, tup);
-        out.write_slice("flux_dn_direct_sw", oc, sdn); out.write_slice("flux_dn_sw", oc, sdn); out.write_slice("flux_up_sw", oc, sup);
-        if (p_bnd_dn) { out.write_slice("spectral_flux_dn_direct_surf_sw", oc, all_dn); out.write_slice("spectral_flux_up_toa_sw", oc, all_up); }
-      } else {
-        if (col.temperature_hl.empty()) fail(ECCKD_PARAMETER_ERROR, "temperature_hl missing from %s", gases[0].path.c_str());
-        std::vector<double> bdn((size_t)nband * (nlay + 1)), bup((size_t)nband * (nlay + 1));
-        ck(ecckd_lbl_band_fluxes_lw_angles(dev.ctx(), nl.nangle, nlay, nwav, col.temperature_hl.data(), d_wn.as<double>(), d_dwn.as<double>(),
-                                       d_merged.ptr(), ECCKD_F64, nwav, nband, bbegin.data(), bend.data(), bdn.data(), bup.data(),
-                                       p_bnd_dn, p_bnd_up));
-        // [band][level] -> (half_level, band) and the broadband sums
-        std::vector<double> tdn((size_t)(nlay + 1) * nband), tup((size_t)(nlay + 1) * nband), sdn(nlay + 1, 0.0), sup(nlay + 1, 0.0);
-        for (int b = 0; b < nband; ++b)
-          for (int i = 0; i <= nlay; ++i) {
-            tdn[(size_t)i * nband + b] = bdn[(size_t)b * (nlay + 1) + i];
-            tup[(size_t)i * nband + b] = bup[(size_t)b * (nlay + 1) + i];
-            sdn[i] += bdn[(size_t)b * (nlay + 1) + i];
-            sup[i] += bup[(size_t)b * (nlay + 1) + i];
-          }
-        out.write_slice("mole_fraction_fl", oc, vmr_all);
-        out.write_slice("band_flux_dn_lw", oc, tdn); out.write_slice("band_flux_up_lw", oc, tup);
-        out.write_slice("flux_dn_lw", oc, sdn); out.write_slice("flux_up_lw", oc, sup);
-        if (p_bnd_dn) {
-          out.write_slice("spectral_flux_dn_surf_lw", oc, d_bnd_dn.download<double>());
-          out.write_slice("spectral_flux_up_toa_lw", oc, d_bnd_up.download<double>());
-        }
-      }
-      LOG("  column %d done\n", c + 1);
+// ---- default, and --merge-only: the gases of every column merged with their scalings, then written or carried through the
+// radiative transfer.  Fluxes [row][band][half_level], a row per angle (longwave: one row): flux 0 is the downwelling one
+// (shortwave: the direct beam, the whole downwelling flux too unless --rayleigh scatters), the last the upwelling one. ----
+int mode_default(const Args& a, Spectra& s) {
+  const Namelist& nl = a.nl;
+  const bool sw = a.sw, rayleigh = !a.rayleigh_file.empty(), bnd = nl.boundary_fluxes && !a.merge_only;
+  const Device& dev = s.dev;
+  const int nlay = s.g.nlay, nband = s.nband, nrow = sw ? s.nmu : 1;
+  const size_t nwav = s.g.nwav, nhl = (size_t)nlay + 1;
+  DevBuf d_merged(dev, (size_t)nlay * nwav * sizeof(double));
+  NcOut out(a.output);
+  define_flux_file(out, a, s, a.scenario, rayleigh);
+  const int nflux = rayleigh ? 3 : 2, dn = rayleigh ? 1 : 0, up = nflux - 1;
+  const int ngroup = rayleigh ? std::min(8, std::max(nrow, 1)) : 1;   // angles per call: the Rayleigh entry takes up to 8
+  DevBuf d_bnd[3];                                                    // the boundary fluxes of a call, [angle][wavenumber]
+  double* p_bnd[3] = {nullptr, nullptr, nullptr};
+  if (bnd)
+    for (int k = 0; k < nflux; ++k) { d_bnd[k].alloc(dev, (size_t)ngroup * nwav * sizeof(double)); p_bnd[k] = d_bnd[k].as<double>(); }
+  const std::string x = sw ? "_sw" : "_lw";
+
+  for (int c = s.g.c0; c <= s.g.c1; ++c) {
+    const Spectrum col = c == 0 ? s.g.first : read_spectrum(a.gases[0].path, c, false);
+    std::vector<double> vmr_all;   // [gas][level]
+    for (size_t ig = 0; ig < a.gases.size(); ++ig) {
+      const GasArg& gas = a.gases[ig];
+      NcIn f(gas.path);
+      double ref = -1.0;
+      std::vector<double> vmr, profile, vmr_out;
+      std::string mol;
+      read_od_meta(f, c, nlay, ref, vmr, mol);
+      gas_scaling(gas, gas.path, nlay, col.pressure_hl, ref, vmr, profile, vmr_out);
+      vmr_all.insert(vmr_all.end(), vmr_out.begin(), vmr_out.end());
+      DevOd od = read_od_dev(dev, f, c, nlay, nwav);
+      ck(ecckd_merge_spectrum_dev(dev.ctx(), nlay, nwav, od.buf.ptr(), od.type, nwav, profile.data(), ig == 0 ? 1 : 0,
+                                  d_merged.as<double>(), nwav));
+      ck(ecckd_synchronize(dev.ctx()));
     }
-    out.close();
-    return done(0);
+    const size_t oc = (size_t)(c - s.g.c0);
+    out.write_slice("pressure_hl", oc, col.pressure_hl);
+    if (!col.temperature_hl.empty()) out.write_slice("temperature_hl", oc, col.temperature_hl);
+    if (a.merge_only) {
+      out.write_slice("optical_depth", oc, d_merged.download<double>());
+      LOG("  column %d done\n", c + 1);
+      continue;
+    }
+    DevOd ray;                                   // --rayleigh: the spectrum that scatters, beside the merged absorbers
+    if (rayleigh) {
+      NcIn fr(a.rayleigh_file);
+      ray = read_od_dev(dev, fr, c, nlay, nwav);
+      ck(ecckd_synchronize(dev.ctx()));
+    } else if (!sw && col.temperature_hl.empty()) {
+      fail(ECCKD_PARAMETER_ERROR, "temperature_hl missing from %s", a.gases[0].path.c_str());
+    }
+    std::vector<double> t[3], sum[3], all[3], g[3];   // (row, half_level, band), (row, half_level), (row, wavenumber), one call's
+    for (int k = 0; k < nflux; ++k) { t[k].resize((size_t)nrow * nhl * nband); sum[k].resize((size_t)nrow * nhl); }
+    for (int m0 = 0; m0 < nrow; m0 += ngroup) {
+      const int nm = std::min(ngroup, nrow - m0);
+      for (int k = 0; k < nflux; ++k) g[k].assign((size_t)nm * nband * nhl, 0.0);
+      if (rayleigh)
+        ck(ecckd_lbl_band_fluxes_sw_rayleigh(dev.ctx(), nlay, nwav, nm, s.mu0.data() + m0, s.d_ssi.as<double>(), s.d_albedo.as<double>(), d_merged.ptr(),
+                                             ECCKD_F64, nwav, ray.buf.ptr(), ray.type, nwav, nband, s.bbegin.data(), s.bend.data(), g[0].data(),
+                                             g[1].data(), g[2].data(), p_bnd[0], p_bnd[1], p_bnd[2]));
+      else if (sw)
+        ck(ecckd_lbl_band_fluxes_sw_ex(dev.ctx(), nlay, nwav, s.mu0[m0], s.d_ssi.as<double>(), s.d_albedo.as<double>(), d_merged.ptr(), ECCKD_F64, nwav,
+                                       nband, s.bbegin.data(), s.bend.data(), g[0].data(), g[1].data(), p_bnd[0], p_bnd[1]));
+      else
+        ck(ecckd_lbl_band_fluxes_lw_angles(dev.ctx(), nl.nangle, nlay, nwav, col.temperature_hl.data(), s.d_wn.as<double>(), s.d_dwn.as<double>(),
+                                           d_merged.ptr(), ECCKD_F64, nwav, nband, s.bbegin.data(), s.bend.data(), g[0].data(), g[1].data(),
+                                           p_bnd[0], p_bnd[1]));
+      for (int k = 0; k < nflux; ++k) {
+        if (bnd) {
+          const std::vector<double> b = d_bnd[k].download<double>();
+          all[k].insert(all[k].end(), b.begin(), b.begin() + (size_t)nm * nwav);
+        }
+        for (int m = 0; m < nm; ++m)
+          bands_to_file_order(nband, nhl, &g[k][(size_t)m * nband * nhl], &t[k][(size_t)(m0 + m) * nhl * nband], &sum[k][(size_t)(m0 + m) * nhl]);
+      }
+    }
+    out.write_slice("mole_fraction_fl", oc, vmr_all);
+    out.write_slice(sw ? "band_flux_dn_direct_sw" : "band_flux_dn_lw", oc, t[0]);
+    if (rayleigh) out.write_slice("band_flux_dn_sw", oc, t[1]);
+    out.write_slice("band_flux_up" + x, oc, t[up]);
+    if (sw) out.write_slice("flux_dn_direct_sw", oc, sum[0]);
+    out.write_slice("flux_dn" + x, oc, sum[dn]); out.write_slice("flux_up" + x, oc, sum[up]);
+    if (bnd) {
+      out.write_slice(sw ? "spectral_flux_dn_direct_surf_sw" : "spectral_flux_dn_surf_lw", oc, all[0]);
+      if (rayleigh) out.write_slice("spectral_flux_dn_surf_sw", oc, all[1]);
+      out.write_slice("spectral_flux_up_toa" + x, oc, all[up]);
+    }
+    LOG("  column %d done\n", c + 1);
+  }
+  out.close();
+  return done(0);
+}
+
+}  // namespace
+
+inline int ckdmip_main(int argc, char** argv, bool sw) {
+  try {
+    const Args a = parse_args(argc, argv, sw);
+    if (!a.ckd_file.empty()) return mode_ckd(a);
+    if (a.gases.empty()) fail(ECCKD_PARAMETER_ERROR, "No spectrum files given");
+    Spectra s(a);
+    return a.table.empty() ? mode_default(a, s) : mode_scenarios(a, s);
   } catch (const Fatal& f) {
     std::fprintf(stderr, "*** Error: %s\n", f.msg.c_str());
     return f.code ? f.code : 1;

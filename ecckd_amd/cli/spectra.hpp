@@ -1,0 +1,228 @@
+// spectra.hpp - bin/lw_spectra and bin/sw_spectra (their header comments say what each one is): line-by-line fluxes of every
+// column (or of column `iprofile`) of a merged spectrum, written per wavenumber or, with `gpoints`, summed over the wavenumbers
+// of each g point, together with the optical depth.  One program: the shortwave tool has an angle dimension, the `ssi` input
+// and its own names; the longwave tool keeps the reference's quirks (src/ecckd/lw_spectra.cpp:31-275).
+#pragma once
+#include <algorithm>
+#include <memory>
+
+#include "tool.hpp"
+
+using namespace tool;
+
+namespace {
+
+// the optical depths of a merged spectrum as doubles on the host, from FLOAT or DOUBLE as they are on the device
+std::vector<double> download_od(const Device& dev, const Merged& m, size_t n) {
+  std::vector<double> od(n);
+  if (m.od_type() == ECCKD_F32) {
+    const std::vector<float> f = m.single.buf.download<float>();
+    std::copy(f.begin(), f.end(), od.begin());
+  } else {
+    ck(ecckd_d2h(dev.ctx(), od.data(), m.od_ptr(), od.size() * sizeof(double)));
+  }
+  return od;
+}
+
+std::vector<double> download_as_double(const DevBuf& b) {
+  const std::vector<float> f = b.download<float>();
+  return std::vector<double>(f.begin(), f.end());
+}
+
+}  // namespace
+
+inline int spectra_main(int argc, char** argv, bool sw) {
+  return run(argc, argv, [&](Config& config) -> int {
+    std::string output, ssi_file_name;
+    if (!config.read(output, "output")) fail(ECCKD_PARAMETER_ERROR, "\"output\" file not specified");
+    std::vector<double> mu0;
+    double surface_albedo = 0.15;
+    if (sw) {                                   // every check of the shortwave parameters before a device is opened
+      if (!config.read(ssi_file_name, "ssi")) fail(ECCKD_PARAMETER_ERROR, "\"ssi\" file not specified");
+      if (!config.read(mu0, "cos_solar_zenith_angle")) mu0 = {0.5};
+      if (mu0.empty() || mu0.size() > 8) fail(ECCKD_PARAMETER_ERROR, "cos_solar_zenith_angle must list 1 to 8 numbers");
+      for (double m : mu0)
+        if (!(m > 0.0 && m <= 1.0)) fail(ECCKD_PARAMETER_ERROR, "cos_solar_zenith_angle %g is not in (0, 1]", m);
+      config.read(surface_albedo, "surface_albedo");
+    }
+    const int nmu = sw ? (int)mu0.size() : 1;   // rows of fluxes per column
+    SearchPath paths;
+    paths.configure(config);
+    Device dev;
+
+    // ---- g points (:63-74) ----
+    std::vector<int32_t> g_point;
+    int ng = -1;
+    const bool have_gpoints = config.exist("gpoints");
+    if (have_gpoints) {
+      std::string gpoint_file;
+      config.read(gpoint_file, "gpoints");
+      const std::vector<double> g = NcIn(paths.find(gpoint_file)).read("g_point");
+      g_point.assign(g.begin(), g.end());
+      for (int32_t v : g_point) ng = std::max(ng, (int)v + 1);
+      if (ng < 1) fail(ECCKD_PARAMETER_ERROR, "%s assigns no wavenumber to a g point", gpoint_file.c_str());
+    }
+    std::vector<double> ssi;
+    if (sw) {
+      LOG("Reading %s\n", ssi_file_name.c_str());
+      ssi = NcIn(paths.find(ssi_file_name)).read("solar_spectral_irradiance");
+    }
+    int iprofile = -1;
+    const bool do_one_profile = config.read(iprofile, "iprofile");
+    int icol = do_one_profile ? iprofile : 0;
+    int ncol = 10000;
+    size_t irec = 0;
+
+    NcOut file(output);
+    ecckd_gmap* gmap = nullptr;
+    DevBuf d_wn, d_dwn, d_g, d_ssi, d_albedo, d_spec_dn, d_spec_up;
+    const std::string spec_name = have_gpoints ? "g_point" : "wavenumber";
+    const std::string bb_dn_name = sw ? "flux_dn_direct_sw" : "flux_dn_lw", bb_up_name = sw ? "flux_up_sw" : "flux_up_lw";
+    const std::string spec_dn_name = "spectral_" + bb_dn_name, spec_up_name = "spectral_" + bb_up_name;
+    bool is_first_profile = true, have_temperature = true;
+    while (icol < ncol) {
+      LOG("Profile %d\n", icol);
+      Merged m = read_merged_spectrum(dev, config, paths, icol, "");
+      ncol = m.first.ncol;
+      const int nlay = m.first.nlay;
+      const int nhl = nlay + 1;
+      const size_t nwav = m.first.nwav;
+      if (is_first_profile) {
+        is_first_profile = false;
+        if (have_gpoints && g_point.size() != nwav)
+          fail(ECCKD_PARAMETER_ERROR, "g_point has %zu elements, the spectrum %zu wavenumbers", g_point.size(), nwav);
+        if (sw && ssi.size() != nwav)
+          fail(ECCKD_PARAMETER_ERROR, "solar_spectral_irradiance has %zu points, the spectrum %zu", ssi.size(), nwav);
+        if (sw) have_temperature = !m.first.temperature_hl.empty();
+        std::vector<std::string> hl = {"column", "half_level"};
+        if (sw) hl.insert(hl.begin() + 1, "mu0");
+        std::vector<std::string> hl_spec = hl;
+        hl_spec.push_back(spec_name);
+        file.dim("column", 0);                                                                // unlimited (:132)
+        if (sw) file.dim("mu0", (size_t)nmu);
+        file.dim("level", (size_t)nlay);
+        file.dim("half_level", (size_t)nhl);
+        file.dim(spec_name, have_gpoints ? (size_t)ng : nwav);
+        file.dim("gas", m.vmr_fl.size());
+        if (sw) file.var("mu0", NC_FLOAT_T, {"mu0"}, "Cosine of solar zenith angle", "1");
+        file.var("pressure_hl", NC_FLOAT_T, {"column", "half_level"}, "Pressure at half levels", "Pa");
+        if (have_temperature) file.var("temperature_hl", NC_FLOAT_T, {"column", "half_level"}, "Temperature at half levels", "K");
+        if (!have_gpoints) {
+          file.var("wavenumber", NC_DOUBLE_T, {"wavenumber"});
+          file.deflate("wavenumber");
+          file.att("Wavenumber", "long_name", "wavenumber");
+          file.att("cm-1", "units", "wavenumber");
+        } else if (sw) {
+          file.var("solar_irradiance", NC_FLOAT_T, {"g_point"}, "Solar irradiance across each g point", "W m-2");
+        }
+        file.var("vmr_fl", NC_FLOAT_T, {"column", "gas", "level"}, "Volume mixing ratio", "mol mol-1");
+        file.att("The gases are listed in the global attribute \"molecules\".", "comment", "vmr_fl");
+        if (sw) {
+          file.var(bb_dn_name, NC_FLOAT_T, hl, "Downwelling direct shortwave flux", "W m-2");
+          file.var(bb_up_name, NC_FLOAT_T, hl, "Upwelling shortwave flux", "W m-2");
+        } else {
+          file.var(bb_dn_name, NC_FLOAT_T, hl, "Upwelling longwave flux", "W m-2");   // (sic, :169)
+          file.var(bb_up_name, NC_FLOAT_T, hl, "Upwelling longwave flux", "W m-2");
+        }
+        file.var("optical_depth", NC_FLOAT_T, {"column", "level", spec_name});
+        if (!have_gpoints) file.deflate("optical_depth");
+        file.att("Layer optical depth", "long_name", "optical_depth");
+        if (sw) {
+          file.var(spec_dn_name, NC_FLOAT_T, hl_spec,
+                   have_gpoints ? "Downwelling direct shortwave flux per g point" : "Downwelling direct shortwave spectral flux", "W m-2");
+          file.var(spec_up_name, NC_FLOAT_T, hl_spec, have_gpoints ? "Upwelling shortwave flux per g point" : "Upwelling shortwave spectral flux",
+                   "W m-2");
+        } else {
+          file.var(spec_dn_name, NC_FLOAT_T, hl_spec, "Downwelling longwave spectral flux", "W m-2");
+          file.var(spec_up_name, NC_FLOAT_T, hl_spec, "Upwelling longwave spectral flux", "W m-2");
+        }
+        file.att(history_line(argc, argv), "history");
+        std::string molecules = m.molecules;
+        std::replace(molecules.begin(), molecules.end(), ',', ' ');                           // :193
+        file.att(molecules, "molecules");
+        file.att(config.str(), "config");
+        file.end_define();
+        if (sw) file.write("mu0", mu0);
+        if (!have_gpoints) file.write("wavenumber", m.first.wavenumber_cm_1);
+        if (sw) {
+          d_ssi.upload(dev, ssi);
+          d_albedo.upload(dev, std::vector<double>(nwav, surface_albedo));
+        }
+        if (!sw || have_gpoints) {
+          d_wn.upload(dev, m.first.wavenumber_cm_1);
+          d_dwn.upload(dev, m.first.d_wavenumber_cm_1);
+        }
+        if (have_gpoints) {
+          d_g.upload(dev, g_point);
+          ck(ecckd_gmap_create(dev.ctx(), nwav, d_g.as<int32_t>(), ng, d_wn.as<double>(), d_dwn.as<double>(), &gmap));
+          if (sw) {
+            std::vector<double> solar((size_t)ng);
+            ck(ecckd_gmap_sum_rows(gmap, 1, d_ssi.ptr(), ECCKD_F64, nwav, solar.data()));
+            file.write("solar_irradiance", solar);
+          }
+        } else {
+          d_spec_dn.alloc(dev, (size_t)nhl * nwav * sizeof(float));
+          d_spec_up.alloc(dev, (size_t)nhl * nwav * sizeof(float));
+        }
+      }
+      file.write_slice("pressure_hl", irec, m.first.pressure_hl);
+      if (have_temperature) file.write_slice("temperature_hl", irec, m.first.temperature_hl);
+      std::vector<double> vmr;
+      for (const std::vector<double>& row : m.vmr_fl) vmr.insert(vmr.end(), row.begin(), row.end());
+      file.write_slice("vmr_fl", irec, vmr);
+
+      if (sw) LOG("  Performing shortwave radiative transfer for %d solar zenith angles\n", nmu);
+      else LOG("  Computing Planck function and performing longwave radiative transfer\n");
+      std::vector<double> bb_dn((size_t)nmu * nhl), bb_up((size_t)nmu * nhl);
+      const std::vector<double>& p = m.first.pressure_hl;
+      const std::vector<double>& t = m.first.temperature_hl;
+      if (!have_gpoints && sw) {
+        for (int s = 0; s < nmu; ++s) {                           // one angle at a time, on the device and on the host
+          ck(ecckd_lbl_spectral_fluxes_sw(dev.ctx(), nlay, nwav, 1, &mu0[s], d_ssi.as<double>(), d_albedo.as<double>(), m.od_ptr(),
+                                          m.od_type(), nwav, d_spec_dn.as<float>(), d_spec_up.as<float>(), nwav, &bb_dn[(size_t)s * nhl],
+                                          &bb_up[(size_t)s * nhl]));
+          file.write_subslice(spec_dn_name, irec, (size_t)s, download_as_double(d_spec_dn));
+          file.write_subslice(spec_up_name, irec, (size_t)s, download_as_double(d_spec_up));
+        }
+        file.write_slice(bb_dn_name, irec, bb_dn);
+        file.write_slice(bb_up_name, irec, bb_up);
+        file.write_slice("optical_depth", irec, download_od(dev, m, (size_t)nlay * nwav));
+      } else if (!have_gpoints) {
+        ck(ecckd_lbl_spectral_fluxes_lw(dev.ctx(), nlay, nwav, t.data(), d_wn.as<double>(), d_dwn.as<double>(), m.od_ptr(), m.od_type(), nwav,
+                                        d_spec_dn.as<float>(), d_spec_up.as<float>(), nwav, bb_dn.data(), bb_up.data()));
+        file.write_slice(bb_dn_name, irec, bb_dn);                                            // :231-232
+        file.write_slice(bb_up_name, irec, bb_up);
+        file.write_slice("optical_depth", irec, download_od(dev, m, (size_t)nlay * nwav));
+        file.write_slice(spec_dn_name, irec, download_as_double(d_spec_dn));
+        file.write_slice(spec_up_name, irec, download_as_double(d_spec_up));
+      } else {
+        std::vector<double> dn((size_t)nmu * nhl * ng), up((size_t)nmu * nhl * ng), od_g((size_t)nlay * ng), t_fl;
+        if (sw) {
+          ck(ecckd_lbl_gpoint_fluxes_sw(gmap, nlay, nmu, mu0.data(), d_ssi.as<double>(), d_albedo.as<double>(), m.od_ptr(), m.od_type(),
+                                        nwav, dn.data(), up.data(), bb_dn.data(), bb_up.data()));
+        } else {
+          ck(ecckd_lbl_gpoint_fluxes_lw(gmap, nlay, t.data(), m.od_ptr(), m.od_type(), nwav, dn.data(), up.data(), bb_dn.data(), bb_up.data()));
+          t_fl.resize(nlay);          // the Planck weight at the pressure-weighted full-level temperature (:242-251)
+          for (int l = 0; l < nlay; ++l) {
+            const double p_fl = 0.5 * (p[l] + p[l + 1]);
+            t_fl[l] = 0.5 * (t[l] * p[l] + t[l + 1] * p[l + 1]) / p_fl;
+          }
+        }
+        file.write_slice(bb_dn_name, irec, bb_dn);
+        file.write_slice(bb_up_name, irec, bb_up);
+        // averaged by transmission: the weight the Planck function at t_fl, or the solar spectral irradiance
+        ck(ecckd_average_to_gpoints(gmap, nlay, p.data(), sw ? nullptr : t_fl.data(), sw ? d_ssi.as<double>() : nullptr, m.od_ptr(), m.od_type(),
+                                    nwav, ECCKD_AVG_TRANSMISSION, 0.0, od_g.data(), nullptr, nullptr));
+        file.write_slice("optical_depth", irec, od_g);
+        file.write_slice(spec_dn_name, irec, dn);
+        file.write_slice(spec_up_name, irec, up);
+      }
+      if (do_one_profile) break;
+      ++icol;
+      ++irec;
+    }
+    if (gmap) ecckd_gmap_destroy(gmap);
+    file.close();
+    return 0;
+  });
+}

@@ -126,3 +126,19 @@ int slots_wait(hipStream_t stream, const double* h, int n, const char* what);
   } while (0)
 
 static inline size_t ecckd_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+namespace ecckd {
+
+// The context's scratch cut into N pieces of bytes[i] each, in order, every piece on a 256-byte boundary: the scratch grows
+// once (ensure_scratch), ptr[i] is where piece i begins.  The pieces live until the next call that takes the scratch.
+template <size_t N>
+inline int carve_scratch(ecckd_ctx* ctx, const size_t (&bytes)[N], void* (&ptr)[N]) {
+  size_t total = 0;
+  for (size_t i = 0; i < N; ++i) total += ecckd_align_up(bytes[i], 256);
+  ECCKD_CHECK(ensure_scratch(ctx, total));
+  char* q = (char*)ctx->scratch;
+  for (size_t i = 0; i < N; ++i) { ptr[i] = q; q += ecckd_align_up(bytes[i], 256); }
+  return ECCKD_OK;
+}
+
+}  // namespace ecckd

@@ -164,4 +164,21 @@ int bin_column_ranges(ecckd_ctx* ctx, int ng, bool mapped, int max_cols, int nbl
   return ECCKD_OK;
 }
 
+// The finished out[nsza][2][nhl][ng + 1] (direction 0 down, 1 up; longwave: nsza = 1) split into the caller's arrays: the g
+// points into h_dn, h_up [nsza][nhl][ng], and every wavenumber - the g points in order, then the points of none
+// (lw_spectra.cpp:231-232) - into the broadband rows h_bb_dn, h_bb_up [nsza][nhl], each of the two wanted or NULL.
+inline void unpack_gpoint_out(const double* out, int nsza, int nhl, int ng, double* h_dn, double* h_up, double* h_bb_dn, double* h_bb_up) {
+  for (int s = 0; s < nsza; ++s)
+    for (int l = 0; l < nhl; ++l) {
+      const double* dn = &out[((size_t)(s * 2) * nhl + l) * (ng + 1)];
+      const double* up = &out[((size_t)(s * 2 + 1) * nhl + l) * (ng + 1)];
+      double bdn = 0.0, bup = 0.0;
+      for (int g = 0; g <= ng; ++g) { bdn += dn[g]; bup += up[g]; }
+      const size_t o = (size_t)s * nhl + l;
+      for (int g = 0; g < ng; ++g) { h_dn[o * ng + g] = dn[g]; h_up[o * ng + g] = up[g]; }
+      if (h_bb_dn) h_bb_dn[o] = bdn;
+      if (h_bb_up) h_bb_up[o] = bup;
+    }
+}
+
 }  // namespace

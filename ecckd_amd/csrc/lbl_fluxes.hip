@@ -208,18 +208,23 @@ k_rt_sw_gpoints_rayleigh(int ncol, int nlay, int ng, double mu0, double minus_se
   }
 }
 
-int combine(ecckd_ctx* ctx, int nlay, int nband, const std::vector<BandChunk>& chunks, const double* d_partial,
-            double* h_flux_dn, double* h_flux_up) {
-  const int nhl = nlay + 1;
-  std::vector<double> part(chunks.size() * 2 * nhl);
-  if (!chunks.empty()) ECCKD_CHECK(ecckd_d2h(ctx, part.data(), d_partial, part.size() * sizeof(double)));
-  std::fill(h_flux_dn, h_flux_dn + (size_t)nband * nhl, 0.0);
-  if (h_flux_up) std::fill(h_flux_up, h_flux_up + (size_t)nband * nhl, 0.0);
-  for (size_t c = 0; c < chunks.size(); ++c)          // chunk order = wavenumber order within each band
-    for (int i = 0; i < nhl; ++i) {
-      h_flux_dn[(size_t)chunks[c].band * nhl + i] += part[c * 2 * nhl + i];
-      if (h_flux_up) h_flux_up[(size_t)chunks[c].band * nhl + i] += part[c * 2 * nhl + nhl + i];
-    }
+struct HostArray { const double* in; double* out; size_t n; };   // n doubles that go to the device (in) or come back (out)
+
+// The host arrays of a g-point transfer through the context's scratch, one piece per array in list order: the inputs copied
+// in, launch(d) with d[i] the piece of array i, the outputs copied back, the stream synchronised.
+template <size_t N, typename Launch>
+int through_scratch(ecckd_ctx* ctx, const HostArray (&a)[N], Launch launch) {
+  size_t bytes[N];
+  void* d[N];
+  for (size_t i = 0; i < N; ++i) bytes[i] = a[i].n * sizeof(double);
+  ECCKD_CHECK(ecckd::carve_scratch(ctx, bytes, d));
+  for (size_t i = 0; i < N; ++i)
+    if (a[i].in) ECCKD_HIP_CHECK(hipMemcpyAsync(d[i], a[i].in, bytes[i], hipMemcpyHostToDevice, ctx->stream));
+  launch((double* const*)d);
+  ECCKD_HIP_CHECK(hipGetLastError());
+  for (size_t i = 0; i < N; ++i)
+    if (a[i].out) ECCKD_HIP_CHECK(hipMemcpyAsync(a[i].out, d[i], bytes[i], hipMemcpyDeviceToHost, ctx->stream));
+  ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return ECCKD_OK;
 }
 
@@ -283,31 +288,23 @@ int ecckd_lbl_band_fluxes_lw_angles(ecckd_ctx* ctx, int nangle, int nlay, size_t
   ECCKD_CHECK(check_od(who, od_type, od_stride, nwav));
   ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
   const int nhl = nlay + 1;
-  std::vector<BandChunk> chunks;
-  ECCKD_CHECK(make_chunks(nullptr, nwav, nband, h_band_begin, h_band_end, chunks));
-  // wavenumbers outside every band carry no flux
-  if (d_surf_dn) ECCKD_HIP_CHECK(hipMemsetAsync(d_surf_dn, 0, nwav * sizeof(double), ctx->stream));
-  if (d_toa_up) ECCKD_HIP_CHECK(hipMemsetAsync(d_toa_up, 0, nwav * sizeof(double), ctx->stream));
+  BandRun r;
+  ECCKD_CHECK(band_start(r, ctx, nullptr, nwav, nband, h_band_begin, h_band_end, nhl, {{d_surf_dn, 1}, {d_toa_up, 1}},
+                         {h_flux_dn, h_flux_up}, 1));
   std::vector<double> hk;
   ECCKD_CHECK(make_hk(who, nhl, h_temperature_hl, hk));
   hk.insert(hk.end(), sec_wgt.begin(), sec_wgt.end());   // one upload: hk[nhl], then the angles
-  Buf d_chunks, d_hk, d_part;
-  if (!chunks.empty()) {
-    ECCKD_HIP_CHECK(hipMalloc(&d_chunks.p, chunks.size() * sizeof(BandChunk)));
-    ECCKD_HIP_CHECK(hipMalloc(&d_hk.p, hk.size() * sizeof(double)));
-    ECCKD_HIP_CHECK(hipMalloc(&d_part.p, chunks.size() * 2 * nhl * sizeof(double)));
-    ECCKD_CHECK(ecckd_h2d(ctx, d_chunks.p, chunks.data(), chunks.size() * sizeof(BandChunk)));
-    ECCKD_CHECK(ecckd_h2d(ctx, d_hk.p, hk.data(), hk.size() * sizeof(double)));
-    const size_t lds = (size_t)4 * 2 * nhl * sizeof(double);
-    with_od_type(od_type, [&](auto t) {
-      using OdT = decltype(t);
-      hipLaunchKernelGGL(k_lbl_fluxes_lw<OdT>, dim3((unsigned)chunks.size()), dim3(LBL_THREADS), lds, ctx->stream, nang,
-                         (const double*)d_hk.p + nhl, nlay, od_stride, (const BandChunk*)d_chunks.p, (const double*)d_hk.p,
-                         d_wavenumber, d_d_wavenumber, (const OdT*)d_od, (double*)d_part.p, d_surf_dn, d_toa_up);
-    });
-    ECCKD_HIP_CHECK(hipGetLastError());
-  }
-  return combine(ctx, nlay, nband, chunks, (const double*)d_part.p, h_flux_dn, h_flux_up);
+  if (r.chunks.empty()) return ECCKD_OK;
+  ECCKD_CHECK(band_device(r, hk.data(), hk.size(), nullptr, 0, r.chunks.size() * 2 * nhl, 0));
+  const size_t lds = (size_t)4 * 2 * nhl * sizeof(double);
+  with_od_type(od_type, [&](auto t) {
+    using OdT = decltype(t);
+    hipLaunchKernelGGL(k_lbl_fluxes_lw<OdT>, dim3((unsigned)r.chunks.size()), dim3(LBL_THREADS), lds, ctx->stream, nang,
+                       r.d_tab0 + nhl, nlay, od_stride, r.d_chunks, r.d_tab0, d_wavenumber, d_d_wavenumber, (const OdT*)d_od,
+                       r.d_part, d_surf_dn, d_toa_up);
+  });
+  ECCKD_HIP_CHECK(hipGetLastError());
+  return band_collect(r, 1, nullptr, {h_flux_dn, h_flux_up});
 }
 
 int ecckd_lbl_band_fluxes_sw(ecckd_ctx* ctx, int nlay, size_t nwav, double cos_sza, const double* d_ssi,
@@ -329,25 +326,19 @@ int ecckd_lbl_band_fluxes_sw_ex(ecckd_ctx* ctx, int nlay, size_t nwav, double co
   ECCKD_CHECK(check_od("ecckd_lbl_band_fluxes_sw", od_type, od_stride, nwav));
   ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
   const int nhl = nlay + 1;
-  std::vector<BandChunk> chunks;
-  ECCKD_CHECK(make_chunks(nullptr, nwav, nband, h_band_begin, h_band_end, chunks));
-  if (d_surf_dn) ECCKD_HIP_CHECK(hipMemsetAsync(d_surf_dn, 0, nwav * sizeof(double), ctx->stream));
-  if (d_toa_up) ECCKD_HIP_CHECK(hipMemsetAsync(d_toa_up, 0, nwav * sizeof(double), ctx->stream));
-  Buf d_chunks, d_part;
-  if (!chunks.empty()) {
-    ECCKD_HIP_CHECK(hipMalloc(&d_chunks.p, chunks.size() * sizeof(BandChunk)));
-    ECCKD_HIP_CHECK(hipMalloc(&d_part.p, chunks.size() * 2 * nhl * sizeof(double)));
-    ECCKD_CHECK(ecckd_h2d(ctx, d_chunks.p, chunks.data(), chunks.size() * sizeof(BandChunk)));
-    const size_t lds = (size_t)4 * 2 * nhl * sizeof(double);
-    with_od_type(od_type, [&](auto t) {
-      using OdT = decltype(t);
-      hipLaunchKernelGGL(k_lbl_fluxes_sw<OdT>, dim3((unsigned)chunks.size()), dim3(LBL_THREADS), lds, ctx->stream, nlay, od_stride,
-                         (const BandChunk*)d_chunks.p, cos_sza, d_ssi, d_albedo, (const OdT*)d_od, (double*)d_part.p, d_surf_dn,
-                         d_toa_up);
-    });
-    ECCKD_HIP_CHECK(hipGetLastError());
-  }
-  return combine(ctx, nlay, nband, chunks, (const double*)d_part.p, h_flux_dn_direct, h_flux_up);
+  BandRun r;
+  ECCKD_CHECK(band_start(r, ctx, nullptr, nwav, nband, h_band_begin, h_band_end, nhl, {{d_surf_dn, 1}, {d_toa_up, 1}},
+                         {h_flux_dn_direct, h_flux_up}, 1));
+  if (r.chunks.empty()) return ECCKD_OK;
+  ECCKD_CHECK(band_device(r, nullptr, 0, nullptr, 0, r.chunks.size() * 2 * nhl, 0));
+  const size_t lds = (size_t)4 * 2 * nhl * sizeof(double);
+  with_od_type(od_type, [&](auto t) {
+    using OdT = decltype(t);
+    hipLaunchKernelGGL(k_lbl_fluxes_sw<OdT>, dim3((unsigned)r.chunks.size()), dim3(LBL_THREADS), lds, ctx->stream, nlay, od_stride,
+                       r.d_chunks, cos_sza, d_ssi, d_albedo, (const OdT*)d_od, r.d_part, d_surf_dn, d_toa_up);
+  });
+  ECCKD_HIP_CHECK(hipGetLastError());
+  return band_collect(r, 1, nullptr, {h_flux_dn_direct, h_flux_up});   // h_flux_up may be NULL
 }
 
 // The fluxes of a CKD model's g points from the optical depths and Planck functions run_ckd wrote (the `--ckd` mode of the
@@ -362,25 +353,12 @@ int ecckd_rt_lw_gpoints(ecckd_ctx* ctx, int nangle, int ncol, int nlay, int ng, 
   std::vector<double> sw;
   ECCKD_CHECK(lw_angle_table("ecckd_rt_lw_gpoints", nangle, &nsec, sw));
   const size_t nl = (size_t)ncol * nlay * ng, nh = (size_t)ncol * (nlay + 1) * ng;
-  const size_t b_sw = ecckd_align_up(sw.size() * sizeof(double), 256), b_l = ecckd_align_up(nl * sizeof(double), 256),
-               b_h = ecckd_align_up(nh * sizeof(double), 256);
-  ECCKD_CHECK(ecckd::ensure_scratch(ctx, b_sw + b_l + 3 * b_h));
-  char* q = (char*)ctx->scratch;
-  double* d_sw = (double*)q; q += b_sw;
-  double* d_od = (double*)q; q += b_l;
-  double* d_pl = (double*)q; q += b_h;
-  double* d_dn = (double*)q; q += b_h;
-  double* d_up = (double*)q;
-  ECCKD_HIP_CHECK(hipMemcpyAsync(d_sw, sw.data(), sw.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ECCKD_HIP_CHECK(hipMemcpyAsync(d_od, h_od, nl * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ECCKD_HIP_CHECK(hipMemcpyAsync(d_pl, h_planck_hl, nh * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_rt_lw_gpoints, dim3((unsigned)(((size_t)ncol * ng + 255) / 256)), dim3(256), 0, ctx->stream, ncol, nlay, ng, nsec, d_sw,
-                     d_pl, d_od, d_dn, d_up);
-  ECCKD_HIP_CHECK(hipGetLastError());
-  ECCKD_HIP_CHECK(hipMemcpyAsync(h_flux_dn, d_dn, nh * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ECCKD_HIP_CHECK(hipMemcpyAsync(h_flux_up, d_up, nh * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  return ECCKD_OK;
+  const HostArray a[] = {{sw.data(), nullptr, sw.size()}, {h_od, nullptr, nl}, {h_planck_hl, nullptr, nh}, {nullptr, h_flux_dn, nh},
+                         {nullptr, h_flux_up, nh}};
+  return through_scratch(ctx, a, [&](double* const* d) {
+    hipLaunchKernelGGL(k_rt_lw_gpoints, dim3((unsigned)(((size_t)ncol * ng + 255) / 256)), dim3(256), 0, ctx->stream, ncol, nlay, ng, nsec,
+                       d[0], d[2], d[1], d[3], d[4]);
+  });
 }
 
 int ecckd_rt_sw_gpoints(ecckd_ctx* ctx, int ncol, int nlay, int ng, double cos_sza, double albedo, const double* h_incoming,
@@ -389,23 +367,11 @@ int ecckd_rt_sw_gpoints(ecckd_ctx* ctx, int ncol, int nlay, int ng, double cos_s
   ECCKD_REQUIRE(cos_sza > 0.0, "ecckd_rt_sw_gpoints: cos_sza must be positive");
   ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
   const size_t nl = (size_t)ncol * nlay * ng, nh = (size_t)ncol * (nlay + 1) * ng, ni = (size_t)ncol * ng;
-  const size_t b_i = ecckd_align_up(ni * sizeof(double), 256), b_l = ecckd_align_up(nl * sizeof(double), 256),
-               b_h = ecckd_align_up(nh * sizeof(double), 256);
-  ECCKD_CHECK(ecckd::ensure_scratch(ctx, b_i + b_l + 2 * b_h));
-  char* q = (char*)ctx->scratch;
-  double* d_in = (double*)q; q += b_i;
-  double* d_od = (double*)q; q += b_l;
-  double* d_dn = (double*)q; q += b_h;
-  double* d_up = (double*)q;
-  ECCKD_HIP_CHECK(hipMemcpyAsync(d_in, h_incoming, ni * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ECCKD_HIP_CHECK(hipMemcpyAsync(d_od, h_od, nl * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_rt_sw_gpoints, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, ctx->stream, ncol, nlay, ng, cos_sza, albedo, d_in,
-                     d_od, d_dn, d_up);
-  ECCKD_HIP_CHECK(hipGetLastError());
-  ECCKD_HIP_CHECK(hipMemcpyAsync(h_flux_dn, d_dn, nh * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ECCKD_HIP_CHECK(hipMemcpyAsync(h_flux_up, d_up, nh * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  return ECCKD_OK;
+  const HostArray a[] = {{h_incoming, nullptr, ni}, {h_od, nullptr, nl}, {nullptr, h_flux_dn, nh}, {nullptr, h_flux_up, nh}};
+  return through_scratch(ctx, a, [&](double* const* d) {
+    hipLaunchKernelGGL(k_rt_sw_gpoints, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, ctx->stream, ncol, nlay, ng, cos_sza, albedo, d[0],
+                       d[1], d[2], d[3]);
+  });
 }
 
 int ecckd_rt_sw_gpoints_rayleigh(ecckd_ctx* ctx, int ncol, int nlay, int ng, double cos_sza, double albedo, const double* h_incoming,
@@ -418,27 +384,12 @@ int ecckd_rt_sw_gpoints_rayleigh(ecckd_ctx* ctx, int ncol, int nlay, int ng, dou
   ECCKD_CHECK(sw_angle_table(who, 1, &cos_sza, h_ang));
   ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
   const size_t nl = (size_t)ncol * nlay * ng, nh = (size_t)ncol * (nlay + 1) * ng, ni = (size_t)ncol * ng;
-  const size_t b_i = ecckd_align_up(ni * sizeof(double), 256), b_l = ecckd_align_up(nl * sizeof(double), 256),
-               b_h = ecckd_align_up(nh * sizeof(double), 256);
-  ECCKD_CHECK(ecckd::ensure_scratch(ctx, b_i + 2 * b_l + 3 * b_h));
-  char* q = (char*)ctx->scratch;
-  double* d_in = (double*)q; q += b_i;
-  double* d_od = (double*)q; q += b_l;
-  double* d_ray = (double*)q; q += b_l;
-  double* d_dir = (double*)q; q += b_h;
-  double* d_dn = (double*)q; q += b_h;
-  double* d_up = (double*)q;
-  ECCKD_HIP_CHECK(hipMemcpyAsync(d_in, h_incoming, ni * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ECCKD_HIP_CHECK(hipMemcpyAsync(d_od, h_od, nl * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ECCKD_HIP_CHECK(hipMemcpyAsync(d_ray, h_od_rayleigh, nl * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_rt_sw_gpoints_rayleigh, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, ctx->stream, ncol, nlay, ng, h_ang[0],
-                     h_ang[LBL_MAX_SZA], albedo, d_in, d_od, d_ray, d_dir, d_dn, d_up);
-  ECCKD_HIP_CHECK(hipGetLastError());
-  ECCKD_HIP_CHECK(hipMemcpyAsync(h_flux_dn_direct, d_dir, nh * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ECCKD_HIP_CHECK(hipMemcpyAsync(h_flux_dn, d_dn, nh * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ECCKD_HIP_CHECK(hipMemcpyAsync(h_flux_up, d_up, nh * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  return ECCKD_OK;
+  const HostArray a[] = {{h_incoming, nullptr, ni}, {h_od, nullptr, nl}, {h_od_rayleigh, nullptr, nl}, {nullptr, h_flux_dn_direct, nh},
+                         {nullptr, h_flux_dn, nh}, {nullptr, h_flux_up, nh}};
+  return through_scratch(ctx, a, [&](double* const* d) {
+    hipLaunchKernelGGL(k_rt_sw_gpoints_rayleigh, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, ctx->stream, ncol, nlay, ng, h_ang[0],
+                       h_ang[LBL_MAX_SZA], albedo, d[0], d[1], d[2], d[3], d[4], d[5]);
+  });
 }
 
 }  // extern "C"

@@ -138,52 +138,25 @@ int ecckd_lbl_band_fluxes_sw_rayleigh(ecckd_ctx* ctx, int nlay, size_t nwav, int
   const size_t lds = (size_t)4 * RAYLEIGH_FLUXES * nhl * sizeof(double);
   ECCKD_REQUIRE(lds <= 64 * 1024, "%s: nlay = %d needs %zu bytes of LDS for the level sums (64 KB at most)", who, nlay, lds);
   ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
-  std::vector<BandChunk> chunks;
-  ECCKD_CHECK(make_chunks(who, nwav, nband, h_band_begin, h_band_end, chunks));
-  // wavenumbers outside every band carry no flux
-  for (double* p : {d_surf_dn_direct, d_surf_dn, d_toa_up})
-    if (p) ECCKD_HIP_CHECK(hipMemsetAsync(p, 0, (size_t)nsza * nwav * sizeof(double), ctx->stream));
-  const size_t nslab = (size_t)nsza * nband * nhl;
-  std::fill(h_flux_dn_direct, h_flux_dn_direct + nslab, 0.0);
-  std::fill(h_flux_dn, h_flux_dn + nslab, 0.0);
-  std::fill(h_flux_up, h_flux_up + nslab, 0.0);
-  if (chunks.empty()) return ECCKD_OK;
-  const size_t nchunk = chunks.size(), grid = rayleigh_grid(ctx, nchunk);
-  const size_t npart = nchunk * nsza * RAYLEIGH_FLUXES * nhl;
-  const size_t b_ang = ecckd_align_up(sizeof(h_ang), 256), b_chunks = ecckd_align_up(nchunk * sizeof(BandChunk), 256),
-               b_part = ecckd_align_up(npart * sizeof(double), 256),
-               b_ws = grid * RAYLEIGH_SLOTS * nhl * LBL_THREADS * sizeof(double);
-  ECCKD_CHECK(ecckd::ensure_scratch(ctx, b_ang + b_chunks + b_part + b_ws));
-  char* q = (char*)ctx->scratch;
-  double* d_ang = (double*)q; q += b_ang;
-  BandChunk* d_chunks = (BandChunk*)q; q += b_chunks;
-  double* d_part = (double*)q; q += b_part;
-  double* d_ws = (double*)q;
-  ECCKD_HIP_CHECK(hipMemcpyAsync(d_ang, h_ang, sizeof(h_ang), hipMemcpyHostToDevice, ctx->stream));
-  ECCKD_CHECK(ecckd_h2d(ctx, d_chunks, chunks.data(), nchunk * sizeof(BandChunk)));
+  BandRun r;
+  const size_t rows = (size_t)nsza;
+  ECCKD_CHECK(band_start(r, ctx, who, nwav, nband, h_band_begin, h_band_end, nhl, {{d_surf_dn_direct, rows}, {d_surf_dn, rows}, {d_toa_up, rows}},
+                         {h_flux_dn_direct, h_flux_dn, h_flux_up}, rows));
+  if (r.chunks.empty()) return ECCKD_OK;
+  const size_t nchunk = r.chunks.size(), grid = rayleigh_grid(ctx, nchunk);
+  ECCKD_CHECK(band_device(r, h_ang, 2 * LBL_MAX_SZA, nullptr, 0, nchunk * nsza * RAYLEIGH_FLUXES * nhl,
+                          grid * RAYLEIGH_SLOTS * nhl * LBL_THREADS * sizeof(double)));
   with_od_type(abs_type, [&](auto ta) {
     with_od_type(ray_type, [&](auto tr) {
       using AbsT = decltype(ta);
       using RayT = decltype(tr);
       hipLaunchKernelGGL((k_lbl_fluxes_sw_rayleigh<AbsT, RayT>), dim3((unsigned)grid), dim3(LBL_THREADS), lds, ctx->stream, nlay, nsza,
-                         (int)nchunk, nwav, abs_stride, ray_stride, (const BandChunk*)d_chunks, (const double*)d_ang, d_ssi, d_albedo,
-                         (const AbsT*)d_od_abs, (const RayT*)d_od_ray, d_ws, d_part, d_surf_dn_direct, d_surf_dn, d_toa_up);
+                         (int)nchunk, nwav, abs_stride, ray_stride, r.d_chunks, r.d_tab0, d_ssi, d_albedo, (const AbsT*)d_od_abs,
+                         (const RayT*)d_od_ray, (double*)r.d_work, r.d_part, d_surf_dn_direct, d_surf_dn, d_toa_up);
     });
   });
   ECCKD_HIP_CHECK(hipGetLastError());
-  std::vector<double> part(npart);
-  ECCKD_CHECK(ecckd_d2h(ctx, part.data(), d_part, npart * sizeof(double)));
-  for (size_t c = 0; c < nchunk; ++c)                  // chunk order = wavenumber order within each band
-    for (int s = 0; s < nsza; ++s) {
-      const double* p = &part[(c * nsza + s) * RAYLEIGH_FLUXES * nhl];
-      const size_t to = ((size_t)s * nband + chunks[c].band) * nhl;
-      for (size_t i = 0; i < nhl; ++i) {
-        h_flux_dn_direct[to + i] += p[i];
-        h_flux_dn[to + i] += p[nhl + i];
-        h_flux_up[to + i] += p[2 * nhl + i];
-      }
-    }
-  return ECCKD_OK;
+  return band_collect(r, nsza, nullptr, {h_flux_dn_direct, h_flux_dn, h_flux_up});
 }
 
 }  // extern "C"

@@ -111,13 +111,12 @@ int run(ecckd_ctx* ctx, int nlay, size_t nwav, const double* h_temperature_hl, c
   ECCKD_CHECK(make_hk("line-by-line g-point fluxes", nhl, h_temperature_hl, hk));
   const TileGrid grid = tile_grid(nwav);
   const int tpb = grid.tpb, nblk = grid.nblk;
-  const size_t b_hk = ecckd_align_up((size_t)nhl * sizeof(double), 256);
-  const size_t b_out = ecckd_align_up((size_t)2 * nhl * out_cols * sizeof(double), 256);
-  const size_t b_part = ecckd_align_up((size_t)nblk * 2 * nhl * std::min(max_cols, out_cols) * sizeof(double), 256);
-  ECCKD_CHECK(ecckd::ensure_scratch(ctx, b_hk + b_out + b_part));
-  double* d_hk = (double*)ctx->scratch;
-  double* d_out = (double*)((char*)ctx->scratch + b_hk);
-  double* d_part = (double*)((char*)ctx->scratch + b_hk + b_out);
+  void* d[3];
+  ECCKD_CHECK(ecckd::carve_scratch(ctx, {(size_t)nhl * sizeof(double), (size_t)2 * nhl * out_cols * sizeof(double),
+                                         (size_t)nblk * 2 * nhl * std::min(max_cols, out_cols) * sizeof(double)}, d));
+  double* d_hk = (double*)d[0];
+  double* d_out = (double*)d[1];
+  double* d_part = (double*)d[2];
   ECCKD_CHECK(ecckd_h2d(ctx, d_hk, hk.data(), (size_t)nhl * sizeof(double)));
   ECCKD_HIP_CHECK(hipMemsetAsync(d_out, 0, (size_t)2 * nhl * out_cols * sizeof(double), ctx->stream));
   const bool spectral = d_spec_dn != nullptr;
@@ -152,15 +151,7 @@ int ecckd_lbl_gpoint_fluxes_lw(ecckd_gmap* gmap, int nlay, const double* h_tempe
   const int nhl = nlay + 1, ng = gmap->ng;
   std::vector<double> out;
   ECCKD_CHECK(run(ctx, nlay, gmap->n, h_temperature_hl, d_wn, d_dwn, d_od, od_type, od_stride, d_g, ng, nullptr, nullptr, 0, out));
-  for (int l = 0; l < nhl; ++l) {
-    const double* dn = &out[(size_t)l * (ng + 1)];
-    const double* up = &out[(size_t)(nhl + l) * (ng + 1)];
-    double bdn = 0.0, bup = 0.0;                   // every wavenumber: the g points in order, then the points of none (:231-232)
-    for (int g = 0; g <= ng; ++g) { bdn += dn[g]; bup += up[g]; }
-    for (int g = 0; g < ng; ++g) { h_flux_dn[(size_t)l * ng + g] = dn[g]; h_flux_up[(size_t)l * ng + g] = up[g]; }
-    if (h_bb_dn) h_bb_dn[l] = bdn;
-    if (h_bb_up) h_bb_up[l] = bup;
-  }
+  unpack_gpoint_out(out.data(), 1, nhl, ng, h_flux_dn, h_flux_up, h_bb_dn, h_bb_up);
   return ECCKD_OK;
 }
 
@@ -177,10 +168,7 @@ int ecckd_lbl_spectral_fluxes_lw(ecckd_ctx* ctx, int nlay, size_t nwav, const do
   std::vector<double> out;
   ECCKD_CHECK(run(ctx, nlay, nwav, h_temperature_hl, d_wavenumber, d_d_wavenumber, d_od, od_type, od_stride, nullptr, 0, d_flux_dn,
                   d_flux_up, flux_stride, out));
-  for (int l = 0; l < nhl; ++l) {
-    if (h_bb_dn) h_bb_dn[l] = out[l];
-    if (h_bb_up) h_bb_up[l] = out[nhl + l];
-  }
+  unpack_gpoint_out(out.data(), 1, nhl, 0, nullptr, nullptr, h_bb_dn, h_bb_up);   // one column: the broadband sums
   return ECCKD_OK;
 }
 

@@ -154,13 +154,12 @@ int run(ecckd_ctx* ctx, int nlay, size_t nwav, int nsza, const double* h_ang /* 
   const int tpb = grid.tpb, nblk = grid.nblk;
   const size_t nrows = (size_t)nsza * 2 * nhl;
   const size_t max_acc = (size_t)ang_per_launch * 2 * nhl * std::min(cols_per_launch, out_cols);
-  const size_t b_out = ecckd_align_up(nrows * out_cols * sizeof(double), 256);
-  const size_t b_part = ecckd_align_up((size_t)nblk * max_acc * sizeof(double), 256);
-  const size_t b_ang = ecckd_align_up((size_t)2 * LBL_MAX_SZA * sizeof(double), 256);
-  ECCKD_CHECK(ecckd::ensure_scratch(ctx, b_ang + b_out + b_part));
-  double* d_ang = (double*)ctx->scratch;
-  double* d_out = (double*)((char*)ctx->scratch + b_ang);
-  double* d_part = (double*)((char*)ctx->scratch + b_ang + b_out);
+  void* d[3];
+  ECCKD_CHECK(ecckd::carve_scratch(ctx, {(size_t)2 * LBL_MAX_SZA * sizeof(double), nrows * out_cols * sizeof(double),
+                                         (size_t)nblk * max_acc * sizeof(double)}, d));
+  double* d_ang = (double*)d[0];
+  double* d_out = (double*)d[1];
+  double* d_part = (double*)d[2];
   ECCKD_CHECK(ecckd_h2d(ctx, d_ang, h_ang, 2 * LBL_MAX_SZA * sizeof(double)));
   ECCKD_HIP_CHECK(hipMemsetAsync(d_out, 0, nrows * out_cols * sizeof(double), ctx->stream));
   const bool spectral = d_spec_dn != nullptr;
@@ -207,17 +206,7 @@ int ecckd_lbl_gpoint_fluxes_sw(ecckd_gmap* gmap, int nlay, int nsza, const doubl
   const int nhl = nlay + 1, ng = gmap->ng;
   std::vector<double> out;
   ECCKD_CHECK(run(ctx, nlay, gmap->n, nsza, h_ang, d_ssi, d_albedo, d_od, od_type, od_stride, d_g, ng, nullptr, nullptr, 0, out));
-  for (int s = 0; s < nsza; ++s)
-    for (int l = 0; l < nhl; ++l) {
-      const double* dn = &out[((size_t)(s * 2) * nhl + l) * (ng + 1)];
-      const double* up = &out[((size_t)(s * 2 + 1) * nhl + l) * (ng + 1)];
-      double bdn = 0.0, bup = 0.0;                 // every wavenumber: the g points in order, then the points of none
-      for (int g = 0; g <= ng; ++g) { bdn += dn[g]; bup += up[g]; }
-      const size_t o = (size_t)s * nhl + l;
-      for (int g = 0; g < ng; ++g) { h_flux_dn_direct[o * ng + g] = dn[g]; h_flux_up[o * ng + g] = up[g]; }
-      if (h_bb_dn) h_bb_dn[o] = bdn;
-      if (h_bb_up) h_bb_up[o] = bup;
-    }
+  unpack_gpoint_out(out.data(), nsza, nhl, ng, h_flux_dn_direct, h_flux_up, h_bb_dn, h_bb_up);
   return ECCKD_OK;
 }
 
@@ -235,11 +224,7 @@ int ecckd_lbl_spectral_fluxes_sw(ecckd_ctx* ctx, int nlay, size_t nwav, int nsza
   std::vector<double> out;
   ECCKD_CHECK(run(ctx, nlay, nwav, nsza, h_ang, d_ssi, d_albedo, d_od, od_type, od_stride, nullptr, 0, d_flux_dn_direct,
                   d_flux_up, flux_stride, out));
-  for (int s = 0; s < nsza; ++s)
-    for (int l = 0; l < nhl; ++l) {
-      if (h_bb_dn) h_bb_dn[(size_t)s * nhl + l] = out[(size_t)(s * 2) * nhl + l];
-      if (h_bb_up) h_bb_up[(size_t)s * nhl + l] = out[(size_t)(s * 2 + 1) * nhl + l];
-    }
+  unpack_gpoint_out(out.data(), nsza, nhl, 0, nullptr, nullptr, h_bb_dn, h_bb_up);   // one column: the broadband sums
   return ECCKD_OK;
 }
 

@@ -34,6 +34,7 @@
 #include "rt_device.hpp"
 
 #include <algorithm>
+#include <initializer_list>
 #include <vector>
 
 namespace ecckd {
@@ -127,11 +128,6 @@ using ecckd::kPlanckOverBoltzmann; using ecckd::make_hk;   // rt_device.hpp
 
 struct BandChunk { long long i1, i2; int band; int pad; };
 
-struct Buf {
-  void* p = nullptr;
-  ~Buf() { if (p) (void)hipFree(p); }
-};
-
 // one chunk per LBL_THREADS wavenumbers of a band, in wavenumber order; `who` (or NULL) prefixes the message
 inline int make_chunks(const char* who, size_t nwav, int nband, const int64_t* b0, const int64_t* b1, std::vector<BandChunk>& chunks) {
   for (int b = 0; b < nband; ++b) {
@@ -141,6 +137,71 @@ inline int make_chunks(const char* who, size_t nwav, int nband, const int64_t* b
     for (long long i = b0[b]; i <= b1[b]; i += LBL_THREADS)
       chunks.push_back(BandChunk{i, std::min<long long>(i + LBL_THREADS - 1, b1[b]), b, 0});
   }
+  return ECCKD_OK;
+}
+
+// The host path of the band-flux entries (lbl_fluxes.hip, lbl_scenarios.hip, lbl_fluxes_sw_rayleigh.hip): an entry checks its
+// own arguments, then  band_start - band_device - per launch { its kernel, band_collect }.  Which launches there are, and the
+// kernel, stay with the entry; the workspace is the context's scratch, kept for the next call.
+struct BandRun {
+  ecckd_ctx* ctx = nullptr;
+  int nband = 0;
+  size_t nhl = 0;
+  std::vector<BandChunk> chunks;
+  std::vector<double> part;                // a launch's partials on the host
+  const BandChunk* d_chunks = nullptr;     // band_device: the chunk table, the entry's two small tables, the partials of
+  const double* d_tab0 = nullptr;          // one launch and the workspace of its kernel
+  const double* d_tab1 = nullptr;
+  double* d_part = nullptr;
+  void* d_work = nullptr;
+};
+struct DevRows { double* p; size_t rows; };   // a per-wavenumber device output [rows][nwav], or p = NULL
+
+// The band ranges checked and cut into chunks; the device outputs zeroed (wavenumbers outside every band carry no flux) and the
+// host outputs h_out, [h_rows][nband][nhl] each or NULL.  With every band empty that is the result: the stream is
+// synchronised and r.chunks stays empty.
+inline int band_start(BandRun& r, ecckd_ctx* ctx, const char* who, size_t nwav, int nband, const int64_t* b0, const int64_t* b1, size_t nhl,
+                      std::initializer_list<DevRows> d_out, std::initializer_list<double*> h_out, size_t h_rows) {
+  r.ctx = ctx; r.nband = nband; r.nhl = nhl;
+  ECCKD_CHECK(make_chunks(who, nwav, nband, b0, b1, r.chunks));
+  for (const DevRows& d : d_out)
+    if (d.p) ECCKD_HIP_CHECK(hipMemsetAsync(d.p, 0, d.rows * nwav * sizeof(double), ctx->stream));
+  for (double* h : h_out)
+    if (h) std::fill(h, h + h_rows * nband * nhl, 0.0);
+  if (r.chunks.empty()) ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return ECCKD_OK;
+}
+
+// The chunk table and the entry's small host tables (n0, n1 doubles; 0: none) on the device, with room for npart doubles of
+// partials and work_bytes of workspace: one carve of the scratch
+inline int band_device(BandRun& r, const double* h_tab0, size_t n0, const double* h_tab1, size_t n1, size_t npart, size_t work_bytes) {
+  void* d[5];
+  ECCKD_CHECK(ecckd::carve_scratch(r.ctx, {r.chunks.size() * sizeof(BandChunk), n0 * sizeof(double), n1 * sizeof(double),
+                                           npart * sizeof(double), work_bytes}, d));
+  r.d_chunks = (const BandChunk*)d[0]; r.d_tab0 = (const double*)d[1]; r.d_tab1 = (const double*)d[2];
+  r.d_part = (double*)d[3]; r.d_work = d[4];
+  ECCKD_CHECK(ecckd_h2d(r.ctx, d[0], r.chunks.data(), r.chunks.size() * sizeof(BandChunk)));
+  ECCKD_CHECK(ecckd_h2d(r.ctx, d[1], h_tab0, n0 * sizeof(double)));
+  return ecckd_h2d(r.ctx, d[2], h_tab1, n1 * sizeof(double));
+}
+
+// After a launch: its partials d_part[chunk][nslot][nflux][nhl] read back and added to the nflux host arrays h_flux (NULL: that
+// flux is not wanted) at (slot_row[slot] * nband + band) * nhl; slot_row = NULL: slot k is row k.  The chunks are the outer
+// loop, in order - wavenumber order within each band - so every output element is summed in one fixed order, bit for bit
+// whatever the launch split.
+inline int band_collect(BandRun& r, int nslot, const size_t* slot_row, std::initializer_list<double*> h_flux) {
+  const size_t nflux = h_flux.size(), nhl = r.nhl;
+  r.part.resize(r.chunks.size() * nslot * nflux * nhl);
+  ECCKD_CHECK(ecckd_d2h(r.ctx, r.part.data(), r.d_part, r.part.size() * sizeof(double)));
+  for (size_t c = 0; c < r.chunks.size(); ++c)
+    for (int k = 0; k < nslot; ++k) {
+      const double* p = &r.part[(c * nslot + k) * nflux * nhl];
+      const size_t o = ((slot_row ? slot_row[k] : (size_t)k) * r.nband + r.chunks[c].band) * nhl;
+      for (double* h : h_flux) {
+        if (h) for (size_t i = 0; i < nhl; ++i) h[o + i] += p[i];
+        p += nhl;
+      }
+    }
   return ECCKD_OK;
 }
 

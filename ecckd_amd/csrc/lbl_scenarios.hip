@@ -269,17 +269,6 @@ int check_gases(const char* who, int ngas, const void* const* d_od, const int* o
   return ECCKD_OK;
 }
 
-// partial[chunk][nslot][2*nhl] of one launch -> the rows of its slots; chunk order = wavenumber order within each band
-void add_partials(const std::vector<BandChunk>& chunks, const std::vector<double>& part, int nslot, int nhl, int nband,
-                  const std::vector<size_t>& slot_row /* [nslot]: index of the slot's [nband][nhl] block */, double* h_dn, double* h_up) {
-  for (size_t c = 0; c < chunks.size(); ++c)
-    for (int k = 0; k < nslot; ++k) {
-      const double* p = &part[(c * nslot + k) * 2 * nhl];
-      const size_t o = (slot_row[k] * nband + chunks[c].band) * nhl;
-      for (int i = 0; i < nhl; ++i) { h_dn[o + i] += p[i]; h_up[o + i] += p[nhl + i]; }
-    }
-}
-
 template <int A>
 void launch_sw(ecckd_ctx* ctx, unsigned nblk, size_t lds, int nlay, int ngas, const GasRows& gr, int ns, const double* d_scale,
                const BandChunk* d_chunks, const double* d_mu, const double* d_msec, const double* d_ssi, const double* d_albedo,
@@ -318,40 +307,25 @@ int ecckd_lbl_band_fluxes_lw_scenarios(ecckd_ctx* ctx, int nangle, int nlay, siz
   ECCKD_CHECK(make_hk(who, nhl, h_temperature_hl, hk));
   hk.insert(hk.end(), sec_wgt.begin(), sec_wgt.end());   // one upload: hk[nhl], then the angles
   ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
-  std::vector<BandChunk> chunks;
-  ECCKD_CHECK(make_chunks(who, nwav, nband, h_band_begin, h_band_end, chunks));
-  // wavenumbers outside every band carry no flux
-  if (d_surf_dn) ECCKD_HIP_CHECK(hipMemsetAsync(d_surf_dn, 0, (size_t)nscen * nwav * sizeof(double), ctx->stream));
-  if (d_toa_up) ECCKD_HIP_CHECK(hipMemsetAsync(d_toa_up, 0, (size_t)nscen * nwav * sizeof(double), ctx->stream));
-  std::fill(h_flux_dn, h_flux_dn + (size_t)nscen * nband * nhl, 0.0);
-  std::fill(h_flux_up, h_flux_up + (size_t)nscen * nband * nhl, 0.0);
-  if (chunks.empty()) return ecckd_synchronize(ctx);
+  BandRun r;
+  ECCKD_CHECK(band_start(r, ctx, who, nwav, nband, h_band_begin, h_band_end, nhl, {{d_surf_dn, (size_t)nscen}, {d_toa_up, (size_t)nscen}},
+                         {h_flux_dn, h_flux_up}, nscen));
+  if (r.chunks.empty()) return ECCKD_OK;
   // the scenarios evenly over ceil(nscen / T) launches
   const int nlaunch = (nscen + T - 1) / T, per = (nscen + nlaunch - 1) / nlaunch;
-  const size_t nscale = (size_t)nscen * ngas * nlay;
-  Buf d_chunks, d_hk, d_scale, d_part;
-  ECCKD_HIP_CHECK(hipMalloc(&d_chunks.p, chunks.size() * sizeof(BandChunk)));
-  ECCKD_HIP_CHECK(hipMalloc(&d_hk.p, hk.size() * sizeof(double)));
-  ECCKD_HIP_CHECK(hipMalloc(&d_scale.p, nscale * sizeof(double)));
-  ECCKD_HIP_CHECK(hipMalloc(&d_part.p, chunks.size() * per * 2 * nhl * sizeof(double)));
-  ECCKD_CHECK(ecckd_h2d(ctx, d_chunks.p, chunks.data(), chunks.size() * sizeof(BandChunk)));
-  ECCKD_CHECK(ecckd_h2d(ctx, d_hk.p, hk.data(), hk.size() * sizeof(double)));
-  ECCKD_CHECK(ecckd_h2d(ctx, d_scale.p, h_scale, nscale * sizeof(double)));
-  std::vector<double> part;
+  ECCKD_CHECK(band_device(r, hk.data(), hk.size(), h_scale, (size_t)nscen * ngas * nlay, r.chunks.size() * per * 2 * nhl, 0));
   std::vector<size_t> slot_row;
   for (int s0 = 0; s0 < nscen; s0 += per) {
     const int ns = std::min(per, nscen - s0);
     const size_t lds = (size_t)4 * ns * 2 * nhl * sizeof(double);
-    hipLaunchKernelGGL(k_lbl_scenarios_lw, dim3((unsigned)chunks.size()), dim3(LBL_THREADS), lds, ctx->stream, nang,
-                       (const double*)d_hk.p + nhl, nlay, ngas, gr, ns, (const double*)d_scale.p + (size_t)s0 * ngas * nlay,
-                       (const BandChunk*)d_chunks.p, (const double*)d_hk.p, d_wavenumber, d_d_wavenumber, (double*)d_part.p,
-                       d_surf_dn ? d_surf_dn + (size_t)s0 * nwav : nullptr, d_toa_up ? d_toa_up + (size_t)s0 * nwav : nullptr, nwav);
+    hipLaunchKernelGGL(k_lbl_scenarios_lw, dim3((unsigned)r.chunks.size()), dim3(LBL_THREADS), lds, ctx->stream, nang, r.d_tab0 + nhl,
+                       nlay, ngas, gr, ns, r.d_tab1 + (size_t)s0 * ngas * nlay, r.d_chunks, r.d_tab0, d_wavenumber, d_d_wavenumber,
+                       r.d_part, d_surf_dn ? d_surf_dn + (size_t)s0 * nwav : nullptr, d_toa_up ? d_toa_up + (size_t)s0 * nwav : nullptr,
+                       nwav);
     ECCKD_HIP_CHECK(hipGetLastError());
-    part.resize(chunks.size() * ns * 2 * nhl);
-    ECCKD_CHECK(ecckd_d2h(ctx, part.data(), d_part.p, part.size() * sizeof(double)));
     slot_row.resize(ns);
     for (int k = 0; k < ns; ++k) slot_row[k] = (size_t)(s0 + k);
-    add_partials(chunks, part, ns, nhl, nband, slot_row, h_flux_dn, h_flux_up);
+    ECCKD_CHECK(band_collect(r, ns, slot_row.data(), {h_flux_dn, h_flux_up}));
   }
   return ECCKD_OK;
 }
@@ -373,14 +347,11 @@ int ecckd_lbl_band_fluxes_sw_scenarios(ecckd_ctx* ctx, int nlay, size_t nwav, in
                 (int)(LS_SW_LDS / 64) - 1);
   const int nhl = nlay + 1;
   ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
-  std::vector<BandChunk> chunks;
-  ECCKD_CHECK(make_chunks(who, nwav, nband, h_band_begin, h_band_end, chunks));
   const size_t nslots = (size_t)nscen * nsza;
-  if (d_surf_dn_direct) ECCKD_HIP_CHECK(hipMemsetAsync(d_surf_dn_direct, 0, nslots * nwav * sizeof(double), ctx->stream));
-  if (d_toa_up) ECCKD_HIP_CHECK(hipMemsetAsync(d_toa_up, 0, nslots * nwav * sizeof(double), ctx->stream));
-  std::fill(h_flux_dn_direct, h_flux_dn_direct + nslots * nband * nhl, 0.0);
-  std::fill(h_flux_up, h_flux_up + nslots * nband * nhl, 0.0);
-  if (chunks.empty()) return ecckd_synchronize(ctx);
+  BandRun r;
+  ECCKD_CHECK(band_start(r, ctx, who, nwav, nband, h_band_begin, h_band_end, nhl, {{d_surf_dn_direct, nslots}, {d_toa_up, nslots}},
+                         {h_flux_dn_direct, h_flux_up}, nslots));
+  if (r.chunks.empty()) return ECCKD_OK;
   // the split (see the header): scenarios first, angles only where one scenario's angles do not fit
   int ang_per = nsza, scen_per = 1;
   if (nsza <= T) {
@@ -391,16 +362,8 @@ int ecckd_lbl_band_fluxes_sw_scenarios(ecckd_ctx* ctx, int nlay, size_t nwav, in
     const int nl = (nsza + T - 1) / T;
     ang_per = (nsza + nl - 1) / nl;
   }
-  const size_t nscale = (size_t)nscen * ngas * nlay;
-  Buf d_chunks, d_ang, d_scale, d_part;
-  ECCKD_HIP_CHECK(hipMalloc(&d_chunks.p, chunks.size() * sizeof(BandChunk)));
-  ECCKD_HIP_CHECK(hipMalloc(&d_ang.p, sizeof(h_ang)));
-  ECCKD_HIP_CHECK(hipMalloc(&d_scale.p, nscale * sizeof(double)));
-  ECCKD_HIP_CHECK(hipMalloc(&d_part.p, chunks.size() * scen_per * ang_per * 2 * nhl * sizeof(double)));
-  ECCKD_CHECK(ecckd_h2d(ctx, d_chunks.p, chunks.data(), chunks.size() * sizeof(BandChunk)));
-  ECCKD_CHECK(ecckd_h2d(ctx, d_ang.p, h_ang, sizeof(h_ang)));
-  ECCKD_CHECK(ecckd_h2d(ctx, d_scale.p, h_scale, nscale * sizeof(double)));
-  std::vector<double> part;
+  ECCKD_CHECK(band_device(r, h_ang, 2 * LBL_MAX_SZA, h_scale, (size_t)nscen * ngas * nlay,
+                          r.chunks.size() * scen_per * ang_per * 2 * nhl, 0));
   std::vector<size_t> slot_row;
   const size_t scen_stride = (size_t)nsza * nwav;
   for (int s0 = 0; s0 < nscen; s0 += scen_per) {
@@ -411,23 +374,21 @@ int ecckd_lbl_band_fluxes_sw_scenarios(ecckd_ctx* ctx, int nlay, size_t nwav, in
       const size_t first = ((size_t)s0 * nsza + a0) * nwav;
       double* surf = d_surf_dn_direct ? d_surf_dn_direct + first : nullptr;
       double* toa = d_toa_up ? d_toa_up + first : nullptr;
-      const double* d_mu = (const double*)d_ang.p + a0;
-      const double* d_msec = (const double*)d_ang.p + LBL_MAX_SZA + a0;
-      const double* d_sc = (const double*)d_scale.p + (size_t)s0 * ngas * nlay;
+      const double* d_mu = r.d_tab0 + a0;
+      const double* d_msec = r.d_tab0 + LBL_MAX_SZA + a0;
+      const double* d_sc = r.d_tab1 + (size_t)s0 * ngas * nlay;
 #define LS_SW(A)                                                                                                           \
   case A:                                                                                                                  \
-    launch_sw<A>(ctx, (unsigned)chunks.size(), lds, nlay, ngas, gr, ns, d_sc, (const BandChunk*)d_chunks.p, d_mu, d_msec, d_ssi,  \
-                 d_albedo, (double*)d_part.p, surf, toa, scen_stride, nwav);                                               \
+    launch_sw<A>(ctx, (unsigned)r.chunks.size(), lds, nlay, ngas, gr, ns, d_sc, r.d_chunks, d_mu, d_msec, d_ssi, d_albedo, \
+                 r.d_part, surf, toa, scen_stride, nwav);                                                                  \
     break
       switch (na) { LS_SW(1); LS_SW(2); LS_SW(3); LS_SW(4); LS_SW(5); LS_SW(6); LS_SW(7); LS_SW(8); }
 #undef LS_SW
       ECCKD_HIP_CHECK(hipGetLastError());
-      part.resize(chunks.size() * ns * na * 2 * nhl);
-      ECCKD_CHECK(ecckd_d2h(ctx, part.data(), d_part.p, part.size() * sizeof(double)));
       slot_row.resize((size_t)ns * na);
       for (int k = 0; k < ns; ++k)
         for (int a = 0; a < na; ++a) slot_row[(size_t)k * na + a] = (size_t)(s0 + k) * nsza + a0 + a;
-      add_partials(chunks, part, ns * na, nhl, nband, slot_row, h_flux_dn_direct, h_flux_up);
+      ECCKD_CHECK(band_collect(r, ns * na, slot_row.data(), {h_flux_dn_direct, h_flux_up}));
     }
   }
   return ECCKD_OK;

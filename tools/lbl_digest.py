@@ -1,5 +1,5 @@
 """SHA-256 of everything the line-by-line flux entry points return, at the smallest shapes where each piece of their kernels can
-go wrong (csrc/lbl_fluxes.hip, lbl_gpoint_fluxes.hip, lbl_gpoint_fluxes_sw.hip, lbl_scenarios.hip): a change that is meant to
+go wrong (csrc/lbl_fluxes.hip, lbl_gpoint_fluxes.hip, lbl_gpoint_fluxes_sw.hip, lbl_scenarios.hip, lbl_fluxes_sw_rayleigh.hip), and of every band entry with every band empty: a change that is meant to
 leave their arithmetic alone is run once on the build before it and once on the build after it, on the same GPU, and every
 digest has to be equal.  profiles/lbl_digests.json holds the output of the build it was committed with; a ROCm math-library
 update may change digests legitimately, which is why this is a tool and not a test.
@@ -109,6 +109,31 @@ with api.Context(0) as ctx:
         for alb in (None, albedo):
             out[f"band_sw {nlay} {nwav} {dtype} albedo={alb is not None}"] = digest(*api.lbl_band_fluxes_sw(
                 ctx, 0.5, ssi, dev(od), begin, end, albedo=alb, boundary=True))
+
+        # Rayleigh scattering: 1 and 5 angles; the Rayleigh spectrum float32 beside a float64 absorber, then the reverse
+        ray = syn.optical_depth(np, p, wn, syn.SEED_BASE + 7, nlines=6, column_scale=0.3, lo=250.0, hi=50000.0)
+        for nsza in (1, 5):
+            for abs_dt, ray_dt in (("float64", "float32"), ("float32", "float64")):
+                out[f"band_sw_rayleigh {nlay} {nwav} nsza={nsza} abs={abs_dt} ray={ray_dt}"] = digest(*api.lbl_band_fluxes_sw_rayleigh(
+                    ctx, ANGLES[nsza], ssi, dev(od.astype(abs_dt)), dev(ray.astype(ray_dt)), begin, end, albedo=albedo, boundary=True))
+
+    # Rayleigh scattering per g point, host arrays: ncol 2, nlay 16, ng 7
+    rs = np.random.RandomState(5)
+    odg, rayg, inc = rs.uniform(0.0, 0.4, (2, 16, 7)), rs.uniform(0.0, 0.05, (2, 16, 7)), rs.uniform(10.0, 300.0, (2, 7))
+    rayg[:, 1, 2] = 0.0
+    out["rt_sw_gpoints_rayleigh 2 16 7"] = digest(*api.rt_sw_gpoints_rayleigh(ctx, 0.5, 0.15, inc, odg, rayg))
+
+    # every band empty (begin 0, end -1): each band entry returns zeros, on the host and in the boundary spectra
+    nlay, nwav = 3, 300
+    begin, end = np.zeros(2, dtype=np.int64), -np.ones(2, dtype=np.int64)
+    p, wn, dwn, od = column(nlay, nwav, "float64", seed=5, lo=250.0, hi=50000.0, column_scale=3.0)
+    t_hl, d_wn, d_dwn, d_od, one = syn.temperature_profile(p), dev(wn), dev(dwn), dev(od), np.ones((2, 1, nlay))
+    ssi = dev(syn.solar_spectral_irradiance(wn, dwn))
+    out["empty band_lw"] = digest(*api.lbl_band_fluxes_lw(ctx, t_hl, d_wn, d_dwn, d_od, begin, end, boundary=True))
+    out["empty band_sw"] = digest(*api.lbl_band_fluxes_sw(ctx, 0.5, ssi, d_od, begin, end, boundary=True))
+    out["empty band_sw_rayleigh"] = digest(*api.lbl_band_fluxes_sw_rayleigh(ctx, ANGLES[3], ssi, d_od, d_od, begin, end, boundary=True))
+    out["empty scenarios_lw"] = digest(*api.lbl_band_fluxes_lw_scenarios(ctx, t_hl, d_wn, d_dwn, [d_od], one, begin, end, boundary=True))
+    out["empty scenarios_sw"] = digest(*api.lbl_band_fluxes_sw_scenarios(ctx, ANGLES[3], ssi, [d_od], one, begin, end, boundary=True))
 
     # scenarios: a FLOAT and a DOUBLE gas; longwave 11 scenarios (two launches at 8 slots); shortwave 7 scenarios with 1 and 5
     # angles (3 scenarios per launch); 130 layers: 5 longwave scenarios per launch, and the 8 angles of one shortwave scenario
