@@ -1327,24 +1327,46 @@ k_opt_sum_cost(const double* __restrict__ jcol, size_t ncol, const double* __res
 
 }  // namespace
 
-struct ecckd_opt {
+// ---------------------------------------------------------------------------------------
+// The host side.  The tables a handle uploads are built by opt_tables.cpp, the L-BFGS history is lbfgs_history.hpp; here:
+// the handle and its memory, the launches, and the entry points.
+#include "lbfgs_history.hpp"
+#include "opt_tables.hpp"
+
+#include <memory>
+#include <string>
+
+namespace ot = ecckd::opt_tables;
+
+static_assert(ot::MIN_X == MIN_X && ot::ACCEL_GRAVITY == ECCKD_ACCEL_GRAVITY && ot::SPECIFIC_HEAT_AIR == ECCKD_SPECIFIC_HEAT_AIR,
+              "opt_tables.hpp repeats these constants");
+static_assert(ecckd::LbfgsHistory::M == LB_M, "lbfgs_history.hpp repeats the number of pairs");
+
+// Pinned, host-coherent result slots that the kernels write and the host watches (pageable read-backs cost ~30 us each through
+// the runtime's staging path): the L-BFGS dot products (LB_NPART of them), then step / d.d / d.g of a trial point, the cost of
+// an evaluation, and the all-reduced cost.
+constexpr int PIN_LB_DOTS = 0, PIN_LB_STEP = 64, PIN_COST = 70, PIN_REDUCED_COST = 71, PIN_SLOTS = 80;
+static_assert(PIN_LB_DOTS + LB_NPART <= PIN_LB_STEP, "the dot products overlap the step slots");
+
+struct ecckd_opt : ot::Layout {
   ecckd_ctx* ctx = nullptr;
-  int ng = 0, nt = 0, np = 0, nband = 0, ngas = 0, nlay = 0, nent = 0;
-  size_t nx = 0, nk = 0, ncol = 0, ncell = 0, nnode_active = 0;
-  std::vector<GasInfo> gases;       // in k order: active gases first
-  std::vector<int> user_to_k;       // user gas index -> position in `gases`
   ecckd_opt_config cfg{};
-  bool have_prior = false;
-  bool have_boundary = false;
-  bool do_sw = false;
-  int eval_ray_ent = -1;   // >= 0 only inside ecckd_run_ckd
+  // evaluation mode of the forward kernel, set for the length of a diagnostic pass only (opt_diagnostic_pass)
+  int eval_ray_ent = -1;   // >= 0: entry of the Rayleigh term, added after the clamp (ecckd_run_ckd)
   int eval_keep_negative = 0;
+  double* d_od_out = nullptr; double* d_flux_out = nullptr;   // non-NULL marks a diagnostic pass
+  // Every other device block of the handle comes from alloc(), which records it; opt_free releases what is recorded.  The
+  // named members below are views for the launch sites.
+  std::vector<void*> blocks;
+  template <typename T> hipError_t alloc(T** p, size_t count) {
+    void* v = nullptr;
+    const hipError_t e = hipMalloc(&v, std::max<size_t>(count, 1) * sizeof(T));
+    if (e == hipSuccess) blocks.push_back(v);
+    *p = (T*)v;
+    return e;
+  }
   double* d_rel = nullptr;   // relative-to CKD fluxes [ncol][2][nhl][ng]
-  int ray_ent = -1;        // entry index of the Rayleigh pseudo gas
   double* d_mu0 = nullptr;
-  // host copies
-  std::vector<double> h_k0, h_kmin, h_kmax;
-  // device
   double *d_k = nullptr, *d_x = nullptr, *d_xprior = nullptr, *d_grad = nullptr, *d_dtau = nullptr;
   double *d_jcol = nullptr, *d_jb = nullptr;
   int* d_ent_idx = nullptr; double* d_ent_coef = nullptr; int* d_band = nullptr;
@@ -1353,25 +1375,19 @@ struct ecckd_opt {
   int *d_run_order = nullptr, *d_run_r0 = nullptr, *d_run_last = nullptr, *d_node_run0 = nullptr;   // K8b gather: the runs
   double* d_run_sum = nullptr;                      // [nrun][nchunk][64]
   unsigned gradient_grid = 0, gather_grid = 0;
-  int grad_nchunk = 1, grad_nslot = 0, gather_nslot = 0;
+  int grad_nslot = 0, gather_nslot = 0;
   size_t grad_nrun = 0;
   double *d_planck = nullptr, *d_semis = nullptr, *d_conv = nullptr, *d_lw = nullptr;
   double *d_hr = nullptr, *d_fdn = nullptr, *d_fup = nullptr, *d_sfds = nullptr, *d_sfut = nullptr;
   int *d_ref_ptr = nullptr, *d_ref_cell = nullptr; double* d_ref_coef = nullptr;
   int *d_node_gas = nullptr, *d_st_nb = nullptr;    // K9: gas of each active node, its stencil's neighbours [nnode][27]
   double *d_st_w = nullptr, *d_inv_sigma2 = nullptr;
-  double* d_od_out = nullptr; double* d_flux_out = nullptr;
   unsigned grad_blocks = 0;
-  // pinned host staging: per-profile costs, per-node prior terms, L-BFGS scalars (pageable read-backs cost
-  // ~30 us each through the runtime's staging path)
-  // pinned, host-coherent result slots that the kernels write and the host watches: [0, 64) L-BFGS dot products, [64, 67)
-  // step / d.d / d.g, [70] the cost of an evaluation
-  double* h_pin = nullptr;
+  double* h_pin = nullptr;    // the PIN_SLOTS pinned slots
   double* d_pin = nullptr;    // the same memory as the device sees it
-  double* h_rb = nullptr;     // = h_pin
   // device L-BFGS workspace (allocated by ecckd_opt_minimize)
   double *d_xmin = nullptr, *d_xmax = nullptr, *d_xn = nullptr, *d_gn = nullptr, *d_dir = nullptr, *d_q = nullptr;
-  double *d_S = nullptr, *d_Y = nullptr, *d_part = nullptr, *d_sc = nullptr;
+  double *d_S = nullptr, *d_Y = nullptr, *d_part = nullptr;
   // profile-sharded optimisation: sum of [gradient, J] over the ranks (ecckd_opt_set_allreduce)
   ecckd_allreduce_fn reduce_fn = nullptr;
   void* reduce_user = nullptr;
@@ -1390,42 +1406,69 @@ struct ecckd_opt {
 
 namespace {
 
-template <typename T>
-int upload(ecckd_ctx* ctx, T** d, const std::vector<T>& h) {
-  ECCKD_HIP_CHECK(hipMalloc((void**)d, std::max<size_t>(h.size(), 1) * sizeof(T)));
-  if (!h.empty())
-    ECCKD_HIP_CHECK(hipMemcpyAsync(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-  ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  return ECCKD_OK;
-}
-
 void opt_free(ecckd_opt* o) {
   if (!o) return;
   if (o->ctx) (void)hipStreamSynchronize(o->ctx->stream);
-  void* ptrs[] = {o->d_k, o->d_x, o->d_xprior, o->d_grad, o->d_dtau, o->d_jcol, o->d_jb, o->d_ent_idx, o->d_ent_coef,
-                  o->d_band, o->d_band_ptr, o->d_band_g, o->d_node_order, o->d_run_order, o->d_run_r0, o->d_run_last, o->d_node_run0,
-                  o->d_run_sum, o->d_planck, o->d_semis, o->d_conv, o->d_lw, o->d_hr, o->d_fdn, o->d_fup, o->d_sfds,
-                  o->d_sfut, o->d_ref_ptr, o->d_ref_cell, o->d_ref_coef, o->d_node_gas, o->d_st_nb, o->d_st_w, o->d_inv_sigma2, o->d_od_out, o->d_flux_out, o->d_xmin, o->d_xmax,
-                  o->d_xn, o->d_gn, o->d_dir, o->d_q, o->d_S, o->d_Y, o->d_part, o->d_sc, o->d_mu0, o->d_rel};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
+  for (void* p : o->blocks) (void)hipFree(p);
+  if (o->d_od_out) (void)hipFree(o->d_od_out);
+  if (o->d_flux_out) (void)hipFree(o->d_flux_out);
   if (o->h_pin) (void)hipHostFree(o->h_pin);
   for (hipEvent_t e : o->tev)
     if (e) (void)hipEventDestroy(e);
   delete o;
 }
 
-// CkdModel::calc_planck_function, ckd_model.cpp:1121-1145
-void planck_lut(int ntp, const double* tpl, const double* pf, int ng, double t, double* out) {
-  const double d_t = tpl[1] - tpl[0], t0 = tpl[0];
-  const double tindex0 = (t - t0) / d_t;
-  if (tindex0 >= 0) {
-    int it0 = std::min((int)tindex0, ntp - 2);
-    const double w1 = tindex0 - it0, w0 = 1.0 - w1;
-    for (int g = 0; g < ng; ++g) out[g] = w0 * pf[(size_t)it0 * ng + g] + w1 * pf[(size_t)(it0 + 1) * ng + g];
-  } else {
-    for (int g = 0; g < ng; ++g) out[g] = (t / t0) * pf[g];
-  }
+// a handle under construction: every early return frees it
+struct OptDelete { void operator()(ecckd_opt* o) const { opt_free(o); } };
+using OptPtr = std::unique_ptr<ecckd_opt, OptDelete>;
+
+// (the sources are pageable vectors: the copy has left them when the stream has drained)
+template <typename T>
+int upload(ecckd_opt* o, T** d, const std::vector<T>& h) {
+  ECCKD_HIP_CHECK(o->alloc(d, h.size()));
+  if (!h.empty())
+    ECCKD_HIP_CHECK(hipMemcpyAsync(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, o->ctx->stream));
+  ECCKD_HIP_CHECK(hipStreamSynchronize(o->ctx->stream));
+  return ECCKD_OK;
+}
+
+int opt_upload_tables(ecckd_opt* o, const ot::Tables& t) {
+  int rc = ECCKD_OK;
+  auto up = [&](auto** d, const auto& h) { if (rc == ECCKD_OK) rc = upload(o, d, h); };
+  up(&o->d_k, o->k0);
+  up(&o->d_ent_idx, t.ent_idx); up(&o->d_ent_coef, t.ent_coef); up(&o->d_band, t.band); up(&o->d_band_ptr, t.band_ptr); up(&o->d_band_g, t.band_g);
+  up(&o->d_planck, t.planck); up(&o->d_semis, t.semis); up(&o->d_conv, t.conv); up(&o->d_lw, t.lw);
+  up(&o->d_hr, t.hr); up(&o->d_fdn, t.fdn); up(&o->d_fup, t.fup);
+  if (o->have_boundary) { up(&o->d_sfds, t.sfds); up(&o->d_sfut, t.sfut); }
+  if (o->do_sw) up(&o->d_mu0, t.mu0);
+  if (!t.rel.empty()) up(&o->d_rel, t.rel);
+  up(&o->d_ref_ptr, t.ref_ptr); up(&o->d_ref_cell, t.ref_cell); up(&o->d_ref_coef, t.ref_coef); up(&o->d_node_order, t.node_order);
+  up(&o->d_run_order, t.run_order); up(&o->d_run_r0, t.run_r0); up(&o->d_run_last, t.run_last); up(&o->d_node_run0, t.node_run0);
+  up(&o->d_node_gas, t.node_gas); up(&o->d_st_nb, t.st_nb); up(&o->d_st_w, t.st_w); up(&o->d_inv_sigma2, t.inv_sigma2);
+  return rc;
+}
+
+// the launch sizes of K8b and of the element-wise kernels, the work buffers and the pinned slots
+int opt_alloc_work(ecckd_opt* o, const ot::Tables& t) {
+  // every virtual block resident at once where that fits (8 blocks of 4 waves per CU), else a grid-stride loop
+  auto grid_of = [&](size_t nslot) {
+    unsigned gsz = (unsigned)std::min<size_t>((nslot + K8B_WAVES - 1) / K8B_WAVES, (size_t)std::max(o->ctx->num_cu, 1) * 8);
+    return std::max(8u, (gsz + 7) / 8 * 8);
+  };
+  o->gradient_grid = grid_of(t.node_order.size());
+  o->gather_grid = grid_of(t.run_order.size());
+  o->grad_nslot = (int)t.node_order.size();
+  o->gather_nslot = (int)t.run_order.size();
+  o->grad_nrun = t.run_r0.size();
+  o->grad_blocks = (unsigned)((o->nx + 255) / 256);
+  if (o->alloc(&o->d_x, o->nx) != hipSuccess || o->alloc(&o->d_xprior, o->nx) != hipSuccess ||
+      o->alloc(&o->d_grad, o->nx + 1) != hipSuccess || o->alloc(&o->d_dtau, o->ncell * o->ng) != hipSuccess ||
+      o->alloc(&o->d_run_sum, std::max<size_t>(o->grad_nrun, 1) * o->grad_nchunk * 64) != hipSuccess ||
+      o->alloc(&o->d_jcol, o->ncol) != hipSuccess || o->alloc(&o->d_jb, o->nnode_active * (size_t)o->grad_nchunk) != hipSuccess)
+    return ecckd::fail(ECCKD_OUT_OF_MEMORY, "ecckd_opt_create: device allocation failed");
+  ECCKD_HIP_CHECK(hipHostMalloc((void**)&o->h_pin, PIN_SLOTS * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+  ECCKD_HIP_CHECK(hipHostGetDevicePointer((void**)&o->d_pin, o->h_pin, 0));
+  return ECCKD_OK;
 }
 
 }  // namespace
@@ -1436,501 +1479,24 @@ int ecckd_opt_create(ecckd_ctx* ctx, const ecckd_opt_model* m, int nscene, const
                      const ecckd_opt_config* cfg, ecckd_opt** out) {
   ECCKD_REQUIRE(ctx && m && scenes && cfg && out && nscene > 0, "ecckd_opt_create: NULL/empty argument");
   *out = nullptr;
-  ECCKD_REQUIRE(m->ng > 0 && m->ng <= 1024 && m->nt >= 2 && m->np >= 2 && m->ngas > 0 && m->gases &&
-                    m->log_pressure && m->temperature && m->iband_per_g,
-                "ecckd_opt_create: bad model dimensions (ng=%d nt=%d np=%d ngas=%d)", m->ng, m->nt, m->np, m->ngas);
-  const bool do_sw = m->solar_irradiance != nullptr;
-  ECCKD_REQUIRE(do_sw || (m->ntp >= 2 && m->temperature_planck && m->planck_function),
-                "ecckd_opt_create: Planck look-up table missing");
-  ECCKD_REQUIRE(!m->logarithmic_interpolation,
-                "ecckd_opt_create: logarithmic LUT interpolation is not supported (ckd_model.h:359 default is linear)");
+  const char* plain = std::getenv("ECCKD_K8B_PLAIN_ORDER");
+  const ot::Schedule schedule = {K8B_WAVES, K8B_RUN, plain && plain[0] == '1'};
+  ot::Tables t;
+  std::string refusal;
+  const int rc = ot::build_tables(m, nscene, scenes, cfg, schedule, t, refusal);
+  if (rc != ECCKD_OK) return ecckd::fail(rc, "%s", refusal.c_str());
   ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
-  const int ng = m->ng, nt = m->nt, np = m->np;
-  ecckd_opt* o = new ecckd_opt();
+  OptPtr o(new ecckd_opt());
   o->ctx = ctx;
-  o->ng = ng; o->nt = nt; o->np = np; o->ngas = m->ngas;
   o->cfg = *cfg;
-  o->do_sw = do_sw;
-  int nband = 0;
-  for (int g = 0; g < ng; ++g) nband = std::max(nband, m->iband_per_g[g] + 1);
-  o->nband = nband;
-
-  // ---- coefficient vector: active gases first (they are the state x), then fixed gases ----
-  std::vector<int> order;
-  for (int a = 1; a >= 0; --a)
-    for (int i = 0; i < m->ngas; ++i)
-      if ((m->gases[i].is_active != 0) == (a == 1)) order.push_back(i);
-  o->user_to_k.assign(m->ngas, -1);
-  size_t off = 0;
-  for (size_t pos = 0; pos < order.size(); ++pos) {
-    const ecckd_opt_gas& ug = m->gases[order[pos]];
-    GasInfo gi;
-    gi.conc = ug.conc_dependence;
-    gi.active = ug.is_active != 0;
-    gi.nconc = (ug.conc_dependence == 2) ? ug.nconc : 1;
-    if (!(ug.conc_dependence >= 0 && ug.conc_dependence <= 3) || !ug.molar_abs ||
-        (ug.conc_dependence == 2 && (ug.nconc < 2 || !ug.vmr))) {
-      opt_free(o);
-      return ecckd::fail(ECCKD_PARAMETER_ERROR, "ecckd_opt_create: gas %d is ill-defined", order[pos]);
-    }
-    gi.nnode = (size_t)gi.nconc * nt * np;
-    gi.ix = off;
-    gi.reference_vmr = ug.reference_vmr;
-    if (ug.conc_dependence == 2) gi.vmr.assign(ug.vmr, ug.vmr + ug.nconc);
-    off += gi.nnode * ng;
-    if (gi.active) { o->nx = off; o->nnode_active += gi.nnode; }
-    o->user_to_k[order[pos]] = (int)pos;
-    o->gases.push_back(gi);
-  }
-  // Rayleigh scattering (calc_total_optical_depth, solve_adept.cpp:33-36; ckd_model.h:242-252): a fixed
-  // one-node pseudo gas at the end of the coefficient vector
-  const bool have_rayleigh = do_sw && m->rayleigh_molar_scattering != nullptr;
-  const size_t rayleigh_ix = off;
-  if (have_rayleigh) off += ng;
-  o->nk = off;
-  ECCKD_REQUIRE(o->nx > 0, "ecckd_opt_create: no active gas to optimise");
-  ECCKD_REQUIRE(o->nk < (size_t)0x7fffffff, "ecckd_opt_create: coefficient vector too long for int32 indexing");
-  o->h_k0.assign(o->nk, 0.0);
-  o->h_kmin.assign(o->nx, 0.0);
-  o->h_kmax.assign(o->nx, 0.0);
-  bool have_minmax = true;
-  for (size_t pos = 0; pos < order.size(); ++pos) {
-    const ecckd_opt_gas& ug = m->gases[order[pos]];
-    const GasInfo& gi = o->gases[pos];
-    std::memcpy(&o->h_k0[gi.ix], ug.molar_abs, gi.nnode * ng * sizeof(double));
-    if (gi.active) {
-      if (ug.min_molar_abs && ug.max_molar_abs) {
-        std::memcpy(&o->h_kmin[gi.ix], ug.min_molar_abs, gi.nnode * ng * sizeof(double));
-        std::memcpy(&o->h_kmax[gi.ix], ug.max_molar_abs, gi.nnode * ng * sizeof(double));
-      } else {
-        have_minmax = false;
-      }
-    }
-  }
-  if (!have_minmax) { o->h_kmin.clear(); o->h_kmax.clear(); }
-  if (have_rayleigh) std::memcpy(&o->h_k0[rayleigh_ix], m->rayleigh_molar_scattering, ng * sizeof(double));
-
-  // cap_relative_linear_coeffts(0.8), optimize_lut.cpp:185, ckd_model.cpp:883-917
-  {
-    int ibg = -1;
-    for (size_t pos = 0; pos < o->gases.size(); ++pos)
-      if (o->gases[pos].conc == 0) ibg = (int)pos;  // the LAST gas with NONE, as the reference loop leaves it
-    if (ibg >= 0 && cfg->cap_relative_linear > 0.0) {
-      const GasInfo& bg = o->gases[ibg];
-      for (GasInfo& gi : o->gases) {
-        if (gi.active && gi.conc == 3 && gi.nnode == bg.nnode) {
-          for (size_t e = 0; e < gi.nnode * ng; ++e) {
-            const double cap = o->h_k0[bg.ix + e] / (gi.reference_vmr * cfg->cap_relative_linear);
-            if (o->h_k0[gi.ix + e] * (gi.reference_vmr * cfg->cap_relative_linear) > o->h_k0[bg.ix + e])
-              o->h_k0[gi.ix + e] = std::min(o->h_k0[gi.ix + e], cap);
-          }
-        }
-      }
-    }
-  }
-
-  // ---- prior (create_error_covariances, ckd_model.cpp:646-832) ----
-  o->have_prior = true;  // the reference always adds calc_background_cost_function (:273)
-  std::vector<double> tri;
-  std::vector<int> tri_off(o->gases.size(), 0), gas_dims(o->gases.size() * 4, 0);
-  std::vector<double> inv_sigma2(o->gases.size() * ng, 0.0);
-  std::vector<int> node_gas, node_ic, node_it, node_ip;
-  {
-    size_t node0 = 0;
-    for (size_t pos = 0; pos < o->gases.size(); ++pos) {
-      GasInfo& gi = o->gases[pos];
-      gas_dims[pos * 4 + 0] = gi.nconc; gas_dims[pos * 4 + 1] = nt; gas_dims[pos * 4 + 2] = np;
-      gas_dims[pos * 4 + 3] = (int)node0;
-      if (!gi.active) continue;
-      tri_off[pos] = (int)tri.size();
-      const Tri tc = ar1_inverse(gi.nconc, cfg->conc_corr), tt = ar1_inverse(nt, cfg->temperature_corr),
-                tp = ar1_inverse(np, cfg->pressure_corr);
-      for (const Tri* t : {&tc, &tt, &tp}) {
-        tri.insert(tri.end(), t->lo.begin(), t->lo.end());
-        tri.insert(tri.end(), t->di.begin(), t->di.end());
-        tri.insert(tri.end(), t->up.begin(), t->up.end());
-      }
-      // background_error per g: fixed prior_error, or estimated from min/max (:679-745)
-      gi.sigma.assign(ng, cfg->prior_error > 0.0 ? cfg->prior_error : 1.0);
-      if (cfg->prior_error <= 0.0 && have_minmax) {
-        for (int g = 0; g < ng; ++g) {
-          double local_sum = 0.0;
-          int local_count = 0;
-          for (size_t nd = 0; nd < gi.nnode; ++nd) {
-            const size_t e = gi.ix + nd * ng + g;
-            if (o->h_k0[e] > 0.0) {
-              if (o->h_kmin[e] > 0.0) local_sum += 0.25 * std::log(o->h_kmax[e] / o->h_kmin[e]);
-              else local_sum += 0.5 * std::log(o->h_kmax[e] / o->h_k0[e]);
-              ++local_count;
-            }
-          }
-          if (local_count > 0) gi.sigma[g] = cfg->prior_error_scaling * local_sum / local_count;
-        }
-        if (cfg->min_prior_error > 0.0) for (double& sg : gi.sigma) sg = std::max(cfg->min_prior_error, sg);
-        if (cfg->max_prior_error > 0.0) for (double& sg : gi.sigma) sg = std::min(sg, cfg->max_prior_error);
-      }
-      for (int g = 0; g < ng; ++g) inv_sigma2[pos * ng + g] = 1.0 / (gi.sigma[g] * gi.sigma[g]);
-      for (int ic = 0; ic < gi.nconc; ++ic)
-        for (int it = 0; it < nt; ++it)
-          for (int ip = 0; ip < np; ++ip) {
-            node_gas.push_back((int)pos); node_ic.push_back(ic); node_it.push_back(it); node_ip.push_back(ip);
-          }
-      node0 += gi.nnode;
-    }
-  }
-
-  // ---- training scenes -> flat per-profile arrays and the sparse interpolation table ----
-  const int nlay = scenes[0].nlay;
-  if (nlay < 1 || nlay > 128) {
-    opt_free(o);
-    return ecckd::fail(ECCKD_PARAMETER_ERROR, "ecckd_opt_create: nlay = %d outside the supported range 1..128", nlay);
-  }
-  o->nlay = nlay;
-  const int nhl = nlay + 1;
-  size_t ncol = 0;
-  for (int s = 0; s < nscene; ++s) {
-    if (scenes[s].nlay != nlay || scenes[s].ncol <= 0 || !scenes[s].pressure_hl || !scenes[s].temperature_hl ||
-        !scenes[s].flux_dn || !scenes[s].flux_up || scenes[s].nband != nband ||
-        (do_sw && (!scenes[s].mu0 || !scenes[s].albedo || !(scenes[s].tsi > 0.0)))) {
-      opt_free(o);
-      return ecckd::fail(ECCKD_PARAMETER_ERROR, "ecckd_opt_create: scene %d is inconsistent (nlay/nband/arrays)", s);
-    }
-    ncol += scenes[s].ncol;
-  }
-  o->ncol = ncol;
-  o->ncell = ncol * nlay;
-  int nent = have_rayleigh ? 1 : 0;
-  for (const GasInfo& gi : o->gases) nent += (gi.conc == 2) ? 8 : 4;
-  o->ray_ent = have_rayleigh ? nent - 1 : -1;
-  o->nent = nent;
-  std::vector<int> ent_idx(o->ncell * nent, -1);
-  std::vector<double> ent_coef(o->ncell * nent, 0.0);
-  std::vector<double> planck(ncol * nhl * ng), semis(ncol * nband, 1.0), conv(ncol * nlay), lwv(ncol * nlay);
-  std::vector<double> hr(ncol * nlay * nband), fdn(ncol * nhl * nband), fup(ncol * nhl * nband);
-  std::vector<double> sfds, sfut;
-  bool any_boundary = false;
-  for (int s = 0; s < nscene; ++s)
-    any_boundary = any_boundary || (scenes[s].spectral_flux_dn_surf &&
-                                    (do_sw ? scenes[s].spectral_boundary_weights != nullptr : scenes[s].spectral_flux_up_toa != nullptr));
-  std::vector<double> mu0v(do_sw ? ncol : 0);
-  double solar_sum = 0.0;
-  if (do_sw)
-    for (int g = 0; g < ng; ++g) solar_sum += m->solar_irradiance[g];
-  o->have_boundary = any_boundary;
-  if (any_boundary) { sfds.assign(ncol * ng, 0.0); sfut.assign(ncol * ng, 0.0); }
-
-  const double log_p_0 = m->log_pressure[0];
-  const double d_log_p = m->log_pressure[1] - m->log_pressure[0];
-  const double d_t = m->temperature[1 * np + 0] - m->temperature[0];
-  const double global_weight = 1.0 / (ECCKD_ACCEL_GRAVITY * 0.001 * 28.970);
-  size_t col0 = 0;
-  for (int s = 0; s < nscene; ++s) {
-    const ecckd_opt_scene& sc = scenes[s];
-    for (int c = 0; c < sc.ncol; ++c) {
-      const size_t col = col0 + c;
-      const double* p = sc.pressure_hl + (size_t)c * nhl;
-      const double* T = sc.temperature_hl + (size_t)c * nhl;
-      if (!do_sw) {
-        for (int i = 0; i < nhl; ++i) planck_lut(m->ntp, m->temperature_planck, m->planck_function, ng, T[i], &planck[(col * nhl + i) * ng]);
-        if (sc.surf_emissivity) std::memcpy(&semis[col * nband], sc.surf_emissivity + (size_t)c * nband, nband * sizeof(double));
-      } else {
-        // tsi_scaling * ckd_model.solar_irradiance() (solve_adept.cpp:176,186) in row 0; band albedo
-        const double tsi_scaling = sc.tsi / solar_sum;
-        for (int g = 0; g < ng; ++g) planck[(col * nhl) * ng + g] = tsi_scaling * m->solar_irradiance[g];
-        std::memcpy(&semis[col * nband], sc.albedo, nband * sizeof(double));
-        mu0v[col] = sc.mu0[c];
-      }
-      // layer weights, solve_adept.cpp:131-143
-      double wsum = 0.0;
-      for (int l = 0; l < nlay; ++l) {
-        double w;
-        if (cfg->pressure_weight_power == 0.5) w = std::sqrt(p[l + 1]) - std::sqrt(p[l]);
-        else if (cfg->pressure_weight_power == 1.0) w = p[l + 1] - p[l];
-        else w = std::pow(p[l + 1], cfg->pressure_weight_power) - std::pow(p[l], cfg->pressure_weight_power);
-        lwv[col * nlay + l] = w;
-        wsum += w;
-        conv[col * nlay + l] = -(ECCKD_ACCEL_GRAVITY / ECCKD_SPECIFIC_HEAT_AIR) / (p[l + 1] - p[l]);
-      }
-      for (int l = 0; l < nlay; ++l) lwv[col * nlay + l] /= wsum;
-      // truth: band fluxes and their heating rate (lbl_fluxes.cpp:380-388, heating_rate.h:30-50)
-      std::memcpy(&fdn[col * nhl * nband], sc.flux_dn + (size_t)c * nhl * nband, (size_t)nhl * nband * sizeof(double));
-      std::memcpy(&fup[col * nhl * nband], sc.flux_up + (size_t)c * nhl * nband, (size_t)nhl * nband * sizeof(double));
-      for (int l = 0; l < nlay; ++l)
-        for (int b = 0; b < nband; ++b) {
-          const double* d = &fdn[col * nhl * nband];
-          const double* u = &fup[col * nhl * nband];
-          // LW: net flux divergence; SW: direct beam only (lbl_fluxes.cpp:365-369 passes an empty flux_up)
-          hr[(col * nlay + l) * nband + b] =
-              do_sw ? conv[col * nlay + l] * (d[(l + 1) * nband + b] - d[l * nband + b])
-                    : conv[col * nlay + l] * (d[(l + 1) * nband + b] - d[l * nband + b] - u[(l + 1) * nband + b] + u[l * nband + b]);
-        }
-      if (any_boundary && sc.spectral_flux_dn_surf && (do_sw ? sc.spectral_boundary_weights != nullptr : sc.spectral_flux_up_toa != nullptr)) {
-        std::memcpy(&sfds[col * ng], sc.spectral_flux_dn_surf + (size_t)c * ng, ng * sizeof(double));
-        // SW: the second array carries the per-g weights (calc_cost_function_sw.cpp:271-274)
-        if (do_sw) std::memcpy(&sfut[col * ng], sc.spectral_boundary_weights, ng * sizeof(double));
-        else std::memcpy(&sfut[col * ng], sc.spectral_flux_up_toa + (size_t)c * ng, ng * sizeof(double));
-      }
-      // interpolation entries, ckd_model.cpp:960-1086
-      for (int l = 0; l < nlay; ++l) {
-        const size_t cell = col * nlay + l;
-        // full-level temperature, solve_adept.cpp:38-41
-        const double t_fl = sc.temperature_fl ? sc.temperature_fl[(size_t)c * nlay + l]
-                                              : (T[l] * p[l] + T[l + 1] * p[l + 1]) / (p[l] + p[l + 1]);
-        const double log_pressure_fl = std::log(0.5 * (p[l + 1] + p[l]));
-        double pindex0 = (log_pressure_fl - log_p_0) / d_log_p;
-        pindex0 = std::fmax(0.0, std::fmin(pindex0, np - 1.0001));
-        const int ip0 = (int)pindex0;
-        const double pw1 = pindex0 - ip0, pw0 = 1.0 - pw1;
-        const double t_0 = pw0 * m->temperature[ip0] + pw1 * m->temperature[ip0 + 1];
-        double tindex0 = (t_fl - t_0) / d_t;
-        tindex0 = std::fmax(0.0, std::fmin(tindex0, nt - 1.0001));
-        const int it0 = (int)tindex0;
-        const double tw1 = tindex0 - it0, tw0 = 1.0 - tw1;
-        const double simple_weight = global_weight * (p[l + 1] - p[l]);
-        int e = 0;
-        for (size_t pos = 0; pos < o->gases.size(); ++pos) {
-          const GasInfo& gi = o->gases[pos];
-          const int ugas = order[pos];
-          const int width = (gi.conc == 2) ? 8 : 4;
-          const bool present = sc.gas_present ? sc.gas_present[ugas] != 0 : true;
-          // ckd_model.cpp:995-1004, :1066-1073 and solve_adept.cpp:47-67: a gas without a
-          // concentration dependence always contributes with the dry-air weight; the others need
-          // their mole fraction from the training file and are skipped when it is absent
-          double weight = 0.0, vm = 0.0;
-          bool use = true;
-          if (gi.conc == 0) {
-            weight = simple_weight;
-          } else if (present && sc.vmr_fl) {
-            vm = sc.vmr_fl[((size_t)c * m->ngas + ugas) * nlay + l];
-            weight = (gi.conc == 3) ? simple_weight * (vm - gi.reference_vmr) : simple_weight * vm;
-          } else {
-            use = false;
-          }
-          if (use) {
-            if (gi.conc == 2) {
-              const double log_conc = std::log(vm);
-              const double d_log_c = std::log(gi.vmr[1] / gi.vmr[0]);
-              double cindex0 = (log_conc - std::log(gi.vmr[0])) / d_log_c;
-              cindex0 = std::fmax(0.0, std::fmin(cindex0, gi.nconc - 1.0001));
-              const int ic0 = (int)cindex0;
-              const double cw1 = cindex0 - ic0, cw0 = 1.0 - cw1;
-              int q = 0;
-              for (int dc = 0; dc < 2; ++dc)
-                for (int dt = 0; dt < 2; ++dt)
-                  for (int dp = 0; dp < 2; ++dp) {
-                    const size_t node = ((size_t)(ic0 + dc) * nt + (it0 + dt)) * np + (ip0 + dp);
-                    ent_idx[cell * nent + e + q] = (int)(gi.ix + node * ng);
-                    ent_coef[cell * nent + e + q] = weight * (dc ? cw1 : cw0) * (dt ? tw1 : tw0) * (dp ? pw1 : pw0);
-                    ++q;
-                  }
-            } else {
-              int q = 0;
-              for (int dt = 0; dt < 2; ++dt)
-                for (int dp = 0; dp < 2; ++dp) {
-                  const size_t node = (size_t)(it0 + dt) * np + (ip0 + dp);
-                  ent_idx[cell * nent + e + q] = (int)(gi.ix + node * ng);
-                  ent_coef[cell * nent + e + q] = weight * (dt ? tw1 : tw0) * (dp ? pw1 : pw0);
-                  ++q;
-                }
-            }
-          }
-          e += width;
-        }
-        if (have_rayleigh) {
-          // moles of air per unit area in the layer (ckd_model.h:246-247) times the molar scattering
-          ent_idx[cell * nent + e] = (int)rayleigh_ix;
-          ent_coef[cell * nent + e] = (p[l + 1] - p[l]) * (1.0 / (ECCKD_ACCEL_GRAVITY * 0.001 * 28.970));
-        }
-      }
-    }
-    col0 += sc.ncol;
-  }
-
-  // ---- transpose of the gather for the active nodes: node -> (cell, coef), in cell order ----
-  std::vector<int> ref_ptr(o->nnode_active + 1, 0);
-  for (size_t cell = 0; cell < o->ncell; ++cell)
-    for (int e = 0; e < nent; ++e) {
-      const int idx = ent_idx[cell * nent + e];
-      if (idx >= 0 && (size_t)idx < o->nx && ent_coef[cell * nent + e] != 0.0) ++ref_ptr[(size_t)idx / ng + 1];
-    }
-  for (size_t i = 0; i < o->nnode_active; ++i) ref_ptr[i + 1] += ref_ptr[i];
-  std::vector<int> ref_cell(ref_ptr.back());
-  std::vector<double> ref_coef(ref_ptr.back());
-  {
-    std::vector<int> fill(ref_ptr.begin(), ref_ptr.end() - 1);
-    for (size_t cell = 0; cell < o->ncell; ++cell)
-      for (int e = 0; e < nent; ++e) {
-        const int idx = ent_idx[cell * nent + e];
-        if (idx >= 0 && (size_t)idx < o->nx && ent_coef[cell * nent + e] != 0.0) {
-          const int slot = fill[(size_t)idx / ng]++;
-          ref_cell[slot] = (int)cell;
-          ref_coef[slot] = ent_coef[cell * nent + e];
-        }
-      }
-  }
-
-  // ---- K8b: which block takes which node.  The pressure axis is cut into 8 contiguous pieces of about equal numbers of
-  // references; piece x is walked, pressure index ascending, by the blocks x, x + 8, x + 16, ... (one XCD, in dispatch order)
-  std::vector<int> node_order, run_order, run_r0_v, run_last_v, node_run0_v;
-  {
-    constexpr int NX = 8;
-    std::vector<long long> refs_of_ip(np, 0);
-    for (size_t nd = 0; nd < o->nnode_active; ++nd) refs_of_ip[node_ip[nd]] += ref_ptr[nd + 1] - ref_ptr[nd] + 1;
-    long long total = 0;
-    for (long long v : refs_of_ip) total += v;
-    std::vector<int> piece_of_ip(np, 0);
-    long long run = 0;
-    for (int ip = 0; ip < np; ++ip) {
-      piece_of_ip[ip] = (int)std::min<long long>(NX - 1, run * NX / std::max<long long>(total, 1));
-      run += refs_of_ip[ip];
-    }
-    std::vector<std::vector<int>> list(NX);
-    for (int ip = 0; ip < np; ++ip)
-      for (size_t nd = 0; nd < o->nnode_active; ++nd)
-        if (node_ip[nd] == ip) list[piece_of_ip[ip]].push_back((int)nd);
-    // a wave per task, K8B_WAVES waves per block: virtual block j of piece x (= j * NX + x) takes the next K8B_WAVES entries of
-    // the piece's list.  Tasks of the first launch: the runs (at most K8B_RUN references of one node) x 64-g chunks; of the
-    // second: the nodes x 64-g chunks.
-    const int nchunk = (ng + 63) / 64;
-    o->grad_nchunk = nchunk;
-    const bool plain = [] { const char* e = std::getenv("ECCKD_K8B_PLAIN_ORDER"); return e && e[0] == '1'; }();
-    std::vector<int> node_run0(o->nnode_active + 1, 0), run_r0, run_last;
-    for (size_t nd = 0; nd < o->nnode_active; ++nd) {
-      node_run0[nd] = (int)run_r0.size();
-      for (int r = ref_ptr[nd]; r < ref_ptr[nd + 1]; r += K8B_RUN) {
-        run_r0.push_back(r);
-        run_last.push_back(std::min(r + K8B_RUN, ref_ptr[nd + 1]));
-      }
-    }
-    node_run0[o->nnode_active] = (int)run_r0.size();
-    o->grad_nrun = run_r0.size();
-    auto lay_out = [&](const std::vector<std::vector<int>>& entries) {
-      size_t longest = 0;
-      for (const auto& l : entries) longest = std::max(longest, (l.size() + K8B_WAVES - 1) / K8B_WAVES);
-      std::vector<int> order(longest * NX * K8B_WAVES, -1);
-      for (int x = 0; x < NX; ++x)
-        for (size_t q = 0; q < entries[x].size(); ++q) order[((q / K8B_WAVES) * NX + x) * K8B_WAVES + q % K8B_WAVES] = entries[x][q];
-      return order;
-    };
-    std::vector<std::vector<int>> node_entries(NX), run_entries(NX);
-    for (int x = 0; x < NX; ++x)
-      for (int nd : list[x]) {
-        for (int c = 0; c < nchunk; ++c) node_entries[x].push_back(nd * nchunk + c);
-        for (int t = node_run0[nd]; t < node_run0[nd + 1]; ++t)
-          for (int c = 0; c < nchunk; ++c) run_entries[x].push_back(t * nchunk + c);
-      }
-    if (plain) {
-      for (auto& v : node_entries) v.clear();
-      for (auto& v : run_entries) v.clear();
-      for (size_t q = 0; q < o->nnode_active * nchunk; ++q) node_entries[(q / K8B_WAVES) % NX].push_back((int)q);
-      for (size_t q = 0; q < run_r0.size() * nchunk; ++q) run_entries[(q / K8B_WAVES) % NX].push_back((int)q);
-    }
-    node_order = lay_out(node_entries);
-    run_order = lay_out(run_entries);
-    run_r0_v = run_r0; run_last_v = run_last; node_run0_v = node_run0;
-    // every virtual block resident at once where that fits (8 blocks of 4 waves per CU), else a grid-stride loop
-    auto grid_of = [&](size_t nslot) {
-      unsigned gsz = (unsigned)std::min<size_t>((nslot + K8B_WAVES - 1) / K8B_WAVES, (size_t)std::max(ctx->num_cu, 1) * 8);
-      return std::max(8u, (gsz + 7) / 8 * 8);
-    };
-    o->gradient_grid = grid_of(node_order.size());
-    o->gather_grid = grid_of(run_order.size());
-  }
-
-  // ---- K9: the prior's stencil per node.  B^-1 is the Kronecker product of the three AR(1) inverses (tridiagonal each):
-  // up to 27 neighbours, weight = wc * wt * wp, entries below MIN_ERROR_COVARIANCE dropped as the reference zeroes them in its
-  // dense inverse (ckd_model.cpp:650, :709-713, :776-780); neighbours in the order (dc, dt, dp) = (-1,-1,-1) ... (1,1,1)
-  std::vector<int> st_nb(o->nnode_active * 27, -1);
-  std::vector<double> st_w(o->nnode_active * 27, 0.0);
-  for (size_t nd = 0; nd < o->nnode_active; ++nd) {
-    const int gas = node_gas[nd];
-    const int nconc = gas_dims[gas * 4 + 0];
-    const size_t node0 = (size_t)gas_dims[gas * 4 + 3];
-    const double* tc = tri.data() + tri_off[gas];
-    const double* tt = tc + 3 * nconc;
-    const double* tp = tt + 3 * nt;
-    const int ic = node_ic[nd], it = node_it[nd], ip = node_ip[nd];
-    int slot = 0;
-    for (int dc = -1; dc <= 1; ++dc) {
-      const int jc = ic + dc;
-      if (jc < 0 || jc >= nconc) continue;
-      const double wc = tc[(dc + 1) * nconc + ic];
-      if (wc == 0.0) continue;
-      for (int dt = -1; dt <= 1; ++dt) {
-        const int jt = it + dt;
-        if (jt < 0 || jt >= nt) continue;
-        const double wt = tt[(dt + 1) * nt + it];
-        if (wt == 0.0) continue;
-        for (int dp = -1; dp <= 1; ++dp) {
-          const int jp = ip + dp;
-          if (jp < 0 || jp >= np) continue;
-          const double w = wc * wt * tp[(dp + 1) * np + ip];
-          if (std::fabs(w) < 1.0e-6) continue;             // MIN_ERROR_COVARIANCE
-          st_nb[nd * 27 + slot] = (int)(node0 + ((size_t)jc * nt + jt) * np + jp);
-          st_w[nd * 27 + slot] = w;
-          ++slot;
-        }
-      }
-    }
-  }
-
-  std::vector<int> band(m->iband_per_g, m->iband_per_g + ng);
-  int rc = ECCKD_OK;
-#define UP(dst, vec) do { rc = upload(ctx, &o->dst, vec); if (rc) { opt_free(o); return rc; } } while (0)
-  UP(d_k, o->h_k0);
-  std::vector<int> band_ptr(nband + 1, 0), band_g;
-  for (int b = 0; b < nband; ++b) {
-    for (int g = 0; g < ng; ++g) if (band[g] == b) band_g.push_back(g);
-    band_ptr[b + 1] = (int)band_g.size();
-  }
-  band_g.resize(ng, 0);                     // (a g point with a negative band number belongs to no band)
-  UP(d_ent_idx, ent_idx); UP(d_ent_coef, ent_coef); UP(d_band, band); UP(d_band_ptr, band_ptr); UP(d_band_g, band_g);
-  UP(d_planck, planck); UP(d_semis, semis); UP(d_conv, conv); UP(d_lw, lwv);
-  UP(d_hr, hr); UP(d_fdn, fdn); UP(d_fup, fup);
-  if (any_boundary) { UP(d_sfds, sfds); UP(d_sfut, sfut); }
-  if (do_sw) UP(d_mu0, mu0v);
-  {
-    bool any_rel = false;
-    for (int s2 = 0; s2 < nscene; ++s2) any_rel = any_rel || (scenes[s2].relative_flux_dn && scenes[s2].relative_flux_up);
-    if (any_rel) {
-      std::vector<double> rel(ncol * 2 * nhl * ng, 0.0);
-      size_t c0 = 0;
-      for (int s2 = 0; s2 < nscene; ++s2) {
-        const ecckd_opt_scene& sc = scenes[s2];
-        if (sc.relative_flux_dn && sc.relative_flux_up)
-          for (size_t c = 0; c < (size_t)sc.ncol; ++c) {
-            std::memcpy(&rel[((c0 + c) * 2) * nhl * ng], sc.relative_flux_dn + c * nhl * ng, nhl * ng * sizeof(double));
-            std::memcpy(&rel[((c0 + c) * 2 + 1) * nhl * ng], sc.relative_flux_up + c * nhl * ng, nhl * ng * sizeof(double));
-          }
-        c0 += sc.ncol;
-      }
-      UP(d_rel, rel);
-    }
-  }
-  UP(d_ref_ptr, ref_ptr); UP(d_ref_cell, ref_cell); UP(d_ref_coef, ref_coef); UP(d_node_order, node_order);
-  UP(d_run_order, run_order); UP(d_run_r0, run_r0_v); UP(d_run_last, run_last_v); UP(d_node_run0, node_run0_v);
-  o->grad_nslot = (int)node_order.size();
-  o->gather_nslot = (int)run_order.size();
-  UP(d_node_gas, node_gas); UP(d_st_nb, st_nb); UP(d_st_w, st_w); UP(d_inv_sigma2, inv_sigma2);
-#undef UP
-  o->grad_blocks = (unsigned)((o->nx + 255) / 256);
-  auto dalloc = [&](double** p, size_t n) { return hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(double)); };
-  if (dalloc(&o->d_x, o->nx) != hipSuccess || dalloc(&o->d_xprior, o->nx) != hipSuccess ||
-      dalloc(&o->d_grad, o->nx + 1) != hipSuccess || dalloc(&o->d_dtau, o->ncell * ng) != hipSuccess ||
-      dalloc(&o->d_run_sum, std::max<size_t>(o->grad_nrun, 1) * o->grad_nchunk * 64) != hipSuccess ||
-      dalloc(&o->d_jcol, ncol) != hipSuccess || dalloc(&o->d_jb, o->nnode_active * (size_t)((ng + 63) / 64)) != hipSuccess) {
-    opt_free(o);
-    return ecckd::fail(ECCKD_OUT_OF_MEMORY, "ecckd_opt_create: device allocation failed");
-  }
-  ECCKD_HIP_CHECK(hipHostMalloc((void**)&o->h_pin, 80 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-  ECCKD_HIP_CHECK(hipHostGetDevicePointer((void**)&o->d_pin, o->h_pin, 0));
-  o->h_rb = o->h_pin;
-  // x_prior = ln k0 (MIN_X where k0 <= 0), solve_adept.cpp:335-341
+  static_cast<ot::Layout&>(*o) = std::move(static_cast<ot::Layout&>(t));   // (k0 among it: from here on it is o->k0)
+  ECCKD_CHECK(opt_upload_tables(o.get(), t));
+  ECCKD_CHECK(opt_alloc_work(o.get(), t));
   std::vector<double> xp(o->nx);
-  for (size_t e = 0; e < o->nx; ++e) xp[e] = o->h_k0[e] > 0.0 ? std::log(o->h_k0[e]) : MIN_X;
+  ot::initial_state(*o, xp.data(), nullptr, nullptr);
   ECCKD_HIP_CHECK(hipMemcpyAsync(o->d_xprior, xp.data(), o->nx * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  *out = o;
+  *out = o.release();
   return ECCKD_OK;
 }
 
@@ -1941,9 +1507,6 @@ int ecckd_opt_destroy(ecckd_opt* o) {
 
 size_t ecckd_opt_nx(ecckd_opt* o) { return o ? o->nx : 0; }
 
-// Initial state and log-space bounds, solve_adept.cpp:335-353.  h_x_min/h_x_max may be NULL;
-// unbounded elements get -/+ infinity.  Returns the gas order of the state in h_gas_order
-// (user gas indices of the active gases, in state order) if not NULL.
 int ecckd_opt_set_evaluator(ecckd_opt* o, ecckd_evaluator_fn fn, void* user) {
   ECCKD_REQUIRE(o, "ecckd_opt_set_evaluator: NULL handle");
   o->eval_fn = fn;
@@ -1978,30 +1541,50 @@ int ecckd_opt_set_allreduce(ecckd_opt* o, ecckd_allreduce_fn fn, void* user, int
   return ECCKD_OK;
 }
 
+// Initial state and log-space bounds, solve_adept.cpp:335-353.  h_x_min/h_x_max may be NULL;
+// unbounded elements get -/+ infinity.  Returns the gas order of the state in h_gas_order
+// (user gas indices of the active gases, in state order) if not NULL.
 int ecckd_opt_initial_state(ecckd_opt* o, double* h_x, double* h_x_min, double* h_x_max) {
   ECCKD_REQUIRE(o && h_x, "ecckd_opt_initial_state: NULL argument");
-  for (size_t e = 0; e < o->nx; ++e) h_x[e] = o->h_k0[e] > 0.0 ? std::log(o->h_k0[e]) : MIN_X;
-  if (h_x_min && h_x_max) {
-    for (size_t e = 0; e < o->nx; ++e) {
-      h_x_min[e] = -INFINITY;
-      h_x_max[e] = INFINITY;
-      if (!o->h_kmin.empty()) {
-        if (o->h_kmin[e] > 0.0) h_x_min[e] = std::log(o->h_kmin[e]);
-        if (o->h_kmax[e] > 0.0) h_x_max[e] = std::log(o->h_kmax[e]);
-        if (o->h_kmin[e] == 0.0 && o->h_k0[e] > 0.0 && o->h_kmax[e] > 0.0)
-          h_x_min[e] = std::min(3.0 * h_x[e] - 2.0 * h_x_max[e], h_x_max[e] - 1.0);
-      }
-    }
-  }
+  ot::initial_state(*o, h_x, h_x_min, h_x_max);
   return ECCKD_OK;
 }
 
-// CkdOptimizable::calc_cost_function_gradient (solve_adept.cpp:240-292).
-// cost and gradient at the DEVICE state d_x -> d_grad; J on the host (one stream sync).
-// Results the host needs at once (the cost of a trial point, the dot products of the L-BFGS update) arrive in pinned slots
-// that the host watches (slots_mark_pending / slots_wait, common.hpp): two waits per iteration, each a PCIe write away from
-// the kernel's end.
-static int opt_launch_forward(ecckd_opt* o) {
+}  // extern "C"
+
+namespace {
+
+// The cell-parallel K8a kernel, one instance per (cells per thread, shortwave, 8-entry batches of a cell's table).
+template <int NC, bool SW, int NB>
+int launch_cells(ecckd_opt* o, int threads, size_t lds, int ngpad) {
+  const auto kernel = k_opt_forward_adjoint_cells<NC, SW, NB>;
+  ECCKD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  hipLaunchKernelGGL(kernel, dim3((unsigned)o->ncol), dim3(threads), lds, o->ctx->stream, o->d_mu0, o->eval_ray_ent,
+                     o->eval_keep_negative, o->d_rel, o->nlay, o->ng, ngpad, o->nband, o->nent, o->d_k, o->d_ent_idx, o->d_ent_coef,
+                     o->d_band, o->d_band_ptr, o->d_band_g, o->d_planck, o->d_semis, o->d_conv, o->d_lw, o->d_hr, o->d_fdn, o->d_fup,
+                     o->d_sfds, o->d_sfut, o->cfg.flux_weight, o->cfg.flux_profile_weight, o->cfg.broadband_weight,
+                     o->cfg.spectral_boundary_weight, o->cfg.negative_od_penalty, o->d_dtau, o->d_jcol, o->d_od_out, o->d_flux_out);
+  return ECCKD_OK;
+}
+
+template <int NC, bool SW>
+int launch_cells_nb(int nb, ecckd_opt* o, int threads, size_t lds, int ngpad) {
+  switch (nb) {
+    case 1: return launch_cells<NC, SW, 1>(o, threads, lds, ngpad);
+    case 2: return launch_cells<NC, SW, 2>(o, threads, lds, ngpad);
+    case 3: return launch_cells<NC, SW, 3>(o, threads, lds, ngpad);
+    case 4: return launch_cells<NC, SW, 4>(o, threads, lds, ngpad);
+    default: return launch_cells<NC, SW, 0>(o, threads, lds, ngpad);
+  }
+}
+
+int launch_cells_for(int nc, int nb, ecckd_opt* o, int threads, size_t lds, int ngpad) {
+  if (o->do_sw) return nc <= 4 ? launch_cells_nb<4, true>(nb, o, threads, lds, ngpad) : launch_cells_nb<8, true>(nb, o, threads, lds, ngpad);
+  return nc <= 4 ? launch_cells_nb<4, false>(nb, o, threads, lds, ngpad) : launch_cells_nb<8, false>(nb, o, threads, lds, ngpad);
+}
+
+// K8a at the coefficients in d_k: the cell-parallel kernel where the profile fits it, else the general one.
+int opt_launch_forward(ecckd_opt* o) {
   ecckd_ctx* ctx = o->ctx;
   const int nlay = o->nlay, nhl = nlay + 1, ng = o->ng, nband = o->nband;
   const int ngpad = (ng + 63) / 64 * 64;
@@ -2018,33 +1601,8 @@ static int opt_launch_forward(ecckd_opt* o) {
                         nlay + 2 * (size_t)nhl + 16) * sizeof(double) + ((size_t)nband + 1 + ng) * sizeof(int);
     if (!force_generic && nc <= 8 && lds <= 160 * 1024 && ngpad * lgroups <= 1024 && nhl * nband <= K8A_MAXR * ngpad * lgroups) {
       const int threads = ngpad * lgroups;
-#define ECCKD_K8A_CELLS(NC_, SW_, NB_)                                                                                              \
-      do {                                                                                                                            \
-        ECCKD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_opt_forward_adjoint_cells<NC_, SW_, NB_>),             \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                              \
-        hipLaunchKernelGGL((k_opt_forward_adjoint_cells<NC_, SW_, NB_>), dim3((unsigned)o->ncol), dim3(threads), lds, ctx->stream,  \
-                           o->d_mu0, o->eval_ray_ent, o->eval_keep_negative, o->d_rel, nlay, ng, ngpad, nband, o->nent, o->d_k,     \
-                           o->d_ent_idx, o->d_ent_coef, o->d_band, o->d_band_ptr, o->d_band_g, o->d_planck, o->d_semis, o->d_conv, \
-                           o->d_lw, o->d_hr, o->d_fdn,                                                                               \
-                           o->d_fup, o->d_sfds, o->d_sfut, o->cfg.flux_weight, o->cfg.flux_profile_weight,                          \
-                           o->cfg.broadband_weight, o->cfg.spectral_boundary_weight, o->cfg.negative_od_penalty, o->d_dtau,         \
-                           o->d_jcol, o->d_od_out, o->d_flux_out);                                                                  \
-      } while (0)
-#define ECCKD_K8A_NB(NC_, SW_)                                                                                                      \
-      do {                                                                                                                            \
-        switch (nb) {                                                                                                                 \
-          case 1: ECCKD_K8A_CELLS(NC_, SW_, 1); break;                                                                                \
-          case 2: ECCKD_K8A_CELLS(NC_, SW_, 2); break;                                                                                \
-          case 3: ECCKD_K8A_CELLS(NC_, SW_, 3); break;                                                                                \
-          case 4: ECCKD_K8A_CELLS(NC_, SW_, 4); break;                                                                                \
-          default: ECCKD_K8A_CELLS(NC_, SW_, 0); break;                                                                               \
-        }                                                                                                                             \
-      } while (0)
       const int nb = (std::min(o->nent, 64) + K8A_GB - 1) / K8A_GB;       // 8-entry batches of a cell's table (first 64 entries)
-      if (o->do_sw) { if (nc <= 4) ECCKD_K8A_NB(4, true); else ECCKD_K8A_NB(8, true); }
-      else { if (nc <= 4) ECCKD_K8A_NB(4, false); else ECCKD_K8A_NB(8, false); }
-#undef ECCKD_K8A_NB
-#undef ECCKD_K8A_CELLS
+      ECCKD_CHECK(launch_cells_for(nc, nb, o, threads, lds, ngpad));
       ECCKD_HIP_CHECK(hipGetLastError());
       return ECCKD_OK;
     }
@@ -2066,7 +1624,12 @@ static int opt_launch_forward(ecckd_opt* o) {
   return ECCKD_OK;
 }
 
-static int opt_cost_grad_dev(ecckd_opt* o, const double* d_x, double* d_grad, double* J, bool k_ready = false) {
+// CkdOptimizable::calc_cost_function_gradient (solve_adept.cpp:240-292).
+// cost and gradient at the DEVICE state d_x -> d_grad; J on the host (one stream sync).
+// Results the host needs at once (the cost of a trial point, the dot products of the L-BFGS update) arrive in pinned slots
+// that the host watches (slots_mark_pending / slots_wait, common.hpp): two waits per iteration, each a PCIe write away from
+// the kernel's end.
+int opt_cost_grad_dev(ecckd_opt* o, const double* d_x, double* d_grad, double* J, bool k_ready = false) {
   ecckd_ctx* ctx = o->ctx;
   if (o->eval_fn && o->d_od_out == nullptr) {
     // the caller's cost function and gradient in place of the device's: the minimizer itself is unchanged
@@ -2082,7 +1645,7 @@ static int opt_cost_grad_dev(ecckd_opt* o, const double* d_x, double* d_grad, do
     return ECCKD_OK;
   }
   const bool reduce = o->reduce_fn != nullptr && o->d_od_out == nullptr;   // not for the diagnostic forward pass
-  const bool prior = o->have_prior && (!reduce || o->add_prior);
+  const bool prior = !reduce || o->add_prior;   // (the reference always adds calc_background_cost_function, :273)
   if (!k_ready)     // (the minimizer's step kernel leaves exp(x) of its trial point in d_k)
     hipLaunchKernelGGL(k_opt_exp, dim3(o->grad_blocks), dim3(256), 0, ctx->stream, o->nx, d_x, o->d_k);
   const int ng = o->ng;
@@ -2099,10 +1662,10 @@ static int opt_cost_grad_dev(ecckd_opt* o, const double* d_x, double* d_grad, do
   if (timed) ECCKD_HIP_CHECK(hipEventRecord(o->tev[2], ctx->stream));
   // the cost: profiles, then the prior's node terms, summed on the device in a fixed order and delivered to the host's slot
   // (and, for the profile-sharded all-reduce, into the slot behind the gradient: ONE collective of nx + 1 doubles)
-  double* h_cost = o->h_pin + 70;
+  double* h_cost = o->h_pin + PIN_COST;
   ecckd::slots_mark_pending(h_cost, 1);
   hipLaunchKernelGGL(k_opt_sum_cost, dim3(1), dim3(256), 0, ctx->stream, o->d_jcol, o->ncol, o->d_jb, o->nnode_active * (size_t)o->grad_nchunk, prior ? 1 : 0,
-                     o->d_pin + 70, reduce ? d_grad + o->nx : nullptr);
+                     o->d_pin + PIN_COST, reduce ? d_grad + o->nx : nullptr);
   ECCKD_HIP_CHECK(hipGetLastError());
   ECCKD_CHECK(ecckd::slots_wait(ctx->stream, h_cost, 1, "ecckd_opt: results"));
   if (timed) {
@@ -2117,7 +1680,7 @@ static int opt_cost_grad_dev(ecckd_opt* o, const double* d_x, double* d_grad, do
   }
   *J = *h_cost;
   if (reduce) {
-    double* slot = o->h_pin + 71;
+    double* slot = o->h_pin + PIN_REDUCED_COST;
     ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     const int rc = o->reduce_fn(d_grad, o->nx + 1, (void*)ctx->stream, o->reduce_user);
     if (rc != 0) return ecckd::fail(ECCKD_PROCESSING_ERROR, "ecckd_opt: the all-reduce callback failed (%d)", rc);
@@ -2128,6 +1691,40 @@ static int opt_cost_grad_dev(ecckd_opt* o, const double* d_x, double* d_grad, do
   o->n_eval++;
   return ECCKD_OK;
 }
+
+// A diagnostic forward pass: `body` runs K8a with the two output buffers in place and the evaluation mode set (ray_ent: the
+// entry added after the clamp, or -1; keep_negative: 0 clamp, 1 / 2 report the optical depth / also the fluxes unclamped),
+// then total optical depth [ncol][nlay][ng] and CKD fluxes [ncol][2][nlay+1][ng] are copied out where asked for.  The buffers
+// and the mode are the handle's for the length of this call only, whichever way it ends: while they are set the evaluator
+// and the all-reduce are bypassed (opt_cost_grad_dev).
+template <typename Body>
+int opt_diagnostic_pass(ecckd_opt* o, int ray_ent, int keep_negative, double* h_od, double* h_flux, Body body) {
+  ecckd_ctx* ctx = o->ctx;
+  ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
+  const size_t od_bytes = o->ncell * o->ng * sizeof(double), flux_bytes = o->ncol * 2 * (o->nlay + 1) * o->ng * sizeof(double);
+  void* od = nullptr;
+  void* flux = nullptr;
+  ECCKD_HIP_CHECK(hipMalloc(&od, od_bytes));
+  const hipError_t e = hipMalloc(&flux, flux_bytes);
+  if (e != hipSuccess) (void)hipFree(od);
+  ECCKD_HIP_CHECK(e);
+  o->d_od_out = (double*)od;
+  o->d_flux_out = (double*)flux;
+  o->eval_ray_ent = ray_ent;
+  o->eval_keep_negative = keep_negative;
+  int rc = body();
+  o->eval_ray_ent = -1;
+  o->eval_keep_negative = 0;
+  if (rc == ECCKD_OK && h_od) rc = ecckd_d2h(ctx, h_od, o->d_od_out, od_bytes);
+  if (rc == ECCKD_OK && h_flux) rc = ecckd_d2h(ctx, h_flux, o->d_flux_out, flux_bytes);
+  (void)hipFree(o->d_od_out); (void)hipFree(o->d_flux_out);
+  o->d_od_out = nullptr; o->d_flux_out = nullptr;
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
 
 int ecckd_opt_cost_grad(ecckd_opt* o, const double* h_x, double* J, double* h_grad) {
   ECCKD_REQUIRE(o && h_x && J, "ecckd_opt_cost_grad: NULL argument");
@@ -2154,41 +1751,66 @@ int ecckd_opt_forward(ecckd_opt* o, const double* h_x, double* h_od, double* h_f
 // the clamp lives in calc_cost_function_and_gradient only, solve_adept.cpp:107-116).
 int ecckd_opt_forward_ex(ecckd_opt* o, const double* h_x, int unclamped, double* h_od, double* h_flux) {
   ECCKD_REQUIRE(o && h_x, "ecckd_opt_forward: NULL argument");
-  ecckd_ctx* ctx = o->ctx;
-  const size_t nod = o->ncell * o->ng, nfl = o->ncol * 2 * (o->nlay + 1) * o->ng;
-  if (!o->d_od_out) ECCKD_HIP_CHECK(hipMalloc((void**)&o->d_od_out, nod * sizeof(double)));
-  if (!o->d_flux_out) ECCKD_HIP_CHECK(hipMalloc((void**)&o->d_flux_out, nfl * sizeof(double)));
-  double J;
-  const int saved_mode = o->eval_keep_negative;
-  if (unclamped) o->eval_keep_negative = 2;
-  int rc = ecckd_opt_cost_grad(o, h_x, &J, nullptr);
-  o->eval_keep_negative = saved_mode;
-  if (rc == ECCKD_OK) {
-    if (h_od) rc = ecckd_d2h(ctx, h_od, o->d_od_out, nod * sizeof(double));
-    if (rc == ECCKD_OK && h_flux) rc = ecckd_d2h(ctx, h_flux, o->d_flux_out, nfl * sizeof(double));
-  }
-  (void)hipFree(o->d_od_out); (void)hipFree(o->d_flux_out);
-  o->d_od_out = nullptr; o->d_flux_out = nullptr;
-  return rc;
+  return opt_diagnostic_pass(o, -1, unclamped ? 2 : 0, h_od, h_flux, [&] {
+    double J;
+    return ecckd_opt_cost_grad(o, h_x, &J, nullptr);
+  });
 }
 
 // The optimised molar absorption coefficients of one (user-indexed) gas at state h_x:
 // k = exp(x), 0 where x is pinned at MIN_X (solve_adept.cpp:242-249).
 int ecckd_opt_coefficients(ecckd_opt* o, const double* h_x, int gas, double* h_molar_abs) {
   ECCKD_REQUIRE(o && h_molar_abs && gas >= 0 && gas < o->ngas, "ecckd_opt_coefficients: bad argument");
-  const GasInfo& gi = o->gases[o->user_to_k[gas]];
+  const ot::GasInfo& gi = o->gases[o->user_to_k[gas]];
   for (size_t e = 0; e < gi.nnode * o->ng; ++e) {
     const size_t ge = gi.ix + e;
     if (gi.active && h_x) h_molar_abs[e] = h_x[ge] > MIN_X ? std::exp(h_x[ge]) : 0.0;
-    else h_molar_abs[e] = o->h_k0[ge];
+    else h_molar_abs[e] = o->k0[ge];
   }
   return ECCKD_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// the minimizer's device workspace (kept by the handle for the next call), the start point and the bounds
+int opt_minimize_workspace(ecckd_opt* o, const std::vector<double>& x0, const std::vector<double>& xmin, const std::vector<double>& xmax) {
+  hipStream_t stream = o->ctx->stream;
+  const size_t n = o->nx;
+  auto ensure = [&](double** p, size_t cnt) -> int {
+    if (!*p) ECCKD_HIP_CHECK(o->alloc(p, cnt));
+    return ECCKD_OK;
+  };
+  ECCKD_CHECK(ensure(&o->d_xn, n)); ECCKD_CHECK(ensure(&o->d_gn, n + 1)); ECCKD_CHECK(ensure(&o->d_dir, n));
+  ECCKD_CHECK(ensure(&o->d_q, n)); ECCKD_CHECK(ensure(&o->d_S, (size_t)LB_M * n)); ECCKD_CHECK(ensure(&o->d_Y, (size_t)LB_M * n));
+  ECCKD_HIP_CHECK(hipMemsetAsync(o->d_S, 0, (size_t)LB_M * n * sizeof(double), stream));     // unused pairs are read (with zero weight)
+  ECCKD_HIP_CHECK(hipMemsetAsync(o->d_Y, 0, (size_t)LB_M * n * sizeof(double), stream));
+  ECCKD_CHECK(ensure(&o->d_part, (size_t)(LB_NPART + 2) * VEC_BLOCKS));
+  if (!xmin.empty()) {
+    ECCKD_CHECK(ensure(&o->d_xmin, n)); ECCKD_CHECK(ensure(&o->d_xmax, n));
+    ECCKD_HIP_CHECK(hipMemcpyAsync(o->d_xmin, xmin.data(), n * sizeof(double), hipMemcpyHostToDevice, stream));
+    ECCKD_HIP_CHECK(hipMemcpyAsync(o->d_xmax, xmax.data(), n * sizeof(double), hipMemcpyHostToDevice, stream));
+  }
+  ECCKD_HIP_CHECK(hipMemcpyAsync(o->d_x, x0.data(), n * sizeof(double), hipMemcpyHostToDevice, stream));
+  return ECCKD_OK;
+}
+
+LbSlots lb_slots(const ecckd::LbfgsHistory& h) {
+  LbSlots s;
+  s.n = h.n;
+  h.slots(s.slot);
+  return s;
+}
+
+}  // namespace
+
+extern "C" {
+
 // ---------------------------------------------------------------------------------------
 // solve_adept (solve_adept.cpp:310-417).  adept::Minimizer is a third-party L-BFGS that is not
 // available here (trajectory parity unpinned); this is a standard L-BFGS (m = 6, compact
-// representation, see the k_lb_* kernels) with Armijo backtracking + curvature-guarded updates, the step
+// representation, see the k_lb_* kernels and lbfgs_history.hpp) with Armijo backtracking + curvature-guarded updates, the step
 // capped at max_step_size = 2 in the 2-norm (:331) and simple projection onto [x_min, x_max] when
 // bounded (:344-353).  Status values follow adept::MinimizerStatus (0 success, 2 max
 // iterations, 3 failed to converge, 6 invalid cost function, 7 invalid gradient).
@@ -2198,57 +1820,42 @@ int ecckd_opt_minimize(ecckd_opt* o, int max_iterations, double convergence_crit
   ecckd_ctx* ctx = o->ctx;
   ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
   const size_t n = o->nx;
-  constexpr int M = LB_M;
-  // state, bounds and history live on the device; the host only sees scalars
-  std::vector<double> x0(n), xmin, xmax;
-  const bool bounded = is_bounded && !o->h_kmin.empty();
-  if (bounded) {
-    xmin.resize(n); xmax.resize(n);
-    ECCKD_CHECK(ecckd_opt_initial_state(o, x0.data(), xmin.data(), xmax.data()));
-  } else {
-    ECCKD_CHECK(ecckd_opt_initial_state(o, x0.data(), nullptr, nullptr));
-  }
-  auto dalloc = [&](double** p, size_t cnt) -> int {
-    if (*p) return ECCKD_OK;
-    ECCKD_HIP_CHECK(hipMalloc((void**)p, cnt * sizeof(double)));
-    return ECCKD_OK;
-  };
   constexpr int NPART = LB_NPART;   // update: |q|^2, S.q, Y.q (1 + 2M) | pair dots (2 + 3M)
-  ECCKD_CHECK(dalloc(&o->d_xn, n)); ECCKD_CHECK(dalloc(&o->d_gn, n + 1)); ECCKD_CHECK(dalloc(&o->d_dir, n));
-  ECCKD_CHECK(dalloc(&o->d_q, n)); ECCKD_CHECK(dalloc(&o->d_S, (size_t)M * n)); ECCKD_CHECK(dalloc(&o->d_Y, (size_t)M * n));
-  ECCKD_HIP_CHECK(hipMemsetAsync(o->d_S, 0, (size_t)M * n * sizeof(double), ctx->stream));     // unused pairs are read (with zero weight)
-  ECCKD_HIP_CHECK(hipMemsetAsync(o->d_Y, 0, (size_t)M * n * sizeof(double), ctx->stream));
-  ECCKD_CHECK(dalloc(&o->d_part, (size_t)(NPART + 2) * VEC_BLOCKS));
-  if (bounded) {
-    ECCKD_CHECK(dalloc(&o->d_xmin, n)); ECCKD_CHECK(dalloc(&o->d_xmax, n));
-    ECCKD_HIP_CHECK(hipMemcpyAsync(o->d_xmin, xmin.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    ECCKD_HIP_CHECK(hipMemcpyAsync(o->d_xmax, xmax.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  }
-  ECCKD_HIP_CHECK(hipMemcpyAsync(o->d_x, x0.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  // state, bounds and history live on the device; the host only sees scalars
+  const bool bounded = is_bounded && !o->kmin.empty();
+  std::vector<double> x0(n), xmin(bounded ? n : 0), xmax(bounded ? n : 0);
+  ot::initial_state(*o, x0.data(), bounded ? xmin.data() : nullptr, bounded ? xmax.data() : nullptr);
+  ECCKD_CHECK(opt_minimize_workspace(o, x0, xmin, xmax));
   const double* bmin = bounded ? o->d_xmin : nullptr;
   const double* bmax = bounded ? o->d_xmax : nullptr;
   double* x = o->d_x; double* g = o->d_grad; double* xn = o->d_xn; double* gn = o->d_gn;
   double* part_a = o->d_part;                                  // the update's NPART partial arrays
   double* part_dg = o->d_part + (size_t)NPART * VEC_BLOCKS;    // direction: d.g, then d.d
   double* part_dd = part_dg + VEC_BLOCKS;
-  // scalars the kernels deliver into the pinned slots: [0 .. 1+2M) direction dots, [1+2M .. 3+5M) pair dots, [64..67) step, d.d, d.g
-  double* sc = o->d_pin;
-  double* sc_step = o->d_pin + 64;
-  double* h_rb = o->h_rb;
-  double* h_step = o->h_rb + 64;
+  double* h_dots = o->h_pin + PIN_LB_DOTS;
+  double* h_step = o->h_pin + PIN_LB_STEP;
   // one block of 16 waves per CU is what the update kernel's registers allow: no more blocks than CUs (a second, nearly empty
   // round would cost a whole pass again)
   const int nblk = (int)std::min<size_t>(std::min<size_t>(VEC_BLOCKS, (size_t)std::max(ctx->num_cu, 1)), std::max<size_t>(1, (n + VEC_THREADS - 1) / VEC_THREADS));
   const dim3 vb(nblk), vt(VEC_THREADS);
   const double max_step = 2.0;  // minimizer.set_max_step_size(2.0), solve_adept.cpp:331
-
-  // host side of the compact representation: S^T Y and Y^T Y of the stored pairs, by ring slot
-  double SY[M][M] = {}, YY[M][M] = {};
-  int ord[M];        // ring slots, oldest first
-  int hist = 0;
-  double gamma = 1.0;
-  bool pending = false;   // a pair has been written to `pend_slot`; its dots arrive with the next direction's
-  int pend_slot = 0;
+  ecckd::LbfgsHistory lb;
+  // the pair (x1 - x0, g1 - g0) into ring slot `slot` (-1: none), its dots with the pairs `keep`, and the projected gradient
+  // at x1 with every pair's dots, in ONE pass; awaited at the top of the loop
+  auto launch_update = [&](const LbSlots& keep, int slot, const double* x0d, const double* x1d, const double* g0d, const double* g1d) {
+    ecckd::slots_mark_pending(h_dots, NPART);
+    hipLaunchKernelGGL(k_lb_update, vb, vt, 0, ctx->stream, n, keep, slot, x0d, x1d, g0d, g1d, bmin, bmax, o->d_q, o->d_S, o->d_Y, part_a);
+    hipLaunchKernelGGL(k_lb_finish, dim3(NPART), dim3(FIN_THREADS), 0, ctx->stream, part_a, nblk, o->d_pin + PIN_LB_DOTS);
+    return hipGetLastError();
+  };
+  // the trial point (and its coefficients) at `step` along the direction (-1: the first trial, its length chosen on the
+  // device), then the cost there
+  auto trial = [&](double step, bool steepest, double* Jn) {
+    hipLaunchKernelGGL(k_lb_step, vb, vt, 0, ctx->stream, n, step, steepest ? 1 : 0, max_step, 1.0, part_dg, part_dd,
+                       x, o->d_dir, bmin, bmax, xn, o->d_k, o->d_pin + PIN_LB_STEP);
+    ECCKD_HIP_CHECK(hipGetLastError());
+    return opt_cost_grad_dev(o, xn, gn, Jn, true);
+  };
 
   const auto wall0 = std::chrono::steady_clock::now();
   const double dev0 = o->t_rt + o->t_prior;
@@ -2257,39 +1864,12 @@ int ecckd_opt_minimize(ecckd_opt* o, int max_iterations, double convergence_crit
   int st = 2, it = 0;
   double gnorm = 0.0;
   if (!(J == J)) { *status = 6; if (J_final) *J_final = J; return ECCKD_OK; }
-  {
-    // projected gradient and its norm at the starting point (no pair yet)
-    LbSlots none;
-    none.n = 0;
-    for (int a = 0; a < M; ++a) none.slot[a] = 0;
-    ecckd::slots_mark_pending(h_rb, NPART);
-    hipLaunchKernelGGL(k_lb_update, vb, vt, 0, ctx->stream, n, none, -1, x, x, g, g, bmin, bmax, o->d_q, o->d_S, o->d_Y, part_a);
-    hipLaunchKernelGGL(k_lb_finish, dim3(NPART), dim3(FIN_THREADS), 0, ctx->stream, part_a, nblk, sc);
-    ECCKD_HIP_CHECK(hipGetLastError());
-  }
+  ECCKD_HIP_CHECK(launch_update(lb_slots(lb), -1, x, x, g, g));   // projected gradient and its norm at the starting point (no pair yet)
   for (it = 0; it <= max_iterations; ++it) {
-    // |q|^2, S^T q, Y^T q at the current point (the pending pair included, as the newest) and the pending pair's own dots:
-    // launched at the end of the previous iteration (k_lb_update), awaited here
-    ECCKD_CHECK(ecckd::slots_wait(ctx->stream, h_rb, NPART, "ecckd_opt: results"));
-    int npairs = hist;           // pairs that enter this direction
-    if (pending) {
-      const double* rp = h_rb + 1 + 2 * M;   // s.y, y.y, s.Y_a, S_a.y, y.Y_a for a < hist
-      const double sy = rp[0], yy = rp[1];
-      if (sy > 1.0e-12) {
-        for (int a = 0; a < hist; ++a) {
-          SY[pend_slot][ord[a]] = rp[2 + a];
-          SY[ord[a]][pend_slot] = rp[2 + M + a];
-          YY[pend_slot][ord[a]] = YY[ord[a]][pend_slot] = rp[2 + 2 * M + a];
-        }
-        SY[pend_slot][pend_slot] = sy;
-        YY[pend_slot][pend_slot] = yy;
-        ord[hist++] = pend_slot;
-        gamma = sy / yy;
-        npairs = hist;
-      }
-      pending = false;
-    }
-    gnorm = std::sqrt(h_rb[0]);
+    // |q|^2, S^T q, Y^T q at the current point (the pending pair included, as the newest) and the pending pair's own dots
+    ECCKD_CHECK(ecckd::slots_wait(ctx->stream, h_dots, NPART, "ecckd_opt: results"));
+    lb.absorb_pending(h_dots);
+    gnorm = std::sqrt(h_dots[0]);
     if (o->progress_fn) o->progress_fn(it, J, gnorm, o->progress_user);   // report_progress, solve_adept.cpp:295-299
     if (!(gnorm == gnorm)) { st = 7; break; }
     if (gnorm <= convergence_criterion) { st = 0; break; }
@@ -2299,44 +1879,12 @@ int ecckd_opt_minimize(ecckd_opt* o, int max_iterations, double convergence_crit
     double Jn = J, step = 0.0, dg = 0.0;
     bool ok = false;
     for (;;) {
-      // coefficients of the direction: u = R^-1 p, top = R^-T ((D + gamma YY) u - gamma qy)
       LbCoef cf;
-      cf.gamma = npairs > 0 ? gamma : 1.0;
-      for (int a = 0; a < M; ++a) { cf.cs[a] = 0.0; cf.cy[a] = 0.0; }
-      LbSlots sd;
-      sd.n = npairs;
-      for (int a = 0; a < M; ++a) sd.slot[a] = a < npairs ? ord[a] : 0;
-      if (npairs > 0) {
-        double pv[M], qv[M], u[M], w[M], top[M];
-        for (int a = 0; a < npairs; ++a) {
-          // position of pair a in the dot arrays of this iteration: the stored pairs first, the pending one last
-          pv[a] = h_rb[1 + a];
-          qv[a] = h_rb[1 + M + a];
-        }
-        for (int a = npairs - 1; a >= 0; --a) {
-          double v = pv[a];
-          for (int c = a + 1; c < npairs; ++c) v -= SY[ord[a]][ord[c]] * u[c];
-          u[a] = v / SY[ord[a]][ord[a]];
-        }
-        for (int a = 0; a < npairs; ++a) {
-          double v = SY[ord[a]][ord[a]] * u[a] - cf.gamma * qv[a];
-          for (int c = 0; c < npairs; ++c) v += cf.gamma * YY[ord[a]][ord[c]] * u[c];
-          w[a] = v;
-        }
-        for (int a = 0; a < npairs; ++a) {
-          double v = w[a];
-          for (int c = 0; c < a; ++c) v -= SY[ord[c]][ord[a]] * top[c];
-          top[a] = v / SY[ord[a]][ord[a]];
-        }
-        for (int a = 0; a < npairs; ++a) { cf.cs[a] = top[a]; cf.cy[a] = cf.gamma * u[a]; }
-      }
-      hipLaunchKernelGGL(k_lb_direction, vb, vt, 0, ctx->stream, n, sd, cf, o->d_q, o->d_S, o->d_Y, g, o->d_dir, part_dg);
-      // the trial point (and its coefficients) with the step chosen on the device, then the cost there; one wait for both
+      cf.gamma = lb.coefficients(h_dots, cf.cs, cf.cy);
+      hipLaunchKernelGGL(k_lb_direction, vb, vt, 0, ctx->stream, n, lb_slots(lb), cf, o->d_q, o->d_S, o->d_Y, g, o->d_dir, part_dg);
+      // one wait for the step and the cost of the first trial
       ecckd::slots_mark_pending(h_step, 3);
-      hipLaunchKernelGGL(k_lb_step, vb, vt, 0, ctx->stream, n, -1.0, npairs == 0 ? 1 : 0, max_step, 1.0, part_dg,
-                         part_dd, x, o->d_dir, bmin, bmax, xn, o->d_k, sc_step);
-      ECCKD_HIP_CHECK(hipGetLastError());
-      ECCKD_CHECK(opt_cost_grad_dev(o, xn, gn, &Jn, true));
+      ECCKD_CHECK(trial(-1.0, lb.n == 0, &Jn));
       ECCKD_CHECK(ecckd::slots_wait(ctx->stream, h_step, 3, "ecckd_opt: results"));
       step = h_step[0];
       dg = h_step[2];
@@ -2344,10 +1892,9 @@ int ecckd_opt_minimize(ecckd_opt* o, int max_iterations, double convergence_crit
         // not a descent direction: drop the history, steepest descent on the projected gradient
         // steepest descent on a non-zero projected gradient that is not a descent direction either: the gradient is not
         // a number (MINIMIZER_STATUS_INVALID_GRADIENT) or no direction can be found (..._DIRECTION_FAILURE) - not "converged"
-        if (restarted || npairs == 0) { ok = false; st = (dg != dg) ? 7 : 4; break; }
+        if (restarted || lb.n == 0) { ok = false; st = (dg != dg) ? 7 : 4; break; }
         restarted = true;
-        hist = 0;
-        npairs = 0;
+        lb.restart();
         continue;
       }
       ok = (Jn == Jn && Jn <= J + 1.0e-4 * step * dg);
@@ -2357,43 +1904,23 @@ int ecckd_opt_minimize(ecckd_opt* o, int max_iterations, double convergence_crit
       // fewer evaluations per iteration, smaller steps, nothing gained.)
       for (int ls = 1; !ok && ls < 30; ++ls) {
         step *= 0.5;
-        hipLaunchKernelGGL(k_lb_step, vb, vt, 0, ctx->stream, n, step, 0, max_step, 1.0, part_dg, part_dd, x, o->d_dir, bmin,
-                           bmax, xn, o->d_k, sc_step);
-        ECCKD_CHECK(opt_cost_grad_dev(o, xn, gn, &Jn, true));
+        ECCKD_CHECK(trial(step, false, &Jn));
         ok = (Jn == Jn && Jn <= J + 1.0e-4 * step * dg);
       }
-      if (!ok && npairs > 0 && !restarted) {
+      if (!ok && lb.n > 0 && !restarted) {
         // the quasi-Newton direction did not give a sufficient decrease (typically many variables at their bounds):
         // forget the history and try the projected steepest descent before giving up
         restarted = true;
-        hist = 0;
-        npairs = 0;
+        lb.restart();
         continue;
       }
       if (!ok) st = 3;
       break;
     }
     if (!ok) break;
-    // curvature pair into the next ring slot (replacing the oldest when the ring is full); its dots with the pairs that
-    // stay, and the projected gradient at the new point with every pair's dots, in ONE pass; read at the top of the loop
-    if (hist == M) {
-      pend_slot = ord[0];
-      for (int a = 1; a < M; ++a) ord[a - 1] = ord[a];
-      --hist;
-    } else {
-      bool used[M] = {};
-      for (int a = 0; a < hist; ++a) used[ord[a]] = true;
-      pend_slot = 0;
-      while (used[pend_slot]) ++pend_slot;
-    }
-    LbSlots sp;
-    sp.n = hist;
-    for (int a = 0; a < M; ++a) sp.slot[a] = a < hist ? ord[a] : 0;
-    ecckd::slots_mark_pending(h_rb, NPART);
-    hipLaunchKernelGGL(k_lb_update, vb, vt, 0, ctx->stream, n, sp, pend_slot, x, xn, g, gn, bmin, bmax, o->d_q, o->d_S, o->d_Y, part_a);
-    hipLaunchKernelGGL(k_lb_finish, dim3(NPART), dim3(FIN_THREADS), 0, ctx->stream, part_a, nblk, sc);
-    ECCKD_HIP_CHECK(hipGetLastError());
-    pending = true;
+    // curvature pair into the next ring slot (replacing the oldest when the ring is full)
+    const int slot = lb.next_slot();
+    ECCKD_HIP_CHECK(launch_update(lb_slots(lb), slot, x, xn, g, gn));
     std::swap(x, xn);
     std::swap(g, gn);
     J = Jn;
@@ -2415,7 +1942,7 @@ int ecckd_opt_minimize(ecckd_opt* o, int max_iterations, double convergence_crit
 // longwave fluxes come from radiative_transfer_lw with unit emissivity and the surface Planck
 // function at temperature_hl(end) (:343-347), the shortwave direct beam from
 // radiative_transfer_direct_sw at the scene's mu0 with tsi / sum(ssi) scaling (:358-363).
-// The coefficients are used as they are (no exp(log k) round trip).
+// The coefficients are used as they are (no exp(log k) round trip): d_k still holds what ecckd_opt_create uploaded.
 static int run_ckd_impl(ecckd_ctx* ctx, const ecckd_opt_model* m, const ecckd_opt_scene* scene, double* h_od,
                         double* h_rayleigh_od, double* h_planck_hl, double* h_flux, int keep_negative) {
   ECCKD_REQUIRE(ctx && m && scene && m->gases && m->iband_per_g, "ecckd_run_ckd: NULL argument");
@@ -2458,38 +1985,25 @@ static int run_ckd_impl(ecckd_ctx* ctx, const ecckd_opt_model* m, const ecckd_op
   cfg.pressure_weight_power = 0.5;
   cfg.prior_error = 1.0;
   cfg.pressure_corr = cfg.temperature_corr = cfg.conc_corr = 0.5;
-  ecckd_opt* o = nullptr;
-  ECCKD_CHECK(ecckd_opt_create(ctx, &mm, 1, &sc, &cfg, &o));
-  int rc = ECCKD_OK;
-  do {
-    hipError_t e = hipMemcpyAsync(o->d_k, o->h_k0.data(), o->nk * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->d_od_out, o->ncell * ng * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&o->d_flux_out, ncol * 2 * nhl * ng * sizeof(double));
-    if (e != hipSuccess) { rc = ecckd::fail(ECCKD_UNEXPECTED_EXCEPTION, "ecckd_run_ckd: %s", hipGetErrorString(e)); break; }
-    o->eval_ray_ent = o->ray_ent;
-    o->eval_keep_negative = keep_negative;
-    rc = opt_launch_forward(o);
-    if (rc != ECCKD_OK) break;
-    if (h_od) rc = ecckd_d2h(ctx, h_od, o->d_od_out, o->ncell * ng * sizeof(double));
-    if (rc == ECCKD_OK && h_flux) rc = ecckd_d2h(ctx, h_flux, o->d_flux_out, ncol * 2 * nhl * ng * sizeof(double));
-    if (rc == ECCKD_OK && h_planck_hl) rc = ecckd_d2h(ctx, h_planck_hl, o->d_planck, ncol * nhl * ng * sizeof(double));
-  } while (0);
-  if (rc == ECCKD_OK && h_rayleigh_od) {
+  ecckd_opt* created = nullptr;
+  ECCKD_CHECK(ecckd_opt_create(ctx, &mm, 1, &sc, &cfg, &created));
+  const OptPtr o(created);
+  ECCKD_CHECK(opt_diagnostic_pass(o.get(), o->ray_ent, keep_negative, h_od, h_flux, [&] {
+    ECCKD_CHECK(opt_launch_forward(o.get()));
+    return h_planck_hl ? ecckd_d2h(ctx, h_planck_hl, o->d_planck, ncol * nhl * ng * sizeof(double)) : ECCKD_OK;
+  }));
+  if (h_rayleigh_od) {
     // CkdModel::calc_rayleigh_optical_depth (ckd_model.h:242-252)
     for (size_t c = 0; c < ncol; ++c)
       for (size_t l = 0; l < nlay; ++l) {
         const double* p = scene->pressure_hl + c * nhl;
-        const double moles = (p[l + 1] - p[l]) * (1.0 / (ECCKD_ACCEL_GRAVITY * 0.001 * 28.970));
+        const double moles = (p[l + 1] - p[l]) * ot::MOLES_PER_PA;
         for (size_t g = 0; g < ng; ++g)
           h_rayleigh_od[(c * nlay + l) * ng + g] = m->rayleigh_molar_scattering ? moles * m->rayleigh_molar_scattering[g] : 0.0;
       }
   }
-  (void)hipFree(o->d_od_out); (void)hipFree(o->d_flux_out);
-  o->d_od_out = nullptr; o->d_flux_out = nullptr;
-  ecckd_opt_destroy(o);
-  return rc;
+  return ECCKD_OK;
 }
-
 
 int ecckd_run_ckd(ecckd_ctx* ctx, const ecckd_opt_model* m, const ecckd_opt_scene* scene, double* h_od,
                   double* h_rayleigh_od, double* h_planck_hl, double* h_flux) {
@@ -2569,3 +2083,4 @@ int ecckd_scale_lut(ecckd_ctx* ctx, const ecckd_opt_model* m, int nz, const doub
 }
 
 }  // extern "C"
+

@@ -1,0 +1,282 @@
+// ASan/UBSan harness for the optimiser's host tables (csrc/opt_tables.cpp) and its L-BFGS history (csrc/lbfgs_history.hpp): builds
+// the tables at the edge shapes - two-node temperature and pressure axes, two mole fractions, 1 and 128 layers, 1, 64 and 65 g
+// points, a g point of no band, a gas absent from a scene, a profile outside the look-up table on both sides, longwave and shortwave
+// with Rayleigh scattering, both K8b orders - and checks that every index the kernels follow is -1 or in range, that the two K8b
+// orders hold every task once, and that the transpose holds exactly the non-zero entries of the gather.  Then the history: more
+// pairs than the ring holds, one rejected, one restart; the triangular solves are checked by their residuals.
+// build: g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Iecckd_amd/csrc tools/check_opt_tables.cpp \
+//        ecckd_amd/csrc/opt_tables.cpp -o /tmp/check_opt_tables && /tmp/check_opt_tables
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <random>
+#include <tuple>
+#include <vector>
+#include "lbfgs_history.hpp"
+#include "opt_tables.hpp"
+namespace ot = ecckd::opt_tables;
+
+#define REQUIRE(cond)                                                                  \
+  do {                                                                                 \
+    if (!(cond)) { std::printf("%s:%d: %s does not hold (%s)\n", __FILE__, __LINE__, #cond, what); std::exit(1); } \
+  } while (0)
+
+static const char* what = "";
+
+struct Case { int ng, nt, np, nconc, nlay; bool sw, plain; };
+
+// the model and two scenes of one case; the vectors own what the C structs point to
+struct Problem {
+  std::vector<double> log_p, temperature, tpl, planck, ssi, rayleigh, vmr_lut;
+  std::vector<int> iband, present0, present1;
+  std::vector<std::vector<double>> k, kmin, kmax;
+  std::vector<ecckd_opt_gas> gases;
+  ecckd_opt_model m{};
+  std::vector<double> p_hl, t_hl, vmr_fl, flux, mu0, albedo, weights;
+  ecckd_opt_scene scenes[2] = {};
+  ecckd_opt_config cfg{};
+
+  explicit Problem(const Case& c, std::mt19937_64& rng) {
+    std::uniform_real_distribution<double> u(0.5, 1.5);
+    const int ng = c.ng, nt = c.nt, np = c.np, nband = 3;
+    for (int i = 0; i < np; ++i) log_p.push_back(std::log(2.0) + i * (std::log(110000.0) - std::log(2.0)) / (np - 1));
+    for (int it = 0; it < nt; ++it)
+      for (int ip = 0; ip < np; ++ip) temperature.push_back(200.0 + 12.0 * (log_p[ip] - log_p[0]) + 20.0 * it);
+    for (int i = 0; i < 4; ++i) tpl.push_back(150.0 + 60.0 * i);
+    for (size_t i = 0; i < tpl.size() * ng; ++i) planck.push_back(u(rng));
+    for (int g = 0; g < ng; ++g) { iband.push_back(g * nband / ng); ssi.push_back(u(rng)); rayleigh.push_back(1e-6 * u(rng)); }
+    iband[ng - 1] = nband - 1;
+    if (ng > 2) iband[1] = -1;                                // a g point of no band
+    for (int i = 0; i < c.nconc; ++i) vmr_lut.push_back(1e-6 * std::pow(4e4, (double)i / (c.nconc - 1)));
+    const int conc[5] = {0, 2, 1, 3, 1};
+    for (int i = 0; i < 5; ++i) {
+      const size_t n = (size_t)(conc[i] == 2 ? c.nconc : 1) * nt * np * ng;
+      k.emplace_back(n); kmin.emplace_back(n); kmax.emplace_back(n);
+      for (size_t e = 0; e < n; ++e) { k[i][e] = e % 7 == 3 ? 0.0 : u(rng); kmin[i][e] = e % 5 ? 0.5 * k[i][e] : 0.0; kmax[i][e] = 2.0 * k[i][e]; }
+    }
+    for (int i = 0; i < 5; ++i) {
+      ecckd_opt_gas g{};
+      g.conc_dependence = conc[i];
+      g.is_active = i != 4;
+      g.nconc = conc[i] == 2 ? c.nconc : 1;
+      g.vmr = conc[i] == 2 ? vmr_lut.data() : nullptr;
+      g.reference_vmr = 1.8e-6;
+      g.molar_abs = k[i].data(); g.min_molar_abs = kmin[i].data(); g.max_molar_abs = kmax[i].data();
+      gases.push_back(g);
+    }
+    m.ng = ng; m.nt = nt; m.np = np; m.ngas = 5;
+    m.log_pressure = log_p.data(); m.temperature = temperature.data(); m.iband_per_g = iband.data(); m.gases = gases.data();
+    if (c.sw) { m.solar_irradiance = ssi.data(); m.rayleigh_molar_scattering = rayleigh.data(); }
+    else { m.ntp = (int)tpl.size(); m.temperature_planck = tpl.data(); m.planck_function = planck.data(); }
+    // three profiles: inside the table; above its top and colder than its coldest node; below its bottom and hotter
+    const int ncol = 3, nlay = c.nlay, nhl = nlay + 1;
+    const double top[3] = {5.0, 1e-4, 2.0e5}, bottom[3] = {101325.0, 1.0, 9.0e5}, t0[3] = {250.0, 20.0, 900.0};
+    for (int col = 0; col < ncol; ++col)
+      for (int i = 0; i < nhl; ++i) {
+        p_hl.push_back(std::exp(std::log(top[col]) + i * (std::log(bottom[col]) - std::log(top[col])) / nlay));
+        t_hl.push_back(t0[col] + i);
+      }
+    const double vm[5] = {1.0, 3e-3, 4e-4, 0.9e-6, 5e-6};
+    for (int col = 0; col < ncol; ++col)
+      for (int gas = 0; gas < 5; ++gas)
+        for (int l = 0; l < nlay; ++l) vmr_fl.push_back(vm[gas] * (col == 1 ? 1e-4 : col == 2 ? 50.0 : 1.0) * u(rng));   // also outside the mole-fraction axis
+    for (size_t i = 0; i < (size_t)ncol * nhl * std::max(nband, ng); ++i) flux.push_back(100.0 * u(rng));
+    mu0.assign(ncol, 0.6); albedo.assign(nband, 0.2); weights.assign(ng, 0.01);
+    present0.assign(5, 1); present1.assign(5, 1);
+    present1[2] = 0; present1[4] = 0;                          // an active and a fixed gas absent from the second scene
+    for (int s = 0; s < 2; ++s) {
+      ecckd_opt_scene& sc = scenes[s];
+      sc.ncol = ncol; sc.nlay = nlay; sc.nband = nband;
+      sc.pressure_hl = p_hl.data(); sc.temperature_hl = t_hl.data(); sc.vmr_fl = vmr_fl.data();
+      sc.gas_present = s ? present1.data() : present0.data();
+      sc.flux_dn = sc.flux_up = flux.data();
+      sc.mu0 = mu0.data(); sc.tsi = 1361.0; sc.albedo = albedo.data();
+      if (s == 0) {                                            // boundary terms and relative-to fluxes in the first scene only
+        sc.spectral_flux_dn_surf = flux.data();
+        sc.spectral_flux_up_toa = flux.data();
+        sc.spectral_boundary_weights = weights.data();
+        sc.relative_flux_dn = sc.relative_flux_up = flux.data();
+      }
+    }
+    cfg.pressure_weight_power = 0.7; cfg.prior_error = -1.0; cfg.prior_error_scaling = 1.0; cfg.min_prior_error = 0.1; cfg.max_prior_error = 3.0;
+    cfg.pressure_corr = cfg.temperature_corr = 0.95; cfg.conc_corr = 0.9; cfg.cap_relative_linear = 0.8;
+  }
+};
+
+// every value of `order` is -1 or a task in [0, ntask), and every task is there once
+static void check_order(const std::vector<int>& order, size_t ntask, int waves) {
+  std::vector<int> seen(ntask, 0);
+  REQUIRE(order.size() % (8 * waves) == 0);
+  for (int v : order) {
+    REQUIRE(v >= -1 && v < (int)ntask);
+    if (v >= 0) ++seen[v];
+  }
+  for (int n : seen) REQUIRE(n == 1);
+}
+
+static void check_tables(const Case& c, std::mt19937_64& rng) {
+  static char label[160];
+  std::snprintf(label, sizeof(label), "ng=%d nt=%d np=%d nconc=%d nlay=%d sw=%d plain=%d", c.ng, c.nt, c.np, c.nconc, c.nlay, c.sw, c.plain);
+  what = label;
+  Problem pr(c, rng);
+  ot::Tables t;
+  std::string err;
+  const ot::Schedule sched = {4, 64, c.plain};
+  const int rc = ot::build_tables(&pr.m, 2, pr.scenes, &pr.cfg, sched, t, err);
+  if (rc != ECCKD_OK) { std::printf("%s: refused: %s\n", what, err.c_str()); std::exit(1); }
+  const size_t ng = c.ng, nchunk = (ng + 63) / 64;
+  REQUIRE(t.ncol == 6 && t.ncell == 6 * (size_t)c.nlay && t.nx > 0 && t.nx <= t.nk && t.nx % ng == 0 && t.nnode_active == t.nx / ng);
+  REQUIRE(t.k0.size() == t.nk && t.kmin.size() == t.nx && t.kmax.size() == t.nx && (t.ray_ent >= 0) == c.sw);
+  REQUIRE(t.ent_idx.size() == t.ncell * t.nent && t.ent_coef.size() == t.ent_idx.size());
+  std::vector<std::tuple<int, int, double>> gathered, transposed;   // (node, cell, coefficient)
+  size_t absent = 0;
+  for (size_t i = 0; i < t.ent_idx.size(); ++i) {
+    const int idx = t.ent_idx[i];
+    REQUIRE(idx == -1 || (idx >= 0 && idx % c.ng == 0 && (size_t)idx + ng <= t.nk));
+    REQUIRE(std::isfinite(t.ent_coef[i]) && (idx >= 0 || t.ent_coef[i] == 0.0));
+    absent += idx < 0;
+    if (idx >= 0 && (size_t)idx < t.nx && t.ent_coef[i] != 0.0) gathered.emplace_back(idx / c.ng, (int)(i / t.nent), t.ent_coef[i]);
+  }
+  REQUIRE(absent == 3 * (size_t)c.nlay * 8);                  // the two absent gases' four entries each, in the second scene's cells
+  REQUIRE(t.ref_ptr.size() == t.nnode_active + 1 && t.ref_ptr[0] == 0 && (size_t)t.ref_ptr.back() == t.ref_cell.size() &&
+          t.ref_coef.size() == t.ref_cell.size());
+  for (size_t nd = 0; nd < t.nnode_active; ++nd) {
+    REQUIRE(t.ref_ptr[nd] <= t.ref_ptr[nd + 1]);
+    for (int r = t.ref_ptr[nd]; r < t.ref_ptr[nd + 1]; ++r) {
+      REQUIRE(t.ref_cell[r] >= 0 && (size_t)t.ref_cell[r] < t.ncell);
+      REQUIRE(r == t.ref_ptr[nd] || t.ref_cell[r - 1] <= t.ref_cell[r]);   // in cell order: the gradient's fixed summation order
+      transposed.emplace_back((int)nd, t.ref_cell[r], t.ref_coef[r]);
+    }
+  }
+  std::sort(gathered.begin(), gathered.end());
+  std::sort(transposed.begin(), transposed.end());
+  REQUIRE(!gathered.empty() && gathered == transposed);
+  // K8b: the runs cut every node's references into pieces of at most 64, and both orders hold every task once
+  REQUIRE(t.node_run0.size() == t.nnode_active + 1 && t.run_r0.size() == t.run_last.size() && (size_t)t.node_run0.back() == t.run_r0.size());
+  for (size_t nd = 0; nd < t.nnode_active; ++nd) {
+    int at = t.ref_ptr[nd];
+    for (int r = t.node_run0[nd]; r < t.node_run0[nd + 1]; ++r) {
+      REQUIRE(t.run_r0[r] == at && t.run_last[r] > at && t.run_last[r] - at <= 64);
+      at = t.run_last[r];
+    }
+    REQUIRE(at == t.ref_ptr[nd + 1]);
+  }
+  check_order(t.node_order, t.nnode_active * nchunk, sched.waves);
+  check_order(t.run_order, t.run_r0.size() * nchunk, sched.waves);
+  // K9
+  REQUIRE(t.st_nb.size() == t.nnode_active * 27 && t.st_w.size() == t.st_nb.size() && t.node_gas.size() == t.nnode_active);
+  for (size_t i = 0; i < t.st_nb.size(); ++i) {
+    REQUIRE(t.st_nb[i] >= -1 && t.st_nb[i] < (int)t.nnode_active && std::isfinite(t.st_w[i]));
+    REQUIRE((t.st_nb[i] < 0) == (t.st_w[i] == 0.0));
+    REQUIRE(t.st_nb[i] < 0 || t.node_gas[t.st_nb[i]] == t.node_gas[i / 27]);
+  }
+  for (int gas : t.node_gas) REQUIRE(gas >= 0 && gas < 4);
+  REQUIRE(t.inv_sigma2.size() == 5 * ng);
+  for (size_t i = 0; i < 4 * ng; ++i) REQUIRE(t.inv_sigma2[i] >= 1.0 / 9.0 - 1e-12 && t.inv_sigma2[i] <= 100.0 + 1e-9);   // sigma held in [0.1, 3]
+  // bands
+  REQUIRE(t.band_ptr.size() == (size_t)t.nband + 1 && t.band_g.size() == ng && t.band_ptr[0] == 0);
+  for (int b = 0; b < t.nband; ++b)
+    for (int q = t.band_ptr[b]; q < t.band_ptr[b + 1]; ++q) REQUIRE(t.band_g[q] >= 0 && t.band_g[q] < c.ng && t.band[t.band_g[q]] == b);
+  REQUIRE(t.band_ptr.back() == c.ng - (c.ng > 2));
+  // per-profile arrays
+  const size_t nhl = c.nlay + 1;
+  REQUIRE(t.planck.size() == t.ncol * nhl * ng && t.semis.size() == t.ncol * t.nband && t.conv.size() == t.ncell && t.lw.size() == t.ncell);
+  REQUIRE(t.hr.size() == t.ncell * t.nband && t.fdn.size() == t.ncol * nhl * t.nband && t.fup.size() == t.fdn.size());
+  REQUIRE(t.have_boundary && t.sfds.size() == t.ncol * ng && t.sfut.size() == t.sfds.size() && t.mu0.size() == (c.sw ? t.ncol : 0));
+  REQUIRE(t.rel.size() == t.ncol * 2 * nhl * ng && t.rel[3 * 2 * nhl * ng] == 0.0);   // the second scene brings none
+  for (double v : t.lw) REQUIRE(std::isfinite(v));
+  for (double v : t.planck) REQUIRE(std::isfinite(v));
+  // initial state and bounds
+  std::vector<double> x(t.nx), lo(t.nx), hi(t.nx);
+  ot::initial_state(t, x.data(), lo.data(), hi.data());
+  for (size_t e = 0; e < t.nx; ++e) REQUIRE(t.k0[e] > 0.0 ? (lo[e] <= x[e] && x[e] <= hi[e]) : x[e] == ot::MIN_X);
+}
+
+static void check_refusals() {
+  what = "refusals";
+  std::mt19937_64 rng(1);
+  const Case c = {12, 5, 16, 4, 18, false, false};
+  std::string err;
+  { Problem p(c, rng); REQUIRE(ot::check_arguments(&p.m, 2, p.scenes, &p.cfg, err) == ECCKD_OK); }
+  { Problem p(c, rng); REQUIRE(ot::check_arguments(nullptr, 2, p.scenes, &p.cfg, err) == ECCKD_PARAMETER_ERROR); }
+  { Problem p(c, rng); p.m.nt = 1; REQUIRE(ot::check_arguments(&p.m, 2, p.scenes, &p.cfg, err) == ECCKD_PARAMETER_ERROR); }
+  { Problem p(c, rng); p.m.ntp = 1; REQUIRE(ot::check_arguments(&p.m, 2, p.scenes, &p.cfg, err) == ECCKD_PARAMETER_ERROR); }
+  { Problem p(c, rng); p.m.logarithmic_interpolation = 1; REQUIRE(ot::check_arguments(&p.m, 2, p.scenes, &p.cfg, err) == ECCKD_PARAMETER_ERROR); }
+  { Problem p(c, rng); p.gases[1].nconc = 1; REQUIRE(ot::check_arguments(&p.m, 2, p.scenes, &p.cfg, err) == ECCKD_PARAMETER_ERROR && err == "ecckd_opt_create: gas 1 is ill-defined"); }
+  { Problem p(c, rng); for (auto& g : p.gases) g.is_active = 0; REQUIRE(ot::check_arguments(&p.m, 2, p.scenes, &p.cfg, err) == ECCKD_PARAMETER_ERROR); }
+  { Problem p(c, rng); p.scenes[0].nlay = p.scenes[1].nlay = 129; REQUIRE(ot::check_arguments(&p.m, 2, p.scenes, &p.cfg, err) == ECCKD_PARAMETER_ERROR); }
+  { Problem p(c, rng); p.scenes[1].nband = 2; REQUIRE(ot::check_arguments(&p.m, 2, p.scenes, &p.cfg, err) == ECCKD_PARAMETER_ERROR && err == "ecckd_opt_create: scene 1 is inconsistent (nlay/nband/arrays)"); }
+}
+
+// The history over 20 accepted pairs, one rejected and one restart.  The dots are those of vectors that exist (S, Y, q random),
+// so S^T Y is what a run would see; the direction's coefficients are checked through R u = p.
+static void check_history() {
+  what = "history";
+  constexpr int M = ecckd::LbfgsHistory::M, N = 40;
+  std::mt19937_64 rng(7);
+  std::normal_distribution<double> nrm;
+  auto dot = [](const std::vector<double>& a, const std::vector<double>& b) { double s = 0.0; for (int i = 0; i < N; ++i) s += a[i] * b[i]; return s; };
+  std::vector<std::vector<double>> S(M, std::vector<double>(N)), Y(M, std::vector<double>(N));
+  ecckd::LbfgsHistory lb;
+  double dots[3 + 5 * M];
+  int accepted = 0;
+  for (int round = 0; round < 24; ++round) {
+    const int slot = lb.next_slot();
+    REQUIRE(slot >= 0 && slot < M && lb.pending && lb.n < M);
+    for (int a = 0; a < lb.n; ++a) REQUIRE(lb.ord[a] != slot);
+    const bool reject = round == 9;
+    for (int i = 0; i < N; ++i) { S[slot][i] = nrm(rng); Y[slot][i] = (reject ? -1.0 : 1.0) * S[slot][i] + 0.1 * nrm(rng); }
+    std::vector<double> q(N);
+    for (double& v : q) v = nrm(rng);
+    int slots[M];
+    lb.slots(slots);
+    for (double& v : dots) v = 0.0;
+    dots[0] = dot(q, q);
+    for (int a = 0; a <= lb.n; ++a) {                          // the stored pairs, then the pending one as the newest
+      const int s = a < lb.n ? slots[a] : slot;
+      dots[1 + a] = dot(S[s], q);
+      dots[1 + M + a] = dot(Y[s], q);
+    }
+    double* rp = dots + 1 + 2 * M;
+    rp[0] = dot(S[slot], Y[slot]); rp[1] = dot(Y[slot], Y[slot]);
+    for (int a = 0; a < lb.n; ++a) { rp[2 + a] = dot(S[slot], Y[slots[a]]); rp[2 + M + a] = dot(S[slots[a]], Y[slot]); rp[2 + 2 * M + a] = dot(Y[slot], Y[slots[a]]); }
+    const int before = lb.n;
+    lb.absorb_pending(dots);
+    REQUIRE(!lb.pending && lb.n == before + (reject ? 0 : 1) && lb.n <= M);
+    accepted += !reject;
+    if (!reject) REQUIRE(lb.ord[lb.n - 1] == slot && lb.gamma == rp[0] / rp[1]);
+    lb.slots(slots);
+    for (int a = 0; a < M; ++a)
+      for (int b = 0; b < a; ++b) REQUIRE(a >= lb.n || slots[a] != slots[b]);
+    double cs[M], cy[M];
+    const double gamma = lb.coefficients(dots, cs, cy);
+    REQUIRE(gamma == (lb.n > 0 ? lb.gamma : 1.0));
+    for (int a = 0; a < M; ++a) REQUIRE(std::isfinite(cs[a]) && std::isfinite(cy[a]) && (a < lb.n || (cs[a] == 0.0 && cy[a] == 0.0)));
+    if (!reject)
+      for (int a = 0; a < lb.n; ++a) {                         // R u = p with u = cy / gamma, R the upper triangle of S^T Y in age order
+        double r = -dots[1 + a];
+        for (int b = a; b < lb.n; ++b) r += dot(S[slots[a]], Y[slots[b]]) * cy[b] / gamma;
+        REQUIRE(std::fabs(r) < 1e-8 * (1.0 + std::fabs(dots[1 + a])));
+      }
+    if (round == 15) { lb.restart(); REQUIRE(lb.n == 0 && lb.coefficients(dots, cs, cy) == 1.0 && cs[0] == 0.0); }
+  }
+  REQUIRE(accepted == 23 && lb.n == M);
+}
+
+int main() {
+  std::mt19937_64 rng(2024);
+  int ncase = 0;
+  for (int ng : {1, 64, 65})
+    for (int nlay : {1, 128})
+      for (int small : {0, 1})
+        for (int sw : {0, 1}) {
+          const Case c = {ng, small ? 2 : 5, small ? 2 : 16, small ? 2 : 4, nlay, sw != 0, (ncase % 3) == 1};
+          check_tables(c, rng);
+          ++ncase;
+        }
+  check_refusals();
+  check_history();
+  std::printf("check_opt_tables: %d table cases, the refusals and the history: no complaint\n", ncase);
+  return 0;
+}
