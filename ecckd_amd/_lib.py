@@ -119,6 +119,7 @@ SIGNATURES = {
     "ecckd_opt_nx": (C.c_size_t, [C.c_void_p]),
     "ecckd_opt_initial_state": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, _c_double_p]),
     "ecckd_opt_cost_grad": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, _c_double_p]),
+    "ecckd_opt_forward_plan": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ecckd_opt_forward": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, _c_double_p]),
     "ecckd_opt_set_evaluator": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ecckd_opt_set_progress": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -329,6 +330,11 @@ class OptConfig(C.Structure):
                 ("pressure_weight_power", C.c_double), ("prior_error", C.c_double), ("min_prior_error", C.c_double),
                 ("max_prior_error", C.c_double), ("prior_error_scaling", C.c_double), ("pressure_corr", C.c_double),
                 ("temperature_corr", C.c_double), ("conc_corr", C.c_double), ("cap_relative_linear", C.c_double)]
+
+
+class ForwardPlan(C.Structure):
+    _fields_ = [("cells", C.c_int), ("nc_template", C.c_int), ("nb", C.c_int), ("threads", C.c_int), ("ngpad", C.c_int),
+                ("lgroups", C.c_int), ("lds_bytes", C.c_size_t)]
 
 
 TRACE_FN = C.CFUNCTYPE(None, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p)

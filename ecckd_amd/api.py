@@ -989,6 +989,14 @@ class Optimizer:
         check(self.lib.ecckd_opt_cost_grad(self.handle, _hptr(x), C.byref(J), _hptr(g) if want_grad else None))
         return (J.value, g) if want_grad else J.value
 
+    def forward_plan(self):
+        """The forward kernel the next cost_grad / forward of this handle launches (ecckd_opt_forward_plan), at the environment
+        as it is now: dict(cells: bool, nc_template, nb, threads, ngpad, lgroups, lds_bytes)."""
+        p = _lib.ForwardPlan()
+        check(self.lib.ecckd_opt_forward_plan(self.handle, C.byref(p)))
+        return dict(cells=bool(p.cells), nc_template=p.nc_template, nb=p.nb, threads=p.threads, ngpad=p.ngpad,
+                    lgroups=p.lgroups, lds_bytes=int(p.lds_bytes))
+
     def forward(self, x, unclamped=False):
         """Total optical depths and CKD fluxes at state x; unclamped: without the clamp of negative optical depths (the
         reference's "relative_to" evaluation, optimize_lut.cpp:229-234)."""

@@ -1578,45 +1578,70 @@ int launch_cells_nb(int nb, ecckd_opt* o, int threads, size_t lds, int ngpad) {
   }
 }
 
-int launch_cells_for(int nc, int nb, ecckd_opt* o, int threads, size_t lds, int ngpad) {
+int launch_cells_for(int nc, int nb, ecckd_opt* o, int threads, size_t lds, int ngpad) {   // nc: 4 or 8, the instance
   if (o->do_sw) return nc <= 4 ? launch_cells_nb<4, true>(nb, o, threads, lds, ngpad) : launch_cells_nb<8, true>(nb, o, threads, lds, ngpad);
   return nc <= 4 ? launch_cells_nb<4, false>(nb, o, threads, lds, ngpad) : launch_cells_nb<8, false>(nb, o, threads, lds, ngpad);
+}
+
+// Which K8a kernel a forward pass runs and how it is launched: a function of the shapes and the two environment knobs alone
+// (ecckd_opt_forward_plan reports it, opt_launch_forward launches from it and from nothing else).
+//   cell-parallel kernel: longwave 1 024 threads (16 layer groups at ng = 64, one block per CU), shortwave 512 (8 groups, 79 KB
+//   of LDS: two blocks per CU), `env_threads` (64 ... 1024, else 0) in place of either; up to 8 cells per thread (the <4> and
+//   <8> instances), nb = 8-entry batches of a cell's table among its first 64 entries (1 ... 4 in straight-line code, 0 = the loop);
+//   else the general kernel, whose LDS tile the caller has to check against 160 KB.
+ecckd_forward_plan forward_plan(bool do_sw, int nlay, int ng, int nband, int nent, int env_threads, bool force_generic) {
+  ecckd_forward_plan p{};
+  const int nhl = nlay + 1;
+  p.ngpad = (ng + 63) / 64 * 64;
+  {
+    const int threads_c = env_threads ? env_threads : (do_sw ? 512 : 1024);
+    const int lgroups = std::max(1, threads_c / p.ngpad);
+    const int nc = (nlay + lgroups - 1) / lgroups;
+    const size_t lds = ((do_sw ? (size_t)0 : (size_t)nlay * ng) + 2 * (size_t)nhl * ng + 2 * (size_t)nhl * nband + (size_t)nlay * nband +
+                        nlay + 2 * (size_t)nhl + 16) * sizeof(double) + ((size_t)nband + 1 + ng) * sizeof(int);
+    if (!force_generic && nc <= 8 && lds <= 160 * 1024 && p.ngpad * lgroups <= 1024 && nhl * nband <= K8A_MAXR * p.ngpad * lgroups) {
+      p.cells = 1;
+      p.nc_template = nc <= 4 ? 4 : 8;
+      const int nb = (std::min(nent, 64) + K8A_GB - 1) / K8A_GB;       // 8-entry batches of a cell's table (first 64 entries)
+      p.nb = nb <= 4 ? nb : 0;
+      p.threads = p.ngpad * lgroups;
+      p.lgroups = lgroups;
+      p.lds_bytes = lds;
+      return p;
+    }
+  }
+  const int k8a_threads = env_threads ? env_threads : 1024;
+  p.lgroups = std::max(1, k8a_threads / p.ngpad);
+  p.threads = p.ngpad * p.lgroups;
+  p.lds_bytes = ((size_t)nlay * ng + 2 * (size_t)nhl * ng + 4 * (size_t)nhl * nband + 16) * sizeof(double) +
+                ecckd_align_up((size_t)nlay * ng, 16);
+  return p;
+}
+
+// the plan of this handle at the environment as it is now (both knobs are read at every call: the tests switch between the
+// kernels and the block sizes within one process)
+ecckd_forward_plan opt_forward_plan(const ecckd_opt* o) {
+  const char* e = std::getenv("ECCKD_K8A_THREADS");
+  const int v = e ? std::atoi(e) : 0;
+  const char* env_generic = std::getenv("ECCKD_K8A_GENERIC");
+  return forward_plan(o->do_sw, o->nlay, o->ng, o->nband, o->nent, v >= 64 && v <= 1024 ? v : 0, env_generic && env_generic[0] == '1');
 }
 
 // K8a at the coefficients in d_k: the cell-parallel kernel where the profile fits it, else the general one.
 int opt_launch_forward(ecckd_opt* o) {
   ecckd_ctx* ctx = o->ctx;
-  const int nlay = o->nlay, nhl = nlay + 1, ng = o->ng, nband = o->nband;
-  const int ngpad = (ng + 63) / 64 * 64;
-  static const int env_threads = [] { const char* e = std::getenv("ECCKD_K8A_THREADS"); const int v = e ? std::atoi(e) : 0; return v >= 64 && v <= 1024 ? v : 0; }();
-  const char* env_generic = std::getenv("ECCKD_K8A_GENERIC");       // read at every call: the tests switch between the two kernels
-  const bool force_generic = env_generic && env_generic[0] == '1';
-  // the cell-parallel kernel: longwave 1 024 threads (16 layer groups at ng = 64, one block per CU), shortwave 512 (8 groups,
-  // 79 KB of LDS: two blocks per CU); up to 8 cells per thread, else the general kernel
-  {
-    const int threads_c = env_threads ? env_threads : (o->do_sw ? 512 : 1024);
-    const int lgroups = std::max(1, threads_c / ngpad);
-    const int nc = (nlay + lgroups - 1) / lgroups;
-    const size_t lds = ((o->do_sw ? (size_t)0 : (size_t)nlay * ng) + 2 * (size_t)nhl * ng + 2 * (size_t)nhl * nband + (size_t)nlay * nband +
-                        nlay + 2 * (size_t)nhl + 16) * sizeof(double) + ((size_t)nband + 1 + ng) * sizeof(int);
-    if (!force_generic && nc <= 8 && lds <= 160 * 1024 && ngpad * lgroups <= 1024 && nhl * nband <= K8A_MAXR * ngpad * lgroups) {
-      const int threads = ngpad * lgroups;
-      const int nb = (std::min(o->nent, 64) + K8A_GB - 1) / K8A_GB;       // 8-entry batches of a cell's table (first 64 entries)
-      ECCKD_CHECK(launch_cells_for(nc, nb, o, threads, lds, ngpad));
-      ECCKD_HIP_CHECK(hipGetLastError());
-      return ECCKD_OK;
-    }
+  const ecckd_forward_plan p = opt_forward_plan(o);
+  if (p.cells) {
+    ECCKD_CHECK(launch_cells_for(p.nc_template, p.nb, o, p.threads, p.lds_bytes, p.ngpad));
+    ECCKD_HIP_CHECK(hipGetLastError());
+    return ECCKD_OK;
   }
-  const int k8a_threads = env_threads ? env_threads : 1024;
-  const int lgroups = std::max(1, k8a_threads / ngpad);
-  const int threads = ngpad * lgroups;
-  const size_t lds = ((size_t)nlay * ng + 2 * (size_t)nhl * ng + 4 * (size_t)nhl * nband + 16) * sizeof(double) +
-                     ecckd_align_up((size_t)nlay * ng, 16);
-  ECCKD_REQUIRE(lds <= 160 * 1024, "ecckd_opt_cost_grad: nlay*ng too large for the per-profile LDS tile (%zu B)", lds);
+  const int nlay = o->nlay, ng = o->ng, nband = o->nband;
+  ECCKD_REQUIRE(p.lds_bytes <= 160 * 1024, "ecckd_opt_cost_grad: nlay*ng too large for the per-profile LDS tile (%zu B)", p.lds_bytes);
   ECCKD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_opt_forward_adjoint),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  hipLaunchKernelGGL(k_opt_forward_adjoint, dim3((unsigned)o->ncol), dim3(threads), lds, ctx->stream, o->do_sw ? 1 : 0,
-                     o->d_mu0, o->eval_ray_ent, o->eval_keep_negative, o->d_rel, nlay, ng, ngpad, nband, o->nent, o->d_k, o->d_ent_idx, o->d_ent_coef, o->d_band, o->d_planck, o->d_semis, o->d_conv,
+  hipLaunchKernelGGL(k_opt_forward_adjoint, dim3((unsigned)o->ncol), dim3(p.threads), p.lds_bytes, ctx->stream, o->do_sw ? 1 : 0,
+                     o->d_mu0, o->eval_ray_ent, o->eval_keep_negative, o->d_rel, nlay, ng, p.ngpad, nband, o->nent, o->d_k, o->d_ent_idx, o->d_ent_coef, o->d_band, o->d_planck, o->d_semis, o->d_conv,
                      o->d_lw, o->d_hr, o->d_fdn, o->d_fup, o->d_sfds, o->d_sfut, o->cfg.flux_weight,
                      o->cfg.flux_profile_weight, o->cfg.broadband_weight, o->cfg.spectral_boundary_weight,
                      o->cfg.negative_od_penalty, o->d_dtau, o->d_jcol, o->d_od_out, o->d_flux_out);
@@ -1725,6 +1750,13 @@ int opt_diagnostic_pass(ecckd_opt* o, int ray_ent, int keep_negative, double* h_
 }  // namespace
 
 extern "C" {
+
+// The K8a kernel the next forward pass of this handle runs (forward_plan above), at the environment as it is now.
+int ecckd_opt_forward_plan(ecckd_opt* o, ecckd_forward_plan* out) {
+  ECCKD_REQUIRE(o && out, "ecckd_opt_forward_plan: NULL argument");
+  *out = opt_forward_plan(o);
+  return ECCKD_OK;
+}
 
 int ecckd_opt_cost_grad(ecckd_opt* o, const double* h_x, double* J, double* h_grad) {
   ECCKD_REQUIRE(o && h_x && J, "ecckd_opt_cost_grad: NULL argument");

@@ -740,6 +740,17 @@ size_t ecckd_opt_nx(ecckd_opt* opt);
 /* initial state (MIN_X = -1e20 where the coefficient is 0) and log-space bounds, solve_adept.cpp:335-353 */
 int ecckd_opt_initial_state(ecckd_opt* opt, double* h_x, double* h_x_min, double* h_x_max);
 int ecckd_opt_cost_grad(ecckd_opt* opt, const double* h_x, double* J, double* h_grad);
+/* Which forward kernel ecckd_opt_cost_grad / ecckd_opt_forward launch for this handle, and how: decided from the shapes
+ * (shortwave?, nlay, ng, nband, entries per cell of the look-up tables) and from the environment, read at every call:
+ * ECCKD_K8A_THREADS (64 ... 1024: threads per block in place of 1024 longwave / 512 shortwave), ECCKD_K8A_GENERIC=1 (the general
+ * kernel).  cells: the cell-parallel kernel, instance <nc_template, shortwave, nb> (nc_template 4 or 8 cells per thread; nb 1 ... 4
+ * eight-entry batches in straight-line code, 0 = the loop for more than 32 entries); cells == 0: the general kernel (nc_template
+ * = nb = 0), which refuses lds_bytes > 160 KB when it is launched.  threads = ngpad * lgroups, ngpad = ng rounded up to 64. */
+typedef struct {
+  int cells, nc_template, nb, threads, ngpad, lgroups;
+  size_t lds_bytes;
+} ecckd_forward_plan;
+int ecckd_opt_forward_plan(ecckd_opt* opt, ecckd_forward_plan* plan);
 /* total optical depth [ncol][nlay][ng] and CKD fluxes [ncol][2][nlay+1][ng] at state h_x
  * (calc_total_optical_depth, LblFluxes::calc_ckd_fluxes lbl_fluxes.cpp:443-471) */
 int ecckd_opt_forward(ecckd_opt* opt, const double* h_x, double* h_od, double* h_flux);

@@ -439,8 +439,10 @@ def test_cell_parallel_kernel_matches_the_general_one(ctx, oracle, sw, threads, 
     """k_opt_forward_adjoint_cells (exp / division of every cell side by side, one FMA per layer on the sequential wave) and
     k_opt_forward_adjoint (everything on the sequential wave): optical depths identical, fluxes, cost and gradient equal to
     rounding - both follow the same recurrences, only the grouping of the layer's source terms differs (a few ulp)."""
-    if threads:                         # 128 threads = 2 layer groups: 9 of the 18 layers per thread, which the kernel does not
-                                        # take (8 cells at most): both runs use the general kernel; 192: 3 groups, 6 cells (NC = 8)
+    if threads:                         # (the parameter keeps its old name.)  128 threads would be 2 layer groups: 9 of the 18
+                                        # layers per thread, which the cell-parallel kernel does not take (8 cells at most) - both
+                                        # runs would use the general kernel; 192: 3 groups, 6 cells per thread (NC = 8).  The
+                                        # library reads the variable at every call, and the plan below proves what ran.
         threads = 192
         monkeypatch.setenv("ECCKD_K8A_THREADS", str(threads))
     model, scenes, cfg, orc = (_problem_sw if sw else _problem)(oracle, seed=4, boundary=True, ch4_low=True,
@@ -455,6 +457,13 @@ def test_cell_parallel_kernel_matches_the_general_one(ctx, oracle, sw, threads, 
     out = {}
     for generic in ("1", "0"):
         monkeypatch.setenv("ECCKD_K8A_GENERIC", generic)
+        plan = opt.forward_plan()
+        if generic == "1":
+            assert not plan["cells"]
+        elif threads:
+            assert (plan["cells"], plan["nc_template"], plan["lgroups"], plan["threads"]) == (True, 8, 3, 192)
+        else:
+            assert (plan["cells"], plan["nc_template"], plan["threads"]) == (True, 4, 512 if sw else 1024)
         J, g = opt.cost_grad(x)
         od, fl = opt.forward(x)
         od_u, fl_u = opt.forward(x, unclamped=True)

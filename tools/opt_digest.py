@@ -6,8 +6,9 @@ Models and scenes of tests/ckd_synth.py with fixed seeds; the truth fluxes are f
 shortwave (Rayleigh on), with boundary terms, with relative-to fluxes, with 70 g points; longwave with an active gas absent from a
 scene, with temperature_fl given, without min/max arrays, with the prior's sigma estimated from them, with cap_relative_linear
 biting, and with pressure_weight_power 1.0 and 0.7 beside the base's 0.5.  The two base cases also run under ECCKD_K8A_GENERIC=1,
-ECCKD_K8A_THREADS=128 and ECCKD_K8B_PLAIN_ORDER=1.  Each setting runs in a child process of its own (the threads knob is read once
-per process), one after another, each under its own time limit; a child that fails ends the run.  Prints one JSON object.
+ECCKD_K8A_THREADS=128 and ECCKD_K8B_PLAIN_ORDER=1.  Each setting runs in a child process of its own
+(ECCKD_K8B_PLAIN_ORDER is read when a handle is created, the two K8a knobs at every forward launch: a child per setting keeps
+the settings apart), one after another, each under its own time limit; a child that fails ends the run.  Prints one JSON object.
 usage: python tools/opt_digest.py"""
 import hashlib
 import json
