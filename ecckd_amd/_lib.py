@@ -115,6 +115,7 @@ SIGNATURES = {
     "ecckd_partition_set_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ecckd_partition_status_string": (C.c_char_p, [C.c_int]),
     "ecckd_opt_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "ecckd_opt_create_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint, C.POINTER(C.c_void_p)]),
     "ecckd_opt_destroy": (C.c_int, [C.c_void_p]),
     "ecckd_opt_nx": (C.c_size_t, [C.c_void_p]),
     "ecckd_opt_initial_state": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, _c_double_p]),

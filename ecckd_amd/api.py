@@ -804,6 +804,7 @@ class GasSW(GasLW):
 # optimize_lut
 
 CONC = {"none": 0, "linear": 1, "lut": 2, "relative-linear": 3}
+OPT_RAYLEIGH_SCATTERING = 1          # ECCKD_OPT_RAYLEIGH_SCATTERING
 
 
 def _f64c(a):
@@ -886,11 +887,15 @@ class Optimizer:
     scenes: list of dict(pressure_hl[ncol,nhl], temperature_hl, vmr_fl[ncol,ngas,nlay], flux_dn[ncol,nhl,nband],
                          flux_up, gas_present=None, surf_emissivity=None, spectral_flux_dn_surf=None,
                          spectral_flux_up_toa=None)
+    rayleigh_scattering: the shortwave forward model is the two-stream transfer with Rayleigh scattering
+        (ECCKD_OPT_RAYLEIGH_SCATTERING of ecckd_opt_create_ex): flux_dn, spectral_flux_dn_surf and relative_flux_dn are total
+        (direct + diffuse) downwelling fluxes, forward() returns (total dn, up), the heating rates come from dn - up.
     """
 
-    def __init__(self, ctx, model, scenes, **cfg):
+    def __init__(self, ctx, model, scenes, rayleigh_scattering=False, **cfg):
         self.ctx = ctx
         self.lib = ctx.lib
+        self.rayleigh_scattering = bool(rayleigh_scattering)
         keep = []
         m = _opt_model(model, keep)
         sc = (_lib.OptScene * len(scenes))()
@@ -905,8 +910,8 @@ class Optimizer:
         for k, v in defaults.items():
             setattr(c, k, float(v))
         h = C.c_void_p()
-        check(self.lib.ecckd_opt_create(ctx.handle, C.byref(m), len(scenes), C.cast(sc, C.c_void_p), C.byref(c),
-                                        C.byref(h)))
+        check(self.lib.ecckd_opt_create_ex(ctx.handle, C.byref(m), len(scenes), C.cast(sc, C.c_void_p), C.byref(c),
+                                           OPT_RAYLEIGH_SCATTERING if rayleigh_scattering else 0, C.byref(h)))
         self.handle = h
         self.nx = int(self.lib.ecckd_opt_nx(h))
         self.ng = m.ng
@@ -991,11 +996,13 @@ class Optimizer:
 
     def forward_plan(self):
         """The forward kernel the next cost_grad / forward of this handle launches (ecckd_opt_forward_plan), at the environment
-        as it is now: dict(cells: bool, nc_template, nb, threads, ngpad, lgroups, lds_bytes)."""
+        as it is now: dict(kernel, cells: bool, nc_template, nb, threads, ngpad, lgroups, lds_bytes, rayleigh: bool).  kernel
+        names what the header's `cells` encodes: "general" (0), "cells" (1: the cell-parallel kernel, the only one for which
+        cells is True and nc_template / nb mean something) or "rayleigh" (2: the one kernel of a scattering handle)."""
         p = _lib.ForwardPlan()
         check(self.lib.ecckd_opt_forward_plan(self.handle, C.byref(p)))
-        return dict(cells=bool(p.cells), nc_template=p.nc_template, nb=p.nb, threads=p.threads, ngpad=p.ngpad,
-                    lgroups=p.lgroups, lds_bytes=int(p.lds_bytes))
+        return dict(kernel=("general", "cells", "rayleigh")[p.cells], cells=p.cells == 1, nc_template=p.nc_template, nb=p.nb,
+                    threads=p.threads, ngpad=p.ngpad, lgroups=p.lgroups, lds_bytes=int(p.lds_bytes), rayleigh=p.cells == 2)
 
     def forward(self, x, unclamped=False):
         """Total optical depths and CKD fluxes at state x; unclamped: without the clamp of negative optical depths (the

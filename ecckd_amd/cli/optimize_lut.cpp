@@ -12,6 +12,12 @@
 // fluxes of the training files are summed per g point on the GPU (ecckd_gmap_sum_rows, lbl_fluxes.cpp:180-246,
 // :300-325); g points stored inside the CKD file take precedence over "gpointfile" (CkdModel::read_g_points).
 // Not handled: rayleigh_prior_error > 0 (Rayleigh scattering as an optimised pseudo-gas).
+// rayleigh_scattering (bool, default 0; not a key of the reference): the shortwave forward model is the two-stream transfer
+// with Rayleigh scattering (ECCKD_OPT_RAYLEIGH_SCATTERING).  The model needs a Rayleigh coefficient; every training_input and
+// relative_to file must carry the global attribute rayleigh_scattering = "two-stream" that ckdmip_sw --rayleigh writes.  The
+// truth's downwelling flux is then the total one (band_flux_dn_sw, or spectral_flux_dn_sw), the per-g surface flux comes
+// from spectral_flux_dn_surf_sw, the band albedo is sum(up) / sum(total dn) at the surface, nothing is masked
+// (max_no_rayleigh_wavenumber is read and ignored) and relative_to is evaluated through a scattering handle.
 // The cost function, its gradient and the L-BFGS iteration run on the GPU (ecckd_opt_*); adept::Minimizer is
 // replaced by the library's own L-BFGS, so iteration counts differ from the reference's.
 #include <algorithm>
@@ -53,9 +59,15 @@ void map_bands(std::vector<double>& a, size_t nrow, int nb_file, const std::vect
   a.swap(out);
 }
 
-Scene read_lbl_fluxes(const std::string& path, const std::vector<int>& band_mapping, const Device& dev, const GPointMap& gp) {
+Scene read_lbl_fluxes(const std::string& path, const std::vector<int>& band_mapping, const Device& dev, const GPointMap& gp, bool scattering) {
   NcIn f(path);
   Scene s;
+  if (scattering) {
+    // training a scattering model on no-scattering fluxes would be a silent science error
+    std::string how;
+    if (!f.exist("mu0") || !f.att_text("rayleigh_scattering", how) || how != "two-stream")
+      fail(ECCKD_PARAMETER_ERROR, "rayleigh_scattering=1: %s does not hold shortwave fluxes with the global attribute rayleigh_scattering = \"two-stream\"", path.c_str());
+  }
   std::vector<size_t> sh = f.shape("pressure_hl");
   const int ncol_file = (int)sh.at(0);
   s.nlay = (int)sh.at(1) - 1;
@@ -106,9 +118,12 @@ Scene read_lbl_fluxes(const std::string& path, const std::vector<int>& band_mapp
     };
     std::vector<double> bb = pick(f.read("flux_dn_direct_sw"), nhl);
     s.tsi = bb[0] / s.mu0[0];                                   // :116
-    if (f.exist("spectral_flux_dn_direct_sw")) { dn_name = "spectral_flux_dn_direct_sw"; up_name = "spectral_flux_up_sw"; }
-    else if (f.exist("band_flux_dn_direct_sw")) {
-      dn_name = "band_flux_dn_direct_sw"; up_name = "band_flux_up_sw"; w1_name = "band_wavenumber1_sw"; w2_name = "band_wavenumber2_sw";
+    // the downwelling flux the optimiser is trained on: the direct beam, or with scattering the total (direct + diffuse)
+    const std::string spectral_dn = scattering ? "spectral_flux_dn_sw" : "spectral_flux_dn_direct_sw";
+    const std::string band_dn = scattering ? "band_flux_dn_sw" : "band_flux_dn_direct_sw";
+    if (f.exist(spectral_dn)) { dn_name = spectral_dn; up_name = "spectral_flux_up_sw"; }
+    else if (f.exist(band_dn)) {
+      dn_name = band_dn; up_name = "band_flux_up_sw"; w1_name = "band_wavenumber1_sw"; w2_name = "band_wavenumber2_sw";
       s.have_band = true;
     } else fail(ECCKD_PARAMETER_ERROR, "%s: no spectral or band fluxes", path.c_str());
     {
@@ -151,7 +166,7 @@ Scene read_lbl_fluxes(const std::string& path, const std::vector<int>& band_mapp
     }
   }
   // high-resolution fluxes at the boundaries -> sums over the wavenumbers of each g point (:180-246, :300-325)
-  const std::string hi_dn = s.is_sw ? "spectral_flux_dn_direct_surf_sw" : "spectral_flux_dn_surf_lw";
+  const std::string hi_dn = s.is_sw ? (scattering ? "spectral_flux_dn_surf_sw" : "spectral_flux_dn_direct_surf_sw") : "spectral_flux_dn_surf_lw";
   const std::string hi_up = s.is_sw ? "spectral_flux_up_toa_sw" : "spectral_flux_up_toa_lw";
   if (f.exist(hi_dn) && f.exist(hi_up)) {
     if (!gp.gmap) {
@@ -294,6 +309,8 @@ int main(int argc, char** argv) {
     if (config.exist("bounded_minimization")) config.read(is_bounded, "bounded_minimization");
     bool remove_min_max = false;                                            // :243-244
     if (config.exist("remove_min_max")) config.read(remove_min_max, "remove_min_max");
+    bool rayleigh_scattering = false;
+    if (config.exist("rayleigh_scattering")) config.read(rayleigh_scattering, "rayleigh_scattering");
     if (rayleigh_prior_error > 0.0) fail(ECCKD_PARAMETER_ERROR, "rayleigh_prior_error > 0 (optimised Rayleigh scattering) is not supported by this tool");
     std::vector<int> band_mapping;
     if (config.exist("band_mapping")) config.read(band_mapping, "band_mapping");
@@ -301,6 +318,10 @@ int main(int argc, char** argv) {
     LOG("Reading %s\n", input.c_str());
     CkdFile model = read_ckd(paths.find(input));
     model.model_id = model_id;
+    if (rayleigh_scattering && !(model.is_sw && !model.rayleigh_molar_scattering.empty()))
+      fail(ECCKD_PARAMETER_ERROR, "rayleigh_scattering=1 needs a shortwave CKD model with a Rayleigh coefficient, %s is not one", input.c_str());
+    if (rayleigh_scattering) LOG("Rayleigh scattering is modelled (two-stream): max_no_rayleigh_wavenumber = %g is ignored, no band is masked\n", max_no_rayleigh_wavenumber);
+    const unsigned opt_flags = rayleigh_scattering ? ECCKD_OPT_RAYLEIGH_SCATTERING : 0u;
     for (const std::string& g : gas_list) {
       bool found = false;
       for (const GasTable& t : model.gases) found = found || t.name == g;
@@ -339,7 +360,7 @@ int main(int argc, char** argv) {
     auto load = [&](const std::string& name) {
       const std::string path = paths.find(name);
       LOG("Reading %s\n", path.c_str());
-      Scene s = read_lbl_fluxes(path, band_mapping, dev, gp);
+      Scene s = read_lbl_fluxes(path, band_mapping, dev, gp, rayleigh_scattering);
       if (s.is_sw && erythemal_weight > 0.0 && !s.erythemal.empty()) {   // solve_adept.cpp:182
         s.boundary_weights.resize(s.erythemal.size());
         for (size_t g = 0; g < s.erythemal.size(); ++g) s.boundary_weights[g] = erythemal_weight * s.erythemal[g];
@@ -347,7 +368,7 @@ int main(int argc, char** argv) {
       if (s.is_sw != model.is_sw) fail(ECCKD_PARAMETER_ERROR, "%s and the CKD model are not for the same spectral region", path.c_str());
       if (s.have_band) s.iband_per_g = iband_per_g(model, s.wn1, s.wn2);          // :273-276
       else s.iband_per_g = model.band_number;
-      if (s.is_sw && s.have_band) {   // LblFluxes::mask_rayleigh_up (lbl_fluxes.cpp:415-429), :278-283
+      if (s.is_sw && s.have_band && !rayleigh_scattering) {   // LblFluxes::mask_rayleigh_up (lbl_fluxes.cpp:415-429), :278-283
         for (int b = 0; b < s.nband; ++b)
           if (s.wn2[b] > max_no_rayleigh_wavenumber) {
             s.albedo[b] = 0.0;
@@ -370,7 +391,7 @@ int main(int argc, char** argv) {
       make_model(model, gas_list, rel.iband_per_g, mv);
       ecckd_opt_scene sv = scene_view(rel);
       ecckd_opt* ro = nullptr;
-      ck(ecckd_opt_create(dev.ctx(), &mv.m, 1, &sv, &oc, &ro));
+      ck(ecckd_opt_create_ex(dev.ctx(), &mv.m, 1, &sv, &oc, opt_flags, &ro));
       std::vector<double> x0(ecckd_opt_nx(ro));
       ck(ecckd_opt_initial_state(ro, x0.data(), nullptr, nullptr));
       rel_flux.resize((size_t)rel.ncol * 2 * (rel.nlay + 1) * model.ng);
@@ -403,7 +424,7 @@ int main(int argc, char** argv) {
     std::vector<ecckd_opt_scene> views;
     for (const Scene& s : scenes) views.push_back(scene_view(s));
     ecckd_opt* opt = nullptr;
-    ck(ecckd_opt_create(dev.ctx(), &mv.m, (int)views.size(), views.data(), &oc, &opt));
+    ck(ecckd_opt_create_ex(dev.ctx(), &mv.m, (int)views.size(), views.data(), &oc, opt_flags, &opt));
     const size_t nx = ecckd_opt_nx(opt);
     LOG("Optimizing %zu coefficients against %zu training file(s)\n", nx, scenes.size());
     std::vector<double> x(nx);

@@ -1,6 +1,7 @@
 // lbl_rt.hpp - the transfer of ONE wavenumber, written once for the line-by-line kernels (lbl_fluxes.hip,
 // lbl_gpoint_fluxes.hip, lbl_gpoint_fluxes_sw.hip, lbl_scenarios.hip: no scattering; lbl_fluxes_sw_rayleigh.hip and
-// k_rt_sw_gpoints_rayleigh of lbl_fluxes.hip: Rayleigh scattering), and the host plumbing they share.  DESIGN.md and the
+// k_rt_sw_gpoints_rayleigh of lbl_fluxes.hip: Rayleigh scattering; k_opt_forward_adjoint_rayleigh of optimize.hip takes the same
+// Rayleigh functions and their derivative rayleigh_layer_d), and the host plumbing they share.  DESIGN.md and the
 // tests compare these kernels with each other, bit for bit where they can: one source text keeps an edit from reaching only
 // one of them.  The files are compiled with the default contraction, so an expression here and in rt_device.hpp keeps its form
 // and operand order; a reordered one can fuse differently and change bits.
@@ -106,6 +107,84 @@ __device__ __forceinline__ RayleighLayer rayleigh_layer(double tau_abs, double t
   L.Rdir = fmin(fmax(rdir, 0.0), 1.0 - L.Tdir);
   L.Tdd = fmin(fmax(tdd, 0.0), 1.0 - L.Tdir - L.Rdir);
   return L;
+}
+
+// d / d tau_abs of rayleigh_direct at fixed tau_ray, forward mode: every d* argument is the derivative of the argument before
+// it.  mu may itself depend on tau_abs (the shifted angles of the resonance treatment, dmu != 0).
+__device__ __forceinline__ void rayleigh_direct_d(double w, double dw, double k, double dk, double e, double de, double e2, double de2,
+                                                  double f, double df, double a1, double da1, double a2, double da2, double mu,
+                                                  double dmu, double tdir, double dtdir, double& rdir, double& drdir, double& tdd,
+                                                  double& dtdd) {
+  const double g3 = 0.5, g4 = 0.5;
+  const double km = k * mu, dkm = dk * mu + k * dmu;
+  const double om = 1.0 / (1.0 - km * km);
+  const double f2 = w * f * om;
+  const double df2 = (dw * f + w * df) * om + f2 * (2.0 * km * dkm) * om;
+  const double ke = k * e, dke = dk * e + k * de;
+  const double p1 = a2 + k * g3, dp1 = da2 + dk * g3;
+  const double p2 = a2 - k * g3, dp2 = da2 - dk * g3;
+  const double p3 = g3 - a2 * mu, dp3 = -(da2 * mu + a2 * dmu);
+  const double brd = (1.0 - km) * p1 - (1.0 + km) * p2 * e2 - 2.0 * ke * p3 * tdir;
+  const double dbrd = -dkm * p1 + (1.0 - km) * dp1 - dkm * p2 * e2 - (1.0 + km) * (dp2 * e2 + p2 * de2) -
+                      2.0 * (dke * p3 * tdir + ke * dp3 * tdir + ke * p3 * dtdir);
+  const double q1 = a1 + k * g4, dq1 = da1 + dk * g4;
+  const double q2 = a1 - k * g4, dq2 = da1 - dk * g4;
+  const double q3 = g4 + a1 * mu, dq3 = da1 * mu + a1 * dmu;
+  const double c = (1.0 + km) * q1 - (1.0 - km) * q2 * e2;
+  const double dc = dkm * q1 + (1.0 + km) * dq1 + dkm * q2 * e2 - (1.0 - km) * (dq2 * e2 + q2 * de2);
+  const double btd = 2.0 * ke * q3 - tdir * c;
+  const double dbtd = 2.0 * (dke * q3 + ke * dq3) - dtdir * c - tdir * dc;
+  rdir = f2 * brd; drdir = df2 * brd + f2 * dbrd;
+  tdd = f2 * btd; dtdd = df2 * btd + f2 * dbtd;
+}
+
+// d / d tau_abs of the five terms of rayleigh_layer at fixed tau_ray, branch by branch as rayleigh_layer takes them (the
+// optimiser's adjoint, optimize.hip): the w = 0 branch, the clamp of k (dk = 0 where it is active), the resonance interpolation
+// (mu_a, mu_b and x move with k) and the two clamps of Rdir / Tdd - zero below 0, and the derivative of the bound 1 - Tdir
+// (- Rdir) where that is the active one.  The values themselves are rayleigh_layer's: the caller takes them from there.
+__device__ __forceinline__ RayleighLayer rayleigh_layer_d(double tau_abs, double tau_ray, double mu0, double minus_sec_sza) {
+  RayleighLayer d;
+  const double tau = tau_abs + tau_ray;
+  const double Tdir = exp(minus_sec_sza * tau);
+  d.Tdir = minus_sec_sza * Tdir;
+  if (!(tau_ray > 0.0 && tau > 0.0)) {
+    d.R = 0.0; d.T = -2.0 * exp(-2.0 * tau); d.Rdir = 0.0; d.Tdd = 0.0;
+    return d;
+  }
+  const double g3 = 0.5, g4 = 0.5;
+  const double w = tau_ray / tau, dw = -w / tau;
+  const double g1 = 2.0 - 1.25 * w, g2 = 0.75 * w, dg1 = -1.25 * dw, dg2 = 0.75 * dw;
+  const double a1 = g1 * g4 + g2 * g3, da1 = dg1 * g4 + dg2 * g3;
+  const double a2 = g1 * g3 + g2 * g4, da2 = dg1 * g3 + dg2 * g4;
+  const double q = (g1 - g2) * (g1 + g2);
+  const double k = sqrt(fmax(q, 1e-12));
+  const double dk = q > 1e-12 ? ((dg1 - dg2) * (g1 + g2) + (g1 - g2) * (dg1 + dg2)) / (2.0 * k) : 0.0;
+  const double e = exp(-k * tau), de = -e * (dk * tau + k);
+  const double e2 = e * e, de2 = 2.0 * e * de;
+  const double f = 1.0 / (k + g1 + (k - g1) * e2);
+  const double df = -f * f * (dk + dg1 + (dk - dg1) * e2 + (k - g1) * de2);
+  d.R = dg2 * (1.0 - e2) * f - g2 * de2 * f + g2 * (1.0 - e2) * df;
+  d.T = 2.0 * (dk * e * f + k * de * f + k * e * df);
+  double rdir, drdir, tdd, dtdd;
+  if (fabs(1.0 - k * mu0) < RAYLEIGH_RESONANCE_H) {
+    const double mu_a = (1.0 - 2.0 * RAYLEIGH_RESONANCE_H) / k, mu_b = (1.0 + 2.0 * RAYLEIGH_RESONANCE_H) / k;
+    const double dmu_a = -mu_a * dk / k, dmu_b = -mu_b * dk / k;
+    const double t_a = exp((-1.0 / mu_a) * tau), t_b = exp((-1.0 / mu_b) * tau);
+    const double dt_a = t_a * (-1.0 / mu_a + tau * dmu_a / (mu_a * mu_a)), dt_b = t_b * (-1.0 / mu_b + tau * dmu_b / (mu_b * mu_b));
+    double ra, dra, ta, dta, rb, drb, tb, dtb;
+    rayleigh_direct_d(w, dw, k, dk, e, de, e2, de2, f, df, a1, da1, a2, da2, mu_a, dmu_a, t_a, dt_a, ra, dra, ta, dta);
+    rayleigh_direct_d(w, dw, k, dk, e, de, e2, de2, f, df, a1, da1, a2, da2, mu_b, dmu_b, t_b, dt_b, rb, drb, tb, dtb);
+    const double x = (mu0 - mu_a) / (mu_b - mu_a);
+    const double dx = dk * mu0 / (4.0 * RAYLEIGH_RESONANCE_H);      // x = (k mu0 - (1 - 2h)) / (4h)
+    rdir = ra + (rb - ra) * x; drdir = dra + (drb - dra) * x + (rb - ra) * dx;
+    tdd = ta + (tb - ta) * x; dtdd = dta + (dtb - dta) * x + (tb - ta) * dx;
+  } else {
+    rayleigh_direct_d(w, dw, k, dk, e, de, e2, de2, f, df, a1, da1, a2, da2, mu0, 0.0, Tdir, d.Tdir, rdir, drdir, tdd, dtdd);
+  }
+  const double Rdir = fmin(fmax(rdir, 0.0), 1.0 - Tdir);
+  d.Rdir = rdir < 0.0 ? 0.0 : (rdir > 1.0 - Tdir ? -d.Tdir : drdir);
+  d.Tdd = tdd < 0.0 ? 0.0 : (tdd > 1.0 - Tdir - Rdir ? -d.Tdir - d.Rdir : dtdd);
+  return d;
 }
 
 // adding, upwards: the albedo A and the source S (the upwelling flux the direct beam alone causes) seen from the layer's top

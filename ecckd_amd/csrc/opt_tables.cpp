@@ -290,9 +290,11 @@ void flatten_scenes(const ecckd_opt_model* m, int nscene, const ecckd_opt_scene*
       std::memcpy(u, sc.flux_up + (size_t)c * nhl * nband, (size_t)nhl * nband * sizeof(double));
       for (int l = 0; l < nlay; ++l)
         for (int b = 0; b < nband; ++b)
-          // LW: net flux divergence; SW: direct beam only (lbl_fluxes.cpp:365-369 passes an empty flux_up)
+          // LW: net flux divergence; SW: direct beam only (lbl_fluxes.cpp:365-369 passes an empty flux_up), unless the
+          // handle scatters: then flux_dn is the total downwelling and the heating rate is the net one, as the model's
           t.hr[(col * nlay + l) * nband + b] =
-              do_sw ? conv[l] * (d[(l + 1) * nband + b] - d[l * nband + b])
+              do_sw && !t.scattering
+                    ? conv[l] * (d[(l + 1) * nband + b] - d[l * nband + b])
                     : conv[l] * (d[(l + 1) * nband + b] - d[l * nband + b] - u[(l + 1) * nband + b] + u[l * nband + b]);
       if (has_boundary(sc, do_sw)) {
         std::memcpy(&t.sfds[col * ng], sc.spectral_flux_dn_surf + (size_t)c * ng, ng * sizeof(double));

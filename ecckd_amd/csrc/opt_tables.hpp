@@ -40,6 +40,8 @@ struct Layout {
   size_t nx = 0, nk = 0, ncol = 0, ncell = 0, nnode_active = 0;
   bool do_sw = false;
   bool have_boundary = false;
+  bool scattering = false;          // ECCKD_OPT_RAYLEIGH_SCATTERING, set by the caller of build_tables: the two-stream transfer with
+                                    // Rayleigh scattering between optical depth and fluxes; the heating rates come from the net flux
   int ray_ent = -1;                 // entry index of the Rayleigh pseudo gas
   int grad_nchunk = 1;              // 64-g chunks of a row
   std::vector<GasInfo> gases;       // in k order: active gases first

@@ -32,6 +32,7 @@
 #include "common.hpp"
 #include <chrono>
 #include "rt_device.hpp"
+#include "lbl_rt.hpp"      // rayleigh_layer, rayleigh_layer_d, rayleigh_up, rayleigh_down: k_opt_forward_adjoint_rayleigh
 
 #include <algorithm>
 #include <atomic>
@@ -953,6 +954,360 @@ k_opt_forward_adjoint_cells(
   if (threadIdx.x == 0) jcol[col] = jtot;
 }
 
+// ---- K8a with Rayleigh scattering (ECCKD_OPT_RAYLEIGH_SCATTERING): the two-stream transfer of lbl_rt.hpp and its adjoint ----
+// Between optical depth and fluxes sits, per column and g point (levels 0 .. nlay from the top, D direct, V diffuse down, U up):
+//   terms    R_l, T_l, Tdir_l, Rdir_l, Tdd_l = rayleigh_layer(tau_abs, tau_ray, mu0)            per cell
+//   direct   D_0 = mu0 ssi,  D_l+1 = D_l Tdir_l
+//   up       A_n = albedo, S_n = albedo D_n;  A_l, S_l = rayleigh_up(layer l, D_l, A_l+1, S_l+1)           l = n-1 .. 0
+//   down     V_0 = 0, U_0 = S_0;  V_l+1, U_l+1 = rayleigh_down(layer l, D_l, A_l+1, S_l+1, V_l)            l = 0 .. n-1
+//   model    dn_i = D_i + V_i, up_i = U_i -> band sums -> the shortwave cost (phase D, heating rate from dn - up)
+// The adjoint (bars: dJ/d of the quantity; dnb_i, upb_i the seeds of phase D at the band of g, the per-g surface term added
+// to dnb_n; i = 1 / (1 - A_l+1 R_l), a = A_l+1, s = S_l+1, everything at layer l unless indexed):
+//   down sweep reversed, l = n-1 .. 0, c the carry into V_l (0 at the start):
+//     vb = dnb_l+1 + c + upb_l+1 a;  nb = vb i;  q = vb V_l+1 i                  (q = -d/d(1 - a R))
+//     Ab_l+1 = upb_l+1 V_l+1 + q R;  Sb_l+1 = upb_l+1 + nb R;  Db_l = dnb_l + nb Tdd
+//     Rb = nb s + q a;  Tb = nb V_l;  Tddb = nb D_l;  c = nb T                   Ab_0 = 0, Sb_0 = upb_0, Db_n = dnb_n
+//   up sweep reversed, l = 0 .. n-1, ca, cs the carries into A_l, S_l:
+//     ab = Ab_l + ca;  sb = Sb_l + cs;  P = s + a Tdd D_l;  ib = ab T^2 a + sb T P
+//     Rb += ab + ib i^2 a;  Tb += 2 ab T a i + sb P i;  Rdirb = sb D_l;  Tddb += sb T a D_l i
+//     Db_l += sb (Rdir + T a Tdd i);  ca = ab T^2 i + sb T Tdd D_l i + ib i^2 R;  cs = sb T i
+//   surface  Db_n += (Sb_n + cs) albedo
+//   direct chain reversed, l = n-1 .. 0, t = Db_n:  Tdirb = t D_l;  t = Db_l + t Tdir
+//   per cell  dJ/dtau_abs = Rb R' + Tb T' + Tdirb Tdir' + Rdirb Rdir' + Tddb Tdd',  ' = d/dtau_abs of rayleigh_layer_d
+// Phases.  A (every lane owns the cells l = lgrp + j nlgrp of its g point): look-up, clamp and penalty, rayleigh_layer and
+// rayleigh_layer_d - every exp, sqrt and division of the layer terms; B (one wave per 64 g points): the three forward
+// recurrences over the stored terms; C, D: band sums and cost as in k_opt_forward_adjoint_cells; E1 (one wave per 64 g
+// points): the three reversed recurrences - FMAs and one division per layer and sweep; E2 (cell owners): the sum above.
+// The per-(level, g) state does not fit the LDS (23 arrays of (nlay + 1) ng doubles): it lives in a workspace of the handle,
+// ws[column][slot][level][g], so a wave reads and writes 512 contiguous bytes; every element is written and read either by its
+// own lane or by its owner with a block barrier in between.  The LDS holds the band and cost arrays only, so one kernel
+// serves every shape.  All sums keep a fixed order.
+enum RaySlot { RS_R, RS_T, RS_TDIR, RS_RDIR, RS_TDD,             // the layer terms, rows 0 .. nlay-1
+               RS_DR, RS_DT, RS_DTDIR, RS_DRDIR, RS_DTDD,        // their d / d tau_abs (0 in clamped cells)
+               RS_D, RS_A, RS_S, RS_V, RS_U,                     // levels 0 .. nlay
+               RS_AB, RS_SB, RS_DB,                              // adjoints of A, S, D
+               RS_RB, RS_TB, RS_TDIRB, RS_RDIRB, RS_TDDB,        // adjoints of the layer terms
+               RS_COUNT };
+
+// B: the forward recurrences of one g point; every pointer is its slot at this g, rows ng apart
+__device__ __forceinline__ void rayleigh_forward_sweeps(int nlay, int ng, double d0, double alb, const double* __restrict__ pR,
+                                                        const double* __restrict__ pT, const double* __restrict__ pTdir,
+                                                        const double* __restrict__ pRdir, const double* __restrict__ pTdd,
+                                                        double* __restrict__ pD, double* __restrict__ pA, double* __restrict__ pS,
+                                                        double* __restrict__ pV, double* __restrict__ pU) {
+  using ecckd::lbl::RayleighLayer;
+  double d = d0;
+  pD[0] = d;
+#pragma unroll 4
+  for (int l = 0; l < nlay; ++l) {
+    d = d * pTdir[(size_t)l * ng];
+    pD[(size_t)(l + 1) * ng] = d;
+  }
+  double a = alb, s = alb * d;
+  pA[(size_t)nlay * ng] = a;
+  pS[(size_t)nlay * ng] = s;
+#pragma unroll 2
+  for (int l = nlay - 1; l >= 0; --l) {
+    const size_t r = (size_t)l * ng;
+    const RayleighLayer L{pR[r], pT[r], pTdir[r], pRdir[r], pTdd[r]};
+    double an, sn;
+    ecckd::lbl::rayleigh_up(L, pD[r], a, s, an, sn);
+    a = an; s = sn;
+    pA[r] = a;
+    pS[r] = s;
+  }
+  double v = 0.0;
+  pV[0] = 0.0;
+  pU[0] = s;
+#pragma unroll 2
+  for (int l = 0; l < nlay; ++l) {
+    const size_t r = (size_t)l * ng, r1 = r + ng;
+    const RayleighLayer L{pR[r], pT[r], pTdir[r], pRdir[r], pTdd[r]};
+    double vn, un;
+    ecckd::lbl::rayleigh_down(L, pD[r], pA[r1], pS[r1], v, vn, un);
+    v = vn;
+    pV[r1] = v;
+    pU[r1] = un;
+  }
+}
+
+// E1: the reversed recurrences of one g point (equations above).  gD, gU: dJ/d(band dn), dJ/d(band up) at the band of g, rows
+// nband apart; dn_surf_extra: the per-g surface term's share of dnb_n.
+__device__ __forceinline__ void rayleigh_adjoint_sweeps(int nlay, int ng, int nband, const double* gD, const double* gU, double dn_surf_extra,
+                                                        double alb, const double* __restrict__ pR, const double* __restrict__ pT,
+                                                        const double* __restrict__ pTdir, const double* __restrict__ pRdir,
+                                                        const double* __restrict__ pTdd, const double* __restrict__ pD,
+                                                        const double* __restrict__ pA, const double* __restrict__ pS,
+                                                        const double* __restrict__ pV, double* __restrict__ pAb, double* __restrict__ pSb,
+                                                        double* __restrict__ pDb, double* __restrict__ pRb, double* __restrict__ pTb,
+                                                        double* __restrict__ pTdirb, double* __restrict__ pRdirb, double* __restrict__ pTddb) {
+  double c = 0.0;
+  pDb[(size_t)nlay * ng] = gD[nlay * nband] + dn_surf_extra;
+#pragma unroll 2
+  for (int l = nlay - 1; l >= 0; --l) {
+    const size_t r = (size_t)l * ng, r1 = r + ng;
+    const double a = pA[r1], s = pS[r1], R = pR[r], T = pT[r], Tdd = pTdd[r], Dl = pD[r], Vl = pV[r], Vn = pV[r1];
+    const double inv = 1.0 / (1.0 - a * R);
+    const double ub = gU[(l + 1) * nband];
+    const double vb = gD[(l + 1) * nband] + (l + 1 == nlay ? dn_surf_extra : 0.0) + c + ub * a;
+    const double nb = vb * inv;
+    const double q = vb * Vn * inv;
+    pAb[r1] = ub * Vn + q * R;
+    pSb[r1] = ub + nb * R;
+    pDb[r] = gD[l * nband] + nb * Tdd;
+    pRb[r] = nb * s + q * a;
+    pTb[r] = nb * Vl;
+    pTddb[r] = nb * Dl;
+    c = nb * T;
+  }
+  pAb[0] = 0.0;
+  pSb[0] = gU[0];
+  double ca = 0.0, cs = 0.0;
+#pragma unroll 2
+  for (int l = 0; l < nlay; ++l) {
+    const size_t r = (size_t)l * ng, r1 = r + ng;
+    const double a = pA[r1], s = pS[r1], R = pR[r], T = pT[r], Rdir = pRdir[r], Tdd = pTdd[r], Dl = pD[r];
+    const double inv = 1.0 / (1.0 - a * R);
+    const double ab = pAb[r] + ca, sb = pSb[r] + cs;
+    const double P = s + a * Tdd * Dl;
+    const double ib = ab * T * T * a + sb * T * P;
+    pRb[r] += ab + ib * inv * inv * a;
+    pTb[r] += 2.0 * ab * T * a * inv + sb * P * inv;
+    pRdirb[r] = sb * Dl;
+    pTddb[r] += sb * T * a * Dl * inv;
+    pDb[r] += sb * (Rdir + T * a * Tdd * inv);
+    ca = ab * T * T * inv + sb * T * Tdd * Dl * inv + ib * inv * inv * R;
+    cs = sb * T * inv;
+  }
+  double t = pDb[(size_t)nlay * ng] + (pSb[(size_t)nlay * ng] + cs) * alb;
+#pragma unroll 4
+  for (int l = nlay - 1; l >= 0; --l) {
+    const size_t r = (size_t)l * ng;
+    pTdirb[r] = t * pD[r];
+    t = pDb[r] + t * pTdir[r];
+  }
+}
+
+__global__ void __launch_bounds__(512)
+k_opt_forward_adjoint_rayleigh(
+    const double* __restrict__ mu0, int ray_ent, int keep_negative, const double* __restrict__ rel_flux,
+    int nlay, int ng, int ngpad, int nband, int nent,
+    const double* __restrict__ k, const int* __restrict__ ent_idx, const double* __restrict__ ent_coef,
+    const int* __restrict__ band_of_g, const int* __restrict__ band_ptr /*[nband+1]*/, const int* __restrict__ band_g /*[ng]: g points by band*/,
+    const double* __restrict__ planck_hl /* row 0 of a column: the scaled solar irradiance */, const double* __restrict__ albedo /*[ncol][nband]*/,
+    const double* __restrict__ conv, const double* __restrict__ layer_weight, const double* __restrict__ hr_true,
+    const double* __restrict__ fdn_true, const double* __restrict__ fup_true, const double* __restrict__ sfds,
+    const double* __restrict__ sfut, double flux_weight, double flux_profile_weight, double broadband_weight,
+    double negative_od_penalty, double* ws /*[ncol][RS_COUNT][nlay+1][ng]*/, double* __restrict__ dtau, double* __restrict__ jcol,
+    double* __restrict__ od_out, double* __restrict__ flux_out) {
+  extern __shared__ double smem[];
+  const int nhl = nlay + 1;
+  double* s_bdn = smem;                                          // [nhl][nband] band fluxes
+  double* s_bup = s_bdn + (size_t)nhl * nband;
+  double* s_gdn = s_bup + (size_t)nhl * nband;                   // [nhl][nband] dJ/d(band flux)
+  double* s_gup = s_gdn + (size_t)nhl * nband;
+  double* s_r = s_gup + (size_t)nhl * nband;                     // [nlay][nband] heating-rate residuals
+  double* s_rsum = s_r + (size_t)nlay * nband;                   // [nlay] their broadband sums
+  double* s_sd = s_rsum + nlay;                                  // [nhl] broadband flux residuals
+  double* s_su = s_sd + nhl;
+  double* s_red = s_su + nhl;                                    // [16]
+  int* s_bp = (int*)(s_red + 16);                                // [nband + 1]
+  int* s_bg = s_bp + nband + 1;                                  // [ng]
+  const int col = blockIdx.x;
+  const int g = threadIdx.x % ngpad;
+  const int lgrp = __builtin_amdgcn_readfirstlane(threadIdx.x / ngpad);     // ngpad is a multiple of 64: uniform in a wave
+  const int nlgrp = blockDim.x / ngpad;
+  const bool in_range = g < ng;
+  const bool live = in_range && lgrp == 0;
+  const int lane = threadIdx.x & 63;
+  const int gl = in_range ? g : 0;        // lanes beyond the last g point read (and drop) the first one's values
+  const double hr_weight = 3600.0 * 24.0;
+  const double* pl = planck_hl + (size_t)col * nhl * ng;
+  const size_t cell0 = (size_t)col * nlay;
+  const size_t slot = (size_t)nhl * ng;
+  double* w = ws + (size_t)col * RS_COUNT * slot + gl;           // slot q of this g point: w + q * slot, rows ng apart
+  bool all_pos = true;
+  for (int b = 0; b < nband; ++b) all_pos = all_pos && albedo[(size_t)col * nband + b] > 0.0;
+  const double cos_sza = mu0[col];
+  const double minus_sec_sza = -1.0 / cos_sza;
+  for (int t = threadIdx.x; t <= nband; t += blockDim.x) s_bp[t] = band_ptr[t];
+  for (int t = threadIdx.x; t < ng; t += blockDim.x) s_bg[t] = band_g[t];
+
+  // ---- A: the cells of this thread ----
+  double penalty = 0.0;
+  for (int l = lgrp; l < nlay; l += nlgrp) {
+    double tau = 0.0, tau_ray = 0.0;
+    for (int e0 = 0; e0 < nent; e0 += 64) {
+      const int ne = min(64, nent - e0);
+      const int my_idx = lane < ne ? ent_idx[(cell0 + l) * nent + e0 + lane] : -1;
+      const double my_c = lane < ne ? ent_coef[(cell0 + l) * nent + e0 + lane] : 0.0;
+      gather_batches<0>(my_idx, my_c, e0, ne, k, gl, ray_ent, tau, tau_ray);
+    }
+    if (in_range) {
+      const double tau_raw = tau;
+      const bool clamped = tau < 0.0;
+      if (clamped) {
+        penalty += tau * tau;                                         // solve_adept.cpp:110-113
+        tau = 0.0;
+      }
+      // the penalty's derivative, all a clamped cell passes on; phase E2 adds the transfer's share (0 there: its d terms are 0)
+      dtau[(cell0 + l) * ng + g] = clamped ? 2.0 * negative_od_penalty * tau_raw : 0.0;
+      if (keep_negative == 2) tau = tau_raw;                          // the "relative_to" evaluation: no clamp
+      if (od_out) od_out[(cell0 + l) * ng + g] = ((keep_negative && clamped) ? tau_raw : tau) + tau_ray;
+      const ecckd::lbl::RayleighLayer L = ecckd::lbl::rayleigh_layer(tau, tau_ray, cos_sza, minus_sec_sza);
+      const ecckd::lbl::RayleighLayer dL = ecckd::lbl::rayleigh_layer_d(tau, tau_ray, cos_sza, minus_sec_sza);
+      double* wl = w + (size_t)l * ng;
+      wl[RS_R * slot] = L.R; wl[RS_T * slot] = L.T; wl[RS_TDIR * slot] = L.Tdir; wl[RS_RDIR * slot] = L.Rdir; wl[RS_TDD * slot] = L.Tdd;
+      wl[RS_DR * slot] = clamped ? 0.0 : dL.R; wl[RS_DT * slot] = clamped ? 0.0 : dL.T; wl[RS_DTDIR * slot] = clamped ? 0.0 : dL.Tdir;
+      wl[RS_DRDIR * slot] = clamped ? 0.0 : dL.Rdir; wl[RS_DTDD * slot] = clamped ? 0.0 : dL.Tdd;
+    }
+  }
+  __syncthreads();
+  // ---- B: the forward recurrences, one wave per 64 g points ----
+  const double alb = fmax(albedo[(size_t)col * nband + band_of_g[gl]], 0.0);      // a non-positive albedo counts as 0
+  if (live)
+    rayleigh_forward_sweeps(nlay, ng, cos_sza * pl[g], alb, w + RS_R * slot, w + RS_T * slot, w + RS_TDIR * slot, w + RS_RDIR * slot,
+                            w + RS_TDD * slot, w + RS_D * slot, w + RS_A * slot, w + RS_S * slot, w + RS_V * slot, w + RS_U * slot);
+  __syncthreads();
+  const double* wc = ws + (size_t)col * RS_COUNT * slot;         // the column's slots, any g
+  if (flux_out && in_range) {
+    double* fo = flux_out + (size_t)col * 2 * nhl * ng;
+    for (int i = lgrp; i < nhl; i += nlgrp) {
+      fo[i * ng + g] = wc[RS_D * slot + i * ng + g] + wc[RS_V * slot + i * ng + g];       // total downwelling
+      fo[(nhl + i) * ng + g] = wc[RS_U * slot + i * ng + g];
+    }
+  }
+  // ---- C: band sums of the total downwelling and the upwelling flux, the g points of a band in increasing order ----
+  const double* cv = conv + (size_t)col * nlay;
+  const double* lw = layer_weight + (size_t)col * nlay;
+  const double* hrt = hr_true + (size_t)col * nlay * nband;
+  const double* fdt = fdn_true + (size_t)col * nhl * nband;
+  const double* fut = fup_true + (size_t)col * nhl * nband;
+  const double* rel = rel_flux ? rel_flux + (size_t)col * 2 * nhl * ng : nullptr;
+  for (int t = threadIdx.x; t < nhl * nband; t += blockDim.x) {
+    const int i = t / nband, b = t % nband;
+    double sd = 0.0, su = 0.0;
+    for (int q = s_bp[b]; q < s_bp[b + 1]; ++q) {
+      const int gg = s_bg[q];
+      const double dn = wc[RS_D * slot + i * ng + gg] + wc[RS_V * slot + i * ng + gg];
+      const double up = wc[RS_U * slot + i * ng + gg];
+      // the relative-to fluxes are subtracted per g point before the band sums (calc_cost_function_sw.cpp:160-163)
+      sd += rel ? dn - rel[i * ng + gg] : dn;
+      su += rel ? up - rel[(nhl + i) * ng + gg] : up;
+    }
+    s_bdn[t] = sd;
+    s_bup[t] = su;
+  }
+  __syncthreads();
+  // ---- D: the shortwave cost (calc_cost_function_sw.cpp:186-277) and its derivative with respect to the band fluxes, as
+  //      phase D of k_opt_forward_adjoint_cells with the heating rate from the net flux ----
+  const double spec_scale = broadband_weight > 0.0 ? (1.0 - broadband_weight) / nband : 1.0;   // :243
+  const double hrw2 = hr_weight * hr_weight;
+  double jpart = 0.0;
+  for (int t = threadIdx.x; t < nlay * nband; t += blockDim.x) {
+    const int l = t / nband, b = t % nband;
+    const double hrf = cv[l] * (s_bdn[(l + 1) * nband + b] - s_bdn[l * nband + b] - (s_bup[(l + 1) * nband + b] - s_bup[l * nband + b]));
+    const double r = hrf - hrt[t];
+    s_r[t] = r;
+    jpart += spec_scale * hrw2 * lw[l] * r * r;
+  }
+  __syncthreads();
+  // weights of the squared residuals of dn / up at half level i: spectral (s) and broadband (b)
+  auto level_weights = [&](int i, double& wd_s, double& wu_s, double& wd_b, double& wu_b) {
+    wd_s = 0.0; wu_s = 0.0; wd_b = 0.0; wu_b = 0.0;
+    if (i == nlay) { wd_s = flux_weight; wd_b = flux_weight; }
+    if (i == 0) {
+      wu_s = 20.0 * flux_weight;                                 // :214
+      wu_b = all_pos ? flux_weight : 0.0;                        // :252
+    }
+    if (i >= 1 && i <= nlay - 1 && flux_profile_weight > 0.0) {
+      const double iw = flux_profile_weight * 0.5 * (lw[i - 1] + lw[i]);
+      wd_s = iw; wu_s = iw; wd_b = iw;
+      wu_b = all_pos ? iw : 0.0;                                 // :264
+    }
+  };
+  for (int t = threadIdx.x; t < nlay + nhl; t += blockDim.x) {
+    if (t < nlay) {
+      double rsum = 0.0;
+      for (int b = 0; b < nband; ++b) rsum += s_r[t * nband + b];
+      s_rsum[t] = rsum;
+      jpart += broadband_weight * hrw2 * lw[t] * rsum * rsum;
+    } else {
+      const int i = t - nlay;
+      double wd_s, wu_s, wd_b, wu_b, sd = 0.0, su = 0.0;
+      level_weights(i, wd_s, wu_s, wd_b, wu_b);
+      if (wd_s != 0.0 || wu_s != 0.0) {
+        for (int b = 0; b < nband; ++b) {
+          sd += s_bdn[i * nband + b] - fdt[i * nband + b];
+          su += s_bup[i * nband + b] - fut[i * nband + b];
+        }
+        jpart += broadband_weight * (wd_b * sd * sd + wu_b * su * su);
+      }
+      s_sd[i] = sd;
+      s_su[i] = su;
+    }
+  }
+  __syncthreads();
+  for (int t = threadIdx.x; t < nhl * nband; t += blockDim.x) {
+    const int i = t / nband, b = t % nband;
+    double gd = 0.0, gu = 0.0;
+    if (i >= 1) {                                                 // layer i-1 ends at this level
+      const int l = i - 1;
+      const double dhr = 2.0 * hrw2 * lw[l] * (spec_scale * s_r[l * nband + b] + broadband_weight * s_rsum[l]);
+      gd = dhr * cv[l];
+      gu = -dhr * cv[l];
+    }
+    if (i <= nlay - 1) {                                          // layer i starts at it
+      const double dhr = 2.0 * hrw2 * lw[i] * (spec_scale * s_r[i * nband + b] + broadband_weight * s_rsum[i]);
+      gd += -dhr * cv[i];
+      gu += dhr * cv[i];
+    }
+    double wd_s, wu_s, wd_b, wu_b;
+    level_weights(i, wd_s, wu_s, wd_b, wu_b);
+    if (wd_s != 0.0 || wu_s != 0.0) {
+      const double dd = s_bdn[t] - fdt[t];
+      const double du = s_bup[t] - fut[t];
+      jpart += spec_scale * (wd_s * dd * dd + wu_s * du * du);
+      gd += 2.0 * (spec_scale * wd_s * dd + broadband_weight * wd_b * s_sd[i]);
+      gu += 2.0 * (spec_scale * wu_s * du + broadband_weight * wu_b * s_su[i]);
+    }
+    s_gdn[t] = gd;
+    s_gup[t] = gu;
+  }
+  double dn_surf_extra = 0.0;
+  if (live && sfds && sfut) {
+    // calc_cost_function_sw.cpp:271-274: per-g weights (erythemal) on the total downwelling flux at the surface
+    const double reld = rel ? rel[nlay * ng + g] : 0.0;
+    const double a = ((wc[RS_D * slot + nlay * ng + g] + wc[RS_V * slot + nlay * ng + g]) - reld) - sfds[(size_t)col * ng + g];
+    const double wgt = sfut[(size_t)col * ng + g];
+    jpart += wgt * a * a;
+    dn_surf_extra = 2.0 * wgt * a;
+  }
+  __syncthreads();
+  // ---- E1: the reversed recurrences, one wave per 64 g points ----
+  if (live) {
+    const int b = band_of_g[g];
+    rayleigh_adjoint_sweeps(nlay, ng, nband, s_gdn + b, s_gup + b, dn_surf_extra, alb, w + RS_R * slot, w + RS_T * slot, w + RS_TDIR * slot,
+                            w + RS_RDIR * slot, w + RS_TDD * slot, w + RS_D * slot, w + RS_A * slot, w + RS_S * slot, w + RS_V * slot,
+                            w + RS_AB * slot, w + RS_SB * slot, w + RS_DB * slot, w + RS_RB * slot, w + RS_TB * slot, w + RS_TDIRB * slot,
+                            w + RS_RDIRB * slot, w + RS_TDDB * slot);
+  }
+  __syncthreads();
+  // ---- E2: dJ/dtau_abs of the cells of this thread, the five terms in a fixed order ----
+  if (in_range) {
+    for (int l = lgrp; l < nlay; l += nlgrp) {
+      const double* wl = w + (size_t)l * ng;
+      const double tau_bar = wl[RS_RB * slot] * wl[RS_DR * slot] + wl[RS_TB * slot] * wl[RS_DT * slot] +
+                             wl[RS_TDIRB * slot] * wl[RS_DTDIR * slot] + wl[RS_RDIRB * slot] * wl[RS_DRDIR * slot] +
+                             wl[RS_TDDB * slot] * wl[RS_DTDD * slot];
+      dtau[(cell0 + l) * ng + g] += tau_bar;
+    }
+  }
+  jpart += negative_od_penalty * penalty;
+  const double jtot = block_reduce_sum(jpart, s_red);
+  if (threadIdx.x == 0) jcol[col] = jtot;
+}
+
 // K8b + K9: gradient of the state, two launches of one WAVE per task, four waves per block, no LDS, no barrier.
 //   grad_k = sum over the cells that reference this node of coef * dtau[cell][g]   (reference order)
 //   grad_x = grad_k * k + B^-1 (x - x_prior) / sigma_g^2                            (:273-283)
@@ -1140,6 +1495,12 @@ __device__ __forceinline__ void write_partials(double (&acc)[NACC], int nused, d
     for (int w = 0; w < VEC_WAVES; ++w) t += s_all[threadIdx.x * VEC_WAVES + w];
     part[(size_t)threadIdx.x * VEC_BLOCKS + blockIdx.x] = t;
   }
+}
+
+// dynamic LDS of k_opt_forward_adjoint_rayleigh: the band and cost arrays alone, whatever the block size
+size_t rayleigh_lds_bytes(int nlay, int nband, int ng) {
+  const size_t nhl = (size_t)nlay + 1;
+  return (4 * nhl * nband + (size_t)nlay * nband + nlay + 2 * nhl + 16) * sizeof(double) + ((size_t)nband + 1 + ng) * sizeof(int);
 }
 
 // ---- L-BFGS on the device, compact representation (Byrd, Nocedal & Schnabel 1994) -----------------------------
@@ -1366,6 +1727,7 @@ struct ecckd_opt : ot::Layout {
     return e;
   }
   double* d_rel = nullptr;   // relative-to CKD fluxes [ncol][2][nhl][ng]
+  double* d_ray_ws = nullptr;   // scattering handles: the per-(level, g) state of k_opt_forward_adjoint_rayleigh [ncol][RS_COUNT][nhl][ng]
   double* d_mu0 = nullptr;
   double *d_k = nullptr, *d_x = nullptr, *d_xprior = nullptr, *d_grad = nullptr, *d_dtau = nullptr;
   double *d_jcol = nullptr, *d_jb = nullptr;
@@ -1477,11 +1839,27 @@ extern "C" {
 
 int ecckd_opt_create(ecckd_ctx* ctx, const ecckd_opt_model* m, int nscene, const ecckd_opt_scene* scenes,
                      const ecckd_opt_config* cfg, ecckd_opt** out) {
+  return ecckd_opt_create_ex(ctx, m, nscene, scenes, cfg, 0u, out);
+}
+
+int ecckd_opt_create_ex(ecckd_ctx* ctx, const ecckd_opt_model* m, int nscene, const ecckd_opt_scene* scenes,
+                        const ecckd_opt_config* cfg, unsigned flags, ecckd_opt** out) {
   ECCKD_REQUIRE(ctx && m && scenes && cfg && out && nscene > 0, "ecckd_opt_create: NULL/empty argument");
   *out = nullptr;
+  ECCKD_REQUIRE((flags & ~ECCKD_OPT_RAYLEIGH_SCATTERING) == 0, "ecckd_opt_create_ex: unknown flags 0x%x", flags);
+  const bool scattering = (flags & ECCKD_OPT_RAYLEIGH_SCATTERING) != 0;
+  if (scattering) {
+    ECCKD_REQUIRE(m->solar_irradiance && m->rayleigh_molar_scattering,
+                  "ecckd_opt_create_ex: ECCKD_OPT_RAYLEIGH_SCATTERING needs a shortwave model with rayleigh_molar_scattering");
+    for (int s = 0; s < nscene; ++s)
+      ECCKD_REQUIRE(scenes[s].mu0 && scenes[s].albedo, "ecckd_opt_create_ex: ECCKD_OPT_RAYLEIGH_SCATTERING: scene %d lacks mu0 or albedo", s);
+    // (a block of k_opt_forward_adjoint_rayleigh has at most 512 threads - 256 VGPRs, nothing spilled - and one per g point)
+    ECCKD_REQUIRE(m->ng <= 512, "ecckd_opt_create_ex: ECCKD_OPT_RAYLEIGH_SCATTERING supports at most 512 g points (ng = %d)", m->ng);
+  }
   const char* plain = std::getenv("ECCKD_K8B_PLAIN_ORDER");
   const ot::Schedule schedule = {K8B_WAVES, K8B_RUN, plain && plain[0] == '1'};
   ot::Tables t;
+  t.scattering = scattering;
   std::string refusal;
   const int rc = ot::build_tables(m, nscene, scenes, cfg, schedule, t, refusal);
   if (rc != ECCKD_OK) return ecckd::fail(rc, "%s", refusal.c_str());
@@ -1490,8 +1868,18 @@ int ecckd_opt_create(ecckd_ctx* ctx, const ecckd_opt_model* m, int nscene, const
   o->ctx = ctx;
   o->cfg = *cfg;
   static_cast<ot::Layout&>(*o) = std::move(static_cast<ot::Layout&>(t));   // (k0 among it: from here on it is o->k0)
+  if (o->scattering) {
+    // the LDS of k_opt_forward_adjoint_rayleigh depends on the shapes alone: refused here, where the handle is made, and the
+    // kernel's limit raised once, not at every launch of the minimiser's loop
+    const size_t lds = rayleigh_lds_bytes(o->nlay, o->nband, o->ng);
+    ECCKD_REQUIRE(lds <= 160 * 1024, "ecckd_opt_create_ex: nlay * nband too large for the LDS of the scattering kernel (%zu B)", lds);
+    ECCKD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_opt_forward_adjoint_rayleigh),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  }
   ECCKD_CHECK(opt_upload_tables(o.get(), t));
   ECCKD_CHECK(opt_alloc_work(o.get(), t));
+  if (o->scattering && o->alloc(&o->d_ray_ws, o->ncol * RS_COUNT * (size_t)(o->nlay + 1) * o->ng) != hipSuccess)
+    return ecckd::fail(ECCKD_OUT_OF_MEMORY, "ecckd_opt_create_ex: device allocation of the scattering workspace failed");
   std::vector<double> xp(o->nx);
   ot::initial_state(*o, xp.data(), nullptr, nullptr);
   ECCKD_HIP_CHECK(hipMemcpyAsync(o->d_xprior, xp.data(), o->nx * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
@@ -1623,6 +2011,17 @@ ecckd_forward_plan forward_plan(bool do_sw, int nlay, int ng, int nband, int nen
 ecckd_forward_plan opt_forward_plan(const ecckd_opt* o) {
   const char* e = std::getenv("ECCKD_K8A_THREADS");
   const int v = e ? std::atoi(e) : 0;
+  if (o->scattering) {
+    // k_opt_forward_adjoint_rayleigh, the one kernel of a scattering handle: 512 threads (8 layer groups at ng = 64), the LDS
+    // holds the band and cost arrays only
+    ecckd_forward_plan p{};
+    p.cells = 2;
+    p.ngpad = (o->ng + 63) / 64 * 64;
+    p.lgroups = std::max(1, (v >= 64 && v <= 512 ? v : 512) / p.ngpad);   // (ecckd_opt_create_ex has refused ng > 512)
+    p.threads = p.ngpad * p.lgroups;
+    p.lds_bytes = rayleigh_lds_bytes(o->nlay, o->nband, o->ng);
+    return p;
+  }
   const char* env_generic = std::getenv("ECCKD_K8A_GENERIC");
   return forward_plan(o->do_sw, o->nlay, o->ng, o->nband, o->nent, v >= 64 && v <= 1024 ? v : 0, env_generic && env_generic[0] == '1');
 }
@@ -1631,6 +2030,16 @@ ecckd_forward_plan opt_forward_plan(const ecckd_opt* o) {
 int opt_launch_forward(ecckd_opt* o) {
   ecckd_ctx* ctx = o->ctx;
   const ecckd_forward_plan p = opt_forward_plan(o);
+  if (o->scattering) {
+    // (ecckd_opt_create_ex has checked the LDS and raised the kernel's limit; the Rayleigh entry is always kept apart from the absorbers; a diagnostic pass changes only keep_negative)
+    hipLaunchKernelGGL(k_opt_forward_adjoint_rayleigh, dim3((unsigned)o->ncol), dim3(p.threads), p.lds_bytes, ctx->stream, o->d_mu0,
+                       o->ray_ent, o->eval_keep_negative, o->d_rel, o->nlay, o->ng, p.ngpad, o->nband, o->nent, o->d_k, o->d_ent_idx,
+                       o->d_ent_coef, o->d_band, o->d_band_ptr, o->d_band_g, o->d_planck, o->d_semis, o->d_conv, o->d_lw, o->d_hr,
+                       o->d_fdn, o->d_fup, o->d_sfds, o->d_sfut, o->cfg.flux_weight, o->cfg.flux_profile_weight, o->cfg.broadband_weight,
+                       o->cfg.negative_od_penalty, o->d_ray_ws, o->d_dtau, o->d_jcol, o->d_od_out, o->d_flux_out);
+    ECCKD_HIP_CHECK(hipGetLastError());
+    return ECCKD_OK;
+  }
   if (p.cells) {
     ECCKD_CHECK(launch_cells_for(p.nc_template, p.nb, o, p.threads, p.lds_bytes, p.ngpad));
     ECCKD_HIP_CHECK(hipGetLastError());

@@ -406,14 +406,18 @@ def read_ckd_model(path, active_gases=None):
 
 # ---- LBL training fluxes (LblFluxes::read lbl_fluxes.cpp:52-397, make_gas_mapping, mask_rayleigh_up, subtract) -----
 
-def read_lbl_fluxes(path, model_molecules, band_mapping=None, gmap=None, ctx=None):
+def read_lbl_fluxes(path, model_molecules, band_mapping=None, gmap=None, ctx=None, rayleigh_scattering=False):
     """LblFluxes::read + make_gas_mapping -> a training-scene dict for api.Optimizer.
 
     model_molecules: the CKD model's gas names in model order (CkdModel::molecules).
     band_mapping:    optional narrow-band -> wide-band index per file band (:150-176, :272-296).
     gmap, ctx:       an api.GPointMap of the g-points file and its context; with them the high-resolution boundary
                      fluxes are summed per g point on the device (:180-246, :300-325) and the shortwave erythemal
-                     weights are formed (:198-230)."""
+                     weights are formed (:198-230).
+    rayleigh_scattering: the scene is for a scattering optimiser (api.Optimizer(rayleigh_scattering=True)): the file must be
+                     a shortwave one with the global attribute rayleigh_scattering = "two-stream" (ckdmip_sw --rayleigh);
+                     flux_dn is then the total downwelling (band_flux_dn_sw or spectral_flux_dn_sw), the surface flux per g
+                     point comes from spectral_flux_dn_surf_sw, and the band albedo is sum(up) / sum(total dn)."""
     bm = None if band_mapping is None else np.asarray(band_mapping, dtype=np.int64)
     with NcFile(path) as f:
         p = f.read("pressure_hl")
@@ -422,6 +426,10 @@ def read_lbl_fluxes(path, model_molecules, band_mapping=None, gmap=None, ctx=Non
         ncol = p.shape[0]
         is_sw = f.exist("mu0")
         out = {"is_sw": is_sw}
+        if rayleigh_scattering and not (is_sw and f.att_text("rayleigh_scattering") == "two-stream"):
+            raise _lib.EcckdError(_lib.PARAMETER_ERROR, f'rayleigh_scattering: {path} does not hold shortwave fluxes with the global '
+                                              'attribute rayleigh_scattering = "two-stream"')
+        dn_kind = "flux_dn_sw" if rayleigh_scattering else "flux_dn_direct_sw"
         dom = "sw" if is_sw else "lw"
 
         def map_bands(a, wn1, wn2):                                  # sum narrow bands into wide ones
@@ -440,10 +448,10 @@ def read_lbl_fluxes(path, model_molecules, band_mapping=None, gmap=None, ctx=Non
             out["mu0"] = np.tile(mu0_all[index_sza], ncol)
             out["tsi"] = float(flux_dn[0, 0] / out["mu0"][0])        # :116
             have_band = False
-            if f.exist("spectral_flux_dn_direct_sw"):
-                sdn, sup = pick(f.read("spectral_flux_dn_direct_sw")), pick(f.read("spectral_flux_up_sw"))
-            elif f.exist("band_flux_dn_direct_sw"):
-                sdn, sup = pick(f.read("band_flux_dn_direct_sw")), pick(f.read("band_flux_up_sw"))
+            if f.exist("spectral_" + dn_kind):
+                sdn, sup = pick(f.read("spectral_" + dn_kind)), pick(f.read("spectral_flux_up_sw"))
+            elif f.exist("band_" + dn_kind):
+                sdn, sup = pick(f.read("band_" + dn_kind)), pick(f.read("band_flux_up_sw"))
                 have_band = True
                 wn1, wn2 = f.read("band_wavenumber1_sw"), f.read("band_wavenumber2_sw")
             else:
@@ -455,7 +463,7 @@ def read_lbl_fluxes(path, model_molecules, band_mapping=None, gmap=None, ctx=Non
                     wn1, wn2 = wn1n, wn2n
                 out["albedo"] = sup[:, -1, :].sum(0) / sdn[:, -1, :].sum(0)      # effective_spectral_albedo_ (:147-148, :166-167)
             ncol *= nsza
-            hi_dn, hi_up = "spectral_flux_dn_direct_surf_sw", "spectral_flux_up_toa_sw"
+            hi_dn, hi_up = ("spectral_flux_dn_surf_sw" if rayleigh_scattering else "spectral_flux_dn_direct_surf_sw"), "spectral_flux_up_toa_sw"
         else:
             flux_dn, flux_up = f.read("flux_dn_lw"), f.read("flux_up_lw")
             have_band = False

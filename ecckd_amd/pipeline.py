@@ -218,7 +218,7 @@ def iband_per_g(model, wavenumber1, wavenumber2):
 
 def optimize_lut(ctx, model, training_files, relative_to=None, band_mapping=None, gmap=None, max_iterations=3000,
                  convergence_criterion=0.0, bounded=True, max_no_rayleigh_wavenumber=None, erythemal_weight=0.0,
-                 remove_min_max=False, **cfg):
+                 remove_min_max=False, rayleigh_scattering=False, **cfg):
     """The driver of optimize_lut.cpp:60-330 on top of api.Optimizer: training scenes from LBL flux files
     (ncio.read_lbl_fluxes), optional "relative_to" file, bounded L-BFGS, optimised coefficients back into the model.
 
@@ -226,15 +226,21 @@ def optimize_lut(ctx, model, training_files, relative_to=None, band_mapping=None
     cfg:   flux_weight, flux_profile_weight, broadband_weight, spectral_boundary_weight, prior_error, ... (api.Optimizer).
     remove_min_max: drop the min / max tables from the model that is returned (`ckd_model.save_min_max(false)`,
            optimize_lut.cpp:243-244, :308-310), so that ncio.write_ckd_model leaves the _min / _max variables out.
+    rayleigh_scattering: train through the two-stream transfer with Rayleigh scattering (api.Optimizer(rayleigh_scattering=True),
+           the tool's key of the same name): every file must be a `ckdmip_sw --rayleigh` one, the truth's downwelling is the
+           total flux, nothing is masked (max_no_rayleigh_wavenumber is ignored) and relative_to goes through a scattering
+           handle as well.
     Returns (model with optimised molar_abs, result dict of Optimizer.minimize)."""
     names = [g["name"] for g in model["gases"]]
     is_sw = model.get("solar_irradiance") is not None
+    if rayleigh_scattering and not (is_sw and model.get("rayleigh_molar_scattering") is not None):
+        raise EcckdError(PARAMETER_ERROR, "rayleigh_scattering needs a shortwave CKD model with a Rayleigh coefficient")
 
     def load(path):
-        s = ncio.read_lbl_fluxes(path, names, band_mapping=band_mapping, gmap=gmap, ctx=ctx)
+        s = ncio.read_lbl_fluxes(path, names, band_mapping=band_mapping, gmap=gmap, ctx=ctx, rayleigh_scattering=rayleigh_scattering)
         if s["have_band_fluxes"]:
             s["iband_per_g"] = iband_per_g(model, s["band_wavenumber1"], s["band_wavenumber2"])     # :273-276
-        if is_sw and max_no_rayleigh_wavenumber is not None:
+        if is_sw and max_no_rayleigh_wavenumber is not None and not rayleigh_scattering:
             ncio.mask_rayleigh_up(s, max_no_rayleigh_wavenumber)                                     # :278-283
         if is_sw and erythemal_weight > 0.0 and "erythemal_spectrum" in s:
             s["spectral_boundary_weights"] = erythemal_weight * s["erythemal_spectrum"]              # solve_adept.cpp:182
@@ -244,7 +250,7 @@ def optimize_lut(ctx, model, training_files, relative_to=None, band_mapping=None
     if relative_to is not None:                                                                      # :204-236
         rel = load(relative_to)
         m0 = dict(model, iband_per_g=rel.get("iband_per_g", model["iband_per_g"]))
-        ref_opt = api.Optimizer(ctx, m0, [_scene_for_optimizer(rel, is_sw)], **cfg)
+        ref_opt = api.Optimizer(ctx, m0, [_scene_for_optimizer(rel, is_sw)], rayleigh_scattering=rayleigh_scattering, **cfg)
         _, fl = ref_opt.forward(ref_opt.initial_state(), unclamped=True)     # od = value(aod), no clamp (:231-234)
         ref_opt.close()
     scenes = []
@@ -263,7 +269,7 @@ def optimize_lut(ctx, model, training_files, relative_to=None, band_mapping=None
     m = dict(model)
     if iband is not None:
         m["iband_per_g"] = iband
-    opt = api.Optimizer(ctx, m, scenes, **dict(dict(cap_relative_linear=0.8), **cfg))                # :185
+    opt = api.Optimizer(ctx, m, scenes, rayleigh_scattering=rayleigh_scattering, **dict(dict(cap_relative_linear=0.8), **cfg))   # :185
     res = opt.minimize(max_iterations=max_iterations, convergence_criterion=convergence_criterion, bounded=bounded)
     out = dict(model, gases=[dict(g) for g in model["gases"]])
     for i, g in enumerate(out["gases"]):

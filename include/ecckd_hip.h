@@ -734,6 +734,21 @@ typedef struct {
 typedef struct ecckd_opt ecckd_opt;
 int ecckd_opt_create(ecckd_ctx* ctx, const ecckd_opt_model* model, int nscene,
                      const ecckd_opt_scene* scenes, const ecckd_opt_config* config, ecckd_opt** opt);
+/* ecckd_opt_create with flags (ecckd_opt_create is flags = 0).
+ * ECCKD_OPT_RAYLEIGH_SCATTERING: the shortwave forward model is the two-stream transfer with Rayleigh scattering that
+ * ecckd_lbl_band_fluxes_sw_rayleigh and ecckd_rt_sw_gpoints_rayleigh compute, not radiative_transfer_norayleigh_sw.  Per
+ * column and g point tau_abs is the gas optical depth after the clamp of negative values (and its penalty), tau_ray =
+ * moles_per_layer * rayleigh_molar_scattering[g], the incoming flux mu0 * tsi_scaling * solar_irradiance[g], the surface
+ * Lambertian with albedo[band of g] (a non-positive albedo counts as 0).  The cost is calc_cost_function_sw.cpp:116-277 on the
+ * TOTAL downwelling (direct + diffuse) and the upwelling flux, with the heating rates of model and scenes from the net flux
+ * dn - up; a scene's flux_dn, spectral_flux_dn_surf and relative_flux_dn are total downwelling fluxes.  ecckd_opt_forward(_ex)
+ * return (total dn, up) in h_flux and tau_abs + tau_ray in h_od.  Refused with ECCKD_PARAMETER_ERROR unless the model is
+ * shortwave with rayleigh_molar_scattering and at most 512 g points, every scene has mu0 and albedo, and the kernel's band and
+ * cost arrays (lds_bytes of ecckd_opt_forward_plan, about 48 nlay nband bytes) fit 160 KB of LDS.  Rayleigh stays a fixed
+ * pseudo gas. */
+#define ECCKD_OPT_RAYLEIGH_SCATTERING 1u
+int ecckd_opt_create_ex(ecckd_ctx* ctx, const ecckd_opt_model* model, int nscene, const ecckd_opt_scene* scenes,
+                        const ecckd_opt_config* config, unsigned flags, ecckd_opt** opt);
 int ecckd_opt_destroy(ecckd_opt* opt);
 /* length of the state vector x = ln(molar_abs) of the active gases, in model gas order */
 size_t ecckd_opt_nx(ecckd_opt* opt);
@@ -745,7 +760,11 @@ int ecckd_opt_cost_grad(ecckd_opt* opt, const double* h_x, double* J, double* h_
  * ECCKD_K8A_THREADS (64 ... 1024: threads per block in place of 1024 longwave / 512 shortwave), ECCKD_K8A_GENERIC=1 (the general
  * kernel).  cells: the cell-parallel kernel, instance <nc_template, shortwave, nb> (nc_template 4 or 8 cells per thread; nb 1 ... 4
  * eight-entry batches in straight-line code, 0 = the loop for more than 32 entries); cells == 0: the general kernel (nc_template
- * = nb = 0), which refuses lds_bytes > 160 KB when it is launched.  threads = ngpad * lgroups, ngpad = ng rounded up to 64. */
+ * = nb = 0), which refuses lds_bytes > 160 KB when it is launched.  threads = ngpad * lgroups, ngpad = ng rounded up to 64.
+ * A handle made with ECCKD_OPT_RAYLEIGH_SCATTERING runs one kernel at every shape, k_opt_forward_adjoint_rayleigh: cells = 2,
+ * nc_template = nb = 0 (its cells and table entries are loops), threads = ngpad * lgroups from 512 or ECCKD_K8A_THREADS (64 ... 512),
+ * lds_bytes = the band and cost arrays only (the per-level state lives in a device workspace of the handle; more than 160 KB
+ * was refused when the handle was made); ECCKD_K8A_GENERIC is not read. */
 typedef struct {
   int cells, nc_template, nb, threads, ngpad, lgroups;
   size_t lds_bytes;
