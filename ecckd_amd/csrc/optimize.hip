@@ -33,45 +33,19 @@
 #include <chrono>
 #include "rt_device.hpp"
 #include "lbl_rt.hpp"      // rayleigh_layer, rayleigh_layer_d, rayleigh_up, rayleigh_down: k_opt_forward_adjoint_rayleigh
+#include "opt_lds.hpp"     // the LDS layouts of the three K8a kernels, shared with the host plan
 
 #include <algorithm>
-#include <atomic>
-#include <immintrin.h>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
 namespace {
 
+namespace lds = ecckd::opt_lds;
+
 constexpr double kD = ECCKD_LW_DIFFUSIVITY;
 constexpr double MIN_X = -1.0e20;  // solve_adept.cpp:21
-
-struct GasInfo {
-  int conc = 0;       // 0 none, 1 linear, 2 lut, 3 relative-linear (ckd_model.cpp:1020-1086)
-  int active = 0;
-  int nconc = 1;
-  size_t nnode = 0;   // nconc*nt*np
-  size_t ix = 0;      // offset of this gas in the coefficient vector k
-  double reference_vmr = 0.0;
-  std::vector<double> vmr;
-  std::vector<double> sigma;  // background_error per g (ckd_model.cpp:672-683)
-};
-
-// per-dimension tridiagonal of an AR(1) inverse
-struct Tri { std::vector<double> lo, di, up; };
-
-Tri ar1_inverse(int n, double rho) {
-  Tri t;
-  t.lo.assign(n, 0.0); t.di.assign(n, 1.0); t.up.assign(n, 0.0);
-  if (n == 1) return t;
-  const double den = 1.0 - rho * rho;
-  for (int i = 0; i < n; ++i) {
-    t.di[i] = ((i == 0 || i == n - 1) ? 1.0 : 1.0 + rho * rho) / den;
-    if (i > 0) t.lo[i] = -rho / den;
-    if (i < n - 1) t.up[i] = -rho / den;
-  }
-  return t;
-}
 
 __device__ __forceinline__ double block_reduce_sum(double v, double* s_red) {
   // fixed-order reduction over a block of up to 1024 threads; result valid in every thread
@@ -89,45 +63,171 @@ __device__ __forceinline__ double block_reduce_sum(double v, double* s_red) {
   return t;
 }
 
-// K8a.  grid = ncolumns (all scenes), block = ng rounded up to 64.
-// LDS: tau[nlay][ng] | fdn[nhl][ng] | fup[nhl][ng] | Bdn[nhl][nband] | Bup[nhl][nband] |
-//      Gdn[nhl][nband] | Gup[nhl][nband] | red[16]
-__global__ void k_opt_forward_adjoint(
-    int do_sw, const double* __restrict__ mu0 /*[ncol], SW*/,
-    int ray_ent /* run_ckd mode: entry of the Rayleigh term, added AFTER the clamp; else -1 */,
-    int keep_negative /* scale_lut mode: the optical depth is reported without the clamp at zero */,
-    const double* __restrict__ rel_flux /* [ncol][2][nhl][ng] CKD fluxes of the relative-to scene, or NULL (solve_adept.cpp:118-125) */,
-    int nlay, int ng, int ngpad, int nband, int nent,
-    const double* __restrict__ k,            // [nk] coefficients of every gas
-    const int* __restrict__ ent_idx,         // [ncell][nent] start of an ng-long row of k, or -1
-    const double* __restrict__ ent_coef,     // [ncell][nent]
-    const int* __restrict__ band_of_g,       // [ng]
-    const double* __restrict__ planck_hl,    // [ncol][nhl][ng]
-    const double* __restrict__ surf_emis,    // [ncol][nband]
-    const double* __restrict__ conv,         // [ncol][nlay] heating-rate conversion
-    const double* __restrict__ layer_weight, // [ncol][nlay] normalised
-    const double* __restrict__ hr_true,      // [ncol][nlay][nband]
-    const double* __restrict__ fdn_true,     // [ncol][nhl][nband]
-    const double* __restrict__ fup_true,     // [ncol][nhl][nband]
-    const double* __restrict__ sfds,         // [ncol][ng] or NULL
-    const double* __restrict__ sfut,         // [ncol][ng] or NULL
-    double flux_weight, double flux_profile_weight, double broadband_weight,
-    double spectral_boundary_weight, double negative_od_penalty,
-    double* __restrict__ dtau,               // [ncell][ng] dJ/d(optical depth)
-    double* __restrict__ jcol,               // [ncol] cost of each profile (incl. penalty)
-    double* __restrict__ od_out,             // optional [ncell][ng] total optical depth (after clamp)
-    double* __restrict__ flux_out) {         // optional [ncol][2][nhl][ng]
+// ---- what the three K8a kernels share --------------------------------------------------------------------------------
+// Their common arguments, filled by k8a_args from the handle and the plan and passed by value.  Members are read by name only
+// (no pointer to the struct, no index into it), so they stay in scalar registers.
+struct K8aArgs {
+  int nlay, ng, ngpad, nband, nent;
+  int ray_ent;                 // entry of the Rayleigh term, kept apart from the absorbers (run_ckd mode: added AFTER the clamp), else -1
+  int keep_negative;           // scale_lut mode: the optical depth is reported without the clamp at zero; 2: the sweeps see it too
+  const double* mu0;           // [ncol], shortwave
+  const double* rel_flux;      // [ncol][2][nhl][ng] CKD fluxes of the relative-to scene, or NULL (solve_adept.cpp:118-125)
+  const double* k;             // [nk] coefficients of every gas
+  const int* ent_idx;          // [ncell][nent] start of an ng-long row of k, or -1
+  const double* ent_coef;      // [ncell][nent]
+  const int* band_of_g;        // [ng]
+  const double* planck_hl;     // [ncol][nhl][ng]; shortwave: row 0 of a column is the scaled solar irradiance
+  const double* surf_emis;     // [ncol][nband]; shortwave: the band albedo
+  const double* conv;          // [ncol][nlay] heating-rate conversion
+  const double* layer_weight;  // [ncol][nlay] normalised
+  const double* hr_true;       // [ncol][nlay][nband]
+  const double* fdn_true;      // [ncol][nhl][nband]
+  const double* fup_true;      // [ncol][nhl][nband]
+  const double* sfds;          // [ncol][ng] or NULL
+  const double* sfut;          // [ncol][ng] or NULL
+  double flux_weight, flux_profile_weight, broadband_weight, spectral_boundary_weight, negative_od_penalty;
+  double* dtau;                // [ncell][ng] dJ/d(optical depth)
+  double* jcol;                // [ncol] cost of each profile (incl. penalty)
+  double* od_out;              // optional [ncell][ng] total optical depth (after clamp)
+  double* flux_out;            // optional [ncol][2][nhl][ng]
+};
+
+constexpr double HR_WEIGHT = 3600.0 * 24.0;
+
+// the truth and weight rows of one column
+struct ColumnTruth { const double *cv, *lw, *hrt, *fdt, *fut; };
+__device__ __forceinline__ ColumnTruth column_truth(const K8aArgs& a, int col) {
+  const int nhl = a.nlay + 1;
+  return {a.conv + (size_t)col * a.nlay, a.layer_weight + (size_t)col * a.nlay, a.hr_true + (size_t)col * a.nlay * a.nband,
+          a.fdn_true + (size_t)col * nhl * a.nband, a.fup_true + (size_t)col * nhl * a.nband};
+}
+
+// How a flux at (half level, g) of this block's column is read: rows of LDS (the general and the cell-parallel kernel) ...
+struct LdsFlux {
+  const double *D, *U;
+  int ng;
+  __device__ __forceinline__ double dn(int i, int g) const { return D[i * ng + g]; }
+  __device__ __forceinline__ double up(int i, int g) const { return U[i * ng + g]; }
+};
+
+// Negative-OD penalty and clamp of one cell (solve_adept.cpp:107-116): penalty = negative_od_penalty * tau^2, then the optical
+// depth is SET to 0, so the only derivative that survives for a clamped cell is the penalty's.  Returns the absorption optical
+// depth as the sweeps see it (keep_negative == 2: as it comes out of the look-up tables, negative cells included: the
+// "relative_to" fluxes, od = value(aod) -> LblFluxes::calc_ckd_fluxes (optimize_lut.cpp:231-234), which has no clamp).
+// SCATTERING marks the two things k_opt_forward_adjoint_rayleigh does differently, both on purpose: it reports the TOTAL
+// optical depth tau + tau_ray (the other kernels: molecular absorption only, run_ckd.cpp:318-326), and it writes dJ/dtau of
+// every cell, 0 where nothing was clamped, because its phase E2 ADDS the transfer's share where the others store theirs.
+// (tau_ray is read by <true> alone, for the reported optical depth; the other kernels add it to what this returns.)
+template <bool SCATTERING>
+__device__ __forceinline__ double clamp_cell(const K8aArgs& a, size_t at, double tau, double tau_ray, bool& clamped, double& penalty) {
+  const double tau_raw = tau;
+  clamped = tau < 0.0;
+  if (clamped) {
+    penalty += tau * tau;
+    tau = 0.0;
+  }
+  if constexpr (SCATTERING) a.dtau[at] = clamped ? 2.0 * a.negative_od_penalty * tau_raw : 0.0;
+  else if (clamped) a.dtau[at] = 2.0 * a.negative_od_penalty * tau_raw;
+  if (a.od_out) {
+    const double od = (a.keep_negative && clamped) ? tau_raw : tau;
+    if constexpr (SCATTERING) a.od_out[at] = od + tau_ray; else a.od_out[at] = od;
+  }
+  return a.keep_negative == 2 ? tau_raw : tau;
+}
+
+// Longwave layer terms (radiative_transfer_lw.cpp:41-43): ex = exp(-D tau), eps = 1 - ex, fac
+__device__ __forceinline__ void lw_eps_fac(double tau, double& ex, double& eps, double& fac) {
+  ex = ecckd::exp_fast(-kD * tau);
+  eps = 1.0 - ex;
+  fac = (eps > 1.0e-5) ? 1.0 - ecckd::div_fast(eps * (1.0 / kD), tau) : 0.5 * eps;
+}
+
+// Adjoint of both longwave sweeps at layer l: dJ/dtau_l from the adjoints dn_bar of dn[l+1] and ubar_l of up[l], the forward
+// dn[l] and up[l+1], the Planck levels b0 = B_l, b1 = B_l+1, and tau, ex = exp(-D tau) of the layer
+//   dn_{l+1} = dn_l*(1-eps) + B_l*(eps-fac) + B_{l+1}*fac
+//   up_l     = up_{l+1}*(1-eps) + B_{l+1}*(eps-fac) + B_l*fac
+__device__ __forceinline__ double lw_tau_bar(double dn_bar, double ubar_l, double dn_l, double up_next, double b0, double b1, double tau, double ex) {
+  const double eps = 1.0 - ex;
+  const bool thick = eps > 1.0e-5;
+  const double rtau = thick ? ecckd::div_fast(1.0 / kD, tau) : 0.0;      // 1 / (D tau)
+  const double t_bar = dn_bar * dn_l + ubar_l * up_next;
+  const double a_bar = dn_bar * b0 + ubar_l * b1;
+  const double f_bar = dn_bar * b1 + ubar_l * b0;
+  const double eps_bar = -t_bar + a_bar;
+  const double fac_bar = f_bar - a_bar;
+  // fac(eps, tau): thick: 1 - eps/(D tau); thin: eps/2   (radiative_transfer_lw.cpp:42-43)
+  const double dfac_deps = thick ? -rtau : 0.5;
+  const double dfac_dtau = thick ? eps * rtau * (kD * rtau) : 0.0;        // eps / (D tau^2)
+  // (eps_bar + fac_bar dfac_deps) (D ex) + fac_bar dfac_dtau, with the fused multiply-add written out: of the two products the
+  // compiler may fuse either one into the sum, and which it picks has changed with the code around this function
+  return __builtin_fma(fac_bar, dfac_dtau, (eps_bar + fac_bar * dfac_deps) * (kD * ex));
+}
+
+// Weights of the squared band residuals of dn / up at half level i: spectral (s) and broadband (b).  lw: the column's layer weights.
+struct LevelWeights { double wd_s, wu_s, wd_b, wu_b; };
+__device__ __forceinline__ LevelWeights level_weights(const K8aArgs& a, const double* lw, bool sw, bool all_pos, int i) {
+  LevelWeights w = {0.0, 0.0, 0.0, 0.0};
+  if (i == a.nlay) { w.wd_s = a.flux_weight; w.wd_b = a.flux_weight; }
+  if (i == 0) {
+    // SW: 20 x on the spectral TOA upwelling (calc_cost_function_sw.cpp:214); its broadband term only if all albedos > 0 (:252)
+    w.wu_s = sw ? 20.0 * a.flux_weight : a.flux_weight;
+    w.wu_b = (!sw || all_pos) ? a.flux_weight : 0.0;
+  }
+  if (i >= 1 && i <= a.nlay - 1 && a.flux_profile_weight > 0.0) {
+    const double iw = a.flux_profile_weight * 0.5 * (lw[i - 1] + lw[i]);
+    w.wd_s = iw; w.wu_s = iw; w.wd_b = iw;
+    w.wu_b = (!sw || all_pos) ? iw : 0.0;                        // :264
+  }
+  return w;
+}
+
+// The per-g boundary term of the g point of this lane: longwave calc_cost_function_lw.cpp:223-229 on the un-banded fluxes at
+// the surface and the TOA; shortwave calc_cost_function_sw.cpp:271-274 with per-g (erythemal) weights, carried in sfut, on the
+// surface downwelling.  The relative-to fluxes are subtracted first.  Adds its cost to jpart and returns the seeds it adds to
+// dJ/d(dn at the surface) and dJ/d(up at the TOA).  (SW is a template argument, not a flag: with a flag the compiler merges the
+// stores of the two branches into one through a selected address, and the seeds leave the registers.)
+template <bool SW, class Flux>
+__device__ __forceinline__ void boundary_term(const K8aArgs& a, int col, int g, const Flux& flux, double& jpart,
+                                              double& g_dn_surf_extra, double& g_up_toa_extra) {
+  g_dn_surf_extra = 0.0; g_up_toa_extra = 0.0;
+  if (a.sfds && a.sfut && (SW || a.spectral_boundary_weight > 0.0)) {
+    const int nhl = a.nlay + 1;
+    const double reld = a.rel_flux ? a.rel_flux[((size_t)col * 2 * nhl + a.nlay) * a.ng + g] : 0.0;
+    const double d = (flux.dn(a.nlay, g) - reld) - a.sfds[(size_t)col * a.ng + g];
+    if constexpr (SW) {
+      const double wgt = a.sfut[(size_t)col * a.ng + g];
+      jpart += wgt * d * d;
+      g_dn_surf_extra = 2.0 * wgt * d;
+    } else {
+      const double relu = a.rel_flux ? a.rel_flux[((size_t)col * 2 * nhl + nhl) * a.ng + g] : 0.0;
+      const double c = (flux.up(0, g) - relu) - a.sfut[(size_t)col * a.ng + g];
+      jpart += a.spectral_boundary_weight * (d * d + c * c);
+      g_dn_surf_extra = 2.0 * a.spectral_boundary_weight * d;
+      g_up_toa_extra = 2.0 * a.spectral_boundary_weight * c;
+    }
+  }
+}
+
+// K8a, the general kernel.  grid = ncolumns (all scenes), block = ng rounded up to 64, LDS: lds::general.
+__global__ void k_opt_forward_adjoint(const K8aArgs a, int do_sw) {
   extern __shared__ double smem[];
+  const int nlay = a.nlay, ng = a.ng, ngpad = a.ngpad, nband = a.nband, nent = a.nent, ray_ent = a.ray_ent;
   const int nhl = nlay + 1;
-  double* s_tau = smem;
-  double* s_fdn = s_tau + (size_t)nlay * ng;
-  double* s_fup = s_fdn + (size_t)nhl * ng;
-  double* s_bdn = s_fup + (size_t)nhl * ng;
-  double* s_bup = s_bdn + (size_t)nhl * nband;
-  double* s_gdn = s_bup + (size_t)nhl * nband;
-  double* s_gup = s_gdn + (size_t)nhl * nband;
-  double* s_red = s_gup + (size_t)nhl * nband;
-  unsigned char* s_clamp = (unsigned char*)(s_red + 16);  // [nlay][ng] 1 where a negative optical depth was clamped
+  const auto L = lds::general(nlay, ng, nband);
+  auto arr = [&](int which) { return (double*)((char*)smem + L.off[which]); };
+  double* s_tau = arr(lds::GL_TAU);
+  double* s_fdn = arr(lds::GL_FDN);
+  double* s_fup = arr(lds::GL_FUP);
+  double* s_bdn = arr(lds::GL_BDN);
+  double* s_bup = arr(lds::GL_BUP);
+  double* s_gdn = arr(lds::GL_GDN);
+  double* s_gup = arr(lds::GL_GUP);
+  double* s_red = arr(lds::GL_RED);
+  unsigned char* s_clamp = (unsigned char*)arr(lds::GL_CLAMP);  // [nlay][ng] 1 where a negative optical depth was clamped
+  const double* const k = a.k; const int* const ent_idx = a.ent_idx; const double* const ent_coef = a.ent_coef;
+  const int* const band_of_g = a.band_of_g; const double* const surf_emis = a.surf_emis; const double* const rel_flux = a.rel_flux;
+  double* const dtau = a.dtau;
+  const double broadband_weight = a.broadband_weight;
   const int col = blockIdx.x;
   // blockDim = ngpad * (layer groups): the LUT gather is parallel over (layer group, g); the
   // sweeps and their adjoint are sequential in the layers and run on the first group only
@@ -136,12 +236,12 @@ __global__ void k_opt_forward_adjoint(
   const int nlgrp = blockDim.x / ngpad;
   const bool in_range = g < ng;
   const bool live = in_range && lgrp == 0;
-  const double hr_weight = 3600.0 * 24.0;
-  const double* pl = planck_hl + (size_t)col * nhl * ng;
+  const double hr_weight = HR_WEIGHT;
+  const double* pl = a.planck_hl + (size_t)col * nhl * ng;
   const size_t cell0 = (size_t)col * nlay;
 
   // ---- optical depth: sparse gather (calc_total_optical_depth, solve_adept.cpp:24-69) and
-  //      the negative-OD penalty with clamp (:107-116)
+  //      the negative-OD penalty with clamp (clamp_cell)
   double penalty = 0.0;
   if (in_range) {
     for (int l = lgrp; l < nlay; l += nlgrp) {
@@ -184,21 +284,9 @@ __global__ void k_opt_forward_adjoint(
           else tau += ec[e] * k[(size_t)idx + g];
         }
       }
-      const double tau_raw = tau;
-      if (tau < 0.0) {
-        // penalty = negative_od_penalty * tau^2, then the optical depth is SET to 0 (:110-113), so
-        // the only derivative that survives for this cell is the penalty's
-        penalty += tau * tau;
-        dtau[(cell0 + l) * ng + g] = 2.0 * negative_od_penalty * tau;
-        tau = 0.0;
-        s_clamp[l * ng + g] = 1;
-      } else {
-        s_clamp[l * ng + g] = 0;
-      }
-      if (od_out) od_out[(cell0 + l) * ng + g] = (keep_negative && s_clamp[l * ng + g]) ? tau_raw : tau;   // run_ckd mode: molecular absorption only (run_ckd.cpp:318-326)
-      // keep_negative == 2: the sweeps see the optical depth as it comes out of the look-up tables, negative cells included:
-      // the "relative_to" fluxes, od = value(aod) -> LblFluxes::calc_ckd_fluxes (optimize_lut.cpp:231-234), which has no clamp
-      if (keep_negative == 2) tau = tau_raw;
+      bool clamped;
+      tau = clamp_cell<false>(a, (cell0 + l) * ng + g, tau, tau_ray, clamped, penalty);
+      s_clamp[l * ng + g] = clamped ? 1 : 0;
       tau += tau_ray;
       s_tau[l * ng + g] = tau;
     }
@@ -215,16 +303,15 @@ __global__ void k_opt_forward_adjoint(
       all_pos = all_pos && pos;
       all_nonpos = all_nonpos && !pos;
     }
-    cos_sza = mu0[col];
+    cos_sza = a.mu0[col];
   }
   if (live && !do_sw) {
     // radiative_transfer_lw.cpp:41-59
     double dn = 0.0;
     s_fdn[g] = 0.0;
     for (int l = 0; l < nlay; ++l) {
-      const double tau = s_tau[l * ng + g];
-      const double eps = 1.0 - ecckd::exp_fast(-kD * tau);
-      const double fac = (eps > 1.0e-5) ? 1.0 - ecckd::div_fast(eps * (1.0 / kD), tau) : 0.5 * eps;
+      double ex, eps, fac;
+      lw_eps_fac(s_tau[l * ng + g], ex, eps, fac);
       dn = dn * (1.0 - eps) + pl[l * ng + g] * (eps - fac) + pl[(l + 1) * ng + g] * fac;
       s_fdn[(l + 1) * ng + g] = dn;
     }
@@ -232,9 +319,8 @@ __global__ void k_opt_forward_adjoint(
     double up = pl[nlay * ng + g] * es + (1.0 - es) * dn;  // surf_planck = planck_hl(end), optimize_lut.cpp:267
     s_fup[nlay * ng + g] = up;
     for (int l = nlay - 1; l >= 0; --l) {
-      const double tau = s_tau[l * ng + g];
-      const double eps = 1.0 - ecckd::exp_fast(-kD * tau);
-      const double fac = (eps > 1.0e-5) ? 1.0 - ecckd::div_fast(eps * (1.0 / kD), tau) : 0.5 * eps;
+      double ex, eps, fac;
+      lw_eps_fac(s_tau[l * ng + g], ex, eps, fac);
       up = up * (1.0 - eps) + pl[(l + 1) * ng + g] * (eps - fac) + pl[l * ng + g] * fac;
       s_fup[l * ng + g] = up;
     }
@@ -259,8 +345,8 @@ __global__ void k_opt_forward_adjoint(
     }
   }
   if (live) {
-    if (flux_out) {
-      double* fo = flux_out + (size_t)col * 2 * nhl * ng;
+    if (a.flux_out) {
+      double* fo = a.flux_out + (size_t)col * 2 * nhl * ng;
       for (int i = 0; i < nhl; ++i) {
         fo[i * ng + g] = s_fdn[i * ng + g];
         fo[(nhl + i) * ng + g] = s_fup[i * ng + g];
@@ -268,6 +354,9 @@ __global__ void k_opt_forward_adjoint(
     }
   }
   __syncthreads();
+  // The band sums and the cost below are this kernel's OWN, not band_sums / cost_residuals / cost_seed of the other two: it
+  // scans band_of_g instead of the bands' CSR, adds the heating-rate seeds in two passes and splits jpart over the threads
+  // differently (sharing would change jcol), and it is the independent form the tests cross-check the other two against.
   // ---- band sums (calc_cost_function_lw.cpp:171-184) ----
   for (int t = threadIdx.x; t < nhl * nband; t += blockDim.x) {
     const int i = t / nband, b = t % nband;
@@ -285,11 +374,8 @@ __global__ void k_opt_forward_adjoint(
   }
   __syncthreads();
   // ---- cost (:186-229) and its derivative w.r.t. the band fluxes ----
-  const double* cv = conv + (size_t)col * nlay;
-  const double* lw = layer_weight + (size_t)col * nlay;
-  const double* hrt = hr_true + (size_t)col * nlay * nband;
-  const double* fdt = fdn_true + (size_t)col * nhl * nband;
-  const double* fut = fup_true + (size_t)col * nhl * nband;
+  const ColumnTruth ct = column_truth(a, col);
+  const double *cv = ct.cv, *lw = ct.lw, *hrt = ct.hrt, *fdt = ct.fdt, *fut = ct.fut;
   // LW always mixes spectral and broadband (calc_cost_function_lw.cpp:209); SW only if broadband_weight > 0
   // (calc_cost_function_sw.cpp:243)
   const double spec_scale = (!do_sw || broadband_weight > 0.0) ? (1.0 - broadband_weight) / nband : 1.0;
@@ -329,21 +415,8 @@ __global__ void k_opt_forward_adjoint(
   }
   // boundary-flux and flux-profile terms: thread per half level
   for (int i = threadIdx.x; i < nhl; i += blockDim.x) {
-    const bool is_surf = (i == nlay), is_toa = (i == 0);
-    const bool interior = (i >= 1 && i <= nlay - 1);
-    // weights of the squared band residuals of dn / up at this level: spectral (s) and broadband (b)
-    double wd_s = 0.0, wu_s = 0.0, wd_b = 0.0, wu_b = 0.0;
-    if (is_surf) { wd_s = flux_weight; wd_b = flux_weight; }
-    if (is_toa) {
-      // SW: 20 x on the spectral TOA upwelling (:214); its broadband term only if all albedos > 0 (:252)
-      wu_s = do_sw ? 20.0 * flux_weight : flux_weight;
-      wu_b = (!do_sw || all_pos) ? flux_weight : 0.0;
-    }
-    if (interior && flux_profile_weight > 0.0) {
-      const double iw = flux_profile_weight * 0.5 * (lw[i - 1] + lw[i]);
-      wd_s = iw; wu_s = iw; wd_b = iw;
-      wu_b = (!do_sw || all_pos) ? iw : 0.0;   // :264
-    }
+    const LevelWeights w = level_weights(a, lw, do_sw != 0, all_pos, i);
+    const double wd_s = w.wd_s, wu_s = w.wu_s, wd_b = w.wd_b, wu_b = w.wu_b;
     if (wd_s != 0.0 || wu_s != 0.0) {
       double sd = 0.0, su = 0.0;
       for (int b = 0; b < nband; ++b) {
@@ -362,18 +435,12 @@ __global__ void k_opt_forward_adjoint(
   }
   __syncthreads();
   // ---- adjoint of the two sweeps, per g ----
+  const LdsFlux flux = {s_fdn, s_fup, ng};
+  double g_dn_surf_extra = 0.0, g_up_toa_extra = 0.0;
   if (live && do_sw) {
     const int b = band_of_g[g];
     const double alb = all_nonpos ? 0.0 : surf_emis[(size_t)col * nband + b];
-    double g_dn_surf_extra = 0.0;
-    if (sfds && sfut) {
-      // calc_cost_function_sw.cpp:271-274: per-g weights (erythemal) on the surface direct flux
-      const double wgt = sfut[(size_t)col * ng + g];
-      const double reld = rel_flux ? rel_flux[((size_t)col * 2 * nhl + nlay) * ng + g] : 0.0;
-      const double a = (s_fdn[nlay * ng + g] - reld) - sfds[(size_t)col * ng + g];
-      jpart += wgt * a * a;
-      g_dn_surf_extra = 2.0 * wgt * a;
-    }
+    boundary_term<true>(a, col, g, flux, jpart, g_dn_surf_extra, g_up_toa_extra);
     // up_l = up_{l+1} * exp(-2 tau_l): d up_l / d tau_l = -2 up_l
     double up_bar = s_gup[b];
     for (int l = 0; l < nlay; ++l) {
@@ -393,17 +460,7 @@ __global__ void k_opt_forward_adjoint(
   if (live && !do_sw) {
     const int b = band_of_g[g];
     const double es = surf_emis[(size_t)col * nband + b];
-    double g_dn_surf_extra = 0.0, g_up_toa_extra = 0.0;
-    if (spectral_boundary_weight > 0.0 && sfds && sfut) {
-      // :223-229 on the un-banded fluxes
-      const double reld = rel_flux ? rel_flux[((size_t)col * 2 * nhl + nlay) * ng + g] : 0.0;
-      const double relu = rel_flux ? rel_flux[((size_t)col * 2 * nhl + nhl) * ng + g] : 0.0;
-      const double a = (s_fdn[nlay * ng + g] - reld) - sfds[(size_t)col * ng + g];
-      const double c = (s_fup[g] - relu) - sfut[(size_t)col * ng + g];
-      jpart += spectral_boundary_weight * (a * a + c * c);
-      g_dn_surf_extra = 2.0 * spectral_boundary_weight * a;
-      g_up_toa_extra = 2.0 * spectral_boundary_weight * c;
-    }
+    boundary_term<false>(a, col, g, flux, jpart, g_dn_surf_extra, g_up_toa_extra);
     // Adjoint of the up sweep.  It ran l = nlay-1 .. 0 (up_l from up_{l+1}), so the adjoint of
     // up[l] is complete once levels 0..l-1 have been visited: u_bar[0] = seed[0],
     // u_bar[l+1] = seed[l+1] + u_bar[l]*(1-eps_l).  u_bar[l] overwrites the forward up[l] in LDS
@@ -425,22 +482,19 @@ __global__ void k_opt_forward_adjoint(
       const double eps = 1.0 - ex;
       const bool thick = eps > 1.0e-5;
       const double rtau = thick ? ecckd::div_fast(1.0 / kD, tau) : 0.0;      // 1 / (D tau)
-      const double fac = thick ? 1.0 - eps * rtau : 0.5 * eps;
+      // fac as the adjoint writes it, eps * (1 / (D tau)), not lw_eps_fac's (eps / D) / tau, and the product rounded before the
+      // subtraction: the rebuilt up[l] has always been this one (the product used to be shared with dfac_dtau, which kept the
+      // compiler from fusing it; written out so that it no longer depends on that)
+      double fac;
+      {
+#pragma clang fp contract(off)
+        const double eps_rtau = eps * rtau;
+        fac = thick ? 1.0 - eps_rtau : 0.5 * eps;
+      }
       const double b0 = pl[l * ng + g], b1 = pl[(l + 1) * ng + g];
       const double ubar_l = s_fup[l * ng + g];  // adjoint of up[l]
       const double dn_l = s_fdn[l * ng + g];
-      // partials of both sweeps for layer l
-      //   dn_{l+1} = dn_l*(1-eps) + B_l*(eps-fac) + B_{l+1}*fac
-      //   up_l     = up_{l+1}*(1-eps) + B_{l+1}*(eps-fac) + B_l*fac
-      const double t_bar = dn_bar * dn_l + ubar_l * up_fwd_next;
-      const double a_bar = dn_bar * b0 + ubar_l * b1;
-      const double f_bar = dn_bar * b1 + ubar_l * b0;
-      const double eps_bar = -t_bar + a_bar;
-      const double fac_bar = f_bar - a_bar;
-      // fac(eps, tau): thick: 1 - eps/(D tau); thin: eps/2   (radiative_transfer_lw.cpp:42-43)
-      const double dfac_deps = thick ? -rtau : 0.5;
-      const double dfac_dtau = thick ? eps * rtau * (kD * rtau) : 0.0;        // eps / (D tau^2)
-      const double tau_bar = (eps_bar + fac_bar * dfac_deps) * (kD * ex) + fac_bar * dfac_dtau;
+      const double tau_bar = lw_tau_bar(dn_bar, ubar_l, dn_l, up_fwd_next, b0, b1, tau, ex);
       if (!clamped) dtau[(cell0 + l) * ng + g] = tau_bar;
       // propagate
       const double up_l = up_fwd_next * (1.0 - eps) + b1 * (eps - fac) + b0 * fac;
@@ -448,9 +502,9 @@ __global__ void k_opt_forward_adjoint(
       dn_bar = dn_bar * (1.0 - eps) + s_gdn[l * nband + b];
     }
   }
-  jpart += negative_od_penalty * penalty;
+  jpart += a.negative_od_penalty * penalty;
   const double jtot = block_reduce_sum(jpart, s_red);
-  if (threadIdx.x == 0) jcol[col] = jtot;
+  if (threadIdx.x == 0) a.jcol[col] = jtot;
 }
 
 // ---- K8a, the form that runs (the kernel above stays as the general fall-back and as the cross-check of this one) ----
@@ -459,12 +513,14 @@ __global__ void k_opt_forward_adjoint(
 //      layer's transmittance and its two source terms (longwave: 1 - eps, B_l (eps - fac) + B_l+1 fac, B_l+1 (eps - fac) +
 //      B_l fac; shortwave: the two transmittances) - the `exp` and the division of every cell, 16 layers side by side;
 //   B  ONE wave runs the two recurrences dn_l+1 = dn_l t_l + s_l, up_l = up_l+1 t_l + s'_l: one FMA per layer from LDS;
-//   C, D  band sums and cost terms as in the kernel above (same code, same summation order);
+//   C, D  band sums and cost terms: band_sums, cost_residuals and cost_seed below, shared with the scattering kernel (the
+//      kernel above keeps a form of its own: it is the cross-check);
 //   E  the adjoint recurrences (again one FMA per layer on one wave), then every thread forms dJ/dtau of ITS cells from the
 //      adjoint and forward fluxes at its layer and what it kept in registers (tau, exp(-D tau)).
 // The sequential part of a profile shrinks from 4 x nlay (exp + division + recurrence) to 4 x nlay FMAs.  LDS per profile:
 // longwave t | dn | up, shortwave dn | up only (the transmittances sit in the rows the fluxes then overwrite, and come back
-// from the owners' registers for the adjoint recurrences) -> 107 KB / 79 KB at nlay = 54, ng = 64: two shortwave blocks per CU.
+// from the owners' registers for the adjoint recurrences) -> lds::cells: 100 KiB / 73 KiB at nlay = 54, ng = 64, 13 bands: two
+// shortwave blocks per CU (tools/check_opt_tables.cpp holds these figures).
 __device__ __forceinline__ double readlane_f64(double v, int src_lane) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), src_lane);
   const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src_lane);
@@ -532,41 +588,138 @@ __device__ __forceinline__ void gather_batches(int my_idx, double my_c, int e0, 
 constexpr int K8A_CH = 8;      // layers per prefetch chunk of the sequential recurrences
 constexpr int K8A_MAXR = 4;    // (half level, band) slots per thread in the cost phase: (nlay + 1) * nband <= K8A_MAXR * blockDim
 
+// ---- phases C and D of the cell-parallel and the scattering kernel ----
+// C: band sums (calc_cost_function_lw.cpp:171-184, calc_cost_function_sw.cpp:160-163) of the column's fluxes, read through
+// `flux`; the g points of a band (CSR s_bp, s_bg) in increasing order.
+template <class Flux>
+__device__ __forceinline__ void band_sums(const K8aArgs& a, int col, const Flux& flux, const int* s_bp, const int* s_bg, double* s_bdn, double* s_bup) {
+  const int nhl = a.nlay + 1, ng = a.ng, nband = a.nband;
+  const double* rel = a.rel_flux ? a.rel_flux + (size_t)col * 2 * nhl * ng : nullptr;
+  for (int t = threadIdx.x; t < nhl * nband; t += blockDim.x) {
+    const int i = t / nband, b = t % nband;
+    double sd = 0.0, su = 0.0;
+    for (int q = s_bp[b]; q < s_bp[b + 1]; ++q) {
+      const int gg = s_bg[q];
+      const double dn = flux.dn(i, gg), up = flux.up(i, gg);
+      // the relative-to fluxes are subtracted per g point before the band sums (calc_cost_function_lw.cpp:162-165)
+      sd += rel ? dn - rel[i * ng + gg] : dn;
+      su += rel ? up - rel[(nhl + i) * ng + gg] : up;
+    }
+    s_bdn[t] = sd;
+    s_bup[t] = su;
+  }
+}
+
+// The arrays of phase D in LDS: band fluxes in, residuals and their broadband sums out
+struct CostLds { double *bdn, *bup, *r, *rsum, *sd, *su; };
+
+// SW: the shortwave weights and scaling; NET: the heating rate comes from dn - up (longwave, scattering), else from dn alone
+// (shortwave without scattering: the direct beam, calc_cost_function_sw.cpp:197).  Instances: <false, true> longwave cells,
+// <true, false> shortwave cells, <true, true> scattering.
+template <bool SW>
+__device__ __forceinline__ double spectral_scale(const K8aArgs& a) {   // calc_cost_function_lw.cpp:209, sw :243
+  return (!SW || a.broadband_weight > 0.0) ? (1.0 - a.broadband_weight) / a.nband : 1.0;
+}
+
+// D1 one thread per (layer, band): heating-rate residual; D2 per layer / half level: the broadband sums, bands in order.
+// (calc_cost_function_lw.cpp:186-229; sw :186-277).  A barrier follows each; the cost shares go to this thread's jpart.
+template <bool SW, bool NET>
+__device__ __forceinline__ void cost_residuals(const K8aArgs& a, const ColumnTruth& ct, bool all_pos, const CostLds& s, double& jpart) {
+  const int nlay = a.nlay, nhl = nlay + 1, nband = a.nband;
+  const double spec_scale = spectral_scale<SW>(a);
+  const double up_in_hr = NET ? 1.0 : 0.0;
+  const double hrw2 = HR_WEIGHT * HR_WEIGHT;
+  for (int t = threadIdx.x; t < nlay * nband; t += blockDim.x) {
+    const int l = t / nband, b = t % nband;
+    const double hrf = ct.cv[l] * (s.bdn[(l + 1) * nband + b] - s.bdn[l * nband + b] -
+                                   up_in_hr * (s.bup[(l + 1) * nband + b] - s.bup[l * nband + b]));
+    const double r = hrf - ct.hrt[t];
+    s.r[t] = r;
+    jpart += spec_scale * hrw2 * ct.lw[l] * r * r;
+  }
+  __syncthreads();
+  for (int t = threadIdx.x; t < nlay + nhl; t += blockDim.x) {
+    if (t < nlay) {
+      double rsum = 0.0;
+      for (int b = 0; b < nband; ++b) rsum += s.r[t * nband + b];
+      s.rsum[t] = rsum;
+      jpart += a.broadband_weight * hrw2 * ct.lw[t] * rsum * rsum;
+    } else {
+      const int i = t - nlay;
+      double sd = 0.0, su = 0.0;
+      const LevelWeights w = level_weights(a, ct.lw, SW, all_pos, i);
+      if (w.wd_s != 0.0 || w.wu_s != 0.0) {
+        for (int b = 0; b < nband; ++b) {
+          sd += s.bdn[i * nband + b] - ct.fdt[i * nband + b];
+          su += s.bup[i * nband + b] - ct.fut[i * nband + b];
+        }
+        jpart += a.broadband_weight * (w.wd_b * sd * sd + w.wu_b * su * su);
+      }
+      s.sd[i] = sd;
+      s.su[i] = su;
+    }
+  }
+  __syncthreads();
+}
+
+// D3, slot t = (half level, band): dJ/d(band flux dn), dJ/d(band flux up), gathered from the two layers that touch the level
+// and the boundary / profile terms - every slot has one writer, no atomics.  The slot's cost share goes to jpart (added here,
+// not returned, so that the sum keeps the shape it has always had: a returned share could not fuse into jpart the same way).
+template <bool SW, bool NET>
+__device__ __forceinline__ void cost_seed(const K8aArgs& a, const ColumnTruth& ct, bool all_pos, const CostLds& s, int t, double& gd, double& gu, double& jpart) {
+  const int nlay = a.nlay, nband = a.nband;
+  const double spec_scale = spectral_scale<SW>(a);
+  const double hrw2 = HR_WEIGHT * HR_WEIGHT;
+  const int i = t / nband, b = t % nband;
+  gd = 0.0; gu = 0.0;
+  if (i >= 1) {                                                 // layer i-1 ends at this level
+    const int l = i - 1;
+    const double dhr = 2.0 * hrw2 * ct.lw[l] * (spec_scale * s.r[l * nband + b] + a.broadband_weight * s.rsum[l]);
+    gd = dhr * ct.cv[l];
+    if (NET) gu = -dhr * ct.cv[l];
+  }
+  if (i <= nlay - 1) {                                          // layer i starts at it
+    const double dhr = 2.0 * hrw2 * ct.lw[i] * (spec_scale * s.r[i * nband + b] + a.broadband_weight * s.rsum[i]);
+    gd += -dhr * ct.cv[i];
+    if (NET) gu += dhr * ct.cv[i];
+  }
+  const LevelWeights w = level_weights(a, ct.lw, SW, all_pos, i);
+  if (w.wd_s != 0.0 || w.wu_s != 0.0) {
+    const double dd = s.bdn[t] - ct.fdt[t];
+    const double du = s.bup[t] - ct.fut[t];
+    jpart += spec_scale * (w.wd_s * dd * dd + w.wu_s * du * du);
+    gd += 2.0 * (spec_scale * w.wd_s * dd + a.broadband_weight * w.wd_b * s.sd[i]);
+    gu += 2.0 * (spec_scale * w.wu_s * du + a.broadband_weight * w.wu_b * s.su[i]);
+  }
+}
+
 template <int NC, bool SW, int NB>
 __global__ void __launch_bounds__(1024)
-k_opt_forward_adjoint_cells(
-    const double* __restrict__ mu0, int ray_ent, int keep_negative, const double* __restrict__ rel_flux,
-    int nlay, int ng, int ngpad, int nband, int nent,
-    const double* __restrict__ k, const int* __restrict__ ent_idx, const double* __restrict__ ent_coef,
-    const int* __restrict__ band_of_g, const int* __restrict__ band_ptr /*[nband+1]*/, const int* __restrict__ band_g /*[ng]: g points by band*/,
-    const double* __restrict__ planck_hl, const double* __restrict__ surf_emis,
-    const double* __restrict__ conv, const double* __restrict__ layer_weight, const double* __restrict__ hr_true,
-    const double* __restrict__ fdn_true, const double* __restrict__ fup_true, const double* __restrict__ sfds,
-    const double* __restrict__ sfut, double flux_weight, double flux_profile_weight, double broadband_weight,
-    double spectral_boundary_weight, double negative_od_penalty, double* __restrict__ dtau, double* __restrict__ jcol,
-    double* __restrict__ od_out, double* __restrict__ flux_out) {
+k_opt_forward_adjoint_cells(const K8aArgs a, const int* __restrict__ band_ptr /*[nband+1]*/, const int* __restrict__ band_g /*[ng]: g points by band*/) {
   extern __shared__ double smem[];
+  const int nlay = a.nlay, ng = a.ng, ngpad = a.ngpad, nband = a.nband, nent = a.nent, ray_ent = a.ray_ent;
   const int nhl = nlay + 1;
-  double* s_T = smem;                                            // longwave only: [nlay][ng] 1 - eps
-  double* s_D = s_T + (SW ? (size_t)0 : (size_t)nlay * ng);      // [nhl][ng] down: sources / transmittances, fluxes, adjoints
-  double* s_U = s_D + (size_t)nhl * ng;                          // [nhl][ng] up
-  double* s_bdn = s_U + (size_t)nhl * ng;                        // [nhl][nband] band fluxes, then dJ/d(band flux)
-  double* s_bup = s_bdn + (size_t)nhl * nband;
-  double* s_r = s_bup + (size_t)nhl * nband;                     // [nlay][nband] heating-rate residuals
-  double* s_rsum = s_r + (size_t)nlay * nband;                   // [nlay] their broadband sums
-  double* s_sd = s_rsum + nlay;                                  // [nhl] broadband flux residuals
-  double* s_su = s_sd + nhl;
-  double* s_red = s_su + nhl;                                    // [16]
-  int* s_bp = (int*)(s_red + 16);                                // [nband + 1]
-  int* s_bg = s_bp + nband + 1;                                  // [ng]
+  const auto L = lds::cells(nlay, ng, nband, SW);
+  auto arr = [&](int which) { return (double*)((char*)smem + L.off[which]); };
+  double* s_T = arr(lds::CL_T);                                  // longwave only: [nlay][ng] 1 - eps
+  double* s_D = arr(lds::CL_D);                                  // [nhl][ng] down: sources / transmittances, fluxes, adjoints
+  double* s_U = arr(lds::CL_U);                                  // [nhl][ng] up
+  double* s_bdn = arr(lds::CL_BDN);                              // [nhl][nband] band fluxes, then dJ/d(band flux)
+  double* s_bup = arr(lds::CL_BUP);
+  // [nlay][nband] heating-rate residuals, [nlay] their broadband sums, 2 x [nhl] broadband flux residuals
+  const CostLds cost = {s_bdn, s_bup, arr(lds::CL_R), arr(lds::CL_RSUM), arr(lds::CL_SD), arr(lds::CL_SU)};
+  double* s_red = arr(lds::CL_RED);                              // [16]
+  int* s_bp = (int*)arr(lds::CL_BP);                             // [nband + 1]
+  int* s_bg = (int*)arr(lds::CL_BG);                             // [ng]
+  const double* const k = a.k; const int* const ent_idx = a.ent_idx; const double* const ent_coef = a.ent_coef;
+  const int* const band_of_g = a.band_of_g; const double* const surf_emis = a.surf_emis; double* const dtau = a.dtau;
   const int col = blockIdx.x;
   const int g = threadIdx.x % ngpad;
   const int lgrp = __builtin_amdgcn_readfirstlane(threadIdx.x / ngpad);     // ngpad is a multiple of 64: uniform in a wave
   const int nlgrp = blockDim.x / ngpad;
   const bool in_range = g < ng;
   const bool live = in_range && lgrp == 0;
-  const double hr_weight = 3600.0 * 24.0;
-  const double* pl = planck_hl + (size_t)col * nhl * ng;
+  const double* pl = a.planck_hl + (size_t)col * nhl * ng;
   const size_t cell0 = (size_t)col * nlay;
   bool all_pos = true, all_nonpos = true;
   double cos_sza = 1.0;
@@ -576,7 +729,7 @@ k_opt_forward_adjoint_cells(
       all_pos = all_pos && pos;
       all_nonpos = all_nonpos && !pos;
     }
-    cos_sza = mu0[col];
+    cos_sza = a.mu0[col];
   }
   const double minus_sec_sza = -1.0 / cos_sza;
   for (int t = threadIdx.x; t <= nband; t += blockDim.x) s_bp[t] = band_ptr[t];
@@ -615,23 +768,14 @@ k_opt_forward_adjoint_cells(
         gather_batches<0>(my_idx, my_c, e0, ne, k, gl, ray_ent, tau, tau_ray);
       }
       if (in_range) {
-        const double tau_raw = tau;
-        bool clamped = false;
-        if (tau < 0.0) {
-          penalty += tau * tau;                                       // solve_adept.cpp:110-113
-          dtau[(cell0 + l) * ng + g] = 2.0 * negative_od_penalty * tau;
-          tau = 0.0;
-          clamped = true;
-          clamp_mask |= 1u << j;
-        }
-        if (od_out) od_out[(cell0 + l) * ng + g] = (keep_negative && clamped) ? tau_raw : tau;
-        if (keep_negative == 2) tau = tau_raw;
+        bool clamped;
+        tau = clamp_cell<false>(a, (cell0 + l) * ng + g, tau, tau_ray, clamped, penalty);
+        if (clamped) clamp_mask |= 1u << j;
         tau += tau_ray;
         c_tau[j] = tau;
         if constexpr (!SW) {
-          const double ex = ecckd::exp_fast(-kD * tau);
-          const double eps = 1.0 - ex;
-          const double fac = (eps > 1.0e-5) ? 1.0 - ecckd::div_fast(eps * (1.0 / kD), tau) : 0.5 * eps;   // radiative_transfer_lw.cpp:41-43
+          double ex, eps, fac;
+          lw_eps_fac(tau, ex, eps, fac);
           const double b0 = pl[l * ng + g], b1 = pl[(l + 1) * ng + g];
           c_t[j] = ex;
           s_T[l * ng + g] = 1.0 - eps;
@@ -703,116 +847,30 @@ k_opt_forward_adjoint_cells(
     }
   }
   __syncthreads();
-  if (flux_out && in_range) {
-    double* fo = flux_out + (size_t)col * 2 * nhl * ng;
+  if (a.flux_out && in_range) {
+    double* fo = a.flux_out + (size_t)col * 2 * nhl * ng;
     for (int i = lgrp; i < nhl; i += nlgrp) {
       fo[i * ng + g] = s_D[i * ng + g];
       fo[(nhl + i) * ng + g] = s_U[i * ng + g];
     }
   }
-  // ---- C: band sums (calc_cost_function_lw.cpp:171-184), the g points of a band in increasing order ----
-  const double* cv = conv + (size_t)col * nlay;
-  const double* lw = layer_weight + (size_t)col * nlay;
-  const double* hrt = hr_true + (size_t)col * nlay * nband;
-  const double* fdt = fdn_true + (size_t)col * nhl * nband;
-  const double* fut = fup_true + (size_t)col * nhl * nband;
-  for (int t = threadIdx.x; t < nhl * nband; t += blockDim.x) {
-    const int i = t / nband, b = t % nband;
-    double sd = 0.0, su = 0.0;
-    const double* rel = rel_flux ? rel_flux + (size_t)col * 2 * nhl * ng : nullptr;
-    for (int q = s_bp[b]; q < s_bp[b + 1]; ++q) {
-      const int gg = s_bg[q];
-      // the relative-to fluxes are subtracted per g point before the band sums (calc_cost_function_lw.cpp:162-165)
-      sd += rel ? s_D[i * ng + gg] - rel[i * ng + gg] : s_D[i * ng + gg];
-      su += rel ? s_U[i * ng + gg] - rel[(nhl + i) * ng + gg] : s_U[i * ng + gg];
-    }
-    s_bdn[t] = sd;
-    s_bup[t] = su;
-  }
+  // ---- C: band sums of the flux rows ----
+  const LdsFlux flux = {s_D, s_U, ng};
+  const ColumnTruth ct = column_truth(a, col);
+  band_sums(a, col, flux, s_bp, s_bg, s_bdn, s_bup);
   __syncthreads();
-  // ---- D: cost (:186-229) and its derivative with respect to the band fluxes ----
-  // D1 one thread per (layer, band): heating-rate residual; D2 per layer / half level: the broadband sums, bands in order;
-  // D3 per (half level, band): dJ/d(band flux) gathered from the two layers that touch the level and the boundary / profile
-  // terms - every slot has one writer, no atomics.
-  const double spec_scale = (!SW || broadband_weight > 0.0) ? (1.0 - broadband_weight) / nband : 1.0;   // :209, sw :243
-  const double up_in_hr = SW ? 0.0 : 1.0;                         // shortwave heating rate from the direct beam only (:197)
-  const double hrw2 = hr_weight * hr_weight;
+  // ---- D: cost and its derivative with respect to the band fluxes; the heating rate takes the net flux in the longwave ----
   double jpart = 0.0;
-  for (int t = threadIdx.x; t < nlay * nband; t += blockDim.x) {
-    const int l = t / nband, b = t % nband;
-    const double hrf = cv[l] * (s_bdn[(l + 1) * nband + b] - s_bdn[l * nband + b] -
-                                up_in_hr * (s_bup[(l + 1) * nband + b] - s_bup[l * nband + b]));
-    const double r = hrf - hrt[t];
-    s_r[t] = r;
-    jpart += spec_scale * hrw2 * lw[l] * r * r;
-  }
-  __syncthreads();
-  // weights of the squared residuals of dn / up at half level i: spectral (s) and broadband (b)
-  auto level_weights = [&](int i, double& wd_s, double& wu_s, double& wd_b, double& wu_b) {
-    wd_s = 0.0; wu_s = 0.0; wd_b = 0.0; wu_b = 0.0;
-    if (i == nlay) { wd_s = flux_weight; wd_b = flux_weight; }
-    if (i == 0) {
-      wu_s = SW ? 20.0 * flux_weight : flux_weight;              // calc_cost_function_sw.cpp:214
-      wu_b = (!SW || all_pos) ? flux_weight : 0.0;               // :252
-    }
-    if (i >= 1 && i <= nlay - 1 && flux_profile_weight > 0.0) {
-      const double iw = flux_profile_weight * 0.5 * (lw[i - 1] + lw[i]);
-      wd_s = iw; wu_s = iw; wd_b = iw;
-      wu_b = (!SW || all_pos) ? iw : 0.0;                        // :264
-    }
-  };
-  for (int t = threadIdx.x; t < nlay + nhl; t += blockDim.x) {
-    if (t < nlay) {
-      double rsum = 0.0;
-      for (int b = 0; b < nband; ++b) rsum += s_r[t * nband + b];
-      s_rsum[t] = rsum;
-      jpart += broadband_weight * hrw2 * lw[t] * rsum * rsum;
-    } else {
-      const int i = t - nlay;
-      double wd_s, wu_s, wd_b, wu_b, sd = 0.0, su = 0.0;
-      level_weights(i, wd_s, wu_s, wd_b, wu_b);
-      if (wd_s != 0.0 || wu_s != 0.0) {
-        for (int b = 0; b < nband; ++b) {
-          sd += s_bdn[i * nband + b] - fdt[i * nband + b];
-          su += s_bup[i * nband + b] - fut[i * nband + b];
-        }
-        jpart += broadband_weight * (wd_b * sd * sd + wu_b * su * su);
-      }
-      s_sd[i] = sd;
-      s_su[i] = su;
-    }
-  }
-  __syncthreads();
+  cost_residuals<SW, !SW>(a, ct, all_pos, cost, jpart);
   {
-    // (at most two rounds: nhl * nband <= 2 * blockDim is not required, the values wait in registers for the barrier)
+    // The seeds overwrite the band fluxes they are made from, so they wait in registers for the barrier: up to K8A_MAXR rounds
+    // of the block over the (half level, band) slots (forward_plan refuses a shape that needs more)
     constexpr int MAXR = K8A_MAXR;
     double gd_r[MAXR], gu_r[MAXR];
     int nr = 0;
     for (int t = threadIdx.x; t < nhl * nband && nr < MAXR; t += blockDim.x, ++nr) {
-      const int i = t / nband, b = t % nband;
-      double gd = 0.0, gu = 0.0;
-      {
-      if (i >= 1) {                                               // layer i-1 ends at this level
-        const int l = i - 1;
-        const double dhr = 2.0 * hrw2 * lw[l] * (spec_scale * s_r[l * nband + b] + broadband_weight * s_rsum[l]);
-        gd = dhr * cv[l];
-        if (!SW) gu = -dhr * cv[l];
-      }
-      if (i <= nlay - 1) {                                        // layer i starts at it
-        const double dhr = 2.0 * hrw2 * lw[i] * (spec_scale * s_r[i * nband + b] + broadband_weight * s_rsum[i]);
-        gd += -dhr * cv[i];
-        if (!SW) gu += dhr * cv[i];
-      }
-      double wd_s, wu_s, wd_b, wu_b;
-      level_weights(i, wd_s, wu_s, wd_b, wu_b);
-      if (wd_s != 0.0 || wu_s != 0.0) {
-        const double dd = s_bdn[t] - fdt[t];
-        const double du = s_bup[t] - fut[t];
-        jpart += spec_scale * (wd_s * dd * dd + wu_s * du * du);
-        gd += 2.0 * (spec_scale * wd_s * dd + broadband_weight * wd_b * s_sd[i]);
-        gu += 2.0 * (spec_scale * wu_s * du + broadband_weight * wu_b * s_su[i]);
-      }
-      }
+      double gd, gu;
+      cost_seed<SW, !SW>(a, ct, all_pos, cost, t, gd, gu, jpart);
       gd_r[nr] = gd;
       gu_r[nr] = gu;
     }
@@ -837,23 +895,7 @@ k_opt_forward_adjoint_cells(
     }
   }
   double g_dn_surf_extra = 0.0, g_up_toa_extra = 0.0;
-  if (live && sfds && sfut && (SW || spectral_boundary_weight > 0.0)) {
-    // per-g boundary terms: calc_cost_function_lw.cpp:223-229 on the un-banded fluxes; calc_cost_function_sw.cpp:271-274
-    // with per-g (erythemal) weights on the surface direct flux
-    const double reld = rel_flux ? rel_flux[((size_t)col * 2 * nhl + nlay) * ng + g] : 0.0;
-    const double a = (s_D[nlay * ng + g] - reld) - sfds[(size_t)col * ng + g];
-    if (SW) {
-      const double wgt = sfut[(size_t)col * ng + g];
-      jpart += wgt * a * a;
-      g_dn_surf_extra = 2.0 * wgt * a;
-    } else {
-      const double relu = rel_flux ? rel_flux[((size_t)col * 2 * nhl + nhl) * ng + g] : 0.0;
-      const double c = (s_U[g] - relu) - sfut[(size_t)col * ng + g];
-      jpart += spectral_boundary_weight * (a * a + c * c);
-      g_dn_surf_extra = 2.0 * spectral_boundary_weight * a;
-      g_up_toa_extra = 2.0 * spectral_boundary_weight * c;
-    }
-  }
+  if (live) boundary_term<SW>(a, col, g, flux, jpart, g_dn_surf_extra, g_up_toa_extra);
   __syncthreads();
   if constexpr (SW) {
     // the transmittances back into the rows the fluxes occupied
@@ -929,29 +971,14 @@ k_opt_forward_adjoint_cells(
         // up_l = up_l+1 exp(-2 tau_l), dn_l+1 = dn_l exp(-tau_l / mu0)
         tau_bar = ubar_l * c_f1[j] * (-2.0) + dnbar * c_f0[j] * minus_sec_sza;
       } else {
-        const double tau = c_tau[j], ex = c_t[j];
-        const double eps = 1.0 - ex;
-        const bool thick = eps > 1.0e-5;
-        const double rtau = thick ? ecckd::div_fast(1.0 / kD, tau) : 0.0;      // 1 / (D tau)
-        const double b0 = pl[l * ng + g], b1 = pl[(l + 1) * ng + g];
-        //   dn_{l+1} = dn_l*(1-eps) + B_l*(eps-fac) + B_{l+1}*fac
-        //   up_l     = up_{l+1}*(1-eps) + B_{l+1}*(eps-fac) + B_l*fac
-        const double t_bar = dnbar * c_f0[j] + ubar_l * c_f1[j];
-        const double a_bar = dnbar * b0 + ubar_l * b1;
-        const double f_bar = dnbar * b1 + ubar_l * b0;
-        const double eps_bar = -t_bar + a_bar;
-        const double fac_bar = f_bar - a_bar;
-        // fac(eps, tau): thick: 1 - eps/(D tau); thin: eps/2   (radiative_transfer_lw.cpp:42-43)
-        const double dfac_deps = thick ? -rtau : 0.5;
-        const double dfac_dtau = thick ? eps * rtau * (kD * rtau) : 0.0;        // eps / (D tau^2)
-        tau_bar = (eps_bar + fac_bar * dfac_deps) * (kD * ex) + fac_bar * dfac_dtau;
+        tau_bar = lw_tau_bar(dnbar, ubar_l, c_f0[j], c_f1[j], pl[l * ng + g], pl[(l + 1) * ng + g], c_tau[j], c_t[j]);
       }
       dtau[(cell0 + l) * ng + g] = tau_bar;
     }
   }
-  jpart += negative_od_penalty * penalty;
+  jpart += a.negative_od_penalty * penalty;
   const double jtot = block_reduce_sum(jpart, s_red);
-  if (threadIdx.x == 0) jcol[col] = jtot;
+  if (threadIdx.x == 0) a.jcol[col] = jtot;
 }
 
 // ---- K8a with Rayleigh scattering (ECCKD_OPT_RAYLEIGH_SCATTERING): the two-stream transfer of lbl_rt.hpp and its adjoint ----
@@ -976,7 +1003,8 @@ k_opt_forward_adjoint_cells(
 //   per cell  dJ/dtau_abs = Rb R' + Tb T' + Tdirb Tdir' + Rdirb Rdir' + Tddb Tdd',  ' = d/dtau_abs of rayleigh_layer_d
 // Phases.  A (every lane owns the cells l = lgrp + j nlgrp of its g point): look-up, clamp and penalty, rayleigh_layer and
 // rayleigh_layer_d - every exp, sqrt and division of the layer terms; B (one wave per 64 g points): the three forward
-// recurrences over the stored terms; C, D: band sums and cost as in k_opt_forward_adjoint_cells; E1 (one wave per 64 g
+// recurrences over the stored terms; C, D: band_sums over D + V and U of the workspace, then cost_residuals and cost_seed
+// <shortwave, net flux>, the functions the cell-parallel kernel calls; E1 (one wave per 64 g
 // points): the three reversed recurrences - FMAs and one division per layer and sweep; E2 (cell owners): the sum above.
 // The per-(level, g) state does not fit the LDS (23 arrays of (nlay + 1) ng doubles): it lives in a workspace of the handle,
 // ws[column][slot][level][g], so a wave reads and writes 512 contiguous bytes; every element is written and read either by its
@@ -988,6 +1016,15 @@ enum RaySlot { RS_R, RS_T, RS_TDIR, RS_RDIR, RS_TDD,             // the layer te
                RS_AB, RS_SB, RS_DB,                              // adjoints of A, S, D
                RS_RB, RS_TB, RS_TDIRB, RS_RDIRB, RS_TDDB,        // adjoints of the layer terms
                RS_COUNT };
+
+// ... or (see LdsFlux) the column's slots of the workspace: total downwelling D + V, upwelling U
+struct RayleighFlux {
+  const double* wc;
+  size_t slot;
+  int ng;
+  __device__ __forceinline__ double dn(int i, int g) const { return wc[RS_D * slot + i * ng + g] + wc[RS_V * slot + i * ng + g]; }
+  __device__ __forceinline__ double up(int i, int g) const { return wc[RS_U * slot + i * ng + g]; }
+};
 
 // B: the forward recurrences of one g point; every pointer is its slot at this g, rows ng apart
 __device__ __forceinline__ void rayleigh_forward_sweeps(int nlay, int ng, double d0, double alb, const double* __restrict__ pR,
@@ -1089,30 +1126,24 @@ __device__ __forceinline__ void rayleigh_adjoint_sweeps(int nlay, int ng, int nb
 }
 
 __global__ void __launch_bounds__(512)
-k_opt_forward_adjoint_rayleigh(
-    const double* __restrict__ mu0, int ray_ent, int keep_negative, const double* __restrict__ rel_flux,
-    int nlay, int ng, int ngpad, int nband, int nent,
-    const double* __restrict__ k, const int* __restrict__ ent_idx, const double* __restrict__ ent_coef,
-    const int* __restrict__ band_of_g, const int* __restrict__ band_ptr /*[nband+1]*/, const int* __restrict__ band_g /*[ng]: g points by band*/,
-    const double* __restrict__ planck_hl /* row 0 of a column: the scaled solar irradiance */, const double* __restrict__ albedo /*[ncol][nband]*/,
-    const double* __restrict__ conv, const double* __restrict__ layer_weight, const double* __restrict__ hr_true,
-    const double* __restrict__ fdn_true, const double* __restrict__ fup_true, const double* __restrict__ sfds,
-    const double* __restrict__ sfut, double flux_weight, double flux_profile_weight, double broadband_weight,
-    double negative_od_penalty, double* ws /*[ncol][RS_COUNT][nlay+1][ng]*/, double* __restrict__ dtau, double* __restrict__ jcol,
-    double* __restrict__ od_out, double* __restrict__ flux_out) {
+k_opt_forward_adjoint_rayleigh(const K8aArgs a, const int* __restrict__ band_ptr /*[nband+1]*/, const int* __restrict__ band_g /*[ng]: g points by band*/,
+                               double* ws /*[ncol][RS_COUNT][nlay+1][ng]*/) {
   extern __shared__ double smem[];
+  const int nlay = a.nlay, ng = a.ng, ngpad = a.ngpad, nband = a.nband, nent = a.nent, ray_ent = a.ray_ent;
   const int nhl = nlay + 1;
-  double* s_bdn = smem;                                          // [nhl][nband] band fluxes
-  double* s_bup = s_bdn + (size_t)nhl * nband;
-  double* s_gdn = s_bup + (size_t)nhl * nband;                   // [nhl][nband] dJ/d(band flux)
-  double* s_gup = s_gdn + (size_t)nhl * nband;
-  double* s_r = s_gup + (size_t)nhl * nband;                     // [nlay][nband] heating-rate residuals
-  double* s_rsum = s_r + (size_t)nlay * nband;                   // [nlay] their broadband sums
-  double* s_sd = s_rsum + nlay;                                  // [nhl] broadband flux residuals
-  double* s_su = s_sd + nhl;
-  double* s_red = s_su + nhl;                                    // [16]
-  int* s_bp = (int*)(s_red + 16);                                // [nband + 1]
-  int* s_bg = s_bp + nband + 1;                                  // [ng]
+  const auto layout = lds::rayleigh(nlay, ng, nband);
+  auto arr = [&](int which) { return (double*)((char*)smem + layout.off[which]); };
+  double* s_bdn = arr(lds::RL_BDN);                              // [nhl][nband] band fluxes
+  double* s_bup = arr(lds::RL_BUP);
+  double* s_gdn = arr(lds::RL_GDN);                              // [nhl][nband] dJ/d(band flux)
+  double* s_gup = arr(lds::RL_GUP);
+  // [nlay][nband] heating-rate residuals, [nlay] their broadband sums, 2 x [nhl] broadband flux residuals
+  const CostLds cost = {s_bdn, s_bup, arr(lds::RL_R), arr(lds::RL_RSUM), arr(lds::RL_SD), arr(lds::RL_SU)};
+  double* s_red = arr(lds::RL_RED);                              // [16]
+  int* s_bp = (int*)arr(lds::RL_BP);                             // [nband + 1]
+  int* s_bg = (int*)arr(lds::RL_BG);                             // [ng]
+  const double* const k = a.k; const int* const ent_idx = a.ent_idx; const double* const ent_coef = a.ent_coef;
+  const int* const band_of_g = a.band_of_g; const double* const albedo = a.surf_emis; double* const dtau = a.dtau;
   const int col = blockIdx.x;
   const int g = threadIdx.x % ngpad;
   const int lgrp = __builtin_amdgcn_readfirstlane(threadIdx.x / ngpad);     // ngpad is a multiple of 64: uniform in a wave
@@ -1121,14 +1152,13 @@ k_opt_forward_adjoint_rayleigh(
   const bool live = in_range && lgrp == 0;
   const int lane = threadIdx.x & 63;
   const int gl = in_range ? g : 0;        // lanes beyond the last g point read (and drop) the first one's values
-  const double hr_weight = 3600.0 * 24.0;
-  const double* pl = planck_hl + (size_t)col * nhl * ng;
+  const double* pl = a.planck_hl + (size_t)col * nhl * ng;      // row 0: the scaled solar irradiance
   const size_t cell0 = (size_t)col * nlay;
   const size_t slot = (size_t)nhl * ng;
   double* w = ws + (size_t)col * RS_COUNT * slot + gl;           // slot q of this g point: w + q * slot, rows ng apart
   bool all_pos = true;
   for (int b = 0; b < nband; ++b) all_pos = all_pos && albedo[(size_t)col * nband + b] > 0.0;
-  const double cos_sza = mu0[col];
+  const double cos_sza = a.mu0[col];
   const double minus_sec_sza = -1.0 / cos_sza;
   for (int t = threadIdx.x; t <= nband; t += blockDim.x) s_bp[t] = band_ptr[t];
   for (int t = threadIdx.x; t < ng; t += blockDim.x) s_bg[t] = band_g[t];
@@ -1144,16 +1174,10 @@ k_opt_forward_adjoint_rayleigh(
       gather_batches<0>(my_idx, my_c, e0, ne, k, gl, ray_ent, tau, tau_ray);
     }
     if (in_range) {
-      const double tau_raw = tau;
-      const bool clamped = tau < 0.0;
-      if (clamped) {
-        penalty += tau * tau;                                         // solve_adept.cpp:110-113
-        tau = 0.0;
-      }
-      // the penalty's derivative, all a clamped cell passes on; phase E2 adds the transfer's share (0 there: its d terms are 0)
-      dtau[(cell0 + l) * ng + g] = clamped ? 2.0 * negative_od_penalty * tau_raw : 0.0;
-      if (keep_negative == 2) tau = tau_raw;                          // the "relative_to" evaluation: no clamp
-      if (od_out) od_out[(cell0 + l) * ng + g] = ((keep_negative && clamped) ? tau_raw : tau) + tau_ray;
+      // <true>: dJ/dtau of every cell is written here - the penalty's derivative, all a clamped cell passes on (phase E2 adds
+      // the transfer's share, 0 there: its d terms are 0) - and the reported optical depth includes tau_ray; both are meant
+      bool clamped;
+      tau = clamp_cell<true>(a, (cell0 + l) * ng + g, tau, tau_ray, clamped, penalty);
       const ecckd::lbl::RayleighLayer L = ecckd::lbl::rayleigh_layer(tau, tau_ray, cos_sza, minus_sec_sza);
       const ecckd::lbl::RayleighLayer dL = ecckd::lbl::rayleigh_layer_d(tau, tau_ray, cos_sza, minus_sec_sza);
       double* wl = w + (size_t)l * ng;
@@ -1170,119 +1194,32 @@ k_opt_forward_adjoint_rayleigh(
                             w + RS_TDD * slot, w + RS_D * slot, w + RS_A * slot, w + RS_S * slot, w + RS_V * slot, w + RS_U * slot);
   __syncthreads();
   const double* wc = ws + (size_t)col * RS_COUNT * slot;         // the column's slots, any g
-  if (flux_out && in_range) {
-    double* fo = flux_out + (size_t)col * 2 * nhl * ng;
+  const RayleighFlux flux = {wc, slot, ng};
+  if (a.flux_out && in_range) {
+    double* fo = a.flux_out + (size_t)col * 2 * nhl * ng;
     for (int i = lgrp; i < nhl; i += nlgrp) {
-      fo[i * ng + g] = wc[RS_D * slot + i * ng + g] + wc[RS_V * slot + i * ng + g];       // total downwelling
-      fo[(nhl + i) * ng + g] = wc[RS_U * slot + i * ng + g];
+      fo[i * ng + g] = flux.dn(i, g);                            // total downwelling
+      fo[(nhl + i) * ng + g] = flux.up(i, g);
     }
   }
-  // ---- C: band sums of the total downwelling and the upwelling flux, the g points of a band in increasing order ----
-  const double* cv = conv + (size_t)col * nlay;
-  const double* lw = layer_weight + (size_t)col * nlay;
-  const double* hrt = hr_true + (size_t)col * nlay * nband;
-  const double* fdt = fdn_true + (size_t)col * nhl * nband;
-  const double* fut = fup_true + (size_t)col * nhl * nband;
-  const double* rel = rel_flux ? rel_flux + (size_t)col * 2 * nhl * ng : nullptr;
-  for (int t = threadIdx.x; t < nhl * nband; t += blockDim.x) {
-    const int i = t / nband, b = t % nband;
-    double sd = 0.0, su = 0.0;
-    for (int q = s_bp[b]; q < s_bp[b + 1]; ++q) {
-      const int gg = s_bg[q];
-      const double dn = wc[RS_D * slot + i * ng + gg] + wc[RS_V * slot + i * ng + gg];
-      const double up = wc[RS_U * slot + i * ng + gg];
-      // the relative-to fluxes are subtracted per g point before the band sums (calc_cost_function_sw.cpp:160-163)
-      sd += rel ? dn - rel[i * ng + gg] : dn;
-      su += rel ? up - rel[(nhl + i) * ng + gg] : up;
-    }
-    s_bdn[t] = sd;
-    s_bup[t] = su;
-  }
+  // ---- C: band sums of the total downwelling and the upwelling flux ----
+  const ColumnTruth ct = column_truth(a, col);
+  band_sums(a, col, flux, s_bp, s_bg, s_bdn, s_bup);
   __syncthreads();
-  // ---- D: the shortwave cost (calc_cost_function_sw.cpp:186-277) and its derivative with respect to the band fluxes, as
-  //      phase D of k_opt_forward_adjoint_cells with the heating rate from the net flux ----
-  const double spec_scale = broadband_weight > 0.0 ? (1.0 - broadband_weight) / nband : 1.0;   // :243
-  const double hrw2 = hr_weight * hr_weight;
+  // ---- D: the shortwave cost (calc_cost_function_sw.cpp:186-277) with the heating rate from the net flux, and its
+  //      derivative with respect to the band fluxes; a second pair of arrays takes the seeds, so they are stored directly ----
   double jpart = 0.0;
-  for (int t = threadIdx.x; t < nlay * nband; t += blockDim.x) {
-    const int l = t / nband, b = t % nband;
-    const double hrf = cv[l] * (s_bdn[(l + 1) * nband + b] - s_bdn[l * nband + b] - (s_bup[(l + 1) * nband + b] - s_bup[l * nband + b]));
-    const double r = hrf - hrt[t];
-    s_r[t] = r;
-    jpart += spec_scale * hrw2 * lw[l] * r * r;
-  }
-  __syncthreads();
-  // weights of the squared residuals of dn / up at half level i: spectral (s) and broadband (b)
-  auto level_weights = [&](int i, double& wd_s, double& wu_s, double& wd_b, double& wu_b) {
-    wd_s = 0.0; wu_s = 0.0; wd_b = 0.0; wu_b = 0.0;
-    if (i == nlay) { wd_s = flux_weight; wd_b = flux_weight; }
-    if (i == 0) {
-      wu_s = 20.0 * flux_weight;                                 // :214
-      wu_b = all_pos ? flux_weight : 0.0;                        // :252
-    }
-    if (i >= 1 && i <= nlay - 1 && flux_profile_weight > 0.0) {
-      const double iw = flux_profile_weight * 0.5 * (lw[i - 1] + lw[i]);
-      wd_s = iw; wu_s = iw; wd_b = iw;
-      wu_b = all_pos ? iw : 0.0;                                 // :264
-    }
-  };
-  for (int t = threadIdx.x; t < nlay + nhl; t += blockDim.x) {
-    if (t < nlay) {
-      double rsum = 0.0;
-      for (int b = 0; b < nband; ++b) rsum += s_r[t * nband + b];
-      s_rsum[t] = rsum;
-      jpart += broadband_weight * hrw2 * lw[t] * rsum * rsum;
-    } else {
-      const int i = t - nlay;
-      double wd_s, wu_s, wd_b, wu_b, sd = 0.0, su = 0.0;
-      level_weights(i, wd_s, wu_s, wd_b, wu_b);
-      if (wd_s != 0.0 || wu_s != 0.0) {
-        for (int b = 0; b < nband; ++b) {
-          sd += s_bdn[i * nband + b] - fdt[i * nband + b];
-          su += s_bup[i * nband + b] - fut[i * nband + b];
-        }
-        jpart += broadband_weight * (wd_b * sd * sd + wu_b * su * su);
-      }
-      s_sd[i] = sd;
-      s_su[i] = su;
-    }
-  }
-  __syncthreads();
+  cost_residuals<true, true>(a, ct, all_pos, cost, jpart);
   for (int t = threadIdx.x; t < nhl * nband; t += blockDim.x) {
-    const int i = t / nband, b = t % nband;
-    double gd = 0.0, gu = 0.0;
-    if (i >= 1) {                                                 // layer i-1 ends at this level
-      const int l = i - 1;
-      const double dhr = 2.0 * hrw2 * lw[l] * (spec_scale * s_r[l * nband + b] + broadband_weight * s_rsum[l]);
-      gd = dhr * cv[l];
-      gu = -dhr * cv[l];
-    }
-    if (i <= nlay - 1) {                                          // layer i starts at it
-      const double dhr = 2.0 * hrw2 * lw[i] * (spec_scale * s_r[i * nband + b] + broadband_weight * s_rsum[i]);
-      gd += -dhr * cv[i];
-      gu += dhr * cv[i];
-    }
-    double wd_s, wu_s, wd_b, wu_b;
-    level_weights(i, wd_s, wu_s, wd_b, wu_b);
-    if (wd_s != 0.0 || wu_s != 0.0) {
-      const double dd = s_bdn[t] - fdt[t];
-      const double du = s_bup[t] - fut[t];
-      jpart += spec_scale * (wd_s * dd * dd + wu_s * du * du);
-      gd += 2.0 * (spec_scale * wd_s * dd + broadband_weight * wd_b * s_sd[i]);
-      gu += 2.0 * (spec_scale * wu_s * du + broadband_weight * wu_b * s_su[i]);
-    }
+    double gd, gu;
+    cost_seed<true, true>(a, ct, all_pos, cost, t, gd, gu, jpart);
     s_gdn[t] = gd;
     s_gup[t] = gu;
   }
-  double dn_surf_extra = 0.0;
-  if (live && sfds && sfut) {
-    // calc_cost_function_sw.cpp:271-274: per-g weights (erythemal) on the total downwelling flux at the surface
-    const double reld = rel ? rel[nlay * ng + g] : 0.0;
-    const double a = ((wc[RS_D * slot + nlay * ng + g] + wc[RS_V * slot + nlay * ng + g]) - reld) - sfds[(size_t)col * ng + g];
-    const double wgt = sfut[(size_t)col * ng + g];
-    jpart += wgt * a * a;
-    dn_surf_extra = 2.0 * wgt * a;
-  }
+  // the per-g (erythemal) weights act on the total downwelling flux at the surface; no term on the upwelling in the shortwave:
+  // boundary_term<true> leaves up_toa_extra at 0 and nothing reads it
+  double dn_surf_extra = 0.0, up_toa_extra = 0.0;
+  if (live) boundary_term<true>(a, col, g, flux, jpart, dn_surf_extra, up_toa_extra);
   __syncthreads();
   // ---- E1: the reversed recurrences, one wave per 64 g points ----
   if (live) {
@@ -1303,9 +1240,9 @@ k_opt_forward_adjoint_rayleigh(
       dtau[(cell0 + l) * ng + g] += tau_bar;
     }
   }
-  jpart += negative_od_penalty * penalty;
+  jpart += a.negative_od_penalty * penalty;
   const double jtot = block_reduce_sum(jpart, s_red);
-  if (threadIdx.x == 0) jcol[col] = jtot;
+  if (threadIdx.x == 0) a.jcol[col] = jtot;
 }
 
 // K8b + K9: gradient of the state, two launches of one WAVE per task, four waves per block, no LDS, no barrier.
@@ -1495,12 +1432,6 @@ __device__ __forceinline__ void write_partials(double (&acc)[NACC], int nused, d
     for (int w = 0; w < VEC_WAVES; ++w) t += s_all[threadIdx.x * VEC_WAVES + w];
     part[(size_t)threadIdx.x * VEC_BLOCKS + blockIdx.x] = t;
   }
-}
-
-// dynamic LDS of k_opt_forward_adjoint_rayleigh: the band and cost arrays alone, whatever the block size
-size_t rayleigh_lds_bytes(int nlay, int nband, int ng) {
-  const size_t nhl = (size_t)nlay + 1;
-  return (4 * nhl * nband + (size_t)nlay * nband + nlay + 2 * nhl + 16) * sizeof(double) + ((size_t)nband + 1 + ng) * sizeof(int);
 }
 
 // ---- L-BFGS on the device, compact representation (Byrd, Nocedal & Schnabel 1994) -----------------------------
@@ -1871,8 +1802,8 @@ int ecckd_opt_create_ex(ecckd_ctx* ctx, const ecckd_opt_model* m, int nscene, co
   if (o->scattering) {
     // the LDS of k_opt_forward_adjoint_rayleigh depends on the shapes alone: refused here, where the handle is made, and the
     // kernel's limit raised once, not at every launch of the minimiser's loop
-    const size_t lds = rayleigh_lds_bytes(o->nlay, o->nband, o->ng);
-    ECCKD_REQUIRE(lds <= 160 * 1024, "ecckd_opt_create_ex: nlay * nband too large for the LDS of the scattering kernel (%zu B)", lds);
+    const size_t bytes = lds::rayleigh(o->nlay, o->ng, o->nband).bytes();
+    ECCKD_REQUIRE(bytes <= 160 * 1024, "ecckd_opt_create_ex: nlay * nband too large for the LDS of the scattering kernel (%zu B)", bytes);
     ECCKD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_opt_forward_adjoint_rayleigh),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   }
@@ -1942,38 +1873,50 @@ int ecckd_opt_initial_state(ecckd_opt* o, double* h_x, double* h_x_min, double* 
 
 namespace {
 
+// The arguments the three K8a kernels share, from the handle and the plan.  A scattering handle always keeps the Rayleigh entry
+// apart from the absorbers; the others only in a run_ckd pass.  A diagnostic pass changes keep_negative and the two outputs.
+K8aArgs k8a_args(const ecckd_opt* o, const ecckd_forward_plan& p) {
+  K8aArgs a{};
+  a.nlay = o->nlay; a.ng = o->ng; a.ngpad = p.ngpad; a.nband = o->nband; a.nent = o->nent;
+  a.ray_ent = o->scattering ? o->ray_ent : o->eval_ray_ent;
+  a.keep_negative = o->eval_keep_negative;
+  a.mu0 = o->d_mu0; a.rel_flux = o->d_rel; a.k = o->d_k; a.ent_idx = o->d_ent_idx; a.ent_coef = o->d_ent_coef; a.band_of_g = o->d_band;
+  a.planck_hl = o->d_planck; a.surf_emis = o->d_semis; a.conv = o->d_conv; a.layer_weight = o->d_lw;
+  a.hr_true = o->d_hr; a.fdn_true = o->d_fdn; a.fup_true = o->d_fup; a.sfds = o->d_sfds; a.sfut = o->d_sfut;
+  a.flux_weight = o->cfg.flux_weight; a.flux_profile_weight = o->cfg.flux_profile_weight; a.broadband_weight = o->cfg.broadband_weight;
+  a.spectral_boundary_weight = o->cfg.spectral_boundary_weight; a.negative_od_penalty = o->cfg.negative_od_penalty;
+  a.dtau = o->d_dtau; a.jcol = o->d_jcol; a.od_out = o->d_od_out; a.flux_out = o->d_flux_out;
+  return a;
+}
+
 // The cell-parallel K8a kernel, one instance per (cells per thread, shortwave, 8-entry batches of a cell's table).
 template <int NC, bool SW, int NB>
-int launch_cells(ecckd_opt* o, int threads, size_t lds, int ngpad) {
+int launch_cells(ecckd_opt* o, const ecckd_forward_plan& p) {
   const auto kernel = k_opt_forward_adjoint_cells<NC, SW, NB>;
   ECCKD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  hipLaunchKernelGGL(kernel, dim3((unsigned)o->ncol), dim3(threads), lds, o->ctx->stream, o->d_mu0, o->eval_ray_ent,
-                     o->eval_keep_negative, o->d_rel, o->nlay, o->ng, ngpad, o->nband, o->nent, o->d_k, o->d_ent_idx, o->d_ent_coef,
-                     o->d_band, o->d_band_ptr, o->d_band_g, o->d_planck, o->d_semis, o->d_conv, o->d_lw, o->d_hr, o->d_fdn, o->d_fup,
-                     o->d_sfds, o->d_sfut, o->cfg.flux_weight, o->cfg.flux_profile_weight, o->cfg.broadband_weight,
-                     o->cfg.spectral_boundary_weight, o->cfg.negative_od_penalty, o->d_dtau, o->d_jcol, o->d_od_out, o->d_flux_out);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)o->ncol), dim3(p.threads), p.lds_bytes, o->ctx->stream, k8a_args(o, p), o->d_band_ptr, o->d_band_g);
   return ECCKD_OK;
 }
 
 template <int NC, bool SW>
-int launch_cells_nb(int nb, ecckd_opt* o, int threads, size_t lds, int ngpad) {
-  switch (nb) {
-    case 1: return launch_cells<NC, SW, 1>(o, threads, lds, ngpad);
-    case 2: return launch_cells<NC, SW, 2>(o, threads, lds, ngpad);
-    case 3: return launch_cells<NC, SW, 3>(o, threads, lds, ngpad);
-    case 4: return launch_cells<NC, SW, 4>(o, threads, lds, ngpad);
-    default: return launch_cells<NC, SW, 0>(o, threads, lds, ngpad);
+int launch_cells_nb(ecckd_opt* o, const ecckd_forward_plan& p) {
+  switch (p.nb) {
+    case 1: return launch_cells<NC, SW, 1>(o, p);
+    case 2: return launch_cells<NC, SW, 2>(o, p);
+    case 3: return launch_cells<NC, SW, 3>(o, p);
+    case 4: return launch_cells<NC, SW, 4>(o, p);
+    default: return launch_cells<NC, SW, 0>(o, p);
   }
 }
 
-int launch_cells_for(int nc, int nb, ecckd_opt* o, int threads, size_t lds, int ngpad) {   // nc: 4 or 8, the instance
-  if (o->do_sw) return nc <= 4 ? launch_cells_nb<4, true>(nb, o, threads, lds, ngpad) : launch_cells_nb<8, true>(nb, o, threads, lds, ngpad);
-  return nc <= 4 ? launch_cells_nb<4, false>(nb, o, threads, lds, ngpad) : launch_cells_nb<8, false>(nb, o, threads, lds, ngpad);
+int launch_cells_for(ecckd_opt* o, const ecckd_forward_plan& p) {   // p.nc_template: 4 or 8, the instance
+  if (o->do_sw) return p.nc_template <= 4 ? launch_cells_nb<4, true>(o, p) : launch_cells_nb<8, true>(o, p);
+  return p.nc_template <= 4 ? launch_cells_nb<4, false>(o, p) : launch_cells_nb<8, false>(o, p);
 }
 
 // Which K8a kernel a forward pass runs and how it is launched: a function of the shapes and the two environment knobs alone
 // (ecckd_opt_forward_plan reports it, opt_launch_forward launches from it and from nothing else).
-//   cell-parallel kernel: longwave 1 024 threads (16 layer groups at ng = 64, one block per CU), shortwave 512 (8 groups, 79 KB
+//   cell-parallel kernel: longwave 1 024 threads (16 layer groups at ng = 64, one block per CU), shortwave 512 (8 groups, 73 KiB
 //   of LDS: two blocks per CU), `env_threads` (64 ... 1024, else 0) in place of either; up to 8 cells per thread (the <4> and
 //   <8> instances), nb = 8-entry batches of a cell's table among its first 64 entries (1 ... 4 in straight-line code, 0 = the loop);
 //   else the general kernel, whose LDS tile the caller has to check against 160 KB.
@@ -1985,24 +1928,22 @@ ecckd_forward_plan forward_plan(bool do_sw, int nlay, int ng, int nband, int nen
     const int threads_c = env_threads ? env_threads : (do_sw ? 512 : 1024);
     const int lgroups = std::max(1, threads_c / p.ngpad);
     const int nc = (nlay + lgroups - 1) / lgroups;
-    const size_t lds = ((do_sw ? (size_t)0 : (size_t)nlay * ng) + 2 * (size_t)nhl * ng + 2 * (size_t)nhl * nband + (size_t)nlay * nband +
-                        nlay + 2 * (size_t)nhl + 16) * sizeof(double) + ((size_t)nband + 1 + ng) * sizeof(int);
-    if (!force_generic && nc <= 8 && lds <= 160 * 1024 && p.ngpad * lgroups <= 1024 && nhl * nband <= K8A_MAXR * p.ngpad * lgroups) {
+    const size_t bytes = lds::cells(nlay, ng, nband, do_sw).bytes();
+    if (!force_generic && nc <= 8 && bytes <= 160 * 1024 && p.ngpad * lgroups <= 1024 && nhl * nband <= K8A_MAXR * p.ngpad * lgroups) {
       p.cells = 1;
       p.nc_template = nc <= 4 ? 4 : 8;
       const int nb = (std::min(nent, 64) + K8A_GB - 1) / K8A_GB;       // 8-entry batches of a cell's table (first 64 entries)
       p.nb = nb <= 4 ? nb : 0;
       p.threads = p.ngpad * lgroups;
       p.lgroups = lgroups;
-      p.lds_bytes = lds;
+      p.lds_bytes = bytes;
       return p;
     }
   }
   const int k8a_threads = env_threads ? env_threads : 1024;
   p.lgroups = std::max(1, k8a_threads / p.ngpad);
   p.threads = p.ngpad * p.lgroups;
-  p.lds_bytes = ((size_t)nlay * ng + 2 * (size_t)nhl * ng + 4 * (size_t)nhl * nband + 16) * sizeof(double) +
-                ecckd_align_up((size_t)nlay * ng, 16);
+  p.lds_bytes = lds::general(nlay, ng, nband).bytes();
   return p;
 }
 
@@ -2019,7 +1960,7 @@ ecckd_forward_plan opt_forward_plan(const ecckd_opt* o) {
     p.ngpad = (o->ng + 63) / 64 * 64;
     p.lgroups = std::max(1, (v >= 64 && v <= 512 ? v : 512) / p.ngpad);   // (ecckd_opt_create_ex has refused ng > 512)
     p.threads = p.ngpad * p.lgroups;
-    p.lds_bytes = rayleigh_lds_bytes(o->nlay, o->nband, o->ng);
+    p.lds_bytes = lds::rayleigh(o->nlay, o->ng, o->nband).bytes();
     return p;
   }
   const char* env_generic = std::getenv("ECCKD_K8A_GENERIC");
@@ -2032,28 +1973,20 @@ int opt_launch_forward(ecckd_opt* o) {
   const ecckd_forward_plan p = opt_forward_plan(o);
   if (o->scattering) {
     // (ecckd_opt_create_ex has checked the LDS and raised the kernel's limit; the Rayleigh entry is always kept apart from the absorbers; a diagnostic pass changes only keep_negative)
-    hipLaunchKernelGGL(k_opt_forward_adjoint_rayleigh, dim3((unsigned)o->ncol), dim3(p.threads), p.lds_bytes, ctx->stream, o->d_mu0,
-                       o->ray_ent, o->eval_keep_negative, o->d_rel, o->nlay, o->ng, p.ngpad, o->nband, o->nent, o->d_k, o->d_ent_idx,
-                       o->d_ent_coef, o->d_band, o->d_band_ptr, o->d_band_g, o->d_planck, o->d_semis, o->d_conv, o->d_lw, o->d_hr,
-                       o->d_fdn, o->d_fup, o->d_sfds, o->d_sfut, o->cfg.flux_weight, o->cfg.flux_profile_weight, o->cfg.broadband_weight,
-                       o->cfg.negative_od_penalty, o->d_ray_ws, o->d_dtau, o->d_jcol, o->d_od_out, o->d_flux_out);
+    hipLaunchKernelGGL(k_opt_forward_adjoint_rayleigh, dim3((unsigned)o->ncol), dim3(p.threads), p.lds_bytes, ctx->stream, k8a_args(o, p),
+                       o->d_band_ptr, o->d_band_g, o->d_ray_ws);
     ECCKD_HIP_CHECK(hipGetLastError());
     return ECCKD_OK;
   }
   if (p.cells) {
-    ECCKD_CHECK(launch_cells_for(p.nc_template, p.nb, o, p.threads, p.lds_bytes, p.ngpad));
+    ECCKD_CHECK(launch_cells_for(o, p));
     ECCKD_HIP_CHECK(hipGetLastError());
     return ECCKD_OK;
   }
-  const int nlay = o->nlay, ng = o->ng, nband = o->nband;
   ECCKD_REQUIRE(p.lds_bytes <= 160 * 1024, "ecckd_opt_cost_grad: nlay*ng too large for the per-profile LDS tile (%zu B)", p.lds_bytes);
   ECCKD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_opt_forward_adjoint),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  hipLaunchKernelGGL(k_opt_forward_adjoint, dim3((unsigned)o->ncol), dim3(p.threads), p.lds_bytes, ctx->stream, o->do_sw ? 1 : 0,
-                     o->d_mu0, o->eval_ray_ent, o->eval_keep_negative, o->d_rel, nlay, ng, p.ngpad, nband, o->nent, o->d_k, o->d_ent_idx, o->d_ent_coef, o->d_band, o->d_planck, o->d_semis, o->d_conv,
-                     o->d_lw, o->d_hr, o->d_fdn, o->d_fup, o->d_sfds, o->d_sfut, o->cfg.flux_weight,
-                     o->cfg.flux_profile_weight, o->cfg.broadband_weight, o->cfg.spectral_boundary_weight,
-                     o->cfg.negative_od_penalty, o->d_dtau, o->d_jcol, o->d_od_out, o->d_flux_out);
+  hipLaunchKernelGGL(k_opt_forward_adjoint, dim3((unsigned)o->ncol), dim3(p.threads), p.lds_bytes, ctx->stream, k8a_args(o, p), o->do_sw ? 1 : 0);
   ECCKD_HIP_CHECK(hipGetLastError());
   return ECCKD_OK;
 }

@@ -221,6 +221,16 @@ def test_more_level_band_slots_than_threads(ctx, oracle, monkeypatch):
     _check(ctx, oracle, monkeypatch, prob, plan, sw=True, negative=True)[0].close()
 
 
+@pytest.mark.parametrize("sw", [False, True], ids=["lw", "sw"])
+def test_second_round_of_the_staged_seed_store(ctx, oracle, monkeypatch, sw):
+    """ECCKD_K8A_THREADS = 64, 9 bands, 8 layers: 9 * 9 = 81 (half level, band) slots on one wave - 17 threads hold a second
+    slot in registers across the barrier before the seeds overwrite the band fluxes; one layer group, 8 cells per thread"""
+    monkeypatch.setenv("ECCKD_K8A_THREADS", "64")
+    prob = opt_shapes.problem(oracle, ng=12, nband=9, nlay=8, ncol=2, sw=sw, negative=True, seed=5)
+    plan = dict(cells=True, nc_template=8, nb=4 if sw else 3, threads=64, ngpad=64, lgroups=1)
+    _check(ctx, oracle, monkeypatch, prob, plan, sw=sw, negative=True)[0].close()
+
+
 # ---- (d) a profile too large for either kernel ------------------------------------------------------------------------------
 
 def test_profile_too_large_is_refused_and_the_context_lives_on(ctx, oracle, monkeypatch):

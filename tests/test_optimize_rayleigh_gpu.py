@@ -166,6 +166,20 @@ def test_shapes(ctx, oracle, nlay, ng, nband, threads, monkeypatch):
     opt.close()
 
 
+def test_more_level_band_slots_than_threads(ctx, oracle, monkeypatch):
+    """ECCKD_K8A_THREADS = 64, 9 bands, 8 layers: 81 (half level, band) slots on one wave, so the band sums, the residuals and
+    the seeds of the cost phase each take a second round of the block; one layer group"""
+    monkeypatch.setenv("ECCKD_K8A_THREADS", "64")
+    model, scenes, cfg, orc = _problem(oracle, seed=3, ng=12, nband=9, nlay=8, nscene=1, ncol=2, albedo=np.linspace(0.3, 0.06, 9))
+    opt = _opt(ctx, model, scenes, cfg)
+    plan = opt.forward_plan()
+    assert plan["kernel"] == "rayleigh" and plan["threads"] == 64 and plan["lgroups"] == 1
+    x, free, rs = _state(opt, orc, 6)
+    _check_forward(ctx, opt, orc, scenes, x)
+    _check_cost_and_gradient(opt, orc, cfg, scenes, x, free, rs)
+    opt.close()
+
+
 def test_degenerate_limit_matches_the_plain_shortwave_handle(ctx, oracle):
     """rayleigh_molar_scattering = 0: no diffuse light, the scattering handle's total downwelling is the plain handle's direct
     beam and the upwelling fluxes agree (the w = 0 branch of rayleigh_layer is the no-scattering transfer)"""

@@ -3,7 +3,8 @@
 // points, a g point of no band, a gas absent from a scene, a profile outside the look-up table on both sides, longwave and shortwave
 // with Rayleigh scattering, both K8b orders - and checks that every index the kernels follow is -1 or in range, that the two K8b
 // orders hold every task once, and that the transpose holds exactly the non-zero entries of the gather.  Then the history: more
-// pairs than the ring holds, one rejected, one restart; the triangular solves are checked by their residuals.
+// pairs than the ring holds, one rejected, one restart; the triangular solves are checked by their residuals.  First of all the
+// LDS layouts of the K8a kernels (csrc/opt_lds.hpp): nlay 1 / 17 / 54 / 128 x ng 1 / 64 / 70 x nband 1 / 13, longwave and shortwave.
 // build: g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Iecckd_amd/csrc tools/check_opt_tables.cpp \
 //        ecckd_amd/csrc/opt_tables.cpp -o /tmp/check_opt_tables && /tmp/check_opt_tables
 #include <algorithm>
@@ -14,6 +15,7 @@
 #include <tuple>
 #include <vector>
 #include "lbfgs_history.hpp"
+#include "opt_lds.hpp"
 #include "opt_tables.hpp"
 namespace ot = ecckd::opt_tables;
 
@@ -264,7 +266,57 @@ static void check_history() {
   REQUIRE(accepted == 23 && lb.n == M);
 }
 
+// The LDS layouts of the three K8a kernels (csrc/opt_lds.hpp) against the byte formulas the host plan used before the kernels
+// and the plan shared one header, written out here as literals.  Every array has the size its kernel indexes it with, so the
+// arrays neither overlap nor leave a gap; the doubles start on 8 bytes and the int (or byte) arrays follow them.
+template <int N>
+static void check_layout(const ecckd::opt_lds::Layout<N>& l, const size_t (&size)[N], int ndouble_arrays, size_t total) {
+  REQUIRE(l.off[0] == 0 && l.bytes() == total);
+  size_t doubles_end = 0;
+  for (int i = 0; i < N; ++i) {
+    REQUIRE(l.off[i + 1] - l.off[i] == size[i] && l.off[i + 1] >= l.off[i]);
+    if (i < ndouble_arrays) { REQUIRE(l.off[i] % 8 == 0 && size[i] % 8 == 0); doubles_end = l.off[i + 1]; }
+    else REQUIRE(l.off[i] >= doubles_end && l.off[i] % 4 == 0);
+  }
+}
+
+static int check_lds() {
+  namespace lds = ecckd::opt_lds;
+  static char label[96];
+  int ncase = 0;
+  for (size_t nlay : {1, 17, 54, 128})
+    for (size_t ng : {1, 64, 70})
+      for (size_t nband : {1, 13}) {
+        const size_t nhl = nlay + 1, d = sizeof(double), flux = nhl * ng * d, band = nhl * nband * d;
+        for (int sw = 0; sw < 2; ++sw) {
+          std::snprintf(label, sizeof(label), "LDS nlay=%zu ng=%zu nband=%zu sw=%d", nlay, ng, nband, sw);
+          what = label;
+          const size_t cells_total = ((sw ? (size_t)0 : nlay * ng) + 2 * nhl * ng + 2 * nhl * nband + nlay * nband + nlay + 2 * nhl + 16) * sizeof(double) +
+                                     (nband + 1 + ng) * sizeof(int);
+          const size_t cells_size[lds::CL_COUNT] = {sw ? 0 : nlay * ng * d, flux, flux, band, band, nlay * nband * d, nlay * d, nhl * d, nhl * d,
+                                                    16 * d, (nband + 1) * 4, ng * 4};
+          check_layout(lds::cells((int)nlay, (int)ng, (int)nband, sw != 0), cells_size, lds::CL_BP, cells_total);
+          ++ncase;
+        }
+        std::snprintf(label, sizeof(label), "LDS nlay=%zu ng=%zu nband=%zu", nlay, ng, nband);
+        const size_t rayleigh_total = (4 * nhl * nband + nlay * nband + nlay + 2 * nhl + 16) * sizeof(double) + (nband + 1 + ng) * sizeof(int);
+        const size_t rayleigh_size[lds::RL_COUNT] = {band, band, band, band, nlay * nband * d, nlay * d, nhl * d, nhl * d, 16 * d, (nband + 1) * 4, ng * 4};
+        check_layout(lds::rayleigh((int)nlay, (int)ng, (int)nband), rayleigh_size, lds::RL_BP, rayleigh_total);
+        const size_t general_total = (nlay * ng + 2 * nhl * ng + 4 * nhl * nband + 16) * sizeof(double) + (nlay * ng + 15) / 16 * 16;
+        const size_t general_size[lds::GL_COUNT] = {nlay * ng * d, flux, flux, band, band, band, band, 16 * d, (nlay * ng + 15) / 16 * 16};
+        check_layout(lds::general((int)nlay, (int)ng, (int)nband), general_size, lds::GL_CLAMP, general_total);
+        ncase += 2;
+      }
+  // the figures in the comment of k_opt_forward_adjoint_cells, at the benchmark's shapes (13 bands): 100 KiB longwave - one block
+  // per CU -, 73 KiB shortwave - two
+  what = "LDS of the cell-parallel kernel at nlay = 54, ng = 64, nband = 13";
+  const size_t lw = lds::cells(54, 64, 13, false).bytes(), sw = lds::cells(54, 64, 13, true).bytes();
+  REQUIRE(lw == 102776 && lw / 1024 == 100 && sw == 75128 && sw / 1024 == 73 && 2 * sw <= 160 * 1024 && 2 * lw > 160 * 1024);
+  return ncase;
+}
+
 int main() {
+  const int nlds = check_lds();
   std::mt19937_64 rng(2024);
   int ncase = 0;
   for (int ng : {1, 64, 65})
@@ -277,6 +329,6 @@ int main() {
         }
   check_refusals();
   check_history();
-  std::printf("check_opt_tables: %d table cases, the refusals and the history: no complaint\n", ncase);
+  std::printf("check_opt_tables: %d LDS layouts, %d table cases, the refusals and the history: no complaint\n", nlds, ncase);
   return 0;
 }

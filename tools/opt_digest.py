@@ -5,8 +5,10 @@ build it was committed with; a ROCm math-library update may change digests legit
 Models and scenes of tests/ckd_synth.py with fixed seeds; the truth fluxes are fixed-seed arrays (no oracle).  Cases: longwave and
 shortwave (Rayleigh on), with boundary terms, with relative-to fluxes, with 70 g points; longwave with an active gas absent from a
 scene, with temperature_fl given, without min/max arrays, with the prior's sigma estimated from them, with cap_relative_linear
-biting, and with pressure_weight_power 1.0 and 0.7 beside the base's 0.5.  The two base cases also run under ECCKD_K8A_GENERIC=1,
-ECCKD_K8A_THREADS=128 and ECCKD_K8B_PLAIN_ORDER=1.  Each setting runs in a child process of its own
+biting, and with pressure_weight_power 1.0 and 0.7 beside the base's 0.5; the shortwave on a scattering handle
+(rayleigh_scattering=True: cost and gradient, both forward passes and the bounded minimiser): base, with boundary terms, with
+relative-to fluxes, with 70 g points.  The two base cases also run under ECCKD_K8A_GENERIC=1, ECCKD_K8A_THREADS=128 and
+ECCKD_K8B_PLAIN_ORDER=1, the scattering base case under ECCKD_K8A_THREADS=192.  Each setting runs in a child process of its own
 (ECCKD_K8B_PLAIN_ORDER is read when a handle is created, the two K8a knobs at every forward launch: a child per setting keeps
 the settings apart), one after another, each under its own time limit; a child that fails ends the run.  Prints one JSON object.
 usage: python tools/opt_digest.py"""
@@ -19,7 +21,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SETTINGS = [("default", {}, "all"), ("ECCKD_K8A_GENERIC=1", {"ECCKD_K8A_GENERIC": "1"}, "base"),
             ("ECCKD_K8A_THREADS=128", {"ECCKD_K8A_THREADS": "128"}, "base"),
-            ("ECCKD_K8B_PLAIN_ORDER=1", {"ECCKD_K8B_PLAIN_ORDER": "1"}, "base")]
+            ("ECCKD_K8B_PLAIN_ORDER=1", {"ECCKD_K8B_PLAIN_ORDER": "1"}, "base"),
+            ("ECCKD_K8A_THREADS=192", {"ECCKD_K8A_THREADS": "192"}, "scattering base")]
+SCATTERING = "sw scattering"            # cases whose name starts so run on a scattering handle
 CHILD_TIMEOUT_S = 240
 CFG = dict(flux_weight=0.2, flux_profile_weight=0.05, broadband_weight=0.4, spectral_boundary_weight=0.0,
            negative_od_penalty=1.0e4, pressure_weight_power=0.5, prior_error=4.0, pressure_corr=0.95,
@@ -89,6 +93,8 @@ def child(which):
         return model, scenes, cfg
 
     cases = {"lw": problem, "sw": lambda: problem(sw=True)}
+    if which == "scattering base":
+        cases = {SCATTERING: lambda: problem(sw=True)}
     if which == "all":
         cases.update({
             "lw boundary": lambda: problem(boundary=True, spectral_boundary_weight=0.3), "sw boundary": lambda: problem(sw=True, boundary=True),
@@ -98,15 +104,20 @@ def child(which):
             "lw estimated sigma": lambda: problem(prior_error=-1.0, min_prior_error=0.5, max_prior_error=3.0, prior_error_scaling=1.0),
             "lw cap_relative_linear": lw_cap,
             "lw pressure_weight_power=1.0": lambda: problem(pressure_weight_power=1.0),
-            "lw pressure_weight_power=0.7": lambda: problem(pressure_weight_power=0.7)})
+            "lw pressure_weight_power=0.7": lambda: problem(pressure_weight_power=0.7),
+            SCATTERING: lambda: problem(sw=True), SCATTERING + " boundary": lambda: problem(sw=True, boundary=True),
+            SCATTERING + " relative": lambda: problem(sw=True, relative=True),
+            SCATTERING + " ng=70": lambda: problem(sw=True, ng=70, nband=5)})
     out = {}
     with api.Context(0) as ctx:
         for name, make in cases.items():
             model, scenes, cfg = make()
             d = out[name] = {}
-            opt = api.Optimizer(ctx, model, scenes, **cfg)
+            scattering = name.startswith(SCATTERING)
+            opt = api.Optimizer(ctx, model, scenes, rayleigh_scattering=scattering, **cfg)
             x0, lo, hi = opt.initial_state(bounds=True)
-            d["initial state and bounds"] = digest(x0, lo, hi)
+            if not scattering:
+                d["initial state and bounds"] = digest(x0, lo, hi)
             rs = np.random.RandomState(8)
             x = x0 + np.where(x0 > -1.0e20, 0.2 * rs.normal(size=x0.size), 0.0)
             sizes = np.cumsum([0] + [g["molar_abs"].size for g in model["gases"] if g["active"]])
@@ -114,12 +125,15 @@ def child(which):
             d["forward"] = digest(*opt.forward(x))
             d["forward unclamped"] = digest(*opt.forward(x, unclamped=True))
             d["cost and gradient"] = digest(*opt.cost_grad(x))
-            d["coefficients"] = digest(*[opt.coefficients(x, i, g["molar_abs"].shape) for i, g in enumerate(model["gases"])])
-            for bounded in (True, False):
+            if not scattering:
+                d["coefficients"] = digest(*[opt.coefficients(x, i, g["molar_abs"].shape) for i, g in enumerate(model["gases"])])
+            for bounded in ((True,) if scattering else (True, False)):
                 r = opt.minimize(max_iterations=30, convergence_criterion=0.0, bounded=bounded)
                 d[f"minimize bounded={bounded}"] = digest(r["x"], r["status"], r["iterations"], r["cost"], r["gradient_norm"])
                 d[f"minimize bounded={bounded} (status, iterations)"] = [r["status"], r["iterations"]]
             opt.close()
+            if scattering:                                       # what follows makes no scattering handle
+                continue
             r = api.run_ckd(ctx, model, scenes[0])
             d["run_ckd"] = digest(*[r[k] for k in sorted(r)])
             s = scenes[0]
