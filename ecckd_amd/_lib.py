@@ -163,6 +163,9 @@ SIGNATURES = {
                                        _c_int64_p, C.c_int, C.POINTER(C.c_int), _c_double_p]),
     "ecckd_gas_median_sorting_variable": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _c_int64_p, _c_int64_p,
                                                     _c_double_p]),
+    "ecckd_median_sorting_variable_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, _c_int64_p,
+                                                    _c_int64_p, _c_double_p]),
+    "ecckd_index_geometry": (C.c_int, [C.POINTER(C.c_int)] * 6),
     "ecckd_run_ckd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
     "ecckd_scale_lut": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _c_double_p, _c_double_p, _c_double_p,
                                   C.POINTER(C.c_int), C.c_double, _c_double_p, _c_double_p, C.POINTER(_c_double_p)]),

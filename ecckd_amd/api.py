@@ -764,6 +764,30 @@ def invert_permutation(ctx, perm):
     return inv
 
 
+def median_sorting_variable(ctx, weight, sorting_variable_sorted, ind1, ind2):
+    """calc_median_sorting_variable (find_g_points.cpp:35-49) per interval with the caller's own weights (device tensors of
+    float64 in one order) -> numpy array; Gas.median_sorting_variable runs the same launches with the gas's weights."""
+    i1 = np.ascontiguousarray(ind1, dtype=np.int64)
+    i2 = np.ascontiguousarray(ind2, dtype=np.int64)
+    if weight.numel() != sorting_variable_sorted.numel():
+        raise EcckdError(_lib.PARAMETER_ERROR, "weight and sorting_variable_sorted differ in length")
+    out = np.zeros(i1.size)
+    ctx.fence_from_torch()
+    check(ctx.lib.ecckd_median_sorting_variable_dev(ctx.handle, weight.numel(), _dptr(weight), _dptr(sorting_variable_sorted),
+                                                    i1.size, i1.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                    i2.ctypes.data_as(C.POINTER(C.c_int64)), _hptr(out)))
+    return out
+
+
+def index_geometry():
+    """The tiling of the index kernels as this process runs them (ecckd_index_geometry; host only) -> dict."""
+    names = ("sort_keys_per_tile", "sort_keys_per_wave", "sort_scan_round_tiles", "sort_max_one_sort_bands", "median_tile",
+             "max_groups")
+    vals = [C.c_int() for _ in names]
+    check(_lib.load_library().ecckd_index_geometry(*[C.byref(v) for v in vals]))
+    return {k: int(v.value) for k, v in zip(names, vals)}
+
+
 class GasSW(GasLW):
     """A prepared shortwave gas (ecckd_gas_create_sw); same batched-error interface as GasLW."""
 

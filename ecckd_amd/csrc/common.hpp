@@ -90,6 +90,8 @@ void streamer_delete(ecckd_ctx* ctx);               // nc_stream.hip
 // the launcher started on this node (LOCAL_WORLD_SIZE: one process per GPU); ECCKD_HOST_CORES overrides.  At least 1.
 int host_cores();
 bool host_oversubscribed();     // find_g_band.hip: more spinning search / batcher threads than cores (they then yield while waiting)
+// radix_sort.hip: the tiling of K3 as this process runs it (ECCKD_SORT_ITEMS honoured), for ecckd_index_geometry
+void sort_geometry(int* keys_per_tile, int* keys_per_wave, int* scan_round_tiles, int* max_one_sort_bands);
 
 // Results the host needs at once (the errors of a batch of intervals, the cost of a trial point, the dot products of the
 // L-BFGS update) arrive in pinned, host-coherent memory, written by the last kernel of the train that produces them.  Waiting

@@ -77,7 +77,8 @@ k_invert_perm(size_t n, const int32_t* __restrict__ perm, int32_t* __restrict__ 
 // tile sums, then a walk through the one segment that holds the crossing), point inside that tile, tail.  The reference
 // adds the weights one by one; here sums are formed by tile and by scan, so where the running sum comes within rounding
 // of half the total the crossing can fall on the neighbouring point (whose sorting variable differs from its
-// neighbour's by the local spacing of the sorted keys).
+// neighbour's by the local spacing of the sorted keys).  With weights whose sums are exact in any order the point is the
+// reference's, an interval without weight included (half == 0: the reference stops at i1, wherever i1 lies in its tile).
 constexpr int MED_TILE = 256;
 
 __global__ void __launch_bounds__(256)
@@ -162,7 +163,10 @@ k_median_sorting(const long long* __restrict__ ind1, const long long* __restrict
     block_scan_256(seg_sum, s_scan);                               // which thread's run of tiles
     const double before = carry + (tid ? s_scan[tid - 1] : 0.0), inc = carry + s_scan[tid];
     const double all_tiles = s_scan[255];
-    if (ta < tb && inc >= half && before < half) {
+    // (an interval without weight whose head is empty: i1 is the first point of the first whole tile, and as in the head the
+    // reference stops there with nothing before it)
+    const bool at_i1 = ta == t1 && t1 * MED_TILE == i1;
+    if (ta < tb && inc >= half && (before < half || at_i1)) {
       double cum = before;                                         // which tile of the run: walk it
       for (long long t = ta; t < tb; ++t) {
         const double next = cum + ts[t];
@@ -176,7 +180,7 @@ k_median_sorting(const long long* __restrict__ ind1, const long long* __restrict
       const bool in = i <= last;
       block_scan_256(in ? weight[i] : 0.0, s_scan);
       const double b0 = s_before + (tid ? s_scan[tid - 1] : 0.0), inc2 = s_before + s_scan[tid];
-      if (in && inc2 >= half && b0 < half) atomicMin(&s_found, i);
+      if (in && inc2 >= half && (b0 < half || i == i1)) atomicMin(&s_found, i);
       __syncthreads();
       // (the tile's own sum said "reached", the scan of its points rounds differently: the tile's last point then)
       if (tid == 0 && s_found == NONE) s_found = (s_tile + 1) * MED_TILE - 1 <= last ? (s_tile + 1) * MED_TILE - 1 : NONE;
@@ -309,34 +313,50 @@ int ecckd_subband_setup_dev(ecckd_ctx* ctx, size_t nwav, const double* d_wavenum
   return ECCKD_OK;
 }
 
+int ecckd_median_sorting_variable_dev(ecckd_ctx* ctx, size_t n, const double* d_weight, const double* d_sorting_variable_sorted,
+                                      int nint, const int64_t* h_ind1, const int64_t* h_ind2, double* h_median) {
+  ECCKD_REQUIRE(ctx && d_weight && d_sorting_variable_sorted && (nint == 0 || (h_ind1 && h_ind2 && h_median)),
+                "ecckd_median_sorting_variable_dev: NULL argument");
+  if (nint <= 0) return ECCKD_OK;
+  ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
+  for (int k = 0; k < nint; ++k)
+    ECCKD_REQUIRE(h_ind1[k] >= 0 && h_ind1[k] <= h_ind2[k] && (size_t)h_ind2[k] < n,
+                  "ecckd_median_sorting_variable_dev: interval %d [%lld,%lld] outside the spectrum", k,
+                  (long long)h_ind1[k], (long long)h_ind2[k]);
+  const size_t ntiles = (n + MED_TILE - 1) / MED_TILE;
+  const size_t ts_bytes = ecckd_align_up(ntiles * sizeof(double), 256), idx_bytes = ecckd_align_up((size_t)nint * 2 * sizeof(long long), 256);
+  ECCKD_CHECK(ecckd::ensure_scratch(ctx, ts_bytes + idx_bytes + (size_t)nint * sizeof(double)));
+  double* d_ts = (double*)ctx->scratch;
+  long long* d_i1 = (long long*)((char*)ctx->scratch + ts_bytes);
+  long long* d_i2 = d_i1 + nint;
+  double* d_out = (double*)((char*)ctx->scratch + ts_bytes + idx_bytes);
+  std::vector<long long> tmp(2 * (size_t)nint);
+  for (int k = 0; k < nint; ++k) { tmp[k] = h_ind1[k]; tmp[nint + k] = h_ind2[k]; }
+  ECCKD_HIP_CHECK(hipMemcpyAsync(d_i1, tmp.data(), tmp.size() * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(k_median_tile_sums, dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, n, d_weight, d_ts);
+  hipLaunchKernelGGL(k_median_sorting, dim3(nint), dim3(256), 0, ctx->stream, d_i1, d_i2, d_weight, d_ts, d_sorting_variable_sorted, d_out);
+  ECCKD_HIP_CHECK(hipGetLastError());
+  ECCKD_HIP_CHECK(hipMemcpyAsync(h_median, d_out, (size_t)nint * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return ECCKD_OK;
+}
+
 int ecckd_gas_median_sorting_variable(ecckd_gas* g, const double* d_sorting_variable_sorted, int n, const int64_t* h_ind1,
                                       const int64_t* h_ind2, double* h_median) {
   ECCKD_REQUIRE(g && d_sorting_variable_sorted && (n == 0 || (h_ind1 && h_ind2 && h_median)),
                 "ecckd_gas_median_sorting_variable: NULL argument");
-  if (n <= 0) return ECCKD_OK;
-  ecckd_ctx* ctx = g->ctx;
-  ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
-  for (int k = 0; k < n; ++k)
-    ECCKD_REQUIRE(h_ind1[k] >= 0 && h_ind1[k] <= h_ind2[k] && (size_t)h_ind2[k] < g->n,
-                  "ecckd_gas_median_sorting_variable: interval %d [%lld,%lld] outside the spectrum", k,
-                  (long long)h_ind1[k], (long long)h_ind2[k]);
   // weight: surface Planck function (LW, :1405) or reordered solar irradiance (SW, :1408)
   const double* weight = g->do_sw ? g->ssi : g->planck_hl + (size_t)g->nlay * g->n;
-  const size_t ntiles = (g->n + MED_TILE - 1) / MED_TILE;
-  const size_t ts_bytes = ecckd_align_up(ntiles * sizeof(double), 256), idx_bytes = ecckd_align_up((size_t)n * 2 * sizeof(long long), 256);
-  ECCKD_CHECK(ecckd::ensure_scratch(ctx, ts_bytes + idx_bytes + (size_t)n * sizeof(double)));
-  double* d_ts = (double*)ctx->scratch;
-  long long* d_i1 = (long long*)((char*)ctx->scratch + ts_bytes);
-  long long* d_i2 = d_i1 + n;
-  double* d_out = (double*)((char*)ctx->scratch + ts_bytes + idx_bytes);
-  std::vector<long long> tmp(2 * (size_t)n);
-  for (int k = 0; k < n; ++k) { tmp[k] = h_ind1[k]; tmp[n + k] = h_ind2[k]; }
-  ECCKD_HIP_CHECK(hipMemcpyAsync(d_i1, tmp.data(), tmp.size() * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_median_tile_sums, dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, g->n, weight, d_ts);
-  hipLaunchKernelGGL(k_median_sorting, dim3(n), dim3(256), 0, ctx->stream, d_i1, d_i2, weight, d_ts, d_sorting_variable_sorted, d_out);
-  ECCKD_HIP_CHECK(hipGetLastError());
-  ECCKD_HIP_CHECK(hipMemcpyAsync(h_median, d_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return ecckd_median_sorting_variable_dev(g->ctx, g->n, weight, d_sorting_variable_sorted, n, h_ind1, h_ind2, h_median);
+}
+
+int ecckd_index_geometry(int* sort_keys_per_tile, int* sort_keys_per_wave, int* sort_scan_round_tiles,
+                         int* sort_max_one_sort_bands, int* median_tile, int* max_groups) {
+  ECCKD_REQUIRE(sort_keys_per_tile && sort_keys_per_wave && sort_scan_round_tiles && sort_max_one_sort_bands && median_tile &&
+                max_groups, "ecckd_index_geometry: NULL argument");
+  ecckd::sort_geometry(sort_keys_per_tile, sort_keys_per_wave, sort_scan_round_tiles, sort_max_one_sort_bands);
+  *median_tile = MED_TILE;
+  *max_groups = MAX_GROUPS;
   return ECCKD_OK;
 }
 

@@ -133,19 +133,22 @@ k_sort_hist(size_t n, int shift, const unsigned long long* __restrict__ skey, co
   tile_hist[(size_t)tid * ntiles + blockIdx.x] = total;
 }
 
+constexpr int SCAN_PER = 8;                  // tile counts per thread and round of k_sort_scan_rows
+constexpr int SCAN_ROUND = 256 * SCAN_PER;   // tile counts per round
+
 // (2) one block per digit: exclusive scan of that digit's row of per-tile counts (in place) and the row total ->
 // digit_total[digit].  Every thread takes eight consecutive counts (the loads of a round are in flight together), the block
 // scans the threads' sums once per round of 2 048 counts.  The scan over the 256 digit totals is done by every scatter block
-// in LDS.
+// in LDS.  (SCAN_PER, SCAN_ROUND)
 __global__ void __launch_bounds__(256)
 k_sort_scan_rows(unsigned* __restrict__ tile_hist, unsigned ntiles, unsigned* __restrict__ digit_total) {
   __shared__ unsigned s_wave[4];
-  constexpr int PER = 8;
+  constexpr int PER = SCAN_PER;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   unsigned* row = tile_hist + (size_t)blockIdx.x * ntiles;
   unsigned carry = 0;
-  for (unsigned base = 0; base < ntiles; base += 256 * PER) {
+  for (unsigned base = 0; base < ntiles; base += SCAN_ROUND) {
     const unsigned first = base + (unsigned)tid * PER;
     unsigned v[PER];
 #pragma unroll
@@ -488,6 +491,15 @@ void sort_prepare_hist(hipStream_t stream, size_t off, size_t n, const double* k
 }
 
 }  // namespace
+
+namespace ecckd {
+void sort_geometry(int* keys_per_tile, int* keys_per_wave, int* scan_round_tiles, int* max_one_sort_bands) {
+  *keys_per_tile = SORT_THREADS * sort_items();
+  *keys_per_wave = 64 * sort_items();
+  *scan_round_tiles = SCAN_ROUND;
+  *max_one_sort_bands = (MAX_SEG - 1) / 2;
+}
+}  // namespace ecckd
 
 extern "C" int ecckd_stable_argsort_bands_dev(ecckd_ctx* ctx, size_t nwav, const double* d_key,
                                               int nband, const int64_t* h_band_begin,

@@ -438,6 +438,20 @@ int ecckd_find_g_gases_target_observe(ecckd_target_trial_fn fn, void* user);
  * cumulative weight is within ~1e-13 (relative) of one half. */
 int ecckd_gas_median_sorting_variable(ecckd_gas* gas, const double* d_sorting_variable_sorted, int n,
                                       const int64_t* h_ind1, const int64_t* h_ind2, double* h_median);
+/* The same two launches with the caller's own weights: d_weight[n] and d_sorting_variable_sorted[n] in one order,
+ * nint intervals [h_ind1[k], h_ind2[k]] inside 0..n-1.  ecckd_gas_median_sorting_variable calls through it with the gas's
+ * surface Planck row or reordered irradiance.  With weights whose partial sums are exact in any order (small integers)
+ * the point chosen is the reference's at every placement, `cumulative == half` included. */
+int ecckd_median_sorting_variable_dev(ecckd_ctx* ctx, size_t n, const double* d_weight,
+                                      const double* d_sorting_variable_sorted, int nint,
+                                      const int64_t* h_ind1, const int64_t* h_ind2, double* h_median);
+
+/* Host only: the tiling of the index kernels as this process runs them.  K3 (ecckd_stable_argsort_bands_dev): keys per
+ * tile (ECCKD_SORT_ITEMS honoured) and per wave, tile counts per round of the row scan, the largest number of bands that
+ * one nine-pass sort takes; the tile of the median's weight sums; the largest number of groups of
+ * ecckd_regroup_rank_by_wavenumber_dev. */
+int ecckd_index_geometry(int* sort_keys_per_tile, int* sort_keys_per_wave, int* sort_scan_round_tiles,
+                         int* sort_max_one_sort_bands, int* median_tile, int* max_groups);
 
 /* d_dst[i] = d_src[d_index[i]], i < n (the reordering gathers of find_g_points.cpp:781,:865). */
 int ecckd_gather_f64_dev(ecckd_ctx* ctx, size_t n, const double* d_src, const int32_t* d_index,
