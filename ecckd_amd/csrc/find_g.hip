@@ -56,32 +56,8 @@ constexpr int PREP_THREADS = 256;  // K4 block
 __device__ constexpr double kD = ECCKD_LW_DIFFUSIVITY;
 
 // ---------------------------------------------------------------------------
-// deterministic reductions (wave_sum: rt_device.hpp)
-using ecckd::wave_sum;
-
-// sum over a 256-thread block; result valid in thread 0.  s4 = 4 doubles of LDS.
-__device__ __forceinline__ double block_sum_256(double v, double* s4) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) s4[wave] = v;
-  __syncthreads();
-  return ((s4[0] + s4[1]) + s4[2]) + s4[3];
-}
-
-// two (or three) block sums behind ONE pair of barriers; every sum is formed exactly as block_sum_256 forms it
-__device__ __forceinline__ void block_sum_256_x3(double& a, double& b, double& c, double (*s4)[4]) {
-  a = wave_sum(a);
-  b = wave_sum(b);
-  c = wave_sum(c);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) { s4[0][wave] = a; s4[1][wave] = b; s4[2][wave] = c; }
-  __syncthreads();
-  a = ((s4[0][0] + s4[0][1]) + s4[0][2]) + s4[0][3];
-  b = ((s4[1][0] + s4[1][1]) + s4[1][2]) + s4[1][3];
-  c = ((s4[2][0] + s4[2][1]) + s4[2][2]) + s4[2][3];
-}
+// deterministic reductions (rt_device.hpp)
+using ecckd::wave_sum; using ecckd::block_sum_256; using ecckd::block_sum_256_x3;
 
 }  // namespace
 

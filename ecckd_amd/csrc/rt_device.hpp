@@ -1,6 +1,7 @@
 // rt_device.hpp - the device and host primitives that every kernel file takes from ONE place: the physical constants, the wave
-// reductions, the Planck function and the longwave layer step.  The line-by-line kernels reach them through lbl_rt.hpp, the
-// tuned kernels of find_g.hip, reorder.hip, create_lut.hip and optimize.hip include this file.  DESIGN.md and the tests compare
+// and block reductions, the Planck function and the longwave layer step.  The line-by-line kernels reach them through lbl_rt.hpp,
+// the tuned kernels of find_g.hip, reorder.hip, create_lut.hip and optimize.hip include this file (the block sums are those of
+// find_g.hip's interval kernels and of create_lut.hip's partial kernels).  DESIGN.md and the tests compare
 // kernels of different files with each other bit for bit (k_planck_sorted rebuilds the matrix k_gas_prep_lw writes): one
 // source text keeps an edit from reaching only one of them.  The files are compiled with the default contraction, so an
 // expression here keeps its form and operand order; a reordered one can fuse differently and change bits - in every caller.
@@ -45,6 +46,30 @@ __device__ __forceinline__ void wave_add(double* acc, int lane, double v) {
 // the four waves' accumulators s[w * n + t], added in a fixed order
 __device__ __forceinline__ double add_waves(const double* s, int n, int t) {
   return ((s[t] + s[n + t]) + s[2 * n + t]) + s[3 * n + t];
+}
+
+// sum over a 256-thread block; result valid in thread 0.  s4 = 4 doubles of LDS.
+__device__ __forceinline__ double block_sum_256(double v, double* s4) {
+  v = wave_sum(v);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) s4[wave] = v;
+  __syncthreads();
+  return ((s4[0] + s4[1]) + s4[2]) + s4[3];
+}
+
+// two (or three) block sums behind ONE pair of barriers; every sum is formed exactly as block_sum_256 forms it
+__device__ __forceinline__ void block_sum_256_x3(double& a, double& b, double& c, double (*s4)[4]) {
+  a = wave_sum(a);
+  b = wave_sum(b);
+  c = wave_sum(c);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) { s4[0][wave] = a; s4[1][wave] = b; s4[2][wave] = c; }
+  __syncthreads();
+  a = ((s4[0][0] + s4[0][1]) + s4[0][2]) + s4[0][3];
+  b = ((s4[1][0] + s4[1][1]) + s4[1][2]) + s4[1][3];
+  c = ((s4[2][0] + s4[2][1]) + s4[2][2]) + s4[2][3];
 }
 
 // Several per-lane values reduced over the wave TOGETHER: at lane distance 32 a lane hands over one half of its values and

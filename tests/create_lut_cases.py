@@ -3,14 +3,17 @@ averages under every averaging method, the Planck look-up table, the g-point fra
 (test_create_lut_cases.py on the CPU, test_create_lut_edges_gpu.py on the device).  numpy only.
 
 Every kernel of that file reduces a g point - a contiguous segment of the g-sorted order - in three levels: a block of
-GA_THREADS threads takes a chunk of GA_CHUNK sorted positions, GA_PPT per thread; its four waves meet in LDS; a "final" kernel
-adds the chunk partials of a g point, lane j taking the chunks j, j + 64, ...  What a segment goes through is decided by its
+GA_THREADS threads takes a chunk of GA_CHUNK sorted positions, GA_PPT per thread (chunk_positions); its four waves meet in
+LDS (block_sum_256 of rt_device.hpp; in k_gavg_partial after the last layer); a second kernel - k_gavg_final for the averages,
+k_combine_chunks for everything else - adds the chunk partials of a g point, lane j taking the chunks j, j + 64, ...
+(combine_chunks).  What a segment goes through is decided by its
 number of points alone, so a LAYOUT is the list of the g points' counts.  layout_g() hands out natural positions run by run
 (runs of varying length, g points and points without one interleaved by a seeded permutation): the wavenumbers ascend in
 natural order, so they ascend inside every g point, as ecckd_gmap_create demands.
 
 The numbers of the kernels that the layouts are written for are repeated here (test_create_lut_cases.py reads them out of
-the source and fails when they differ).
+the source - create_lut.hip and gmap_layout.hpp, which holds the chunk constants, the chunking and the sizes of the work
+buffer - and fails when they differ; tools/check_gmap_layout.cpp holds gmap_layout.hpp to CHUNKS and to work_bytes()).
 
 The reference restates the formulas of average_optical_depth_to_g_point, planck_function, the g-point fraction and the
 erythemal weight - not the oracle's code -: every term is computed in np.longdouble (64-bit mantissa; np.expm1 / np.log1p
@@ -26,7 +29,7 @@ import numpy as np
 GA_THREADS = 256
 GA_PPT = 8
 GA_CHUNK = GA_THREADS * GA_PPT      # 2048 sorted positions per block
-FINAL_LANES = 64                    # k_gavg_final, k_planck_lut_final, k_width_totals: lane j adds the chunks j, j + 64, ...
+FINAL_LANES = 64                    # combine_chunks (k_gavg_final, k_combine_chunks): lane j adds the chunks j, j + 64, ...
 
 METHODS = ["linear", "transmission", "transmission-2", "transmission-3", "transmission-10", "square-root",
            "logarithmic", "hybrid-logarithmic-transmission-3"]
@@ -394,7 +397,8 @@ def _up(n):
 
 
 def work_bytes(call, nchunk, ng, n):
-    """bytes of the map's work buffer that a call asks gmap_work() for (the host code of create_lut.hip)"""
+    """bytes of the map's work buffer that a call asks gmap_work() for (carve_work of create_lut.hip over the pieces that
+    gmap_layout.hpp lists per call)"""
     nchunk = max(nchunk, 1)
     if call == "average":
         return _up(nchunk * n * 6 * 8) + _up(3 * n * ng * 8) + _up(n * (2 * 8 + 4))

@@ -16,8 +16,10 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 
 
 def test_the_constants_are_those_of_the_source():
-    with open(os.path.join(CSRC, "create_lut.hip")) as f:
-        src = f.read()
+    src = ""
+    for name in ("create_lut.hip", "gmap_layout.hpp"):          # the kernels; the chunk constants and the chunking
+        with open(os.path.join(CSRC, name)) as f:
+            src += f.read()
 
     def const(name):
         m = re.search(r"constexpr\s+int\s+%s\s*=\s*([^;]+);" % name, src)
@@ -27,9 +29,9 @@ def test_the_constants_are_those_of_the_source():
     assert const("GA_THREADS") == "256" and K.GA_THREADS == 256
     assert const("GA_PPT") == "8" and K.GA_PPT == 8
     assert const("GA_CHUNK") == "GA_THREADS * GA_PPT" and K.GA_CHUNK == 2048
-    # the three lane-strided loops of the final kernels, and nowhere another stride
-    strides = re.findall(r"for \(int c = [^;]+; c < [^;]+; c \+= (\d+)\)", src)
-    assert strides == [str(K.FINAL_LANES)] * 3, strides
+    # the one lane-strided loop that combines chunk partials (combine_chunks), and nowhere another stride
+    strides = re.findall(r"for \(int c = [^;]+; c < [^;]+; c \+= (\w+)\)", src)
+    assert strides == [str(K.FINAL_LANES)], strides
     assert "for (int t = tid; t < nlay * 6; t += GA_THREADS)" in src
     assert "for (; i + 192 < hi; i += 256)" in src and "for (; i < hi; i += 64)" in src
     import test_create_lut_gpu

@@ -4,14 +4,16 @@ extended-precision reference of create_lut_cases.py (validated on the CPU by tes
 What each case pins (kernels and statements of create_lut.hip):
 
   STRIDE (64, 64, 65 and 66 chunks: 131 071, 131 072, 131 073 and 133 121 points; 3 layers)
-      the second trip of `for (c = c0 + lane; c < c1; c += 64)` in k_gavg_final (test_average), k_planck_lut_final
-      (test_planck_lut, test_erythemal, test_sum_rows_over_more_than_64_chunks) and k_width_totals (test_fractions_exact)
+      the second trip of `for (c = c0 + lane; c < c1; c += 64)` of combine_chunks: in k_gavg_final (test_average), and in
+      k_combine_chunks with [nrows][ng] output (test_planck_lut, test_erythemal, test_sum_rows_over_more_than_64_chunks) and
+      with the last column of width[ng][nint + 1] as output (test_fractions_exact)
   EDGE with 43 and 54 layers against 42
       the second trip of `for (t = tid; t < nlay * 6; t += GA_THREADS)` at the end of k_gavg_partial (test_average)
   EDGE (g points of 0, 1, 2047, 2048, 2049, 4096, 4097 and 0 points)
-      `ii = live ? i : c.p1` and the `live[p]` skip of k_gavg_partial, k_planck_lut_partial, k_erythemal_partial and
-      k_width_chunk_sums at a chunk of one point, one short of full, full, and full plus a chunk of one (test_average,
-      test_planck_lut, test_erythemal, test_fractions_exact); `c1 > c0` of k_gavg_final at the empty g points
+      `ii[p] = live[p] ? i : c.p1` of chunk_positions and the `live[p]` skip of k_gavg_partial, k_planck_lut_partial,
+      k_erythemal_partial and k_width_chunk_sums at a chunk of one point, one short of full, full, and full plus a chunk of
+      one (test_average, test_planck_lut, test_erythemal, test_fractions_exact); `c1 > c0` of k_gavg_final at the empty g
+      points
   width intervals of 0, 1, 63, 64, 65, 255, 256, 257, 511, 512, 513 and 1100 points with bounds ON wavenumbers
       `for (; i + 192 < hi; i += 256)` of k_gpoint_width, its hand-over to `for (; i < hi; i += 64)`, and both ends of
       (w1, w2] in its two binary searches (test_fractions_exact)
@@ -21,9 +23,10 @@ What each case pins (kernels and statements of create_lut.hip):
   test_results_do_not_depend_on_other_g_points
       a read across c.p1 or before c.p0 in any partial kernel, a chunk partial of another g point in a final kernel
   test_regrowth_and_reproducibility
-      gmap_work(): free and regrow under a sequence of calls of growing need
+      gmap_work(): release and regrow under a sequence of calls of growing need
   NONE_ONLY
-      `nchunk > 0` of every entry point: no partial kernel is launched, the final kernels read nothing
+      `nchunk > 0` of ecckd_average_to_gpoints and `!m->chunks.empty()` of reduce_rows: no partial kernel is launched, the
+      combining kernels read nothing
 
 Bounds.  min and max are copies of inputs: equal to the reference where reference_surface_vmr <= 0.  The fit is within
 64 eps max(1, condition) of the reference (condition: of the fit with respect to a relative error of its sums): all terms of
@@ -227,7 +230,7 @@ def test_erythemal(ctx, name):
 
 
 def test_sum_rows_over_more_than_64_chunks(ctx):
-    """ecckd_gmap_sum_rows shares k_planck_lut_final: integer rows below 2^24 over STRIDE, against integer sums"""
+    """ecckd_gmap_sum_rows goes through k_combine_chunks like the Planck table: integer rows below 2^24 over STRIDE, against integer sums"""
     g, ng = K.layout_g("STRIDE"), K.layout_ng("STRIDE")
     rows = np.random.default_rng(9).integers(0, 2 ** 24, size=(3, g.size))
     have = g >= 0
@@ -243,7 +246,7 @@ def test_sum_rows_over_more_than_64_chunks(ctx):
 def test_fractions_exact(ctx, name, ig):
     """Integer widths: every width and every total is an exact sum in any order, the fraction is the correctly rounded quotient
     - bit for bit; an empty g point has 0 / 0.  The last interval holds everything: its fraction is exactly 1, so the sum that
-    k_gpoint_width forms of a whole segment is the sum that k_width_chunk_sums and k_width_totals form of it."""
+    k_gpoint_width forms of a whole segment is the sum that k_width_chunk_sums and k_combine_chunks form of it."""
     g, ng = K.layout_g(name), K.layout_ng(name)
     wn, dwn = K.grid(g.size)
     w1, w2, _ = K.width_intervals(g, wn, ig)

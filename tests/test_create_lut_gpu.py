@@ -91,6 +91,25 @@ def test_empty_g_point_and_errors(ctx, oracle):
     assert e.value.code == 147
 
 
+def test_descending_wavenumbers_inside_a_g_point_are_refused(ctx):
+    """300 points in 3 g points, two neighbouring wavenumbers of one g point swapped: code 147; the next map of the same size on
+    the same context is built as usual."""
+    from ecckd_amd import api, EcckdError
+    nwav, ng = 300, 3
+    g_point = (np.arange(nwav) // 100).astype(np.int32)
+    wn = 600.0 + np.arange(nwav) / 64.0
+    dwn = np.ones(nwav)
+    bad = wn.copy()
+    bad[[150, 151]] = bad[[151, 150]]
+    assert g_point[150] == g_point[151] == 1
+    with pytest.raises(EcckdError) as e:
+        api.GPointMap(ctx, _dev(ctx, g_point), ng, _dev(ctx, bad), _dev(ctx, dwn))
+    assert e.value.code == 147
+    gm = api.GPointMap(ctx, _dev(ctx, g_point), ng, _dev(ctx, wn), _dev(ctx, dwn))
+    assert gm.counts().tolist() == [100, 100, 100]
+    gm.close()
+
+
 def test_gpoint_fraction_and_planck_lut(ctx, oracle):
     from ecckd_amd import api
     ng = 9

@@ -120,10 +120,11 @@ def test_small_maps_keep_the_chains():
 
 
 def test_the_constants_are_those_of_the_sources():
-    """256 / 8 / 32 / 2048 and the accumulator budgets, read out of gpoint_bin.hpp and create_lut.hip"""
+    """256 / 8 / 32 / 2048 and the accumulator budgets, read out of gpoint_bin.hpp and gmap_layout.hpp (the chunks of
+    create_lut.hip)"""
     with open(os.path.join(CSRC, "gpoint_bin.hpp")) as f:
         hpp = f.read()
-    with open(os.path.join(CSRC, "create_lut.hip")) as f:
+    with open(os.path.join(CSRC, "gmap_layout.hpp")) as f:
         lut = f.read()
 
     def const(text, name):
