@@ -44,7 +44,8 @@ inline uint32_t reverse_bits(uint32_t code, int len) {
 
 // canonical Huffman code of `lens[0..n)` into a two-level table with `primary` index bits; `make` turns a symbol into an
 // entry without its length.  False for an over-subscribed code and, as in zlib's inflate_table, for an incomplete one unless it
-// consists of a single one-bit code (a lone distance code); the unused half of that one leaves T_INVALID entries.
+// consists of a single one-bit code (a lone distance code) or of no code at all (the distance code of a block without matches,
+// RFC 1951 3.2.7): the unused half of the one, and all of the other, are T_INVALID entries, so any use of them is refused.
 template <typename Make>
 bool build(uint32_t* table, int primary, int sub_bits, const uint8_t* lens, int n, Make make) {
   int count[16] = {};
@@ -61,7 +62,7 @@ bool build(uint32_t* table, int primary, int sub_bits, const uint8_t* lens, int 
     code = (code + (uint32_t)count[l - 1]) << 1;
     next[l] = code;
   }
-  if (left > 0 && longest != 1) return false;
+  if (left > 0 && longest > 1) return false;
   const uint32_t psize = 1u << primary;
   for (uint32_t i = 0; i < psize; ++i) table[i] = entry(T_INVALID, 0, 0, 0);
   uint32_t used = psize;                        // subtables are handed out behind the primary table

@@ -1,7 +1,9 @@
 """The host-side zlib-stream decoder of the NetCDF-4 read path (csrc/fast_inflate.cpp, reached here through
 ecckd_inflate_host) against Python's zlib: every block type, every compression level and strategy, long codes, runs, random
 bytes, the shuffled-FLOAT data it is meant for - and streams that are damaged, cut short or of another length, which it must
-refuse (the caller then asks zlib) without reading or writing outside its buffers."""
+refuse (the caller then asks zlib) without reading or writing outside its buffers.  All but one of these streams come out of
+zlib's compressor, which never codes a match farther back than 32768 - 262 = 32506 bytes; distances up to 32768 and the
+streams that are laid against the decoder's own switches are in test_fast_inflate_edges.py (hand-built: deflate_cases.py)."""
 import ctypes as C
 import zlib
 
@@ -116,7 +118,8 @@ def test_damaged_streams_never_decode_to_something_else(lib):
 
 def test_long_codes_and_far_matches(lib):
     """An alphabet whose frequencies fall off geometrically gives 15-bit codes (second-level tables); matches at the far end of
-    the window and of the maximum length."""
+    the window (as far as zlib's compressor looks: 32506 bytes; the repeat at 32768 below reaches the decoder as literals) and
+    of the maximum length."""
     rs = np.random.RandomState(5)
     p = 0.5 ** np.arange(1, 41); p /= p.sum()
     skew = rs.choice(40, 400_000, p=p).astype(np.uint8).tobytes()

@@ -1,7 +1,9 @@
 """zlib / DEFLATE streams inflated on the device (csrc/inflate.hip, the NetCDF-4 read path of ecckd_nc_read_dev) against
 Python's zlib (the library HDF5's deflate filter uses): bit-exact for stored, fixed-Huffman and dynamic-Huffman blocks,
-matches at every distance up to the 32 KB window, run-length matches (distance < length), long codes, many streams of
-different sizes in one launch, and damaged streams reported per stream."""
+the matches zlib's compressor emits (distances up to 32768 - 262 = 32506: it looks no farther back, so the repeat of "far
+matches" at distance 32751 reaches the decoder as literals), run-length matches (distance < length), long codes, many
+streams of different sizes in one launch, and damaged streams reported per stream.  Distances 32507 .. 32768, the window
+wrap and what no compressor emits: test_inflate_edges_gpu.py, from the hand-built streams of deflate_cases.py."""
 import zlib
 
 import numpy as np
