@@ -21,6 +21,7 @@
 // optical depth (nlay) rows = (2*nlay+1)*8 B per point, coalesced 512-B wave
 // loads, with per-half-level flux sums reduced wave -> block -> interval in a
 // fixed order (bitwise reproducible; no float atomics).
+#include "chunk_layout.hpp"
 #include "common.hpp"
 #include "partition_search.hpp"
 #include "rt_device.hpp"
@@ -28,6 +29,7 @@
 #include <atomic>
 #include <cmath>
 #include <chrono>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -544,10 +546,11 @@ k_tile_sums(int nrows, size_t n, size_t ntiles, const double* const* __restrict_
 // sums[k][r] = sum_{i=i1_k..i2_k} rows[r][i] = ragged head + whole tiles + ragged tail
 struct Interval {
   long long i1, i2;      // inclusive global sorted indices
-  long long chunk0;      // first RT chunk of this interval
-  long long chunk_pts;   // points per RT chunk of THIS interval: a function of its length alone (interval_chunk_pts), so that the
-                         // order in which its points are summed - and with it every bit of its error - does not depend on what else
-                         // is evaluated in the same batch
+  int chunk0;            // first RT chunk of this interval (a batch has fewer than 2^31 chunks)
+  int head;              // i1 mod 16 where the chunks are counted from the 128-byte line below i1 (chunk_layout.hpp), else 0
+  long long chunk_pts;   // points per RT chunk of THIS interval: a function of the interval alone (chunk_layout::of_interval), so
+                         // that the order in which its points are summed - and with it every bit of its error - does not depend
+                         // on what else is evaluated in the same batch
   long long npoints;     // band length (for the logarithmic fit)
   double albedo;         // shortwave: surface albedo of the interval's band
 };
@@ -568,9 +571,10 @@ __device__ __forceinline__ Interval interval_of(int use_ka, const Interval* __re
   if (!use_ka) return iv[k];
   typedef const __attribute__((address_space(4))) long long* karg_ptr;
   karg_ptr q = (karg_ptr)__builtin_amdgcn_kernarg_segment_ptr() + (size_t)k * (sizeof(Interval) / sizeof(long long));
-  static_assert(sizeof(Interval) == 6 * sizeof(long long), "Interval is six 8-byte fields");
+  static_assert(sizeof(Interval) == 6 * sizeof(long long) && offsetof(Interval, chunk0) == 16 && offsetof(Interval, head) == 20,
+                "Interval is six 8-byte slots; chunk0 and head share the third");
   Interval me;
-  me.i1 = q[0]; me.i2 = q[1]; me.chunk0 = q[2]; me.chunk_pts = q[3]; me.npoints = q[4];
+  me.i1 = q[0]; me.i2 = q[1]; me.chunk0 = (int)q[2]; me.head = (int)(q[2] >> 32); me.chunk_pts = q[3]; me.npoints = q[4];
   me.albedo = __longlong_as_double(q[5]);
   return me;
 }
@@ -959,11 +963,11 @@ k_rt_lw_bb_mirror(size_t n, int nint, long long nchunks, const Interval* __restr
   }
   const int k = lo;
   klo = k;
-  const long long chunk_pts = iv[k].chunk_pts;
-  const long long c = chunk - iv[k].chunk0;
-  const long long p0 = iv[k].i1 + c * chunk_pts;
-  long long p1 = p0 + chunk_pts - 1;
-  if (p1 > iv[k].i2) p1 = iv[k].i2;
+  // The chunk's tiles are counted from the interval's aligned origin (chunk_layout.hpp): with head = i1 mod 16 every tile
+  // starts on a 128-byte line of every row, so a wave's 64 values of a row are four whole lines.  The `head` lanes below i1
+  // (the first tile of the interval's first chunk only) are dead like the lanes past p1.
+  const ecckd::chunk_layout::Span sp = ecckd::chunk_layout::chunk_span(iv[k].i1, iv[k].i2, iv[k].chunk_pts, iv[k].head, chunk - iv[k].chunk0);
+  const long long p0 = sp.p0, p1 = sp.p1;
   // wave-uniform -> scalar loads; the odd waves read the bottom-up copy (k_interval_sums_fit_lw), so that both halves take
   // their layers at ascending constant offsets
   const double* __restrict__ grey = od_fit + ((size_t)(half ? nint : 0) + k) * NLAY;
@@ -971,10 +975,10 @@ k_rt_lw_bb_mirror(size_t n, int nint, long long nchunks, const Interval* __restr
 #pragma unroll
   for (int j = 0; j < NCH; ++j) acc[j] = 0.0;
 
-  for (long long base = p0; base <= p1; base += PTS, parity ^= 1) {
+  for (long long base = sp.base; base <= p1; base += PTS, parity ^= 1) {
     const long long i = base + pair * 64 + lane;
-    const bool live = i <= p1;
-    const size_t ii = live ? (size_t)i : (size_t)p1;
+    const bool live = i >= p0 && i <= p1;
+    const size_t ii = (size_t)(i < p0 ? p0 : i > p1 ? p1 : i);      // a dead lane loads a point of the chunk
     double a[H];       // optical depth -> transmittance
     double b[H + 1];   // Planck function -> source of the second sweep
     __builtin_amdgcn_s_setprio(ECCKD_PRIO_LOAD);     // a wave that is about to issue its 55 loads goes ahead of the waves that are computing
@@ -1015,9 +1019,10 @@ k_rt_lw_bb_mirror(size_t n, int nint, long long nchunks, const Interval* __restr
     }
     __builtin_amdgcn_s_setprio(ECCKD_PRIO_SWEEP1);   // first sweep: the partner wave waits for its result
 
-    // A lane past the end of the chunk (only the chunk's last tile has any) sweeps zero Planck functions: every flux of its
-    // column is then an exact zero and adds nothing to the level sums - no select per level.
-    if (base + PTS - 1 > p1) {
+    // A lane past the end of the chunk or below the interval's first point (only the chunk's last tile and the interval's
+    // first tile have any) sweeps zero Planck functions: every flux of its column is then an exact zero and adds nothing to
+    // the level sums - no select per level.
+    if (base + PTS - 1 > p1 || base < p0) {
       const double keep = live ? 1.0 : 0.0;
 #pragma unroll
       for (int l = 0; l <= H; ++l) b[l] *= keep;
@@ -1102,7 +1107,7 @@ k_rt_lw_bb_mirror(size_t n, int nint, long long nchunks, const Interval* __restr
   }
 }
 
-constexpr int COST_GROUPS = 64;    // K5d: groups of 32 chunks per interval it has room for (2 048 chunks)
+constexpr int COST_GROUPS = ecckd::chunk_layout::COST_GROUPS;    // K5d: groups of 32 chunks per interval it has room for (2 048 chunks)
 
 // K5d: combine chunk partials of each interval in order, heating rate, cost
 // (calc_cost_function_lw.cpp:100-109).  grid nint, block 1024 = 8 groups x 128.
@@ -1863,13 +1868,6 @@ k_cost_sw(int nlay, int ntotal, SwTruthRows rows, const Interval* __restrict__ i
   }
 }
 
-// Chunk size of an interval of `len` points: the smallest multiple of `gran` that covers it with at most `blocks` chunks.
-long long interval_chunk_pts(long long len, long long blocks, long long gran) {
-  long long c = (len + blocks - 1) / blocks;
-  c = (c + gran - 1) / gran * gran;
-  return c < gran ? gran : c;
-}
-
 int gas_ensure_work(ecckd_gas* g, size_t dev_bytes, size_t pinned_bytes) {
   if (dev_bytes > g->work_bytes) {
     if (g->work) {
@@ -2136,6 +2134,7 @@ static int make_interval(const ecckd_gas* g, size_t ibegin, size_t npoints, doub
   iv.i1 = (long long)ibegin + i1;
   iv.i2 = (long long)ibegin + i2;
   iv.chunk0 = 0;
+  iv.head = 0;
   iv.chunk_pts = 0;
   iv.npoints = (long long)npoints;
   iv.albedo = albedo;
@@ -2193,6 +2192,7 @@ int ecckd_gas_create_lw(ecckd_ctx* ctx, int nlay, size_t nwav, const double* h_p
   const bool is_log = averaging_method == ECCKD_AVG_LOGARITHMIC;
   const size_t nhl = nlay + 1;
   const size_t mat = (size_t)nlay * nwav * sizeof(double);
+  g->chunks_from_line = std::getenv("ECCKD_RT_UNALIGNED") == nullptr;
   if (d_planck_hl_reuse) g->planck_hl = const_cast<double*>(d_planck_hl_reuse);   // not recorded: its owner frees it
   else ECCKD_HIP_CHECK(g->alloc(&g->planck_hl, nhl * nwav * sizeof(double)));
   // The background rows.  FLOAT pairs for the sweep (k_rt_lw_bb_mirror<.., true>) whenever every value is a float: with a
@@ -2673,10 +2673,12 @@ static int eval_intervals(ecckd_gas* g, std::vector<Interval>& iv, double* error
   // Chunking.  Every interval is cut into chunks of ITS OWN size: the smallest multiple of what one block iteration covers
   // (the longwave mirror kernel: two wave pairs = 128 points; the other sweeps: 256) with which the interval fills at most
   // one round of resident blocks.  The chunk size - and with it the order in which the interval's points are added up, chunk
-  // by chunk in K5c and partial by partial in K5d - is a function of the interval's length alone, so an interval's error has
-  // the same bits whether it is evaluated alone, with its neighbours (calc_error_all, equipartition.h:98-116) or next to
-  // other bands' intervals (ecckd_calc_error_multi).  A batch of n intervals launches up to n rounds of small blocks; the
-  // hardware's block dispatcher balances them.
+  // by chunk in K5c and partial by partial in K5d - is a function of the interval alone (its first index and its length,
+  // chunk_layout.hpp), so an interval's error has the same bits whether it is evaluated alone, with its neighbours
+  // (calc_error_all, equipartition.h:98-116) or next to other bands' intervals (ecckd_calc_error_multi).  A batch of n
+  // intervals launches up to n rounds of small blocks; the hardware's block dispatcher balances them.
+  // The longwave mirror sweep counts the chunks from the 128-byte line that holds the interval's first point, so that every
+  // row load of every tile is four whole lines: where the rows start on a line and a row is a whole number of lines.
   // ECCKD_RT_GENERIC (read per call): the run-time-nlay sweeps instead of the compile-time ones, for cross-checks at full size
   b.fast_path = (nlay == 54 || nlay == 30) && std::getenv("ECCKD_RT_GENERIC") == nullptr;
   // mirror path: 3 resident blocks per CU (3 waves/SIMD); the two-fit shortwave sweep holds 2
@@ -2685,12 +2687,16 @@ static int eval_intervals(ecckd_gas* g, std::vector<Interval>& iv, double* error
   const bool is_tt = g->do_sw && g->method == ECCKD_AVG_TOTAL_TRANSMISSION;
   b.target_blocks = (long long)ctx->num_cu * (is_tt && b.fast_path ? sw2_bpc : b.fast_path ? rt_bpc : 8);
   const long long gran = (!g->do_sw && b.fast_path) ? RT_THREADS / 2 : RT_THREADS;
+  const auto on_line = [](const void* q) { return (uintptr_t)q % (ecckd::chunk_layout::LINE_PTS * sizeof(double)) == 0; };
+  const bool aligned = !g->do_sw && b.fast_path && g->chunks_from_line && g->n % ecckd::chunk_layout::LINE_PTS == 0 &&
+                       on_line(g->planck_hl) && on_line(g->bg_od) && on_line(g->bg_pair);
   b.nchunks = 0;
   for (int k = 0; k < n; ++k) {
-    const long long len = iv[k].i2 - iv[k].i1 + 1;
-    iv[k].chunk_pts = interval_chunk_pts(len, b.target_blocks, gran);
-    iv[k].chunk0 = b.nchunks;
-    b.nchunks += (len + iv[k].chunk_pts - 1) / iv[k].chunk_pts;
+    const ecckd::chunk_layout::Layout lay = ecckd::chunk_layout::of_interval(iv[k].i1, iv[k].i2, b.target_blocks, gran, aligned);
+    iv[k].chunk_pts = lay.chunk_pts;
+    iv[k].head = (int)lay.head;
+    iv[k].chunk0 = (int)std::min<long long>(b.nchunks, 0x7fffffffLL);
+    b.nchunks += lay.nchunks;
   }
   ECCKD_REQUIRE(b.nchunks < 0x7fffffffLL, "ecckd_calc_error_batch: %lld chunks in one batch", b.nchunks);
   b.cost_lds = (size_t)(COST_GROUPS * 2 * nhl + 2 * nhl + nlay) * sizeof(double);

@@ -60,6 +60,10 @@ struct ecckd_gas {
   double* planck_hl = nullptr;  // [nlay+1][n]  its own, or the matrix of an earlier gas (then not among `blocks`)
   double* bg_od = nullptr;      // [nlay][n]
   float* bg_pair = nullptr;     // [nlay/2][n][2]  longwave, only if every background value is a float: layers 2p, 2p+1 of a point side by side
+  // longwave: the mirror sweep may count an interval's chunks from the 128-byte line below its first point (chunk_layout.hpp);
+  // false with ECCKD_RT_UNALIGNED set when the gas was made (A/B knob: the chunks are counted from the first point itself).
+  // Fixed for the life of the gas: the memo of interval errors holds the bits of one layout.
+  bool chunks_from_line = false;
   double* w1 = nullptr;         // [nlay][n]  metric * weight          (log: log(metric)*weight)
   double* w2 = nullptr;         // [nlay][n]  log only: weight of the denominator where metric > 0
   double* cnt = nullptr;        // [nlay][n]  log only: 1 where metric > 0
