@@ -169,6 +169,8 @@ def reorder_key_sw(ctx, pressure_hl, optical_depth, threshold_optical_depth=0.25
     if optical_depth.dim() != 2 or optical_depth.shape[0] != nlay:
         raise EcckdError(_lib.PARAMETER_ERROR, "optical_depth must be (nlay, nwav)")
     nwav = optical_depth.shape[1]
+    if optical_depth.stride(1) != 1 and nwav > 1:
+        raise EcckdError(_lib.PARAMETER_ERROR, "optical_depth rows must be contiguous")
     stride = optical_depth.stride(0) if nlay > 1 else max(nwav, 1)
     if key is None:
         key = torch.empty(nwav, dtype=torch.float64, device=ctx.device)
