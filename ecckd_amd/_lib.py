@@ -185,6 +185,12 @@ SIGNATURES = {
     "ecckd_lbl_spectral_fluxes_sw": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_int, _c_double_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, _c_double_p,
                                                _c_double_p]),
+    "ecckd_lbl_gpoint_fluxes_sw_rayleigh": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _c_double_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, _c_double_p, _c_double_p,
+                                                      _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "ecckd_lbl_spectral_fluxes_sw_rayleigh": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_int, _c_double_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_size_t, _c_double_p, _c_double_p, _c_double_p]),
     "ecckd_nc_open": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
     "ecckd_nc_close": (C.c_int, [C.c_void_p]),
     "ecckd_nc_inq_dim": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_size_t)]),

@@ -1375,6 +1375,36 @@ def lbl_spectral_fluxes_sw(ctx, cos_sza, ssi, optical_depth, albedo=None):
     return dn, up, bdn, bup
 
 
+def _rayleigh_pair(optical_depth, rayleigh_optical_depth):
+    """(nlay, nwav, the two row strides) of an absorption / Rayleigh pair of (nlay, nwav) device tensors"""
+    nlay, nwav = optical_depth.shape
+    if tuple(rayleigh_optical_depth.shape) != (nlay, nwav):
+        raise ValueError("optical_depth and rayleigh_optical_depth must have one shape (nlay, nwav)")
+    stride = lambda od: od.stride(0) if nlay > 1 else nwav
+    return nlay, nwav, stride(optical_depth), stride(rayleigh_optical_depth)
+
+
+def lbl_spectral_fluxes_sw_rayleigh(ctx, cos_sza, ssi, optical_depth, rayleigh_optical_depth, albedo=None):
+    """Line-by-line shortwave spectral fluxes of one column with Rayleigh scattering (two-stream,
+    ecckd_lbl_spectral_fluxes_sw_rayleigh) for every solar zenith angle of cos_sza (a scalar is one angle): device tensors ssi
+    (nwav,), optical_depth (absorption) and rayleigh_optical_depth (nlay, nwav), each float32 or float64, albedo (nwav,) or
+    None (albedo 0) -> (flux_dn_direct, flux_dn, flux_up) FLOAT device tensors (nsza, nlay+1, nwav), flux_dn direct plus
+    diffuse, and (bb_dn_direct, bb_dn, bb_up) host arrays (nsza, nlay+1) summed in double."""
+    mu = _f64c(np.atleast_1d(cos_sza))
+    nlay, nwav, abs_stride, ray_stride = _rayleigh_pair(optical_depth, rayleigh_optical_depth)
+    torch = _torch()
+    spec = [torch.empty((mu.size, nlay + 1, nwav), dtype=torch.float32, device=ctx.device) for _ in range(3)]
+    bb = [np.empty((mu.size, nlay + 1)) for _ in range(3)]
+    ctx.fence_from_torch()
+    check(ctx.lib.ecckd_lbl_spectral_fluxes_sw_rayleigh(ctx.handle, nlay, nwav, mu.size, _hptr(mu), _dptr(ssi),
+                                                        _dptr(albedo) if albedo is not None else None, _dptr(optical_depth),
+                                                        _od_type(optical_depth), abs_stride, _dptr(rayleigh_optical_depth),
+                                                        _od_type(rayleigh_optical_depth), ray_stride, *[_dptr(t) for t in spec], nwav,
+                                                        *[_hptr(b) for b in bb]))
+    ctx.synchronize()
+    return (*spec, *bb)
+
+
 def scale_lut(ctx, model, flux_sums, pressure_hl, temperature_hl, vmr_fl, gas_present, mu0):
     """scale_lut.cpp:117-189 + CkdModel::scale_optical_depth for one reference profile.  `flux_sums` (nz+1, ng)
     from GPointMap.sum_rows of the LBL direct spectral flux.  -> (list of scaled molar_abs arrays, scaling[nz, ng])."""
@@ -1478,6 +1508,24 @@ class GPointMap:
                                                   _dptr(albedo) if albedo is not None else None, _dptr(optical_depth),
                                                   _od_type(optical_depth), stride, _hptr(dn), _hptr(up), _hptr(bdn), _hptr(bup)))
         return dn, up, bdn, bup
+
+    def lbl_fluxes_sw_rayleigh(self, cos_sza, ssi, optical_depth, rayleigh_optical_depth, albedo=None):
+        """Line-by-line shortwave fluxes of one column per g point with Rayleigh scattering (two-stream,
+        ecckd_lbl_gpoint_fluxes_sw_rayleigh), fused, for every solar zenith angle of cos_sza (a scalar is one angle): device
+        tensors ssi (nwav,), optical_depth (absorption) and rayleigh_optical_depth (nlay, nwav), each float32 or float64,
+        albedo (nwav,) or None (albedo 0) -> (flux_dn_direct, flux_dn, flux_up) each (nsza, nlay+1, ng), flux_dn direct plus
+        diffuse, and (bb_dn_direct, bb_dn, bb_up) each (nsza, nlay+1): the sums over ALL wavenumbers."""
+        mu = _f64c(np.atleast_1d(cos_sza))
+        nlay, nwav, abs_stride, ray_stride = _rayleigh_pair(optical_depth, rayleigh_optical_depth)
+        flux = [np.empty((mu.size, nlay + 1, self.ng)) for _ in range(3)]
+        bb = [np.empty((mu.size, nlay + 1)) for _ in range(3)]
+        self.ctx.fence_from_torch()
+        check(self.lib.ecckd_lbl_gpoint_fluxes_sw_rayleigh(self.handle, nlay, mu.size, _hptr(mu), _dptr(ssi),
+                                                           _dptr(albedo) if albedo is not None else None, _dptr(optical_depth),
+                                                           _od_type(optical_depth), abs_stride, _dptr(rayleigh_optical_depth),
+                                                           _od_type(rayleigh_optical_depth), ray_stride, *[_hptr(f) for f in flux],
+                                                           *[_hptr(b) for b in bb]))
+        return (*flux, *bb)
 
     def erythemal_spectrum(self):
         """sqrt(erythemal action spectrum) per g point, 5777 K Planck weighted (lbl_fluxes.cpp:198-230)."""

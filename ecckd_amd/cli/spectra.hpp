@@ -33,7 +33,7 @@ std::vector<double> download_as_double(const DevBuf& b) {
 
 inline int spectra_main(int argc, char** argv, bool sw) {
   return run(argc, argv, [&](Config& config) -> int {
-    std::string output, ssi_file_name;
+    std::string output, ssi_file_name, rayleigh_file_name;
     if (!config.read(output, "output")) fail(ECCKD_PARAMETER_ERROR, "\"output\" file not specified");
     std::vector<double> mu0;
     double surface_albedo = 0.15;
@@ -45,6 +45,9 @@ inline int spectra_main(int argc, char** argv, bool sw) {
         if (!(m > 0.0 && m <= 1.0)) fail(ECCKD_PARAMETER_ERROR, "cos_solar_zenith_angle %g is not in (0, 1]", m);
       config.read(surface_albedo, "surface_albedo");
     }
+    // rayleigh=FILE (shortwave): a spectrum file whose optical_depth scatters, beside the merged absorbers (two-stream transfer)
+    const bool rayleigh = config.read(rayleigh_file_name, "rayleigh");
+    if (rayleigh && !sw) fail(ECCKD_PARAMETER_ERROR, "\"rayleigh\" is a key of sw_spectra: the longwave fluxes do not scatter");
     const int nmu = sw ? (int)mu0.size() : 1;   // rows of fluxes per column
     SearchPath paths;
     paths.configure(config);
@@ -75,7 +78,8 @@ inline int spectra_main(int argc, char** argv, bool sw) {
 
     NcOut file(output);
     ecckd_gmap* gmap = nullptr;
-    DevBuf d_wn, d_dwn, d_g, d_ssi, d_albedo, d_spec_dn, d_spec_up;
+    DevBuf d_wn, d_dwn, d_g, d_ssi, d_albedo, d_spec_dn, d_spec_up, d_spec_tot;
+    std::string rayleigh_path;
     const std::string spec_name = have_gpoints ? "g_point" : "wavenumber";
     const std::string bb_dn_name = sw ? "flux_dn_direct_sw" : "flux_dn_lw", bb_up_name = sw ? "flux_up_sw" : "flux_up_lw";
     const std::string spec_dn_name = "spectral_" + bb_dn_name, spec_up_name = "spectral_" + bb_up_name;
@@ -94,6 +98,15 @@ inline int spectra_main(int argc, char** argv, bool sw) {
         if (sw && ssi.size() != nwav)
           fail(ECCKD_PARAMETER_ERROR, "solar_spectral_irradiance has %zu points, the spectrum %zu", ssi.size(), nwav);
         if (sw) have_temperature = !m.first.temperature_hl.empty();
+        if (rayleigh) {                         // the grid of the spectrum that scatters is the merged one's
+          rayleigh_path = paths.find(rayleigh_file_name);
+          LOG("  Reading %s\n", rayleigh_path.c_str());
+          const Spectrum r = read_spectrum(rayleigh_path, icol, false);
+          if (r.nwav != nwav || r.wavenumber_cm_1 != m.first.wavenumber_cm_1)
+            fail(ECCKD_PARAMETER_ERROR, "%s: %zu wavenumbers that are not the %zu of the merged spectrum", rayleigh_path.c_str(), r.nwav, nwav);
+          if (r.nlay != nlay) fail(ECCKD_PARAMETER_ERROR, "%s has %d levels, the merged spectrum %d", rayleigh_path.c_str(), r.nlay, nlay);
+          if (r.ncol != ncol) fail(ECCKD_PARAMETER_ERROR, "%s has %d columns, the input %d", rayleigh_path.c_str(), r.ncol, ncol);
+        }
         std::vector<std::string> hl = {"column", "half_level"};
         if (sw) hl.insert(hl.begin() + 1, "mu0");
         std::vector<std::string> hl_spec = hl;
@@ -120,6 +133,7 @@ inline int spectra_main(int argc, char** argv, bool sw) {
         if (sw) {
           file.var(bb_dn_name, NC_FLOAT_T, hl, "Downwelling direct shortwave flux", "W m-2");
           file.var(bb_up_name, NC_FLOAT_T, hl, "Upwelling shortwave flux", "W m-2");
+          if (rayleigh) file.var("flux_dn_sw", NC_FLOAT_T, hl, "Downwelling shortwave flux", "W m-2");
         } else {
           file.var(bb_dn_name, NC_FLOAT_T, hl, "Upwelling longwave flux", "W m-2");   // (sic, :169)
           file.var(bb_up_name, NC_FLOAT_T, hl, "Upwelling longwave flux", "W m-2");
@@ -127,11 +141,16 @@ inline int spectra_main(int argc, char** argv, bool sw) {
         file.var("optical_depth", NC_FLOAT_T, {"column", "level", spec_name});
         if (!have_gpoints) file.deflate("optical_depth");
         file.att("Layer optical depth", "long_name", "optical_depth");
+        if (rayleigh && have_gpoints)
+          file.var("rayleigh_optical_depth", NC_FLOAT_T, {"column", "level", spec_name}, "Layer optical depth due to Rayleigh scattering");
         if (sw) {
           file.var(spec_dn_name, NC_FLOAT_T, hl_spec,
                    have_gpoints ? "Downwelling direct shortwave flux per g point" : "Downwelling direct shortwave spectral flux", "W m-2");
           file.var(spec_up_name, NC_FLOAT_T, hl_spec, have_gpoints ? "Upwelling shortwave flux per g point" : "Upwelling shortwave spectral flux",
                    "W m-2");
+          if (rayleigh)
+            file.var("spectral_flux_dn_sw", NC_FLOAT_T, hl_spec,
+                     have_gpoints ? "Downwelling shortwave flux per g point" : "Downwelling shortwave spectral flux", "W m-2");
         } else {
           file.var(spec_dn_name, NC_FLOAT_T, hl_spec, "Downwelling longwave spectral flux", "W m-2");
           file.var(spec_up_name, NC_FLOAT_T, hl_spec, "Upwelling longwave spectral flux", "W m-2");
@@ -141,6 +160,7 @@ inline int spectra_main(int argc, char** argv, bool sw) {
         std::replace(molecules.begin(), molecules.end(), ',', ' ');                           // :193
         file.att(molecules, "molecules");
         file.att(config.str(), "config");
+        if (rayleigh) file.att("two-stream", "rayleigh_scattering");
         file.end_define();
         if (sw) file.write("mu0", mu0);
         if (!have_gpoints) file.write("wavenumber", m.first.wavenumber_cm_1);
@@ -163,6 +183,7 @@ inline int spectra_main(int argc, char** argv, bool sw) {
         } else {
           d_spec_dn.alloc(dev, (size_t)nhl * nwav * sizeof(float));
           d_spec_up.alloc(dev, (size_t)nhl * nwav * sizeof(float));
+          if (rayleigh) d_spec_tot.alloc(dev, (size_t)nhl * nwav * sizeof(float));
         }
       }
       file.write_slice("pressure_hl", irec, m.first.pressure_hl);
@@ -173,10 +194,29 @@ inline int spectra_main(int argc, char** argv, bool sw) {
 
       if (sw) LOG("  Performing shortwave radiative transfer for %d solar zenith angles\n", nmu);
       else LOG("  Computing Planck function and performing longwave radiative transfer\n");
-      std::vector<double> bb_dn((size_t)nmu * nhl), bb_up((size_t)nmu * nhl);
+      std::vector<double> bb_dn((size_t)nmu * nhl), bb_up((size_t)nmu * nhl), bb_tot(rayleigh ? (size_t)nmu * nhl : 0);
+      DevOd ray;                                // the column of the spectrum that scatters, unscaled, as it is stored
+      if (rayleigh) {
+        ray = read_od_dev(dev, NcIn(rayleigh_path), icol, nlay, nwav);
+        ck(ecckd_synchronize(dev.ctx()));
+      }
       const std::vector<double>& p = m.first.pressure_hl;
       const std::vector<double>& t = m.first.temperature_hl;
-      if (!have_gpoints && sw) {
+      if (!have_gpoints && rayleigh) {
+        for (int s = 0; s < nmu; ++s) {                           // one angle at a time, as without scattering
+          ck(ecckd_lbl_spectral_fluxes_sw_rayleigh(dev.ctx(), nlay, nwav, 1, &mu0[s], d_ssi.as<double>(), d_albedo.as<double>(), m.od_ptr(),
+                                                   m.od_type(), nwav, ray.buf.ptr(), ray.type, nwav, d_spec_dn.as<float>(),
+                                                   d_spec_tot.as<float>(), d_spec_up.as<float>(), nwav, &bb_dn[(size_t)s * nhl],
+                                                   &bb_tot[(size_t)s * nhl], &bb_up[(size_t)s * nhl]));
+          file.write_subslice(spec_dn_name, irec, (size_t)s, download_as_double(d_spec_dn));
+          file.write_subslice(spec_up_name, irec, (size_t)s, download_as_double(d_spec_up));
+          file.write_subslice("spectral_flux_dn_sw", irec, (size_t)s, download_as_double(d_spec_tot));
+        }
+        file.write_slice(bb_dn_name, irec, bb_dn);
+        file.write_slice(bb_up_name, irec, bb_up);
+        file.write_slice("flux_dn_sw", irec, bb_tot);
+        file.write_slice("optical_depth", irec, download_od(dev, m, (size_t)nlay * nwav));
+      } else if (!have_gpoints && sw) {
         for (int s = 0; s < nmu; ++s) {                           // one angle at a time, on the device and on the host
           ck(ecckd_lbl_spectral_fluxes_sw(dev.ctx(), nlay, nwav, 1, &mu0[s], d_ssi.as<double>(), d_albedo.as<double>(), m.od_ptr(),
                                           m.od_type(), nwav, d_spec_dn.as<float>(), d_spec_up.as<float>(), nwav, &bb_dn[(size_t)s * nhl],
@@ -197,7 +237,12 @@ inline int spectra_main(int argc, char** argv, bool sw) {
         file.write_slice(spec_up_name, irec, download_as_double(d_spec_up));
       } else {
         std::vector<double> dn((size_t)nmu * nhl * ng), up((size_t)nmu * nhl * ng), od_g((size_t)nlay * ng), t_fl;
-        if (sw) {
+        std::vector<double> tot(rayleigh ? dn.size() : 0);
+        if (rayleigh) {
+          ck(ecckd_lbl_gpoint_fluxes_sw_rayleigh(gmap, nlay, nmu, mu0.data(), d_ssi.as<double>(), d_albedo.as<double>(), m.od_ptr(), m.od_type(),
+                                                 nwav, ray.buf.ptr(), ray.type, nwav, dn.data(), tot.data(), up.data(), bb_dn.data(),
+                                                 bb_tot.data(), bb_up.data()));
+        } else if (sw) {
           ck(ecckd_lbl_gpoint_fluxes_sw(gmap, nlay, nmu, mu0.data(), d_ssi.as<double>(), d_albedo.as<double>(), m.od_ptr(), m.od_type(),
                                         nwav, dn.data(), up.data(), bb_dn.data(), bb_up.data()));
         } else {
@@ -216,6 +261,13 @@ inline int spectra_main(int argc, char** argv, bool sw) {
         file.write_slice("optical_depth", irec, od_g);
         file.write_slice(spec_dn_name, irec, dn);
         file.write_slice(spec_up_name, irec, up);
+        if (rayleigh) {                       // the Rayleigh spectrum averaged like optical_depth, which stays the absorbers'
+          ck(ecckd_average_to_gpoints(gmap, nlay, p.data(), nullptr, d_ssi.as<double>(), ray.buf.ptr(), ray.type, nwav, ECCKD_AVG_TRANSMISSION,
+                                      0.0, od_g.data(), nullptr, nullptr));
+          file.write_slice("flux_dn_sw", irec, bb_tot);
+          file.write_slice("rayleigh_optical_depth", irec, od_g);
+          file.write_slice("spectral_flux_dn_sw", irec, tot);
+        }
       }
       if (do_one_profile) break;
       ++icol;

@@ -14,6 +14,16 @@
 // angles in one call) / ecckd_lbl_spectral_fluxes_sw (one angle per call, written to the file angle by angle: device memory
 // stays at 2 (nlay+1) nwav floats, host memory at one angle's rows), the g-point optical depths from
 // ecckd_average_to_gpoints (include/ecckd_hip.h).
+// rayleigh=FILE: a spectrum file like any gas file whose optical_depth SCATTERS, read column by column beside the merged
+// absorbers, unscaled (as ckdmip_sw --rayleigh reads it); its wavenumbers and levels must be the merged spectrum's and it must
+// have as many columns as `input`, otherwise the tool fails with a parameter error.  The fluxes are then those of the
+// two-stream transfer (ecckd_lbl_gpoint_fluxes_sw_rayleigh / ecckd_lbl_spectral_fluxes_sw_rayleigh): the file holds in
+// addition flux_dn_sw and spectral_flux_dn_sw (direct plus diffuse), its upwelling fluxes hold the backscatter, the global
+// attribute rayleigh_scattering = "two-stream" is set and, with `gpoints`, rayleigh_optical_depth(column, level, g_point) is
+// that spectrum averaged like optical_depth, which stays the absorbers' average: the file then holds the flux variables of a
+// ckdmip_sw --ckd --rayleigh-scattering output (ckdmip.hpp: define_ckd_output) and the two optical depths run_ckd writes, so a
+// CKD model is compared with it variable by variable.  Without `gpoints` device memory is 3 (nlay+1) nwav floats.  Without
+// the key the file is byte for byte what it was.
 #include "spectra.hpp"
 
 int main(int argc, char** argv) { return spectra_main(argc, argv, true); }

@@ -181,4 +181,19 @@ inline void unpack_gpoint_out(const double* out, int nsza, int nhl, int ng, doub
     }
 }
 
+// The three-flux sibling (lbl_gpoint_fluxes_sw_rayleigh.hip): out[nsza][3][nhl][ng + 1], flux 0 the direct beam, 1 the total
+// downwelling flux, 2 the upwelling one; h_flux[k] [nsza][nhl][ng] (all NULL when ng = 0) and h_bb[k] [nsza][nhl], each or NULL
+inline void unpack_gpoint_out3(const double* out, int nsza, int nhl, int ng, double* const (&h_flux)[3], double* const (&h_bb)[3]) {
+  for (int s = 0; s < nsza; ++s)
+    for (int k = 0; k < 3; ++k)
+      for (int l = 0; l < nhl; ++l) {
+        const double* row = &out[((size_t)(s * 3 + k) * nhl + l) * (ng + 1)];
+        double bb = 0.0;
+        for (int g = 0; g <= ng; ++g) bb += row[g];
+        const size_t o = (size_t)s * nhl + l;
+        for (int g = 0; g < ng; ++g) h_flux[k][o * ng + g] = row[g];
+        if (h_bb[k]) h_bb[k][o] = bb;
+      }
+}
+
 }  // namespace

@@ -25,10 +25,6 @@ namespace {
 
 using namespace ecckd::lbl;
 
-constexpr int RAYLEIGH_BLOCKS_PER_CU = 3;     // the waves per SIMD its registers allow
-constexpr int RAYLEIGH_SLOTS = 3;        // D, A, S per level
-constexpr int RAYLEIGH_FLUXES = 3;       // direct, total down, up per level
-
 // LDS: acc[4][3][nhl]; ws: [gridDim.x][3][nhl][LBL_THREADS]; partial: [nchunk][nsza][3][nhl]
 template <typename AbsT, typename RayT>
 __global__ void __launch_bounds__(LBL_THREADS)
@@ -106,16 +102,6 @@ k_lbl_fluxes_sw_rayleigh(int nlay, int nsza, int nchunk, size_t nwav, size_t abs
       __syncthreads();
     }
   }
-}
-
-// blocks of the launch: every chunk its own up to the bound, ECCKD_RAYLEIGH_GRID (>= 1) in place of the bound
-size_t rayleigh_grid(const ecckd_ctx* ctx, size_t nchunk) {
-  size_t cap = (size_t)std::max(ctx->num_cu, 1) * RAYLEIGH_BLOCKS_PER_CU;
-  if (const char* e = std::getenv("ECCKD_RAYLEIGH_GRID")) {
-    const long v = std::atol(e);
-    if (v >= 1) cap = (size_t)v;
-  }
-  return std::min(nchunk, cap);
 }
 
 }  // namespace

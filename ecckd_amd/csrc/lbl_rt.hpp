@@ -1,6 +1,6 @@
 // lbl_rt.hpp - the transfer of ONE wavenumber, written once for the line-by-line kernels (lbl_fluxes.hip,
-// lbl_gpoint_fluxes.hip, lbl_gpoint_fluxes_sw.hip, lbl_scenarios.hip: no scattering; lbl_fluxes_sw_rayleigh.hip and
-// k_rt_sw_gpoints_rayleigh of lbl_fluxes.hip: Rayleigh scattering; k_opt_forward_adjoint_rayleigh of optimize.hip takes the same
+// lbl_gpoint_fluxes.hip, lbl_gpoint_fluxes_sw.hip, lbl_scenarios.hip: no scattering; lbl_fluxes_sw_rayleigh.hip,
+// lbl_gpoint_fluxes_sw_rayleigh.hip and k_rt_sw_gpoints_rayleigh of lbl_fluxes.hip: Rayleigh scattering; k_opt_forward_adjoint_rayleigh of optimize.hip takes the same
 // Rayleigh functions and their derivative rayleigh_layer_d), and the host plumbing they share.  DESIGN.md and the
 // tests compare these kernels with each other, bit for bit where they can: one source text keeps an edit from reaching only
 // one of them.  The files are compiled with the default contraction, so an expression here and in rt_device.hpp keeps its form
@@ -35,6 +35,7 @@
 #include "rt_device.hpp"
 
 #include <algorithm>
+#include <cstdlib>
 #include <initializer_list>
 #include <vector>
 
@@ -314,6 +315,23 @@ inline int sw_angle_table(const char* who, int nsza, const double* h_cos_sza, do
     h_ang[LBL_MAX_SZA + s] = -1.0 / h_ang[s];
   }
   return ECCKD_OK;
+}
+
+// The line-by-line Rayleigh kernels (lbl_fluxes_sw_rayleigh.hip, lbl_gpoint_fluxes_sw_rayleigh.hip) keep what one sweep leaves
+// the next per level in a device workspace [block][slot][level][thread], so their grid is bounded and its blocks loop over
+// the work: every unit (a chunk, a logical block of tiles) its own block up to blocks_per_cu per compute unit, or
+// ECCKD_RAYLEIGH_GRID (>= 1) blocks in place of that bound.
+constexpr int RAYLEIGH_BLOCKS_PER_CU = 3;     // the waves per SIMD the registers of k_lbl_fluxes_sw_rayleigh allow
+constexpr int RAYLEIGH_SLOTS = 3;             // D, A, S per level
+constexpr int RAYLEIGH_FLUXES = 3;            // direct, total down, up per level
+
+inline size_t rayleigh_grid(const ecckd_ctx* ctx, size_t nwork, int blocks_per_cu = RAYLEIGH_BLOCKS_PER_CU) {
+  size_t cap = (size_t)std::max(ctx->num_cu, 1) * blocks_per_cu;
+  if (const char* e = std::getenv("ECCKD_RAYLEIGH_GRID")) {
+    const long v = std::atol(e);
+    if (v >= 1) cap = (size_t)v;
+  }
+  return std::min(nwork, cap);
 }
 
 inline int check_od(const char* who, int od_type, size_t od_stride, size_t nwav) {

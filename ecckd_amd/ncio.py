@@ -695,6 +695,7 @@ def write_sw_spectra(path, s, config_str="", history=None):
     nrec, nlay = s["optical_depth"].shape[:2]
     have_g = s["ng"] > 0
     have_t = "temperature_hl" in s
+    rayleigh = bool(s.get("rayleigh"))       # flux_dn_sw, spectral_flux_dn_sw and (per g point) rayleigh_optical_depth too
     spec = "g_point" if have_g else "wavenumber"
     w = NcWriter(path)
     w.define_dimension("column", 0)
@@ -724,17 +725,26 @@ def write_sw_spectra(path, s, config_str="", history=None):
     w.write_attribute("comment", 'The gases are listed in the global attribute "molecules".', var="vmr_fl")
     var("flux_dn_direct_sw", ("column", "mu0", "half_level"), "Downwelling direct shortwave flux", "W m-2")
     var("flux_up_sw", ("column", "mu0", "half_level"), "Upwelling shortwave flux", "W m-2")
+    if rayleigh:
+        var("flux_dn_sw", ("column", "mu0", "half_level"), "Downwelling shortwave flux", "W m-2")
     w.define_variable("optical_depth", "float", "column", "level", spec)
     if not have_g:
         w.deflate_variable("optical_depth")
     w.write_attribute("long_name", "Layer optical depth", var="optical_depth")
+    if rayleigh and have_g:
+        var("rayleigh_optical_depth", ("column", "level", spec), "Layer optical depth due to Rayleigh scattering")
     var("spectral_flux_dn_direct_sw", ("column", "mu0", "half_level", spec),
         "Downwelling direct shortwave flux per g point" if have_g else "Downwelling direct shortwave spectral flux", "W m-2")
     var("spectral_flux_up_sw", ("column", "mu0", "half_level", spec),
         "Upwelling shortwave flux per g point" if have_g else "Upwelling shortwave spectral flux", "W m-2")
+    if rayleigh:
+        var("spectral_flux_dn_sw", ("column", "mu0", "half_level", spec),
+            "Downwelling shortwave flux per g point" if have_g else "Downwelling shortwave spectral flux", "W m-2")
     w.write_attribute("history", history or "")
     w.write_attribute("molecules", s["molecules"])
     w.write_attribute("config", config_str)
+    if rayleigh:
+        w.write_attribute("rayleigh_scattering", "two-stream")
     w.end_define_mode()
     w.write("mu0", s["mu0"])
     if not have_g:
@@ -743,6 +753,8 @@ def write_sw_spectra(path, s, config_str="", history=None):
         w.write("solar_irradiance", s["solar_irradiance"])
     names = ["pressure_hl"] + (["temperature_hl"] if have_t else []) + ["vmr_fl", "flux_dn_direct_sw", "flux_up_sw", "optical_depth",
                                                                         "spectral_flux_dn_direct_sw", "spectral_flux_up_sw"]
+    if rayleigh:
+        names += ["flux_dn_sw", "spectral_flux_dn_sw"] + (["rayleigh_optical_depth"] if have_g else [])
     for r in range(nrec):
         for name in names:
             if not have_g and name.startswith("spectral_flux"):      # angle by angle, as the tool

@@ -976,21 +976,26 @@ def lw_spectra(ctx, inputs, output_path=None, scaling=None, conc=None, g_point=N
 
 
 def sw_spectra(ctx, inputs, ssi, output_path=None, scaling=None, conc=None, g_point=None, iprofile=None, cos_sza=(0.5,),
-               surface_albedo=0.15, config_str="", history=None):
+               surface_albedo=0.15, config_str="", history=None, rayleigh=None):
     """bin/sw_spectra as the tool does it: per column the merged spectrum, then either the spectral fluxes one angle at a time
     (ecckd_lbl_spectral_fluxes_sw) or, with g_point (one value per wavenumber, -1 = none), the fluxes per g point for all
     angles in one call (ecckd_lbl_gpoint_fluxes_sw) and the optical depth averaged by transmission with the `ssi` weight
     (ecckd_average_to_gpoints, reference_surface_vmr = 0).  `ssi`: solar spectral irradiance per wavenumber (host array).
+    `rayleigh`: the path of a spectrum file whose optical_depth scatters (the tool's key): the fluxes are those of the two-stream
+    transfer (ecckd_lbl_spectral_fluxes_sw_rayleigh / ecckd_lbl_gpoint_fluxes_sw_rayleigh), flux_dn_sw and spectral_flux_dn_sw
+    (direct plus diffuse) are returned too and, with g_point, rayleigh_optical_depth: that spectrum averaged like optical_depth.
     Arrays are returned in double as the library gives them (the tool's file holds their FLOAT casts): dict of (nrec, ...)
     arrays; written to output_path when given."""
     import torch
     names = ["pressure_hl", "temperature_hl", "vmr_fl", "flux_dn_direct_sw", "flux_up_sw", "optical_depth",
              "spectral_flux_dn_direct_sw", "spectral_flux_up_sw"]
+    have_g = g_point is not None
+    if rayleigh is not None:
+        names += ["flux_dn_sw", "spectral_flux_dn_sw"] + (["rayleigh_optical_depth"] if have_g else [])
     out = {k: [] for k in names}
     mu0 = np.atleast_1d(np.asarray(cos_sza, dtype=np.float64))
     if not (1 <= mu0.size <= 8) or np.any(~((mu0 > 0.0) & (mu0 <= 1.0))):
         raise EcckdError(PARAMETER_ERROR, "cos_sza must hold 1 to 8 numbers in (0, 1]")
-    have_g = g_point is not None
     ng = int(np.max(g_point)) + 1 if have_g else -1
     if have_g and ng < 1:
         raise EcckdError(PARAMETER_ERROR, "g_point assigns no wavenumber to a g point")
@@ -1012,24 +1017,44 @@ def sw_spectra(ctx, inputs, ssi, output_path=None, scaling=None, conc=None, g_po
                 gm = api.GPointMap(ctx, torch.as_tensor(np.ascontiguousarray(g_point, dtype=np.int32), device=ctx.device), ng, d_wn, d_dwn)
                 out["solar_irradiance"] = gm.sum_rows(d_ssi[None, :])[0]
             out["wavenumber"], out["molecules"] = first["wavenumber_cm_1"], molecules.replace(",", " ")
+        ray = None
+        if rayleigh is not None:                     # the spectrum that scatters: this column of it, unscaled, as it is stored
+            r = ncio.read_spectrum(rayleigh, icol)
+            if not np.array_equal(r["wavenumber_cm_1"], first["wavenumber_cm_1"]) or r["pressure_hl"].size != p.size or r["ncol"] != ncol:
+                raise EcckdError(PARAMETER_ERROR, "the Rayleigh spectrum does not have the merged spectrum's wavenumbers, levels and columns")
+            ray = _to_device(r["optical_depth"], ctx.device)
         out["pressure_hl"].append(p)
         if t is not None:
             out["temperature_hl"].append(t)
         out["vmr_fl"].append(vmr)
         if not have_g:
-            sdn, sup, bdn, bup = [], [], [], []
+            sdn, sup, stot, bdn, bup, btot = [], [], [], [], [], []
             for mu in mu0:                                                                     # one angle at a time, as the tool
-                a, b, c, d = api.lbl_spectral_fluxes_sw(ctx, mu, d_ssi, od, d_albedo)
+                if ray is not None:
+                    a, e, b, c, f, d = api.lbl_spectral_fluxes_sw_rayleigh(ctx, mu, d_ssi, od, ray, d_albedo)
+                    stot.append(e[0].cpu().numpy().astype(np.float64))
+                    btot.append(f[0])
+                else:
+                    a, b, c, d = api.lbl_spectral_fluxes_sw(ctx, mu, d_ssi, od, d_albedo)
                 sdn.append(a[0].cpu().numpy().astype(np.float64))
                 sup.append(b[0].cpu().numpy().astype(np.float64))
                 bdn.append(c[0])
                 bup.append(d[0])
             bdn, bup = np.stack(bdn), np.stack(bup)
+            if ray is not None:
+                out["spectral_flux_dn_sw"].append(np.stack(stot))
+                out["flux_dn_sw"].append(np.stack(btot))
             out["optical_depth"].append(od.cpu().numpy().astype(np.float64))
             out["spectral_flux_dn_direct_sw"].append(np.stack(sdn))
             out["spectral_flux_up_sw"].append(np.stack(sup))
         else:
-            dn, up, bdn, bup = gm.lbl_fluxes_sw(mu0, d_ssi, od, d_albedo)
+            if ray is not None:
+                dn, tot, up, bdn, btot, bup = gm.lbl_fluxes_sw_rayleigh(mu0, d_ssi, od, ray, d_albedo)
+                out["spectral_flux_dn_sw"].append(tot)
+                out["flux_dn_sw"].append(btot)
+                out["rayleigh_optical_depth"].append(gm.average_optical_depth(p, ray, "transmission", 0.0, ssi=d_ssi)[0])
+            else:
+                dn, up, bdn, bup = gm.lbl_fluxes_sw(mu0, d_ssi, od, d_albedo)
             od_g, _, _ = gm.average_optical_depth(p, od, "transmission", 0.0, ssi=d_ssi)
             out["optical_depth"].append(od_g)
             out["spectral_flux_dn_direct_sw"].append(dn)
@@ -1047,6 +1072,8 @@ def sw_spectra(ctx, inputs, ssi, output_path=None, scaling=None, conc=None, g_po
     for k in names:
         out[k] = np.stack(out[k])
     out["ng"], out["mu0"] = ng, mu0
+    if rayleigh is not None:
+        out["rayleigh"] = True                      # write_sw_spectra: the variables and the attribute the key adds
     if output_path is not None:
         ncio.write_sw_spectra(output_path, out, config_str=config_str, history=history)
     return out

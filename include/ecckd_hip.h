@@ -921,6 +921,26 @@ int ecckd_lbl_gpoint_fluxes_sw(ecckd_gmap* gmap, int nlay, int nsza, const doubl
 int ecckd_lbl_spectral_fluxes_sw(ecckd_ctx* ctx, int nlay, size_t nwav, int nsza, const double* h_cos_sza, const double* d_ssi,
                                  const double* d_albedo, const void* d_od, int od_type, size_t od_stride, float* d_flux_dn_direct,
                                  float* d_flux_up, size_t flux_stride, double* h_bb_dn, double* h_bb_up);
+/* The same per g point WITH Rayleigh scattering: the two-stream transfer of ecckd_lbl_band_fluxes_sw_rayleigh (d_od_abs
+ * absorbs, d_od_ray scatters; each FLOAT or DOUBLE with its own stride) per wavenumber and, in the same pass,
+ * h_flux_dn_direct / h_flux_dn (direct plus diffuse) / h_flux_up[nsza][nlay+1][ng] = the sums over the wavenumbers of each g
+ * point (exactly 0 for a g point without wavenumbers); h_bb_*[nsza][nlay+1] (each may be NULL) = the sums over ALL
+ * wavenumbers, those with g_point = -1 included.  d_albedo = NULL is albedo 0.  One angle per launch: angle s of a call has
+ * the bits of a single-angle call with h_cos_sza[s].  Bitwise reproducible, whatever ECCKD_RAYLEIGH_GRID bounds the grid to.
+ * The per-block accumulator (3 (nlay+1) x columns of doubles in 58 KB of LDS) is filled in ceil((ng + 1) / columns) launches
+ * per angle where it does not fit (44 columns at nlay = 54), each repeating the transfer.  PARAMETER_ERROR: nsza outside
+ * 1..8, a cos_sza outside (0, 1], an od type that is not 4 or 8, a stride below nwav, nlay above 1 236. */
+int ecckd_lbl_gpoint_fluxes_sw_rayleigh(ecckd_gmap* gmap, int nlay, int nsza, const double* h_cos_sza, const double* d_ssi,
+                                        const double* d_albedo, const void* d_od_abs, int abs_type, size_t abs_stride,
+                                        const void* d_od_ray, int ray_type, size_t ray_stride, double* h_flux_dn_direct,
+                                        double* h_flux_dn, double* h_flux_up, double* h_bb_dn_direct, double* h_bb_dn, double* h_bb_up);
+/* The same kernel's other output: the spectral fluxes themselves, d_flux_dn_direct / d_flux_dn / d_flux_up[nsza][nlay+1]
+ * [flux_stride] FLOAT device rows, and the broadband sums h_bb_*[nsza][nlay+1] (each may be NULL) of the DOUBLE fluxes. */
+int ecckd_lbl_spectral_fluxes_sw_rayleigh(ecckd_ctx* ctx, int nlay, size_t nwav, int nsza, const double* h_cos_sza, const double* d_ssi,
+                                          const double* d_albedo, const void* d_od_abs, int abs_type, size_t abs_stride,
+                                          const void* d_od_ray, int ray_type, size_t ray_stride, float* d_flux_dn_direct,
+                                          float* d_flux_dn, float* d_flux_up, size_t flux_stride, double* h_bb_dn_direct,
+                                          double* h_bb_dn, double* h_bb_up);
 /* LblFluxes::read, lbl_fluxes.cpp:198-230: the square root of the erythemal action spectrum (Webb et al.
  * 2011) averaged over each g point with a 5777 K Planck weight, h_erythemal[ng]; NaN for an empty g point
  * (0/0 as in the reference). */

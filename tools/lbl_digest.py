@@ -1,5 +1,5 @@
 """SHA-256 of everything the line-by-line flux entry points return, at the smallest shapes where each piece of their kernels can
-go wrong (csrc/lbl_fluxes.hip, lbl_gpoint_fluxes.hip, lbl_gpoint_fluxes_sw.hip, lbl_scenarios.hip, lbl_fluxes_sw_rayleigh.hip), and of every band entry with every band empty: a change that is meant to
+go wrong (csrc/lbl_fluxes.hip, lbl_gpoint_fluxes.hip, lbl_gpoint_fluxes_sw.hip, lbl_scenarios.hip, lbl_fluxes_sw_rayleigh.hip, lbl_gpoint_fluxes_sw_rayleigh.hip), and of every band entry with every band empty: a change that is meant to
 leave their arithmetic alone is run once on the build before it and once on the build after it, on the same GPU, and every
 digest has to be equal.  profiles/lbl_digests.json holds the output of the build it was committed with; a ROCm math-library
 update may change digests legitimately, which is why this is a tool and not a test.
@@ -96,6 +96,11 @@ with api.Context(0) as ctx:
             tag = f"{nlay} {nwav} {ng} nsza={nsza} {dtype} albedo={alb is not None}"
             out["gpoint_sw " + tag] = digest(*gm.lbl_fluxes_sw(ANGLES[nsza], ssi, d_od, alb))
             out["spectral_sw " + tag] = digest(*api.lbl_spectral_fluxes_sw(ctx, ANGLES[nsza], ssi, d_od, alb))
+        # Rayleigh scattering per g point and per wavenumber: a float32 Rayleigh spectrum beside the absorber as it is
+        d_ray = dev(syn.optical_depth(np, p, wn, syn.SEED_BASE + 7, nlines=6, column_scale=0.3, lo=250.0, hi=50000.0).astype("float32"))
+        tag = f"{nlay} {nwav} {ng} nsza={nsza} {dtype}"
+        out["gpoint_sw_rayleigh " + tag] = digest(*gm.lbl_fluxes_sw_rayleigh(ANGLES[nsza], ssi, d_od, d_ray, albedo))
+        out["spectral_sw_rayleigh " + tag] = digest(*api.lbl_spectral_fluxes_sw_rayleigh(ctx, ANGLES[nsza], ssi, d_od, d_ray, albedo))
         gm.close()
 
     for nlay, nwav, dtype in BAND_CASES:
