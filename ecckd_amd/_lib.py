@@ -127,6 +127,9 @@ SIGNATURES = {
     "ecckd_opt_timings": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, _c_double_p]),
     "ecckd_opt_forward_ex": (C.c_int, [C.c_void_p, _c_double_p, C.c_int, _c_double_p, _c_double_p]),
     "ecckd_opt_coefficients": (C.c_int, [C.c_void_p, _c_double_p, C.c_int, _c_double_p]),
+    "ecckd_opt_set_rayleigh_prior": (C.c_int, [C.c_void_p, C.c_double]),
+    "ecckd_opt_rayleigh_coefficients": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p]),
+    "ecckd_opt_rayleigh_plan": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ecckd_opt_minimize": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, _c_double_p, C.POINTER(C.c_int),
                                      C.POINTER(C.c_int), _c_double_p, _c_double_p]),
     "ecckd_gmap_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
@@ -345,6 +348,11 @@ class OptConfig(C.Structure):
 class ForwardPlan(C.Structure):
     _fields_ = [("cells", C.c_int), ("nc_template", C.c_int), ("nb", C.c_int), ("threads", C.c_int), ("ngpad", C.c_int),
                 ("lgroups", C.c_int), ("lds_bytes", C.c_size_t)]
+
+
+class RayleighPlan(C.Structure):
+    _fields_ = [("active", C.c_int), ("chunk_rows", C.c_int), ("finish_waves", C.c_int), ("batch", C.c_int),
+                ("nrows", C.c_size_t), ("npart", C.c_size_t)]
 
 
 TRACE_FN = C.CFUNCTYPE(None, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p)

@@ -831,6 +831,7 @@ class GasSW(GasLW):
 
 CONC = {"none": 0, "linear": 1, "lut": 2, "relative-linear": 3}
 OPT_RAYLEIGH_SCATTERING = 1          # ECCKD_OPT_RAYLEIGH_SCATTERING
+OPT_RAYLEIGH_ACTIVE = 2              # ECCKD_OPT_RAYLEIGH_ACTIVE
 
 
 def _f64c(a):
@@ -916,12 +917,16 @@ class Optimizer:
     rayleigh_scattering: the shortwave forward model is the two-stream transfer with Rayleigh scattering
         (ECCKD_OPT_RAYLEIGH_SCATTERING of ecckd_opt_create_ex): flux_dn, spectral_flux_dn_surf and relative_flux_dn are total
         (direct + diffuse) downwelling fluxes, forward() returns (total dn, up), the heating rates come from dn - up.
+    optimize_rayleigh: the ng Rayleigh coefficients are optimised too (ECCKD_OPT_RAYLEIGH_ACTIVE), with either forward model:
+        the state carries ng more elements ln(rayleigh_molar_scattering) behind the gases', without bounds; every gas may be
+        inactive.  rayleigh_prior_error: sigma of their prior 0.5 sum d^2 / sigma^2, gradient included; <= 0: no prior.
     """
 
-    def __init__(self, ctx, model, scenes, rayleigh_scattering=False, **cfg):
+    def __init__(self, ctx, model, scenes, rayleigh_scattering=False, optimize_rayleigh=False, rayleigh_prior_error=0.0, **cfg):
         self.ctx = ctx
         self.lib = ctx.lib
         self.rayleigh_scattering = bool(rayleigh_scattering)
+        self.optimize_rayleigh = bool(optimize_rayleigh)
         keep = []
         m = _opt_model(model, keep)
         sc = (_lib.OptScene * len(scenes))()
@@ -937,8 +942,11 @@ class Optimizer:
             setattr(c, k, float(v))
         h = C.c_void_p()
         check(self.lib.ecckd_opt_create_ex(ctx.handle, C.byref(m), len(scenes), C.cast(sc, C.c_void_p), C.byref(c),
-                                           OPT_RAYLEIGH_SCATTERING if rayleigh_scattering else 0, C.byref(h)))
+                                           (OPT_RAYLEIGH_SCATTERING if rayleigh_scattering else 0) |
+                                           (OPT_RAYLEIGH_ACTIVE if optimize_rayleigh else 0), C.byref(h)))
         self.handle = h
+        if optimize_rayleigh:
+            self.set_rayleigh_prior(rayleigh_prior_error)
         self.nx = int(self.lib.ecckd_opt_nx(h))
         self.ng = m.ng
         self.ncol = sum(int(s.ncol) for s in sc)
@@ -1044,6 +1052,28 @@ class Optimizer:
         xx = np.ascontiguousarray(x, dtype=np.float64)
         check(self.lib.ecckd_opt_coefficients(self.handle, _hptr(xx), int(gas), _hptr(out)))
         return out
+
+    def set_rayleigh_prior(self, prior_error):
+        """sigma of the prior of the optimised Rayleigh coefficients (ecckd_opt_set_rayleigh_prior); <= 0: none.  Refused on a
+        handle made without optimize_rayleigh."""
+        check(self.lib.ecckd_opt_set_rayleigh_prior(self.handle, float(prior_error)))
+
+    def rayleigh_coefficients(self, x=None):
+        """rayleigh_molar_scattering[ng] at state x (ecckd_opt_rayleigh_coefficients): exp of the state's tail as the device forms
+        it for the forward kernels, 0 where pinned;
+        the model's own values for a handle made without optimize_rayleigh, or x = None."""
+        out = np.empty(self.ng)
+        xx = np.ascontiguousarray(x, dtype=np.float64) if x is not None else None
+        check(self.lib.ecckd_opt_rayleigh_coefficients(self.handle, _hptr(xx) if xx is not None else None, _hptr(out)))
+        return out
+
+    def rayleigh_plan(self):
+        """The shape of the reduction behind the Rayleigh gradient elements (ecckd_opt_rayleigh_plan): dict(active, chunk_rows,
+        finish_waves, batch, nrows, npart)."""
+        p = _lib.RayleighPlan()
+        check(self.lib.ecckd_opt_rayleigh_plan(self.handle, C.byref(p)))
+        return dict(active=bool(p.active), chunk_rows=p.chunk_rows, finish_waves=p.finish_waves, batch=p.batch,
+                    nrows=int(p.nrows), npart=int(p.npart))
 
     def minimize(self, max_iterations=100, convergence_criterion=0.02, bounded=True):
         x = np.empty(self.nx)

@@ -11,7 +11,14 @@
 // spectral_boundary_weight / erythemal_weight with "gpointfile": the high-resolution surface / top-of-atmosphere
 // fluxes of the training files are summed per g point on the GPU (ecckd_gmap_sum_rows, lbl_fluxes.cpp:180-246,
 // :300-325); g points stored inside the CKD file take precedence over "gpointfile" (CkdModel::read_g_points).
-// Not handled: rayleigh_prior_error > 0 (Rayleigh scattering as an optimised pseudo-gas).
+// optimize_rayleigh (bool, default 0; not a key of the reference): the ng Rayleigh coefficients are optimised too
+// (ECCKD_OPT_RAYLEIGH_ACTIVE), with or without rayleigh_scattering.  rayleigh_prior_error is then accepted and is the sigma of their
+// prior 0.5 sum (ln k - ln k_first_guess)^2 / sigma^2, whose gradient is included (the reference adds it to the cost and drops
+// the gradient, ckd_model.cpp:869-874); <= 0: no prior.  The elements have no bounds.  Under the key the name "rayleigh" in
+// `gases` is recognised: a list holding only "rayleigh" optimises the Rayleigh coefficients alone (the state the reference
+// reaches at :133-137 from an empty list), any other list its gases plus Rayleigh, no list all gases plus Rayleigh.
+// relative_to is evaluated through a handle without the flag.  Without optimize_rayleigh=1 nothing changes: rayleigh_prior_error
+// > 0 is refused and "rayleigh" in `gases` is a name the model does not have, warned about as before.
 // rayleigh_scattering (bool, default 0; not a key of the reference): the shortwave forward model is the two-stream transfer
 // with Rayleigh scattering (ECCKD_OPT_RAYLEIGH_SCATTERING).  The model needs a Rayleigh coefficient; every training_input and
 // relative_to file must carry the global attribute rayleigh_scattering = "two-stream" that ckdmip_sw --rayleigh writes.  The
@@ -311,7 +318,15 @@ int main(int argc, char** argv) {
     if (config.exist("remove_min_max")) config.read(remove_min_max, "remove_min_max");
     bool rayleigh_scattering = false;
     if (config.exist("rayleigh_scattering")) config.read(rayleigh_scattering, "rayleigh_scattering");
-    if (rayleigh_prior_error > 0.0) fail(ECCKD_PARAMETER_ERROR, "rayleigh_prior_error > 0 (optimised Rayleigh scattering) is not supported by this tool");
+    bool key_optimize_rayleigh = false;
+    if (config.exist("optimize_rayleigh")) config.read(key_optimize_rayleigh, "optimize_rayleigh");
+    if (rayleigh_prior_error > 0.0 && !key_optimize_rayleigh)
+      fail(ECCKD_PARAMETER_ERROR, "rayleigh_prior_error > 0 (optimised Rayleigh scattering) is not supported by this tool without optimize_rayleigh=1");
+    const bool optimize_rayleigh = key_optimize_rayleigh;
+    const bool rayleigh_listed = optimize_rayleigh && std::find(gas_list.begin(), gas_list.end(), "rayleigh") != gas_list.end();
+    // a list holding only "rayleigh": no gas is active (the name matches none); the relative-to handle, made without the flag,
+    // then takes every gas, as it would from no list
+    const bool only_rayleigh = rayleigh_listed && gas_list.size() == 1;
     std::vector<int> band_mapping;
     if (config.exist("band_mapping")) config.read(band_mapping, "band_mapping");
 
@@ -321,9 +336,15 @@ int main(int argc, char** argv) {
     if (rayleigh_scattering && !(model.is_sw && !model.rayleigh_molar_scattering.empty()))
       fail(ECCKD_PARAMETER_ERROR, "rayleigh_scattering=1 needs a shortwave CKD model with a Rayleigh coefficient, %s is not one", input.c_str());
     if (rayleigh_scattering) LOG("Rayleigh scattering is modelled (two-stream): max_no_rayleigh_wavenumber = %g is ignored, no band is masked\n", max_no_rayleigh_wavenumber);
+    if (optimize_rayleigh && !(model.is_sw && !model.rayleigh_molar_scattering.empty()))
+      fail(ECCKD_PARAMETER_ERROR, "optimize_rayleigh=1 needs a shortwave CKD model with a Rayleigh coefficient, %s is not one", input.c_str());
+    if (optimize_rayleigh) {
+      if (rayleigh_prior_error > 0.0) LOG("Optimizing Rayleigh scattering coefficients with prior error of %g\n", rayleigh_prior_error);
+      else LOG("Optimizing Rayleigh scattering coefficients without a prior\n");
+    }
     const unsigned opt_flags = rayleigh_scattering ? ECCKD_OPT_RAYLEIGH_SCATTERING : 0u;
     for (const std::string& g : gas_list) {
-      bool found = false;
+      bool found = optimize_rayleigh && g == "rayleigh";
       for (const GasTable& t : model.gases) found = found || t.name == g;
       if (!found) WARN("gas \"%s\" is not in %s", g.c_str(), input.c_str());
     }
@@ -388,7 +409,7 @@ int main(int argc, char** argv) {
       LOG("Fluxes will be fitted relative to those of %s\n", relative_to_file.c_str());
       rel = load(relative_to_file);
       ModelView mv;
-      make_model(model, gas_list, rel.iband_per_g, mv);
+      make_model(model, only_rayleigh ? std::vector<std::string>() : gas_list, rel.iband_per_g, mv);
       ecckd_opt_scene sv = scene_view(rel);
       ecckd_opt* ro = nullptr;
       ck(ecckd_opt_create_ex(dev.ctx(), &mv.m, 1, &sv, &oc, opt_flags, &ro));
@@ -424,7 +445,8 @@ int main(int argc, char** argv) {
     std::vector<ecckd_opt_scene> views;
     for (const Scene& s : scenes) views.push_back(scene_view(s));
     ecckd_opt* opt = nullptr;
-    ck(ecckd_opt_create_ex(dev.ctx(), &mv.m, (int)views.size(), views.data(), &oc, opt_flags, &opt));
+    ck(ecckd_opt_create_ex(dev.ctx(), &mv.m, (int)views.size(), views.data(), &oc, opt_flags | (optimize_rayleigh ? ECCKD_OPT_RAYLEIGH_ACTIVE : 0u), &opt));
+    if (optimize_rayleigh) ck(ecckd_opt_set_rayleigh_prior(opt, rayleigh_prior_error));
     const size_t nx = ecckd_opt_nx(opt);
     LOG("Optimizing %zu coefficients against %zu training file(s)\n", nx, scenes.size());
     std::vector<double> x(nx);
@@ -442,6 +464,7 @@ int main(int argc, char** argv) {
     LOG("Minimizer status: %s after %d iterations, cost function %g, gradient norm %g\n",
         status >= 0 && status < 9 ? status_str[status] : "unknown", niter, J, gnorm);
     for (size_t i = 0; i < model.gases.size(); ++i) ck(ecckd_opt_coefficients(opt, x.data(), (int)i, model.gases[i].molar_abs.data()));
+    if (optimize_rayleigh) ck(ecckd_opt_rayleigh_coefficients(opt, x.data(), model.rayleigh_molar_scattering.data()));
     {
       double t_min = 0.0, t_prior = 0.0, t_rt = 0.0;   // Timer::print (Timer.h:59-69)
       ck(ecckd_opt_timings(opt, &t_min, &t_prior, &t_rt));

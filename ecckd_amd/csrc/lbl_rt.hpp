@@ -143,17 +143,23 @@ __device__ __forceinline__ void rayleigh_direct_d(double w, double dw, double k,
 // optimiser's adjoint, optimize.hip): the w = 0 branch, the clamp of k (dk = 0 where it is active), the resonance interpolation
 // (mu_a, mu_b and x move with k) and the two clamps of Rdir / Tdd - zero below 0, and the derivative of the bound 1 - Tdir
 // (- Rdir) where that is the active one.  The values themselves are rayleigh_layer's: the caller takes them from there.
-__device__ __forceinline__ RayleighLayer rayleigh_layer_d(double tau_abs, double tau_ray, double mu0, double minus_sec_sza) {
+// WRT_RAY: d / d tau_ray at fixed tau_abs instead (the optimised Rayleigh coefficients, ECCKD_OPT_RAYLEIGH_ACTIVE).  With
+// tau = tau_abs + tau_ray and w = tau_ray / tau both partial derivatives move tau with seed 1, so they differ in ONE seed only,
+// dw = (1 - w) / tau in place of -w / tau; every other line is common.  The no-scattering branch tau_ray <= 0 belongs to a
+// pinned element, whose gradient is 0 by definition: all five terms are 0 there.
+template <bool WRT_RAY>
+__device__ __forceinline__ RayleighLayer rayleigh_layer_dx(double tau_abs, double tau_ray, double mu0, double minus_sec_sza) {
   RayleighLayer d;
   const double tau = tau_abs + tau_ray;
   const double Tdir = exp(minus_sec_sza * tau);
   d.Tdir = minus_sec_sza * Tdir;
   if (!(tau_ray > 0.0 && tau > 0.0)) {
-    d.R = 0.0; d.T = -2.0 * exp(-2.0 * tau); d.Rdir = 0.0; d.Tdd = 0.0;
+    if constexpr (WRT_RAY) { d.R = 0.0; d.T = 0.0; d.Tdir = 0.0; d.Rdir = 0.0; d.Tdd = 0.0; }
+    else { d.R = 0.0; d.T = -2.0 * exp(-2.0 * tau); d.Rdir = 0.0; d.Tdd = 0.0; }
     return d;
   }
   const double g3 = 0.5, g4 = 0.5;
-  const double w = tau_ray / tau, dw = -w / tau;
+  const double w = tau_ray / tau, dw = WRT_RAY ? (1.0 - w) / tau : -w / tau;
   const double g1 = 2.0 - 1.25 * w, g2 = 0.75 * w, dg1 = -1.25 * dw, dg2 = 0.75 * dw;
   const double a1 = g1 * g4 + g2 * g3, da1 = dg1 * g4 + dg2 * g3;
   const double a2 = g1 * g3 + g2 * g4, da2 = dg1 * g3 + dg2 * g4;
@@ -186,6 +192,14 @@ __device__ __forceinline__ RayleighLayer rayleigh_layer_d(double tau_abs, double
   d.Rdir = rdir < 0.0 ? 0.0 : (rdir > 1.0 - Tdir ? -d.Tdir : drdir);
   d.Tdd = tdd < 0.0 ? 0.0 : (tdd > 1.0 - Tdir - Rdir ? -d.Tdir - d.Rdir : dtdd);
   return d;
+}
+
+__device__ __forceinline__ RayleighLayer rayleigh_layer_d(double tau_abs, double tau_ray, double mu0, double minus_sec_sza) {
+  return rayleigh_layer_dx<false>(tau_abs, tau_ray, mu0, minus_sec_sza);
+}
+
+__device__ __forceinline__ RayleighLayer rayleigh_layer_dray(double tau_abs, double tau_ray, double mu0, double minus_sec_sza) {
+  return rayleigh_layer_dx<true>(tau_abs, tau_ray, mu0, minus_sec_sza);
 }
 
 // adding, upwards: the albedo A and the source S (the upwelling flux the direct beam alone causes) seen from the layer's top

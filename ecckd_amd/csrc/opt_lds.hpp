@@ -33,7 +33,8 @@ constexpr Layout<CL_COUNT> cells(int nlay, int ng, int nband, bool sw) {
 }
 
 // k_opt_forward_adjoint_rayleigh: bdn, bup, gdn, gup [nhl][nband] | r [nlay][nband] | rsum [nlay] | sd, su [nhl] | red [16] |
-// int bp [nband + 1] | int bg [ng]
+// int bp [nband + 1] | int bg [ng]   (its <true> instance, the optimised Rayleigh coefficients, puts one double per thread
+// behind this layout, from the next multiple of 8 bytes: ray_lds_offset and ray_lds_bytes of optimize.hip)
 enum RayleighArray { RL_BDN, RL_BUP, RL_GDN, RL_GUP, RL_R, RL_RSUM, RL_SD, RL_SU, RL_RED, RL_BP, RL_BG, RL_COUNT };
 constexpr Layout<RL_COUNT> rayleigh(int nlay, int ng, int nband) {
   const size_t d = sizeof(double), nhl = (size_t)nlay + 1, band = nhl * nband * d;

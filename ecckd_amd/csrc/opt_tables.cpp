@@ -107,7 +107,8 @@ AxisPos axis_pos(double index0, int n) {
 
 }  // namespace
 
-int check_arguments(const ecckd_opt_model* m, int nscene, const ecckd_opt_scene* scenes, const ecckd_opt_config* cfg, std::string& err) {
+int check_arguments(const ecckd_opt_model* m, int nscene, const ecckd_opt_scene* scenes, const ecckd_opt_config* cfg, std::string& err,
+                    bool rayleigh_active) {
   if (!(m && scenes && cfg && nscene > 0)) return refuse(err, "ecckd_opt_create: NULL/empty argument");
   if (!(m->ng > 0 && m->ng <= 1024 && m->nt >= 2 && m->np >= 2 && m->ngas > 0 && m->gases && m->log_pressure && m->temperature &&
         m->iband_per_g))
@@ -117,7 +118,9 @@ int check_arguments(const ecckd_opt_model* m, int nscene, const ecckd_opt_scene*
     return refuse(err, "ecckd_opt_create: Planck look-up table missing");
   if (m->logarithmic_interpolation)
     return refuse(err, "ecckd_opt_create: logarithmic LUT interpolation is not supported (ckd_model.h:359 default is linear)");
-  size_t nx = 0, nk = has_rayleigh(m) ? m->ng : 0;
+  if (rayleigh_active && !has_rayleigh(m))
+    return refuse(err, "ecckd_opt_create_ex: ECCKD_OPT_RAYLEIGH_ACTIVE needs a shortwave model with rayleigh_molar_scattering");
+  size_t nx = rayleigh_active ? m->ng : 0, nk = has_rayleigh(m) ? m->ng : 0;
   for (int i : gas_order(m)) {
     const ecckd_opt_gas& ug = m->gases[i];
     if (!(ug.conc_dependence >= 0 && ug.conc_dependence <= 3) || !ug.molar_abs ||
@@ -148,8 +151,17 @@ void order_gases(const ecckd_opt_model* m, Tables& t) {
   t.order = gas_order(m);
   t.user_to_k.assign(m->ngas, -1);
   size_t off = 0;
+  bool rayleigh_placed = false;
+  // rayleigh_active: the Rayleigh row directly behind the last active gas, so that x[e] <-> k[e] holds for the whole state
+  auto place_rayleigh = [&] {
+    t.rayleigh_ix = off;
+    off += ng;
+    t.nx = off;
+    rayleigh_placed = true;
+  };
   for (size_t pos = 0; pos < t.order.size(); ++pos) {
     const ecckd_opt_gas& ug = m->gases[t.order[pos]];
+    if (t.rayleigh_active && !rayleigh_placed && !ug.is_active) place_rayleigh();
     GasInfo gi;
     gi.conc = ug.conc_dependence;
     gi.active = ug.is_active != 0;
@@ -164,9 +176,13 @@ void order_gases(const ecckd_opt_model* m, Tables& t) {
     t.gases.push_back(gi);
   }
   // Rayleigh scattering (calc_total_optical_depth, solve_adept.cpp:33-36; ckd_model.h:242-252): a fixed
-  // one-node pseudo gas at the end of the coefficient vector
-  t.rayleigh_ix = off;
-  if (has_rayleigh(m)) off += ng;
+  // one-node pseudo gas at the end of the coefficient vector (rayleigh_active: part of the state, placed above or here)
+  if (t.rayleigh_active) {
+    if (!rayleigh_placed) place_rayleigh();
+  } else {
+    t.rayleigh_ix = off;
+    if (has_rayleigh(m)) off += ng;
+  }
   t.nk = off;
   t.k0.assign(t.nk, 0.0);
   t.kmin.assign(t.nx, 0.0);
@@ -318,6 +334,7 @@ void build_entries(const ecckd_opt_model* m, int nscene, const ecckd_opt_scene* 
   t.nent = nent;
   t.ent_idx.assign(t.ncell * nent, -1);
   t.ent_coef.assign(t.ncell * nent, 0.0);
+  if (t.rayleigh_active) t.moles.assign(t.ncell, 0.0);
   const double log_p_0 = m->log_pressure[0];
   const double d_log_p = m->log_pressure[1] - m->log_pressure[0];
   const double d_t = m->temperature[1 * np + 0] - m->temperature[0];
@@ -380,6 +397,7 @@ void build_entries(const ecckd_opt_model* m, int nscene, const ecckd_opt_scene* 
           // moles of air per unit area in the layer (ckd_model.h:246-247) times the molar scattering
           idx[e] = (int)t.rayleigh_ix;
           coef[e] = (p[l + 1] - p[l]) * MOLES_PER_PA;
+          if (t.rayleigh_active) t.moles[col * nlay + l] = coef[e];
         }
       }
     }
@@ -389,7 +407,9 @@ void build_entries(const ecckd_opt_model* m, int nscene, const ecckd_opt_scene* 
 // transpose of the gather for the active nodes: node -> (cell, coef), in cell order
 void transpose_entries(Tables& t) {
   const int nent = t.nent, ng = t.ng;
-  auto kept = [&](size_t i) { return t.ent_idx[i] >= 0 && (size_t)t.ent_idx[i] < t.nx && t.ent_coef[i] != 0.0; };
+  // (the active gases' part of the state: all of it unless rayleigh_active, whose tail is no node)
+  const size_t nx_gas = t.nnode_active * ng;
+  auto kept = [&](size_t i) { return t.ent_idx[i] >= 0 && (size_t)t.ent_idx[i] < nx_gas && t.ent_coef[i] != 0.0; };
   t.ref_ptr.assign(t.nnode_active + 1, 0);
   for (size_t i = 0; i < t.ncell * nent; ++i)
     if (kept(i)) ++t.ref_ptr[(size_t)t.ent_idx[i] / ng + 1];
@@ -532,7 +552,7 @@ void gather_relative_fluxes(int nscene, const ecckd_opt_scene* scenes, Tables& t
 
 int build_tables(const ecckd_opt_model* m, int nscene, const ecckd_opt_scene* scenes, const ecckd_opt_config* cfg,
                  const Schedule& s, Tables& t, std::string& err) {
-  const int rc = check_arguments(m, nscene, scenes, cfg, err);
+  const int rc = check_arguments(m, nscene, scenes, cfg, err, t.rayleigh_active);
   if (rc != ECCKD_OK) return rc;
   order_gases(m, t);
   cap_relative_linear(cfg->cap_relative_linear, t);

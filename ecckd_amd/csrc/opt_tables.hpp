@@ -43,6 +43,10 @@ struct Layout {
   bool scattering = false;          // ECCKD_OPT_RAYLEIGH_SCATTERING, set by the caller of build_tables: the two-stream transfer with
                                     // Rayleigh scattering between optical depth and fluxes; the heating rates come from the net flux
   int ray_ent = -1;                 // entry index of the Rayleigh pseudo gas
+  bool rayleigh_active = false;     // ECCKD_OPT_RAYLEIGH_ACTIVE, set by the caller of build_tables: the Rayleigh row sits directly behind
+                                    // the active gases in k and its ng elements x = ln k_ray are the tail of the state (nx grows by ng);
+                                    // no bounds (kmin = kmax = 0 there), not a node of the prior's stencil or of K8b
+  size_t rayleigh_ix = 0;           // offset of the Rayleigh pseudo gas in k (ray_ent >= 0)
   int grad_nchunk = 1;              // 64-g chunks of a row
   std::vector<GasInfo> gases;       // in k order: active gases first
   std::vector<int> order;           // position in `gases` -> user gas index
@@ -52,7 +56,6 @@ struct Layout {
 
 // Everything ecckd_opt_create uploads, in the layouts the kernels read.
 struct Tables : Layout {
-  size_t rayleigh_ix = 0;           // offset of the Rayleigh pseudo gas in k (ray_ent >= 0)
   // prior
   std::vector<double> tri;          // per active gas: lo | di | up of the concentration, temperature and pressure AR(1) inverses
   std::vector<int> tri_off, gas_dims;   // [ngas] offset into tri; [ngas][4] nconc, nt, np, first node
@@ -72,6 +75,8 @@ struct Tables : Layout {
   std::vector<double> st_w;
   // g points by band
   std::vector<int> band, band_ptr, band_g;
+  // rayleigh_active: moles of air per unit area of every cell [ncell], the weight of dJ/dtau in dJ/dk_ray
+  std::vector<double> moles;
 };
 
 // K8b's constants (optimize.hip) and the ECCKD_K8B_PLAIN_ORDER knob
@@ -79,7 +84,8 @@ struct Schedule { int waves = 4, run = 64; bool plain_order = false; };
 
 // The steps, in the order they run; each reads what the ones before left in `t`.  check_arguments returns ECCKD_OK, or
 // ECCKD_PARAMETER_ERROR with the refusal in `err`; the others assume arguments that passed it.
-int check_arguments(const ecckd_opt_model* m, int nscene, const ecckd_opt_scene* scenes, const ecckd_opt_config* cfg, std::string& err);
+int check_arguments(const ecckd_opt_model* m, int nscene, const ecckd_opt_scene* scenes, const ecckd_opt_config* cfg, std::string& err,
+                    bool rayleigh_active = false);
 void order_gases(const ecckd_opt_model* m, Tables& t);              // gas order, sizes and the coefficient vector
 void cap_relative_linear(double cap_fraction, Tables& t);
 void build_prior(const ecckd_opt_config& cfg, Tables& t);           // AR(1) inverses, sigma, the active nodes

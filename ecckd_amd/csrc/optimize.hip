@@ -1125,10 +1125,23 @@ __device__ __forceinline__ void rayleigh_adjoint_sweeps(int nlay, int ng, int nb
   }
 }
 
+// RAY_ACTIVE (ECCKD_OPT_RAYLEIGH_ACTIVE on a scattering handle): the kernel also leaves dJ/dk_ray per (column, g).  Phase A
+// stores d/dtau_ray of the five layer terms (rayleigh_layer_dray) in five more slots of the workspace, RS_RAY_D ..., as the
+// d/dtau_abs terms are stored - they are NOT zeroed in clamped cells: the clamp acts on the gases alone; phase E2 forms
+//   dJ/dtau_ray = Rb R* + Tb T* + Tdirb Tdir* + Rdirb Rdir* + Tddb Tdd*          (* = d/dtau_ray at fixed tau_abs)
+// of every cell, each thread adds moles_l dJ/dtau_ray over its own layers in ascending l, and the layer groups are added in
+// group order through LDS (blockDim doubles behind the layout of lds::rayleigh) to ray_part[column][g], which sits behind the
+// ncol columns of the workspace: no further kernel argument, and the <false> instance is the kernel it has always been.
+constexpr int RS_RAY_D = RS_COUNT;                 // dR, dT, dTdir, dRdir, dTdd / dtau_ray
+constexpr int RS_COUNT_ACTIVE = RS_COUNT + 5;
+constexpr size_t ray_lds_offset(size_t layout_bytes) { return (layout_bytes + 7) / 8 * 8; }
+
+template <bool RAY_ACTIVE>
 __global__ void __launch_bounds__(512)
 k_opt_forward_adjoint_rayleigh(const K8aArgs a, const int* __restrict__ band_ptr /*[nband+1]*/, const int* __restrict__ band_g /*[ng]: g points by band*/,
-                               double* ws /*[ncol][RS_COUNT][nlay+1][ng]*/) {
+                               double* ws /*[ncol][NSLOT][nlay+1][ng], RAY_ACTIVE: then ray_part[ncol][ng]*/) {
   extern __shared__ double smem[];
+  constexpr int NSLOT = RAY_ACTIVE ? RS_COUNT_ACTIVE : RS_COUNT;
   const int nlay = a.nlay, ng = a.ng, ngpad = a.ngpad, nband = a.nband, nent = a.nent, ray_ent = a.ray_ent;
   const int nhl = nlay + 1;
   const auto layout = lds::rayleigh(nlay, ng, nband);
@@ -1155,7 +1168,7 @@ k_opt_forward_adjoint_rayleigh(const K8aArgs a, const int* __restrict__ band_ptr
   const double* pl = a.planck_hl + (size_t)col * nhl * ng;      // row 0: the scaled solar irradiance
   const size_t cell0 = (size_t)col * nlay;
   const size_t slot = (size_t)nhl * ng;
-  double* w = ws + (size_t)col * RS_COUNT * slot + gl;           // slot q of this g point: w + q * slot, rows ng apart
+  double* w = ws + (size_t)col * NSLOT * slot + gl;              // slot q of this g point: w + q * slot, rows ng apart
   bool all_pos = true;
   for (int b = 0; b < nband; ++b) all_pos = all_pos && albedo[(size_t)col * nband + b] > 0.0;
   const double cos_sza = a.mu0[col];
@@ -1184,6 +1197,12 @@ k_opt_forward_adjoint_rayleigh(const K8aArgs a, const int* __restrict__ band_ptr
       wl[RS_R * slot] = L.R; wl[RS_T * slot] = L.T; wl[RS_TDIR * slot] = L.Tdir; wl[RS_RDIR * slot] = L.Rdir; wl[RS_TDD * slot] = L.Tdd;
       wl[RS_DR * slot] = clamped ? 0.0 : dL.R; wl[RS_DT * slot] = clamped ? 0.0 : dL.T; wl[RS_DTDIR * slot] = clamped ? 0.0 : dL.Tdir;
       wl[RS_DRDIR * slot] = clamped ? 0.0 : dL.Rdir; wl[RS_DTDD * slot] = clamped ? 0.0 : dL.Tdd;
+      if constexpr (RAY_ACTIVE) {
+        // (a clamped cell keeps these: tau is tau_ray there, w = 1 and the seed of w is 0)
+        const ecckd::lbl::RayleighLayer rL = ecckd::lbl::rayleigh_layer_dray(tau, tau_ray, cos_sza, minus_sec_sza);
+        wl[(RS_RAY_D + 0) * slot] = rL.R; wl[(RS_RAY_D + 1) * slot] = rL.T; wl[(RS_RAY_D + 2) * slot] = rL.Tdir;
+        wl[(RS_RAY_D + 3) * slot] = rL.Rdir; wl[(RS_RAY_D + 4) * slot] = rL.Tdd;
+      }
     }
   }
   __syncthreads();
@@ -1193,7 +1212,7 @@ k_opt_forward_adjoint_rayleigh(const K8aArgs a, const int* __restrict__ band_ptr
     rayleigh_forward_sweeps(nlay, ng, cos_sza * pl[g], alb, w + RS_R * slot, w + RS_T * slot, w + RS_TDIR * slot, w + RS_RDIR * slot,
                             w + RS_TDD * slot, w + RS_D * slot, w + RS_A * slot, w + RS_S * slot, w + RS_V * slot, w + RS_U * slot);
   __syncthreads();
-  const double* wc = ws + (size_t)col * RS_COUNT * slot;         // the column's slots, any g
+  const double* wc = ws + (size_t)col * NSLOT * slot;            // the column's slots, any g
   const RayleighFlux flux = {wc, slot, ng};
   if (a.flux_out && in_range) {
     double* fo = a.flux_out + (size_t)col * 2 * nhl * ng;
@@ -1231,6 +1250,7 @@ k_opt_forward_adjoint_rayleigh(const K8aArgs a, const int* __restrict__ band_ptr
   }
   __syncthreads();
   // ---- E2: dJ/dtau_abs of the cells of this thread, the five terms in a fixed order ----
+  double ray_bar = 0.0;                                          // RAY_ACTIVE: sum over this thread's layers of moles_l dJ/dtau_ray
   if (in_range) {
     for (int l = lgrp; l < nlay; l += nlgrp) {
       const double* wl = w + (size_t)l * ng;
@@ -1238,6 +1258,23 @@ k_opt_forward_adjoint_rayleigh(const K8aArgs a, const int* __restrict__ band_ptr
                              wl[RS_TDIRB * slot] * wl[RS_DTDIR * slot] + wl[RS_RDIRB * slot] * wl[RS_DRDIR * slot] +
                              wl[RS_TDDB * slot] * wl[RS_DTDD * slot];
       dtau[(cell0 + l) * ng + g] += tau_bar;
+      if constexpr (RAY_ACTIVE) {
+        const double tau_ray_bar = wl[RS_RB * slot] * wl[(RS_RAY_D + 0) * slot] + wl[RS_TB * slot] * wl[(RS_RAY_D + 1) * slot] +
+                                   wl[RS_TDIRB * slot] * wl[(RS_RAY_D + 2) * slot] + wl[RS_RDIRB * slot] * wl[(RS_RAY_D + 3) * slot] +
+                                   wl[RS_TDDB * slot] * wl[(RS_RAY_D + 4) * slot];
+        ray_bar += ent_coef[(cell0 + l) * nent + ray_ent] * tau_ray_bar;        // the entry's coefficient: moles of air in the layer
+      }
+    }
+  }
+  if constexpr (RAY_ACTIVE) {
+    // the layer groups of a g point in group order: thread (lgrp, g) sits at lgrp * ngpad + g = threadIdx.x
+    double* s_ray = (double*)((char*)smem + ray_lds_offset(layout.bytes()));      // [blockDim.x]
+    s_ray[threadIdx.x] = ray_bar;
+    __syncthreads();
+    if (live) {
+      double t = 0.0;
+      for (int q = 0; q < nlgrp; ++q) t += s_ray[q * ngpad + g];
+      ws[(size_t)gridDim.x * NSLOT * slot + (size_t)col * ng + g] = t;
     }
   }
   jpart += a.negative_od_penalty * penalty;
@@ -1371,6 +1408,137 @@ k_opt_gradient_finish(int nslot /*entries of node_order*/, int ng, int nchunk /*
     for (int off = 32; off > 0; off >>= 1) jb += __shfl_down(jb, off, 64);
     if (lane == 0) jb_part[ordered] = jb;
   }
+}
+
+// ---- the ng gradient elements of the optimised Rayleigh coefficients (ECCKD_OPT_RAYLEIGH_ACTIVE) ----
+//   dJ/dk_ray[g] = sum over the rows r of wgt[r] * src[r][g]
+// plain handle: rows = cells, src = dJ/dtau as the K8a kernels leave it (Rayleigh is one more absorber before the clamp, so a
+// clamped cell's penalty derivative counts), wgt = moles of air of the cell; scattering handle: rows = columns, src = what
+// k_opt_forward_adjoint_rayleigh<true> leaves per (column, g), no weights.  Two launches, every sum in a fixed order, no atomics:
+//   k_opt_rayleigh_reduce: a wave per (RAY_CHUNK consecutive rows, 64 g points) adds its rows in row order - whole 512-byte
+//     rows at ng = 64, RAY_BATCH loads in flight, the weights one per lane and handed round as scalars -> part[chunk][g];
+//   k_opt_rayleigh_finish: a block of RAY_FIN_WAVES waves per 64 g points; wave w adds the partials [w per, (w + 1) per) in
+//     order, per = ceil(npart / RAY_FIN_WAVES), RAY_BATCH loads in flight per round; wave 0 adds the waves' sums in wave order,
+//     then per element: chain rule x = ln k, the prior d / sigma^2 (d = x - x_prior), 0 for a pinned element, the 1e-80 rule
+//     (solve_adept.cpp:286), and the chunk's share 0.5 sum d^2 / sigma^2 of J_b into its slot behind the nodes' shares, where
+//     k_opt_sum_cost finds it.
+// About 1 000 partials at 64 000 cells: 63 per finishing wave, 8 rounds of 8 loads - not 1 000 in a row on one wave.
+// Both levels add in double-double (two_sum: the rounding error of every addition is kept in a second word, which travels with
+// the partials), so the sum of the rows is the correctly rounded one but for ties: a scene whose columns are repeated K = 2^n
+// times gives K times the gradient of the scene itself, which a plain sum of 10^4 rows misses by several units in the last
+// place (tests/test_optimize_rayleigh_active_gpu.py::test_many_rows).  The kernels are bound by their loads; the extra five
+// additions per row do not show.
+// two_sum is exact only in IEEE arithmetic as written: under -ffast-math (or any option that lets the compiler reassociate) the
+// error word (hi - (s - b)) + (v - b) folds to 0 and the sums silently fall back to plain ones.  The build does not enable it
+// (HIP_COMPILE_FLAGS of __graft_entry__.py, HIPFLAGS of the Makefile); a build that does is refused here.
+#if defined(__FAST_MATH__) || defined(__ASSOCIATIVE_MATH__)
+#error "optimize.hip: two_sum needs IEEE floating-point arithmetic without reassociation (no -ffast-math)"
+#endif
+__device__ __forceinline__ void two_sum(double& hi, double& lo, double v) {
+  const double s = hi + v;
+  const double b = s - hi;
+  lo += (hi - (s - b)) + (v - b);
+  hi = s;
+}
+constexpr int RAY_CHUNK = 64;        // rows per first-level wave
+constexpr int RAY_FIN_WAVES = 16;    // waves of the finishing block
+constexpr int RAY_BATCH = 8;         // loads in flight per wave
+constexpr int RAY_RED_WAVES = 4;     // waves per block of the first level
+
+__global__ void __launch_bounds__(64 * RAY_RED_WAVES)
+k_opt_rayleigh_reduce(size_t nrows, int ng, int nchunk /*64-g chunks of a row*/, const double* __restrict__ src /*[nrows][ng]*/,
+                      const double* __restrict__ wgt /*[nrows] or NULL = 1*/, double* __restrict__ part /*[2: sum, error word][ceil(nrows / RAY_CHUNK)][nchunk][64]*/) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const size_t ntask = (nrows + RAY_CHUNK - 1) / RAY_CHUNK * nchunk;
+  const size_t task = (size_t)blockIdx.x * RAY_RED_WAVES + wave;
+  if (task >= ntask) return;
+  const size_t rc = task / nchunk;
+  const int g = (int)(task % nchunk) * 64 + lane;
+  const int gl = g < ng ? g : 0;                           // lanes beyond the last g point read (and their sums are never read) the first one's
+  const size_t r0 = rc * RAY_CHUNK;
+  const int cnt = (int)min((size_t)RAY_CHUNK, nrows - r0);   // >= 1
+  const double my_w = lane < cnt ? (wgt ? wgt[r0 + lane] : 1.0) : 0.0;
+  double acc = 0.0, err = 0.0;
+  for (int q0 = 0; q0 < cnt; q0 += RAY_BATCH) {
+    double v[RAY_BATCH], w[RAY_BATCH];
+#pragma unroll
+    for (int q = 0; q < RAY_BATCH; ++q) {
+      v[q] = src[(r0 + min(q0 + q, cnt - 1)) * ng + gl];  // past the end: the last row again, dropped below
+      w[q] = readlane_f64(my_w, (q0 + q) & 63);
+    }
+#pragma unroll
+    for (int q = 0; q < RAY_BATCH; ++q) {
+      double term;
+      {
+#pragma clang fp contract(off)       // the term is rounded once, before two_sum: fused into its first addition it would be two numbers
+        term = w[q] * v[q];
+      }
+      two_sum(acc, err, q0 + q < cnt ? term : 0.0);
+    }
+  }
+  part[task * 64 + lane] = acc;
+  part[(ntask + task) * 64 + lane] = err;
+}
+
+__global__ void __launch_bounds__(64 * RAY_FIN_WAVES)
+k_opt_rayleigh_finish(size_t npart, int ng, int nchunk, const double* __restrict__ part /*[2][npart][nchunk][64]*/, size_t e0 /*first Rayleigh element of x, k, grad*/,
+                      const double* __restrict__ x, const double* __restrict__ x_prior, const double* __restrict__ k,
+                      double inv_sigma2, int have_prior, double* __restrict__ grad, double* __restrict__ jb_part /*[nchunk]*/) {
+  __shared__ double s_sum[2][RAY_FIN_WAVES][64];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int chunk = blockIdx.x;
+  const size_t per = (npart + RAY_FIN_WAVES - 1) / RAY_FIN_WAVES;
+  const size_t p0 = min(npart, wave * per), p1 = min(npart, p0 + per);
+  const double* part_err = part + npart * nchunk * 64;
+  double acc = 0.0, err = 0.0;
+  for (size_t t = p0; t < p1; t += RAY_BATCH) {
+    double v[RAY_BATCH], ve[RAY_BATCH];
+#pragma unroll
+    for (int q = 0; q < RAY_BATCH; ++q) {
+      const size_t at = (min(t + q, p1 - 1) * nchunk + chunk) * 64 + lane;
+      v[q] = part[at];
+      ve[q] = part_err[at];
+    }
+#pragma unroll
+    for (int q = 0; q < RAY_BATCH; ++q) {
+      two_sum(acc, err, t + q < p1 ? v[q] : 0.0);
+      err += t + q < p1 ? ve[q] : 0.0;
+    }
+  }
+  s_sum[0][wave][lane] = acc;
+  s_sum[1][wave][lane] = err;
+  __syncthreads();
+  if (wave != 0) return;
+  double gk_hi = 0.0, gk_lo = 0.0;
+#pragma unroll
+  for (int w = 0; w < RAY_FIN_WAVES; ++w) {
+    two_sum(gk_hi, gk_lo, s_sum[0][w][lane]);
+    gk_lo += s_sum[1][w][lane];
+  }
+  const double gk = gk_hi + gk_lo;
+  const int g = chunk * 64 + lane;
+  double jb = 0.0;
+  if (g < ng) {
+    const size_t e = e0 + g;
+    const double xv = x[e];
+    double gx = 0.0;
+    if (xv > MIN_X) {
+      gx = gk * k[e];                                            // dJ/dx = dJ/dk * k (:276-283)
+      if (have_prior) {
+        const double d = xv - x_prior[e];
+        const double gb = d * inv_sigma2;
+        gx += gb;
+        jb = 0.5 * d * gb;
+      }
+      if (fabs(gx) < 1.0e-80) gx = 0.0;  // :286
+    }
+    grad[e] = gx;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) jb += __shfl_down(jb, off, 64);
+  if (lane == 0) jb_part[chunk] = jb;
 }
 
 // k = exp(x) for the active part (:242-249)
@@ -1660,6 +1828,12 @@ struct ecckd_opt : ot::Layout {
   double* d_rel = nullptr;   // relative-to CKD fluxes [ncol][2][nhl][ng]
   double* d_ray_ws = nullptr;   // scattering handles: the per-(level, g) state of k_opt_forward_adjoint_rayleigh [ncol][RS_COUNT][nhl][ng]
   double* d_mu0 = nullptr;
+  // ECCKD_OPT_RAYLEIGH_ACTIVE: the cells' moles of air (plain handle: the weights of dJ/dtau), the first-level partials of the
+  // Rayleigh reduction, and the prior error of the ng tail elements (<= 0: no prior term on them)
+  double* d_moles = nullptr;
+  double* d_ray_part = nullptr;
+  double* d_ray_exp = nullptr;          // [2][ng] ecckd_opt_rayleigh_coefficients: the state's tail and its exp
+  double ray_prior_error = 0.0;
   double *d_k = nullptr, *d_x = nullptr, *d_xprior = nullptr, *d_grad = nullptr, *d_dtau = nullptr;
   double *d_jcol = nullptr, *d_jb = nullptr;
   int* d_ent_idx = nullptr; double* d_ent_coef = nullptr; int* d_band = nullptr;
@@ -1734,11 +1908,28 @@ int opt_upload_tables(ecckd_opt* o, const ot::Tables& t) {
   up(&o->d_hr, t.hr); up(&o->d_fdn, t.fdn); up(&o->d_fup, t.fup);
   if (o->have_boundary) { up(&o->d_sfds, t.sfds); up(&o->d_sfut, t.sfut); }
   if (o->do_sw) up(&o->d_mu0, t.mu0);
+  if (o->rayleigh_active && !o->scattering) up(&o->d_moles, t.moles);
   if (!t.rel.empty()) up(&o->d_rel, t.rel);
   up(&o->d_ref_ptr, t.ref_ptr); up(&o->d_ref_cell, t.ref_cell); up(&o->d_ref_coef, t.ref_coef); up(&o->d_node_order, t.node_order);
   up(&o->d_run_order, t.run_order); up(&o->d_run_r0, t.run_r0); up(&o->d_run_last, t.run_last); up(&o->d_node_run0, t.node_run0);
   up(&o->d_node_gas, t.node_gas); up(&o->d_st_nb, t.st_nb); up(&o->d_st_w, t.st_w); up(&o->d_inv_sigma2, t.inv_sigma2);
   return rc;
+}
+
+// The Rayleigh reduction of a handle with ECCKD_OPT_RAYLEIGH_ACTIVE: its rows (plain: cells, scattering: columns) and its
+// first-level partials; and the shares of J_b that k_opt_sum_cost adds: the nodes' and, behind them, the Rayleigh chunks'.
+size_t ray_nrows(const ecckd_opt* o) { return o->scattering ? o->ncol : o->ncell; }
+size_t ray_npart(const ecckd_opt* o) { return (ray_nrows(o) + RAY_CHUNK - 1) / RAY_CHUNK; }
+size_t opt_njb(const ecckd_opt* o) { return (o->nnode_active + (o->rayleigh_active ? 1 : 0)) * (size_t)o->grad_nchunk; }
+// (slots per column of the scattering workspace, and the doubles of the per-(column, g) sums behind the columns)
+size_t ray_ws_doubles(const ecckd_opt* o) {
+  const size_t slot = (size_t)(o->nlay + 1) * o->ng;
+  return o->ncol * (o->rayleigh_active ? RS_COUNT_ACTIVE : RS_COUNT) * slot + (o->rayleigh_active ? o->ncol * (size_t)o->ng : 0);
+}
+// dynamic LDS of the scattering kernel: the band and cost arrays; <true>: one double per thread behind them
+size_t ray_lds_bytes(const ecckd_opt* o, int threads) {
+  const size_t bytes = lds::rayleigh(o->nlay, o->ng, o->nband).bytes();
+  return o->rayleigh_active ? ray_lds_offset(bytes) + (size_t)threads * sizeof(double) : bytes;
 }
 
 // the launch sizes of K8b and of the element-wise kernels, the work buffers and the pinned slots
@@ -1757,7 +1948,9 @@ int opt_alloc_work(ecckd_opt* o, const ot::Tables& t) {
   if (o->alloc(&o->d_x, o->nx) != hipSuccess || o->alloc(&o->d_xprior, o->nx) != hipSuccess ||
       o->alloc(&o->d_grad, o->nx + 1) != hipSuccess || o->alloc(&o->d_dtau, o->ncell * o->ng) != hipSuccess ||
       o->alloc(&o->d_run_sum, std::max<size_t>(o->grad_nrun, 1) * o->grad_nchunk * 64) != hipSuccess ||
-      o->alloc(&o->d_jcol, o->ncol) != hipSuccess || o->alloc(&o->d_jb, o->nnode_active * (size_t)o->grad_nchunk) != hipSuccess)
+      o->alloc(&o->d_jcol, o->ncol) != hipSuccess || o->alloc(&o->d_jb, opt_njb(o)) != hipSuccess ||
+      (o->rayleigh_active && (o->alloc(&o->d_ray_part, 2 * ray_npart(o) * o->grad_nchunk * 64) != hipSuccess ||
+                              o->alloc(&o->d_ray_exp, 2 * (size_t)o->ng) != hipSuccess)))
     return ecckd::fail(ECCKD_OUT_OF_MEMORY, "ecckd_opt_create: device allocation failed");
   ECCKD_HIP_CHECK(hipHostMalloc((void**)&o->h_pin, PIN_SLOTS * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
   ECCKD_HIP_CHECK(hipHostGetDevicePointer((void**)&o->d_pin, o->h_pin, 0));
@@ -1777,8 +1970,9 @@ int ecckd_opt_create_ex(ecckd_ctx* ctx, const ecckd_opt_model* m, int nscene, co
                         const ecckd_opt_config* cfg, unsigned flags, ecckd_opt** out) {
   ECCKD_REQUIRE(ctx && m && scenes && cfg && out && nscene > 0, "ecckd_opt_create: NULL/empty argument");
   *out = nullptr;
-  ECCKD_REQUIRE((flags & ~ECCKD_OPT_RAYLEIGH_SCATTERING) == 0, "ecckd_opt_create_ex: unknown flags 0x%x", flags);
+  ECCKD_REQUIRE((flags & ~(ECCKD_OPT_RAYLEIGH_SCATTERING | ECCKD_OPT_RAYLEIGH_ACTIVE)) == 0, "ecckd_opt_create_ex: unknown flags 0x%x", flags);
   const bool scattering = (flags & ECCKD_OPT_RAYLEIGH_SCATTERING) != 0;
+  // (ECCKD_OPT_RAYLEIGH_ACTIVE on a model that is not shortwave with rayleigh_molar_scattering: refused by build_tables)
   if (scattering) {
     ECCKD_REQUIRE(m->solar_irradiance && m->rayleigh_molar_scattering,
                   "ecckd_opt_create_ex: ECCKD_OPT_RAYLEIGH_SCATTERING needs a shortwave model with rayleigh_molar_scattering");
@@ -1791,6 +1985,7 @@ int ecckd_opt_create_ex(ecckd_ctx* ctx, const ecckd_opt_model* m, int nscene, co
   const ot::Schedule schedule = {K8B_WAVES, K8B_RUN, plain && plain[0] == '1'};
   ot::Tables t;
   t.scattering = scattering;
+  t.rayleigh_active = (flags & ECCKD_OPT_RAYLEIGH_ACTIVE) != 0;
   std::string refusal;
   const int rc = ot::build_tables(m, nscene, scenes, cfg, schedule, t, refusal);
   if (rc != ECCKD_OK) return ecckd::fail(rc, "%s", refusal.c_str());
@@ -1802,14 +1997,15 @@ int ecckd_opt_create_ex(ecckd_ctx* ctx, const ecckd_opt_model* m, int nscene, co
   if (o->scattering) {
     // the LDS of k_opt_forward_adjoint_rayleigh depends on the shapes alone: refused here, where the handle is made, and the
     // kernel's limit raised once, not at every launch of the minimiser's loop
-    const size_t bytes = lds::rayleigh(o->nlay, o->ng, o->nband).bytes();
+    const size_t bytes = ray_lds_bytes(o.get(), 512);
     ECCKD_REQUIRE(bytes <= 160 * 1024, "ecckd_opt_create_ex: nlay * nband too large for the LDS of the scattering kernel (%zu B)", bytes);
-    ECCKD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_opt_forward_adjoint_rayleigh),
+    ECCKD_HIP_CHECK(hipFuncSetAttribute(o->rayleigh_active ? reinterpret_cast<const void*>(k_opt_forward_adjoint_rayleigh<true>)
+                                                           : reinterpret_cast<const void*>(k_opt_forward_adjoint_rayleigh<false>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   }
   ECCKD_CHECK(opt_upload_tables(o.get(), t));
   ECCKD_CHECK(opt_alloc_work(o.get(), t));
-  if (o->scattering && o->alloc(&o->d_ray_ws, o->ncol * RS_COUNT * (size_t)(o->nlay + 1) * o->ng) != hipSuccess)
+  if (o->scattering && o->alloc(&o->d_ray_ws, ray_ws_doubles(o.get())) != hipSuccess)
     return ecckd::fail(ECCKD_OUT_OF_MEMORY, "ecckd_opt_create_ex: device allocation of the scattering workspace failed");
   std::vector<double> xp(o->nx);
   ot::initial_state(*o, xp.data(), nullptr, nullptr);
@@ -1849,6 +2045,49 @@ int ecckd_opt_timings(ecckd_opt* o, double* minimizer_s, double* a_priori_s, dou
   if (minimizer_s) *minimizer_s = o->t_minimizer;
   if (a_priori_s) *a_priori_s = o->t_prior;
   if (radiative_transfer_s) *radiative_transfer_s = o->t_rt;
+  return ECCKD_OK;
+}
+
+// The prior of the optimised Rayleigh coefficients: J_b += 0.5 sum_g d_g^2 / sigma^2, d = x - x_prior on the unpinned tail
+// elements, WITH its gradient d_g / sigma^2 (the reference adds the cost and drops the gradient, ckd_model.cpp:869-874).
+int ecckd_opt_set_rayleigh_prior(ecckd_opt* o, double prior_error) {
+  ECCKD_REQUIRE(o, "ecckd_opt_set_rayleigh_prior: NULL handle");
+  ECCKD_REQUIRE(o->rayleigh_active, "ecckd_opt_set_rayleigh_prior: the handle was made without ECCKD_OPT_RAYLEIGH_ACTIVE");
+  o->ray_prior_error = prior_error > 0.0 ? prior_error : 0.0;
+  return ECCKD_OK;
+}
+
+// The Rayleigh molar scattering coefficients at state h_x: exp of the tail of an ECCKD_OPT_RAYLEIGH_ACTIVE handle's state (0 where
+// pinned), formed by k_opt_exp on the device - the very numbers the forward kernels read at that state, which the host's exp
+// matches only to a unit in the last place; any other handle, or h_x = NULL: the model's own.
+int ecckd_opt_rayleigh_coefficients(ecckd_opt* o, const double* h_x, double* h_coeff) {
+  ECCKD_REQUIRE(o && h_coeff, "ecckd_opt_rayleigh_coefficients: NULL argument");
+  ECCKD_REQUIRE(o->ray_ent >= 0, "ecckd_opt_rayleigh_coefficients: the model has no rayleigh_molar_scattering");
+  const size_t ng = (size_t)o->ng;
+  if (!(o->rayleigh_active && h_x)) {
+    std::memcpy(h_coeff, &o->k0[o->rayleigh_ix], ng * sizeof(double));
+    return ECCKD_OK;
+  }
+  ecckd_ctx* ctx = o->ctx;
+  ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
+  double* d_in = o->d_ray_exp;                // [2][ng]: the tail of the state, its exp
+  ECCKD_HIP_CHECK(hipMemcpyAsync(d_in, h_x + o->rayleigh_ix, ng * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(k_opt_exp, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, ctx->stream, ng, d_in, d_in + ng);
+  ECCKD_HIP_CHECK(hipGetLastError());
+  ECCKD_HIP_CHECK(hipMemcpyAsync(h_coeff, d_in + ng, ng * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return ECCKD_OK;
+}
+
+// The shape of the Rayleigh reduction of this handle (k_opt_rayleigh_reduce / _finish).
+int ecckd_opt_rayleigh_plan(ecckd_opt* o, ecckd_rayleigh_plan* out) {
+  ECCKD_REQUIRE(o && out, "ecckd_opt_rayleigh_plan: NULL argument");
+  ecckd_rayleigh_plan p{};
+  p.active = o->rayleigh_active ? 1 : 0;
+  p.chunk_rows = RAY_CHUNK; p.finish_waves = RAY_FIN_WAVES; p.batch = RAY_BATCH;
+  p.nrows = o->rayleigh_active ? ray_nrows(o) : 0;
+  p.npart = o->rayleigh_active ? ray_npart(o) : 0;
+  *out = p;
   return ECCKD_OK;
 }
 
@@ -1960,7 +2199,7 @@ ecckd_forward_plan opt_forward_plan(const ecckd_opt* o) {
     p.ngpad = (o->ng + 63) / 64 * 64;
     p.lgroups = std::max(1, (v >= 64 && v <= 512 ? v : 512) / p.ngpad);   // (ecckd_opt_create_ex has refused ng > 512)
     p.threads = p.ngpad * p.lgroups;
-    p.lds_bytes = lds::rayleigh(o->nlay, o->ng, o->nband).bytes();
+    p.lds_bytes = ray_lds_bytes(o, p.threads);
     return p;
   }
   const char* env_generic = std::getenv("ECCKD_K8A_GENERIC");
@@ -1973,8 +2212,12 @@ int opt_launch_forward(ecckd_opt* o) {
   const ecckd_forward_plan p = opt_forward_plan(o);
   if (o->scattering) {
     // (ecckd_opt_create_ex has checked the LDS and raised the kernel's limit; the Rayleigh entry is always kept apart from the absorbers; a diagnostic pass changes only keep_negative)
-    hipLaunchKernelGGL(k_opt_forward_adjoint_rayleigh, dim3((unsigned)o->ncol), dim3(p.threads), p.lds_bytes, ctx->stream, k8a_args(o, p),
-                       o->d_band_ptr, o->d_band_g, o->d_ray_ws);
+    if (o->rayleigh_active)
+      hipLaunchKernelGGL(k_opt_forward_adjoint_rayleigh<true>, dim3((unsigned)o->ncol), dim3(p.threads), p.lds_bytes, ctx->stream, k8a_args(o, p),
+                         o->d_band_ptr, o->d_band_g, o->d_ray_ws);
+    else
+      hipLaunchKernelGGL(k_opt_forward_adjoint_rayleigh<false>, dim3((unsigned)o->ncol), dim3(p.threads), p.lds_bytes, ctx->stream, k8a_args(o, p),
+                         o->d_band_ptr, o->d_band_g, o->d_ray_ws);
     ECCKD_HIP_CHECK(hipGetLastError());
     return ECCKD_OK;
   }
@@ -2025,13 +2268,25 @@ int opt_cost_grad_dev(ecckd_opt* o, const double* d_x, double* d_grad, double* J
   hipLaunchKernelGGL(k_opt_gradient_finish, dim3(o->gradient_grid), dim3(64 * K8B_WAVES), 0, ctx->stream, o->grad_nslot, ng, o->grad_nchunk,
                      d_x, o->d_xprior, o->d_k, o->d_node_run0, o->d_run_sum, o->d_node_gas, o->d_st_nb, o->d_st_w, o->d_inv_sigma2,
                      prior ? 1 : 0, d_grad, o->d_jb, o->d_node_order);
+  if (o->rayleigh_active) {
+    // the ng tail elements: rows -> first-level partials -> gradient and the tail's share of J_b (two launches, no host wait)
+    const size_t nrows = ray_nrows(o), npart = ray_npart(o);
+    const double* src = o->scattering ? o->d_ray_ws + (ray_ws_doubles(o) - o->ncol * (size_t)ng) : o->d_dtau;
+    const bool ray_prior = prior && o->ray_prior_error > 0.0;
+    hipLaunchKernelGGL(k_opt_rayleigh_reduce, dim3((unsigned)((npart * o->grad_nchunk + RAY_RED_WAVES - 1) / RAY_RED_WAVES)), dim3(64 * RAY_RED_WAVES),
+                       0, ctx->stream, nrows, ng, o->grad_nchunk, src, o->scattering ? nullptr : o->d_moles, o->d_ray_part);
+    hipLaunchKernelGGL(k_opt_rayleigh_finish, dim3((unsigned)o->grad_nchunk), dim3(64 * RAY_FIN_WAVES), 0, ctx->stream, npart, ng, o->grad_nchunk,
+                       o->d_ray_part, o->rayleigh_ix, d_x, o->d_xprior, o->d_k,
+                       ray_prior ? 1.0 / (o->ray_prior_error * o->ray_prior_error) : 0.0, ray_prior ? 1 : 0, d_grad,
+                       o->d_jb + o->nnode_active * (size_t)o->grad_nchunk);
+  }
   ECCKD_HIP_CHECK(hipGetLastError());
   if (timed) ECCKD_HIP_CHECK(hipEventRecord(o->tev[2], ctx->stream));
   // the cost: profiles, then the prior's node terms, summed on the device in a fixed order and delivered to the host's slot
   // (and, for the profile-sharded all-reduce, into the slot behind the gradient: ONE collective of nx + 1 doubles)
   double* h_cost = o->h_pin + PIN_COST;
   ecckd::slots_mark_pending(h_cost, 1);
-  hipLaunchKernelGGL(k_opt_sum_cost, dim3(1), dim3(256), 0, ctx->stream, o->d_jcol, o->ncol, o->d_jb, o->nnode_active * (size_t)o->grad_nchunk, prior ? 1 : 0,
+  hipLaunchKernelGGL(k_opt_sum_cost, dim3(1), dim3(256), 0, ctx->stream, o->d_jcol, o->ncol, o->d_jb, opt_njb(o), prior ? 1 : 0,
                      o->d_pin + PIN_COST, reduce ? d_grad + o->nx : nullptr);
   ECCKD_HIP_CHECK(hipGetLastError());
   ECCKD_CHECK(ecckd::slots_wait(ctx->stream, h_cost, 1, "ecckd_opt: results"));

@@ -218,7 +218,7 @@ def iband_per_g(model, wavenumber1, wavenumber2):
 
 def optimize_lut(ctx, model, training_files, relative_to=None, band_mapping=None, gmap=None, max_iterations=3000,
                  convergence_criterion=0.0, bounded=True, max_no_rayleigh_wavenumber=None, erythemal_weight=0.0,
-                 remove_min_max=False, rayleigh_scattering=False, **cfg):
+                 remove_min_max=False, rayleigh_scattering=False, optimize_rayleigh=False, rayleigh_prior_error=0.0, **cfg):
     """The driver of optimize_lut.cpp:60-330 on top of api.Optimizer: training scenes from LBL flux files
     (ncio.read_lbl_fluxes), optional "relative_to" file, bounded L-BFGS, optimised coefficients back into the model.
 
@@ -230,11 +230,17 @@ def optimize_lut(ctx, model, training_files, relative_to=None, band_mapping=None
            the tool's key of the same name): every file must be a `ckdmip_sw --rayleigh` one, the truth's downwelling is the
            total flux, nothing is masked (max_no_rayleigh_wavenumber is ignored) and relative_to goes through a scattering
            handle as well.
+    optimize_rayleigh: the ng Rayleigh coefficients are optimised too (api.Optimizer(optimize_rayleigh=True), the tool's key of
+           the same name), with either forward model; rayleigh_prior_error is the sigma of their prior (<= 0: none).  Every
+           gas of the model may then be inactive.  The relative_to handle is made without it.  The model that is returned
+           carries the optimised rayleigh_molar_scattering.
     Returns (model with optimised molar_abs, result dict of Optimizer.minimize)."""
     names = [g["name"] for g in model["gases"]]
     is_sw = model.get("solar_irradiance") is not None
     if rayleigh_scattering and not (is_sw and model.get("rayleigh_molar_scattering") is not None):
         raise EcckdError(PARAMETER_ERROR, "rayleigh_scattering needs a shortwave CKD model with a Rayleigh coefficient")
+    if optimize_rayleigh and not (is_sw and model.get("rayleigh_molar_scattering") is not None):
+        raise EcckdError(PARAMETER_ERROR, "optimize_rayleigh needs a shortwave CKD model with a Rayleigh coefficient")
 
     def load(path):
         s = ncio.read_lbl_fluxes(path, names, band_mapping=band_mapping, gmap=gmap, ctx=ctx, rayleigh_scattering=rayleigh_scattering)
@@ -250,6 +256,8 @@ def optimize_lut(ctx, model, training_files, relative_to=None, band_mapping=None
     if relative_to is not None:                                                                      # :204-236
         rel = load(relative_to)
         m0 = dict(model, iband_per_g=rel.get("iband_per_g", model["iband_per_g"]))
+        if not any(g.get("active", True) for g in model["gases"]):     # Rayleigh alone: this handle, made without the flag, takes every gas
+            m0["gases"] = [dict(g, active=True) for g in model["gases"]]
         ref_opt = api.Optimizer(ctx, m0, [_scene_for_optimizer(rel, is_sw)], rayleigh_scattering=rayleigh_scattering, **cfg)
         _, fl = ref_opt.forward(ref_opt.initial_state(), unclamped=True)     # od = value(aod), no clamp (:231-234)
         ref_opt.close()
@@ -269,7 +277,8 @@ def optimize_lut(ctx, model, training_files, relative_to=None, band_mapping=None
     m = dict(model)
     if iband is not None:
         m["iband_per_g"] = iband
-    opt = api.Optimizer(ctx, m, scenes, rayleigh_scattering=rayleigh_scattering, **dict(dict(cap_relative_linear=0.8), **cfg))   # :185
+    opt = api.Optimizer(ctx, m, scenes, rayleigh_scattering=rayleigh_scattering, optimize_rayleigh=optimize_rayleigh,
+                        rayleigh_prior_error=rayleigh_prior_error, **dict(dict(cap_relative_linear=0.8), **cfg))   # :185
     res = opt.minimize(max_iterations=max_iterations, convergence_criterion=convergence_criterion, bounded=bounded)
     out = dict(model, gases=[dict(g) for g in model["gases"]])
     for i, g in enumerate(out["gases"]):
@@ -277,6 +286,8 @@ def optimize_lut(ctx, model, training_files, relative_to=None, band_mapping=None
         if remove_min_max:
             g.pop("min_molar_abs", None)
             g.pop("max_molar_abs", None)
+    if optimize_rayleigh:
+        out["rayleigh_molar_scattering"] = opt.rayleigh_coefficients(res["x"])
     opt.close()
     return out, res
 

@@ -704,7 +704,8 @@ typedef struct {
   const ecckd_opt_gas* gases;
   int logarithmic_interpolation;     /* must be 0 (ckd_model.h:359) */
   /* shortwave (NULL / NULL = longwave model): solar irradiance per g point and the Rayleigh molar
-   * scattering coefficient per g point (ckd_model.h:242-252; kept fixed, not optimised) */
+   * scattering coefficient per g point (ckd_model.h:242-252; fixed unless the handle is made with
+   * ECCKD_OPT_RAYLEIGH_ACTIVE) */
   const double* solar_irradiance;           /* [ng] */
   const double* rayleigh_molar_scattering;  /* [ng] or NULL */
 } ecckd_opt_model;
@@ -758,13 +759,31 @@ int ecckd_opt_create(ecckd_ctx* ctx, const ecckd_opt_model* model, int nscene,
  * dn - up; a scene's flux_dn, spectral_flux_dn_surf and relative_flux_dn are total downwelling fluxes.  ecckd_opt_forward(_ex)
  * return (total dn, up) in h_flux and tau_abs + tau_ray in h_od.  Refused with ECCKD_PARAMETER_ERROR unless the model is
  * shortwave with rayleigh_molar_scattering and at most 512 g points, every scene has mu0 and albedo, and the kernel's band and
- * cost arrays (lds_bytes of ecckd_opt_forward_plan, about 48 nlay nband bytes) fit 160 KB of LDS.  Rayleigh stays a fixed
- * pseudo gas. */
+ * cost arrays (lds_bytes of ecckd_opt_forward_plan, about 48 nlay nband bytes) fit 160 KB of LDS.  Rayleigh is a fixed
+ * pseudo gas unless ECCKD_OPT_RAYLEIGH_ACTIVE is set as well.
+ * ECCKD_OPT_RAYLEIGH_ACTIVE: the ng Rayleigh coefficients are optimised too.  The state carries ng more elements
+ * x = ln(rayleigh_molar_scattering[g]) BEHIND the active gases' elements, in g order (ckd_model.cpp:109-111, :244-252), so
+ * ecckd_opt_nx grows by ng; all gases may then be inactive (the state is the ng elements alone).  A coefficient of 0 is pinned
+ * at MIN_X with gradient exactly 0.  The elements have NO bounds: ecckd_opt_initial_state gives them -inf / +inf whatever the
+ * gases' min / max tables (the reference activates bounds it never sets, ckd_model.cpp:136-137, solve_adept.cpp:346-347).
+ * Their prior is set with ecckd_opt_set_rayleigh_prior (none until then).  Gradient, by forward model:
+ *   without ECCKD_OPT_RAYLEIGH_SCATTERING Rayleigh is one more absorber, added before the clamp of negative optical depths
+ *     (solve_adept.cpp:32-35): dJ/dk_ray[g] = sum over all cells of moles_per_layer(cell) * dJ/dtau[cell][g], the clamped
+ *     cells' penalty derivative included;
+ *   with it tau_ray enters the two-stream layer terms beside tau_abs, after the clamp: dJ/dtau_ray of a cell is the adjoint
+ *     of the five layer terms times their derivative with respect to tau_ray at fixed tau_abs, and a cell whose gas optical
+ *     depth was clamped keeps it;
+ *   then dJ/dx = dJ/dk * k, the prior's d / sigma^2, and |g| < 1e-80 -> 0 (solve_adept.cpp:286).
+ * Every sum has a fixed order (no atomics): cost and gradient are bitwise reproducible.  Refused with ECCKD_PARAMETER_ERROR
+ * unless the model is shortwave with rayleigh_molar_scattering.  Every other function works unchanged on the longer vector;
+ * ecckd_opt_forward(_ex) take the coefficients from h_x. */
 #define ECCKD_OPT_RAYLEIGH_SCATTERING 1u
+#define ECCKD_OPT_RAYLEIGH_ACTIVE 2u
 int ecckd_opt_create_ex(ecckd_ctx* ctx, const ecckd_opt_model* model, int nscene, const ecckd_opt_scene* scenes,
                         const ecckd_opt_config* config, unsigned flags, ecckd_opt** opt);
 int ecckd_opt_destroy(ecckd_opt* opt);
-/* length of the state vector x = ln(molar_abs) of the active gases, in model gas order */
+/* length of the state vector x = ln(molar_abs) of the active gases, in model gas order (ECCKD_OPT_RAYLEIGH_ACTIVE: then the ng
+ * elements ln(rayleigh_molar_scattering)) */
 size_t ecckd_opt_nx(ecckd_opt* opt);
 /* initial state (MIN_X = -1e20 where the coefficient is 0) and log-space bounds, solve_adept.cpp:335-353 */
 int ecckd_opt_initial_state(ecckd_opt* opt, double* h_x, double* h_x_min, double* h_x_max);
@@ -792,6 +811,26 @@ int ecckd_opt_forward(ecckd_opt* opt, const double* h_x, double* h_od, double* h
  * the clamp belongs to the cost function alone, solve_adept.cpp:107-116) */
 int ecckd_opt_forward_ex(ecckd_opt* opt, const double* h_x, int unclamped, double* h_od, double* h_flux);
 int ecckd_opt_coefficients(ecckd_opt* opt, const double* h_x, int gas, double* h_molar_abs);
+/* Handles made with ECCKD_OPT_RAYLEIGH_ACTIVE.  The prior of the ng Rayleigh elements: with prior_error = sigma > 0
+ * J_b += 0.5 sum_g d_g^2 / sigma^2 and dJ_b/dx_g = d_g / sigma^2, d = x - ln(first guess) on the unpinned elements; <= 0: no
+ * prior term on them.  The gradient IS included: the reference adds this term to the cost and drops its gradient
+ * (ckd_model.cpp:869-874), and a cost whose gradient omits one of its terms is not a minimisation.  The term follows add_prior
+ * of ecckd_opt_set_allreduce as the gases' prior does.  Refused (ECCKD_PARAMETER_ERROR) on a handle without the flag. */
+int ecckd_opt_set_rayleigh_prior(ecckd_opt* opt, double prior_error);
+/* h_coeff[ng] = rayleigh_molar_scattering at state h_x: exp of the state's tail (0 where pinned) for a handle made with
+ * ECCKD_OPT_RAYLEIGH_ACTIVE, formed on the device by the kernel that feeds the forward model, so these are the numbers the
+ * cost at h_x was computed from, bit for bit; the model's own values for any other handle or h_x = NULL.  Refused if the model
+ * has none. */
+int ecckd_opt_rayleigh_coefficients(ecckd_opt* opt, const double* h_x, double* h_coeff);
+/* The shape of the fixed-order reduction that forms the Rayleigh gradient elements: first-level waves add chunk_rows
+ * consecutive rows each (nrows rows: the cells of a plain handle, the columns of a scattering one) into npart partials per
+ * g point, then finish_waves waves per 64 g points add ceil(npart / finish_waves) partials each, `batch` loads per round.
+ * active = 0 (and nrows = npart = 0) for a handle without ECCKD_OPT_RAYLEIGH_ACTIVE. */
+typedef struct {
+  int active, chunk_rows, finish_waves, batch;
+  size_t nrows, npart;
+} ecckd_rayleigh_plan;
+int ecckd_opt_rayleigh_plan(ecckd_opt* opt, ecckd_rayleigh_plan* plan);
 /* status follows adept::MinimizerStatus: 0 success, 2 max iterations, 3 failed to converge,
  * >= 6 anomalous (optimize_lut.cpp:315-319 exits 1 for those) */
 int ecckd_opt_minimize(ecckd_opt* opt, int max_iterations, double convergence_criterion, int is_bounded,

@@ -5,6 +5,8 @@
 // orders hold every task once, and that the transpose holds exactly the non-zero entries of the gather.  Then the history: more
 // pairs than the ring holds, one rejected, one restart; the triangular solves are checked by their residuals.  First of all the
 // LDS layouts of the K8a kernels (csrc/opt_lds.hpp): nlay 1 / 17 / 54 / 128 x ng 1 / 64 / 70 x nband 1 / 13, longwave and shortwave.
+// Last the tables of a handle that optimises the Rayleigh coefficients (Tables::rayleigh_active): with active gases against the
+// tables without the flag, Rayleigh alone, a zero coefficient, and the flag on a longwave model, refused.
 // build: g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Iecckd_amd/csrc tools/check_opt_tables.cpp \
 //        ecckd_amd/csrc/opt_tables.cpp -o /tmp/check_opt_tables && /tmp/check_opt_tables
 #include <algorithm>
@@ -211,6 +213,98 @@ static void check_refusals() {
   { Problem p(c, rng); p.scenes[1].nband = 2; REQUIRE(ot::check_arguments(&p.m, 2, p.scenes, &p.cfg, err) == ECCKD_PARAMETER_ERROR && err == "ecckd_opt_create: scene 1 is inconsistent (nlay/nband/arrays)"); }
 }
 
+// Tables::rayleigh_active.  With active gases: against the tables of the same problem without the flag - the Rayleigh row sits
+// directly behind the active gases (its ng elements are the tail of the state: no bounds, no node), the fixed gas moves up by
+// ng, and everything that is not an offset into k is the same bytes.  Rayleigh alone: every gas inactive, the state is the ng
+// elements and K8b / K9 have no node.  A zero coefficient is pinned at MIN_X.  The flag on a longwave model is refused.
+static int check_rayleigh_active() {
+  int ncase = 0;
+  for (int ng : {1, 64, 65})
+    for (int nlay : {1, 128}) {
+      static char label[96];
+      std::snprintf(label, sizeof(label), "rayleigh_active ng=%d nlay=%d", ng, nlay);
+      what = label;
+      const Case c = {ng, 5, 16, 4, nlay, true, false};
+      const ot::Schedule sched = {4, 64, false};
+      std::string err;
+      std::mt19937_64 rng0(99), rng1(99), rng2(99);
+      Problem p0(c, rng0), p1(c, rng1), p2(c, rng2);
+      if (ng > 2) p1.rayleigh[2] = p0.rayleigh[2] = 0.0;          // a zero coefficient
+      ot::Tables t0, t1, t2;
+      t1.rayleigh_active = true;
+      t2.rayleigh_active = true;
+      REQUIRE(ot::build_tables(&p0.m, 2, p0.scenes, &p0.cfg, sched, t0, err) == ECCKD_OK);
+      REQUIRE(ot::build_tables(&p1.m, 2, p1.scenes, &p1.cfg, sched, t1, err) == ECCKD_OK);
+      const size_t n = ng;
+      // flag with active gases
+      REQUIRE(t1.nx == t0.nx + n && t1.nk == t0.nk && t1.nnode_active == t0.nnode_active && t1.rayleigh_ix == t0.nx && t0.rayleigh_ix == t0.nk - n);
+      REQUIRE(t1.kmin.size() == t1.nx && t1.kmax.size() == t1.nx && t1.k0.size() == t1.nk && t1.moles.size() == t1.ncell && t0.moles.empty());
+      for (size_t e = 0; e < t0.nx; ++e) REQUIRE(t1.k0[e] == t0.k0[e] && t1.kmin[e] == t0.kmin[e] && t1.kmax[e] == t0.kmax[e]);
+      for (size_t g = 0; g < n; ++g) REQUIRE(t1.k0[t1.rayleigh_ix + g] == p1.rayleigh[g] && t1.kmin[t0.nx + g] == 0.0 && t1.kmax[t0.nx + g] == 0.0);
+      for (size_t e = t0.nx; e < t0.nk - n; ++e) REQUIRE(t1.k0[e + n] == t0.k0[e]);      // the fixed gas, moved up by ng
+      REQUIRE(t1.nent == t0.nent && t1.ray_ent == t0.ray_ent && t1.ent_coef == t0.ent_coef && t1.ent_idx.size() == t0.ent_idx.size());
+      for (size_t i = 0; i < t0.ent_idx.size(); ++i) {
+        const int a = t0.ent_idx[i], b = t1.ent_idx[i];
+        const bool ray = (int)(i % t0.nent) == t0.ray_ent;
+        REQUIRE(ray ? (a == (int)t0.rayleigh_ix && b == (int)t1.rayleigh_ix) : (a < 0 || (size_t)a < t0.nx) ? b == a : b == a + ng);
+        if (ray) REQUIRE(t1.moles[i / t0.nent] == t1.ent_coef[i] && t1.moles[i / t0.nent] > 0.0);
+      }
+      REQUIRE(t1.ref_ptr == t0.ref_ptr && t1.ref_cell == t0.ref_cell && t1.ref_coef == t0.ref_coef && t1.node_order == t0.node_order &&
+              t1.run_order == t0.run_order && t1.run_r0 == t0.run_r0 && t1.run_last == t0.run_last && t1.node_run0 == t0.node_run0);
+      REQUIRE(t1.st_nb == t0.st_nb && t1.st_w == t0.st_w && t1.inv_sigma2 == t0.inv_sigma2 && t1.node_gas == t0.node_gas);
+      REQUIRE(t1.planck == t0.planck && t1.hr == t0.hr && t1.lw == t0.lw && t1.rel == t0.rel && t1.band_g == t0.band_g);
+      {
+        std::vector<double> x0(t0.nx), lo0(t0.nx), hi0(t0.nx), x(t1.nx), lo(t1.nx), hi(t1.nx);
+        ot::initial_state(t0, x0.data(), lo0.data(), hi0.data());
+        ot::initial_state(t1, x.data(), lo.data(), hi.data());
+        for (size_t e = 0; e < t0.nx; ++e) REQUIRE(x[e] == x0[e] && lo[e] == lo0[e] && hi[e] == hi0[e]);
+        for (size_t g = 0; g < n; ++g) {
+          const size_t e = t0.nx + g;
+          REQUIRE(lo[e] == -INFINITY && hi[e] == INFINITY);                               // no bounds, with min / max tables present
+          REQUIRE(p1.rayleigh[g] > 0.0 ? x[e] == std::log(p1.rayleigh[g]) : x[e] == ot::MIN_X);
+        }
+        if (ng > 2) REQUIRE(x[t0.nx + 2] == ot::MIN_X);
+      }
+      // Rayleigh alone
+      for (auto& g : p2.gases) g.is_active = 0;
+      REQUIRE(ot::check_arguments(&p2.m, 2, p2.scenes, &p2.cfg, err) == ECCKD_PARAMETER_ERROR && err == "ecckd_opt_create: no active gas to optimise");
+      REQUIRE(ot::build_tables(&p2.m, 2, p2.scenes, &p2.cfg, sched, t2, err) == ECCKD_OK);
+      REQUIRE(t2.nx == n && t2.nk == t0.nk && t2.rayleigh_ix == 0 && t2.nnode_active == 0 && t2.kmin == std::vector<double>(n, 0.0) && t2.kmax == t2.kmin);
+      REQUIRE(t2.ref_ptr.size() == 1 && t2.ref_cell.empty() && t2.run_r0.empty() && t2.node_run0.size() == 1 && t2.st_nb.empty() && t2.node_gas.empty());
+      for (int v : t2.node_order) REQUIRE(v == -1);
+      for (int v : t2.run_order) REQUIRE(v == -1);
+      for (size_t i = 0; i < t2.ent_idx.size(); ++i) {
+        const int idx = t2.ent_idx[i];
+        REQUIRE(idx == -1 || ((int)(i % t2.nent) == t2.ray_ent ? idx == 0 : (idx >= ng && idx % ng == 0 && (size_t)idx + n <= t2.nk)));
+      }
+      {
+        std::vector<double> x(t2.nx), lo(t2.nx), hi(t2.nx);
+        ot::initial_state(t2, x.data(), lo.data(), hi.data());
+        for (size_t g = 0; g < n; ++g) REQUIRE(x[g] == std::log(p2.rayleigh[g]) && lo[g] == -INFINITY && hi[g] == INFINITY);
+      }
+      ncase += 2;
+    }
+  // the flag on a longwave model, and on a shortwave model without the coefficient
+  what = "rayleigh_active refusals";
+  std::mt19937_64 rng(5);
+  std::string err;
+  const ot::Schedule sched = {4, 64, false};
+  {
+    Problem p(Case{12, 5, 16, 4, 18, false, false}, rng);
+    ot::Tables t;
+    t.rayleigh_active = true;
+    REQUIRE(ot::build_tables(&p.m, 2, p.scenes, &p.cfg, sched, t, err) == ECCKD_PARAMETER_ERROR && err.find("ECCKD_OPT_RAYLEIGH_ACTIVE") != std::string::npos);
+  }
+  {
+    Problem p(Case{12, 5, 16, 4, 18, true, false}, rng);
+    p.m.rayleigh_molar_scattering = nullptr;
+    ot::Tables t;
+    t.rayleigh_active = true;
+    REQUIRE(ot::build_tables(&p.m, 2, p.scenes, &p.cfg, sched, t, err) == ECCKD_PARAMETER_ERROR && err.find("ECCKD_OPT_RAYLEIGH_ACTIVE") != std::string::npos);
+  }
+  return ncase + 2;
+}
+
 // The history over 20 accepted pairs, one rejected and one restart.  The dots are those of vectors that exist (S, Y, q random),
 // so S^T Y is what a run would see; the direction's coefficients are checked through R u = p.
 static void check_history() {
@@ -329,6 +423,8 @@ int main() {
         }
   check_refusals();
   check_history();
-  std::printf("check_opt_tables: %d LDS layouts, %d table cases, the refusals and the history: no complaint\n", nlds, ncase);
+  const int nray = check_rayleigh_active();
+  std::printf("check_opt_tables: %d LDS layouts, %d table cases, %d cases of the optimised Rayleigh row, the refusals and the history: no complaint\n",
+              nlds, ncase, nray);
   return 0;
 }

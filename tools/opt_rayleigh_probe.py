@@ -1,8 +1,9 @@
 """L-BFGS iterations per second of a scattering optimiser handle (api.Optimizer(rayleigh_scattering=True),
 k_opt_forward_adjoint_rayleigh) and of a plain shortwave handle on the same machine and in the same run, at the shortwave
 optimiser shape of bench.py --full: ng = 64, 6 x 53 (T, p) grid, 12 mole fractions, 13 bands, 8 scenarios x 50 columns x three
-zenith angles x 54 layers.  Each handle is trained on the fluxes of a perturbed model through its own transfer.  Writes
-profiles/opt_rayleigh_probe.json and prints it.
+zenith angles x 54 layers.  Each handle is trained on the fluxes of a perturbed model through its own transfer.  Then both
+again with the Rayleigh coefficients optimised too (optimize_rayleigh=True, prior error 1: 64 more state elements, two more
+launches per evaluation).  Writes profiles/opt_rayleigh_probe.json and prints it.
 usage: python tools/opt_rayleigh_probe.py [iterations]"""
 import json
 import os
@@ -43,7 +44,7 @@ def problem():
     return model, truth, scenes
 
 
-def run(ctx, scattering):
+def run(ctx, scattering, active=False):
     model, truth, scenes = problem()
     cfg = dict(flux_weight=0.2, flux_profile_weight=0.0, broadband_weight=0.5, prior_error=2.0, pressure_corr=0.8,
                temperature_corr=0.8, conc_corr=0.8)
@@ -60,7 +61,8 @@ def run(ctx, scattering):
         ncs = s["pressure_hl"].shape[0]
         s["flux_dn"], s["flux_up"] = np.ascontiguousarray(band[c0:c0 + ncs, 0]), np.ascontiguousarray(band[c0:c0 + ncs, 1])
         c0 += ncs
-    opt = api.Optimizer(ctx, model, scenes, rayleigh_scattering=scattering, **cfg)
+    extra = dict(optimize_rayleigh=True, rayleigh_prior_error=1.0) if active else {}
+    opt = api.Optimizer(ctx, model, scenes, rayleigh_scattering=scattering, **extra, **cfg)
     x0 = opt.initial_state()
     J0, _ = opt.cost_grad(x0)                                # warm-up
     t0 = time.perf_counter()
@@ -72,13 +74,16 @@ def run(ctx, scattering):
     dt = time.perf_counter() - t0
     out = dict(iters_per_s=res["iterations"] / dt, iterations=res["iterations"], cost_grad_ms=eval_ms, J0=J0, J_final=res["cost"],
                status=res["status"], nx=opt.nx, plan=opt.forward_plan())
+    if active:
+        out["rayleigh_plan"] = opt.rayleigh_plan()
     opt.close()
     return out
 
 
 with api.Context(0) as ctx:
     result = {"shape": "ng 64, nlay 54, nband 13, 8 x 150 columns", "iterations_asked": iterations,
-              "plain_shortwave": run(ctx, False), "rayleigh_scattering": run(ctx, True)}
+              "plain_shortwave": run(ctx, False), "rayleigh_scattering": run(ctx, True),
+              "plain_shortwave_optimize_rayleigh": run(ctx, False, True), "rayleigh_scattering_optimize_rayleigh": run(ctx, True, True)}
 result["ratio_scattering_to_plain"] = result["rayleigh_scattering"]["iters_per_s"] / result["plain_shortwave"]["iters_per_s"]
 os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
 with open(os.path.join(ROOT, "profiles", "opt_rayleigh_probe.json"), "w") as f:
