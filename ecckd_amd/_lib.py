@@ -250,6 +250,12 @@ SIGNATURES = {
                                                     C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_int,
                                                     _c_int64_p, _c_int64_p, _c_double_p, _c_double_p, _c_double_p, C.c_void_p,
                                                     C.c_void_p, C.c_void_p]),
+    "ecckd_lbl_band_fluxes_sw_rayleigh_scenarios": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_int, _c_double_p, C.c_void_p,
+                                                              C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int),
+                                                              C.POINTER(C.c_size_t), C.c_void_p, C.c_int, C.c_size_t, C.c_int,
+                                                              _c_double_p, C.c_int, _c_int64_p, _c_int64_p, _c_double_p,
+                                                              _c_double_p, _c_double_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ecckd_lbl_rayleigh_scenarios_per_launch": (C.c_int, [C.c_int, C.c_int, C.c_size_t]),
     "ecckd_rt_sw_gpoints_rayleigh": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _c_double_p, _c_double_p,
                                                _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
     "ecckd_gather_f64_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1385,6 +1385,45 @@ def lbl_band_fluxes_sw_scenarios(ctx, cos_sza, ssi, optical_depths, scales, band
     return dn, up
 
 
+def lbl_rayleigh_scenarios_per_launch(nlay, nsza, nchunk):
+    """Scenarios one launch of lbl_band_fluxes_sw_rayleigh_scenarios carries at nlay layers, nsza angles and nchunk
+    256-wavenumber chunks: what fits the budget of partial bytes (ECCKD_RAYLEIGH_SCENARIO_BYTES), one at least."""
+    return int(_lib.load_library().ecckd_lbl_rayleigh_scenarios_per_launch(int(nlay), int(nsza), int(nchunk)))
+
+
+def lbl_band_fluxes_sw_rayleigh_scenarios(ctx, cos_sza, ssi, optical_depths, rayleigh_optical_depth, scales, band_begin, band_end,
+                                          albedo=None, boundary=False):
+    """lbl_band_fluxes_sw_rayleigh of many scenarios and every solar zenith angle of cos_sza (a scalar is one angle, 8 at most)
+    from one read of the gases' spectra: optical_depths (the absorbers) and scales as lbl_band_fluxes_sw_scenarios;
+    rayleigh_optical_depth (nlay, nwav), float32 or float64, scatters unscaled in every scenario ->
+    (flux_dn_direct, flux_dn, flux_up), each (nscen, nsza, nband, nlay+1), flux_dn direct plus diffuse; boundary=True: also the
+    spectral direct and total downwelling fluxes at the surface and the upwelling one at the top, device tensors
+    (nscen, nsza, nwav).  Scenario s is merge_spectrum gas after gas, then lbl_band_fluxes_sw_rayleigh (bit for bit with one gas)."""
+    mu = _f64c(np.atleast_1d(cos_sza))
+    ngas, nlay, nwav, ptrs, types, strides, sc = _scenario_args(optical_depths, scales)
+    ray = rayleigh_optical_depth
+    if tuple(ray.shape) != (nlay, nwav) or ray.stride(1) != 1:
+        raise ValueError("rayleigh_optical_depth must have the absorbers' shape (nlay, nwav) and contiguous rows")
+    nscen = sc.shape[0]
+    b0 = np.ascontiguousarray(band_begin, dtype=np.int64)
+    b1 = np.ascontiguousarray(band_end, dtype=np.int64)
+    shape = (nscen, mu.size, b0.size, nlay + 1)
+    direct, dn, up = np.empty(shape), np.empty(shape), np.empty(shape)
+    torch = _torch()
+    bnd = [torch.empty((nscen, mu.size, nwav), dtype=torch.float64, device=ctx.device) if boundary else None for _ in range(3)]
+    ctx.fence_from_torch()
+    check(ctx.lib.ecckd_lbl_band_fluxes_sw_rayleigh_scenarios(ctx.handle, nlay, nwav, mu.size, _hptr(mu), _dptr(ssi),
+                                                              _dptr(albedo) if albedo is not None else None, ngas, ptrs, types,
+                                                              strides, _dptr(ray), _od_type(ray),
+                                                              ray.stride(0) if nlay > 1 else nwav, nscen, _hptr(sc), b0.size,
+                                                              _hptr(b0, C.c_int64), _hptr(b1, C.c_int64), _hptr(direct), _hptr(dn),
+                                                              _hptr(up), *[_dptr(b) if boundary else None for b in bnd]))
+    if boundary:
+        ctx.synchronize()
+        return (direct, dn, up, *bnd)
+    return direct, dn, up
+
+
 def lbl_spectral_fluxes_sw(ctx, cos_sza, ssi, optical_depth, albedo=None):
     """Line-by-line shortwave spectral fluxes of one column for every solar zenith angle of cos_sza (a scalar is one angle):
     device tensors ssi (nwav,), optical_depth (nlay, nwav), albedo (nwav,) or None (no upwelling sweep) ->

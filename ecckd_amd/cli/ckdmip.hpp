@@ -7,6 +7,7 @@
 // ckdmip_sw      ... [--rayleigh rayleigh-spectrum-file] spectrum-file... --output file
 // ckdmip_sw      ... --ckd optical-depth-file --rayleigh-scattering --output file
 // ckdmip_{lw,sw} [--config file.nam] [--column-range a b] [--ssi file] --scenarios table spectrum-file...
+// ckdmip_sw      ... --scenarios table --scenarios-rayleigh rayleigh-spectrum-file spectrum-file...
 //
 //   --merge-only   test/merge_well_mixed_lw.sh:28-31, :46-49, :60-63 (merge_well_mixed_sw.sh:35-81): the optical depths of
 //                  several gas files added up, each scaled as requested, written as one spectrum file that read_spectrum /
@@ -42,6 +43,14 @@
 //                  (ecckd_lbl_band_fluxes_lw_scenarios / _sw_scenarios), and every OUTPUT is the file the default mode would
 //                  have written with `--scenario NAME --output OUTPUT` and the line's scalings.  Not with --merge-only, --ckd,
 //                  --output, --scenario or a per-file --scale / --conc / --const.
+//   --scenarios-rayleigh FILE   (ckdmip_sw --scenarios) the spectrum whose optical depth SCATTERS in every scenario of the
+//                  table: checked against the grid as --rayleigh FILE is, read once per column, never scaled, and not one of
+//                  the gases of the outputs.  All scenarios and angles come from one read of the gas files
+//                  (ecckd_lbl_band_fluxes_sw_rayleigh_scenarios), and every OUTPUT is the file
+//                  `--rayleigh FILE --scenario NAME --output OUTPUT` with the line's scalings would have written.  The spelling
+//                  `--rayleigh FILE --scenarios TABLE` stays refused, as it always was - which is why the combination has a
+//                  switch of its own.  Only with --scenarios, and not with --rayleigh, --rayleigh-scattering, --ckd,
+//                  --merge-only or ckdmip_lw.
 // A file may be preceded by  --scale s  (optical depth times s),  --conc c  (scaled so that the file's reference surface
 // mole fraction becomes c)  or  --const c  (a mole fraction c at every level: each level scaled by c / its own).
 // Namelist (&longwave_config / &shortwave_config): band_wavenumber1 / band_wavenumber2, nspectralstride (1 only), nangle (0:
@@ -275,7 +284,7 @@ std::vector<double> sum_over_g_points(const std::vector<double>& f, size_t nrow,
 struct Args {
   bool sw = false;
   std::vector<GasArg> gases;
-  std::string config_file, scenario, output, ckd_file, ssi_file, scenarios_file, rayleigh_file, history;
+  std::string config_file, scenario, output, ckd_file, ssi_file, scenarios_file, rayleigh_file, scenarios_rayleigh_file, history;
   bool merge_only = false, per_file_scaling = false, rayleigh_scattering = false;
   long col_a = -1, col_b = -1;
   std::vector<ScenarioRow> table;              // --scenarios
@@ -298,6 +307,7 @@ Args parse_args(int argc, char** argv, bool sw) {
     else if (a == "--merge-only") p.merge_only = true;
     else if (a == "--scenarios") { need(1); p.scenarios_file = argv[++i]; }
     else if (a == "--rayleigh") { need(1); p.rayleigh_file = argv[++i]; }
+    else if (a == "--scenarios-rayleigh") { need(1); p.scenarios_rayleigh_file = argv[++i]; }
     else if (a == "--rayleigh-scattering") p.rayleigh_scattering = true;
     else if (a == "--column-range") { need(2); p.col_a = std::atol(argv[++i]); p.col_b = std::atol(argv[++i]); }
     else if (a == "--scale") scaling(GasArg::SCALE);
@@ -305,6 +315,13 @@ Args parse_args(int argc, char** argv, bool sw) {
     else if (a == "--const") scaling(GasArg::CONST);
     else if (a.rfind("--", 0) == 0) fail(ECCKD_PARAMETER_ERROR, "Argument \"%s\" not understood", a.c_str());
     else { pending.path = a; p.gases.push_back(pending); pending = GasArg(); }
+  }
+  if (!p.scenarios_rayleigh_file.empty()) {     // the scattering spectrum of a table: shortwave, and only beside --scenarios
+    const char* with = !sw ? "the longwave tool" : !p.rayleigh_file.empty() ? "--rayleigh" : p.rayleigh_scattering ? "--rayleigh-scattering"
+                       : !p.ckd_file.empty() ? "--ckd" : p.merge_only ? "--merge-only" : nullptr;
+    if (with) fail(ECCKD_PARAMETER_ERROR, "\"--scenarios-rayleigh\" cannot be combined with %s", with);
+    if (p.scenarios_file.empty())
+      fail(ECCKD_PARAMETER_ERROR, "\"--scenarios-rayleigh\" needs --scenarios; for one scenario name the spectrum with --rayleigh");
   }
   if (!p.rayleigh_file.empty() || p.rayleigh_scattering) {     // scattering is opt-in, shortwave only, one column set per call
     const char* sw_switch = !p.rayleigh_file.empty() ? "--rayleigh" : "--rayleigh-scattering";
@@ -504,21 +521,23 @@ void define_flux_file(NcOut& o, const Args& a, const Spectra& s, const std::stri
 // ---- --scenarios: every scenario of the table from one read of the gas files per column ----
 int mode_scenarios(const Args& a, Spectra& s) {
   const Namelist& nl = a.nl;
-  const bool sw = a.sw;
+  const bool sw = a.sw, rayleigh = !a.scenarios_rayleigh_file.empty();
   const Device& dev = s.dev;
   const int nlay = s.g.nlay, nband = s.nband, nmu = s.nmu;
   const size_t nwav = s.g.nwav, nscen = a.table.size(), ngas = a.gases.size(), nhl = (size_t)nlay + 1;
   std::vector<std::unique_ptr<NcOut>> outs;
   for (const ScenarioRow& row : a.table) {
     outs.emplace_back(new NcOut(row.output));
-    define_flux_file(*outs.back(), a, s, row.name, false);
+    define_flux_file(*outs.back(), a, s, row.name, rayleigh);
   }
   const size_t nslot = sw ? nscen * nmu : nscen;            // rows of fluxes: (scenario[, angle])
   const int ngroup = sw ? std::min(8, nmu) : 1;              // angles per call: the entry takes up to 8
-  DevBuf d_sdn, d_tup;
+  DevBuf d_sdn, d_tup, d_tot;                                // d_tot: direct plus diffuse at the surface (--scenarios-rayleigh)
   if (nl.boundary_fluxes) { d_sdn.alloc(dev, nscen * ngroup * nwav * sizeof(double)); d_tup.alloc(dev, nscen * ngroup * nwav * sizeof(double)); }
+  if (nl.boundary_fluxes && rayleigh) d_tot.alloc(dev, nscen * ngroup * nwav * sizeof(double));
   double* const p_sdn = nl.boundary_fluxes ? d_sdn.as<double>() : nullptr;
   double* const p_tup = nl.boundary_fluxes ? d_tup.as<double>() : nullptr;
+  double* const p_tot = nl.boundary_fluxes && rayleigh ? d_tot.as<double>() : nullptr;
   for (int c = s.g.c0; c <= s.g.c1; ++c) {
     const Spectrum col = c == 0 ? s.g.first : read_spectrum(a.gases[0].path, c, false);
     std::vector<DevOd> ods;                                  // the gases side by side on the device, read once
@@ -541,26 +560,42 @@ int mode_scenarios(const Args& a, Spectra& s) {
       od_ptr.push_back(ods.back().buf.ptr());
       od_type.push_back(ods.back().type);
     }
+    DevOd ray;                                               // --scenarios-rayleigh: what scatters, read once, never scaled
+    if (rayleigh) {
+      NcIn fr(a.scenarios_rayleigh_file);
+      ray = read_od_dev(dev, fr, c, nlay, nwav);
+    }
     ck(ecckd_synchronize(dev.ctx()));
-    std::vector<double> bdn(nslot * nband * nhl), bup(nslot * nband * nhl);
-    std::vector<double> all_dn, all_up;                      // [slot][wavenumber] boundary fluxes of this column
+    std::vector<double> bdn(nslot * nband * nhl), bup(nslot * nband * nhl), btot;   // bdn: the direct beam where light scatters
+    std::vector<double> all_dn, all_up, all_tot;             // [slot][wavenumber] boundary fluxes of this column
+    if (rayleigh) btot.resize(nslot * nband * nhl);
     if (nl.boundary_fluxes) { all_dn.resize(nslot * nwav); all_up.resize(nslot * nwav); }
+    if (nl.boundary_fluxes && rayleigh) all_tot.resize(nslot * nwav);
     if (sw) {
       for (int m0 = 0; m0 < nmu; m0 += ngroup) {             // [scenario][angle] rows per group of angles
         const size_t nm = (size_t)std::min(ngroup, nmu - m0);
-        std::vector<double> gdn(nscen * nm * nband * nhl), gup(gdn.size());
-        ck(ecckd_lbl_band_fluxes_sw_scenarios(dev.ctx(), nlay, nwav, (int)nm, s.mu0.data() + m0, s.d_ssi.as<double>(), s.d_albedo.as<double>(),
-                                              (int)ngas, od_ptr.data(), od_type.data(), od_stride.data(), (int)nscen, scale.data(), nband,
-                                              s.bbegin.data(), s.bend.data(), gdn.data(), gup.data(), p_sdn, p_tup));
-        std::vector<double> sd, tu;
+        std::vector<double> gdn(nscen * nm * nband * nhl), gup(gdn.size()), gtot(rayleigh ? gdn.size() : 0);
+        if (rayleigh)
+          ck(ecckd_lbl_band_fluxes_sw_rayleigh_scenarios(dev.ctx(), nlay, nwav, (int)nm, s.mu0.data() + m0, s.d_ssi.as<double>(),
+                                                         s.d_albedo.as<double>(), (int)ngas, od_ptr.data(), od_type.data(), od_stride.data(),
+                                                         ray.buf.ptr(), ray.type, nwav, (int)nscen, scale.data(), nband, s.bbegin.data(),
+                                                         s.bend.data(), gdn.data(), gtot.data(), gup.data(), p_sdn, p_tot, p_tup));
+        else
+          ck(ecckd_lbl_band_fluxes_sw_scenarios(dev.ctx(), nlay, nwav, (int)nm, s.mu0.data() + m0, s.d_ssi.as<double>(), s.d_albedo.as<double>(),
+                                                (int)ngas, od_ptr.data(), od_type.data(), od_stride.data(), (int)nscen, scale.data(), nband,
+                                                s.bbegin.data(), s.bend.data(), gdn.data(), gup.data(), p_sdn, p_tup));
+        std::vector<double> sd, tu, tt;
         if (nl.boundary_fluxes) { sd = d_sdn.download<double>(); tu = d_tup.download<double>(); }
+        if (nl.boundary_fluxes && rayleigh) tt = d_tot.download<double>();
         for (size_t k = 0; k < nscen; ++k) {
           const size_t n = nm * nband * nhl, to = (k * nmu + m0) * nband * nhl;
           std::copy(gdn.begin() + k * n, gdn.begin() + (k + 1) * n, bdn.begin() + to);
           std::copy(gup.begin() + k * n, gup.begin() + (k + 1) * n, bup.begin() + to);
+          if (rayleigh) std::copy(gtot.begin() + k * n, gtot.begin() + (k + 1) * n, btot.begin() + to);
           if (nl.boundary_fluxes) {
             std::copy(sd.begin() + k * nm * nwav, sd.begin() + (k + 1) * nm * nwav, all_dn.begin() + (k * nmu + m0) * nwav);
             std::copy(tu.begin() + k * nm * nwav, tu.begin() + (k + 1) * nm * nwav, all_up.begin() + (k * nmu + m0) * nwav);
+            if (rayleigh) std::copy(tt.begin() + k * nm * nwav, tt.begin() + (k + 1) * nm * nwav, all_tot.begin() + (k * nmu + m0) * nwav);
           }
         }
       }
@@ -572,7 +607,8 @@ int mode_scenarios(const Args& a, Spectra& s) {
       if (nl.boundary_fluxes) { all_dn = d_sdn.download<double>(); all_up = d_tup.download<double>(); }
     }
     const size_t oc = (size_t)(c - s.g.c0), per = sw ? (size_t)nmu : 1;   // rows per scenario
-    std::vector<double> tdn(per * nhl * nband), tup(per * nhl * nband), sdn(per * nhl), sup(per * nhl);
+    std::vector<double> tdn(per * nhl * nband), tup(per * nhl * nband), sdn(per * nhl), sup(per * nhl), ttot, stot;
+    if (rayleigh) { ttot.resize(per * nhl * nband); stot.resize(per * nhl); }
     const std::string x = sw ? "_sw" : "_lw";
     for (size_t k = 0; k < nscen; ++k) {
       NcOut& o = *outs[k];
@@ -581,15 +617,20 @@ int mode_scenarios(const Args& a, Spectra& s) {
       for (size_t m = 0; m < per; ++m) {
         bands_to_file_order(nband, nhl, &bdn[(k * per + m) * nband * nhl], &tdn[m * nhl * nband], &sdn[m * nhl]);
         bands_to_file_order(nband, nhl, &bup[(k * per + m) * nband * nhl], &tup[m * nhl * nband], &sup[m * nhl]);
+        if (rayleigh) bands_to_file_order(nband, nhl, &btot[(k * per + m) * nband * nhl], &ttot[m * nhl * nband], &stot[m * nhl]);
       }
       o.write_slice("mole_fraction_fl", oc, std::vector<double>(vmr_all.begin() + k * ngas * nlay, vmr_all.begin() + (k + 1) * ngas * nlay));
-      o.write_slice(sw ? "band_flux_dn_direct_sw" : "band_flux_dn_lw", oc, tdn); o.write_slice("band_flux_up" + x, oc, tup);
+      o.write_slice(sw ? "band_flux_dn_direct_sw" : "band_flux_dn_lw", oc, tdn);
+      if (rayleigh) o.write_slice("band_flux_dn_sw", oc, ttot);
+      o.write_slice("band_flux_up" + x, oc, tup);
       if (sw) o.write_slice("flux_dn_direct_sw", oc, sdn);
-      o.write_slice("flux_dn" + x, oc, sdn); o.write_slice("flux_up" + x, oc, sup);
+      o.write_slice("flux_dn" + x, oc, rayleigh ? stot : sdn); o.write_slice("flux_up" + x, oc, sup);
       if (nl.boundary_fluxes) {
         const std::vector<double> sd(all_dn.begin() + k * per * nwav, all_dn.begin() + (k + 1) * per * nwav);
         const std::vector<double> tu(all_up.begin() + k * per * nwav, all_up.begin() + (k + 1) * per * nwav);
         o.write_slice(sw ? "spectral_flux_dn_direct_surf_sw" : "spectral_flux_dn_surf_lw", oc, sd);
+        if (rayleigh)
+          o.write_slice("spectral_flux_dn_surf_sw", oc, std::vector<double>(all_tot.begin() + k * per * nwav, all_tot.begin() + (k + 1) * per * nwav));
         o.write_slice("spectral_flux_up_toa" + x, oc, tu);
       }
     }

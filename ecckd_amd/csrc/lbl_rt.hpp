@@ -1,6 +1,6 @@
 // lbl_rt.hpp - the transfer of ONE wavenumber, written once for the line-by-line kernels (lbl_fluxes.hip,
 // lbl_gpoint_fluxes.hip, lbl_gpoint_fluxes_sw.hip, lbl_scenarios.hip: no scattering; lbl_fluxes_sw_rayleigh.hip,
-// lbl_gpoint_fluxes_sw_rayleigh.hip and k_rt_sw_gpoints_rayleigh of lbl_fluxes.hip: Rayleigh scattering; k_opt_forward_adjoint_rayleigh of optimize.hip takes the same
+// lbl_scenarios_sw_rayleigh.hip, lbl_gpoint_fluxes_sw_rayleigh.hip and k_rt_sw_gpoints_rayleigh of lbl_fluxes.hip: Rayleigh scattering; k_opt_forward_adjoint_rayleigh of optimize.hip takes the same
 // Rayleigh functions and their derivative rayleigh_layer_d), and the host plumbing they share.  DESIGN.md and the
 // tests compare these kernels with each other, bit for bit where they can: one source text keeps an edit from reaching only
 // one of them.  The files are compiled with the default contraction, so an expression here and in rt_device.hpp keeps its form
@@ -234,9 +234,10 @@ inline int make_chunks(const char* who, size_t nwav, int nband, const int64_t* b
   return ECCKD_OK;
 }
 
-// The host path of the band-flux entries (lbl_fluxes.hip, lbl_scenarios.hip, lbl_fluxes_sw_rayleigh.hip): an entry checks its
-// own arguments, then  band_start - band_device - per launch { its kernel, band_collect }.  Which launches there are, and the
-// kernel, stay with the entry; the workspace is the context's scratch, kept for the next call.
+// The host path of the band-flux entries (lbl_fluxes.hip, lbl_scenarios.hip, lbl_fluxes_sw_rayleigh.hip,
+// lbl_scenarios_sw_rayleigh.hip): an entry checks its own arguments, then  band_start - band_device - per launch { its kernel,
+// band_collect }.  Which launches there are, and the kernel, stay with the entry; the workspace is the context's scratch, kept
+// for the next call.
 struct BandRun {
   ecckd_ctx* ctx = nullptr;
   int nband = 0;

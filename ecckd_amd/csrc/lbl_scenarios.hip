@@ -31,6 +31,7 @@
 // one scenario.  The shortwave kernel is instantiated per number of angles of a launch (1..8), so that fluxes stay in registers.
 #include "common.hpp"
 #include "gpoint_bin.hpp"
+#include "lbl_gases.hpp"
 #include "lbl_rt.hpp"
 
 #include <algorithm>
@@ -41,37 +42,11 @@ namespace {
 
 using namespace ecckd::lbl;
 
-constexpr int LS_MAX_GAS = 16;
 constexpr int LS_LW_SLOTS = 8;
 constexpr int LS_SW_SLOTS = 16;
 constexpr size_t LS_LW_LDS = GF_ACC_BYTES;         // 43008: the accumulator budgets of the g-point kernels (gpoint_bin.hpp)
 constexpr size_t LS_SW_LDS = SF_ACC_BYTES;         // 59392
 static_assert(LS_LW_LDS == 43008 && LS_SW_LDS == 59392, "the slot counts of ecckd_lbl_scenarios_slots follow from these");
-
-// the gases' rows, by value in the kernel arguments: indexed with the (uniform) gas counter, so scalar loads
-struct GasRows {
-  const void* od[LS_MAX_GAS];
-  unsigned long long stride[LS_MAX_GAS];
-  int type[LS_MAX_GAS];
-};
-
-// tau[s] = sum over the gases, in gas order, of od_g * scale[s][g][l] (k_merge, merge.hip:36-38), s < ns
-template <int S>
-__device__ __forceinline__ void merged_tau(const GasRows& gr, int ngas, int nlay, int l, size_t j, int ns,
-                                           const double* __restrict__ scale, double (&tau)[S]) {
-  for (int g = 0; g < ngas; ++g) {
-    const size_t at = (size_t)l * gr.stride[g] + j;
-    const double x = gr.type[g] == ECCKD_F64 ? static_cast<const double*>(gr.od[g])[at]
-                                             : (double)static_cast<const float*>(gr.od[g])[at];
-    const double* sc = scale + (size_t)g * nlay + l;
-#pragma unroll
-    for (int s = 0; s < S; ++s)
-      if (s < ns) {
-        const double v = __dmul_rn(x, sc[(size_t)s * ngas * nlay]);
-        tau[s] = g == 0 ? v : __dadd_rn(tau[s], v);
-      }
-  }
-}
 
 // LDS: acc[4][ns][2*nhl]
 __global__ void __launch_bounds__(LBL_THREADS)
@@ -252,21 +227,6 @@ k_lbl_scenarios_sw(int nlay, int ngas, GasRows gr, int ns, const double* __restr
 int slots_per_launch(bool sw, int nlay) {
   const size_t per_slot = (size_t)4 * 2 * ((size_t)nlay + 1) * sizeof(double);
   return (int)std::min<size_t>(sw ? LS_SW_SLOTS : LS_LW_SLOTS, (sw ? LS_SW_LDS : LS_LW_LDS) / per_slot);
-}
-
-int check_gases(const char* who, int ngas, const void* const* d_od, const int* od_type, const size_t* od_stride, size_t nwav,
-                int nscen, const double* h_scale, GasRows& gr) {
-  ECCKD_REQUIRE(ngas >= 1 && ngas <= LS_MAX_GAS, "%s: ngas (%d) must be between 1 and %d", who, ngas, LS_MAX_GAS);
-  ECCKD_REQUIRE(nscen >= 1, "%s: nscen (%d) must be at least 1", who, nscen);
-  ECCKD_REQUIRE(d_od && od_type && od_stride && h_scale, "%s: NULL argument", who);
-  for (int g = 0; g < LS_MAX_GAS; ++g) { gr.od[g] = nullptr; gr.stride[g] = 0; gr.type[g] = ECCKD_F64; }
-  for (int g = 0; g < ngas; ++g) {
-    ECCKD_REQUIRE(d_od[g], "%s: d_od[%d] is NULL", who, g);
-    ECCKD_REQUIRE(od_type[g] == ECCKD_F32 || od_type[g] == ECCKD_F64, "%s: od_type[%d] must be 4 or 8", who, g);
-    ECCKD_REQUIRE(od_stride[g] >= nwav, "%s: od_stride[%d] (%zu) < nwav (%zu)", who, g, od_stride[g], nwav);
-    gr.od[g] = d_od[g]; gr.stride[g] = od_stride[g]; gr.type[g] = od_type[g];
-  }
-  return ECCKD_OK;
 }
 
 template <int A>

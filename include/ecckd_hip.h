@@ -566,6 +566,34 @@ int ecckd_lbl_band_fluxes_sw_scenarios(ecckd_ctx* ctx, int nlay, size_t nwav, in
 /* Slots per launch of the two calls above at nlay layers (0: more layers than the accumulator holds; no device needed). */
 int ecckd_lbl_scenarios_slots(int shortwave, int nlay);
 
+/* ecckd_lbl_band_fluxes_sw_rayleigh for nscen SCENARIOS from one read of the gases' spectra.  d_od[ngas], od_type, od_stride and
+ * h_scale[nscen][ngas][nlay] are the absorbers and their scaling profiles as ecckd_lbl_band_fluxes_sw_scenarios takes them
+ * (1 <= ngas <= 16); d_od_ray [nlay][ray_stride], ECCKD_F32 or ECCKD_F64, is what scatters, the same unscaled row in every
+ * scenario.  Scenario s at angle a is what ngas calls of ecckd_merge_spectrum_dev with h_scale[s] followed by
+ * ecckd_lbl_band_fluxes_sw_rayleigh on that DOUBLE matrix and d_od_ray give: tau_abs = sum_g od_g * scale[s][g][level] in gas
+ * order as ecckd_lbl_band_fluxes_sw_scenarios forms it (bit for bit the matrix with one gas; with more, the product and sum of
+ * a gas may be fused where the merge kernel rounds twice: a few 1e-14 of the incoming flux), formed once per
+ * scenario in the kernel and never written as a matrix; tau = tau_abs + (double)od_ray, added once; the same layer terms,
+ * adding sweeps and reduction order.  nsza = 1..8, every cos_sza in (0, 1]; d_albedo[nwav] or NULL (albedo 0).  Results:
+ * h_flux_dn_direct, h_flux_dn (direct plus diffuse), h_flux_up [nscen][nsza][nband][nlay+1]; d_surf_dn_direct, d_surf_dn,
+ * d_toa_up: NULL or device arrays [nscen][nsza][nwav], zero outside the bands.
+ * Launch split: the chunk partials of a launch are nchunk x ns x nsza x 3 x (nlay+1) doubles (nchunk: 256-wavenumber chunks of
+ * the bands), so a launch takes ns = ecckd_lbl_rayleigh_scenarios_per_launch(nlay, nsza, nchunk) whole scenarios with all their
+ * angles: as many as fit 512 MB of partials (ECCKD_RAYLEIGH_SCENARIO_BYTES = N bytes instead), one at least.  Per-level state
+ * lives in the context's scratch, 4 (nlay+1) doubles per thread of a bounded grid (4 blocks per compute unit;
+ * ECCKD_RAYLEIGH_GRID = N blocks instead).
+ * Bit equality: scenario s (and angle a) of a call has the bits of that scenario (and angle) computed by a call of its own;
+ * neither the scenarios that share a launch, nor the grid, nor which block walks a chunk changes a bit of any result. */
+int ecckd_lbl_band_fluxes_sw_rayleigh_scenarios(ecckd_ctx* ctx, int nlay, size_t nwav, int nsza, const double* h_cos_sza,
+                                                const double* d_ssi, const double* d_albedo, int ngas, const void* const* d_od,
+                                                const int* od_type, const size_t* od_stride, const void* d_od_ray, int ray_type,
+                                                size_t ray_stride, int nscen, const double* h_scale, int nband,
+                                                const int64_t* h_band_begin, const int64_t* h_band_end, double* h_flux_dn_direct,
+                                                double* h_flux_dn, double* h_flux_up, double* d_surf_dn_direct, double* d_surf_dn,
+                                                double* d_toa_up);
+/* Scenarios per launch of the call above under the current budget (0: nlay or nsza below 1; no device needed). */
+int ecckd_lbl_rayleigh_scenarios_per_launch(int nlay, int nsza, size_t nchunk);
+
 /* ---- NetCDF classic files (file parts of a1, a9, a21) ----------------------------
  * A self-contained reader / writer for the classic on-disk formats CDF-1, CDF-2 (64-bit offset)
  * and CDF-5 (64-bit data): what the reference reads / writes for *.nc, *.cdf names

@@ -1,5 +1,5 @@
 """SHA-256 of everything the line-by-line flux entry points return, at the smallest shapes where each piece of their kernels can
-go wrong (csrc/lbl_fluxes.hip, lbl_gpoint_fluxes.hip, lbl_gpoint_fluxes_sw.hip, lbl_scenarios.hip, lbl_fluxes_sw_rayleigh.hip, lbl_gpoint_fluxes_sw_rayleigh.hip), and of every band entry with every band empty: a change that is meant to
+go wrong (csrc/lbl_fluxes.hip, lbl_gpoint_fluxes.hip, lbl_gpoint_fluxes_sw.hip, lbl_scenarios.hip, lbl_fluxes_sw_rayleigh.hip, lbl_gpoint_fluxes_sw_rayleigh.hip, lbl_scenarios_sw_rayleigh.hip), and of every band entry with every band empty: a change that is meant to
 leave their arithmetic alone is run once on the build before it and once on the build after it, on the same GPU, and every
 digest has to be equal.  profiles/lbl_digests.json holds the output of the build it was committed with; a ROCm math-library
 update may change digests legitimately, which is why this is a tool and not a test.
@@ -139,6 +139,8 @@ with api.Context(0) as ctx:
     out["empty band_sw_rayleigh"] = digest(*api.lbl_band_fluxes_sw_rayleigh(ctx, ANGLES[3], ssi, d_od, d_od, begin, end, boundary=True))
     out["empty scenarios_lw"] = digest(*api.lbl_band_fluxes_lw_scenarios(ctx, t_hl, d_wn, d_dwn, [d_od], one, begin, end, boundary=True))
     out["empty scenarios_sw"] = digest(*api.lbl_band_fluxes_sw_scenarios(ctx, ANGLES[3], ssi, [d_od], one, begin, end, boundary=True))
+    out["empty scenarios_sw_rayleigh"] = digest(*api.lbl_band_fluxes_sw_rayleigh_scenarios(ctx, ANGLES[3], ssi, [d_od], d_od, one, begin, end,
+                                                                                          boundary=True))
 
     # scenarios: a FLOAT and a DOUBLE gas; longwave 11 scenarios (two launches at 8 slots); shortwave 7 scenarios with 1 and 5
     # angles (3 scenarios per launch); 130 layers: 5 longwave scenarios per launch, and the 8 angles of one shortwave scenario
@@ -162,5 +164,11 @@ with api.Context(0) as ctx:
             for alb in (albedo,) if nlay == 130 else (None, albedo):
                 out[f"scenarios_sw {nlay} nscen={nscen} nsza={len(mu)} albedo={alb is not None}"] = digest(*api.lbl_band_fluxes_sw_scenarios(
                     ctx, mu, ssi, ods, scales(nscen, 2, nlay, 5), begin, end, albedo=alb, boundary=True))
+        # with Rayleigh scattering: the same absorbers and scalings, a float32 row that scatters; 1 and 5 angles, with albedo
+        if nlay != 130:
+            d_ray = dev(syn.optical_depth(np, p, wn, syn.SEED_BASE + 7, nlines=6, column_scale=0.3, lo=250.0, hi=50000.0).astype("float32"))
+            for mu in (ANGLES[1], ANGLES[5]):
+                out[f"scenarios_sw_rayleigh {nlay} nscen={nscen} nsza={len(mu)}"] = digest(*api.lbl_band_fluxes_sw_rayleigh_scenarios(
+                    ctx, mu, ssi, ods, d_ray, scales(nscen, 2, nlay, 5), begin, end, albedo=albedo, boundary=True))
 
 print(json.dumps(out, indent=1))
