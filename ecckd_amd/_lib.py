@@ -183,6 +183,11 @@ SIGNATURES = {
                                              _c_double_p, _c_double_p, _c_double_p]),
     "ecckd_lbl_spectral_fluxes_lw": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _c_double_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, _c_double_p, _c_double_p]),
+    "ecckd_lbl_gpoint_fluxes_lw_angles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _c_double_p, C.c_void_p, C.c_int, C.c_size_t,
+                                                    _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "ecckd_lbl_spectral_fluxes_lw_angles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, _c_double_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                      _c_double_p, _c_double_p]),
     "ecckd_lbl_gpoint_fluxes_sw": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                              C.c_size_t, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
     "ecckd_lbl_spectral_fluxes_sw": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_int, _c_double_p, C.c_void_p, C.c_void_p,

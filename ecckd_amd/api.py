@@ -1209,9 +1209,10 @@ def lbl_band_fluxes_lw(ctx, temperature_hl, wavenumber, d_wavenumber, optical_de
     return dn, up
 
 
-def lbl_spectral_fluxes_lw(ctx, temperature_hl, wavenumber, d_wavenumber, optical_depth):
+def lbl_spectral_fluxes_lw(ctx, temperature_hl, wavenumber, d_wavenumber, optical_depth, nangle=0):
     """Line-by-line longwave spectral fluxes of one column (lw_spectra.cpp:222-237): device tensors in ->
-    (flux_dn, flux_up) FLOAT device tensors (nlay+1, nwav), (bb_dn, bb_up) host arrays (nlay+1,) summed in double."""
+    (flux_dn, flux_up) FLOAT device tensors (nlay+1, nwav), (bb_dn, bb_up) host arrays (nlay+1,) summed in double.
+    nangle as in lbl_band_fluxes_lw: 0 the two-stream form, N > 0 N Gauss-Legendre zenith angles per hemisphere."""
     t = _f64c(temperature_hl)
     nlay = t.size - 1
     torch = _torch()
@@ -1221,9 +1222,9 @@ def lbl_spectral_fluxes_lw(ctx, temperature_hl, wavenumber, d_wavenumber, optica
     bdn, bup = np.empty(nlay + 1), np.empty(nlay + 1)
     stride = optical_depth.stride(0) if nlay > 1 else nwav
     ctx.fence_from_torch()
-    check(ctx.lib.ecckd_lbl_spectral_fluxes_lw(ctx.handle, nlay, nwav, _hptr(t), _dptr(wavenumber), _dptr(d_wavenumber),
-                                               _dptr(optical_depth), _od_type(optical_depth), stride, _dptr(dn), _dptr(up),
-                                               nwav, _hptr(bdn), _hptr(bup)))
+    check(ctx.lib.ecckd_lbl_spectral_fluxes_lw_angles(ctx.handle, int(nangle), nlay, nwav, _hptr(t), _dptr(wavenumber),
+                                                      _dptr(d_wavenumber), _dptr(optical_depth), _od_type(optical_depth), stride,
+                                                      _dptr(dn), _dptr(up), nwav, _hptr(bdn), _hptr(bup)))
     ctx.synchronize()
     return dn, up, bdn, bup
 
@@ -1550,17 +1551,18 @@ class GPointMap:
                                            _hptr(out)))
         return out
 
-    def lbl_fluxes_lw(self, temperature_hl, optical_depth):
+    def lbl_fluxes_lw(self, temperature_hl, optical_depth, nangle=0):
         """Line-by-line longwave fluxes of one column per g point, fused (lw_spectra.cpp:222-257): device tensor optical_depth
-        (nlay, nwav) -> (flux_dn, flux_up) each (nlay+1, ng), (bb_dn, bb_up) each (nlay+1,): the sums over ALL wavenumbers."""
+        (nlay, nwav) -> (flux_dn, flux_up) each (nlay+1, ng), (bb_dn, bb_up) each (nlay+1,): the sums over ALL wavenumbers.
+        nangle as in lbl_band_fluxes_lw: 0 the two-stream form, N > 0 N Gauss-Legendre zenith angles per hemisphere."""
         t = _f64c(temperature_hl)
         nlay = t.size - 1
         dn, up = np.empty((nlay + 1, self.ng)), np.empty((nlay + 1, self.ng))
         bdn, bup = np.empty(nlay + 1), np.empty(nlay + 1)
         stride = optical_depth.stride(0) if nlay > 1 else self.nwav
         self.ctx.fence_from_torch()
-        check(self.lib.ecckd_lbl_gpoint_fluxes_lw(self.handle, nlay, _hptr(t), _dptr(optical_depth), _od_type(optical_depth),
-                                                  stride, _hptr(dn), _hptr(up), _hptr(bdn), _hptr(bup)))
+        check(self.lib.ecckd_lbl_gpoint_fluxes_lw_angles(self.handle, int(nangle), nlay, _hptr(t), _dptr(optical_depth),
+                                                         _od_type(optical_depth), stride, _hptr(dn), _hptr(up), _hptr(bdn), _hptr(bup)))
         return dn, up, bdn, bup
 
     def lbl_fluxes_sw(self, cos_sza, ssi, optical_depth, albedo=None):

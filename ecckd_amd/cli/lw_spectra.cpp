@@ -6,8 +6,11 @@
 // together with the optical depth (per wavenumber, or averaged to the g points by transmission).
 // Keys: output (mandatory), input / scaling / conc / conc_input as read_merged_spectrum reads them, gpoints, iprofile,
 // log_level, prepend_path, append_path.  `column` is the unlimited dimension (:132), in classic and in NetCDF-4 (*.h5) files.
-// The fluxes come from ecckd_lbl_gpoint_fluxes_lw / ecckd_lbl_spectral_fluxes_lw, the g-point optical depths from
-// ecckd_average_to_gpoints (include/ecckd_hip.h).
+// Not in the reference: nangle=N (0..16, default 0), the CKDMIP tool's key (test/run_ckd_lw.sh:28).  0 is the reference's
+// two-stream form (diffusivity 1.66); N > 0 integrates N Gauss-Legendre zenith angles per hemisphere, in both output modes, and
+// the file then carries the global attribute `nangle`; the other variables do not depend on the key.
+// The fluxes come from ecckd_lbl_gpoint_fluxes_lw_angles / ecckd_lbl_spectral_fluxes_lw_angles, the g-point optical depths
+// from ecckd_average_to_gpoints (include/ecckd_hip.h).
 #include "spectra.hpp"
 
 int main(int argc, char** argv) { return spectra_main(argc, argv, false); }

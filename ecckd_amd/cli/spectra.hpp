@@ -48,6 +48,11 @@ inline int spectra_main(int argc, char** argv, bool sw) {
     // rayleigh=FILE (shortwave): a spectrum file whose optical_depth scatters, beside the merged absorbers (two-stream transfer)
     const bool rayleigh = config.read(rayleigh_file_name, "rayleigh");
     if (rayleigh && !sw) fail(ECCKD_PARAMETER_ERROR, "\"rayleigh\" is a key of sw_spectra: the longwave fluxes do not scatter");
+    // nangle=N (longwave): N Gauss-Legendre zenith angles per hemisphere in place of the two-stream form (0), the CKDMIP tool's key
+    int nangle = 0;
+    const bool have_nangle = config.read(nangle, "nangle");
+    if (have_nangle && sw) fail(ECCKD_PARAMETER_ERROR, "\"nangle\" is a key of lw_spectra: the shortwave angles are cos_solar_zenith_angle");
+    if (nangle < 0 || nangle > 16) fail(ECCKD_PARAMETER_ERROR, "nangle = %d outside 0..16", nangle);
     const int nmu = sw ? (int)mu0.size() : 1;   // rows of fluxes per column
     SearchPath paths;
     paths.configure(config);
@@ -161,6 +166,7 @@ inline int spectra_main(int argc, char** argv, bool sw) {
         file.att(molecules, "molecules");
         file.att(config.str(), "config");
         if (rayleigh) file.att("two-stream", "rayleigh_scattering");
+        if (nangle > 0) file.att_int(nangle, "nangle");
         file.end_define();
         if (sw) file.write("mu0", mu0);
         if (!have_gpoints) file.write("wavenumber", m.first.wavenumber_cm_1);
@@ -228,8 +234,9 @@ inline int spectra_main(int argc, char** argv, bool sw) {
         file.write_slice(bb_up_name, irec, bb_up);
         file.write_slice("optical_depth", irec, download_od(dev, m, (size_t)nlay * nwav));
       } else if (!have_gpoints) {
-        ck(ecckd_lbl_spectral_fluxes_lw(dev.ctx(), nlay, nwav, t.data(), d_wn.as<double>(), d_dwn.as<double>(), m.od_ptr(), m.od_type(), nwav,
-                                        d_spec_dn.as<float>(), d_spec_up.as<float>(), nwav, bb_dn.data(), bb_up.data()));
+        ck(ecckd_lbl_spectral_fluxes_lw_angles(dev.ctx(), nangle, nlay, nwav, t.data(), d_wn.as<double>(), d_dwn.as<double>(), m.od_ptr(),
+                                               m.od_type(), nwav, d_spec_dn.as<float>(), d_spec_up.as<float>(), nwav, bb_dn.data(),
+                                               bb_up.data()));
         file.write_slice(bb_dn_name, irec, bb_dn);                                            // :231-232
         file.write_slice(bb_up_name, irec, bb_up);
         file.write_slice("optical_depth", irec, download_od(dev, m, (size_t)nlay * nwav));
@@ -246,7 +253,8 @@ inline int spectra_main(int argc, char** argv, bool sw) {
           ck(ecckd_lbl_gpoint_fluxes_sw(gmap, nlay, nmu, mu0.data(), d_ssi.as<double>(), d_albedo.as<double>(), m.od_ptr(), m.od_type(),
                                         nwav, dn.data(), up.data(), bb_dn.data(), bb_up.data()));
         } else {
-          ck(ecckd_lbl_gpoint_fluxes_lw(gmap, nlay, t.data(), m.od_ptr(), m.od_type(), nwav, dn.data(), up.data(), bb_dn.data(), bb_up.data()));
+          ck(ecckd_lbl_gpoint_fluxes_lw_angles(gmap, nangle, nlay, t.data(), m.od_ptr(), m.od_type(), nwav, dn.data(), up.data(),
+                                               bb_dn.data(), bb_up.data()));
           t_fl.resize(nlay);          // the Planck weight at the pressure-weighted full-level temperature (:242-251)
           for (int l = 0; l < nlay; ++l) {
             const double p_fl = 0.5 * (p[l] + p[l + 1]);

@@ -291,6 +291,10 @@ class NcOut {
   void att(const std::string& text, const std::string& name, const char* var = nullptr) {
     ck(ecckd_nc_put_att_text(f_, var, name.c_str(), text.c_str()));
   }
+  void att_int(int value, const std::string& name, const char* var = nullptr) {
+    const double v = value;
+    ck(ecckd_nc_put_att_double(f_, var, name.c_str(), NC_INT_T, 1, &v));
+  }
   // OutputDataFile::deflate_variable (:345-359): shuffle + deflate level 2 where the file is NetCDF-4 (*.h5 / *.hdf), nothing otherwise
   void deflate(const std::string& name) { ck(ecckd_nc_deflate_var(f_, name.c_str())); }
   void end_define() { ck(ecckd_nc_enddef(f_)); }

@@ -680,6 +680,10 @@ def write_lw_spectra(path, s, config_str="", history=None):
     w.write_attribute("history", history or "")
     w.write_attribute("molecules", s["molecules"])
     w.write_attribute("config", config_str)
+    if s.get("nangle", 0) > 0:                                                                 # (int, as the tool writes it)
+        v = np.array([s["nangle"]], dtype=np.float64)
+        check(w.lib.ecckd_nc_put_att_double(w.handle, _b(None), _b("nangle"), NC_TYPES["int"], 1,
+                                            v.ctypes.data_as(C.POINTER(C.c_double))))
     w.end_define_mode()
     if not have_g:
         w.write("wavenumber", s["wavenumber"])

@@ -931,11 +931,13 @@ def merge_spectra(ctx, inputs, output_path=None, scaling=None, conc=None, config
     return out
 
 
-def lw_spectra(ctx, inputs, output_path=None, scaling=None, conc=None, g_point=None, iprofile=None, config_str="", history=None):
+def lw_spectra(ctx, inputs, output_path=None, scaling=None, conc=None, g_point=None, iprofile=None, config_str="", history=None,
+               nangle=0):
     """lw_spectra.cpp:31-275 as bin/lw_spectra does it: per column the merged spectrum, then either the spectral fluxes
     (ecckd_lbl_spectral_fluxes_lw) or, with g_point (one value per wavenumber, -1 = none), the fluxes per g point
     (ecckd_lbl_gpoint_fluxes_lw) and the optical depth averaged by transmission with the Planck weight at the pressure-weighted
-    full-level temperature (ecckd_average_to_gpoints, reference_surface_vmr = 0).  Arrays are returned in double as the library
+    full-level temperature (ecckd_average_to_gpoints, reference_surface_vmr = 0).  nangle (the tool's key): 0 the two-stream
+    fluxes, N > 0 those of N Gauss-Legendre zenith angles per hemisphere.  Arrays are returned in double as the library
     gives them (the tool's file holds their FLOAT casts): dict of (nrec, ...) arrays; written to output_path when given."""
     import torch
     names = ("pressure_hl", "temperature_hl", "vmr_fl", "flux_dn_lw", "flux_up_lw", "optical_depth", "spectral_flux_dn_lw",
@@ -959,12 +961,12 @@ def lw_spectra(ctx, inputs, output_path=None, scaling=None, conc=None, g_point=N
         out["temperature_hl"].append(t)
         out["vmr_fl"].append(vmr)
         if not have_g:
-            sdn, sup, bdn, bup = api.lbl_spectral_fluxes_lw(ctx, t, d_wn, d_dwn, od)
+            sdn, sup, bdn, bup = api.lbl_spectral_fluxes_lw(ctx, t, d_wn, d_dwn, od, nangle=nangle)
             out["optical_depth"].append(od.cpu().numpy().astype(np.float64))
             out["spectral_flux_dn_lw"].append(sdn.cpu().numpy().astype(np.float64))
             out["spectral_flux_up_lw"].append(sup.cpu().numpy().astype(np.float64))
         else:
-            dn, up, bdn, bup = gm.lbl_fluxes_lw(t, od)
+            dn, up, bdn, bup = gm.lbl_fluxes_lw(t, od, nangle=nangle)
             p_fl = 0.5 * (p[:-1] + p[1:])
             t_fl = 0.5 * (t[:-1] * p[:-1] + t[1:] * p[1:]) / p_fl                              # :242-244
             od_g, _, _ = gm.average_optical_depth(p, od, "transmission", 0.0, temperature_fl=t_fl)
@@ -981,6 +983,7 @@ def lw_spectra(ctx, inputs, output_path=None, scaling=None, conc=None, g_point=N
     for k in names:
         out[k] = np.stack(out[k])
     out["ng"] = ng
+    out["nangle"] = int(nangle)
     if output_path is not None:
         ncio.write_lw_spectra(output_path, out, config_str=config_str, history=history)
     return out

@@ -969,6 +969,19 @@ int ecckd_lbl_spectral_fluxes_lw(ecckd_ctx* ctx, int nlay, size_t nwav, const do
                                  const double* d_wavenumber, const double* d_d_wavenumber, const void* d_od, int od_type,
                                  size_t od_stride, float* d_flux_dn, float* d_flux_up, size_t flux_stride, double* h_bb_dn,
                                  double* h_bb_up);
+/* Both with the zenith-angle quadrature of ecckd_lbl_band_fluxes_lw_angles: nangle = 0 is the two entry points above, bit for
+ * bit; nangle = N in 1..16 integrates N Gauss-Legendre angles per hemisphere, flux = sum_k 2 w_k mu_k L(mu_k) formed in angle
+ * order per wavenumber and level before it is binned or written.  A thread carries the N intensities of its wavenumber through
+ * ONE walk of the layers (one load of the optical depth and one Planck function per level for all angles), so the
+ * accumulator, the limits and the launch split above do not depend on nangle.  nangle outside 0..16: PARAMETER_ERROR before
+ * any launch. */
+int ecckd_lbl_gpoint_fluxes_lw_angles(ecckd_gmap* gmap, int nangle, int nlay, const double* h_temperature_hl, const void* d_od,
+                                      int od_type, size_t od_stride, double* h_flux_dn, double* h_flux_up, double* h_bb_dn,
+                                      double* h_bb_up);
+int ecckd_lbl_spectral_fluxes_lw_angles(ecckd_ctx* ctx, int nangle, int nlay, size_t nwav, const double* h_temperature_hl,
+                                        const double* d_wavenumber, const double* d_d_wavenumber, const void* d_od, int od_type,
+                                        size_t od_stride, float* d_flux_dn, float* d_flux_up, size_t flux_stride, double* h_bb_dn,
+                                        double* h_bb_up);
 /* Line-by-line shortwave fluxes of one column resolved per g point, for nsza (1..8) solar zenith angles in one call:
  * radiative_transfer_direct_sw / _norayleigh_sw (radiative_transfer_sw.cpp:26-77, the arithmetic of ecckd_lbl_band_fluxes_sw) and,
  * in the same pass over the optical depths, h_flux_*[nsza][nlay+1][ng] = the sum of the spectral flux at each half level over
