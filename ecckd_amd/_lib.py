@@ -117,6 +117,9 @@ SIGNATURES = {
     "ecckd_opt_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "ecckd_opt_create_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint, C.POINTER(C.c_void_p)]),
     "ecckd_opt_destroy": (C.c_int, [C.c_void_p]),
+    "ecckd_opt_create_angles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint, C.c_int,
+                                          C.POINTER(C.c_void_p)]),
+    "ecckd_opt_nangle": (C.c_int, [C.c_void_p]),
     "ecckd_opt_nx": (C.c_size_t, [C.c_void_p]),
     "ecckd_opt_initial_state": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, _c_double_p]),
     "ecckd_opt_cost_grad": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, _c_double_p]),

@@ -920,11 +920,17 @@ class Optimizer:
     optimize_rayleigh: the ng Rayleigh coefficients are optimised too (ECCKD_OPT_RAYLEIGH_ACTIVE), with either forward model:
         the state carries ng more elements ln(rayleigh_molar_scattering) behind the gases', without bounds; every gas may be
         inactive.  rayleigh_prior_error: sigma of their prior 0.5 sum d^2 / sigma^2, gradient included; <= 0: no prior.
+    nangle: N in 1..16: the longwave forward model integrates N Gauss-Legendre zenith angles per hemisphere
+        (ecckd_opt_create_angles), the transfer of the line-by-line truth made with the same nangle and of
+        rt_lw_gpoints(nangle=N); 0: the two-stream form at the diffusivity 1.66, the handle it has always been.  Longwave models
+        only, and not with the Rayleigh switches.
     """
 
-    def __init__(self, ctx, model, scenes, rayleigh_scattering=False, optimize_rayleigh=False, rayleigh_prior_error=0.0, **cfg):
+    def __init__(self, ctx, model, scenes, rayleigh_scattering=False, optimize_rayleigh=False, rayleigh_prior_error=0.0, nangle=0,
+                 **cfg):
         self.ctx = ctx
         self.lib = ctx.lib
+        self.nangle = int(nangle)
         self.rayleigh_scattering = bool(rayleigh_scattering)
         self.optimize_rayleigh = bool(optimize_rayleigh)
         keep = []
@@ -941,9 +947,9 @@ class Optimizer:
         for k, v in defaults.items():
             setattr(c, k, float(v))
         h = C.c_void_p()
-        check(self.lib.ecckd_opt_create_ex(ctx.handle, C.byref(m), len(scenes), C.cast(sc, C.c_void_p), C.byref(c),
-                                           (OPT_RAYLEIGH_SCATTERING if rayleigh_scattering else 0) |
-                                           (OPT_RAYLEIGH_ACTIVE if optimize_rayleigh else 0), C.byref(h)))
+        check(self.lib.ecckd_opt_create_angles(ctx.handle, C.byref(m), len(scenes), C.cast(sc, C.c_void_p), C.byref(c),
+                                               (OPT_RAYLEIGH_SCATTERING if rayleigh_scattering else 0) |
+                                               (OPT_RAYLEIGH_ACTIVE if optimize_rayleigh else 0), self.nangle, C.byref(h)))
         self.handle = h
         if optimize_rayleigh:
             self.set_rayleigh_prior(rayleigh_prior_error)
@@ -1032,10 +1038,11 @@ class Optimizer:
         """The forward kernel the next cost_grad / forward of this handle launches (ecckd_opt_forward_plan), at the environment
         as it is now: dict(kernel, cells: bool, nc_template, nb, threads, ngpad, lgroups, lds_bytes, rayleigh: bool).  kernel
         names what the header's `cells` encodes: "general" (0), "cells" (1: the cell-parallel kernel, the only one for which
-        cells is True and nc_template / nb mean something) or "rayleigh" (2: the one kernel of a scattering handle)."""
+        cells is True and nc_template / nb mean something), "rayleigh" (2: the one kernel of a scattering handle) or "lw_angles"
+        (3: the one kernel of a handle made with nangle > 0)."""
         p = _lib.ForwardPlan()
         check(self.lib.ecckd_opt_forward_plan(self.handle, C.byref(p)))
-        return dict(kernel=("general", "cells", "rayleigh")[p.cells], cells=p.cells == 1, nc_template=p.nc_template, nb=p.nb,
+        return dict(kernel=("general", "cells", "rayleigh", "lw_angles")[p.cells], cells=p.cells == 1, nc_template=p.nc_template, nb=p.nb,
                     threads=p.threads, ngpad=p.ngpad, lgroups=p.lgroups, lds_bytes=int(p.lds_bytes), rayleigh=p.cells == 2)
 
     def forward(self, x, unclamped=False):
@@ -1289,6 +1296,19 @@ def lbl_band_fluxes_sw_rayleigh(ctx, cos_sza, ssi, optical_depth, rayleigh_optic
         ctx.synchronize()
         return (direct, dn, up, *bnd)
     return direct, dn, up
+
+
+def rt_lw_gpoints(ctx, planck_hl, optical_depth, nangle=0):
+    """Longwave fluxes per g point from what run_ckd wrote (ecckd_rt_lw_gpoints, unit surface emissivity): host arrays
+    planck_hl (ncol, nlay+1, ng) and optical_depth (ncol, nlay, ng) -> (flux_dn, flux_up), each (ncol, nlay+1, ng).  nangle = 0:
+    the two-stream form at the diffusivity 1.66; N in 1..16: N Gauss-Legendre zenith angles per hemisphere."""
+    od, pl = _f64c(optical_depth), _f64c(planck_hl)
+    if od.ndim != 3 or pl.shape != (od.shape[0], od.shape[1] + 1, od.shape[2]):
+        raise ValueError("optical_depth must be (ncol, nlay, ng) and planck_hl (ncol, nlay+1, ng)")
+    ncol, nlay, ng = od.shape
+    dn, up = np.empty((ncol, nlay + 1, ng)), np.empty((ncol, nlay + 1, ng))
+    check(ctx.lib.ecckd_rt_lw_gpoints(ctx.handle, int(nangle), ncol, nlay, ng, _hptr(pl), _hptr(od), _hptr(dn), _hptr(up)))
+    return dn, up
 
 
 def rt_sw_gpoints_rayleigh(ctx, cos_sza, albedo, incoming, optical_depth, rayleigh_optical_depth):

@@ -25,9 +25,16 @@
 // truth's downwelling flux is then the total one (band_flux_dn_sw, or spectral_flux_dn_sw), the per-g surface flux comes
 // from spectral_flux_dn_surf_sw, the band albedo is sum(up) / sum(total dn) at the surface, nothing is masked
 // (max_no_rayleigh_wavenumber is read and ignored) and relative_to is evaluated through a scattering handle.
+// nangle (int, default 0; not a key of the reference): N in 1..16 trains a longwave model under the zenith-angle quadrature of
+// the CKDMIP tools (ecckd_opt_create_angles): N Gauss-Legendre angles per hemisphere, the transfer `ckdmip_lw` with nangle = N
+// made the truth with and `ckdmip_lw --ckd` with nangle = N evaluates the result with; relative_to goes through such a handle
+// as well.  0: the two-stream form at the diffusivity 1.66.  Refused (exit 147) right after the configuration is read, before
+// the device is opened: a value outside 0..16, nangle > 0 with a shortwave input, and a training_input or relative_to file whose
+// global integer attribute `nangle` differs from the key (a file without the attribute is accepted).
 // The cost function, its gradient and the L-BFGS iteration run on the GPU (ecckd_opt_*); adept::Minimizer is
 // replaced by the library's own L-BFGS, so iteration counts differ from the reference's.
 #include <algorithm>
+#include <cmath>
 
 #include "ckd_file.hpp"
 
@@ -323,6 +330,9 @@ int main(int argc, char** argv) {
     if (rayleigh_prior_error > 0.0 && !key_optimize_rayleigh)
       fail(ECCKD_PARAMETER_ERROR, "rayleigh_prior_error > 0 (optimised Rayleigh scattering) is not supported by this tool without optimize_rayleigh=1");
     const bool optimize_rayleigh = key_optimize_rayleigh;
+    int nangle = 0;
+    config.read(nangle, "nangle");
+    if (nangle < 0 || nangle > 16) fail(ECCKD_PARAMETER_ERROR, "nangle = %d outside 0..16", nangle);
     const bool rayleigh_listed = optimize_rayleigh && std::find(gas_list.begin(), gas_list.end(), "rayleigh") != gas_list.end();
     // a list holding only "rayleigh": no gas is active (the name matches none); the relative-to handle, made without the flag,
     // then takes every gas, as it would from no list
@@ -343,6 +353,24 @@ int main(int argc, char** argv) {
       else LOG("Optimizing Rayleigh scattering coefficients without a prior\n");
     }
     const unsigned opt_flags = rayleigh_scattering ? ECCKD_OPT_RAYLEIGH_SCATTERING : 0u;
+    if (nangle > 0 && model.is_sw) fail(ECCKD_PARAMETER_ERROR, "nangle = %d needs a longwave CKD model, %s is a shortwave one", nangle, input.c_str());
+    {
+      // a file made under another quadrature would be a silent science error; checked before the device is opened
+      std::vector<std::string> flux_files = config.read_list("training_input");
+      std::string rel_name;
+      if (config.read(rel_name, "relative_to")) flux_files.push_back(rel_name);
+      for (const std::string& name : flux_files) {
+        const std::string path = paths.find(name);
+        NcIn f(path);
+        int n = -1;
+        double v = 0.0;
+        ck(ecckd_nc_read_att_double(f.handle(), nullptr, "nangle", &n, &v, 1));
+        if (n >= 1 && (int)std::lround(v) != nangle)
+          fail(ECCKD_PARAMETER_ERROR, "%s was made with nangle = %d, the key nangle says %d", path.c_str(), (int)std::lround(v), nangle);
+      }
+    }
+    if (nangle > 0) LOG("Longwave forward model: %d Gauss-Legendre zenith angles per hemisphere (nangle = %d)\n", nangle, nangle);
+    else if (!model.is_sw) LOG("Longwave forward model: two-stream, diffusivity 1.66 (nangle = 0)\n");
     for (const std::string& g : gas_list) {
       bool found = optimize_rayleigh && g == "rayleigh";
       for (const GasTable& t : model.gases) found = found || t.name == g;
@@ -412,7 +440,7 @@ int main(int argc, char** argv) {
       make_model(model, only_rayleigh ? std::vector<std::string>() : gas_list, rel.iband_per_g, mv);
       ecckd_opt_scene sv = scene_view(rel);
       ecckd_opt* ro = nullptr;
-      ck(ecckd_opt_create_ex(dev.ctx(), &mv.m, 1, &sv, &oc, opt_flags, &ro));
+      ck(ecckd_opt_create_angles(dev.ctx(), &mv.m, 1, &sv, &oc, opt_flags, nangle, &ro));
       std::vector<double> x0(ecckd_opt_nx(ro));
       ck(ecckd_opt_initial_state(ro, x0.data(), nullptr, nullptr));
       rel_flux.resize((size_t)rel.ncol * 2 * (rel.nlay + 1) * model.ng);
@@ -445,7 +473,8 @@ int main(int argc, char** argv) {
     std::vector<ecckd_opt_scene> views;
     for (const Scene& s : scenes) views.push_back(scene_view(s));
     ecckd_opt* opt = nullptr;
-    ck(ecckd_opt_create_ex(dev.ctx(), &mv.m, (int)views.size(), views.data(), &oc, opt_flags | (optimize_rayleigh ? ECCKD_OPT_RAYLEIGH_ACTIVE : 0u), &opt));
+    ck(ecckd_opt_create_angles(dev.ctx(), &mv.m, (int)views.size(), views.data(), &oc, opt_flags | (optimize_rayleigh ? ECCKD_OPT_RAYLEIGH_ACTIVE : 0u),
+                               nangle, &opt));
     if (optimize_rayleigh) ck(ecckd_opt_set_rayleigh_prior(opt, rayleigh_prior_error));
     const size_t nx = ecckd_opt_nx(opt);
     LOG("Optimizing %zu coefficients against %zu training file(s)\n", nx, scenes.size());

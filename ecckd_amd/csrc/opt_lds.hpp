@@ -1,4 +1,4 @@
-// opt_lds.hpp - the dynamic LDS of the three K8a kernels of optimize.hip, written once: the kernels carve `smem` from these
+// opt_lds.hpp - the dynamic LDS of the K8a kernels of optimize.hip, written once: the kernels carve `smem` from these
 // layouts and the host plan takes its byte counts from them (forward_plan, opt_forward_plan, ecckd_opt_create_ex), so the two
 // sides cannot drift apart.  Plain constexpr C++ (no device-only code): tools/check_opt_tables.cpp includes it as it is.
 // A layout is the byte offset of every array, in the order of its enum, and the total behind the last one; the double arrays
@@ -39,6 +39,16 @@ enum RayleighArray { RL_BDN, RL_BUP, RL_GDN, RL_GUP, RL_R, RL_RSUM, RL_SD, RL_SU
 constexpr Layout<RL_COUNT> rayleigh(int nlay, int ng, int nband) {
   const size_t d = sizeof(double), nhl = (size_t)nlay + 1, band = nhl * nband * d;
   const size_t size[RL_COUNT] = {band, band, band, band, (size_t)nlay * nband * d, nlay * d, nhl * d, nhl * d, 16 * d,
+                                 ((size_t)nband + 1) * sizeof(int), (size_t)ng * sizeof(int)};
+  return pack(size);
+}
+
+// k_opt_forward_adjoint_lw_angles: D, U [nhl][ng] the angle-summed fluxes | bdn, bup, gdn, gup [nhl][nband] | r [nlay][nband] |
+// rsum [nlay] | sd, su [nhl] | red [16] | int bp [nband + 1] | int bg [ng]   (the per-angle state lives in a device workspace)
+enum LwAnglesArray { AL_D, AL_U, AL_BDN, AL_BUP, AL_GDN, AL_GUP, AL_R, AL_RSUM, AL_SD, AL_SU, AL_RED, AL_BP, AL_BG, AL_COUNT };
+constexpr Layout<AL_COUNT> lw_angles(int nlay, int ng, int nband) {
+  const size_t d = sizeof(double), nhl = (size_t)nlay + 1, flux = nhl * ng * d, band = nhl * nband * d;
+  const size_t size[AL_COUNT] = {flux, flux, band, band, band, band, (size_t)nlay * nband * d, nlay * d, nhl * d, nhl * d, 16 * d,
                                  ((size_t)nband + 1) * sizeof(int), (size_t)ng * sizeof(int)};
   return pack(size);
 }

@@ -163,6 +163,24 @@ __device__ __forceinline__ double lw_tau_bar(double dn_bar, double ubar_l, doubl
   return __builtin_fma(fac_bar, dfac_dtau, (eps_bar + fac_bar * dfac_deps) * (kD * ex));
 }
 
+// The same along a path of secant sec (k_opt_forward_adjoint_lw_angles, once per zenith angle): ex = exp(-sec tau), and
+// rtau = 1 / (sec tau) comes from the caller - it is read only where the layer is thick - who forms it from one reciprocal of tau
+// for all the angles of a cell.  A function of its own: with lw_tau_bar written as the sec = D case of this one the compiler
+// orders the instructions of the two-stream longwave kernels differently, and their code stays what was measured.
+__device__ __forceinline__ double lw_tau_bar_sec(double sec, double rtau, double dn_bar, double ubar_l, double dn_l, double up_next, double b0,
+                                                 double b1, double ex) {
+  const double eps = 1.0 - ex;
+  const bool thick = eps > 1.0e-5;
+  const double t_bar = dn_bar * dn_l + ubar_l * up_next;
+  const double a_bar = dn_bar * b0 + ubar_l * b1;
+  const double f_bar = dn_bar * b1 + ubar_l * b0;
+  const double eps_bar = -t_bar + a_bar;
+  const double fac_bar = f_bar - a_bar;
+  const double dfac_deps = thick ? -rtau : 0.5;
+  const double dfac_dtau = thick ? eps * rtau * (sec * rtau) : 0.0;       // eps / (sec tau^2)
+  return __builtin_fma(fac_bar, dfac_dtau, (eps_bar + fac_bar * dfac_deps) * (sec * ex));
+}
+
 // Weights of the squared band residuals of dn / up at half level i: spectral (s) and broadband (b).  lw: the column's layer weights.
 struct LevelWeights { double wd_s, wu_s, wd_b, wu_b; };
 __device__ __forceinline__ LevelWeights level_weights(const K8aArgs& a, const double* lw, bool sw, bool all_pos, int i) {
@@ -1282,6 +1300,241 @@ k_opt_forward_adjoint_rayleigh(const K8aArgs a, const int* __restrict__ band_ptr
   if (threadIdx.x == 0) a.jcol[col] = jtot;
 }
 
+// ---- K8a with the zenith-angle quadrature (ecckd_opt_create_angles, nangle > 0): the longwave transfer the line-by-line
+// truth is made with (lw_angle_table of lbl_rt.hpp: sec_k = 1 / mu_k, wgt_k = 2 w_k mu_k) and its adjoint ----
+// Per column, g point and angle k (levels 0 .. nlay from the top, B the Planck levels, tau after clamp and penalty):
+//   t_k,l = 1 - eps_k,  eps_k = 1 - exp(-sec_k tau_l),  fac_k = eps_k > 1e-5 ? 1 - eps_k / (sec_k tau_l) : eps_k / 2
+//   dn_k[0] = 0,  dn_k[l+1] = dn_k[l] t_k,l + B_l (eps_k - fac_k) + B_l+1 fac_k;   dn[i] = sum_k wgt_k dn_k[i]
+//   up_k[nlay] = es B_nlay + (1 - es) dn[nlay]  (a Lambertian surface reflects the angle-summed flux: it couples the angles)
+//   up_k[l] = up_k[l+1] t_k,l + B_l+1 (eps_k - fac_k) + B_l fac_k;                  up[i] = sum_k wgt_k up_k[i]
+// and dn, up go the way of the two-stream kernels: band sums, the longwave cost, the seeds dnb_i, upb_i at the band of g.
+// The adjoint (bars: dJ/d of the quantity):
+//   ub_k[0] = wgt_k upb_0,  ub_k[l+1] = wgt_k upb_l+1 + ub_k[l] t_k,l
+//   db_k[nlay] = wgt_k (dnb_nlay + (1 - es) sum_j ub_j[nlay]),  db_k[l] = wgt_k dnb_l + db_k[l+1] t_k,l
+//   dJ/dtau_l = sum_k lw_tau_bar_sec(sec_k; db_k[l+1], ub_k[l], dn_k[l], up_k[l+1], B_l, B_l+1, t_k,l)   (0 in a clamped cell)
+// Phases.  A (every lane owns the cells l = lgrp + j nlgrp of its g point): look-up, clamp and penalty as in the other
+// longwave kernels, then per angle the one exp and, where the layer is thick, the one division of the cell and the layer's
+// three terms; B1 .. B4: the dn chains, their angle sum, the up chains, their sum; C, D: band_sums, cost_residuals and
+// cost_seed <longwave, net flux>; E1, E2: the reversed chains; E3 (cell owners): the sum above, one reciprocal of tau serving
+// all the angles of a cell.  In the chains the layer
+// groups take the ANGLES - wave group w the angles w, w + nlgrp, ... - so the nang dependent chains of FMAs run side by side;
+// every sum over the angles is formed afterwards, by one thread, in angle order, so the grouping cannot change a bit of it.
+// The per-angle state does not fit the LDS (5 nang + 1 arrays of (nlay + 1) ng doubles): it lives in a workspace of the
+// handle, ws[column][slot][level][g], every element written and read by its own lane or with a block barrier in between.
+// The LDS holds the angle-summed flux rows and the band and cost arrays (lds::lw_angles), so one kernel serves every shape.
+// Slots: 0 the optical depth as the sweeps see it, the sign bit set where the cell was clamped; then per angle
+enum LwaSlot { LA_T,        // rows 0 .. nlay-1: 1 - eps
+               LA_DN,       // rows 1 .. nlay: the source of dn_k[l+1], then dn_k (row 0: 0)
+               LA_UP,       // rows 0 .. nlay-1: the source of up_k[l], then up_k (row nlay: the surface)
+               LA_UB,       // ub_k, rows 0 .. nlay
+               LA_DB,       // db_k, rows 1 .. nlay
+               LA_COUNT };
+__host__ __device__ constexpr size_t lwa_slots(int nang) { return 1 + (size_t)LA_COUNT * nang; }
+
+// One chain of nlay dependent FMAs x = x t[l] + src(l), l = l0, l0 + step, ...; dst(l, x) takes x BEFORE the step (the adjoint
+// chains) or after it.  The rows of a chunk of layers are fetched before its FMAs start.
+template <bool STORE_BEFORE, class Src, class Dst>
+__device__ __forceinline__ double lwa_chain(double x, const double* __restrict__ pT, int ng, int nlay, int l0, int step, Src src, Dst dst) {
+  int q0 = 0;
+  for (; q0 + K8A_CH <= nlay; q0 += K8A_CH) {
+    double tt[K8A_CH], ss[K8A_CH];
+#pragma unroll
+    for (int q = 0; q < K8A_CH; ++q) {
+      const int l = l0 + (q0 + q) * step;
+      tt[q] = pT[(size_t)l * ng];
+      ss[q] = src(l);
+    }
+#pragma unroll
+    for (int q = 0; q < K8A_CH; ++q) {
+      const int l = l0 + (q0 + q) * step;
+      if (STORE_BEFORE) dst(l, x);
+      x = x * tt[q] + ss[q];
+      if (!STORE_BEFORE) dst(l, x);
+    }
+  }
+  for (; q0 < nlay; ++q0) {
+    const int l = l0 + q0 * step;
+    const double t = pT[(size_t)l * ng], s = src(l);
+    if (STORE_BEFORE) dst(l, x);
+    x = x * t + s;
+    if (!STORE_BEFORE) dst(l, x);
+  }
+  return x;
+}
+
+__global__ void __launch_bounds__(1024)
+k_opt_forward_adjoint_lw_angles(const K8aArgs a, const int* __restrict__ band_ptr /*[nband+1]*/, const int* __restrict__ band_g /*[ng]: g points by band*/,
+                                int nang, const double* __restrict__ angles /*[3][nang]: sec, 1 / sec, wgt*/,
+                                double* ws /*[ncol][lwa_slots(nang)][nlay+1][ng]*/) {
+  extern __shared__ double smem[];
+  const int nlay = a.nlay, ng = a.ng, ngpad = a.ngpad, nband = a.nband, nent = a.nent, ray_ent = a.ray_ent;
+  const int nhl = nlay + 1;
+  const auto layout = lds::lw_angles(nlay, ng, nband);
+  auto arr = [&](int which) { return (double*)((char*)smem + layout.off[which]); };
+  double* s_D = arr(lds::AL_D);                                  // [nhl][ng] dn, up summed over the angles
+  double* s_U = arr(lds::AL_U);
+  double* s_bdn = arr(lds::AL_BDN);                              // [nhl][nband] band fluxes
+  double* s_bup = arr(lds::AL_BUP);
+  double* s_gdn = arr(lds::AL_GDN);                              // [nhl][nband] dJ/d(band flux)
+  double* s_gup = arr(lds::AL_GUP);
+  const CostLds cost = {s_bdn, s_bup, arr(lds::AL_R), arr(lds::AL_RSUM), arr(lds::AL_SD), arr(lds::AL_SU)};
+  double* s_red = arr(lds::AL_RED);                              // [16]
+  int* s_bp = (int*)arr(lds::AL_BP);                             // [nband + 1]
+  int* s_bg = (int*)arr(lds::AL_BG);                             // [ng]
+  const double* const k = a.k; const int* const ent_idx = a.ent_idx; const double* const ent_coef = a.ent_coef;
+  double* const dtau = a.dtau;
+  const int col = blockIdx.x;
+  const int g = threadIdx.x % ngpad;
+  const int lgrp = __builtin_amdgcn_readfirstlane(threadIdx.x / ngpad);     // ngpad is a multiple of 64: uniform in a wave
+  const int nlgrp = blockDim.x / ngpad;
+  const bool in_range = g < ng;
+  const int lane = threadIdx.x & 63;
+  const int gl = in_range ? g : 0;        // lanes beyond the last g point read (and drop) the first one's values
+  const double* pl = a.planck_hl + (size_t)col * nhl * ng;
+  const size_t cell0 = (size_t)col * nlay;
+  const size_t slot = (size_t)nhl * ng;
+  double* w = ws + (size_t)col * lwa_slots(nang) * slot + gl;    // slot q of this g point: w + q * slot, rows ng apart
+  auto wk = [&](int kk, int which) { return w + (1 + (size_t)LA_COUNT * kk + which) * slot; };
+  const double* const sec = angles;
+  const double* const rsec = angles + nang;
+  const double* const wgt = angles + 2 * nang;
+  for (int t = threadIdx.x; t <= nband; t += blockDim.x) s_bp[t] = band_ptr[t];
+  for (int t = threadIdx.x; t < ng; t += blockDim.x) s_bg[t] = band_g[t];
+
+  // ---- A: the cells of this thread ----
+  double penalty = 0.0;
+  for (int l = lgrp; l < nlay; l += nlgrp) {
+    double tau = 0.0, tau_ray = 0.0;
+    for (int e0 = 0; e0 < nent; e0 += 64) {
+      const int ne = min(64, nent - e0);
+      const int my_idx = lane < ne ? ent_idx[(cell0 + l) * nent + e0 + lane] : -1;
+      const double my_c = lane < ne ? ent_coef[(cell0 + l) * nent + e0 + lane] : 0.0;
+      gather_batches<0>(my_idx, my_c, e0, ne, k, gl, ray_ent, tau, tau_ray);
+    }
+    if (in_range) {
+      bool clamped;
+      tau = clamp_cell<false>(a, (cell0 + l) * ng + g, tau, tau_ray, clamped, penalty);
+      tau += tau_ray;
+      // (a clamped cell: -0.0, or the negative value itself where the sweeps see it, keep_negative == 2)
+      w[(size_t)l * ng] = clamped ? -fabs(tau) : tau;
+      const double b0 = pl[l * ng + g], b1 = pl[(l + 1) * ng + g];
+      for (int kk = 0; kk < nang; ++kk) {
+        // one exp and, where the layer is thick, one division per (cell, angle).  fac is a difference of two numbers near 1
+        // at the thin edge (5e-6 there): a reciprocal of tau shared by the angles would cost it another rounding, 2e-11 each
+        const double path = sec[kk] * tau;
+        const double eps = 1.0 - ecckd::exp_fast(-path);
+        const double fac = (eps > 1.0e-5) ? 1.0 - ecckd::div_fast(eps, path) : 0.5 * eps;
+        wk(kk, LA_T)[(size_t)l * ng] = 1.0 - eps;
+        wk(kk, LA_DN)[(size_t)(l + 1) * ng] = b0 * (eps - fac) + b1 * fac;
+        wk(kk, LA_UP)[(size_t)l * ng] = b1 * (eps - fac) + b0 * fac;
+      }
+    }
+  }
+  __syncthreads();
+  // ---- B1: the dn chains, one wave group per angle ----
+  if (in_range)
+    for (int kk = lgrp; kk < nang; kk += nlgrp) {
+      double* pD = wk(kk, LA_DN);
+      pD[0] = 0.0;
+      lwa_chain<false>(0.0, wk(kk, LA_T), ng, nlay, 0, 1, [&](int l) { return pD[(size_t)(l + 1) * ng]; },
+                       [&](int l, double x) { pD[(size_t)(l + 1) * ng] = x; });
+    }
+  __syncthreads();
+  // ---- B2: dn summed over the angles, in angle order ----
+  if (in_range)
+    for (int i = lgrp; i < nhl; i += nlgrp) {
+      double s = 0.0;
+      for (int kk = 0; kk < nang; ++kk) s += wgt[kk] * wk(kk, LA_DN)[(size_t)i * ng];
+      s_D[i * ng + g] = s;
+    }
+  __syncthreads();
+  // ---- B3: the up chains from the Lambertian surface ----
+  const double es = a.surf_emis[(size_t)col * nband + a.band_of_g[gl]];
+  if (in_range)
+    for (int kk = lgrp; kk < nang; kk += nlgrp) {
+      double* pU = wk(kk, LA_UP);
+      const double up = pl[nlay * ng + g] * es + (1.0 - es) * s_D[nlay * ng + g];
+      pU[(size_t)nlay * ng] = up;
+      lwa_chain<false>(up, wk(kk, LA_T), ng, nlay, nlay - 1, -1, [&](int l) { return pU[(size_t)l * ng]; },
+                       [&](int l, double x) { pU[(size_t)l * ng] = x; });
+    }
+  __syncthreads();
+  // ---- B4: up summed over the angles ----
+  if (in_range)
+    for (int i = lgrp; i < nhl; i += nlgrp) {
+      double s = 0.0;
+      for (int kk = 0; kk < nang; ++kk) s += wgt[kk] * wk(kk, LA_UP)[(size_t)i * ng];
+      s_U[i * ng + g] = s;
+      if (a.flux_out) {
+        double* fo = a.flux_out + (size_t)col * 2 * nhl * ng;
+        fo[i * ng + g] = s_D[i * ng + g];
+        fo[(nhl + i) * ng + g] = s;
+      }
+    }
+  __syncthreads();
+  // ---- C: band sums of the flux rows ----
+  const LdsFlux flux = {s_D, s_U, ng};
+  const ColumnTruth ct = column_truth(a, col);
+  band_sums(a, col, flux, s_bp, s_bg, s_bdn, s_bup);
+  __syncthreads();
+  // ---- D: the longwave cost (calc_cost_function_lw.cpp:186-229) and its derivative with respect to the band fluxes ----
+  double jpart = 0.0;
+  cost_residuals<false, true>(a, ct, true, cost, jpart);
+  for (int t = threadIdx.x; t < nhl * nband; t += blockDim.x) {
+    double gd, gu;
+    cost_seed<false, true>(a, ct, true, cost, t, gd, gu, jpart);
+    s_gdn[t] = gd;
+    s_gup[t] = gu;
+  }
+  // the per-g boundary term: every angle owner needs its seeds, the first layer group adds its cost
+  double dn_surf_extra = 0.0, up_toa_extra = 0.0;
+  if (in_range) {
+    double jb = 0.0;
+    boundary_term<false>(a, col, g, flux, jb, dn_surf_extra, up_toa_extra);
+    if (lgrp == 0) jpart += jb;
+  }
+  __syncthreads();
+  // ---- E1: the up chains reversed; row nlay of ub_k is the adjoint of up_k at the surface ----
+  const int b = a.band_of_g[gl];
+  if (in_range)
+    for (int kk = lgrp; kk < nang; kk += nlgrp) {
+      double* pB = wk(kk, LA_UB);
+      const double wg = wgt[kk];
+      const double ub = lwa_chain<true>(wg * (s_gup[b] + up_toa_extra), wk(kk, LA_T), ng, nlay, 0, 1,
+                                        [&](int l) { return wg * s_gup[(l + 1) * nband + b]; },
+                                        [&](int l, double x) { pB[(size_t)l * ng] = x; });
+      pB[(size_t)nlay * ng] = ub;
+    }
+  __syncthreads();
+  // ---- E2: through the surface (the sum over ALL the angles' ub, in angle order) and the dn chains reversed ----
+  if (in_range)
+    for (int kk = lgrp; kk < nang; kk += nlgrp) {
+      double ub_surf = 0.0;
+      for (int j = 0; j < nang; ++j) ub_surf += wk(j, LA_UB)[(size_t)nlay * ng];
+      double* pB = wk(kk, LA_DB);
+      const double wg = wgt[kk];
+      lwa_chain<true>(wg * (s_gdn[nlay * nband + b] + dn_surf_extra + (1.0 - es) * ub_surf), wk(kk, LA_T), ng, nlay, nlay - 1, -1,
+                      [&](int l) { return wg * s_gdn[l * nband + b]; }, [&](int l, double x) { pB[(size_t)(l + 1) * ng] = x; });
+    }
+  __syncthreads();
+  // ---- E3: dJ/dtau of the cells of this thread, the angles in order; a clamped cell keeps the penalty's derivative ----
+  if (in_range)
+    for (int l = lgrp; l < nlay; l += nlgrp) {
+      const double tau = w[(size_t)l * ng];
+      if (__builtin_signbit(tau)) continue;
+      const double b0 = pl[l * ng + g], b1 = pl[(l + 1) * ng + g];
+      const double rt = ecckd::div_fast(1.0, tau);
+      double tau_bar = 0.0;
+      for (int kk = 0; kk < nang; ++kk)
+        tau_bar += lw_tau_bar_sec(sec[kk], rsec[kk] * rt, wk(kk, LA_DB)[(size_t)(l + 1) * ng], wk(kk, LA_UB)[(size_t)l * ng],
+                                  wk(kk, LA_DN)[(size_t)l * ng], wk(kk, LA_UP)[(size_t)(l + 1) * ng], b0, b1, wk(kk, LA_T)[(size_t)l * ng]);
+      dtau[(cell0 + l) * ng + g] = tau_bar;
+    }
+  jpart += a.negative_od_penalty * penalty;
+  const double jtot = block_reduce_sum(jpart, s_red);
+  if (threadIdx.x == 0) a.jcol[col] = jtot;
+}
+
 // K8b + K9: gradient of the state, two launches of one WAVE per task, four waves per block, no LDS, no barrier.
 //   grad_k = sum over the cells that reference this node of coef * dtau[cell][g]   (reference order)
 //   grad_x = grad_k * k + B^-1 (x - x_prior) / sigma_g^2                            (:273-283)
@@ -1828,6 +2081,11 @@ struct ecckd_opt : ot::Layout {
   double* d_rel = nullptr;   // relative-to CKD fluxes [ncol][2][nhl][ng]
   double* d_ray_ws = nullptr;   // scattering handles: the per-(level, g) state of k_opt_forward_adjoint_rayleigh [ncol][RS_COUNT][nhl][ng]
   double* d_mu0 = nullptr;
+  // ecckd_opt_create_angles with nangle > 0: the longwave forward model is the zenith-angle quadrature; [3][nangle] sec, 1 / sec,
+  // wgt of lw_angle_table, and the per-angle state of k_opt_forward_adjoint_lw_angles [ncol][lwa_slots(nangle)][nhl][ng]
+  int nangle = 0;
+  double* d_lw_angles = nullptr;
+  double* d_lwa_ws = nullptr;
   // ECCKD_OPT_RAYLEIGH_ACTIVE: the cells' moles of air (plain handle: the weights of dJ/dtau), the first-level partials of the
   // Rayleigh reduction, and the prior error of the ng tail elements (<= 0: no prior term on them)
   double* d_moles = nullptr;
@@ -1926,6 +2184,8 @@ size_t ray_ws_doubles(const ecckd_opt* o) {
   const size_t slot = (size_t)(o->nlay + 1) * o->ng;
   return o->ncol * (o->rayleigh_active ? RS_COUNT_ACTIVE : RS_COUNT) * slot + (o->rayleigh_active ? o->ncol * (size_t)o->ng : 0);
 }
+// doubles of the per-angle workspace of k_opt_forward_adjoint_lw_angles: (5 nangle + 1) (nlay + 1) ng per column
+size_t lwa_ws_doubles(const ecckd_opt* o) { return o->ncol * lwa_slots(o->nangle) * (size_t)(o->nlay + 1) * o->ng; }
 // dynamic LDS of the scattering kernel: the band and cost arrays; <true>: one double per thread behind them
 size_t ray_lds_bytes(const ecckd_opt* o, int threads) {
   const size_t bytes = lds::rayleigh(o->nlay, o->ng, o->nband).bytes();
@@ -1968,8 +2228,31 @@ int ecckd_opt_create(ecckd_ctx* ctx, const ecckd_opt_model* m, int nscene, const
 
 int ecckd_opt_create_ex(ecckd_ctx* ctx, const ecckd_opt_model* m, int nscene, const ecckd_opt_scene* scenes,
                         const ecckd_opt_config* cfg, unsigned flags, ecckd_opt** out) {
+  return ecckd_opt_create_angles(ctx, m, nscene, scenes, cfg, flags, 0, out);
+}
+
+int ecckd_opt_create_angles(ecckd_ctx* ctx, const ecckd_opt_model* m, int nscene, const ecckd_opt_scene* scenes,
+                            const ecckd_opt_config* cfg, unsigned flags, int nangle, ecckd_opt** out) {
   ECCKD_REQUIRE(ctx && m && scenes && cfg && out && nscene > 0, "ecckd_opt_create: NULL/empty argument");
   *out = nullptr;
+  ECCKD_REQUIRE(nangle >= 0 && nangle <= ecckd::lbl::LBL_MAX_ANGLES, "ecckd_opt_create_angles: nangle = %d outside 0..%d", nangle,
+                ecckd::lbl::LBL_MAX_ANGLES);
+  std::vector<double> lw_angles;     // [3][nangle] sec, 1 / sec, wgt
+  if (nangle > 0) {
+    ECCKD_REQUIRE(!m->solar_irradiance, "ecckd_opt_create_angles: nangle = %d needs a longwave model (this one has solar_irradiance)", nangle);
+    ECCKD_REQUIRE(flags == 0, "ecckd_opt_create_angles: nangle = %d cannot be combined with the ECCKD_OPT_RAYLEIGH flags (0x%x)", nangle, flags);
+    // (one thread per g point of a column, at most 1 024 threads in a block)
+    ECCKD_REQUIRE(m->ng <= 1024, "ecckd_opt_create_angles: nangle > 0 supports at most 1024 g points (ng = %d)", m->ng);
+    int nang = 0;
+    std::vector<double> sec_wgt;
+    ECCKD_CHECK(ecckd::lbl::lw_angle_table("ecckd_opt_create_angles", nangle, &nang, sec_wgt));
+    lw_angles.resize(3 * (size_t)nangle);
+    for (int a = 0; a < nangle; ++a) {
+      lw_angles[a] = sec_wgt[a];
+      lw_angles[nangle + a] = 1.0 / sec_wgt[a];
+      lw_angles[2 * nangle + a] = sec_wgt[nangle + a];
+    }
+  }
   ECCKD_REQUIRE((flags & ~(ECCKD_OPT_RAYLEIGH_SCATTERING | ECCKD_OPT_RAYLEIGH_ACTIVE)) == 0, "ecckd_opt_create_ex: unknown flags 0x%x", flags);
   const bool scattering = (flags & ECCKD_OPT_RAYLEIGH_SCATTERING) != 0;
   // (ECCKD_OPT_RAYLEIGH_ACTIVE on a model that is not shortwave with rayleigh_molar_scattering: refused by build_tables)
@@ -2003,8 +2286,22 @@ int ecckd_opt_create_ex(ecckd_ctx* ctx, const ecckd_opt_model* m, int nscene, co
                                                            : reinterpret_cast<const void*>(k_opt_forward_adjoint_rayleigh<false>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   }
+  if (nangle > 0) {
+    // as for the scattering kernel: the LDS depends on the shapes alone, so a shape is refused here and the limit raised once
+    const size_t bytes = lds::lw_angles(o->nlay, o->ng, o->nband).bytes();
+    ECCKD_REQUIRE(bytes <= 160 * 1024, "ecckd_opt_create_angles: nangle > 0: (nlay + 1) * (2 ng + 4 nband) too large for the LDS of the kernel (%zu B)", bytes);
+    ECCKD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_opt_forward_adjoint_lw_angles),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    o->nangle = nangle;
+  }
   ECCKD_CHECK(opt_upload_tables(o.get(), t));
   ECCKD_CHECK(opt_alloc_work(o.get(), t));
+  if (nangle > 0) {
+    ECCKD_CHECK(upload(o.get(), &o->d_lw_angles, lw_angles));
+    if (o->alloc(&o->d_lwa_ws, lwa_ws_doubles(o.get())) != hipSuccess)
+      return ecckd::fail(ECCKD_OUT_OF_MEMORY, "ecckd_opt_create_angles: device allocation of the per-angle workspace failed (%zu B)",
+                         lwa_ws_doubles(o.get()) * sizeof(double));
+  }
   if (o->scattering && o->alloc(&o->d_ray_ws, ray_ws_doubles(o.get())) != hipSuccess)
     return ecckd::fail(ECCKD_OUT_OF_MEMORY, "ecckd_opt_create_ex: device allocation of the scattering workspace failed");
   std::vector<double> xp(o->nx);
@@ -2021,6 +2318,8 @@ int ecckd_opt_destroy(ecckd_opt* o) {
 }
 
 size_t ecckd_opt_nx(ecckd_opt* o) { return o ? o->nx : 0; }
+
+int ecckd_opt_nangle(ecckd_opt* o) { return o ? o->nangle : 0; }
 
 int ecckd_opt_set_evaluator(ecckd_opt* o, ecckd_evaluator_fn fn, void* user) {
   ECCKD_REQUIRE(o, "ecckd_opt_set_evaluator: NULL handle");
@@ -2202,6 +2501,17 @@ ecckd_forward_plan opt_forward_plan(const ecckd_opt* o) {
     p.lds_bytes = ray_lds_bytes(o, p.threads);
     return p;
   }
+  if (o->nangle > 0) {
+    // k_opt_forward_adjoint_lw_angles, the one kernel of a handle with the angle quadrature: 1 024 threads (16 layer groups at
+    // ng = 64), the LDS holds the angle-summed flux rows and the band and cost arrays
+    ecckd_forward_plan p{};
+    p.cells = 3;
+    p.ngpad = (o->ng + 63) / 64 * 64;
+    p.lgroups = std::max(1, (v >= 64 && v <= 1024 ? v : 1024) / p.ngpad);   // (ecckd_opt_create_angles has refused ng > 1024)
+    p.threads = p.ngpad * p.lgroups;
+    p.lds_bytes = lds::lw_angles(o->nlay, o->ng, o->nband).bytes();
+    return p;
+  }
   const char* env_generic = std::getenv("ECCKD_K8A_GENERIC");
   return forward_plan(o->do_sw, o->nlay, o->ng, o->nband, o->nent, v >= 64 && v <= 1024 ? v : 0, env_generic && env_generic[0] == '1');
 }
@@ -2218,6 +2528,13 @@ int opt_launch_forward(ecckd_opt* o) {
     else
       hipLaunchKernelGGL(k_opt_forward_adjoint_rayleigh<false>, dim3((unsigned)o->ncol), dim3(p.threads), p.lds_bytes, ctx->stream, k8a_args(o, p),
                          o->d_band_ptr, o->d_band_g, o->d_ray_ws);
+    ECCKD_HIP_CHECK(hipGetLastError());
+    return ECCKD_OK;
+  }
+  if (o->nangle > 0) {
+    // (ecckd_opt_create_angles has checked the LDS and raised the kernel's limit)
+    hipLaunchKernelGGL(k_opt_forward_adjoint_lw_angles, dim3((unsigned)o->ncol), dim3(p.threads), p.lds_bytes, ctx->stream, k8a_args(o, p),
+                       o->d_band_ptr, o->d_band_g, o->nangle, o->d_lw_angles, o->d_lwa_ws);
     ECCKD_HIP_CHECK(hipGetLastError());
     return ECCKD_OK;
   }

@@ -122,12 +122,12 @@ class NcWriter:
         ids = (C.c_int * max(len(dims), 1))(*[self.dims[d] for d in dims])
         check(self.lib.ecckd_nc_def_var(self.handle, _b(name), NC_TYPES[nc_type], len(dims), ids, None))
 
-    def write_attribute(self, name, value, var=None):
+    def write_attribute(self, name, value, var=None, nc_type="double"):
         if isinstance(value, str):
             check(self.lib.ecckd_nc_put_att_text(self.handle, _b(var), _b(name), _b(value)))
         else:
             v = np.atleast_1d(np.asarray(value, dtype=np.float64))
-            check(self.lib.ecckd_nc_put_att_double(self.handle, _b(var), _b(name), NC_TYPES["double"], v.size,
+            check(self.lib.ecckd_nc_put_att_double(self.handle, _b(var), _b(name), NC_TYPES[nc_type], v.size,
                                                    v.ctypes.data_as(C.POINTER(C.c_double))))
 
     def deflate_variable(self, name):
@@ -513,6 +513,14 @@ def read_lbl_fluxes(path, model_molecules, band_mapping=None, gmap=None, ctx=Non
                 present[i] = 1
         out["vmr_fl"], out["gas_present"] = vmr, present
     return out
+
+
+def lbl_fluxes_nangle(path):
+    """The global integer attribute `nangle` of a line-by-line flux file - the zenith angles per hemisphere its longwave fluxes
+    were integrated with - or None where the file carries none (`ckdmip_lw` writes none)."""
+    with NcFile(path) as f:
+        v = f.att_values("nangle")
+    return None if v is None or v.size == 0 else int(round(float(v[0])))
 
 
 def mask_rayleigh_up(scene, max_no_rayleigh_wavenumber):

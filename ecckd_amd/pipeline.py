@@ -218,7 +218,7 @@ def iband_per_g(model, wavenumber1, wavenumber2):
 
 def optimize_lut(ctx, model, training_files, relative_to=None, band_mapping=None, gmap=None, max_iterations=3000,
                  convergence_criterion=0.0, bounded=True, max_no_rayleigh_wavenumber=None, erythemal_weight=0.0,
-                 remove_min_max=False, rayleigh_scattering=False, optimize_rayleigh=False, rayleigh_prior_error=0.0, **cfg):
+                 remove_min_max=False, rayleigh_scattering=False, optimize_rayleigh=False, rayleigh_prior_error=0.0, nangle=0, **cfg):
     """The driver of optimize_lut.cpp:60-330 on top of api.Optimizer: training scenes from LBL flux files
     (ncio.read_lbl_fluxes), optional "relative_to" file, bounded L-BFGS, optimised coefficients back into the model.
 
@@ -234,6 +234,9 @@ def optimize_lut(ctx, model, training_files, relative_to=None, band_mapping=None
            the same name), with either forward model; rayleigh_prior_error is the sigma of their prior (<= 0: none).  Every
            gas of the model may then be inactive.  The relative_to handle is made without it.  The model that is returned
            carries the optimised rayleigh_molar_scattering.
+    nangle: N in 1..16: train a longwave model under the zenith-angle quadrature the truth files were made with (`ckdmip_lw` with
+           nangle = N; api.Optimizer(nangle=N), the tool's key of the same name), for the relative_to handle as well; 0: the
+           two-stream form.  A file that carries a global attribute `nangle` must agree with the key.
     Returns (model with optimised molar_abs, result dict of Optimizer.minimize)."""
     names = [g["name"] for g in model["gases"]]
     is_sw = model.get("solar_irradiance") is not None
@@ -241,6 +244,15 @@ def optimize_lut(ctx, model, training_files, relative_to=None, band_mapping=None
         raise EcckdError(PARAMETER_ERROR, "rayleigh_scattering needs a shortwave CKD model with a Rayleigh coefficient")
     if optimize_rayleigh and not (is_sw and model.get("rayleigh_molar_scattering") is not None):
         raise EcckdError(PARAMETER_ERROR, "optimize_rayleigh needs a shortwave CKD model with a Rayleigh coefficient")
+    nangle = int(nangle)
+    if not 0 <= nangle <= 16:
+        raise EcckdError(PARAMETER_ERROR, f"nangle = {nangle} outside 0..16")
+    if nangle > 0 and is_sw:
+        raise EcckdError(PARAMETER_ERROR, f"nangle = {nangle} needs a longwave CKD model")
+    for path in ([relative_to] if relative_to is not None else []) + list(training_files):
+        file_nangle = ncio.lbl_fluxes_nangle(path)
+        if file_nangle is not None and file_nangle != nangle:
+            raise EcckdError(PARAMETER_ERROR, f"{path} was made with nangle = {file_nangle}, the key nangle says {nangle}")
 
     def load(path):
         s = ncio.read_lbl_fluxes(path, names, band_mapping=band_mapping, gmap=gmap, ctx=ctx, rayleigh_scattering=rayleigh_scattering)
@@ -258,7 +270,8 @@ def optimize_lut(ctx, model, training_files, relative_to=None, band_mapping=None
         m0 = dict(model, iband_per_g=rel.get("iband_per_g", model["iband_per_g"]))
         if not any(g.get("active", True) for g in model["gases"]):     # Rayleigh alone: this handle, made without the flag, takes every gas
             m0["gases"] = [dict(g, active=True) for g in model["gases"]]
-        ref_opt = api.Optimizer(ctx, m0, [_scene_for_optimizer(rel, is_sw)], rayleigh_scattering=rayleigh_scattering, **cfg)
+        ref_opt = api.Optimizer(ctx, m0, [_scene_for_optimizer(rel, is_sw)], rayleigh_scattering=rayleigh_scattering, nangle=nangle,
+                                **cfg)
         _, fl = ref_opt.forward(ref_opt.initial_state(), unclamped=True)     # od = value(aod), no clamp (:231-234)
         ref_opt.close()
     scenes = []
@@ -278,7 +291,7 @@ def optimize_lut(ctx, model, training_files, relative_to=None, band_mapping=None
     if iband is not None:
         m["iband_per_g"] = iband
     opt = api.Optimizer(ctx, m, scenes, rayleigh_scattering=rayleigh_scattering, optimize_rayleigh=optimize_rayleigh,
-                        rayleigh_prior_error=rayleigh_prior_error, **dict(dict(cap_relative_linear=0.8), **cfg))   # :185
+                        rayleigh_prior_error=rayleigh_prior_error, nangle=nangle, **dict(dict(cap_relative_linear=0.8), **cfg))   # :185
     res = opt.minimize(max_iterations=max_iterations, convergence_criterion=convergence_criterion, bounded=bounded)
     out = dict(model, gases=[dict(g) for g in model["gases"]])
     for i, g in enumerate(out["gases"]):

@@ -809,6 +809,30 @@ int ecckd_opt_create(ecckd_ctx* ctx, const ecckd_opt_model* model, int nscene,
 #define ECCKD_OPT_RAYLEIGH_ACTIVE 2u
 int ecckd_opt_create_ex(ecckd_ctx* ctx, const ecckd_opt_model* model, int nscene, const ecckd_opt_scene* scenes,
                         const ecckd_opt_config* config, unsigned flags, ecckd_opt** opt);
+/* ecckd_opt_create_ex with the zenith-angle quadrature of the longwave truth (ecckd_opt_create_ex is nangle = 0, and nangle = 0
+ * here gives the handle it makes: same kernels, same ecckd_opt_forward_plan, the same bits of cost and gradient).
+ * nangle = N in 1..16: the longwave forward model integrates N Gauss-Legendre angles per hemisphere, the nodes of
+ * ecckd_lbl_band_fluxes_lw_angles (sec_k = 1 / mu_k, wgt_k = 2 w_k mu_k, sum_k wgt_k = 1), not one path at the diffusivity 1.66
+ * (nangle = 0 is "no quadrature", not "one angle at 1.66").  Per column, g point and angle k, with the Planck levels B_l and the
+ * optical depth tau_l after clamp and penalty as without the key:
+ *   eps_k = 1 - exp(-sec_k tau_l),  fac_k = eps_k > 1e-5 ? 1 - eps_k / (sec_k tau_l) : eps_k / 2
+ *   dn_k[0] = 0,  dn_k[l+1] = dn_k[l] (1 - eps_k) + B_l (eps_k - fac_k) + B_l+1 fac_k,    dn[i] = sum_k wgt_k dn_k[i]
+ *   up_k[nlay] = es B_nlay + (1 - es) dn[nlay]   (Lambertian surface, es = surf_emissivity of the g point's band)
+ *   up_k[l] = up_k[l+1] (1 - eps_k) + B_l+1 (eps_k - fac_k) + B_l fac_k,                  up[i] = sum_k wgt_k up_k[i]
+ * With es = 1 these are the fluxes of ecckd_rt_lw_gpoints(nangle = N).  Everything behind dn and up is unchanged (band sums,
+ * relative_to, heating rates, every cost term, the penalty), and so is every other function of the handle.  The adjoint is
+ * hand-derived: each angle receives the seeds scaled by wgt_k and runs the two reversed recurrences with sec_k in place of
+ * 1.66; the surface couples them, dn_bar_k[nlay] += wgt_k (1 - es) sum_j up_bar_j[nlay]; dJ/dtau_l is the sum over the angles
+ * in angle order.  Cost and gradient are bitwise reproducible.  One kernel, k_opt_forward_adjoint_lw_angles, serves the handle at
+ * every shape (ecckd_opt_forward_plan: cells = 3, nc_template = nb = 0, threads = ngpad * lgroups from 1024 or ECCKD_K8A_THREADS
+ * (64 ... 1024), lds_bytes = two flux rows of (nlay + 1) ng doubles and the band and cost arrays).  Its per-angle state lives in
+ * a device workspace of the handle, ncol (5 nangle + 1) (nlay + 1) ng doubles, allocated here (ECCKD_OUT_OF_MEMORY if that fails).
+ * Refused with ECCKD_PARAMETER_ERROR: nangle outside 0..16; nangle > 0 on a shortwave model (solar_irradiance), with any
+ * ECCKD_OPT_RAYLEIGH flag, with more than 1024 g points, or with lds_bytes above 160 KB.  Nothing is refused at launch. */
+int ecckd_opt_create_angles(ecckd_ctx* ctx, const ecckd_opt_model* model, int nscene, const ecckd_opt_scene* scenes,
+                            const ecckd_opt_config* config, unsigned flags, int nangle, ecckd_opt** opt);
+/* the nangle the handle was made with (0: ecckd_opt_create, ecckd_opt_create_ex) */
+int ecckd_opt_nangle(ecckd_opt* opt);
 int ecckd_opt_destroy(ecckd_opt* opt);
 /* length of the state vector x = ln(molar_abs) of the active gases, in model gas order (ECCKD_OPT_RAYLEIGH_ACTIVE: then the ng
  * elements ln(rayleigh_molar_scattering)) */
@@ -825,7 +849,10 @@ int ecckd_opt_cost_grad(ecckd_opt* opt, const double* h_x, double* J, double* h_
  * A handle made with ECCKD_OPT_RAYLEIGH_SCATTERING runs one kernel at every shape, k_opt_forward_adjoint_rayleigh: cells = 2,
  * nc_template = nb = 0 (its cells and table entries are loops), threads = ngpad * lgroups from 512 or ECCKD_K8A_THREADS (64 ... 512),
  * lds_bytes = the band and cost arrays only (the per-level state lives in a device workspace of the handle; more than 160 KB
- * was refused when the handle was made); ECCKD_K8A_GENERIC is not read. */
+ * was refused when the handle was made); ECCKD_K8A_GENERIC is not read.
+ * A handle made by ecckd_opt_create_angles with nangle > 0 runs k_opt_forward_adjoint_lw_angles at every shape: cells = 3,
+ * nc_template = nb = 0, threads = ngpad * lgroups from 1024 or ECCKD_K8A_THREADS (64 ... 1024), lds_bytes = the angle-summed flux
+ * rows and the band and cost arrays (checked against 160 KB when the handle was made); ECCKD_K8A_GENERIC is not read. */
 typedef struct {
   int cells, nc_template, nb, threads, ngpad, lgroups;
   size_t lds_bytes;
