@@ -156,6 +156,7 @@ SIGNATURES = {
     "ecckd_cloud_partition_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _c_int64_p,
                                             _c_int64_p, C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                             C.POINTER(C.c_int), _c_int64_p, _c_int64_p, _c_double_p, _c_double_p]),
+    "ecckd_cloud_geometry": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int)] * 5 + [_c_int64_p]),
     "ecckd_find_g_band": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_double, C.c_double, C.c_int,
                                     C.c_int, C.c_int, C.POINTER(C.c_int), _c_double_p, _c_double_p, C.c_int,
                                     C.POINTER(C.c_int), _c_double_p]),

@@ -1748,3 +1748,14 @@ def cloud_partition(ctx, ssi, rank, sorting_variable, band_begin, band_end, max_
                                             _hptr(r2, C.c_int64), _hptr(err), _hptr(med)))
     n = ng.value
     return dict(n_g_points=ngb, band_number=band[:n], rank1=r1[:n], rank2=r2[:n], error=err[:n], median=med[:n])
+
+
+def cloud_geometry(ctx=None):
+    """The tiling of the cloud kernels (ecckd_cloud_geometry; host only) -> dict.  grid_points is what one pass of the grid-stride
+    kernels covers on ctx's device; without a context, on an MI355X."""
+    names = ("lds_knots", "scan_items", "scan_tile", "stats_chunk", "bounds_block")
+    vals = [C.c_int() for _ in names]
+    grid = C.c_int64()
+    check(_lib.load_library().ecckd_cloud_geometry(ctx.handle if ctx is not None else None, *[C.byref(v) for v in vals],
+                                                   C.byref(grid)))
+    return dict({k: int(v.value) for k, v in zip(names, vals)}, grid_points=int(grid.value))

@@ -19,6 +19,9 @@ constexpr int kLdsKnots = 2048;     // knots staged in LDS (2 x 16 KB); a longer
 constexpr int kScanItems = 8;       // consecutive points per thread in a scan tile
 constexpr int kTile = 256 * kScanItems;
 constexpr int kChunk = 8192;        // points per block of the per-g-point statistics
+constexpr int kBoundsBlock = 64;    // boundary searches (one per thread) per block of k_cloud_bounds
+constexpr int kGridBlocksPerCu = 16;  // blocks of 256 points per compute unit in one pass of the grid-stride kernels
+constexpr int kMi355xCu = 256;      // ecckd_cloud_geometry without a context
 
 // reorder_cloud_spectrum.cpp:115-120 per knot.  Every operation rounded on its own (no contraction), so that the keys equal a
 // plain double-precision restatement bit for bit.  asymmetry_de = 1/(1+g) is what the reference writes (:117), not the
@@ -78,7 +81,8 @@ __device__ inline int band_of(int nband, const int64_t* begin, const int64_t* en
 
 // Rank order (ireorder(irank(range(ibegin,iend))-ibegin) = range(ibegin,iend), :607): ssi and the sorting variable of every
 // band point are scattered to their rank.  flag bit 1: a rank outside its band (or, outside every band, not the index itself,
-// as write_order leaves it); bit 2: ssi < 0 somewhere.
+// as write_order leaves it); bit 2: ssi < 0 (or NaN) somewhere; bit 4: the sorting variable of a band point is NaN (fmin / fmax
+// would drop it from the band's range and from the g point's error, while the g point's mean became NaN).
 __global__ void __launch_bounds__(256)
 k_cloud_scatter(size_t nwav, const double* __restrict__ ssi, const double* __restrict__ sv, const int32_t* __restrict__ rank,
                 int nband, const int64_t* __restrict__ begin, const int64_t* __restrict__ end, double* __restrict__ ssi_s,
@@ -93,8 +97,10 @@ k_cloud_scatter(size_t nwav, const double* __restrict__ ssi, const double* __res
       continue;
     }
     if (r < begin[b] || r > end[b]) { atomicOr(flag, 1); continue; }
+    const double v = sv[i];
+    if (v != v) atomicOr(flag, 4);
     ssi_s[r] = s;
-    sv_s[r] = sv[i];
+    sv_s[r] = v;
   }
 }
 
@@ -168,7 +174,7 @@ k_cloud_tile_scan(const int64_t* __restrict__ tile_s, const int64_t* __restrict_
 }
 
 // the first p of [lo, hi) with cum[p] >= value (hi if none): the running sum is monotone where ssi >= 0
-__global__ void __launch_bounds__(64)
+__global__ void __launch_bounds__(kBoundsBlock)
 k_cloud_bounds(int nq, const double* __restrict__ cum, const int64_t* __restrict__ q_lo, const int64_t* __restrict__ q_hi,
                const double* __restrict__ q_val, int64_t* __restrict__ q_pos) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -233,13 +239,26 @@ template <class T> hipError_t download(ecckd_ctx* ctx, std::vector<T>& h, const 
 }
 
 unsigned grid_for(size_t n, int num_cu) {
-  const size_t want = (n + 255) / 256, cap = (size_t)num_cu * 16;
+  const size_t want = (n + 255) / 256, cap = (size_t)num_cu * kGridBlocksPerCu;
   return (unsigned)std::max<size_t>(1, std::min(want, cap));
 }
 
 }  // namespace
 
 extern "C" {
+
+int ecckd_cloud_geometry(ecckd_ctx* ctx, int* lds_knots, int* scan_items, int* scan_tile, int* stats_chunk, int* bounds_block,
+                         int64_t* grid_points) {
+  ECCKD_REQUIRE(lds_knots && scan_items && scan_tile && stats_chunk && bounds_block && grid_points,
+                "ecckd_cloud_geometry: NULL argument");
+  *lds_knots = kLdsKnots;
+  *scan_items = kScanItems;
+  *scan_tile = kTile;
+  *stats_chunk = kChunk;
+  *bounds_block = kBoundsBlock;
+  *grid_points = (int64_t)kGridBlocksPerCu * (ctx ? ctx->num_cu : kMi355xCu) * 256;
+  return ECCKD_OK;
+}
 
 int ecckd_cloud_sorting_variable_dev(ecckd_ctx* ctx, int nknot, const double* h_cloud_wavenumber, const double* h_ssa,
                                      const double* h_asymmetry, size_t nwav, const double* d_wavenumber, double* d_sorting_variable) {
@@ -335,6 +354,7 @@ int ecckd_cloud_partition_dev(ecckd_ctx* ctx, size_t nwav, const double* d_ssi, 
   ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   if (flag & 2) return ecckd::fail(ECCKD_PARAMETER_ERROR, "solar_spectral_irradiance is negative (or NaN) at some wavenumbers");
   if (flag & 1) return ecckd::fail(ECCKD_PARAMETER_ERROR, "The cloud ordering's rank does not permute the wavenumbers of each band among themselves");
+  if (flag & 4) return ecckd::fail(ECCKD_PARAMETER_ERROR, "The cloud ordering's sorting variable is NaN at some wavenumbers of a band");
   hipLaunchKernelGGL(k_cloud_tile_reduce, dim3(ntile), dim3(256), 0, ctx->stream, d_ts, d_te, ssi_s, sv_s, d_tsum, d_tmin, d_tmax);
   ECCKD_HIP_CHECK(hipGetLastError());
   std::vector<double> tsum(ntile), tmin(ntile), tmax(ntile), toff(ntile);
@@ -382,7 +402,8 @@ int ecckd_cloud_partition_dev(ecckd_ctx* ctx, size_t nwav, const double* d_ssi, 
   ECCKD_HIP_CHECK(upload(ctx, d_qlo, qlo));
   ECCKD_HIP_CHECK(upload(ctx, d_qhi, qhi));
   ECCKD_HIP_CHECK(upload(ctx, d_qval, qval));
-  hipLaunchKernelGGL(k_cloud_bounds, dim3((unsigned)((nq + 63) / 64)), dim3(64), 0, ctx->stream, nq, cum, d_qlo, d_qhi, d_qval, d_qpos);
+  hipLaunchKernelGGL(k_cloud_bounds, dim3((unsigned)((nq + kBoundsBlock - 1) / kBoundsBlock)), dim3(kBoundsBlock), 0, ctx->stream,
+                     nq, cum, d_qlo, d_qhi, d_qval, d_qpos);
   ECCKD_HIP_CHECK(hipGetLastError());
   std::vector<int64_t> qpos(nq);
   ECCKD_HIP_CHECK(download(ctx, qpos, d_qpos));

@@ -1094,8 +1094,15 @@ int ecckd_merge_g_points_dev(ecckd_ctx* ctx, size_t nwav, int ngas,
  * capacity) h_band_number, h_rank1, h_rank2, h_error (max - min of the sorting variable) and
  * h_median (-2 + its unweighted mean).  The running sum is a blocked fp64 scan (fixed order, no
  * atomics), so a point can change g point only where the sum is within rounding of a boundary.
- * ECCKD_PARAMETER_ERROR for ssi < 0 anywhere or a rank outside its band; ECCKD_PROCESSING_ERROR
- * for a g point that holds no wavenumber (the reference takes minval of an empty set there). */
+ * ECCKD_PARAMETER_ERROR for ssi < 0 (or NaN) anywhere, a rank outside its band or a NaN sorting
+ * variable inside a band; ECCKD_PROCESSING_ERROR for a g point that holds no wavenumber (the
+ * reference takes minval of an empty set there) and for more than `capacity` g points.
+ * ecckd_cloud_geometry (host only) reports the tiling of these kernels: the longest Mie table
+ * searched in LDS, points per thread and per tile of the scan, points per block of the g-point
+ * statistics, boundary searches per block, and the points one pass of the grid-stride kernels
+ * covers on ctx's device (with ctx NULL: on the 256 compute units of an MI355X). */
+int ecckd_cloud_geometry(ecckd_ctx* ctx, int* lds_knots, int* scan_items, int* scan_tile,
+                         int* stats_chunk, int* bounds_block, int64_t* grid_points);
 int ecckd_cloud_sorting_variable_dev(ecckd_ctx* ctx, int nknot, const double* h_cloud_wavenumber,
                                      const double* h_ssa, const double* h_asymmetry, size_t nwav,
                                      const double* d_wavenumber, double* d_sorting_variable);

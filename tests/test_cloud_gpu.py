@@ -8,32 +8,13 @@ import numpy as np
 import pytest
 from scipy.io import netcdf_file
 
+from cloud_cases import abs_inf_numpy, partition_numpy, stable_ranks
 from ecckd_amd import synthetic as syn
 from test_cli_gpu import _nc, _run_ranks, _write_columns_from, run_tool
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN_MIE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mie_droplet_scattering.nc")
-
-
-def abs_inf_numpy(x, ssa, g, xi):
-    """reorder_cloud_spectrum.cpp:115-122 in plain double precision, adept::interp as linear inter- and extrapolation."""
-    f = g * g
-    g_de = 1.0 / (1.0 + g)
-    ssa_de = ssa * (1.0 - f) / (1.0 - ssa * f)
-    a = np.sqrt((1.0 - ssa_de) / (1.0 - ssa_de * g_de))
-    y = 1.0 - (1.0 - a) / (1.0 + a)
-    j = np.clip(np.searchsorted(x, xi, side="right") - 1, 0, x.size - 2)
-    w = (xi - x[j]) / (x[j + 1] - x[j])
-    return (1.0 - w) * y[j] + w * y[j + 1]
-
-
-def stable_ranks(key, band_begin, band_end):
-    rank = np.arange(key.size, dtype=np.int32)
-    for b, e in zip(band_begin, band_end):
-        order = np.argsort(key[b:e + 1], kind="stable") + b
-        rank[order] = np.arange(b, e + 1, dtype=np.int32)
-    return rank
 
 
 def write_mie(path, wn, ssa, g):
@@ -153,33 +134,6 @@ def test_reorder_cloud_spectrum_exit_codes(tmp_path):
         r = run_tool("reorder_cloud_spectrum", "input=mie.nc", f"isize={isize}", "wavenumber_input=grid.nc", "output=o.nc", cwd=d)
         assert r.returncode == 147 and "isize" in r.stderr, r.stderr
     assert not (d / "o.nc").exists()
-
-
-def partition_numpy(ssi, rank, sv, iband, nband, max_range):
-    """find_g_points.cpp:586-636 as written, with np.cumsum in rank order."""
-    out = dict(n_g_points=[], band_number=[], rank1=[], rank2=[], error=[], median=[])
-    margins = []
-    for b in range(nband):
-        idx = np.nonzero(iband == b)[0]
-        ib, ie = idx[0], idx[-1]
-        mn, mx = sv[ib:ie + 1].min(), sv[ib:ie + 1].max()
-        ng = int((mx - mn) / max_range) + 1
-        out["n_g_points"].append(ng)
-        ireorder = np.empty(ie - ib + 1, dtype=np.int64)
-        ireorder[rank[ib:ie + 1] - ib] = np.arange(ib, ie + 1)
-        cum = np.full(ssi.size, -1.0)
-        cum[ireorder] = np.cumsum(ssi[ireorder])
-        band_irr = ssi[ib:ie + 1].sum()
-        dirr = band_irr * (1.0 + 1.0e-8) / ng
-        bounds = np.arange(ng + 1) * dirr
-        margins.append(np.min(np.abs(cum[ib:ie + 1][:, None] - bounds[None, :])) / band_irr)
-        for jg in range(ng):
-            index = np.nonzero((iband == b) & (cum >= jg * dirr) & (cum < (jg + 1) * dirr))[0]
-            out["rank1"].append(rank[index].min()); out["rank2"].append(rank[index].max())
-            out["error"].append(sv[index].max() - sv[index].min())
-            out["median"].append(-2.0 + np.mean(sv[index]))
-            out["band_number"].append(b)
-    return out, min(margins)
 
 
 def _partition_case(seed, nwav=60000, bands=(0, 9000, 21000, 40000, 52000, 60000)):
