@@ -131,6 +131,7 @@ SIGNATURES = {
     "ecckd_opt_forward_ex": (C.c_int, [C.c_void_p, _c_double_p, C.c_int, _c_double_p, _c_double_p]),
     "ecckd_opt_coefficients": (C.c_int, [C.c_void_p, _c_double_p, C.c_int, _c_double_p]),
     "ecckd_opt_set_rayleigh_prior": (C.c_int, [C.c_void_p, C.c_double]),
+    "ecckd_opt_set_gpoint_truth": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
     "ecckd_opt_rayleigh_coefficients": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p]),
     "ecckd_opt_rayleigh_plan": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ecckd_opt_minimize": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, _c_double_p, C.POINTER(C.c_int),

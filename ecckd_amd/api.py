@@ -924,10 +924,12 @@ class Optimizer:
         (ecckd_opt_create_angles), the transfer of the line-by-line truth made with the same nangle and of
         rt_lw_gpoints(nangle=N); 0: the two-stream form at the diffusivity 1.66, the handle it has always been.  Longwave models
         only, and not with the Rayleigh switches.
+    gpoint_truth, gpoint_profile_weight: the per-g flux-profile term (set_gpoint_truth), set when the weight is > 0; a weight
+        without a truth, or a truth without a weight, is a ValueError.  Longwave models only, with or without nangle.
     """
 
     def __init__(self, ctx, model, scenes, rayleigh_scattering=False, optimize_rayleigh=False, rayleigh_prior_error=0.0, nangle=0,
-                 **cfg):
+                 gpoint_truth=None, gpoint_profile_weight=0.0, **cfg):
         self.ctx = ctx
         self.lib = ctx.lib
         self.nangle = int(nangle)
@@ -958,6 +960,16 @@ class Optimizer:
         self.ncol = sum(int(s.ncol) for s in sc)
         self.nlay = int(sc[0].nlay)
         ctx._children.add(self)
+        if (gpoint_truth is not None) != (float(gpoint_profile_weight) > 0.0):
+            self.close()
+            raise ValueError("Optimizer: gpoint_truth and gpoint_profile_weight > 0 go together "
+                             f"(truth {'given' if gpoint_truth is not None else 'missing'}, weight {gpoint_profile_weight})")
+        if gpoint_truth is not None:
+            try:
+                self.set_gpoint_truth(gpoint_profile_weight, gpoint_truth)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "handle", None):
@@ -1064,6 +1076,23 @@ class Optimizer:
         """sigma of the prior of the optimised Rayleigh coefficients (ecckd_opt_set_rayleigh_prior); <= 0: none.  Refused on a
         handle made without optimize_rayleigh."""
         check(self.lib.ecckd_opt_set_rayleigh_prior(self.handle, float(prior_error)))
+
+    def set_gpoint_truth(self, weight, truth):
+        """The per-g flux-profile term (ecckd_opt_set_gpoint_truth): every column adds
+        weight sum_i hw_i sum_g [((dn - rel_dn) - T_dn)^2 + ((up - rel_up) - T_up)^2] over all half levels, hw_i the mean of the
+        normalised layer weights on either side of level i.  truth: (ncol of all scenes in scene order, 2, nlay + 1, ng), the
+        layout forward() returns and ncio.read_gpoint_fluxes reads from a `lw_spectra gpoints=` file; with relative fluxes, truth
+        minus the relative-to scene's truth.  weight <= 0 or truth None removes the term.  Longwave handles only."""
+        if truth is None or not float(weight) > 0.0:
+            if float(weight) != float(weight):
+                raise ValueError("set_gpoint_truth: the weight is NaN")
+            check(self.lib.ecckd_opt_set_gpoint_truth(self.handle, 0.0, None))
+            return
+        t = np.ascontiguousarray(truth, dtype=np.float64)
+        want = (self.ncol, 2, self.nlay + 1, self.ng)
+        if t.shape != want:
+            raise ValueError(f"set_gpoint_truth: truth has shape {t.shape}, the handle needs (ncol, 2, nlay + 1, ng) = {want}")
+        check(self.lib.ecckd_opt_set_gpoint_truth(self.handle, float(weight), _hptr(t)))
 
     def rayleigh_coefficients(self, x=None):
         """rayleigh_molar_scattering[ng] at state x (ecckd_opt_rayleigh_coefficients): exp of the state's tail as the device forms

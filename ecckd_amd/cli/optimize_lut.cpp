@@ -31,6 +31,14 @@
 // as well.  0: the two-stream form at the diffusivity 1.66.  Refused (exit 147) right after the configuration is read, before
 // the device is opened: a value outside 0..16, nangle > 0 with a shortwave input, and a training_input or relative_to file whose
 // global integer attribute `nangle` differs from the key (a file without the attribute is accepted).
+// gpoint_training_input, gpoint_relative_to, gpoint_profile_weight (not keys of the reference): the flux profile of every g point
+// at every half level enters the cost (ecckd_opt_set_gpoint_truth), weighted by gpoint_profile_weight.  gpoint_training_input: one
+// `lw_spectra gpoints=` file per training_input file, in the same order; gpoint_relative_to: the per-g truth of the relative_to
+// scene, subtracted from each.  Longwave only.  Refused (exit 147) before the device is opened, each with its own message: a
+// weight without files or files without a weight, another number of files than training_input has, a shortwave model,
+// relative_to without gpoint_relative_to or the reverse, a file without spectral_flux_dn_lw / spectral_flux_up_lw, with another
+// number of g points than the model, with other columns or half levels than its training file, with a pressure_hl that differs
+// from the training file's by more than 1e-5 relative, or with a global attribute nangle (absent = 0) that is not the key's.
 // The cost function, its gradient and the L-BFGS iteration run on the GPU (ecckd_opt_*); adept::Minimizer is
 // replaced by the library's own L-BFGS, so iteration counts differ from the reference's.
 #include <algorithm>
@@ -369,6 +377,80 @@ int main(int argc, char** argv) {
           fail(ECCKD_PARAMETER_ERROR, "%s was made with nangle = %d, the key nangle says %d", path.c_str(), (int)std::lround(v), nangle);
       }
     }
+    // ---- the per-g flux-profile term (ecckd_opt_set_gpoint_truth): keys, files and refusals, all before the device is opened ----
+    double gpoint_profile_weight = 0.0;
+    config.read(gpoint_profile_weight, "gpoint_profile_weight");
+    const std::vector<std::string> gpoint_files = config.read_list("gpoint_training_input");
+    std::string gpoint_relative_to;
+    const bool have_gpoint_rel = config.read(gpoint_relative_to, "gpoint_relative_to");
+    std::vector<std::vector<double>> gpoint_truth;   // per training file [ncol][2][nlay+1][ng], gpoint_relative_to's subtracted
+    {
+      const std::vector<std::string> train_files = config.read_list("training_input");
+      std::string rel_name;
+      const bool have_rel_key = config.read(rel_name, "relative_to");
+      if (gpoint_profile_weight > 0.0 && gpoint_files.empty())
+        fail(ECCKD_PARAMETER_ERROR, "gpoint_profile_weight = %g needs gpoint_training_input", gpoint_profile_weight);
+      if (!gpoint_files.empty() && !(gpoint_profile_weight > 0.0))
+        fail(ECCKD_PARAMETER_ERROR, "gpoint_training_input needs gpoint_profile_weight > 0 (it is %g)", gpoint_profile_weight);
+      if (!gpoint_files.empty() && gpoint_files.size() != train_files.size())
+        fail(ECCKD_PARAMETER_ERROR, "gpoint_training_input names %zu files, training_input %zu: one per training file, in the same order",
+             gpoint_files.size(), train_files.size());
+      if (!gpoint_files.empty() && model.is_sw)
+        fail(ECCKD_PARAMETER_ERROR, "gpoint_training_input needs a longwave CKD model, %s is a shortwave one", input.c_str());
+      if (!gpoint_files.empty() && have_rel_key && !have_gpoint_rel)
+        fail(ECCKD_PARAMETER_ERROR, "relative_to with gpoint_training_input needs gpoint_relative_to, the per-g truth of %s", rel_name.c_str());
+      if (have_gpoint_rel && !(have_rel_key && !gpoint_files.empty()))
+        fail(ECCKD_PARAMETER_ERROR, "gpoint_relative_to needs relative_to and gpoint_training_input");
+      // one file: [ncol][2][nhl][ng] of the g points, checked against the model, the key nangle and its training file
+      auto read_gpoints = [&](const std::string& name, const std::string& like_name) {
+        const std::string path = paths.find(name), like_path = paths.find(like_name);
+        NcIn f(path);
+        if (!f.exist("spectral_flux_dn_lw") || !f.exist("spectral_flux_up_lw"))
+          fail(ECCKD_PARAMETER_ERROR, "%s holds no spectral_flux_dn_lw / spectral_flux_up_lw: not a file of lw_spectra gpoints=", path.c_str());
+        const std::vector<size_t> fs = f.shape("spectral_flux_dn_lw");   // (column, half_level, g_point)
+        if (fs.size() != 3 || f.shape("spectral_flux_up_lw") != fs || !f.exist("pressure_hl"))
+          fail(ECCKD_PARAMETER_ERROR, "%s: spectral_flux_dn_lw / spectral_flux_up_lw are not (column, half_level, g_point)", path.c_str());
+        if ((int)fs[2] != model.ng)
+          fail(ECCKD_PARAMETER_ERROR, "%s has %zu g points, the CKD model %d", path.c_str(), fs[2], model.ng);
+        NcIn like(like_path);
+        const std::vector<size_t> ps = like.shape("pressure_hl");
+        if (ps.size() != 2 || ps[0] != fs[0] || ps[1] != fs[1] || f.shape("pressure_hl") != ps)
+          fail(ECCKD_PARAMETER_ERROR, "%s has %zu columns of %zu half levels, its training file %s %zu of %zu", path.c_str(), fs[0], fs[1],
+               like_path.c_str(), ps.empty() ? (size_t)0 : ps[0], ps.size() < 2 ? (size_t)0 : ps[1]);
+        const std::vector<double> p = f.read("pressure_hl"), p_like = like.read("pressure_hl");
+        for (size_t i = 0; i < p.size(); ++i)
+          if (!(std::fabs(p[i] - p_like[i]) <= 1e-5 * std::fabs(p_like[i])))
+            fail(ECCKD_PARAMETER_ERROR, "%s: pressure_hl differs from that of its training file %s by more than 1e-5 (%g against %g)", path.c_str(),
+                 like_path.c_str(), p[i], p_like[i]);
+        int n = -1;
+        double v = 0.0;
+        ck(ecckd_nc_read_att_double(f.handle(), nullptr, "nangle", &n, &v, 1));
+        const int file_nangle = n >= 1 ? (int)std::lround(v) : 0;     // (no attribute: the two-stream form)
+        if (file_nangle != nangle)
+          fail(ECCKD_PARAMETER_ERROR, "%s holds per-g fluxes made with nangle = %d, the key nangle says %d", path.c_str(), file_nangle, nangle);
+        const std::vector<double> dn = f.read("spectral_flux_dn_lw"), up = f.read("spectral_flux_up_lw");
+        const size_t per = fs[1] * fs[2];
+        std::vector<double> out(fs[0] * 2 * per);
+        for (size_t c = 0; c < fs[0]; ++c) {
+          std::copy(dn.begin() + c * per, dn.begin() + (c + 1) * per, out.begin() + (2 * c) * per);
+          std::copy(up.begin() + c * per, up.begin() + (c + 1) * per, out.begin() + (2 * c + 1) * per);
+        }
+        return out;
+      };
+      std::vector<double> gp_rel;
+      if (have_gpoint_rel) gp_rel = read_gpoints(gpoint_relative_to, rel_name);
+      for (size_t i = 0; i < gpoint_files.size(); ++i) {
+        std::vector<double> t = read_gpoints(gpoint_files[i], train_files[i]);
+        if (have_gpoint_rel) {
+          if (t.size() != gp_rel.size())
+            fail(ECCKD_PARAMETER_ERROR, "%s does not match the shape of gpoint_relative_to", gpoint_files[i].c_str());
+          for (size_t e = 0; e < t.size(); ++e) t[e] -= gp_rel[e];
+        }
+        gpoint_truth.push_back(std::move(t));
+      }
+      if (!gpoint_files.empty())
+        LOG("Per-g-point flux profiles of %zu file(s) enter the cost function with gpoint_profile_weight = %g\n", gpoint_files.size(), gpoint_profile_weight);
+    }
     if (nangle > 0) LOG("Longwave forward model: %d Gauss-Legendre zenith angles per hemisphere (nangle = %d)\n", nangle, nangle);
     else if (!model.is_sw) LOG("Longwave forward model: two-stream, diffusivity 1.66 (nangle = 0)\n");
     for (const std::string& g : gas_list) {
@@ -476,6 +558,11 @@ int main(int argc, char** argv) {
     ck(ecckd_opt_create_angles(dev.ctx(), &mv.m, (int)views.size(), views.data(), &oc, opt_flags | (optimize_rayleigh ? ECCKD_OPT_RAYLEIGH_ACTIVE : 0u),
                                nangle, &opt));
     if (optimize_rayleigh) ck(ecckd_opt_set_rayleigh_prior(opt, rayleigh_prior_error));
+    if (!gpoint_truth.empty()) {
+      std::vector<double> truth;                       // the columns of all scenes, in scene order
+      for (const std::vector<double>& t : gpoint_truth) truth.insert(truth.end(), t.begin(), t.end());
+      ck(ecckd_opt_set_gpoint_truth(opt, gpoint_profile_weight, truth.data()));
+    }
     const size_t nx = ecckd_opt_nx(opt);
     LOG("Optimizing %zu coefficients against %zu training file(s)\n", nx, scenes.size());
     std::vector<double> x(nx);

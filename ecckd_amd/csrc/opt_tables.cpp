@@ -567,6 +567,28 @@ int build_tables(const ecckd_opt_model* m, int nscene, const ecckd_opt_scene* sc
   return ECCKD_OK;
 }
 
+int check_gpoint_truth(bool do_sw, bool scattering, bool rayleigh_active, double weight, const double* truth, size_t count, std::string& err) {
+  if (do_sw) {
+    err = "ecckd_opt_set_gpoint_truth: the per-g flux-profile term needs a longwave handle (this one is shortwave)";
+    return ECCKD_PARAMETER_ERROR;
+  }
+  if (scattering || rayleigh_active) {
+    err = "ecckd_opt_set_gpoint_truth: the per-g flux-profile term cannot be combined with the ECCKD_OPT_RAYLEIGH flags";
+    return ECCKD_PARAMETER_ERROR;
+  }
+  if (!std::isfinite(weight)) {
+    err = "ecckd_opt_set_gpoint_truth: the weight is not finite";
+    return ECCKD_PARAMETER_ERROR;
+  }
+  if (!gpoint_truth_active(weight, truth)) return ECCKD_OK;
+  for (size_t e = 0; e < count; ++e)
+    if (!std::isfinite(truth[e])) {
+      err = "ecckd_opt_set_gpoint_truth: truth value " + std::to_string(e) + " of " + std::to_string(count) + " is not finite";
+      return ECCKD_PARAMETER_ERROR;
+    }
+  return ECCKD_OK;
+}
+
 void initial_state(const Layout& l, double* x, double* x_min, double* x_max) {
   for (size_t e = 0; e < l.nx; ++e) x[e] = ln_k0(l.k0[e]);
   if (!(x_min && x_max)) return;

@@ -105,5 +105,15 @@ int build_tables(const ecckd_opt_model* m, int nscene, const ecckd_opt_scene* sc
 // -/+ infinity.
 void initial_state(const Layout& l, double* x, double* x_min, double* x_max);
 
+// ecckd_opt_set_gpoint_truth.  Does the call set the term (a weight > 0 with a truth) or remove it?
+inline bool gpoint_truth_active(double weight, const double* truth) { return weight > 0.0 && truth != nullptr; }
+// Its refusals, ECCKD_PARAMETER_ERROR with the reason in `err`: a shortwave handle, either ECCKD_OPT_RAYLEIGH flag, a weight
+// that is not finite, and - where the call sets the term - a truth value, of `count`, that is not finite.
+int check_gpoint_truth(bool do_sw, bool scattering, bool rayleigh_active, double weight, const double* truth, size_t count, std::string& err);
+// hw_i of the term, the mean of the normalised weights lw[nlay] of the layers that touch half level i: they add up to sum(lw)
+inline double gpoint_level_weight(const double* lw, int nlay, int i) {
+  return 0.5 * ((i >= 1 ? lw[i - 1] : 0.0) + (i <= nlay - 1 ? lw[i] : 0.0));
+}
+
 }  // namespace opt_tables
 }  // namespace ecckd

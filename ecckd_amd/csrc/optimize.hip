@@ -90,6 +90,8 @@ struct K8aArgs {
   double* jcol;                // [ncol] cost of each profile (incl. penalty)
   double* od_out;              // optional [ncell][ng] total optical depth (after clamp)
   double* flux_out;            // optional [ncol][2][nhl][ng]
+  const double* gp_truth;      // [ncol][2][nhl][ng] per-g flux truth of ecckd_opt_set_gpoint_truth (longwave), or NULL: no such term
+  double gp_weight;            // its weight, > 0 where gp_truth is set
 };
 
 constexpr double HR_WEIGHT = 3600.0 * 24.0;
@@ -224,6 +226,38 @@ __device__ __forceinline__ void boundary_term(const K8aArgs& a, int col, int g, 
       g_up_toa_extra = 2.0 * a.spectral_boundary_weight * c;
     }
   }
+}
+
+// The per-g flux-profile term of ecckd_opt_set_gpoint_truth (longwave; the per-g twin of flux_profile_weight, not in the
+// reference): J_gp = w sum_i hw_i sum_g [((dn - rel) - T_dn)^2 + ((up - rel) - T_up)^2] over ALL half levels, hw_i the mean of
+// the normalised weights of the layers that touch level i (half of the one layer at the two ends, so sum_i hw_i = 1).
+// Residual and seed are written once, here.  Called by every thread (layer group lgrp of nlgrp, g point g) of the cell-parallel
+// and the angle kernel once nothing reads the forward flux rows s_D, s_U [nhl][ng] any more - the band sums are formed, the
+// boundary term and the cell owners have taken what they need, a barrier has passed -: the thread turns the two fluxes of ITS
+// half levels i = lgrp, lgrp + nlgrp, ... IN PLACE into the WHOLE seeds of the reversed recurrences at (i, g) - the band seed
+// gdn / gup [nhl][nband] at the band b of g plus this term's 2 w hw_i residual on dJ/d(dn[i]) / dJ/d(up[i]) - and returns the
+// cost of those levels, levels ascending.  The recurrences then find the seed of a level in the row where the forward flux
+// was, in place of the band seed: they read row i before they overwrite it, still one LDS read per level, and the truth is
+// read once, 512 contiguous bytes per wave, by all the waves of the block instead of the one that runs the recurrences.
+// A barrier follows the call.
+__device__ __forceinline__ double gpoint_seed_rows(const K8aArgs& a, const double* lw, int col, int g, int lgrp, int nlgrp, const double* gdn,
+                                                   const double* gup, int b, double* s_D, double* s_U) {
+  const int nlay = a.nlay, nhl = nlay + 1, ng = a.ng, nband = a.nband;
+  const size_t at = (size_t)col * 2 * nhl * ng + g;
+  const double* truth = a.gp_truth + at;
+  const double* rel = a.rel_flux ? a.rel_flux + at : nullptr;
+  double j = 0.0;
+  // (one level at a time: the cell owners hold four values per cell in registers across this loop)
+#pragma unroll 1
+  for (int i = lgrp; i < nhl; i += nlgrp) {
+    const double whw = a.gp_weight * (0.5 * ((i >= 1 ? lw[i - 1] : 0.0) + (i <= nlay - 1 ? lw[i] : 0.0)));
+    const double rd = (s_D[i * ng + g] - (rel ? rel[(size_t)i * ng] : 0.0)) - truth[(size_t)i * ng];
+    const double ru = (s_U[i * ng + g] - (rel ? rel[(size_t)(nhl + i) * ng] : 0.0)) - truth[(size_t)(nhl + i) * ng];
+    j += whw * (rd * rd + ru * ru);
+    s_D[i * ng + g] = gdn[i * nband + b] + 2.0 * whw * rd;
+    s_U[i * ng + g] = gup[i * nband + b] + 2.0 * whw * ru;
+  }
+  return j;
 }
 
 // K8a, the general kernel.  grid = ncolumns (all scenes), block = ng rounded up to 64, LDS: lds::general.
@@ -479,18 +513,38 @@ __global__ void k_opt_forward_adjoint(const K8aArgs a, int do_sw) {
     const int b = band_of_g[g];
     const double es = surf_emis[(size_t)col * nband + b];
     boundary_term<false>(a, col, g, flux, jpart, g_dn_surf_extra, g_up_toa_extra);
+    // The per-g flux-profile term (ecckd_opt_set_gpoint_truth), in this kernel's own plain form (gpoint_seed_rows is the other two's):
+    // its cost, half levels ascending, then gp_dn / gp_up give the seed of a level from the forward flux still in LDS
+    const bool gp = a.gp_truth != nullptr;
+    const double* gp_t = gp ? a.gp_truth + (size_t)col * 2 * nhl * ng + g : nullptr;
+    const double* gp_r = (gp && rel_flux) ? rel_flux + (size_t)col * 2 * nhl * ng + g : nullptr;
+    auto gp_hw = [&](int i) { return 0.5 * ((i > 0 ? lw[i - 1] : 0.0) + (i < nlay ? lw[i] : 0.0)); };
+    auto gp_dn = [&](int i) { return (s_fdn[i * ng + g] - (gp_r ? gp_r[(size_t)i * ng] : 0.0)) - gp_t[(size_t)i * ng]; };
+    auto gp_up = [&](int i) { return (s_fup[i * ng + g] - (gp_r ? gp_r[(size_t)(nhl + i) * ng] : 0.0)) - gp_t[(size_t)(nhl + i) * ng]; };
+    if (gp) {
+      double jg = 0.0;
+      for (int i = 0; i < nhl; ++i) {
+        const double rd = gp_dn(i), ru = gp_up(i);
+        jg += gp_hw(i) * (rd * rd + ru * ru);
+      }
+      jpart += a.gp_weight * jg;
+    }
     // Adjoint of the up sweep.  It ran l = nlay-1 .. 0 (up_l from up_{l+1}), so the adjoint of
     // up[l] is complete once levels 0..l-1 have been visited: u_bar[0] = seed[0],
     // u_bar[l+1] = seed[l+1] + u_bar[l]*(1-eps_l).  u_bar[l] overwrites the forward up[l] in LDS
     // (the forward values are re-generated from the surface in the combine loop below).
     double up_bar = s_gup[b] + g_up_toa_extra;  // level 0
+    if (gp) up_bar += 2.0 * a.gp_weight * gp_hw(0) * gp_up(0);
     for (int l = 0; l < nlay; ++l) {
       const double eps = 1.0 - ecckd::exp_fast(-kD * s_tau[l * ng + g]);
+      double seed = s_gup[(l + 1) * nband + b];
+      if (gp) seed += 2.0 * a.gp_weight * gp_hw(l + 1) * gp_up(l + 1);   // (row l + 1 still holds the forward up)
       s_fup[l * ng + g] = up_bar;
-      up_bar = up_bar * (1.0 - eps) + s_gup[(l + 1) * nband + b];
+      up_bar = up_bar * (1.0 - eps) + seed;
     }
     // up_bar is now the adjoint of up[nlay]; through the surface condition it feeds dn[nlay].
     double dn_bar = s_gdn[nlay * nband + b] + g_dn_surf_extra + up_bar * (1.0 - es);
+    if (gp) dn_bar += 2.0 * a.gp_weight * gp_hw(nlay) * gp_dn(nlay);
     // forward up[l+1] values: rebuild from the surface
     double up_fwd_next = pl[nlay * ng + g] * es + (1.0 - es) * s_fdn[nlay * ng + g];  // up[nlay]
     for (int l = nlay - 1; l >= 0; --l) {
@@ -517,7 +571,9 @@ __global__ void k_opt_forward_adjoint(const K8aArgs a, int do_sw) {
       // propagate
       const double up_l = up_fwd_next * (1.0 - eps) + b1 * (eps - fac) + b0 * fac;
       up_fwd_next = up_l;
-      dn_bar = dn_bar * (1.0 - eps) + s_gdn[l * nband + b];
+      double seed = s_gdn[l * nband + b];
+      if (gp) seed += 2.0 * a.gp_weight * gp_hw(l) * gp_dn(l);
+      dn_bar = dn_bar * (1.0 - eps) + seed;
     }
   }
   jpart += a.negative_od_penalty * penalty;
@@ -711,7 +767,9 @@ __device__ __forceinline__ void cost_seed(const K8aArgs& a, const ColumnTruth& c
   }
 }
 
-template <int NC, bool SW, int NB>
+// GP (longwave only): the handle carries the per-g flux-profile term (gpoint_seed_rows); its seeds join the band seeds where phase E
+// loads them.  A template argument, so that the instances of the handles without the term are the code they have always been.
+template <int NC, bool SW, int NB, bool GP = false>
 __global__ void __launch_bounds__(1024)
 k_opt_forward_adjoint_cells(const K8aArgs a, const int* __restrict__ band_ptr /*[nband+1]*/, const int* __restrict__ band_g /*[ng]: g points by band*/) {
   extern __shared__ double smem[];
@@ -914,7 +972,13 @@ k_opt_forward_adjoint_cells(const K8aArgs a, const int* __restrict__ band_ptr /*
   }
   double g_dn_surf_extra = 0.0, g_up_toa_extra = 0.0;
   if (live) boundary_term<SW>(a, col, g, flux, jpart, g_dn_surf_extra, g_up_toa_extra);
+  static_assert(!(GP && SW), "the per-g flux-profile term is longwave only");
   __syncthreads();
+  if constexpr (GP) {
+    // the flux rows become the seeds of the per-g flux-profile term (the owners hold the forward fluxes they need in c_f0, c_f1)
+    if (in_range) jpart += gpoint_seed_rows(a, ct.lw, col, g, lgrp, nlgrp, s_gdn, s_gup, band_of_g[g], s_D, s_U);
+    __syncthreads();
+  }
   if constexpr (SW) {
     // the transmittances back into the rows the fluxes occupied
 #pragma unroll
@@ -930,19 +994,21 @@ k_opt_forward_adjoint_cells(const K8aArgs a, const int* __restrict__ band_ptr /*
   if (live) {
     const int b = band_of_g[g];
     // u_bar[0] = seed[0], u_bar[l+1] = seed[l+1] + u_bar[l] t_l: row l of s_U becomes the adjoint of up[l]
-    double up_bar = s_gup[b] + g_up_toa_extra;
+    double up_bar = (GP ? s_U[g] : s_gup[b]) + g_up_toa_extra;
     double* pD = s_D + g;
     double* pU = s_U + g;
     const double* pT = s_T + g;
     const double* gU = s_gup + b;
     const double* gD = s_gdn + b;
+    // (GP: the seed of a level comes from row l + 1 of s_U / row l of s_D, which still hold it when the recurrence adds it - each
+    // row is overwritten one step later, and a chunk loads all its rows before it stores any)
     int l = 0;
     for (; l + K8A_CH <= nlay; l += K8A_CH) {
       double tt[K8A_CH], ss[K8A_CH];
 #pragma unroll
       for (int q = 0; q < K8A_CH; ++q) {
         tt[q] = SW ? pU[(l + q) * ng] : pT[(l + q) * ng];
-        ss[q] = gU[(l + q + 1) * nband];
+        ss[q] = GP ? pU[(l + q + 1) * ng] : gU[(l + q + 1) * nband];
       }
 #pragma unroll
       for (int q = 0; q < K8A_CH; ++q) {
@@ -952,19 +1018,22 @@ k_opt_forward_adjoint_cells(const K8aArgs a, const int* __restrict__ band_ptr /*
     }
     for (; l < nlay; ++l) {
       const double t = SW ? pU[l * ng] : pT[l * ng];
+      double seed = 0.0;
+      if constexpr (GP) seed = pU[(l + 1) * ng];
       pU[l * ng] = up_bar;
-      up_bar = up_bar * t + gU[(l + 1) * nband];
+      if constexpr (GP) up_bar = up_bar * t + seed;
+      else up_bar = up_bar * t + gU[(l + 1) * nband];
     }
     // through the surface condition into dn[nlay]; row l+1 of s_D becomes the adjoint of dn[l+1]
     const double refl = SW ? (all_nonpos ? 0.0 : surf_emis[(size_t)col * nband + b]) : 1.0 - surf_emis[(size_t)col * nband + b];
-    double dn_bar = gD[nlay * nband] + g_dn_surf_extra + up_bar * refl;
+    double dn_bar = (GP ? pD[nlay * ng] : gD[nlay * nband]) + g_dn_surf_extra + up_bar * refl;
     l = nlay - 1;
     for (; l - (K8A_CH - 1) >= 0; l -= K8A_CH) {
       double tt[K8A_CH], ss[K8A_CH];
 #pragma unroll
       for (int q = 0; q < K8A_CH; ++q) {
         tt[q] = SW ? pD[(l - q + 1) * ng] : pT[(l - q) * ng];
-        ss[q] = gD[(l - q) * nband];
+        ss[q] = GP ? pD[(l - q) * ng] : gD[(l - q) * nband];
       }
 #pragma unroll
       for (int q = 0; q < K8A_CH; ++q) {
@@ -974,8 +1043,11 @@ k_opt_forward_adjoint_cells(const K8aArgs a, const int* __restrict__ band_ptr /*
     }
     for (; l >= 0; --l) {
       const double t = SW ? pD[(l + 1) * ng] : pT[l * ng];
+      double seed = 0.0;
+      if constexpr (GP) seed = pD[l * ng];
       pD[(l + 1) * ng] = dn_bar;
-      dn_bar = dn_bar * t + gD[l * nband];
+      if constexpr (GP) dn_bar = dn_bar * t + seed;
+      else dn_bar = dn_bar * t + gD[l * nband];
     }
   }
   __syncthreads();
@@ -989,7 +1061,10 @@ k_opt_forward_adjoint_cells(const K8aArgs a, const int* __restrict__ band_ptr /*
         // up_l = up_l+1 exp(-2 tau_l), dn_l+1 = dn_l exp(-tau_l / mu0)
         tau_bar = ubar_l * c_f1[j] * (-2.0) + dnbar * c_f0[j] * minus_sec_sza;
       } else {
-        tau_bar = lw_tau_bar(dnbar, ubar_l, c_f0[j], c_f1[j], pl[l * ng + g], pl[(l + 1) * ng + g], c_tau[j], c_t[j]);
+        // (GP: exp(-D tau) comes back from the row of s_T, 1 - eps, which nothing overwrites - one rounding of 1 away from the
+        // value the owner formed -, so that the instance keeps eight doubles fewer across phase E and stays out of scratch)
+        const double ex = GP ? s_T[l * ng + g] : c_t[j];
+        tau_bar = lw_tau_bar(dnbar, ubar_l, c_f0[j], c_f1[j], pl[l * ng + g], pl[(l + 1) * ng + g], c_tau[j], ex);
       }
       dtau[(cell0 + l) * ng + g] = tau_bar;
     }
@@ -1494,14 +1569,24 @@ k_opt_forward_adjoint_lw_angles(const K8aArgs a, const int* __restrict__ band_pt
     if (lgrp == 0) jpart += jb;
   }
   __syncthreads();
+  // the per-g flux-profile term: nothing below reads the angle-summed rows s_D / s_U, so they become its seeds; every angle owner
+  // adds the seed of a level where its chain loads the band seed, and scales the sum by wgt_k
+  const bool gp = a.gp_truth != nullptr;
+  if (gp) {
+    if (in_range) jpart += gpoint_seed_rows(a, ct.lw, col, g, lgrp, nlgrp, s_gdn, s_gup, a.band_of_g[g], s_D, s_U);
+    __syncthreads();
+  }
   // ---- E1: the up chains reversed; row nlay of ub_k is the adjoint of up_k at the surface ----
   const int b = a.band_of_g[gl];
   if (in_range)
     for (int kk = lgrp; kk < nang; kk += nlgrp) {
       double* pB = wk(kk, LA_UB);
       const double wg = wgt[kk];
-      const double ub = lwa_chain<true>(wg * (s_gup[b] + up_toa_extra), wk(kk, LA_T), ng, nlay, 0, 1,
-                                        [&](int l) { return wg * s_gup[(l + 1) * nband + b]; },
+      const double ub0 = (gp ? s_U[g] : s_gup[b]) + up_toa_extra;
+      const double ub = lwa_chain<true>(wg * ub0, wk(kk, LA_T), ng, nlay, 0, 1,
+                                        [&](int l) {
+                                          return wg * (gp ? s_U[(l + 1) * ng + g] : s_gup[(l + 1) * nband + b]);
+                                        },
                                         [&](int l, double x) { pB[(size_t)l * ng] = x; });
       pB[(size_t)nlay * ng] = ub;
     }
@@ -1513,8 +1598,12 @@ k_opt_forward_adjoint_lw_angles(const K8aArgs a, const int* __restrict__ band_pt
       for (int j = 0; j < nang; ++j) ub_surf += wk(j, LA_UB)[(size_t)nlay * ng];
       double* pB = wk(kk, LA_DB);
       const double wg = wgt[kk];
-      lwa_chain<true>(wg * (s_gdn[nlay * nband + b] + dn_surf_extra + (1.0 - es) * ub_surf), wk(kk, LA_T), ng, nlay, nlay - 1, -1,
-                      [&](int l) { return wg * s_gdn[l * nband + b]; }, [&](int l, double x) { pB[(size_t)(l + 1) * ng] = x; });
+      const double db0 = (gp ? s_D[nlay * ng + g] : s_gdn[nlay * nband + b]) + dn_surf_extra + (1.0 - es) * ub_surf;
+      lwa_chain<true>(wg * db0, wk(kk, LA_T), ng, nlay, nlay - 1, -1,
+                      [&](int l) {
+                        return wg * (gp ? s_D[l * ng + g] : s_gdn[l * nband + b]);
+                      },
+                      [&](int l, double x) { pB[(size_t)(l + 1) * ng] = x; });
     }
   __syncthreads();
   // ---- E3: dJ/dtau of the cells of this thread, the angles in order; a clamped cell keeps the penalty's derivative ----
@@ -2078,7 +2167,17 @@ struct ecckd_opt : ot::Layout {
     *p = (T*)v;
     return e;
   }
+  // frees a block that alloc() recorded and forgets it
+  template <typename T> void release(T** p) {
+    if (!*p) return;
+    blocks.erase(std::remove(blocks.begin(), blocks.end(), (void*)*p), blocks.end());
+    (void)hipFree(*p);
+    *p = nullptr;
+  }
   double* d_rel = nullptr;   // relative-to CKD fluxes [ncol][2][nhl][ng]
+  // ecckd_opt_set_gpoint_truth: the per-g flux truth [ncol][2][nhl][ng] (the layout of d_rel) and its weight; NULL / 0: no such term
+  double* d_gp_truth = nullptr;
+  double gp_weight = 0.0;
   double* d_ray_ws = nullptr;   // scattering handles: the per-(level, g) state of k_opt_forward_adjoint_rayleigh [ncol][RS_COUNT][nhl][ng]
   double* d_mu0 = nullptr;
   // ecckd_opt_create_angles with nangle > 0: the longwave forward model is the zenith-angle quadrature; [3][nangle] sec, 1 / sec,
@@ -2390,6 +2489,30 @@ int ecckd_opt_rayleigh_plan(ecckd_opt* o, ecckd_rayleigh_plan* out) {
   return ECCKD_OK;
 }
 
+// The per-g flux-profile term (gpoint_seed_rows of the K8a kernels): weight and truth [ncol][2][nhl][ng], columns in scene order.
+// weight <= 0 or h_truth == NULL removes the term and frees its block: the handle is then the handle it was.
+int ecckd_opt_set_gpoint_truth(ecckd_opt* o, double weight, const double* h_truth) {
+  ECCKD_REQUIRE(o, "ecckd_opt_set_gpoint_truth: NULL handle");
+  ecckd_ctx* ctx = o->ctx;
+  const size_t count = o->ncol * 2 * (size_t)(o->nlay + 1) * o->ng;
+  std::string refusal;
+  const int rc = ot::check_gpoint_truth(o->do_sw, o->scattering, o->rayleigh_active, weight, h_truth, count, refusal);
+  if (rc != ECCKD_OK) return ecckd::fail(rc, "%s", refusal.c_str());
+  ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
+  ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  if (!ot::gpoint_truth_active(weight, h_truth)) {
+    o->release(&o->d_gp_truth);
+    o->gp_weight = 0.0;
+    return ECCKD_OK;
+  }
+  if (!o->d_gp_truth && o->alloc(&o->d_gp_truth, count) != hipSuccess)
+    return ecckd::fail(ECCKD_OUT_OF_MEMORY, "ecckd_opt_set_gpoint_truth: device allocation failed (%zu B)", count * sizeof(double));
+  ECCKD_HIP_CHECK(hipMemcpyAsync(o->d_gp_truth, h_truth, count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  o->gp_weight = weight;
+  return ECCKD_OK;
+}
+
 int ecckd_opt_set_allreduce(ecckd_opt* o, ecckd_allreduce_fn fn, void* user, int add_prior) {
   ECCKD_REQUIRE(o, "ecckd_opt_set_allreduce: NULL argument");
   o->reduce_fn = fn;
@@ -2424,31 +2547,34 @@ K8aArgs k8a_args(const ecckd_opt* o, const ecckd_forward_plan& p) {
   a.flux_weight = o->cfg.flux_weight; a.flux_profile_weight = o->cfg.flux_profile_weight; a.broadband_weight = o->cfg.broadband_weight;
   a.spectral_boundary_weight = o->cfg.spectral_boundary_weight; a.negative_od_penalty = o->cfg.negative_od_penalty;
   a.dtau = o->d_dtau; a.jcol = o->d_jcol; a.od_out = o->d_od_out; a.flux_out = o->d_flux_out;
+  a.gp_truth = o->d_gp_truth; a.gp_weight = o->d_gp_truth ? o->gp_weight : 0.0;
   return a;
 }
 
-// The cell-parallel K8a kernel, one instance per (cells per thread, shortwave, 8-entry batches of a cell's table).
-template <int NC, bool SW, int NB>
+// The cell-parallel K8a kernel, one instance per (cells per thread, shortwave, 8-entry batches of a cell's table, and in the
+// longwave the per-g flux-profile term).
+template <int NC, bool SW, int NB, bool GP = false>
 int launch_cells(ecckd_opt* o, const ecckd_forward_plan& p) {
-  const auto kernel = k_opt_forward_adjoint_cells<NC, SW, NB>;
+  const auto kernel = k_opt_forward_adjoint_cells<NC, SW, NB, GP>;
   ECCKD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   hipLaunchKernelGGL(kernel, dim3((unsigned)o->ncol), dim3(p.threads), p.lds_bytes, o->ctx->stream, k8a_args(o, p), o->d_band_ptr, o->d_band_g);
   return ECCKD_OK;
 }
 
-template <int NC, bool SW>
+template <int NC, bool SW, bool GP = false>
 int launch_cells_nb(ecckd_opt* o, const ecckd_forward_plan& p) {
   switch (p.nb) {
-    case 1: return launch_cells<NC, SW, 1>(o, p);
-    case 2: return launch_cells<NC, SW, 2>(o, p);
-    case 3: return launch_cells<NC, SW, 3>(o, p);
-    case 4: return launch_cells<NC, SW, 4>(o, p);
-    default: return launch_cells<NC, SW, 0>(o, p);
+    case 1: return launch_cells<NC, SW, 1, GP>(o, p);
+    case 2: return launch_cells<NC, SW, 2, GP>(o, p);
+    case 3: return launch_cells<NC, SW, 3, GP>(o, p);
+    case 4: return launch_cells<NC, SW, 4, GP>(o, p);
+    default: return launch_cells<NC, SW, 0, GP>(o, p);
   }
 }
 
 int launch_cells_for(ecckd_opt* o, const ecckd_forward_plan& p) {   // p.nc_template: 4 or 8, the instance
   if (o->do_sw) return p.nc_template <= 4 ? launch_cells_nb<4, true>(o, p) : launch_cells_nb<8, true>(o, p);
+  if (o->d_gp_truth) return p.nc_template <= 4 ? launch_cells_nb<4, false, true>(o, p) : launch_cells_nb<8, false, true>(o, p);
   return p.nc_template <= 4 ? launch_cells_nb<4, false>(o, p) : launch_cells_nb<8, false>(o, p);
 }
 

@@ -523,6 +523,31 @@ def lbl_fluxes_nangle(path):
     return None if v is None or v.size == 0 else int(round(float(v[0])))
 
 
+def read_gpoint_fluxes(path):
+    """The per-g-point flux profiles of a `lw_spectra gpoints=` file (write_lw_spectra with g points), the truth of the
+    optimiser's per-g flux-profile term: dict(flux (ncol, 2, nhl, ng) float64 - [:, 0] spectral_flux_dn_lw, [:, 1]
+    spectral_flux_up_lw, the layout of Optimizer.set_gpoint_truth -, pressure_hl (ncol, nhl), nangle: the global attribute, 0
+    where the file carries none).  A file without the two variables on a g_point axis is a ValueError."""
+    with NcFile(path) as f:
+        for name in ("spectral_flux_dn_lw", "spectral_flux_up_lw"):
+            if not f.exist(name):
+                raise ValueError(f"{path}: no variable {name} (not a file of `lw_spectra gpoints=`)")
+        try:
+            have_g = f.dim("g_point") > 0
+        except _lib.EcckdError:
+            have_g = False
+        if not have_g:
+            raise ValueError(f"{path}: no dimension g_point (a per-wavenumber file of lw_spectra, not one written with gpoints=)")
+        dn = np.asarray(f.read("spectral_flux_dn_lw"), dtype=np.float64)
+        up = np.asarray(f.read("spectral_flux_up_lw"), dtype=np.float64)
+        p = np.asarray(f.read("pressure_hl"), dtype=np.float64)
+        v = f.att_values("nangle")
+    if dn.ndim != 3 or dn.shape != up.shape or p.shape != dn.shape[:2]:
+        raise ValueError(f"{path}: spectral_flux_dn_lw {dn.shape}, spectral_flux_up_lw {up.shape} and pressure_hl {p.shape} do not agree")
+    return {"flux": np.ascontiguousarray(np.stack([dn, up], axis=1)), "pressure_hl": p,
+            "nangle": 0 if v is None or v.size == 0 else int(round(float(v[0])))}
+
+
 def mask_rayleigh_up(scene, max_no_rayleigh_wavenumber):
     """LblFluxes::mask_rayleigh_up (lbl_fluxes.cpp:415-429): bands above the limit lose their upwelling."""
     idx = scene["band_wavenumber2"] > max_no_rayleigh_wavenumber

@@ -218,7 +218,8 @@ def iband_per_g(model, wavenumber1, wavenumber2):
 
 def optimize_lut(ctx, model, training_files, relative_to=None, band_mapping=None, gmap=None, max_iterations=3000,
                  convergence_criterion=0.0, bounded=True, max_no_rayleigh_wavenumber=None, erythemal_weight=0.0,
-                 remove_min_max=False, rayleigh_scattering=False, optimize_rayleigh=False, rayleigh_prior_error=0.0, nangle=0, **cfg):
+                 remove_min_max=False, rayleigh_scattering=False, optimize_rayleigh=False, rayleigh_prior_error=0.0, nangle=0,
+                 gpoint_training_input=None, gpoint_relative_to=None, gpoint_profile_weight=0.0, **cfg):
     """The driver of optimize_lut.cpp:60-330 on top of api.Optimizer: training scenes from LBL flux files
     (ncio.read_lbl_fluxes), optional "relative_to" file, bounded L-BFGS, optimised coefficients back into the model.
 
@@ -237,9 +238,30 @@ def optimize_lut(ctx, model, training_files, relative_to=None, band_mapping=None
     nangle: N in 1..16: train a longwave model under the zenith-angle quadrature the truth files were made with (`ckdmip_lw` with
            nangle = N; api.Optimizer(nangle=N), the tool's key of the same name), for the relative_to handle as well; 0: the
            two-stream form.  A file that carries a global attribute `nangle` must agree with the key.
+    gpoint_training_input, gpoint_profile_weight: the per-g flux-profile term (Optimizer.set_gpoint_truth; the tool's keys of the
+           same names, none of them the reference's): one `lw_spectra gpoints=` file per training file, in the same order, and the
+           weight of the term; both or neither.  gpoint_relative_to: the per-g truth of the relative_to scene, given exactly when
+           relative_to is; it is subtracted from every file's truth.  Longwave models only.  Every file must hold the model's g
+           points, the columns, half levels and (to 1e-5) pressures of its training file, and the nangle of the key nangle (a
+           file without the attribute counts as 0).
     Returns (model with optimised molar_abs, result dict of Optimizer.minimize)."""
     names = [g["name"] for g in model["gases"]]
     is_sw = model.get("solar_irradiance") is not None
+    gp_files = list(gpoint_training_input) if gpoint_training_input else []
+    gp_weight = float(gpoint_profile_weight)
+    if gp_weight > 0.0 and not gp_files:
+        raise EcckdError(PARAMETER_ERROR, "gpoint_profile_weight > 0 needs gpoint_training_input")
+    if gp_files and not gp_weight > 0.0:
+        raise EcckdError(PARAMETER_ERROR, "gpoint_training_input needs gpoint_profile_weight > 0")
+    if gp_files:
+        if len(gp_files) != len(list(training_files)):
+            raise EcckdError(PARAMETER_ERROR, f"gpoint_training_input names {len(gp_files)} files, training_input {len(list(training_files))}")
+        if is_sw:
+            raise EcckdError(PARAMETER_ERROR, "gpoint_training_input needs a longwave CKD model")
+        if relative_to is not None and gpoint_relative_to is None:
+            raise EcckdError(PARAMETER_ERROR, "relative_to with gpoint_training_input needs gpoint_relative_to")
+    if gpoint_relative_to is not None and (relative_to is None or not gp_files):
+        raise EcckdError(PARAMETER_ERROR, "gpoint_relative_to needs relative_to and gpoint_training_input")
     if rayleigh_scattering and not (is_sw and model.get("rayleigh_molar_scattering") is not None):
         raise EcckdError(PARAMETER_ERROR, "rayleigh_scattering needs a shortwave CKD model with a Rayleigh coefficient")
     if optimize_rayleigh and not (is_sw and model.get("rayleigh_molar_scattering") is not None):
@@ -274,10 +296,37 @@ def optimize_lut(ctx, model, training_files, relative_to=None, band_mapping=None
                                 **cfg)
         _, fl = ref_opt.forward(ref_opt.initial_state(), unclamped=True)     # od = value(aod), no clamp (:231-234)
         ref_opt.close()
+    def load_gpoints(path, like):
+        # the per-g truth of the scene `like`, checked against it, the model and the key nangle
+        try:
+            t = ncio.read_gpoint_fluxes(path)
+        except ValueError as exc:
+            raise EcckdError(PARAMETER_ERROR, str(exc))
+        ng = int(np.asarray(model["iband_per_g"]).size)
+        if t["flux"].shape[3] != ng:
+            raise EcckdError(PARAMETER_ERROR, f"{path} has {t['flux'].shape[3]} g points, the CKD model {ng}")
+        p = np.asarray(like["pressure_hl"], dtype=np.float64)
+        if t["pressure_hl"].shape != p.shape:
+            raise EcckdError(PARAMETER_ERROR, f"{path} has (columns, half levels) = {t['pressure_hl'].shape}, its training file {p.shape}")
+        if np.any(np.abs(t["pressure_hl"] - p) > 1e-5 * np.abs(p)):
+            raise EcckdError(PARAMETER_ERROR, f"{path}: pressure_hl differs from its training file's by more than 1e-5")
+        if t["nangle"] != nangle:
+            raise EcckdError(PARAMETER_ERROR, f"{path} was made with nangle = {t['nangle']}, the key nangle says {nangle}")
+        return t["flux"]
+
+    gp_rel = load_gpoints(gpoint_relative_to, rel) if gpoint_relative_to is not None else None
+    gp_truth = []
     scenes = []
     iband = None
-    for path in training_files:
+    for ifile, path in enumerate(training_files):
         s = load(path)
+        if gp_files:
+            t = load_gpoints(gp_files[ifile], s)
+            if gp_rel is not None:
+                if gp_rel.shape != t.shape:
+                    raise EcckdError(PARAMETER_ERROR, f"{gp_files[ifile]} and {gpoint_relative_to} differ in shape: {t.shape}, {gp_rel.shape}")
+                t = t - gp_rel
+            gp_truth.append(t)
         if rel is not None:
             ncio.subtract_lbl_fluxes(s, rel)                                                         # :251-254
         sc = _scene_for_optimizer(s, is_sw)
@@ -291,7 +340,9 @@ def optimize_lut(ctx, model, training_files, relative_to=None, band_mapping=None
     if iband is not None:
         m["iband_per_g"] = iband
     opt = api.Optimizer(ctx, m, scenes, rayleigh_scattering=rayleigh_scattering, optimize_rayleigh=optimize_rayleigh,
-                        rayleigh_prior_error=rayleigh_prior_error, nangle=nangle, **dict(dict(cap_relative_linear=0.8), **cfg))   # :185
+                        rayleigh_prior_error=rayleigh_prior_error, nangle=nangle,
+                        gpoint_truth=np.concatenate(gp_truth, axis=0) if gp_truth else None, gpoint_profile_weight=gp_weight,
+                        **dict(dict(cap_relative_linear=0.8), **cfg))   # :185
     res = opt.minimize(max_iterations=max_iterations, convergence_criterion=convergence_criterion, bounded=bounded)
     out = dict(model, gases=[dict(g) for g in model["gases"]])
     for i, g in enumerate(out["gases"]):

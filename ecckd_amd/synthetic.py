@@ -271,7 +271,7 @@ def ckd_model(ng=12, nt=5, np_=16, nband=3, seed=0, nconc=4):
         g["min_molar_abs"] = g["molar_abs"] * 0.5
         g["max_molar_abs"] = g["molar_abs"] * 2.0
     gases[2]["min_molar_abs"] = gases[2]["min_molar_abs"].copy()
-    gases[2]["min_molar_abs"][:, :, 3] = 0.0                # exercises the k_min == 0 bound rule
+    gases[2]["min_molar_abs"][:, :, min(3, ng - 1)] = 0.0   # exercises the k_min == 0 bound rule (models of fewer than 4 g points: at the last)
     return dict(log_pressure=log_p, temperature=temperature, temperature_planck=tpl, planck_function=planck,
                 iband_per_g=iband, gases=gases, nband=nband)
 

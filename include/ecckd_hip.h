@@ -872,6 +872,21 @@ int ecckd_opt_coefficients(ecckd_opt* opt, const double* h_x, int gas, double* h
  * (ckd_model.cpp:869-874), and a cost whose gradient omits one of its terms is not a minimisation.  The term follows add_prior
  * of ecckd_opt_set_allreduce as the gases' prior does.  Refused (ECCKD_PARAMETER_ERROR) on a handle without the flag. */
 int ecckd_opt_set_rayleigh_prior(ecckd_opt* opt, double prior_error);
+/* Longwave handles, with or without nangle: the flux profile of every g point at every half level enters the cost (not in the
+ * reference; the per-g twin of flux_profile_weight, the truth is what `lw_spectra gpoints=` writes).  Every column adds
+ *   J_gp = weight sum_{i=0..nlay} hw_i sum_g [((dn[i][g] - rel_dn[i][g]) - T_dn[i][g])^2 + ((up[i][g] - rel_up[i][g]) - T_up[i][g])^2]
+ *   hw_i = 0.5 (lw[i-1] + lw[i]) for 1 <= i <= nlay-1,  hw_0 = 0.5 lw[0],  hw_nlay = 0.5 lw[nlay-1]
+ * with lw the column's normalised layer weights (sum_i hw_i = 1), dn and up the per-g fluxes of the forward model (after clamp
+ * and penalty, summed over the angles when nangle > 0), rel the scene's relative_flux_* or 0, and T = h_truth, [columns of all
+ * scenes in scene order][2: dn, up][nlay+1][ng] - the layout of h_flux of ecckd_opt_forward.  With relative_to the caller passes
+ * truth minus the relative-to scene's truth, the convention of flux_dn.  The gradient is hand-derived: the reversed recurrences
+ * receive 2 weight hw_i residual on dn_bar[i] / up_bar[i] (each angle scaled by wgt_k).  Nothing else in the cost changes, every
+ * sum keeps a fixed order, cost and gradient stay bitwise reproducible.  weight <= 0 or h_truth == NULL removes the term and frees
+ * its device block: the handle is then the handle it was, bit for bit.  ecckd_opt_forward_plan reports the same fields for a handle
+ * with the term; of the cell-parallel kernel it runs the instance <nc_template, longwave, nb, with the term>.  Profile-sharded ranks
+ * pass the truth of their own columns.  Refused with ECCKD_PARAMETER_ERROR: a shortwave handle, either ECCKD_OPT_RAYLEIGH flag, a
+ * weight or (where the term is set) a truth value that is not finite. */
+int ecckd_opt_set_gpoint_truth(ecckd_opt* opt, double weight, const double* h_truth);
 /* h_coeff[ng] = rayleigh_molar_scattering at state h_x: exp of the state's tail (0 where pinned) for a handle made with
  * ECCKD_OPT_RAYLEIGH_ACTIVE, formed on the device by the kernel that feeds the forward model, so these are the numbers the
  * cost at h_x was computed from, bit for bit; the model's own values for any other handle or h_x = NULL.  Refused if the model

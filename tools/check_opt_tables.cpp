@@ -6,7 +6,8 @@
 // pairs than the ring holds, one rejected, one restart; the triangular solves are checked by their residuals.  First of all the
 // LDS layouts of the K8a kernels (csrc/opt_lds.hpp): nlay 1 / 17 / 54 / 128 x ng 1 / 64 / 70 x nband 1 / 13, longwave and shortwave.
 // Last the tables of a handle that optimises the Rayleigh coefficients (Tables::rayleigh_active): with active gases against the
-// tables without the flag, Rayleigh alone, a zero coefficient, and the flag on a longwave model, refused.
+// tables without the flag, Rayleigh alone, a zero coefficient, and the flag on a longwave model, refused.  And the host step of
+// ecckd_opt_set_gpoint_truth (check_gpoint_truth, gpoint_level_weight) at 1 / 7 / 8 / 9 / 17 layers x 1 / 3 / 64 / 65 g points.
 // build: g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Iecckd_amd/csrc tools/check_opt_tables.cpp \
 //        ecckd_amd/csrc/opt_tables.cpp -o /tmp/check_opt_tables && /tmp/check_opt_tables
 #include <algorithm>
@@ -409,7 +410,53 @@ static int check_lds() {
   return ncase;
 }
 
+// The host step of ecckd_opt_set_gpoint_truth (check_gpoint_truth) at the edge shapes - one layer, 1 / 64 / 65 g points, one and two
+// columns -: a finite truth passes and every element of it is read (the last one made NaN or infinite is found), a removal
+// passes with no truth at all, the refusals refuse; and the level weights of the term add up to the layer weights' sum.
+static int check_gpoint() {
+  static char label[96];
+  std::string err;
+  int ncase = 0;
+  for (size_t ncol : {1, 2})
+    for (size_t nlay : {1, 7, 8, 9, 17})
+      for (size_t ng : {1, 3, 64, 65}) {
+        std::snprintf(label, sizeof(label), "gpoint truth ncol=%zu nlay=%zu ng=%zu", ncol, nlay, ng);
+        what = label;
+        const size_t count = ncol * 2 * (nlay + 1) * ng;
+        std::vector<double> truth(count, 1.5);
+        REQUIRE(ot::check_gpoint_truth(false, false, false, 0.1, truth.data(), count, err) == ECCKD_OK);
+        for (const double bad : {(double)NAN, (double)INFINITY}) {
+          for (const size_t at : {(size_t)0, count - 1}) {
+            truth[at] = bad;
+            REQUIRE(ot::check_gpoint_truth(false, false, false, 0.1, truth.data(), count, err) == ECCKD_PARAMETER_ERROR && !err.empty());
+            // (a removal reads no truth)
+            REQUIRE(ot::check_gpoint_truth(false, false, false, 0.0, truth.data(), count, err) == ECCKD_OK);
+            truth[at] = 1.5;
+          }
+        }
+        REQUIRE(ot::check_gpoint_truth(false, false, false, 0.0, nullptr, count, err) == ECCKD_OK);
+        REQUIRE(ot::check_gpoint_truth(false, false, false, 0.1, nullptr, count, err) == ECCKD_OK);
+        REQUIRE(ot::check_gpoint_truth(false, false, false, -1.0, truth.data(), count, err) == ECCKD_OK);
+        REQUIRE(ot::check_gpoint_truth(true, false, false, 0.1, truth.data(), count, err) == ECCKD_PARAMETER_ERROR);
+        REQUIRE(ot::check_gpoint_truth(true, false, false, 0.0, nullptr, count, err) == ECCKD_PARAMETER_ERROR);
+        REQUIRE(ot::check_gpoint_truth(false, true, false, 0.1, truth.data(), count, err) == ECCKD_PARAMETER_ERROR);
+        REQUIRE(ot::check_gpoint_truth(false, false, true, 0.1, truth.data(), count, err) == ECCKD_PARAMETER_ERROR);
+        REQUIRE(ot::check_gpoint_truth(false, false, false, (double)NAN, truth.data(), count, err) == ECCKD_PARAMETER_ERROR);
+        REQUIRE(ot::check_gpoint_truth(false, false, false, (double)INFINITY, truth.data(), count, err) == ECCKD_PARAMETER_ERROR);
+        REQUIRE(ot::gpoint_truth_active(0.1, truth.data()) && !ot::gpoint_truth_active(0.0, truth.data()) && !ot::gpoint_truth_active(0.1, nullptr));
+        std::vector<double> lw(nlay);
+        for (size_t l = 0; l < nlay; ++l) lw[l] = (1.0 + (double)l) / (0.5 * (double)nlay * ((double)nlay + 1.0));
+        double sum = 0.0;
+        for (size_t i = 0; i <= nlay; ++i) sum += ot::gpoint_level_weight(lw.data(), (int)nlay, (int)i);
+        REQUIRE(std::fabs(sum - 1.0) < 1e-14);
+        if (nlay == 1) REQUIRE(ot::gpoint_level_weight(lw.data(), 1, 0) == 0.5 && ot::gpoint_level_weight(lw.data(), 1, 1) == 0.5);
+        ++ncase;
+      }
+  return ncase;
+}
+
 int main() {
+  const int ngp = check_gpoint();
   const int nlds = check_lds();
   std::mt19937_64 rng(2024);
   int ncase = 0;
@@ -424,7 +471,8 @@ int main() {
   check_refusals();
   check_history();
   const int nray = check_rayleigh_active();
-  std::printf("check_opt_tables: %d LDS layouts, %d table cases, %d cases of the optimised Rayleigh row, the refusals and the history: no complaint\n",
-              nlds, ncase, nray);
+  std::printf("check_opt_tables: %d LDS layouts, %d table cases, %d cases of the optimised Rayleigh row, %d shapes of the per-g truth, "
+              "the refusals and the history: no complaint\n",
+              nlds, ncase, nray, ngp);
   return 0;
 }
