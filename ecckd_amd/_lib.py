@@ -183,6 +183,9 @@ SIGNATURES = {
                                       _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
     "ecckd_merge_spectrum_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, _c_double_p,
                                            C.c_int, C.c_void_p, C.c_size_t]),
+    "ecckd_merge_scenario_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int),
+                                           C.POINTER(C.c_size_t), _c_double_p, C.c_void_p, C.c_size_t]),
+    "ecckd_merge_scenario_geometry": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ecckd_gmap_erythemal_spectrum": (C.c_int, [C.c_void_p, _c_double_p]),
     "ecckd_lbl_gpoint_fluxes_lw": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_void_p, C.c_int, C.c_size_t, _c_double_p,
                                              _c_double_p, _c_double_p, _c_double_p]),

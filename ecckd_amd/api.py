@@ -1220,6 +1220,32 @@ def merge_spectrum(ctx, optical_depth, scaling_profile, merged=None):
     return merged
 
 
+def merge_scenario_geometry():
+    """The tile of the one-pass merge kernel (ecckd_merge_scenario_geometry; host only) -> dict."""
+    p, t = C.c_int(), C.c_int()
+    check(_lib.load_library().ecckd_merge_scenario_geometry(C.byref(p), C.byref(t)))
+    return {"points_per_thread": int(p.value), "threads_per_block": int(t.value)}
+
+
+def merge_scenario(ctx, optical_depths, scale, merged=None):
+    """The merged matrix of one scenario from all its gases in one pass (ecckd_merge_scenario_dev): optical_depths a list of
+    (nlay, nwav) arrays, float32 or float64 per gas, device tensors or numpy arrays (uploaded as they are); scale (ngas, nlay),
+    or (ngas,) for one factor per gas.  -> DOUBLE device tensor (nlay, nwav), `merged` itself when given (rows may be strided):
+    the bits of merge_spectrum gas after gas."""
+    torch = _torch()
+    ods = [od if torch.is_tensor(od) else torch.as_tensor(np.ascontiguousarray(od), device=ctx.device) for od in optical_depths]
+    sc = np.asarray(scale, dtype=np.float64)
+    ngas, nlay, nwav, ptrs, types, strides, sc = _scenario_args(ods, sc[None] if sc.ndim in (1, 2) else sc)
+    if merged is None:
+        merged = torch.empty((nlay, nwav), dtype=torch.float64, device=ctx.device)
+    elif tuple(merged.shape) != (nlay, nwav) or merged.dtype != torch.float64 or merged.stride(1) != 1:
+        raise ValueError("merged must be a (nlay, nwav) float64 device tensor with contiguous rows")
+    ctx.fence_from_torch()
+    check(ctx.lib.ecckd_merge_scenario_dev(ctx.handle, nlay, nwav, ngas, ptrs, types, strides, _hptr(sc), _dptr(merged),
+                                           merged.stride(0) if nlay > 1 else nwav))
+    return merged
+
+
 def lbl_band_fluxes_lw(ctx, temperature_hl, wavenumber, d_wavenumber, optical_depth, band_begin, band_end, boundary=False, nangle=0):
     """Line-by-line longwave fluxes of one column summed per band (planck_function + radiative_transfer_lw):
     device tensors wavenumber, d_wavenumber, optical_depth (nlay, nwav) -> (flux_dn, flux_up), each (nband, nlay+1);

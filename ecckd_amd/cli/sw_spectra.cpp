@@ -24,6 +24,8 @@
 // ckdmip_sw --ckd --rayleigh-scattering output (ckdmip.hpp: define_ckd_output) and the two optical depths run_ckd writes, so a
 // CKD model is compared with it variable by variable.  Without `gpoints` device memory is 3 (nlay+1) nwav floats.  Without
 // the key the file is byte for byte what it was.
+// scenarios=TABLE in place of output / scaling / conc / conc_input: many scenarios from one read of the spectra, one output file
+// per line of TABLE (spectra.hpp says how); the spectrum of rayleigh= is read once per column and never scaled.
 #include "spectra.hpp"
 
 int main(int argc, char** argv) { return spectra_main(argc, argv, true); }

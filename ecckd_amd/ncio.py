@@ -710,6 +710,8 @@ def write_lw_spectra(path, s, config_str="", history=None):
     w.write_attribute("long_name", "Layer optical depth", var="optical_depth")
     var("spectral_flux_dn_lw", ("column", "half_level", spec), "Downwelling longwave spectral flux", "W m-2")
     var("spectral_flux_up_lw", ("column", "half_level", spec), "Upwelling longwave spectral flux", "W m-2")
+    if s.get("scenario"):                                                                      # a line of a scenarios= table
+        w.write_attribute("scenario", s["scenario"])
     w.write_attribute("history", history or "")
     w.write_attribute("molecules", s["molecules"])
     w.write_attribute("config", config_str)
@@ -777,6 +779,8 @@ def write_sw_spectra(path, s, config_str="", history=None):
     if rayleigh:
         var("spectral_flux_dn_sw", ("column", "mu0", "half_level", spec),
             "Downwelling shortwave flux per g point" if have_g else "Downwelling shortwave spectral flux", "W m-2")
+    if s.get("scenario"):                                                                      # a line of a scenarios= table
+        w.write_attribute("scenario", s["scenario"])
     w.write_attribute("history", history or "")
     w.write_attribute("molecules", s["molecules"])
     w.write_attribute("config", config_str)

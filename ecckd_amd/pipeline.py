@@ -974,6 +974,89 @@ def _read_merged_spectrum(ctx, inputs, scaling, conc, icol):
     return first, molecules, merged, np.array(vmr)
 
 
+MAX_SCENARIO_INPUTS = 16
+
+
+def _check_scenarios(scenarios, inputs, read_files, **beside):
+    """The checks of the tools' scenarios= key (cli/spectra.hpp), before anything touches a device: `scenarios` a list of
+    dict(name=, output=, scaling=[...] or None, conc=[...] or None) with one scaling / conc per file of `inputs` (None or a
+    negative number: as the file holds the gas); `read_files`: {key: file} of whatever else the run reads; `beside`: the
+    arguments that come from the table.  -> the entries as (name, output, scaling, conc); ValueError otherwise."""
+    for key, value in beside.items():
+        if value is not None:
+            raise ValueError(f'"{key}" cannot be combined with "scenarios" (outputs and scalings come from the table)')
+    inputs = [str(p) for p in inputs]
+    if not inputs:
+        raise ValueError("Unable to read input file names in input")
+    if len(inputs) > MAX_SCENARIO_INPUTS:
+        raise ValueError(f'"scenarios": {len(inputs)} input files, {MAX_SCENARIO_INPUTS} at most')
+    scenarios = list(scenarios)
+    if not scenarios:
+        raise ValueError("Scenario table is empty")
+    table, outputs = [], set()
+    for line, entry in enumerate(scenarios, 1):
+        unknown = set(entry) - {"name", "output", "scaling", "conc"}
+        if "const" in unknown:
+            raise ValueError(f"scenario {line}: const=C is not a scaling of lw_spectra / sw_spectra (scaling or conc)")
+        if unknown or "name" not in entry:
+            raise ValueError(f"scenario {line}: unknown scaling spec {sorted(unknown)} (name, output, scaling, conc)")
+        row = [entry["name"], entry.get("output")]
+        for key in ("scaling", "conc"):
+            v = entry.get(key)
+            if v is not None:
+                v = [-1.0 if x is None else float(x) for x in v]
+                if len(v) != len(inputs):
+                    raise ValueError(f"scenario {line}: {len(v)} {key} value(s) for {len(inputs)} spectrum file(s) (one per file)")
+            row.append(v)
+        out = row[1]
+        if out is not None:
+            out = str(out)
+            if out in outputs:
+                raise ValueError(f'scenario {line}: duplicate output file "{out}"')
+            outputs.add(out)
+            for key, f in [("input", p) for p in inputs] + [(k, str(f)) for k, f in read_files.items() if f is not None]:
+                if _same_file(out, f):
+                    raise ValueError(f'scenario {line}: the output "{out}" is the {key} file of this run')
+        table.append(tuple(row))
+    return table
+
+
+def _same_file(a, b):
+    import os
+    return a == b or (os.path.exists(a) and os.path.exists(b) and os.path.realpath(a) == os.path.realpath(b))
+
+
+def _read_column_gases(ctx, inputs, icol):
+    """One column of every gas file, read once: -> (first spectrum dict, molecules, [(device optical depths as stored,
+    reference_surface_vmr, vmr_fl)])"""
+    first, molecules, gases = None, "", []
+    for ibg, path in enumerate(inputs):
+        s = ncio.read_spectrum(path, icol)
+        if ibg == 0:
+            first, molecules = s, s["molecule"] or ""
+        else:
+            molecules += " " + (s["molecule"] or "")
+        gases.append((_to_device(s["optical_depth"], ctx.device), s["reference_surface_vmr"], s["vmr_fl"]))
+    return first, molecules, gases
+
+
+def _merge_scenario(ctx, first, gases, scaling, conc, merged):
+    """A scenario of a column read by _read_column_gases: the scaling rules on the host, all gases merged in one pass into
+    `merged` (allocated when None; every scenario fills it again).  A single unscaled input stays as stored.
+    -> (device optical depths, vmr rows, merged)"""
+    profiles, vmr = [], []
+    for ibg, (od, ref, vmr_fl) in enumerate(gases):
+        sp, vrow = api.merge_scaling(first["pressure_hl"], -1.0 if scaling is None else scaling[ibg], -1.0 if conc is None else conc[ibg],
+                                     ref, vmr_fl)
+        profiles.append(sp)
+        vmr.append(vrow)
+    if len(gases) == 1 and np.all(profiles[0] == 1.0):
+        return gases[0][0], np.array(vmr), merged
+    merged = api.merge_scenario(ctx, [g[0] for g in gases], np.array(profiles), merged=merged)
+    ctx.synchronize()
+    return merged, np.array(vmr), merged
+
+
 def merge_spectra(ctx, inputs, output_path=None, scaling=None, conc=None, config_str="", history=None):
     """merge_spectra.cpp:27-170: the spectra of several gases merged column by column, as bin/merge_spectra does it.
     -> dict(pressure_hl, temperature_hl (ncol, nlay+1), wavenumber, optical_depth (ncol, nlay, nwav) as the file's FLOATs,
@@ -996,65 +1079,81 @@ def merge_spectra(ctx, inputs, output_path=None, scaling=None, conc=None, config
 
 
 def lw_spectra(ctx, inputs, output_path=None, scaling=None, conc=None, g_point=None, iprofile=None, config_str="", history=None,
-               nangle=0):
+               nangle=0, scenarios=None):
     """lw_spectra.cpp:31-275 as bin/lw_spectra does it: per column the merged spectrum, then either the spectral fluxes
     (ecckd_lbl_spectral_fluxes_lw) or, with g_point (one value per wavenumber, -1 = none), the fluxes per g point
     (ecckd_lbl_gpoint_fluxes_lw) and the optical depth averaged by transmission with the Planck weight at the pressure-weighted
     full-level temperature (ecckd_average_to_gpoints, reference_surface_vmr = 0).  nangle (the tool's key): 0 the two-stream
     fluxes, N > 0 those of N Gauss-Legendre zenith angles per hemisphere.  Arrays are returned in double as the library
-    gives them (the tool's file holds their FLOAT casts): dict of (nrec, ...) arrays; written to output_path when given."""
+    gives them (the tool's file holds their FLOAT casts): dict of (nrec, ...) arrays; written to output_path when given.
+    scenarios (the tool's scenarios= key): a list of dict(name=, output=, scaling=[...] or None, conc=[...] or None) in place of
+    output_path, scaling and conc: every gas file is read once per column, every scenario merged from that read in one pass
+    (api.merge_scenario) -> the list of those dicts, one per scenario in table order, each written where its `output` is set."""
     import torch
+    table = None
+    if scenarios is not None:
+        table = _check_scenarios(scenarios, inputs, {}, output_path=output_path, scaling=scaling, conc=conc)
     names = ("pressure_hl", "temperature_hl", "vmr_fl", "flux_dn_lw", "flux_up_lw", "optical_depth", "spectral_flux_dn_lw",
              "spectral_flux_up_lw")
-    out = {k: [] for k in names}
+    outs = [{k: [] for k in names} for _ in (table or [None])]
     have_g = g_point is not None
     ng = int(np.max(g_point)) + 1 if have_g else -1
     icol = iprofile if iprofile is not None else 0
-    ncol, gm, d_wn, d_dwn = 10000, None, None, None
+    ncol, gm, d_wn, d_dwn, shared = 10000, None, None, None, None
     while icol < ncol:
-        first, molecules, od, vmr = _read_merged_spectrum(ctx, inputs, scaling, conc, icol)
-        ncol = first["ncol"]
-        p, t = first["pressure_hl"], first["temperature_hl"]
-        if d_wn is None:
-            d_wn = torch.as_tensor(first["wavenumber_cm_1"], device=ctx.device)
-            d_dwn = torch.as_tensor(first["d_wavenumber_cm_1"], device=ctx.device)
-            if have_g:
-                gm = api.GPointMap(ctx, torch.as_tensor(np.ascontiguousarray(g_point, dtype=np.int32), device=ctx.device), ng, d_wn, d_dwn)
+        if table is not None:
+            first, molecules, gases = _read_column_gases(ctx, inputs, icol)        # the one read of this column
+        for k, out in enumerate(outs):
+            if table is None:
+                first, molecules, od, vmr = _read_merged_spectrum(ctx, inputs, scaling, conc, icol)
+            else:
+                od, vmr, shared = _merge_scenario(ctx, first, gases, table[k][2], table[k][3], shared)
+            ncol = first["ncol"]
+            p, t = first["pressure_hl"], first["temperature_hl"]
+            if d_wn is None:
+                d_wn = torch.as_tensor(first["wavenumber_cm_1"], device=ctx.device)
+                d_dwn = torch.as_tensor(first["d_wavenumber_cm_1"], device=ctx.device)
+                if have_g:
+                    gm = api.GPointMap(ctx, torch.as_tensor(np.ascontiguousarray(g_point, dtype=np.int32), device=ctx.device), ng, d_wn, d_dwn)
             out["wavenumber"], out["molecules"] = first["wavenumber_cm_1"], molecules.replace(",", " ")
-        out["pressure_hl"].append(p)
-        out["temperature_hl"].append(t)
-        out["vmr_fl"].append(vmr)
-        if not have_g:
-            sdn, sup, bdn, bup = api.lbl_spectral_fluxes_lw(ctx, t, d_wn, d_dwn, od, nangle=nangle)
-            out["optical_depth"].append(od.cpu().numpy().astype(np.float64))
-            out["spectral_flux_dn_lw"].append(sdn.cpu().numpy().astype(np.float64))
-            out["spectral_flux_up_lw"].append(sup.cpu().numpy().astype(np.float64))
-        else:
-            dn, up, bdn, bup = gm.lbl_fluxes_lw(t, od, nangle=nangle)
-            p_fl = 0.5 * (p[:-1] + p[1:])
-            t_fl = 0.5 * (t[:-1] * p[:-1] + t[1:] * p[1:]) / p_fl                              # :242-244
-            od_g, _, _ = gm.average_optical_depth(p, od, "transmission", 0.0, temperature_fl=t_fl)
-            out["optical_depth"].append(od_g)
-            out["spectral_flux_dn_lw"].append(dn)
-            out["spectral_flux_up_lw"].append(up)
-        out["flux_dn_lw"].append(bdn)
-        out["flux_up_lw"].append(bup)
+            out["pressure_hl"].append(p)
+            out["temperature_hl"].append(t)
+            out["vmr_fl"].append(vmr)
+            if not have_g:
+                sdn, sup, bdn, bup = api.lbl_spectral_fluxes_lw(ctx, t, d_wn, d_dwn, od, nangle=nangle)
+                out["optical_depth"].append(od.cpu().numpy().astype(np.float64))
+                out["spectral_flux_dn_lw"].append(sdn.cpu().numpy().astype(np.float64))
+                out["spectral_flux_up_lw"].append(sup.cpu().numpy().astype(np.float64))
+            else:
+                dn, up, bdn, bup = gm.lbl_fluxes_lw(t, od, nangle=nangle)
+                p_fl = 0.5 * (p[:-1] + p[1:])
+                t_fl = 0.5 * (t[:-1] * p[:-1] + t[1:] * p[1:]) / p_fl                              # :242-244
+                od_g, _, _ = gm.average_optical_depth(p, od, "transmission", 0.0, temperature_fl=t_fl)
+                out["optical_depth"].append(od_g)
+                out["spectral_flux_dn_lw"].append(dn)
+                out["spectral_flux_up_lw"].append(up)
+            out["flux_dn_lw"].append(bdn)
+            out["flux_up_lw"].append(bup)
         if iprofile is not None:
             break
         icol += 1
     if gm is not None:
         gm.close()
-    for k in names:
-        out[k] = np.stack(out[k])
-    out["ng"] = ng
-    out["nangle"] = int(nangle)
-    if output_path is not None:
-        ncio.write_lw_spectra(output_path, out, config_str=config_str, history=history)
-    return out
+    for k, out in enumerate(outs):
+        for name in names:
+            out[name] = np.stack(out[name])
+        out["ng"] = ng
+        out["nangle"] = int(nangle)
+        path = output_path
+        if table is not None:
+            out["scenario"], path = table[k][0], table[k][1]
+        if path is not None:
+            ncio.write_lw_spectra(path, out, config_str=config_str, history=history)
+    return outs if table is not None else outs[0]
 
 
 def sw_spectra(ctx, inputs, ssi, output_path=None, scaling=None, conc=None, g_point=None, iprofile=None, cos_sza=(0.5,),
-               surface_albedo=0.15, config_str="", history=None, rayleigh=None):
+               surface_albedo=0.15, config_str="", history=None, rayleigh=None, scenarios=None):
     """bin/sw_spectra as the tool does it: per column the merged spectrum, then either the spectral fluxes one angle at a time
     (ecckd_lbl_spectral_fluxes_sw) or, with g_point (one value per wavenumber, -1 = none), the fluxes per g point for all
     angles in one call (ecckd_lbl_gpoint_fluxes_sw) and the optical depth averaged by transmission with the `ssi` weight
@@ -1063,14 +1162,19 @@ def sw_spectra(ctx, inputs, ssi, output_path=None, scaling=None, conc=None, g_po
     transfer (ecckd_lbl_spectral_fluxes_sw_rayleigh / ecckd_lbl_gpoint_fluxes_sw_rayleigh), flux_dn_sw and spectral_flux_dn_sw
     (direct plus diffuse) are returned too and, with g_point, rayleigh_optical_depth: that spectrum averaged like optical_depth.
     Arrays are returned in double as the library gives them (the tool's file holds their FLOAT casts): dict of (nrec, ...)
-    arrays; written to output_path when given."""
+    arrays; written to output_path when given.
+    scenarios: as in lw_spectra - the gas files are read once per column, the spectrum of `rayleigh` too and never scaled ->
+    the list of the result dicts, one per scenario in table order."""
     import torch
+    table = None
+    if scenarios is not None:
+        table = _check_scenarios(scenarios, inputs, {"rayleigh": rayleigh}, output_path=output_path, scaling=scaling, conc=conc)
     names = ["pressure_hl", "temperature_hl", "vmr_fl", "flux_dn_direct_sw", "flux_up_sw", "optical_depth",
              "spectral_flux_dn_direct_sw", "spectral_flux_up_sw"]
     have_g = g_point is not None
     if rayleigh is not None:
         names += ["flux_dn_sw", "spectral_flux_dn_sw"] + (["rayleigh_optical_depth"] if have_g else [])
-    out = {k: [] for k in names}
+    outs = [{k: [] for k in names} for _ in (table or [None])]
     mu0 = np.atleast_1d(np.asarray(cos_sza, dtype=np.float64))
     if not (1 <= mu0.size <= 8) or np.any(~((mu0 > 0.0) & (mu0 <= 1.0))):
         raise EcckdError(PARAMETER_ERROR, "cos_sza must hold 1 to 8 numbers in (0, 1]")
@@ -1078,80 +1182,93 @@ def sw_spectra(ctx, inputs, ssi, output_path=None, scaling=None, conc=None, g_po
     if have_g and ng < 1:
         raise EcckdError(PARAMETER_ERROR, "g_point assigns no wavenumber to a g point")
     icol = iprofile if iprofile is not None else 0
-    ncol, gm, d_ssi, d_albedo = 10000, None, None, None
+    ncol, gm, d_ssi, d_albedo, shared, solar = 10000, None, None, None, None, None
     while icol < ncol:
-        first, molecules, od, vmr = _read_merged_spectrum(ctx, inputs, scaling, conc, icol)
-        ncol = first["ncol"]
-        p, t = first["pressure_hl"], first["temperature_hl"]
-        if d_ssi is None:
-            nwav = first["wavenumber_cm_1"].size
-            if np.size(ssi) != nwav or (have_g and np.size(g_point) != nwav):
-                raise EcckdError(PARAMETER_ERROR, "ssi / g_point do not have one value per wavenumber")
-            d_ssi = torch.as_tensor(np.ascontiguousarray(ssi, dtype=np.float64), device=ctx.device)
-            d_albedo = torch.full((nwav,), float(surface_albedo), dtype=torch.float64, device=ctx.device)
-            if have_g:
-                d_wn = torch.as_tensor(first["wavenumber_cm_1"], device=ctx.device)
-                d_dwn = torch.as_tensor(first["d_wavenumber_cm_1"], device=ctx.device)
-                gm = api.GPointMap(ctx, torch.as_tensor(np.ascontiguousarray(g_point, dtype=np.int32), device=ctx.device), ng, d_wn, d_dwn)
-                out["solar_irradiance"] = gm.sum_rows(d_ssi[None, :])[0]
-            out["wavenumber"], out["molecules"] = first["wavenumber_cm_1"], molecules.replace(",", " ")
+        if table is not None:
+            first, molecules, gases = _read_column_gases(ctx, inputs, icol)        # the one read of this column
         ray = None
-        if rayleigh is not None:                     # the spectrum that scatters: this column of it, unscaled, as it is stored
-            r = ncio.read_spectrum(rayleigh, icol)
-            if not np.array_equal(r["wavenumber_cm_1"], first["wavenumber_cm_1"]) or r["pressure_hl"].size != p.size or r["ncol"] != ncol:
-                raise EcckdError(PARAMETER_ERROR, "the Rayleigh spectrum does not have the merged spectrum's wavenumbers, levels and columns")
-            ray = _to_device(r["optical_depth"], ctx.device)
-        out["pressure_hl"].append(p)
-        if t is not None:
-            out["temperature_hl"].append(t)
-        out["vmr_fl"].append(vmr)
-        if not have_g:
-            sdn, sup, stot, bdn, bup, btot = [], [], [], [], [], []
-            for mu in mu0:                                                                     # one angle at a time, as the tool
-                if ray is not None:
-                    a, e, b, c, f, d = api.lbl_spectral_fluxes_sw_rayleigh(ctx, mu, d_ssi, od, ray, d_albedo)
-                    stot.append(e[0].cpu().numpy().astype(np.float64))
-                    btot.append(f[0])
-                else:
-                    a, b, c, d = api.lbl_spectral_fluxes_sw(ctx, mu, d_ssi, od, d_albedo)
-                sdn.append(a[0].cpu().numpy().astype(np.float64))
-                sup.append(b[0].cpu().numpy().astype(np.float64))
-                bdn.append(c[0])
-                bup.append(d[0])
-            bdn, bup = np.stack(bdn), np.stack(bup)
-            if ray is not None:
-                out["spectral_flux_dn_sw"].append(np.stack(stot))
-                out["flux_dn_sw"].append(np.stack(btot))
-            out["optical_depth"].append(od.cpu().numpy().astype(np.float64))
-            out["spectral_flux_dn_direct_sw"].append(np.stack(sdn))
-            out["spectral_flux_up_sw"].append(np.stack(sup))
-        else:
-            if ray is not None:
-                dn, tot, up, bdn, btot, bup = gm.lbl_fluxes_sw_rayleigh(mu0, d_ssi, od, ray, d_albedo)
-                out["spectral_flux_dn_sw"].append(tot)
-                out["flux_dn_sw"].append(btot)
-                out["rayleigh_optical_depth"].append(gm.average_optical_depth(p, ray, "transmission", 0.0, ssi=d_ssi)[0])
+        for k, out in enumerate(outs):
+            if table is None:
+                first, molecules, od, vmr = _read_merged_spectrum(ctx, inputs, scaling, conc, icol)
             else:
-                dn, up, bdn, bup = gm.lbl_fluxes_sw(mu0, d_ssi, od, d_albedo)
-            od_g, _, _ = gm.average_optical_depth(p, od, "transmission", 0.0, ssi=d_ssi)
-            out["optical_depth"].append(od_g)
-            out["spectral_flux_dn_direct_sw"].append(dn)
-            out["spectral_flux_up_sw"].append(up)
-        out["flux_dn_direct_sw"].append(bdn)
-        out["flux_up_sw"].append(bup)
+                od, vmr, shared = _merge_scenario(ctx, first, gases, table[k][2], table[k][3], shared)
+            ncol = first["ncol"]
+            p, t = first["pressure_hl"], first["temperature_hl"]
+            if d_ssi is None:
+                nwav = first["wavenumber_cm_1"].size
+                if np.size(ssi) != nwav or (have_g and np.size(g_point) != nwav):
+                    raise EcckdError(PARAMETER_ERROR, "ssi / g_point do not have one value per wavenumber")
+                d_ssi = torch.as_tensor(np.ascontiguousarray(ssi, dtype=np.float64), device=ctx.device)
+                d_albedo = torch.full((nwav,), float(surface_albedo), dtype=torch.float64, device=ctx.device)
+                if have_g:
+                    d_wn = torch.as_tensor(first["wavenumber_cm_1"], device=ctx.device)
+                    d_dwn = torch.as_tensor(first["d_wavenumber_cm_1"], device=ctx.device)
+                    gm = api.GPointMap(ctx, torch.as_tensor(np.ascontiguousarray(g_point, dtype=np.int32), device=ctx.device), ng, d_wn, d_dwn)
+                    solar = gm.sum_rows(d_ssi[None, :])[0]
+            if have_g:
+                out["solar_irradiance"] = solar
+            out["wavenumber"], out["molecules"] = first["wavenumber_cm_1"], molecules.replace(",", " ")
+            if rayleigh is not None and ray is None:     # the spectrum that scatters: this column of it, unscaled, as it is stored
+                r = ncio.read_spectrum(rayleigh, icol)
+                if not np.array_equal(r["wavenumber_cm_1"], first["wavenumber_cm_1"]) or r["pressure_hl"].size != p.size or r["ncol"] != ncol:
+                    raise EcckdError(PARAMETER_ERROR, "the Rayleigh spectrum does not have the merged spectrum's wavenumbers, levels and columns")
+                ray = _to_device(r["optical_depth"], ctx.device)
+            out["pressure_hl"].append(p)
+            if t is not None:
+                out["temperature_hl"].append(t)
+            out["vmr_fl"].append(vmr)
+            if not have_g:
+                sdn, sup, stot, bdn, bup, btot = [], [], [], [], [], []
+                for mu in mu0:                                                                     # one angle at a time, as the tool
+                    if ray is not None:
+                        a, e, b, c, f, d = api.lbl_spectral_fluxes_sw_rayleigh(ctx, mu, d_ssi, od, ray, d_albedo)
+                        stot.append(e[0].cpu().numpy().astype(np.float64))
+                        btot.append(f[0])
+                    else:
+                        a, b, c, d = api.lbl_spectral_fluxes_sw(ctx, mu, d_ssi, od, d_albedo)
+                    sdn.append(a[0].cpu().numpy().astype(np.float64))
+                    sup.append(b[0].cpu().numpy().astype(np.float64))
+                    bdn.append(c[0])
+                    bup.append(d[0])
+                bdn, bup = np.stack(bdn), np.stack(bup)
+                if ray is not None:
+                    out["spectral_flux_dn_sw"].append(np.stack(stot))
+                    out["flux_dn_sw"].append(np.stack(btot))
+                out["optical_depth"].append(od.cpu().numpy().astype(np.float64))
+                out["spectral_flux_dn_direct_sw"].append(np.stack(sdn))
+                out["spectral_flux_up_sw"].append(np.stack(sup))
+            else:
+                if ray is not None:
+                    dn, tot, up, bdn, btot, bup = gm.lbl_fluxes_sw_rayleigh(mu0, d_ssi, od, ray, d_albedo)
+                    out["spectral_flux_dn_sw"].append(tot)
+                    out["flux_dn_sw"].append(btot)
+                    out["rayleigh_optical_depth"].append(gm.average_optical_depth(p, ray, "transmission", 0.0, ssi=d_ssi)[0])
+                else:
+                    dn, up, bdn, bup = gm.lbl_fluxes_sw(mu0, d_ssi, od, d_albedo)
+                od_g, _, _ = gm.average_optical_depth(p, od, "transmission", 0.0, ssi=d_ssi)
+                out["optical_depth"].append(od_g)
+                out["spectral_flux_dn_direct_sw"].append(dn)
+                out["spectral_flux_up_sw"].append(up)
+            out["flux_dn_direct_sw"].append(bdn)
+            out["flux_up_sw"].append(bup)
         if iprofile is not None:
             break
         icol += 1
     if gm is not None:
         gm.close()
-    if not out["temperature_hl"]:
-        del out["temperature_hl"]
-        names.remove("temperature_hl")
-    for k in names:
-        out[k] = np.stack(out[k])
-    out["ng"], out["mu0"] = ng, mu0
-    if rayleigh is not None:
-        out["rayleigh"] = True                      # write_sw_spectra: the variables and the attribute the key adds
-    if output_path is not None:
-        ncio.write_sw_spectra(output_path, out, config_str=config_str, history=history)
-    return out
+    for k, out in enumerate(outs):
+        kept = list(names)
+        if not out["temperature_hl"]:
+            del out["temperature_hl"]
+            kept.remove("temperature_hl")
+        for name in kept:
+            out[name] = np.stack(out[name])
+        out["ng"], out["mu0"] = ng, mu0
+        if rayleigh is not None:
+            out["rayleigh"] = True                      # write_sw_spectra: the variables and the attribute the key adds
+        path = output_path
+        if table is not None:
+            out["scenario"], path = table[k][0], table[k][1]
+        if path is not None:
+            ncio.write_sw_spectra(path, out, config_str=config_str, history=history)
+    return outs if table is not None else outs[0]

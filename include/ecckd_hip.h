@@ -288,6 +288,20 @@ int ecckd_merge_scaling(int nlay, const double* h_pressure_hl, double scaling, d
 int ecckd_merge_spectrum_dev(ecckd_ctx* ctx, int nlay, size_t nwav, const void* d_od, int od_type, size_t od_stride,
                              const double* h_scaling_profile, int first, double* d_merged, size_t merged_stride);
 
+/* The merged matrix of one scenario from all its gases in ONE pass over their rows, which stay where they are for the next
+ * scenario: d_merged[l][j] = sum over g, in gas order, of d_od[g][l][j] * h_scale[g][l], the product rounded, then the sum
+ * (the first gas assigned) - bit for bit the matrix that ngas calls of ecckd_merge_spectrum_dev leave, the first overwriting,
+ * at 4 ngas + 8 bytes per point and layer for FLOAT gases instead of a read-modify-write of the DOUBLE matrix per gas.
+ * d_od[g] is [nlay][od_stride[g]], od_type[g] ECCKD_F32 or ECCKD_F64 per gas, 1 <= ngas <= 16, every stride >= nwav;
+ * h_scale is [ngas][nlay] on the host; d_merged is DOUBLE [nlay][merged_stride], merged_stride >= nwav, columns beyond nwav
+ * untouched, and overlaps no gas.  Rows may begin at any element: 16-byte accesses where a row allows them, single elements
+ * where it does not.  Anything else is ECCKD_PARAMETER_ERROR before any launch.  Synchronous, like ecckd_merge_spectrum_dev.
+ * ecckd_merge_scenario_geometry (host only): the kernel's tile - consecutive wavenumbers per thread, threads per block - for
+ * tests that place their sizes at its edges. */
+int ecckd_merge_scenario_dev(ecckd_ctx* ctx, int nlay, size_t nwav, int ngas, const void* const* d_od, const int* od_type,
+                             const size_t* od_stride, const double* h_scale, double* d_merged, size_t merged_stride);
+int ecckd_merge_scenario_geometry(int* points_per_thread, int* threads_per_block);
+
 /* ---- sub-bands and base split of find_g_points --------------------------------
  * find_g_points.cpp:786-870 (sub-bands of the optically thin part of a band) and :1311-1346
  * (wavenumber split of the base g point) both re-rank a contiguous range of ranks
