@@ -402,6 +402,85 @@ def _same_files(a, b, rtol=0.0, skip=()):
     assert ida == idb
 
 
+# The base split of a band's first g point, the one path on which the tool lends the library host memory of its own
+# (ecckd_band_options.base_wn_bound): in the second gas, so that with two processes the searched band comes back through a
+# part file.  band: the split band; a boundary inside a band re-ranks it, which the search allows only in a band that starts at
+# rank 0 (find_g_points.cpp:1317).
+BASE_SPLIT_CASES = {"base_split": dict(lines="  base_split 1 0.5\n", band=1, base_split=0.5, interior=[]),
+                    "base_wavenumber_boundary": dict(lines="  base_wavenumber_boundary 700\n", band=0, base_split=1.0, interior=[700.0])}
+
+
+def _start_first_band_at_zero(path):
+    """reorder_spectrum clamps the first band's lower bound to the first wavenumber and stores it as FLOAT, which on this grid
+    rounds ABOVE that wavenumber: a split by wavenumber then misses the first point ("Failed to account for all wavenumbers in
+    split", as in the reference).  The bound as it was asked for, 0, is below every wavenumber."""
+    f = netcdf_file(str(path), "a")
+    f.variables["wavenumber1_band"][0] = 0.0
+    f.close()
+
+
+@pytest.fixture(scope="module")
+def base_split_files(tmp_path_factory):
+    d = tmp_path_factory.mktemp("base_split")
+    _make_lw_files(d)
+    os.symlink(d / "h2o.nc", d / "co2_bg_is_h2o.nc")
+    for g in ("h2o", "co2"):
+        r = run_tool("reorder_spectrum", f"input={d}/{g}.nc", f"output={d}/order_{g}.nc", "wavenumber1=0 1300", "wavenumber2=1300 3260")
+        assert r.returncode == 0, r.stderr
+        _start_first_band_at_zero(d / f"order_{g}.nc")
+    return d
+
+
+@pytest.mark.parametrize("case", sorted(BASE_SPLIT_CASES))
+def test_find_g_points_base_split(ctx, base_split_files, tmp_path, case):
+    """(a) The default run, gas after gas and two processes write the same g-points file when a band's base g point is split -
+    by absorption (base_split) or by wavenumber (a base_wavenumber_boundary inside the band, whose re-ranked rank slice reaches
+    process 0 through a part file).  (b) The split band's g points are those of api.GasLW.find_g_band_ex on a gas prepared from
+    the same files, with the same options."""
+    import torch
+    from ecckd_amd import api, ncio, pipeline
+    d, out, c = base_split_files, tmp_path, BASE_SPLIT_CASES[case]
+    cfg = LW_CFG.format(d=d).replace("  min_g_points 2 1\n", "  min_g_points 2 1\n" + c["lines"])
+    assert c["lines"] in cfg
+    (out / "find_g.cfg").write_text(cfg)
+    r = run_tool("find_g_points", out / "find_g.cfg", f"output={out}/side.nc", cwd="/")
+    assert r.returncode == 0, r.stderr + r.stdout
+    r = run_tool("find_g_points", out / "find_g.cfg", f"output={out}/after.nc", "gases_side_by_side=1", cwd="/")
+    assert r.returncode == 0, r.stderr + r.stdout
+    _same_files(out / "side.nc", out / "after.nc", skip=("history", "config"))
+    _run_ranks(2, out / "find_g.cfg", f"output={out}/side.nc.two", "part_timeout=300", cwd="/")
+    _same_files(out / "side.nc", out / "side.nc.two", skip=("history", "config"))
+    assert not [f for f in os.listdir(out) if ".part" in f]
+
+    # (b) co2 as the tool prepares it: background h2o, the Planck matrix of the first gas's ordering
+    r = run_tool("find_g_points", out / "find_g.cfg", f"output={out}/seq.nc", "sequential_bands=1", cwd="/")
+    assert r.returncode == 0, r.stderr + r.stdout
+    dev = ctx.device
+    s, order = ncio.read_spectrum(d / "co2.nc", 0), ncio.read_order(d / "order_co2.nc")
+    h, order_h = ncio.read_spectrum(d / "h2o.nc", 0), ncio.read_order(d / "order_h2o.nc")
+    sp, _ = api.merge_scaling(h["pressure_hl"], -1.0, -1.0, h["reference_surface_vmr"], h["vmr_fl"])
+    bg = api.merge_spectrum(ctx, pipeline._to_device(h["optical_depth"], dev), sp, None)
+    planck = api.planck_hl_sorted(ctx, h["temperature_hl"], torch.as_tensor(h["wavenumber_cm_1"], device=dev),
+                                  torch.as_tensor(h["d_wavenumber_cm_1"], device=dev), torch.as_tensor(order_h["rank"], device=dev))
+    wn, rank = torch.as_tensor(s["wavenumber_cm_1"], device=dev), torch.as_tensor(order["rank"], device=dev)
+    gas = api.GasLW(ctx, s["pressure_hl"], s["temperature_hl"], wn, torch.as_tensor(s["d_wavenumber_cm_1"], device=dev), rank,
+                    pipeline._to_device(s["optical_depth"], dev), bg, "transmission", 0.02, 0.0, planck_hl_reuse=planck.data_ptr())
+    b = c["band"]
+    idx = np.nonzero(order["band_number"] == b)[0]
+    b1, b2 = float(order["wavenumber1_band"][b]), float(order["wavenumber2_band"][b])
+    exp = gas.find_g_band_ex(int(idx[0]), int(idx[-1]), 0.08, 0.02, 40, min_g_points=(2, 1)[b], max_g_points=256,
+                             base_split=c["base_split"], base_wn_bound=[b1, *c["interior"], b2 + 1.0], wavenumber=wn, rank=rank)
+    gas.close()
+    f = _nc(out / "seq.nc")
+    v = f.variables
+    in_band = v["co2_band_number"][:] == b
+    got = [v["co2_" + k][:][in_band] for k in ("rank1", "rank2", "error")]
+    f.close()
+    assert len(exp["rank1"]) > (2, 1)[b] + 1                                  # the base g point was split
+    assert np.array_equal(got[0], exp["rank1"]) and np.array_equal(got[1], exp["rank2"])
+    assert np.array_equal(got[2], np.asarray(exp["error"], dtype=np.float32))
+
+
 @pytest.mark.parametrize("is_sw", [False, True])
 def test_create_look_up_table(ctx, tmp_path, is_sw):
     from ecckd_amd import ncio, pipeline

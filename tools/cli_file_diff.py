@@ -14,7 +14,12 @@ with the same words, and compares every pair of output files:
   * every file, the NetCDF-4 ones (*.h5) included, through ecckd_amd.ncio.NcFile under the names of its classic twin: the
     dimensions' sizes, every variable's type and shape, its values and text attributes, the global text attributes.
 REFUSED are command lines that must fail: their exit code and stderr are compared.  Each tool run has a time limit of its
-own and the first failure ends the script.  Exit status 1 on any difference.  A tool, not a test: it needs a second checkout."""
+own and the first failure ends the script.  Exit status 1 on any difference.  A tool, not a test: it needs a second checkout.
+
+bin/find_g_points likewise (FIND_G_RUNS, FIND_G_REFUSED) on the inputs of its tool tests under find_g/: the 12 000-point
+longwave files of tests/test_cli_gpu.py in two bands, the 16 000-point shortwave files of test_find_g_points_sw and the cloud
+case of tests/test_cloud_gpu.py.  Of these runs stdout is compared too (same working directory, same words, ECCKD_LOG_TIMES
+unset); a run of two processes shares device 0, and the file of rank 0 and the stdout of both ranks are compared."""
 import argparse, os, pathlib, shutil, subprocess, sys, tempfile
 
 import numpy as np
@@ -57,6 +62,32 @@ REFUSED = [
     ("sw", "sw_spectra", (*SW_SPECTRA[:-1], "cos_solar_zenith_angle=1.5", "output=x.nc")),
 ]
 TIME_LIMIT = 120      # seconds per tool run; each takes a few at these sizes
+
+SW_FIND_G = ("averaging_method=total-transmission", "sw.cfg")
+# (directory, arguments, output file, number of processes)
+FIND_G_RUNS = [
+    ("find_g/lw", ("find_g.cfg", "output=plain.nc"), "plain.nc", 1),
+    ("find_g/lw", ("find_g.cfg", "output=seq.nc", "sequential_bands=1"), "seq.nc", 1),
+    ("find_g/lw", ("find_g.cfg", "output=after.nc", "gases_side_by_side=1"), "after.nc", 1),
+    ("find_g/lw", ("g_split.cfg", "output=g_split.nc"), "g_split.nc", 1),
+    ("find_g/lw", ("base_split.cfg", "output=base_split.nc"), "base_split.nc", 1),
+    ("find_g/lw", ("base_boundary.cfg", "output=base_boundary.nc"), "base_boundary.nc", 1),
+    ("find_g/lw", ("find_g.cfg", "output=target.nc", "target_g_points=12"), "target.nc", 1),
+    ("find_g/lw", ("find_g.cfg", "output=plain.h5"), "plain.h5", 1),
+    ("find_g/sw", (*SW_FIND_G, "output=gpoints_sw.nc"), "gpoints_sw.nc", 1),
+    ("find_g/cloud", ("g.cfg", "output=gpoints_cloud.nc"), "gpoints_cloud.nc", 1),
+    ("find_g/lw", ("find_g.cfg", "output=two.nc", "part_timeout=300"), "two.nc", 2),
+    ("find_g/lw", ("base_boundary.cfg", "output=base_boundary_two.nc", "part_timeout=300"), "base_boundary_two.nc", 2),
+    ("find_g/sw", (*SW_FIND_G, "output=two.nc", "part_timeout=300"), "two.nc", 2),
+]
+FIND_G_REFUSED = [
+    ("find_g/lw", ("find_g.cfg",)),                                                                  # no output
+    ("find_g/lw", ("no_tolerance.cfg", "output=x.nc")),
+    ("find_g/lw", ("find_g.cfg", "output=x.nc", "averaging_method=cubic")),
+    ("find_g/cloud", ("lw.cfg", "output=x.nc")),                                                     # cloud without ssi
+    ("find_g/lw", ("find_g.cfg", "output=x.nc", "target_g_points=12", "sequential_bands=1")),
+    ("find_g/lw", ("find_g.cfg", "output=x.nc", "heating_rate_tolerance=0.08 0.08 0.08")),          # three for two bands
+]
 
 
 def write_inputs(work):
@@ -128,6 +159,118 @@ def write_inputs(work):
         w.close()
 
 
+def write_find_g_inputs(work):
+    """find_g/lw, find_g/sw, find_g/cloud: what the find_g_points tool tests run on, with their orderings (this tree's
+    reorder_spectrum and reorder_cloud_spectrum, which are not under comparison)"""
+    from ecckd_amd import synthetic as syn
+    from test_pipeline_gpu import NLAY, _write_spectrum
+    from test_cli_gpu import LW_CFG, _make_lw_files
+    from test_cloud_gpu import CLOUD_CFG, GASES_CFG, _sw_case
+
+    def tool(d, name, *words):
+        subprocess.run([str(ROOT / "bin" / name), *words], cwd=d, check=True, capture_output=True, timeout=TIME_LIMIT)
+
+    lw, sw, cloud = work / "find_g" / "lw", work / "find_g" / "sw", work / "find_g" / "cloud"
+    for d in (lw, sw, cloud):
+        d.mkdir(parents=True)
+    _make_lw_files(lw)
+    os.symlink(lw / "h2o.nc", lw / "co2_bg_is_h2o.nc")
+    for g in ("h2o", "co2"):
+        tool(lw, "reorder_spectrum", f"input={g}.nc", f"output=order_{g}.nc", "wavenumber1=0 1300", "wavenumber2=1300 3260")
+        # for the base splits: the first band from 0, as asked for (tests/test_cli_gpu.py::_start_first_band_at_zero)
+        shutil.copy(lw / f"order_{g}.nc", lw / f"order0_{g}.nc")
+        f = netcdf_file(str(lw / f"order0_{g}.nc"), "a")
+        f.variables["wavenumber1_band"][0] = 0.0
+        f.close()
+    cfg = LW_CFG.format(d=".")
+    after_bg, from_zero = "  background_input \"co2.nc\"\n", cfg.replace("order_", "order0_")
+    (lw / "find_g.cfg").write_text(cfg)
+    (lw / "g_split.cfg").write_text(cfg.replace(after_bg, after_bg + "  g_split 0 0.7\n  subband_wavenumber_boundary 2000 2600\n"))
+    (lw / "base_split.cfg").write_text(from_zero.replace("  min_g_points 2 1\n", "  min_g_points 2 1\n  base_split 1 0.5\n"))
+    (lw / "base_boundary.cfg").write_text(from_zero.replace("  min_g_points 2 1\n", "  min_g_points 2 1\n  base_wavenumber_boundary 700\n"))
+    (lw / "no_tolerance.cfg").write_text(cfg.replace("heating_rate_tolerance 0.08\n", ""))
+    for name in ("g_split", "base_split", "base_boundary", "no_tolerance"):
+        assert (lw / f"{name}.cfg").read_text() not in (cfg, from_zero), name
+
+    nwav, lo, hi = 16000, 250.0, 50000.0                # the shortwave files of test_find_g_points_sw
+    p = syn.pressure_grid(NLAY)
+    wn, dwn = syn.wavenumber_grid(nwav, lo, hi)
+    w = netcdf_file(str(sw / "ssi.nc"), "w", version=2)
+    w.createDimension("wavenumber", nwav)
+    w.createVariable("solar_spectral_irradiance", "d", ("wavenumber",))[:] = syn.solar_spectral_irradiance(wn, dwn)
+    w.close()
+    for g, (seed, scale, vmr) in {"h2o": (61, 5.0, 5e-3), "o3": (67, 1.5, 1e-6)}.items():
+        od = syn.optical_depth(np, p, wn, syn.SEED_BASE + seed, nlines=40, column_scale=scale, dtype="float32", lo=lo, hi=hi)
+        _write_spectrum(sw / f"{g}.nc", g, p, syn.temperature_profile(p), wn, od, vmr)
+        tool(sw, "reorder_spectrum", f"input={g}.nc", f"output=order_{g}.nc", "ssi=ssi.nc", "wavenumber1=250 10000", "wavenumber2=10000 50000")
+    (sw / "sw.cfg").write_text("ssi ssi.nc\naveraging_method transmission\nheating_rate_tolerance 0.03\nmax_iterations 40\ngases h2o o3\n"
+                               "\\begin h2o\n input h2o.nc\n reordering_input order_h2o.nc\n background_input o3.nc\n\\end h2o\n"
+                               "\\begin o3\n input o3.nc\n reordering_input order_o3.nc\n background_input h2o.nc\n max_scaling 3.0\n\\end o3\n")
+
+    _sw_case(cloud)                                     # the inputs of test_find_g_points_with_cloud
+    b1, b2 = "250 2500 10000 25000", "2500 10000 25000 50000"
+    for g in ("h2o", "o3"):
+        tool(cloud, "reorder_spectrum", f"input=present_{g}.nc", f"output=order_{g}.nc", "ssi=ssi.nc", f"wavenumber1={b1}", f"wavenumber2={b2}")
+    tool(cloud, "reorder_cloud_spectrum", "input=mie.nc", "isize=1", "wavenumber_input=ssi.nc", "output=order_cloud.nc", f"wavenumber1={b1}",
+         f"wavenumber2={b2}")
+    with_cloud = CLOUD_CFG.format(order="order_cloud.nc", rng=0.1)
+    (cloud / "g.cfg").write_text(GASES_CFG.format(ext="nc") + with_cloud)
+    (cloud / "lw.cfg").write_text(GASES_CFG.format(ext="nc").replace("ssi ssi.nc\n", "") + with_cloud)
+
+
+def run_find_g(tree, d, words, world):
+    """find_g_points of `tree` as `world` processes on device 0 -> [(exit code, stdout, stderr) per rank]"""
+    env = {k: v for k, v in os.environ.items() if k != "ECCKD_LOG_TIMES"}
+    if world > 1:
+        env.update(WORLD_SIZE=str(world), ECCKD_DEVICE="0")
+    procs = [subprocess.Popen([str(tree / "bin" / "find_g_points"), *words], cwd=d, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)) if world > 1 else env,
+                              stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for r in range(world)]
+    outs = []
+    for p in procs:
+        try:
+            out, err = p.communicate(timeout=TIME_LIMIT)
+        except subprocess.TimeoutExpired:
+            for q in procs:
+                q.kill()
+            raise
+        outs.append((p.returncode, out, err))
+    return outs
+
+
+def compare_find_g(work, trees):
+    """-> number of differences, or None when a run that must succeed did not (nothing more is run then)"""
+    bad = 0
+    for d, words, output, world in FIND_G_RUNS:
+        got = {}
+        for tag, tree in trees.items():
+            got[tag] = run_find_g(tree, work / d, words, world)
+            if any(rc != 0 for rc, _, _ in got[tag]):
+                print(f"{tag} find_g_points {' '.join(words)} ({world} process(es)): exit {[rc for rc, _, _ in got[tag]]}\n" + "\n".join(e for _, _, e in got[tag]))
+                return None
+            (work / d / tag).mkdir(exist_ok=True)
+            shutil.move(str(work / d / output), str(work / d / tag / output))
+        diffs = compare(work / d / "parent" / output, work / d / "branch" / output, work / d / "parent" / (output[:-3] + ".nc"))
+        diffs += [f"stdout of rank {r} differs" for r in range(world) if got["parent"][r][1] != got["branch"][r][1]]
+        if [f for f in os.listdir(work / d) if ".part" in f]:
+            diffs.append("part files left behind")
+        print(f"find_g_points {' '.join(words)} ({world} process(es)) -> {output} and stdout: {'identical' if not diffs else 'DIFFERS'}")
+        for line in diffs:
+            print("    " + line[:300])
+        bad += bool(diffs)
+    for d, words in FIND_G_REFUSED:
+        got = {tag: run_find_g(tree, work / d, words, 1)[0] for tag, tree in trees.items()}
+        for tag, (rc, _, err) in got.items():
+            if rc < 0:                                  # killed by a signal: nothing more runs on this device
+                print(f"{tag} find_g_points {' '.join(words)}: exit {rc}\n{err}")
+                return None
+        same = got["parent"][0] == got["branch"][0] > 0 and got["parent"][2] == got["branch"][2] and not (work / d / "x.nc").exists()
+        print(f"find_g_points {' '.join(words)} (refused, exit {got['parent'][0]}: {got['parent'][2].strip()[:80]}): {'identical' if same else 'DIFFERS'}")
+        if not same:
+            print(f"    parent {got['parent']}\n    branch {got['branch']}")
+        bad += not same
+    return bad
+
+
 def global_att(name, value):
     """A global attribute without what names the executable: None for `history`, `config` without its `0=<argv[0]>; `"""
     if name == "history" or value is None:
@@ -191,6 +334,7 @@ def main():
     work = (args.work or pathlib.Path(tmp.name)).resolve()
     work.mkdir(parents=True, exist_ok=True)
     write_inputs(work)
+    write_find_g_inputs(work)
     bad = 0
     for d, tool, words, outputs in RUNS:
         for tag, tree in trees.items():
@@ -221,6 +365,10 @@ def main():
         if not same:
             print(f"    parent {got['parent']}\n    branch {got['branch']}")
         bad += not same
+    more = compare_find_g(work, trees)
+    if more is None:
+        return 1
+    bad += more
     print(f"{bad} difference(s)")
     return 1 if bad else 0
 
