@@ -175,6 +175,15 @@ SIGNATURES = {
                                                     _c_int64_p, _c_double_p]),
     "ecckd_index_geometry": (C.c_int, [C.POINTER(C.c_int)] * 6),
     "ecckd_run_ckd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "ecckd_gas_optics_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "ecckd_gas_optics_destroy": (C.c_int, [C.c_void_p]),
+    "ecckd_gas_optics_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ecckd_gas_optics_geometry": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ecckd_gas_optics_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(C.c_int), _c_double_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p),
+                                       C.c_void_p]),
+    "ecckd_gas_optics_planck_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
+    "ecckd_gas_optics_incoming": (C.c_int, [C.c_void_p, C.c_double, _c_double_p]),
     "ecckd_scale_lut": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _c_double_p, _c_double_p, _c_double_p,
                                   C.POINTER(C.c_int), C.c_double, _c_double_p, _c_double_p, C.POINTER(_c_double_p)]),
     "ecckd_gmap_sum_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_size_t, _c_double_p]),

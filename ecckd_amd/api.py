@@ -1179,6 +1179,120 @@ def run_ckd(ctx, model, scene, gases=None, scalings=None, per_gas=True):
     return out
 
 
+class GasOptics:
+    """ecckd_gas_optics_*: a CKD model resident on the device, applied to columns that already sit there
+    (CkdModel::calc_optical_depth, ckd_model.cpp:925-1102; calc_planck_function, :1107-1145).  `model` is the dict of
+    Optimizer / run_ckd; min / max tables and `active` are ignored.  Inputs are float64 torch tensors on the context's
+    device, contiguous, used in place (anything else is refused, never copied behind the caller's back); numpy arrays are
+    uploaded as a convenience.  Outputs are torch tensors on the device."""
+
+    def __init__(self, ctx, model):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        keep = []
+        m = _opt_model(model, keep)
+        h = C.c_void_p()
+        check(self.lib.ecckd_gas_optics_create(ctx.handle, C.byref(m), C.byref(h)))
+        self.handle = h
+        ng, ngas, is_sw, nent = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        check(self.lib.ecckd_gas_optics_info(h, C.byref(ng), C.byref(ngas), C.byref(is_sw), C.byref(nent)))
+        self.ng, self.ngas, self.is_sw, self.entries_per_cell = ng.value, ngas.value, bool(is_sw.value), nent.value
+        self.names = [g.get("name", str(i)) for i, g in enumerate(model["gases"])]
+        ctx._children.add(self)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.ecckd_gas_optics_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def geometry(self):
+        """The launch tile -> dict(cells_per_block, threads) (ecckd_gas_optics_geometry)."""
+        cells, threads = C.c_int(), C.c_int()
+        check(self.lib.ecckd_gas_optics_geometry(self.handle, C.byref(cells), C.byref(threads)))
+        return dict(cells_per_block=cells.value, threads=threads.value)
+
+    def _input(self, a, shape, what):
+        torch = _torch()
+        if a is None:
+            return None
+        if not torch.is_tensor(a):
+            a = torch.as_tensor(_f64c(a), device=self.ctx.device)
+        if a.dtype != torch.float64 or a.device != self.ctx.device or not a.is_contiguous() or tuple(a.shape) != tuple(shape):
+            raise EcckdError(_lib.PARAMETER_ERROR, f"{what} must be a contiguous float64 tensor of shape {tuple(shape)} on {self.ctx.device}")
+        return a
+
+    @staticmethod
+    def _out_type(dtype):
+        torch = _torch()
+        if dtype not in (torch.float64, torch.float32):
+            raise EcckdError(_lib.PARAMETER_ERROR, f"dtype must be torch.float64 or torch.float32, got {dtype}")
+        return _lib.F64 if dtype == torch.float64 else _lib.F32
+
+    def optical_depth(self, pressure_hl, temperature_hl, vmr_fl=None, temperature_fl=None, gases=None, scalings=None,
+                      per_gas=False, keep_negative=False, dtype=None):
+        """-> dict of device tensors [ncol, nlay, ng] keyed by run_ckd's variable names: "optical_depth", with per_gas
+        "<gas>_optical_depth" of every gas in the list (all out of the one pass), on a shortwave model
+        "rayleigh_optical_depth".  `gases` restricts the gas list (indices or names) and `scalings` = {gas index: factor}
+        multiplies mole fractions, both as in run_ckd.  keep_negative: no clamp at zero."""
+        torch = _torch()
+        dtype = torch.float64 if dtype is None else dtype
+        out_type = self._out_type(dtype)
+        ncol, nhl = pressure_hl.shape
+        nlay = nhl - 1
+        p = self._input(pressure_hl, (ncol, nhl), "pressure_hl")
+        t = self._input(temperature_hl, (ncol, nhl), "temperature_hl")
+        vmr = self._input(vmr_fl, (ncol, self.ngas, nlay), "vmr_fl")
+        tfl = self._input(temperature_fl, (ncol, nlay), "temperature_fl")
+        present = np.ones(self.ngas, dtype=np.int32)
+        if gases is not None:
+            present = np.array([1 if (i in gases or self.names[i] in gases) else 0 for i in range(self.ngas)], dtype=np.int32)
+        scaling = np.ones(self.ngas)
+        for i, f in (scalings or {}).items():
+            scaling[i] = f
+        new = lambda: torch.empty((ncol, nlay, self.ng), dtype=dtype, device=self.ctx.device)
+        out = {"optical_depth": new()}
+        ptrs = (C.c_void_p * self.ngas)()
+        if per_gas:
+            for i in range(self.ngas):
+                if present[i]:
+                    out[self.names[i] + "_optical_depth"] = new()
+                    ptrs[i] = out[self.names[i] + "_optical_depth"].data_ptr()
+        if self.is_sw:
+            out["rayleigh_optical_depth"] = new()
+        self.ctx.fence_from_torch()
+        check(self.lib.ecckd_gas_optics_dev(
+            self.handle, ncol, nlay, _dptr(p), _dptr(t), _dptr(tfl) if tfl is not None else None,
+            _dptr(vmr) if vmr is not None else None, _hptr(present, C.c_int), _hptr(scaling), int(keep_negative), out_type,
+            _dptr(out["optical_depth"]), ptrs if per_gas else None,
+            _dptr(out["rayleigh_optical_depth"]) if self.is_sw else None))
+        self.ctx.synchronize()
+        return out
+
+    def planck(self, temperature, dtype=None):
+        """Planck function per g point at `temperature` (any shape) -> device tensor of shape temperature.shape + (ng,)."""
+        torch = _torch()
+        dtype = torch.float64 if dtype is None else dtype
+        out_type = self._out_type(dtype)
+        t = self._input(temperature, tuple(temperature.shape), "temperature")
+        out = torch.empty(tuple(t.shape) + (self.ng,), dtype=dtype, device=self.ctx.device)
+        self.ctx.fence_from_torch()
+        check(self.lib.ecckd_gas_optics_planck_dev(self.handle, t.numel(), _dptr(t), out_type, _dptr(out)))
+        self.ctx.synchronize()
+        return out
+
+    def incoming(self, tsi):
+        """incoming_sw[ng] = tsi / sum(ssi) * ssi (numpy; shortwave models)."""
+        out = np.empty(self.ng)
+        check(self.lib.ecckd_gas_optics_incoming(self.handle, float(tsi), _hptr(out)))
+        return out
+
+
 def derive_d_wavenumber(ctx, wavenumber):
     """read_spectrum.cpp:55-65 for a grid stored without d_wavenumber (device tensor in, device tensor out)."""
     import torch

@@ -7,9 +7,83 @@
 // Keys (:50-90): ckd_model, input, output, gases (restricts the gas list), co2_scaling, ch4_scaling, n2o_scaling,
 // cfc11_scaling, cfc12_scaling, write_od_only, tsi, prepend_path, append_path, log_level.
 // All of the arithmetic is ecckd_run_ckd (include/ecckd_hip.h) on the GPU.
+// device_gas_optics=1 (not in the reference): the same file from the resident gas-optics handle - the total and every gas's
+// optical depth out of one pass of ecckd_gas_optics_dev, the Planck function or the incoming flux from the handle, the fluxes
+// from ecckd_rt_lw_gpoints(nangle = 0) / ecckd_rt_sw_gpoints(albedo 0).
 #include "ckd_file.hpp"
 
+#include <memory>
+
 using namespace tool;
+
+namespace {
+
+// a device block of the context's, freed with the scope
+struct DevBlock {
+  ecckd_ctx* ctx;
+  void* p = nullptr;
+  DevBlock(ecckd_ctx* c, size_t bytes, const double* h = nullptr) : ctx(c) {
+    ck(ecckd_dev_alloc(ctx, bytes, &p));
+    if (h) ck(ecckd_h2d(ctx, p, h, bytes));
+  }
+  ~DevBlock() { ecckd_dev_free(ctx, p); }
+  DevBlock(const DevBlock&) = delete;
+  DevBlock& operator=(const DevBlock&) = delete;
+  void to_host(std::vector<double>& h) const { ck(ecckd_d2h(ctx, h.data(), p, h.size() * sizeof(double))); }
+};
+
+// What ecckd_run_ckd returns, from the gas-optics handle: od, ray (shortwave), planck ([ncol][nhl][ng]; shortwave: row 0 of
+// every column the incoming flux), flux ([ncol][2][nhl][ng]), and with want_gases every present gas's optical depth.
+void device_gas_optics_pass(ecckd_ctx* ctx, const ecckd_opt_model& m, const ecckd_opt_scene& sc, bool want_gases, std::vector<double>& od,
+                            std::vector<double>& ray, std::vector<double>& planck, std::vector<double>& flux,
+                            std::vector<std::vector<double>>& od_gases) {
+  const bool is_sw = m.solar_irradiance != nullptr;
+  const size_t ncol = sc.ncol, nlay = sc.nlay, nhl = nlay + 1, ng = m.ng, ncell = ncol * nlay * ng, nlev = ncol * nhl * ng;
+  ecckd_gas_optics* h = nullptr;
+  ck(ecckd_gas_optics_create(ctx, &m, &h));
+  struct Close { ecckd_gas_optics* h; ~Close() { ecckd_gas_optics_destroy(h); } } close{h};
+  const DevBlock d_p(ctx, ncol * nhl * sizeof(double), sc.pressure_hl), d_t(ctx, ncol * nhl * sizeof(double), sc.temperature_hl);
+  const DevBlock d_vmr(ctx, ncol * m.ngas * nlay * sizeof(double), sc.vmr_fl), d_od(ctx, ncell * sizeof(double));
+  std::vector<std::unique_ptr<DevBlock>> d_gas(m.ngas);
+  std::vector<void*> gas_ptr(m.ngas, nullptr);
+  if (want_gases)
+    for (int i = 0; i < m.ngas; ++i)
+      if (sc.gas_present[i]) {
+        d_gas[i].reset(new DevBlock(ctx, ncell * sizeof(double)));
+        gas_ptr[i] = d_gas[i]->p;
+      }
+  std::unique_ptr<DevBlock> d_ray(is_sw ? new DevBlock(ctx, ncell * sizeof(double)) : nullptr);
+  ck(ecckd_gas_optics_dev(h, sc.ncol, sc.nlay, (const double*)d_p.p, (const double*)d_t.p, nullptr, (const double*)d_vmr.p, sc.gas_present,
+                          nullptr, 0, ECCKD_F64, d_od.p, want_gases ? gas_ptr.data() : nullptr, is_sw ? d_ray->p : nullptr));
+  d_od.to_host(od);
+  od_gases.assign(m.ngas, std::vector<double>());
+  for (int i = 0; i < m.ngas; ++i)
+    if (d_gas[i]) { od_gases[i].resize(ncell); d_gas[i]->to_host(od_gases[i]); }
+  std::vector<double> dn(nlev), up(nlev, 0.0);
+  if (!is_sw) {
+    const DevBlock d_planck(ctx, nlev * sizeof(double));
+    ck(ecckd_gas_optics_planck_dev(h, ncol * nhl, (const double*)d_t.p, ECCKD_F64, d_planck.p));
+    d_planck.to_host(planck);
+    ck(ecckd_rt_lw_gpoints(ctx, 0, sc.ncol, sc.nlay, m.ng, planck.data(), od.data(), dn.data(), up.data()));
+  } else {
+    d_ray->to_host(ray);
+    std::vector<double> incoming(ng), incoming_all(ncol * ng), od_total(ncell), up_unused(nlev);
+    ck(ecckd_gas_optics_incoming(h, sc.tsi, incoming.data()));
+    std::fill(planck.begin(), planck.end(), 0.0);
+    for (size_t c = 0; c < ncol; ++c) {
+      std::copy(incoming.begin(), incoming.end(), incoming_all.begin() + c * ng);
+      std::copy(incoming.begin(), incoming.end(), planck.begin() + c * nhl * ng);
+    }
+    for (size_t e = 0; e < ncell; ++e) od_total[e] = od[e] + ray[e];   // Rayleigh joins after the clamp (run_ckd.cpp:361)
+    ck(ecckd_rt_sw_gpoints(ctx, sc.ncol, sc.nlay, m.ng, sc.mu0[0], 0.0, incoming_all.data(), od_total.data(), dn.data(), up_unused.data()));
+  }
+  for (size_t c = 0; c < ncol; ++c) {
+    std::copy(dn.begin() + c * nhl * ng, dn.begin() + (c + 1) * nhl * ng, flux.begin() + (c * 2) * nhl * ng);
+    std::copy(up.begin() + c * nhl * ng, up.begin() + (c + 1) * nhl * ng, flux.begin() + (c * 2 + 1) * nhl * ng);
+  }
+}
+
+}  // namespace
 
 int main(int argc, char** argv) {
   return run(argc, argv, [&](Config& config) -> int {
@@ -27,6 +101,8 @@ int main(int argc, char** argv) {
     config.read(write_od_only, "write_od_only");
     double tsi = 1361.0;
     config.read(tsi, "tsi");
+    bool device_gas_optics = false;
+    config.read(device_gas_optics, "device_gas_optics");
 
     CkdFile model = read_ckd(paths.find(ckd_file));
     const std::string dom = model.is_sw ? "sw" : "lw";
@@ -79,7 +155,9 @@ int main(int argc, char** argv) {
 
     const size_t ncell = (size_t)ncol * nlay * ng, nlev = (size_t)ncol * nhl * ng;
     std::vector<double> od(ncell), ray(model.is_sw ? ncell : 0), planck(nlev), flux(2 * nlev);
-    ck(ecckd_run_ckd(dev.ctx(), &mv.m, &sc, od.data(), model.is_sw ? ray.data() : nullptr, planck.data(), flux.data()));
+    std::vector<std::vector<double>> od_gases;   // device_gas_optics: every gas from the one pass
+    if (device_gas_optics) device_gas_optics_pass(dev.ctx(), mv.m, sc, !write_od_only, od, ray, planck, flux, od_gases);
+    else ck(ecckd_run_ckd(dev.ctx(), &mv.m, &sc, od.data(), model.is_sw ? ray.data() : nullptr, planck.data(), flux.data()));
 
     LOG("Writing %s\n", output_file.c_str());
     NcOut file(output_file);
@@ -125,6 +203,7 @@ int main(int argc, char** argv) {
       std::vector<double> od_gas(ncell);
       for (int i = 0; i < ngas; ++i) {
         if (!present[i]) { std::fill(od_gas.begin(), od_gas.end(), 0.0); }
+        else if (device_gas_optics) { od_gas = od_gases[i]; }
         else {
           std::vector<int> one(ngas, 0);
           one[i] = 1;

@@ -107,31 +107,48 @@ AxisPos axis_pos(double index0, int n) {
 
 }  // namespace
 
-int check_arguments(const ecckd_opt_model* m, int nscene, const ecckd_opt_scene* scenes, const ecckd_opt_config* cfg, std::string& err,
-                    bool rayleigh_active) {
-  if (!(m && scenes && cfg && nscene > 0)) return refuse(err, "ecckd_opt_create: NULL/empty argument");
+int check_model_shape(const ecckd_opt_model* m, const char* who, std::string& err) {
   if (!(m->ng > 0 && m->ng <= 1024 && m->nt >= 2 && m->np >= 2 && m->ngas > 0 && m->gases && m->log_pressure && m->temperature &&
         m->iband_per_g))
-    return refuse(err, "ecckd_opt_create: bad model dimensions (ng=%d nt=%d np=%d ngas=%d)", m->ng, m->nt, m->np, m->ngas);
+    return refuse(err, "%s: bad model dimensions (ng=%d nt=%d np=%d ngas=%d)", who, m->ng, m->nt, m->np, m->ngas);
   const bool do_sw = m->solar_irradiance != nullptr;
   if (!(do_sw || (m->ntp >= 2 && m->temperature_planck && m->planck_function)))
-    return refuse(err, "ecckd_opt_create: Planck look-up table missing");
+    return refuse(err, "%s: Planck look-up table missing", who);
   if (m->logarithmic_interpolation)
-    return refuse(err, "ecckd_opt_create: logarithmic LUT interpolation is not supported (ckd_model.h:359 default is linear)");
-  if (rayleigh_active && !has_rayleigh(m))
-    return refuse(err, "ecckd_opt_create_ex: ECCKD_OPT_RAYLEIGH_ACTIVE needs a shortwave model with rayleigh_molar_scattering");
-  size_t nx = rayleigh_active ? m->ng : 0, nk = has_rayleigh(m) ? m->ng : 0;
+    return refuse(err, "%s: logarithmic LUT interpolation is not supported (ckd_model.h:359 default is linear)", who);
+  return ECCKD_OK;
+}
+
+int check_model_gases(const ecckd_opt_model* m, const char* who, std::string& err, size_t& ncoef) {
+  ncoef = 0;
   for (int i : gas_order(m)) {
     const ecckd_opt_gas& ug = m->gases[i];
     if (!(ug.conc_dependence >= 0 && ug.conc_dependence <= 3) || !ug.molar_abs ||
         (ug.conc_dependence == 2 && (ug.nconc < 2 || !ug.vmr)))
-      return refuse(err, "ecckd_opt_create: gas %d is ill-defined", i);
-    const size_t n = (size_t)nconc_of(ug) * m->nt * m->np * m->ng;
-    nk += n;
-    if (ug.is_active) nx += n;
+      return refuse(err, "%s: gas %d is ill-defined", who, i);
+    ncoef += (size_t)nconc_of(ug) * m->nt * m->np * m->ng;
   }
-  if (!(nx > 0)) return refuse(err, "ecckd_opt_create: no active gas to optimise");
-  if (!(nk < (size_t)0x7fffffff)) return refuse(err, "ecckd_opt_create: coefficient vector too long for int32 indexing");
+  return ECCKD_OK;
+}
+
+int check_arguments(const ecckd_opt_model* m, int nscene, const ecckd_opt_scene* scenes, const ecckd_opt_config* cfg, std::string& err,
+                    bool rayleigh_active) {
+  const char* who = "ecckd_opt_create";
+  if (!(m && scenes && cfg && nscene > 0)) return refuse(err, "%s: NULL/empty argument", who);
+  int rc = check_model_shape(m, who, err);
+  if (rc != ECCKD_OK) return rc;
+  const bool do_sw = m->solar_irradiance != nullptr;
+  if (rayleigh_active && !has_rayleigh(m))
+    return refuse(err, "ecckd_opt_create_ex: ECCKD_OPT_RAYLEIGH_ACTIVE needs a shortwave model with rayleigh_molar_scattering");
+  size_t ncoef = 0;
+  rc = check_model_gases(m, who, err, ncoef);
+  if (rc != ECCKD_OK) return rc;
+  size_t nx = rayleigh_active ? m->ng : 0;
+  const size_t nk = ncoef + (has_rayleigh(m) ? m->ng : 0);
+  for (int i = 0; i < m->ngas; ++i)
+    if (m->gases[i].is_active) nx += (size_t)nconc_of(m->gases[i]) * m->nt * m->np * m->ng;
+  if (!(nx > 0)) return refuse(err, "%s: no active gas to optimise", who);
+  if (!(nk < (size_t)0x7fffffff)) return refuse(err, "%s: coefficient vector too long for int32 indexing", who);
   const int nlay = scenes[0].nlay, nband = count_bands(m);
   if (nlay < 1 || nlay > 128) return refuse(err, "ecckd_opt_create: nlay = %d outside the supported range 1..128", nlay);
   for (int s = 0; s < nscene; ++s)

@@ -86,6 +86,11 @@ struct Schedule { int waves = 4, run = 64; bool plain_order = false; };
 // ECCKD_PARAMETER_ERROR with the refusal in `err`; the others assume arguments that passed it.
 int check_arguments(const ecckd_opt_model* m, int nscene, const ecckd_opt_scene* scenes, const ecckd_opt_config* cfg, std::string& err,
                     bool rayleigh_active = false);
+// The model part of check_arguments, shared with the gas-optics handle (gas_optics_tables.cpp); `who` opens the refusal.
+// check_model_shape: dimensions, the Planck look-up table of a longwave model, linear interpolation.  check_model_gases: every
+// gas well-defined; ncoef = the number of coefficients of all gases.  Both take a non-NULL model.
+int check_model_shape(const ecckd_opt_model* m, const char* who, std::string& err);
+int check_model_gases(const ecckd_opt_model* m, const char* who, std::string& err, size_t& ncoef);
 void order_gases(const ecckd_opt_model* m, Tables& t);              // gas order, sizes and the coefficient vector
 void cap_relative_linear(double cap_fraction, Tables& t);
 void build_prior(const ecckd_opt_config& cfg, Tables& t);           // AR(1) inverses, sigma, the active nodes

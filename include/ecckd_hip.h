@@ -965,6 +965,49 @@ int ecckd_opt_timings(ecckd_opt* opt, double* minimizer_s, double* a_priori_s, d
 int ecckd_run_ckd(ecckd_ctx* ctx, const ecckd_opt_model* model, const ecckd_opt_scene* scene, double* h_od,
                   double* h_rayleigh_od, double* h_planck_hl, double* h_flux);
 
+/* ---- resident gas optics: a CKD model applied to columns in device memory -----------
+ * Replaces CkdModel::calc_optical_depth (ckd_model.cpp:925-1102) and calc_planck_function (:1107-1145) for a host model
+ * whose columns already sit on the device.  ecckd_gas_optics_create validates the model with the model part of
+ * ecckd_opt_create's check (logarithmic interpolation is refused; min_molar_abs, max_molar_abs and is_active are ignored;
+ * at most 32 gases) and uploads it once: all gases' tables in model order, the temperature grid, the Planck look-up table
+ * or the Rayleigh coefficients (the solar irradiance stays on the host: only ecckd_gas_optics_incoming reads it).  Device
+ * memory comes from the context's caching allocator.  The handle keeps no per-call state: calls of any shape may follow each
+ * other, and a cell's result is a pure function of that cell's inputs and the model - the same bits whatever ncol, the cell's
+ * place in the batch, or the calls before.
+ *
+ * ecckd_gas_optics_dev: one launch on the context's stream, no host wait (the host arrays are read before it returns).
+ *   d_pressure_hl, d_temperature_hl [ncol][nlay+1]; d_temperature_fl [ncol][nlay] or NULL = the pressure-weighted mean of
+ *   temperature_hl; d_vmr_fl [ncol][ngas][nlay] in model gas order - device doubles in the layouts of ecckd_opt_scene.
+ *   h_gas_present[ngas] (NULL = all): a gas with 0 contributes nothing whatever its concentration dependence (run_ckd's
+ *   rule, run_ckd.cpp:270-276); h_gas_scaling[ngas] (NULL = 1) multiplies the gas's mole fraction first.
+ *   Outputs: device arrays [ncol][nlay][ng], g fastest, of out_type ECCKD_F64 or ECCKD_F32 (the double result rounded once):
+ *   d_od the sum of the gases in model order; h_d_gas_od a host array of ngas device pointers, NULL entries or a NULL array
+ *   skipped, every gas out of the same pass (an absent gas gives zeros); d_rayleigh_od, shortwave handles only,
+ *   moles_per_layer * rayleigh_molar_scattering[g], zeros for a model without coefficients.  Any of them may be NULL, not all.
+ *   Per cell: ln of the mean pressure, the pressure axis position held inside the table (the n - 1.0001 rule), the
+ *   temperature axis on the table column interpolated at that pressure, for conc_dependence 2 the log-concentration axis;
+ *   weight MOLES_PER_PA dp, times vmr, or times (vmr - reference_vmr); per gas one FMA chain over its 4 or 8 nodes.
+ *   keep_negative 0: the SUM is clamped at 0 and each per-gas output on its own; 1: nothing is clamped.
+ *   ECCKD_PARAMETER_ERROR: NULL pressure or temperature, non-positive sizes, d_rayleigh_od on a longwave handle, d_vmr_fl ==
+ *   NULL with a concentration-dependent gas present, out_type or keep_negative outside their values, no output.
+ * ecckd_gas_optics_planck_dev: d_planck[n][ng] at d_temperature[n], linear in the look-up table, (t / t0) * row 0 below it,
+ *   extrapolated from the last two rows above it; refused on a shortwave handle.
+ * ecckd_gas_optics_incoming: h_incoming[ng] = tsi / sum(ssi) * ssi (host only); refused on a longwave handle.
+ * ecckd_gas_optics_geometry (host only): the launch tile - consecutive cells of the flattened (column, layer) index per
+ *   block, threads per block - for tests that place their sizes at its edges. */
+typedef struct ecckd_gas_optics ecckd_gas_optics;
+int ecckd_gas_optics_create(ecckd_ctx* ctx, const ecckd_opt_model* model, ecckd_gas_optics** gas_optics);
+int ecckd_gas_optics_destroy(ecckd_gas_optics* gas_optics);
+int ecckd_gas_optics_info(ecckd_gas_optics* gas_optics, int* ng, int* ngas, int* is_sw, int* entries_per_cell);
+int ecckd_gas_optics_geometry(ecckd_gas_optics* gas_optics, int* cells_per_block, int* threads);
+int ecckd_gas_optics_dev(ecckd_gas_optics* gas_optics, int ncol, int nlay, const double* d_pressure_hl,
+                         const double* d_temperature_hl, const double* d_temperature_fl, const double* d_vmr_fl,
+                         const int* h_gas_present, const double* h_gas_scaling, int keep_negative, int out_type, void* d_od,
+                         void* const* h_d_gas_od, void* d_rayleigh_od);
+int ecckd_gas_optics_planck_dev(ecckd_gas_optics* gas_optics, size_t n, const double* d_temperature, int out_type,
+                                void* d_planck);
+int ecckd_gas_optics_incoming(ecckd_gas_optics* gas_optics, double tsi, double* h_incoming);
+
 /* ---- scale_lut -----------------------------------------------------
  * scale_lut.cpp:117-133 needs, per g point, the sum over its wavenumbers of every row of a
  * (nrows, nwav) matrix (the LBL direct-beam spectral flux at each half level): h_sums[nrows][ng].
