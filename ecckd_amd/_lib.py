@@ -184,6 +184,14 @@ SIGNATURES = {
                                        C.c_void_p]),
     "ecckd_gas_optics_planck_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
     "ecckd_gas_optics_incoming": (C.c_int, [C.c_void_p, C.c_double, _c_double_p]),
+    "ecckd_gas_optics_fluxes_lw_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.POINTER(C.c_int), _c_double_p, C.c_int, C.c_void_p]),
+    "ecckd_gas_optics_fluxes_sw_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.POINTER(C.c_int), _c_double_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p]),
+    "ecckd_gas_optics_fluxes_geometry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                   C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    "ecckd_gas_optics_fluxes_plan": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int,
+                                               C.c_longlong, C.c_void_p, C.c_char_p, C.c_size_t]),
     "ecckd_scale_lut": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _c_double_p, _c_double_p, _c_double_p,
                                   C.POINTER(C.c_int), C.c_double, _c_double_p, _c_double_p, C.POINTER(_c_double_p)]),
     "ecckd_gmap_sum_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_size_t, _c_double_p]),
@@ -381,6 +389,19 @@ class ForwardPlan(C.Structure):
 class RayleighPlan(C.Structure):
     _fields_ = [("active", C.c_int), ("chunk_rows", C.c_int), ("finish_waves", C.c_int), ("batch", C.c_int),
                 ("nrows", C.c_size_t), ("npart", C.c_size_t)]
+
+
+class FluxOutputs(C.Structure):
+    """ecckd_flux_outputs: device pointers of the fused fluxes, None = not wanted."""
+    _fields_ = [(n, C.c_void_p) for n in ("flux_dn", "flux_up", "band_flux_dn", "band_flux_up", "spectral_flux_dn", "spectral_flux_up",
+                                          "heating_rate", "flux_dn_direct", "band_flux_dn_direct", "spectral_flux_dn_direct")]
+
+
+class FluxPlan(C.Structure):
+    """ecckd_flux_plan"""
+    _fields_ = [("columns_per_block", C.c_int), ("layer_tile", C.c_int), ("threads", C.c_int), ("g_passes", C.c_int),
+                ("state_rows", C.c_int), ("reduce_levels", C.c_int), ("grid", C.c_uint), ("ngroup", C.c_size_t),
+                ("lds_bytes", C.c_size_t), ("scratch_bytes", C.c_size_t)]
 
 
 TRACE_FN = C.CFUNCTYPE(None, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p)

@@ -1190,7 +1190,12 @@ class GasOptics:
         self.ctx = ctx
         self.lib = ctx.lib
         keep = []
-        m = _opt_model(model, keep)
+        if model.get("iband_per_g") is None:      # served, less the band sums of the fused fluxes
+            ng = len(model["solar_irradiance"]) if model.get("planck_function") is None else np.shape(model["planck_function"])[1]
+            m = _opt_model(dict(model, iband_per_g=np.zeros(ng, dtype=np.int32)), keep)
+            m.iband_per_g = None
+        else:
+            m = _opt_model(model, keep)
         h = C.c_void_p()
         check(self.lib.ecckd_gas_optics_create(ctx.handle, C.byref(m), C.byref(h)))
         self.handle = h
@@ -1198,6 +1203,7 @@ class GasOptics:
         check(self.lib.ecckd_gas_optics_info(h, C.byref(ng), C.byref(ngas), C.byref(is_sw), C.byref(nent)))
         self.ng, self.ngas, self.is_sw, self.entries_per_cell = ng.value, ngas.value, bool(is_sw.value), nent.value
         self.names = [g.get("name", str(i)) for i, g in enumerate(model["gases"])]
+        self.nband = 0 if model.get("iband_per_g") is None else 1 + int(np.max(model["iband_per_g"]))
         ctx._children.add(self)
 
     def close(self):
@@ -1291,6 +1297,102 @@ class GasOptics:
         out = np.empty(self.ng)
         check(self.lib.ecckd_gas_optics_incoming(self.handle, float(tsi), _hptr(out)))
         return out
+
+    def fluxes_geometry(self, nlay, mode=0):
+        """The launch of the fused fluxes at nlay layers (ecckd_gas_optics_fluxes_geometry; mode 0 longwave, 1 shortwave direct
+        beam, 2 shortwave two-stream) -> dict(columns_per_block, threads, layer_tile, scratch_bytes)."""
+        cpb, threads, tile, scratch = C.c_int(), C.c_int(), C.c_int(), C.c_size_t()
+        check(self.lib.ecckd_gas_optics_fluxes_geometry(self.handle, int(nlay), int(mode), C.byref(cpb), C.byref(threads), C.byref(tile),
+                                                        C.byref(scratch)))
+        return dict(columns_per_block=cpb.value, threads=threads.value, layer_tile=tile.value, scratch_bytes=scratch.value)
+
+    def _fluxes(self, sw, pressure_hl, temperature_hl, vmr_fl, temperature_fl, gases, scalings, bands, spectral, heating_rate, direct, dtype,
+                call):
+        torch = _torch()
+        dtype = torch.float64 if dtype is None else dtype
+        out_type = self._out_type(dtype)
+        ncol, nhl = pressure_hl.shape
+        nlay = nhl - 1
+        p = self._input(pressure_hl, (ncol, nhl), "pressure_hl")
+        t = self._input(temperature_hl, (ncol, nhl), "temperature_hl")
+        vmr = self._input(vmr_fl, (ncol, self.ngas, nlay), "vmr_fl")
+        tfl = self._input(temperature_fl, (ncol, nlay), "temperature_fl")
+        present = np.ones(self.ngas, dtype=np.int32)
+        if gases is not None:
+            present = np.array([1 if (i in gases or self.names[i] in gases) else 0 for i in range(self.ngas)], dtype=np.int32)
+        scaling = np.ones(self.ngas)
+        for i, f in (scalings or {}).items():
+            scaling[i] = f
+        new = lambda *shape: torch.empty(shape, dtype=dtype, device=self.ctx.device)
+        dom = "_sw" if sw else "_lw"
+        dn = "flux_dn_direct" if (sw and not direct) else "flux_dn"        # without scattering the downwelling flux is the beam
+        res, o = {}, _lib.FluxOutputs()
+        def add(field, key, *shape):
+            res[key] = new(*shape)
+            setattr(o, field, res[key].data_ptr())
+        add("flux_dn", dn + dom, ncol, nhl)
+        add("flux_up", "flux_up" + dom, ncol, nhl)
+        if direct:
+            add("flux_dn_direct", "flux_dn_direct" + dom, ncol, nhl)
+        if bands:
+            nband = self.nband if self.nband else 1          # (without iband_per_g the library refuses)
+            add("band_flux_dn", "band_" + dn + dom, ncol, nhl, nband)
+            add("band_flux_up", "band_flux_up" + dom, ncol, nhl, nband)
+            if direct:
+                add("band_flux_dn_direct", "band_flux_dn_direct" + dom, ncol, nhl, nband)
+        if spectral:
+            add("spectral_flux_dn", "spectral_" + dn + dom, ncol, nhl, self.ng)
+            add("spectral_flux_up", "spectral_flux_up" + dom, ncol, nhl, self.ng)
+            if direct:
+                add("spectral_flux_dn_direct", "spectral_flux_dn_direct" + dom, ncol, nhl, self.ng)
+        if heating_rate:
+            add("heating_rate", "heating_rate" + dom, ncol, nlay)
+        self.ctx.fence_from_torch()
+        check(call(ncol, nlay, _dptr(p), _dptr(t), _dptr(tfl) if tfl is not None else None, _dptr(vmr) if vmr is not None else None,
+                   _hptr(present, C.c_int), _hptr(scaling), out_type, C.byref(o)))
+        self.ctx.synchronize()
+        return res
+
+    def fluxes_lw(self, pressure_hl, temperature_hl, vmr_fl, nangle=0, temperature_fl=None, gases=None, scalings=None,
+                  bands=False, spectral=False, heating_rate=True, dtype=None):
+        """Longwave fluxes and heating rates of device columns in one launch (ecckd_gas_optics_fluxes_lw_dev): the optical
+        depths of optical_depth() and the Planck function of planck() fed to the transfer of rt_lw_gpoints(nangle) without
+        leaving the kernel.  -> dict of device tensors by run_ckd's names: flux_dn_lw, flux_up_lw [ncol, nlay+1];
+        heating_rate_lw [ncol, nlay] (K s-1); bands: band_flux_dn_lw, band_flux_up_lw [ncol, nlay+1, nband]; spectral:
+        spectral_flux_dn_lw, spectral_flux_up_lw [ncol, nlay+1, ng].  Inputs as optical_depth()."""
+        call = lambda ncol, nlay, p, t, tfl, vmr, present, scaling, out_type, o: self.lib.ecckd_gas_optics_fluxes_lw_dev(
+            self.handle, int(nangle), ncol, nlay, p, t, tfl, vmr, present, scaling, out_type, o)
+        return self._fluxes(False, pressure_hl, temperature_hl, vmr_fl, temperature_fl, gases, scalings, bands, spectral, heating_rate, False,
+                            dtype, call)
+
+    def fluxes_sw(self, pressure_hl, temperature_hl, vmr_fl, cos_sza, albedo=None, tsi=1361.0, scattering=False,
+                  temperature_fl=None, gases=None, scalings=None, bands=False, spectral=False, heating_rate=True, dtype=None):
+        """Shortwave fluxes and heating rates of device columns in one launch (ecckd_gas_optics_fluxes_sw_dev).  cos_sza and
+        albedo (None = 0) are device tensors [ncol]; a column without sun gets zeros.  scattering=False: the direct beam and its
+        reflection, rt_sw_gpoints on optical_depth + rayleigh_optical_depth -> flux_dn_direct_sw, flux_up_sw, heating_rate_sw
+        (and band_ / spectral_ forms); scattering=True: the two-stream transfer of rt_sw_gpoints_rayleigh -> flux_dn_sw
+        (direct plus diffuse), flux_up_sw, flux_dn_direct_sw, heating_rate_sw (and band_ / spectral_ forms)."""
+        ncol = pressure_hl.shape[0]
+        if cos_sza is None:
+            raise EcckdError(_lib.PARAMETER_ERROR, "fluxes_sw: cos_sza is needed")
+        mu0 = self._input(cos_sza, (ncol,), "cos_sza")
+        alb = self._input(albedo, (ncol,), "albedo")
+        call = lambda ncol, nlay, p, t, tfl, vmr, present, scaling, out_type, o: self.lib.ecckd_gas_optics_fluxes_sw_dev(
+            self.handle, int(scattering), ncol, nlay, p, t, tfl, vmr, present, scaling, _dptr(mu0), _dptr(alb) if alb is not None else None,
+            float(tsi), out_type, o)
+        return self._fluxes(True, pressure_hl, temperature_hl, vmr_fl, temperature_fl, gases, scalings, bands, spectral, heating_rate,
+                            bool(scattering), dtype, call)
+
+
+def gas_optics_fluxes_plan(ncol, nlay, ng, nent, nband=1, mode=0, nangle=0, wants=1, cu_count=256, grid_override=0):
+    """The launch plan of the fused fluxes as a function of the shape alone (ecckd_gas_optics_fluxes_plan; host only, no
+    context) -> dict of the plan's fields; a refusal raises EcckdError with the plan's message."""
+    plan, msg = _lib.FluxPlan(), C.create_string_buffer(512)
+    rc = _lib.load_library().ecckd_gas_optics_fluxes_plan(int(ncol), int(nlay), int(ng), int(nent), int(nband), int(mode), int(nangle),
+                                                          int(wants), int(cu_count), int(grid_override), C.addressof(plan), msg, 512)
+    if rc != _lib.OK:
+        raise EcckdError(rc, msg.value.decode("utf-8", "replace"))
+    return {n: getattr(plan, n) for n, _ in _lib.FluxPlan._fields_}
 
 
 def derive_d_wavenumber(ctx, wavenumber):
@@ -1477,6 +1579,19 @@ def rt_lw_gpoints(ctx, planck_hl, optical_depth, nangle=0):
     ncol, nlay, ng = od.shape
     dn, up = np.empty((ncol, nlay + 1, ng)), np.empty((ncol, nlay + 1, ng))
     check(ctx.lib.ecckd_rt_lw_gpoints(ctx.handle, int(nangle), ncol, nlay, ng, _hptr(pl), _hptr(od), _hptr(dn), _hptr(up)))
+    return dn, up
+
+
+def rt_sw_gpoints(ctx, cos_sza, albedo, incoming, optical_depth):
+    """Shortwave direct-beam and surface-reflected fluxes per g point from what run_ckd wrote (ecckd_rt_sw_gpoints): host arrays
+    incoming (ncol, ng) and optical_depth (ncol, nlay, ng; absorption plus Rayleigh), scalars cos_sza and albedo ->
+    (flux_dn_direct, flux_up), each (ncol, nlay+1, ng)."""
+    od, inc = _f64c(optical_depth), _f64c(incoming)
+    if od.ndim != 3 or inc.shape != (od.shape[0], od.shape[2]):
+        raise ValueError("optical_depth must be (ncol, nlay, ng) and incoming (ncol, ng)")
+    ncol, nlay, ng = od.shape
+    dn, up = np.empty((ncol, nlay + 1, ng)), np.empty((ncol, nlay + 1, ng))
+    check(ctx.lib.ecckd_rt_sw_gpoints(ctx.handle, ncol, nlay, ng, float(cos_sza), float(albedo), _hptr(inc), _hptr(od), _hptr(dn), _hptr(up)))
     return dn, up
 
 

@@ -10,6 +10,9 @@
 // device_gas_optics=1 (not in the reference): the same file from the resident gas-optics handle - the total and every gas's
 // optical depth out of one pass of ecckd_gas_optics_dev, the Planck function or the incoming flux from the handle, the fluxes
 // from ecckd_rt_lw_gpoints(nangle = 0) / ecckd_rt_sw_gpoints(albedo 0).
+// device_fluxes=1 (with device_gas_optics=1): the flux variables come from the fused call of the handle instead
+// (ecckd_gas_optics_fluxes_lw_dev(nangle = 0) / ecckd_gas_optics_fluxes_sw_dev(scattering 0, albedo 0, the scene's mu0[0])), which
+// forms no optical depth in memory; the optical depths and the Planck / incoming variables come from the calls they came from.
 #include "ckd_file.hpp"
 
 #include <memory>
@@ -34,7 +37,8 @@ struct DevBlock {
 
 // What ecckd_run_ckd returns, from the gas-optics handle: od, ray (shortwave), planck ([ncol][nhl][ng]; shortwave: row 0 of
 // every column the incoming flux), flux ([ncol][2][nhl][ng]), and with want_gases every present gas's optical depth.
-void device_gas_optics_pass(ecckd_ctx* ctx, const ecckd_opt_model& m, const ecckd_opt_scene& sc, bool want_gases, std::vector<double>& od,
+void device_gas_optics_pass(ecckd_ctx* ctx, const ecckd_opt_model& m, const ecckd_opt_scene& sc, bool want_gases, bool device_fluxes,
+                            std::vector<double>& od,
                             std::vector<double>& ray, std::vector<double>& planck, std::vector<double>& flux,
                             std::vector<std::vector<double>>& od_gases) {
   const bool is_sw = m.solar_irradiance != nullptr;
@@ -60,11 +64,32 @@ void device_gas_optics_pass(ecckd_ctx* ctx, const ecckd_opt_model& m, const ecck
   for (int i = 0; i < m.ngas; ++i)
     if (d_gas[i]) { od_gases[i].resize(ncell); d_gas[i]->to_host(od_gases[i]); }
   std::vector<double> dn(nlev), up(nlev, 0.0);
+  // device_fluxes: the per-g fluxes out of the fused call, device columns in, device fluxes out
+  std::unique_ptr<DevBlock> d_dn, d_up;
+  if (device_fluxes) {
+    d_dn.reset(new DevBlock(ctx, nlev * sizeof(double)));
+    ecckd_flux_outputs out{};
+    out.spectral_flux_dn = d_dn->p;
+    if (!is_sw) {
+      d_up.reset(new DevBlock(ctx, nlev * sizeof(double)));
+      out.spectral_flux_up = d_up->p;
+      ck(ecckd_gas_optics_fluxes_lw_dev(h, 0, sc.ncol, sc.nlay, (const double*)d_p.p, (const double*)d_t.p, nullptr, (const double*)d_vmr.p,
+                                        sc.gas_present, nullptr, ECCKD_F64, &out));
+      d_up->to_host(up);
+    } else {
+      const std::vector<double> mu0(ncol, sc.mu0[0]);
+      const DevBlock d_mu0(ctx, ncol * sizeof(double), mu0.data());
+      ck(ecckd_gas_optics_fluxes_sw_dev(h, 0, sc.ncol, sc.nlay, (const double*)d_p.p, (const double*)d_t.p, nullptr, (const double*)d_vmr.p,
+                                        sc.gas_present, nullptr, (const double*)d_mu0.p, nullptr, sc.tsi, ECCKD_F64, &out));
+      ck(ecckd_synchronize(ctx));   // d_mu0 leaves the scope
+    }
+    d_dn->to_host(dn);
+  }
   if (!is_sw) {
     const DevBlock d_planck(ctx, nlev * sizeof(double));
     ck(ecckd_gas_optics_planck_dev(h, ncol * nhl, (const double*)d_t.p, ECCKD_F64, d_planck.p));
     d_planck.to_host(planck);
-    ck(ecckd_rt_lw_gpoints(ctx, 0, sc.ncol, sc.nlay, m.ng, planck.data(), od.data(), dn.data(), up.data()));
+    if (!device_fluxes) ck(ecckd_rt_lw_gpoints(ctx, 0, sc.ncol, sc.nlay, m.ng, planck.data(), od.data(), dn.data(), up.data()));
   } else {
     d_ray->to_host(ray);
     std::vector<double> incoming(ng), incoming_all(ncol * ng), od_total(ncell), up_unused(nlev);
@@ -75,7 +100,8 @@ void device_gas_optics_pass(ecckd_ctx* ctx, const ecckd_opt_model& m, const ecck
       std::copy(incoming.begin(), incoming.end(), planck.begin() + c * nhl * ng);
     }
     for (size_t e = 0; e < ncell; ++e) od_total[e] = od[e] + ray[e];   // Rayleigh joins after the clamp (run_ckd.cpp:361)
-    ck(ecckd_rt_sw_gpoints(ctx, sc.ncol, sc.nlay, m.ng, sc.mu0[0], 0.0, incoming_all.data(), od_total.data(), dn.data(), up_unused.data()));
+    if (!device_fluxes)
+      ck(ecckd_rt_sw_gpoints(ctx, sc.ncol, sc.nlay, m.ng, sc.mu0[0], 0.0, incoming_all.data(), od_total.data(), dn.data(), up_unused.data()));
   }
   for (size_t c = 0; c < ncol; ++c) {
     std::copy(dn.begin() + c * nhl * ng, dn.begin() + (c + 1) * nhl * ng, flux.begin() + (c * 2) * nhl * ng);
@@ -103,6 +129,9 @@ int main(int argc, char** argv) {
     config.read(tsi, "tsi");
     bool device_gas_optics = false;
     config.read(device_gas_optics, "device_gas_optics");
+    bool device_fluxes = false;
+    config.read(device_fluxes, "device_fluxes");
+    if (device_fluxes && !device_gas_optics) fail(ECCKD_PARAMETER_ERROR, "device_fluxes=1 needs device_gas_optics=1");
 
     CkdFile model = read_ckd(paths.find(ckd_file));
     const std::string dom = model.is_sw ? "sw" : "lw";
@@ -156,7 +185,7 @@ int main(int argc, char** argv) {
     const size_t ncell = (size_t)ncol * nlay * ng, nlev = (size_t)ncol * nhl * ng;
     std::vector<double> od(ncell), ray(model.is_sw ? ncell : 0), planck(nlev), flux(2 * nlev);
     std::vector<std::vector<double>> od_gases;   // device_gas_optics: every gas from the one pass
-    if (device_gas_optics) device_gas_optics_pass(dev.ctx(), mv.m, sc, !write_od_only, od, ray, planck, flux, od_gases);
+    if (device_gas_optics) device_gas_optics_pass(dev.ctx(), mv.m, sc, !write_od_only, device_fluxes && !write_od_only, od, ray, planck, flux, od_gases);
     else ck(ecckd_run_ckd(dev.ctx(), &mv.m, &sc, od.data(), model.is_sw ? ray.data() : nullptr, planck.data(), flux.data()));
 
     LOG("Writing %s\n", output_file.c_str());

@@ -1,6 +1,7 @@
 // gas_optics.hip - the resident gas-optics handle: a CKD model uploaded once and applied to atmospheric columns that already sit
 // in device memory (CkdModel::calc_optical_depth, ckd_model.cpp:925-1102, and calc_planck_function, :1107-1145).  The host step
-// (flattening the model, the refusals, the launch plan) is gas_optics_tables.cpp.
+// (flattening the model, the refusals, the launch plan) is gas_optics_tables.cpp; the device code shared with the fused fluxes
+// of gas_optics_fluxes.hip, and the handle itself, are gas_optics_device.hpp.
 //
 // k_gas_optics: a block takes a tile of CELLS_PER_BLOCK consecutive cells of the flattened (column, layer) index.  One lane per
 // cell forms what all g points of the cell share - the three axis positions, their logarithms and the cell's (table row,
@@ -9,9 +10,7 @@
 // a few cells (an LDS broadcast per cell).  Per (cell, g): one FMA chain per gas over its 4 or 8 entries, in build_entries' node
 // order; the total is the sum of the gases' chains in model order; the stores are consecutive over the tile.  No atomics, and
 // nothing a cell computes depends on the batch, the tile or the grid.
-#include "common.hpp"
-#include "gas_optics_tables.hpp"
-#include "opt_tables.hpp"
+#include "gas_optics_device.hpp"
 
 #include <memory>
 #include <string>
@@ -20,93 +19,10 @@ namespace go = ecckd::gas_optics;
 
 namespace {
 
+// the model and the call as the kernels read them, cell_entries, chain4, put, planck_value: gas_optics_device.hpp
+using go::GoModel; using go::GoCall; using go::cell_entries; using go::chain4; using go::put; using go::planck_value;
+
 constexpr int CELLS = go::CELLS_PER_BLOCK, THREADS = go::THREADS;
-constexpr double MOLES_PER_PA = ecckd::opt_tables::MOLES_PER_PA;
-
-struct GoModel {
-  const double* k;
-  const double* temperature;    // [nt][np]; the temperature axis hangs on row 0
-  const double* rayleigh;       // [ng] or NULL
-  const go::GasDesc* gases;
-  double log_p_0, d_log_p, d_t;
-  int ng, nt, np, ngas, nent;
-};
-
-struct GoCall {
-  const double *p_hl, *t_hl, *t_fl, *vmr;
-  void* od;
-  void* ray_od;
-  void* gas_od[go::MAX_GASES];
-  double scaling[go::MAX_GASES];
-  size_t ncell;
-  uint32_t present;
-  int nlay, keep_negative;
-};
-
-struct AxisPos { int i0; double w0, w1; };
-
-// opt_tables.cpp axis_pos: the position on an evenly spaced axis of n nodes, held inside it
-__device__ inline AxisPos axis_pos(double index0, int n) {
-#pragma clang fp contract(off)
-  index0 = fmax(0.0, fmin(index0, n - 1.0001));
-  const int i0 = (int)index0;
-  const double w1 = index0 - i0;
-  return {i0, 1.0 - w1, w1};
-}
-
-// One cell's entries: opt_tables.cpp build_entries, with run_ckd's rule for absent gases (the caller skips them: their slots
-// are never read).  No contraction, so that every product and sum rounds as the host's.
-__device__ inline void cell_entries(const GoModel& m, const GoCall& c, size_t cell, double* coef, uint32_t* idx, double* moles) {
-#pragma clang fp contract(off)
-  const size_t col = cell / (size_t)c.nlay;
-  const int l = (int)(cell - col * (size_t)c.nlay);
-  const double* p = c.p_hl + col * (size_t)(c.nlay + 1);
-  const double* T = c.t_hl + col * (size_t)(c.nlay + 1);
-  const double p0 = p[l], p1 = p[l + 1];
-  const double t_fl = c.t_fl ? c.t_fl[cell] : (T[l] * p0 + T[l + 1] * p1) / (p0 + p1);
-  const double log_pressure_fl = log(0.5 * (p1 + p0));
-  const AxisPos ap = axis_pos((log_pressure_fl - m.log_p_0) / m.d_log_p, m.np);
-  const double t_0 = ap.w0 * m.temperature[ap.i0] + ap.w1 * m.temperature[ap.i0 + 1];
-  const AxisPos at = axis_pos((t_fl - t_0) / m.d_t, m.nt);
-  const double simple_weight = MOLES_PER_PA * (p1 - p0);
-  *moles = simple_weight;
-  for (int i = 0; i < m.ngas; ++i) {
-    if (!((c.present >> i) & 1u)) continue;
-    const go::GasDesc gd = m.gases[i];
-    double weight = simple_weight, vm = 0.0;
-    if (gd.conc != 0) {
-      vm = c.vmr[(col * (size_t)m.ngas + (size_t)i) * (size_t)c.nlay + (size_t)l] * c.scaling[i];
-      weight = (gd.conc == 3) ? simple_weight * (vm - gd.reference_vmr) : simple_weight * vm;
-    }
-    AxisPos ac = {0, 1.0, 1.0};
-    if (gd.conc == 2) ac = axis_pos((log(vm) - gd.log_vmr0) / gd.d_log_c, gd.nconc);
-    const int nc = gd.conc == 2 ? 2 : 1;
-    int q = gd.ent0;
-    for (int dc = 0; dc < nc; ++dc)
-      for (int dt = 0; dt < 2; ++dt)
-        for (int dp = 0; dp < 2; ++dp) {
-          const uint32_t node = ((uint32_t)(ac.i0 + dc) * (uint32_t)m.nt + (uint32_t)(at.i0 + dt)) * (uint32_t)m.np + (uint32_t)(ap.i0 + dp);
-          idx[q] = gd.ix + node * (uint32_t)m.ng;
-          coef[q] = weight * (dc ? ac.w1 : ac.w0) * (dt ? at.w1 : at.w0) * (dp ? ap.w1 : ap.w0);
-          ++q;
-        }
-  }
-}
-
-template <bool F32>
-__device__ inline void put(void* out, size_t i, double v) {
-  if (F32) ((float*)out)[i] = (float)v;
-  else ((double*)out)[i] = v;
-}
-
-// four entries of a chain: the loads go out together, the FMAs follow in entry order
-__device__ inline double chain4(const double* kg, const double* coef, const uint32_t* idx, double acc) {
-  const double k0 = kg[idx[0]], k1 = kg[idx[1]], k2 = kg[idx[2]], k3 = kg[idx[3]];
-  acc = fma(coef[0], k0, acc);
-  acc = fma(coef[1], k1, acc);
-  acc = fma(coef[2], k2, acc);
-  return fma(coef[3], k3, acc);
-}
 
 template <bool F32, bool PER_GAS>
 __global__ __launch_bounds__(THREADS) void k_gas_optics(const GoModel m, const GoCall c) {
@@ -162,39 +78,9 @@ __global__ __launch_bounds__(256) void k_gas_optics_planck(int ntp, const double
   if (j >= n * (size_t)ng) return;
   const size_t i = j / (size_t)ng;
   const size_t g = j - i * (size_t)ng;
-  const double t = temperature[i];
-  const double d_t = tpl[1] - tpl[0], t0 = tpl[0];
-  const double tindex0 = (t - t0) / d_t;
-  double v;
-  if (tindex0 >= 0) {
-    const int it0 = min((int)tindex0, ntp - 2);
-    const double w1 = tindex0 - it0, w0 = 1.0 - w1;
-    v = w0 * pf[(size_t)it0 * ng + g] + w1 * pf[(size_t)(it0 + 1) * ng + g];
-  } else {
-    v = (t / t0) * pf[g];
-  }
+  const double v = planck_value(ntp, tpl, pf, ng, g, temperature[i]);
   put<F32>(out, j, v);
 }
-
-}  // namespace
-
-struct ecckd_gas_optics {
-  ecckd_ctx* ctx = nullptr;
-  go::Flat f;                       // the model's small arrays; the tables themselves live on the device only
-  std::vector<void*> blocks;        // every device block of the handle, from the context's allocator
-  double *d_k = nullptr, *d_temperature = nullptr, *d_tpl = nullptr, *d_planck = nullptr, *d_rayleigh = nullptr;
-  go::GasDesc* d_gases = nullptr;
-  template <typename T> int upload(T** d, const std::vector<T>& h) {
-    void* v = nullptr;
-    ECCKD_HIP_CHECK(ecckd::dev_malloc(ctx, &v, std::max<size_t>(h.size(), 1) * sizeof(T)));
-    blocks.push_back(v);
-    *d = (T*)v;
-    if (!h.empty()) ECCKD_HIP_CHECK(hipMemcpyAsync(v, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-    return ECCKD_OK;
-  }
-};
-
-namespace {
 
 void go_free(ecckd_gas_optics* h) {
   if (!h) return;
@@ -236,6 +122,8 @@ int ecckd_gas_optics_create(ecckd_ctx* ctx, const ecckd_opt_model* model, ecckd_
     ECCKD_CHECK(h->upload(&h->d_planck, f.planck_function));
   }
   if (f.has_rayleigh) ECCKD_CHECK(h->upload(&h->d_rayleigh, f.rayleigh));
+  if (f.is_sw) ECCKD_CHECK(h->upload(&h->d_solar, f.solar_irradiance));      // the fused fluxes form incoming_sw per g point
+  if (f.nband > 0) ECCKD_CHECK(h->upload(&h->d_iband, f.iband));
   // (the sources are pageable vectors: the copies have left them when the stream has drained)
   ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   for (std::vector<double>* v : {&f.k, &f.temperature, &f.planck_function}) std::vector<double>().swap(*v);

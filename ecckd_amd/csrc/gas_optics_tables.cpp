@@ -3,6 +3,7 @@
 
 #include "opt_tables.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -27,7 +28,11 @@ int refuse(std::string& err, const char* fmt, ...) {
 int flatten_model(const ecckd_opt_model* m, Flat& f, std::string& err) {
   const char* who = "ecckd_gas_optics_create";
   if (!m) return refuse(err, "%s: NULL argument", who);
-  int rc = opt_tables::check_model_shape(m, who, err);
+  // (a model without iband_per_g is served, less the band sums: the shared check sees a stand-in for the missing map)
+  const int no_band = 0;
+  ecckd_opt_model checked = *m;
+  if (!m->iband_per_g) checked.iband_per_g = &no_band;
+  int rc = opt_tables::check_model_shape(&checked, who, err);
   if (rc != ECCKD_OK) return rc;
   size_t ncoef = 0;
   rc = opt_tables::check_model_gases(m, who, err, ncoef);
@@ -68,6 +73,11 @@ int flatten_model(const ecckd_opt_model* m, Flat& f, std::string& err) {
     f.ntp = m->ntp;
     f.temperature_planck.assign(m->temperature_planck, m->temperature_planck + f.ntp);
     f.planck_function.assign(m->planck_function, m->planck_function + (size_t)f.ntp * ng);
+  }
+  f.nband = 0;
+  if (m->iband_per_g) {
+    f.iband.assign(m->iband_per_g, m->iband_per_g + ng);
+    for (int b : f.iband) f.nband = std::max(f.nband, b + 1);
   }
   if (tile_lds_bytes(f.nent) > MAX_LDS_BYTES)
     return refuse(err, "%s: %d table entries per cell need %zu bytes of LDS per tile, more than %zu", who, f.nent, tile_lds_bytes(f.nent),
@@ -111,12 +121,102 @@ int check_call(const Flat& f, const CallArgs& a, uint32_t& present_mask, bool& a
   return ECCKD_OK;
 }
 
-void incoming(const Flat& f, double tsi, double* out) {
+double incoming_scaling(const Flat& f, double tsi) {
   double solar_sum = 0.0;
   for (int g = 0; g < f.ng; ++g) solar_sum += f.solar_irradiance[g];
-  const double tsi_scaling = tsi / solar_sum;
+  return tsi / solar_sum;
+}
+
+void incoming(const Flat& f, double tsi, double* out) {
+  const double tsi_scaling = incoming_scaling(f, tsi);
   for (int g = 0; g < f.ng; ++g) out[g] = tsi_scaling * f.solar_irradiance[g];
+}
+
+int fluxes_plan(long long ncol, int nlay, int ng, int nent, int nband, int mode, int nangle, unsigned wants, int cu_count,
+                long long grid_override, ecckd_flux_plan& p, std::string& err) {
+  const char* who = "ecckd_gas_optics_fluxes";
+  p = ecckd_flux_plan{};
+  if (!(ncol > 0 && nlay > 0)) return refuse(err, "%s: ncol, nlay must be positive (ncol=%lld nlay=%d)", who, ncol, nlay);
+  if (ncol > 0x7fffffffLL) return refuse(err, "%s: %lld columns are more than one call holds", who, ncol);
+  if (!(ng > 0 && nent > 0 && nband >= 0 && cu_count > 0))
+    return refuse(err, "%s: bad plan dimensions (ng=%d entries=%d nband=%d compute units=%d)", who, ng, nent, nband, cu_count);
+  if (mode != FLUX_LW && mode != FLUX_SW_DIRECT && mode != FLUX_SW_TWOSTREAM) return refuse(err, "%s: mode %d is not 0, 1 or 2", who, mode);
+  if (nangle < 0 || nangle > FLUX_MAX_ANGLES) return refuse(err, "%s: nangle = %d outside 0..%d", who, nangle, FLUX_MAX_ANGLES);
+  if (wants == 0 || wants > 31u) return refuse(err, "%s: no output asked for (wants=%u)", who, wants);
+  if ((wants & WANT_BANDS) && nband == 0) return refuse(err, "%s: band outputs asked of a model without iband_per_g", who);
+  if ((wants & WANT_DIRECT) && mode != FLUX_SW_TWOSTREAM)
+    return refuse(err, "%s: the direct outputs belong to the two-stream shortwave mode, not to mode %d", who, mode);
+  p.threads = THREADS;
+  p.columns_per_block = std::max(1, THREADS / ng);
+  p.g_passes = ng > THREADS ? (ng + THREADS - 1) / THREADS : 1;
+  p.layer_tile = std::max(1, FLUX_TILE_CELLS / p.columns_per_block);
+  p.state_rows = flux_state_rows(mode);
+  const size_t cells = (size_t)p.columns_per_block * p.layer_tile;      // <= THREADS: one lane forms one cell's entries
+  const size_t width = ng <= THREADS ? (size_t)THREADS : (size_t)ng;      // values of one level in a reduction
+  p.reduce_levels = (int)std::max<size_t>(1, FLUX_REDUCE_DOUBLES / width);
+  p.lds_bytes = cells * ((size_t)nent * 12 + 8) + (size_t)p.reduce_levels * width * 8;
+  if (p.lds_bytes > MAX_LDS_BYTES)
+    return refuse(err, "%s: ng=%d with %d table entries per cell needs %zu bytes of LDS per block, more than %zu", who, ng, nent, p.lds_bytes,
+                  MAX_LDS_BYTES);
+  const size_t nhl = (size_t)nlay + 1;
+  // per block: [g pass][state row][level][thread], then the broadband doubles [2][column][level]; whole 256-byte lines
+  size_t block_doubles = (size_t)p.g_passes * p.state_rows * nhl * THREADS + 2 * (size_t)p.columns_per_block * nhl;
+  block_doubles = (block_doubles + 31) / 32 * 32;
+  p.ngroup = ((size_t)ncol + p.columns_per_block - 1) / p.columns_per_block;
+  const size_t cap = grid_override >= 1 ? (size_t)std::min<long long>(grid_override, 0x7fffffffLL) : (size_t)cu_count * FLUX_BLOCKS_PER_CU;
+  p.grid = (unsigned)std::min(p.ngroup, cap);
+  p.scratch_bytes = (size_t)p.grid * block_doubles * 8;
+  return ECCKD_OK;
+}
+
+int check_fluxes_call(const Flat& f, const FluxCallArgs& a, uint32_t& present_mask, int& mode, unsigned& wants, std::string& err) {
+  const char* who = a.sw_call ? "ecckd_gas_optics_fluxes_sw_dev" : "ecckd_gas_optics_fluxes_lw_dev";
+  if (a.sw_call != f.is_sw)
+    return refuse(err, "%s: the handle holds a %s model", who, f.is_sw ? "shortwave" : "longwave");
+  if (!a.sw_call && (a.nangle < 0 || a.nangle > FLUX_MAX_ANGLES)) return refuse(err, "%s: nangle = %d outside 0..%d", who, a.nangle, FLUX_MAX_ANGLES);
+  if (a.sw_call && a.scattering != 0 && a.scattering != 1) return refuse(err, "%s: scattering must be 0 or 1, not %d", who, a.scattering);
+  if (a.sw_call && a.scattering == 1 && !f.has_rayleigh)
+    return refuse(err, "%s: scattering = 1 needs a model with Rayleigh coefficients (rayleigh_molar_scattering)", who);
+  mode = !a.sw_call ? FLUX_LW : (a.scattering ? FLUX_SW_TWOSTREAM : FLUX_SW_DIRECT);
+  if (!a.out) return refuse(err, "%s: the output structure is NULL", who);
+  const ecckd_flux_outputs& o = *a.out;
+  wants = 0;
+  if (o.flux_dn || o.flux_up) wants |= WANT_BROADBAND;
+  if (o.band_flux_dn || o.band_flux_up) wants |= WANT_BANDS;
+  if (o.spectral_flux_dn || o.spectral_flux_up) wants |= WANT_SPECTRAL;
+  if (o.heating_rate) wants |= WANT_HEATING;
+  if (o.flux_dn_direct || o.band_flux_dn_direct || o.spectral_flux_dn_direct) wants |= WANT_DIRECT;
+  if ((wants & WANT_DIRECT) && mode != FLUX_SW_TWOSTREAM)
+    return refuse(err, "%s: the *_direct outputs need scattering = 1%s", who,
+                  a.sw_call ? " (with scattering = 0 flux_dn is the direct beam)" : ", a longwave call has no direct beam");
+  if (wants == 0) return refuse(err, "%s: no output asked for", who);
+  if (((wants & WANT_BANDS) || o.band_flux_dn_direct) && f.nband == 0)
+    return refuse(err, "%s: band outputs asked of a model created without iband_per_g", who);
+  if (!a.have_pressure) return refuse(err, "%s: d_pressure_hl is NULL", who);
+  if (!a.have_temperature_hl) return refuse(err, "%s: d_temperature_hl is NULL", who);
+  if (a.sw_call && !a.have_cos_sza) return refuse(err, "%s: d_cos_sza is NULL", who);
+  present_mask = 0;
+  for (int i = 0; i < f.ngas; ++i) {
+    const bool present = !a.gas_present || a.gas_present[i] != 0;
+    if (present) present_mask |= 1u << i;
+    if (present && f.gases[i].conc != 0 && !a.have_vmr)
+      return refuse(err, "%s: d_vmr_fl is NULL but gas %d depends on its mole fraction", who, i);
+  }
+  if (a.out_type != ECCKD_F64 && a.out_type != ECCKD_F32)
+    return refuse(err, "%s: out_type %d is neither ECCKD_F32 nor ECCKD_F64", who, a.out_type);
+  return ECCKD_OK;
 }
 
 }  // namespace gas_optics
 }  // namespace ecckd
+
+extern "C" int ecckd_gas_optics_fluxes_plan(long long ncol, int nlay, int ng, int nent, int nband, int mode, int nangle, unsigned wants,
+                                            int cu_count, long long grid_override, ecckd_flux_plan* plan, char* message,
+                                            size_t message_bytes) {
+  std::string err;
+  ecckd_flux_plan p{};
+  const int rc = ecckd::gas_optics::fluxes_plan(ncol, nlay, ng, nent, nband, mode, nangle, wants, cu_count, grid_override, p, err);
+  if (plan) *plan = p;
+  if (message && message_bytes > 0) std::snprintf(message, message_bytes, "%s", err.c_str());
+  return rc;
+}

@@ -44,6 +44,8 @@ struct Flat {
   std::vector<double> temperature_planck, planck_function;   // longwave: [ntp], [ntp][ng]
   std::vector<double> solar_irradiance;  // shortwave: [ng]; stays on the host, only `incoming` reads it
   std::vector<double> rayleigh;          // [ng] or empty
+  std::vector<int> iband;                // [ng] g point -> band, or empty: a model without iband_per_g has no band sums
+  int nband = 0;                         // 1 + max(iband), 0 without iband_per_g
 };
 
 // Validates the model (the model part of the optimiser's check, opt_tables.hpp) and flattens it.  ECCKD_OK, or
@@ -77,6 +79,39 @@ int check_call(const Flat& f, const CallArgs& a, uint32_t& present_mask, bool& a
 
 // tsi / sum(ssi) * ssi, flatten_scenes' expression; out[ng]
 void incoming(const Flat& f, double tsi, double* out);
+// the factor of that expression, tsi / sum(ssi): the fused fluxes multiply it with ssi[g] on the device
+double incoming_scaling(const Flat& f, double tsi);
+
+// ---- the fused fluxes (gas_optics_fluxes.hip) ----
+constexpr int FLUX_LW = 0, FLUX_SW_DIRECT = 1, FLUX_SW_TWOSTREAM = 2;
+constexpr unsigned WANT_BROADBAND = 1, WANT_BANDS = 2, WANT_SPECTRAL = 4, WANT_HEATING = 8, WANT_DIRECT = 16;
+constexpr int FLUX_BLOCKS_PER_CU = 3;
+constexpr int FLUX_TILE_CELLS = 64;        // cells of a layer tile where the columns of a block allow it
+constexpr int FLUX_REDUCE_DOUBLES = 2048;  // LDS doubles of one reduction over g
+constexpr int FLUX_MAX_ANGLES = 16;
+// per-thread state rows of nlay + 1 doubles: longwave tau, Planck, dn, up; direct beam tau, dn, up; two-stream tau_abs,
+// tau_ray, direct, dn, up
+constexpr int flux_state_rows(int mode) { return mode == FLUX_LW ? 4 : (mode == FLUX_SW_DIRECT ? 3 : 5); }
+
+// The launch of a fused-flux call as a function of the shape alone (ecckd_flux_plan, ecckd_hip.h): a block of THREADS threads
+// owns max(1, THREADS / ng) whole columns, with ng > THREADS it loops over g; layers go through LDS in tiles of layer_tile;
+// the grid is bounded (FLUX_BLOCKS_PER_CU per compute unit, or grid_override >= 1 blocks) and its blocks loop over the column
+// groups, so scratch_bytes depends on the grid, not on ncol.  Refused: non-positive sizes, a mode, nangle or wants outside
+// their values, more LDS than a compute unit has.
+int fluxes_plan(long long ncol, int nlay, int ng, int nent, int nband, int mode, int nangle, unsigned wants, int cu_count,
+                long long grid_override, ecckd_flux_plan& p, std::string& err);
+
+struct FluxCallArgs {
+  bool sw_call;                    // ecckd_gas_optics_fluxes_sw_dev
+  int nangle, scattering, ncol, nlay;
+  bool have_pressure, have_temperature_hl, have_vmr, have_cos_sza;
+  const int* gas_present;          // [ngas] or NULL
+  int out_type;
+  const ecckd_flux_outputs* out;
+};
+// The refusals of the two fused-flux calls, each with its own message; on ECCKD_OK the gases that contribute, the mode and
+// what the outputs ask for (WANT_*).
+int check_fluxes_call(const Flat& f, const FluxCallArgs& a, uint32_t& present_mask, int& mode, unsigned& wants, std::string& err);
 
 }  // namespace gas_optics
 }  // namespace ecckd

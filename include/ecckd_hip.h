@@ -1008,6 +1008,62 @@ int ecckd_gas_optics_planck_dev(ecckd_gas_optics* gas_optics, size_t n, const do
                                 void* d_planck);
 int ecckd_gas_optics_incoming(ecckd_gas_optics* gas_optics, double tsi, double* h_incoming);
 
+/* ---- resident fluxes: device columns to fluxes and heating rates in one launch ---------
+ * The per-time-step call of a host model: from the inputs of ecckd_gas_optics_dev to broadband, band and per-g fluxes and
+ * heating rates on the device.  No [ncol][nlay][ng] array is written, nothing is copied to the host, and the only memory used
+ * beside the outputs is the context's scratch (which grows once and stops growing with ncol when the grid is saturated).  The
+ * call is queued on the context's stream and does not wait; the host arrays are read before it returns.
+ * Per (column, g point): the optical depth of every layer exactly as ecckd_gas_optics_dev forms it (keep_negative = 0: the
+ * total clamped at 0), on shortwave handles moles_per_layer * rayleigh[g] beside it; the Planck function at the half levels as
+ * ecckd_gas_optics_planck_dev forms it; then
+ *   longwave                ecckd_rt_lw_gpoints(nangle): unit emissivity, surface Planck function = row nlay
+ *   shortwave, scattering 0 ecckd_rt_sw_gpoints on max(od, 0) + rayleigh_od: the direct beam and its Lambertian reflection
+ *   shortwave, scattering 1 ecckd_rt_sw_gpoints_rayleigh: the two-stream transfer with Rayleigh scattering
+ * with incoming[g] = tsi / sum(ssi) * ssi[g], d_cos_sza[ncol] and d_albedo[ncol] (NULL = 0) per column.  A column whose
+ * cos_sza is not positive gets zeros in every output.  Sums over g (broadband, and per band of iband_per_g) run over g in
+ * ascending order, whatever the batch, the grid or the column's place: a column's results are a pure function of that column
+ * and the model.  heating_rate[l] = -(g / cp) / (p[l+1] - p[l]) * (dn[l+1] - dn[l] - up[l+1] + up[l]) in K s-1 from the
+ * broadband doubles (heating_rate_single, heating_rate.h:55-72), before any rounding to float.
+ * ecckd_flux_outputs: device pointers, any may be NULL, not all; every array of out_type ECCKD_F64 or ECCKD_F32 (the double
+ * result rounded once).  With scattering = 0 flux_dn / band_flux_dn / spectral_flux_dn hold the direct beam and the *_direct
+ * fields must be NULL; with scattering = 1 they hold direct plus diffuse and the *_direct fields the beam.  nband = 1 +
+ * max(iband_per_g); a model created without iband_per_g refuses the band outputs.
+ * ECCKD_PARAMETER_ERROR, each with its own message: the wrong kind of handle, nangle outside 0..16, scattering outside {0, 1},
+ * scattering = 1 on a model without Rayleigh coefficients, *_direct outputs with scattering = 0 or on a longwave call, no
+ * output, NULL inputs, d_vmr_fl == NULL with a concentration-dependent gas present, a bad out_type, a shape the plan refuses
+ * (non-positive sizes, more than 160 KB of LDS per block).
+ * ECCKD_GAS_OPTICS_FLUXES_GRID = N (>= 1), read per call, forces N blocks in place of 3 per compute unit.
+ * ecckd_gas_optics_fluxes_geometry (host only; mode 0 longwave, 1 shortwave direct, 2 shortwave two-stream): whole columns per
+ * block, threads per block, layers per tile and the scratch of a saturated grid, for tests that sit on the edges.
+ * ecckd_gas_optics_fluxes_plan (host only, no handle): the launch plan as a function of the shape alone; `wants` is a bit set
+ * (1 broadband, 2 bands, 4 spectral, 8 heating rate, 16 direct); a refusal returns ECCKD_PARAMETER_ERROR and its message
+ * in `message` (message_bytes including the terminator). */
+typedef struct {
+  void *flux_dn, *flux_up;                    /* [ncol][nlay+1]          broadband                                   */
+  void *band_flux_dn, *band_flux_up;          /* [ncol][nlay+1][nband]   by iband_per_g                              */
+  void *spectral_flux_dn, *spectral_flux_up;  /* [ncol][nlay+1][ng]                                                  */
+  void *heating_rate;                         /* [ncol][nlay] K s-1                                                  */
+  void *flux_dn_direct, *band_flux_dn_direct, *spectral_flux_dn_direct;   /* shortwave, scattering = 1 only          */
+} ecckd_flux_outputs;
+typedef struct {
+  int columns_per_block, layer_tile, threads, g_passes;   /* g_passes > 1: ng > threads, a block loops over g */
+  int state_rows, reduce_levels;                          /* per-thread scratch rows of nlay+1 doubles; levels per LDS reduction */
+  unsigned grid;
+  size_t ngroup, lds_bytes, scratch_bytes;
+} ecckd_flux_plan;
+int ecckd_gas_optics_fluxes_lw_dev(ecckd_gas_optics* gas_optics, int nangle, int ncol, int nlay, const double* d_pressure_hl,
+                                   const double* d_temperature_hl, const double* d_temperature_fl, const double* d_vmr_fl,
+                                   const int* h_gas_present, const double* h_gas_scaling, int out_type,
+                                   const ecckd_flux_outputs* out);
+int ecckd_gas_optics_fluxes_sw_dev(ecckd_gas_optics* gas_optics, int scattering, int ncol, int nlay, const double* d_pressure_hl,
+                                   const double* d_temperature_hl, const double* d_temperature_fl, const double* d_vmr_fl,
+                                   const int* h_gas_present, const double* h_gas_scaling, const double* d_cos_sza,
+                                   const double* d_albedo, double tsi, int out_type, const ecckd_flux_outputs* out);
+int ecckd_gas_optics_fluxes_geometry(ecckd_gas_optics* gas_optics, int nlay, int mode, int* columns_per_block, int* threads,
+                                     int* layer_tile, size_t* scratch_bytes);
+int ecckd_gas_optics_fluxes_plan(long long ncol, int nlay, int ng, int nent, int nband, int mode, int nangle, unsigned wants,
+                                 int cu_count, long long grid_override, ecckd_flux_plan* plan, char* message, size_t message_bytes);
+
 /* ---- scale_lut -----------------------------------------------------
  * scale_lut.cpp:117-133 needs, per g point, the sum over its wavenumbers of every row of a
  * (nrows, nwav) matrix (the LBL direct-beam spectral flux at each half level): h_sums[nrows][ng].
