@@ -61,6 +61,11 @@ struct ecckd_ctx {
   // milliseconds on some hosts - inside the sweep.  Everything runs on `stream`, so reuse is ordered.
   void* cache_impl = nullptr;
   std::mutex cache_mutex;          // dev_malloc / dev_release are called by the gas threads of ecckd_find_g_gases
+  // Line-blocked copies of longwave Planck matrices (find_g.hip, sweep_layout.hpp), shared by the gases that share the
+  // row-major matrix: looked up by its base pointer while its owner lives (then `rowmajor` is cleared: no later gas may
+  // attach), freed with the last reference.  Under cache_mutex.
+  struct PlanckBlk { const void* rowmajor; void* blocked; int refs; };
+  std::vector<PlanckBlk> planck_blk;
   // lanes lent to gases searched side by side (created on demand, kept for the next call, destroyed with the context)
   std::vector<ecckd_lane*> lanes;
   std::mutex lane_mutex;

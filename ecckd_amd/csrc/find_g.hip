@@ -22,6 +22,7 @@
 // loads, with per-half-level flux sums reduced wave -> block -> interval in a
 // fixed order (bitwise reproducible; no float atomics).
 #include "chunk_layout.hpp"
+#include "sweep_layout.hpp"
 #include "common.hpp"
 #include "partition_search.hpp"
 #include "rt_device.hpp"
@@ -34,6 +35,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <thread>
+#include <type_traits>
 #include <vector>
 #include <immintrin.h>
 
@@ -898,6 +900,39 @@ k_unpack_bg32(int npair, size_t n, const float_x2_store* __restrict__ pairs, dou
   }
 }
 
+// A row-major matrix [rows][n] of 8-byte elements (DOUBLE values or FLOAT pairs) into its line-blocked form
+// [n / 16][rows][16] (sweep_layout.hpp), or back: one thread per element in the order of the blocked matrix, so every 16
+// lanes read one whole 128-byte line and store one whole line, each line once.
+template <bool TO_BLOCKED>
+__global__ void __launch_bounds__(256)
+k_reblock(unsigned rows, size_t n, const unsigned long long* __restrict__ src, unsigned long long* __restrict__ dst) {
+  namespace sl = ecckd::sweep_layout;
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)rows * n) return;
+  const size_t per = (size_t)rows * sl::LINE_PTS;
+  const size_t blk = e / per;
+  const unsigned rem = (unsigned)(e - blk * per);
+  const unsigned r = rem / (unsigned)sl::LINE_PTS;
+  const size_t i = blk * sl::LINE_PTS + rem % (unsigned)sl::LINE_PTS;
+  const size_t at_blocked = (size_t)(sl::offset(rows, r, i) / sl::ELEM_BYTES), at_rows = (size_t)r * n + i;
+  if (TO_BLOCKED) __builtin_nontemporal_store(__builtin_nontemporal_load(&src[at_rows]), &dst[at_blocked]);
+  else __builtin_nontemporal_store(__builtin_nontemporal_load(&src[at_blocked]), &dst[at_rows]);
+}
+
+// The DOUBLE rows of a gas that holds only the line-blocked FLOAT pairs (k_unpack_bg32 for the blocked matrix).
+__global__ void __launch_bounds__(256)
+k_unpack_bg32_blocked(int npair, size_t n, const float_x2_store* __restrict__ pairs, double* __restrict__ bg_od) {
+  namespace sl = ecckd::sweep_layout;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float_x2_store* __restrict__ at = pairs + sl::point_base(npair, i) / sl::ELEM_BYTES;
+  for (int p = 0; p < npair; ++p) {
+    const float_x2_store v = at[(size_t)p * sl::LINE_PTS];
+    bg_od[(size_t)(2 * p) * n + i] = (double)v.x;
+    bg_od[(size_t)(2 * p + 1) * n + i] = (double)v.y;
+  }
+}
+
 // K5c mirror path.  The two-stream equations are symmetric under turning the column upside down:
 // the up sweep through layer l, up_l = up_{l+1} t + B_{l+1}(eps-fac) + B_l fac, is the down sweep
 // dn_{l+1} = dn_l t + B_l(eps-fac) + B_{l+1} fac with the two Planck values exchanged
@@ -921,7 +956,11 @@ k_unpack_bg32(int npair, size_t n, const float_x2_store* __restrict__ pairs, dou
 // converted value is the DOUBLE row's value bit for bit and so is everything computed from it.  The even wave takes the
 // pairs top-down, the odd wave bottom-up with the two halves of a pair exchanged; with an odd number of layers per half the
 // middle pair is shared: .x is the even wave's last layer, .y the odd wave's.
-template <int NLAY, bool BG32>
+//
+// BLK: planck_hl and bg_od / bg_pair are the line-blocked matrices (sweep_layout.hpp) of a gas that holds them
+// (ecckd_gas::planck_blk, bg_blk); only the addresses of the loads differ - the same values reach the same lanes, and
+// everything after the loads is the same code, so the partials have the same bits.
+template <int NLAY, bool BG32, bool BLK>
 __global__ void __launch_bounds__(RT_THREADS, 3)
 k_rt_lw_bb_mirror(size_t n, int nint, long long nchunks, const Interval* __restrict__ iv,
                   const double* __restrict__ planck_hl, const double* __restrict__ bg_od,
@@ -986,6 +1025,51 @@ k_rt_lw_bb_mirror(size_t n, int nint, long long nchunks, const Interval* __restr
     // offset in a row (8 bytes per point in the DOUBLE rows and in the FLOAT-pair rows alike).  The row step is made opaque
     // once per tile, otherwise the compiler keeps all 42-55 row pointers of the unrolled loads in scalar registers across the
     // tile loop and spills them.
+    if constexpr (BLK) {
+      // Line-blocked operands (sweep_layout.hpp; planck_hl, bg_od and bg_pair are then the blocked matrices): the lane's byte
+      // offset of its point in row 0, once per tile and 32 bits wide, and every row a compile-time r * 128 bytes from it.  The
+      // even wave counts up from row 0, the odd wave down from its last row: one arm of loads each, all within the immediate
+      // offset of a load, no row pointer to advance.  A wave's 64 points of its half column are four contiguous pieces.
+      namespace sl = ecckd::sweep_layout;
+      constexpr int LB = (int)sl::LINE_BYTES;
+      constexpr unsigned BG_ROWS = BG32 ? H : NLAY;
+      static_assert(H * LB < 4096, "a half column's rows within a load's immediate offset");
+      const unsigned line = (unsigned)(ii / sl::LINE_PTS), in_line = (unsigned)(ii % sl::LINE_PTS) * (unsigned)sl::ELEM_BYTES;
+      const unsigned voff_p = line * (unsigned)(NHL * LB) + in_line;          // sweep_layout::point_base(NHL, ii), in 32 bits: the gas
+      const unsigned voff_b = line * (BG_ROWS * LB) + in_line;                // has the matrices only where they hold every offset
+      const char* const pl_blk = (const char*)planck_hl;
+      const char* const bg_blk = BG32 ? (const char*)bg_pair : (const char*)bg_od;
+      float_x2 v[H / 2];
+      float vm = 0.f;
+      auto loads = [&](auto dir) {
+        constexpr int S = decltype(dir)::value;       // +1: rows 0, 1, ..; -1: the last row, the one before it, ..
+        if constexpr (BG32) {
+          const char* r0 = bg_blk + (S < 0 ? (H - 1) * LB : 0) + voff_b;
+#pragma unroll
+          for (int q = 0; q < H / 2; ++q) v[q] = __builtin_nontemporal_load((const float_x2*)(r0 + S * q * LB));
+          if (H & 1) vm = __builtin_nontemporal_load((const float*)(bg_blk + ((H / 2) * LB + (S < 0 ? 4 : 0)) + voff_b));
+        } else {
+          const char* r0 = bg_blk + (S < 0 ? (NLAY - 1) * LB : 0) + voff_b;
+#pragma unroll
+          for (int l = 0; l < H; ++l) a[l] = __builtin_nontemporal_load((const double*)(r0 + S * l * LB));
+        }
+        const char* r0 = pl_blk + (S < 0 ? NLAY * LB : 0) + voff_p;
+#pragma unroll
+        for (int l = 0; l <= H; ++l) b[l] = __builtin_nontemporal_load((const double*)(r0 + S * l * LB));
+      };
+      // (Each arm ends in a marker of its own: two arms that end alike are merged by the compiler into one sequence of loads
+      // whose row offsets are selected per wave - 55 address pairs in registers, and spills.)
+      if (half) { loads(std::integral_constant<int, -1>{}); asm volatile("; the odd wave's loads are issued"); }
+      else { loads(std::integral_constant<int, 1>{}); asm volatile("; the even wave's loads are issued"); }
+      if constexpr (BG32) {
+#pragma unroll
+        for (int q = 0; q < H / 2; ++q) {
+          a[2 * q] = (double)(half ? v[q].y : v[q].x);
+          a[2 * q + 1] = (double)(half ? v[q].x : v[q].y);
+        }
+        if (H & 1) a[H - 1] = (double)vm;
+      }
+    } else {
     const unsigned voff = (unsigned)ii * 8u;
     long long step_b = row_step * 8;
     asm volatile("" : "+s"(step_b));
@@ -1017,7 +1101,8 @@ k_rt_lw_bb_mirror(size_t n, int nint, long long nchunks, const Interval* __restr
 #pragma unroll
       for (int l = 0; l <= H; ++l, rp += step_b) b[l] = __builtin_nontemporal_load((const double*)(rp + voff));
     }
-    __builtin_amdgcn_s_setprio(ECCKD_PRIO_SWEEP1);   // first sweep: the partner wave waits for its result
+    }
+    __builtin_amdgcn_s_setprio(ECCKD_PRIO_SWEEP1);  // first sweep: the partner wave waits for its result
 
     // A lane past the end of the chunk or below the interval's first point (only the chunk's last tile and the interval's
     // first tile have any) sweeps zero Planck functions: every flux of its column is then an exact zero and adds nothing to
@@ -1892,10 +1977,49 @@ int gas_ensure_work(ecckd_gas* g, size_t dev_bytes, size_t pinned_bytes) {
   return ECCKD_OK;
 }
 
+// The context's table of line-blocked Planck matrices (ecckd_ctx::planck_blk): the gases of a job share the first gas's
+// row-major matrix (d_planck_hl_reuse) and with it one blocked copy, which goes when its last holder goes, whichever that is.
+// A reference to the copy made from the row-major matrix at `rowmajor`, or nullptr: none is known.
+static double* planck_blk_attach(ecckd_ctx* ctx, const void* rowmajor) {
+  std::lock_guard<std::mutex> lock(ctx->cache_mutex);
+  for (ecckd_ctx::PlanckBlk& e : ctx->planck_blk)
+    if (e.rowmajor == rowmajor) { e.refs += 1; return (double*)e.blocked; }
+  return nullptr;
+}
+// A new copy, held once by the gas that made it.  rowmajor: the matrix later gases may name to share it, or nullptr (the
+// gas was handed a matrix the table does not know: nobody can tell how long that one lives, the copy stays the gas's own).
+static void planck_blk_register(ecckd_ctx* ctx, const void* rowmajor, void* blocked) {
+  std::lock_guard<std::mutex> lock(ctx->cache_mutex);
+  if (rowmajor)
+    for (ecckd_ctx::PlanckBlk& e : ctx->planck_blk)
+      if (e.rowmajor == rowmajor) e.rowmajor = nullptr;          // an address handed out again: the old copy is of another matrix
+  ctx->planck_blk.push_back({rowmajor, blocked, 1});
+}
+// One holder less; owned_rowmajor: the holder also frees this row-major matrix, no later gas may attach through it.
+static void planck_blk_drop(ecckd_ctx* ctx, void* blocked, const void* owned_rowmajor) {
+  void* last = nullptr;
+  {
+    std::lock_guard<std::mutex> lock(ctx->cache_mutex);
+    for (size_t k = 0; k < ctx->planck_blk.size(); ++k) {
+      ecckd_ctx::PlanckBlk& e = ctx->planck_blk[k];
+      if (owned_rowmajor && e.rowmajor == owned_rowmajor) e.rowmajor = nullptr;
+      if (e.blocked == blocked && --e.refs == 0) {
+        last = e.blocked;
+        ctx->planck_blk.erase(ctx->planck_blk.begin() + (long)k);
+        --k;
+      }
+    }
+  }
+  ecckd::dev_release(ctx, last);          // takes the mutex itself
+}
+
 void gas_free(ecckd_gas* g) {
   if (!g) return;
   ecckd_ctx* ctx = g->ctx;
   if (ctx) (void)hipStreamSynchronize(ctx->stream);
+  bool owns_planck = false;
+  for (void* b : g->blocks) owns_planck |= b == (void*)g->planck_hl;
+  if (g->planck_blk) planck_blk_drop(ctx, g->planck_blk, owns_planck ? g->planck_hl : nullptr);
   for (void* b : g->blocks) ecckd::dev_release(ctx, b);
   delete g;
 }
@@ -1906,14 +2030,64 @@ typedef std::unique_ptr<ecckd_gas, GasDeleter> GasPtr;
 
 // The DOUBLE rows of the background optical depths.  A longwave gas whose background is FLOAT holds the FLOAT pairs only
 // (ecckd_gas_create_lw); the rows are made from them when something asks: ecckd_gas_view, the run-time-nlay sweep.
+// A gas that holds its background line-blocked (bg_blk) has released both; the rows are made from the blocked matrix.
 static int gas_bg_rows(ecckd_gas* g) {
-  if (g->bg_od || !g->bg_pair) return ECCKD_OK;
+  if (g->bg_od || (!g->bg_pair && !g->bg_blk)) return ECCKD_OK;
   ecckd_ctx* ctx = g->ctx;
   ECCKD_HIP_CHECK(g->alloc(&g->bg_od, (size_t)g->nlay * g->n * sizeof(double)));
-  hipLaunchKernelGGL(k_unpack_bg32, dim3((unsigned)((g->n + 255) / 256)), dim3(256), 0, ctx->stream, g->nlay / 2, g->n,
-                     (const float_x2_store*)g->bg_pair, g->bg_od);
+  const dim3 per_point((unsigned)((g->n + 255) / 256));
+  if (g->bg_pair)
+    hipLaunchKernelGGL(k_unpack_bg32, per_point, dim3(256), 0, ctx->stream, g->nlay / 2, g->n, (const float_x2_store*)g->bg_pair, g->bg_od);
+  else if (g->bg_blk_pairs)
+    hipLaunchKernelGGL(k_unpack_bg32_blocked, per_point, dim3(256), 0, ctx->stream, g->nlay / 2, g->n, (const float_x2_store*)g->bg_blk,
+                       g->bg_od);
+  else
+    hipLaunchKernelGGL(k_reblock<false>, dim3((unsigned)(((size_t)g->nlay * g->n + 255) / 256)), dim3(256), 0, ctx->stream, (unsigned)g->nlay,
+                       g->n, (const unsigned long long*)g->bg_blk, (unsigned long long*)g->bg_od);
   ECCKD_HIP_CHECK(hipGetLastError());
   ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return ECCKD_OK;
+}
+
+// The operands of the mirror sweep of a prepared longwave gas, line-blocked (sweep_layout.hpp), where the aligned mirror path
+// runs - otherwise the gas stays as it is.  The background: a blocked copy of what the sweep reads, the FLOAT pairs or the
+// DOUBLE rows (one pass, every line read once and stored once), after which the row-major matrices are released; for its
+// duration the gas holds its background twice.  The Planck matrix stays (the sums and the fit read it, and the views); its
+// blocked copy is shared through the context's table by the gases that share the matrix.  ECCKD_RT_ROWMAJOR (read here, when
+// the gas is made): no blocked operands, the row-major sweep - A/B knob and fallback.
+static int gas_block_operands(ecckd_gas* g, bool planck_reused) {
+  namespace sl = ecckd::sweep_layout;
+  ecckd_ctx* ctx = g->ctx;
+  const size_t n = g->n;
+  const unsigned nlay = (unsigned)g->nlay, nhl = nlay + 1;
+  const auto on_line = [](const void* q) { return (uintptr_t)q % sl::LINE_BYTES == 0; };
+  if (!(nlay == 54 || nlay == 30) || !g->chunks_from_line || std::getenv("ECCKD_RT_ROWMAJOR") != nullptr) return ECCKD_OK;
+  if (!sl::whole_lines(n) || !sl::fits_32bit(nhl, n) || !on_line(g->planck_hl) || !on_line(g->bg_od) || !on_line(g->bg_pair)) return ECCKD_OK;
+  const auto reblock = [&](unsigned rows, const void* src, void* dst) {
+    hipLaunchKernelGGL(k_reblock<true>, dim3((unsigned)(((size_t)rows * n + 255) / 256)), dim3(256), 0, ctx->stream, rows, n,
+                       (const unsigned long long*)src, (unsigned long long*)dst);
+  };
+  double* shared = planck_reused ? planck_blk_attach(ctx, g->planck_hl) : nullptr;
+  if (shared) g->planck_blk = shared;
+  else {
+    void* mine = nullptr;
+    ECCKD_HIP_CHECK(ecckd::dev_malloc(ctx, &mine, (size_t)sl::bytes(nhl, n)));
+    planck_blk_register(ctx, planck_reused ? nullptr : g->planck_hl, mine);      // from here on gas_free lets go of it
+    g->planck_blk = (double*)mine;
+    reblock(nhl, g->planck_hl, mine);
+    ECCKD_HIP_CHECK(hipGetLastError());
+  }
+  const bool pairs = g->bg_pair != nullptr;
+  const unsigned bg_rows = pairs ? nlay / 2 : nlay;
+  void* blocked = nullptr;
+  ECCKD_HIP_CHECK(g->alloc(&blocked, (size_t)sl::bytes(bg_rows, n)));
+  reblock(bg_rows, pairs ? (const void*)g->bg_pair : (const void*)g->bg_od, blocked);
+  ECCKD_HIP_CHECK(hipGetLastError());
+  ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  g->bg_blk = blocked;
+  g->bg_blk_pairs = pairs;
+  g->give_back(g->bg_pair);
+  g->give_back(g->bg_od);
   return ECCKD_OK;
 }
 
@@ -2279,6 +2453,7 @@ int ecckd_gas_create_lw(ecckd_ctx* ctx, int nlay, size_t nwav, const double* h_p
   ECCKD_HIP_CHECK(hipMemcpyAsync(&not_float, d_flag + 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   if (want_pairs && !pairs_in_k4 && not_float) g->give_back(g->bg_pair);   // a DOUBLE background with values between the floats: the DOUBLE rows serve
+  ECCKD_CHECK(gas_block_operands(g, d_planck_hl_reuse != nullptr));
   *out = gas.release();
   return ECCKD_OK;
 }
@@ -2418,6 +2593,8 @@ int ecckd_gas_view(ecckd_gas* gas, const char* name, const double** d_ptr, size_
   const double* p = nullptr;
   if (!strcmp(name, "planck_hl")) { p = gas->planck_hl; r = nlay + 1; }
   else if (!strcmp(name, "bg_optical_depth")) { ECCKD_CHECK(gas_bg_rows(gas)); p = gas->bg_od; r = nlay; }
+  // the sweep's line-blocked Planck matrix as it lies in memory, [n/16][nlay+1][16] (tests): only a gas that holds one has it
+  else if (!strcmp(name, "planck_hl_blocked")) { p = gas->planck_blk; r = nlay + 1; }
   else if (!strcmp(name, "weighted_metric")) { p = gas->w1; r = nlay; }
   else if (!strcmp(name, "hr")) { p = gas->hr; r = nlay; }
   else if (!strcmp(name, "flux_dn_surf")) { p = gas->fds; r = 1; }
@@ -2584,18 +2761,26 @@ static int sweep_lw(ecckd_gas* g, Batch& b, const IntervalArgs& ka, const SweepT
                      b.d_sums, b.d_fit);
   b.t_first = g_turn.now();
   ECCKD_CHECK(timer.begin(stream));
+  // a gas that holds its operands line-blocked (ecckd_gas::bg_blk) is swept from them; `aligned` holds for it by construction
+  const bool blk = g->bg_blk != nullptr && b.fast_path;
 #define ECCKD_LW_MIRROR(NL, P32)                                                                                          \
-  hipLaunchKernelGGL((k_rt_lw_bb_mirror<NL, P32>), dim3(mirror_grid), dim3(RT_THREADS), 0, stream, g->n, n, b.nchunks, b.d_iv, \
-                     g->planck_hl, g->bg_od, (const float_x2*)g->bg_pair, b.d_fit, b.d_part)
+  do {                                                                                                                    \
+    if (blk)                                                                                                              \
+      hipLaunchKernelGGL((k_rt_lw_bb_mirror<NL, P32, true>), dim3(mirror_grid), dim3(RT_THREADS), 0, stream, g->n, n, b.nchunks, b.d_iv, \
+                         g->planck_blk, P32 ? nullptr : (const double*)g->bg_blk, P32 ? (const float_x2*)g->bg_blk : nullptr, b.d_fit, b.d_part); \
+    else                                                                                                                  \
+      hipLaunchKernelGGL((k_rt_lw_bb_mirror<NL, P32, false>), dim3(mirror_grid), dim3(RT_THREADS), 0, stream, g->n, n, b.nchunks, b.d_iv, \
+                         g->planck_hl, g->bg_od, (const float_x2*)g->bg_pair, b.d_fit, b.d_part);                        \
+  } while (0)
   // a block per chunk.  (ECCKD_RT_PERSISTENT: one resident round of blocks, each taking every mirror_grid-th chunk - measured
   // SLOWER on a partition of unequal intervals, 1 069 against 1 015 us per pass of 38 intervals over 7.2e6 points, equal on
   // equal intervals: the hardware's block dispatcher balances chunks of one to three tiles better than a fixed deal.)
   static const bool persistent = std::getenv("ECCKD_RT_PERSISTENT") != nullptr;
   const unsigned mirror_grid = (unsigned)(persistent ? std::min<long long>(b.nchunks, b.target_blocks) : b.nchunks);
   if (b.fast_path && nlay == 54) {
-    if (g->bg_pair) ECCKD_LW_MIRROR(54, true); else ECCKD_LW_MIRROR(54, false);
+    if (g->bg_as_pairs()) ECCKD_LW_MIRROR(54, true); else ECCKD_LW_MIRROR(54, false);
   } else if (b.fast_path && nlay == 30) {
-    if (g->bg_pair) ECCKD_LW_MIRROR(30, true); else ECCKD_LW_MIRROR(30, false);
+    if (g->bg_as_pairs()) ECCKD_LW_MIRROR(30, true); else ECCKD_LW_MIRROR(30, false);
 #undef ECCKD_LW_MIRROR
   } else {
     ECCKD_CHECK(gas_bg_rows(g));
@@ -2689,7 +2874,7 @@ static int eval_intervals(ecckd_gas* g, std::vector<Interval>& iv, double* error
   const long long gran = (!g->do_sw && b.fast_path) ? RT_THREADS / 2 : RT_THREADS;
   const auto on_line = [](const void* q) { return (uintptr_t)q % (ecckd::chunk_layout::LINE_PTS * sizeof(double)) == 0; };
   const bool aligned = !g->do_sw && b.fast_path && g->chunks_from_line && g->n % ecckd::chunk_layout::LINE_PTS == 0 &&
-                       on_line(g->planck_hl) && on_line(g->bg_od) && on_line(g->bg_pair);
+                       (g->bg_blk /* made only where all of this held */ || (on_line(g->planck_hl) && on_line(g->bg_od) && on_line(g->bg_pair)));
   b.nchunks = 0;
   for (int k = 0; k < n; ++k) {
     const ecckd::chunk_layout::Layout lay = ecckd::chunk_layout::of_interval(iv[k].i1, iv[k].i2, b.target_blocks, gran, aligned);
@@ -2828,7 +3013,7 @@ int ecckd_gas_sweep_bytes_per_point(ecckd_gas* gas, double* bytes) {
   ECCKD_REQUIRE(gas && bytes, "ecckd_gas_sweep_bytes_per_point: NULL argument");
   const int nlay = gas->nlay;
   if (gas->do_sw) *bytes = (double)(nlay + 1) * 8.0;
-  else *bytes = (double)(nlay + 1) * 8.0 + (double)nlay * (gas->bg_pair ? 4.0 : 8.0);
+  else *bytes = (double)(nlay + 1) * 8.0 + (double)nlay * (gas->bg_as_pairs() ? 4.0 : 8.0);
   return ECCKD_OK;
 }
 

@@ -64,7 +64,16 @@ struct ecckd_gas {
   // false with ECCKD_RT_UNALIGNED set when the gas was made (A/B knob: the chunks are counted from the first point itself).
   // Fixed for the life of the gas: the memo of interval errors holds the bits of one layout.
   bool chunks_from_line = false;
-  double* w1 = nullptr;         // [nlay][n]  metric * weight          (log: log(metric)*weight)
+  // longwave, where the aligned mirror sweep runs (nlay 54 or 30, chunks_from_line, rows of whole lines on a line, 32-bit
+  // offsets; not with ECCKD_RT_ROWMAJOR set when the gas was made: the A/B knob): the sweep's operands line-blocked
+  // (sweep_layout.hpp).  The background is then held blocked ONLY - bg_od / bg_pair are released, gas_bg_rows rebuilds bg_od on
+  // demand -; the Planck matrix stays row-major for the sums and the views, its blocked copy is shared by the gases that
+  // share the matrix (the context's table, planck_blk_*) and is not among `blocks`.
+  void* bg_blk = nullptr;       // [n/16][nlay][16] DOUBLE or, bg_blk_pairs, [n/16][nlay/2][16] FLOAT pairs
+  bool bg_blk_pairs = false;
+  double* planck_blk = nullptr; // [n/16][nlay+1][16]
+  bool bg_as_pairs() const { return bg_pair != nullptr || (bg_blk && bg_blk_pairs); }   // what the sweep reads: 4 or 8 bytes per value
+  double* w1 = nullptr;        // [nlay][n]  metric * weight          (log: log(metric)*weight)
   double* w2 = nullptr;         // [nlay][n]  log only: weight of the denominator where metric > 0
   double* cnt = nullptr;        // [nlay][n]  log only: 1 where metric > 0
   double* hr = nullptr;         // [nlay][n]

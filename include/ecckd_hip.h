@@ -195,7 +195,8 @@ int ecckd_gas_set_band_albedo(ecckd_gas* gas, double surf_albedo);
 int ecckd_gas_destroy(ecckd_gas* gas);
 /* device view of a resident array: "planck_hl", "bg_optical_depth", "weighted_metric",
  * "hr", "flux_dn_surf", "flux_up_toa", "wavenumber", "d_wavenumber" (LW), "ssi", "hr_low",
- * "hr_high", "flux_extras" (SW) */
+ * "hr_high", "flux_extras" (SW); "planck_hl_blocked": the line-blocked copy of planck_hl the 54- / 30-layer
+ * longwave sweep reads, [nwav/16][nlay+1][16] as it lies in memory (an error for a gas that holds none) */
 int ecckd_gas_view(ecckd_gas* gas, const char* name, const double** d_ptr, size_t* rows, size_t* cols);
 int ecckd_gas_layer_weight(ecckd_gas* gas, double* h_layer_weight);
 /* total_comp_cost of find_g_points.cpp:320 accumulated by ecckd_calc_error_batch */

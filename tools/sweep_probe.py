@@ -2,7 +2,9 @@
 few single intervals, timed by the library's HIP events around every launch (ECCKD_BG64=1: with DOUBLE background rows;
 ECCKD_RT_PERSISTENT=1: one resident round of blocks walking the chunks; ECCKD_RT_UNALIGNED=1: chunks counted from the
 interval's first point instead of the 128-byte line below it).
-usage: python tools/sweep_probe.py [nwav] [--i1-mod R] [--only SUBSTRING]
+usage: python tools/sweep_probe.py [nwav] [--i1-mod R] [--only SUBSTRING] [--rowmajor | --blocked]
+  --rowmajor   make the gas with ECCKD_RT_ROWMAJOR=1: row-major Planck and background matrices and the row-major sweep
+  --blocked    make it without: the sweep's operands line-blocked (csrc/sweep_layout.hpp), whatever the environment says
   --i1-mod R   move every interval, keeping its length (the spectrum's end cuts it), so that its first sorted index is R
                modulo 16 (16 doubles = one 128-byte line): R = 0 starts every row load of every tile on a line, R = 1 is the
                same batch one point on
@@ -24,6 +26,12 @@ if "--only" in argv:
     k = argv.index("--only")
     only = argv[k + 1]
     del argv[k:k + 2]
+if "--rowmajor" in argv:
+    argv.remove("--rowmajor")
+    os.environ["ECCKD_RT_ROWMAJOR"] = "1"
+if "--blocked" in argv:
+    argv.remove("--blocked")
+    os.environ.pop("ECCKD_RT_ROWMAJOR", None)
 nwav, nlay = int(argv[0]) if argv else 7200000, 54
 
 
@@ -53,7 +61,12 @@ rank, _ = api.stable_argsort_bands(ctx, key, [0], [nwav - 1], want_ordered=False
 gas = api.GasLW(ctx, p, syn.temperature_profile(p), wn, dwn, rank, od, bg, "transmission", flux_weight=0.0)
 bpp = gas.sweep_bytes_per_point()
 cuts = np.linspace(0.0, 1.0, 39) ** 1.5
-out = {"bytes_per_point": bpp, "i1_mod_16": i1_mod}
+try:
+    gas.view_ptr("planck_hl_blocked")
+    layout = "blocked"
+except api.EcckdError:
+    layout = "row-major"
+out = {"bytes_per_point": bpp, "i1_mod_16": i1_mod, "layout": layout}
 even = np.linspace(0.0, 1.0, 39)
 for label, (b1, b2) in (("whole partition, 38 intervals", (cuts[:-1], cuts[1:])), ("whole partition, 38 equal intervals", (even[:-1], even[1:])),
                         ("whole partition, 1 interval", ([0.0], [1.0])), ("whole partition, 4 equal intervals", ([0.0, 0.25, 0.5, 0.75], [0.25, 0.5, 0.75, 1.0])),
