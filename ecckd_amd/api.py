@@ -324,11 +324,15 @@ def planck_hl_sorted(ctx, temperature_hl, wavenumber, d_wavenumber, rank, out=No
 
 class GasLW:
     """A prepared longwave gas (ecckd_gas_create_lw): find_g_points.cpp:872-1150 done once on
-    the device, then batched interval errors (CkdEquipartition::calc_error, :291-405)."""
+    the device, then batched interval errors (CkdEquipartition::calc_error, :291-405).
+
+    The background: the matrix bg_optical_depth, or bg_sources = [(optical depth, scaling profile), ...], the spectra it is
+    merged from with their merge_scaling profiles (ecckd_gas_create_lw_merged: the gas that merge_spectrum's matrix, source
+    after source, would give, without that matrix); an empty list is no background."""
 
     def __init__(self, ctx, pressure_hl, temperature_hl, wavenumber, d_wavenumber, rank, optical_depth,
                  bg_optical_depth=None, averaging_method="transmission", flux_weight=0.02, min_pressure=0.0,
-                 planck_hl_reuse=None):
+                 planck_hl_reuse=None, bg_sources=None):
         self.ctx = ctx
         self.lib = ctx.lib
         p = np.ascontiguousarray(pressure_hl, dtype=np.float64)
@@ -343,8 +347,28 @@ class GasLW:
             raise EcckdError(_lib.PARAMETER_ERROR, "background optical depth must match the target's layout")
         if averaging_method not in _lib.AVG:
             raise EcckdError(_lib.PARAMETER_ERROR, f'Averaging method "{averaging_method}" not understood')
+        if bg_sources is not None and bg_optical_depth is not None:
+            raise EcckdError(_lib.PARAMETER_ERROR, "give the background as bg_optical_depth or as bg_sources, not both")
         h = C.c_void_p()
         ctx.fence_from_torch()
+        if bg_sources is not None:
+            ods = [od for od, _ in bg_sources]
+            nbg = len(ods)
+            for od in ods:
+                if tuple(od.shape) != tuple(optical_depth.shape) or od.stride(1) != 1:
+                    raise EcckdError(_lib.PARAMETER_ERROR, "every background source must be (nlay, nwav) with contiguous rows")
+            scale = np.ascontiguousarray(np.stack([np.broadcast_to(_f64c(sp), (self.nlay,)) for _, sp in bg_sources]) if nbg
+                                         else np.zeros((0, self.nlay)))
+            check(self.lib.ecckd_gas_create_lw_merged(
+                ctx.handle, self.nlay, self.nwav, _hptr(p), _hptr(t), _dptr(wavenumber), _dptr(d_wavenumber), _dptr(rank), nbg,
+                (C.c_void_p * nbg)(*[od.data_ptr() for od in ods]), (C.c_int * nbg)(*[_od_type(od) for od in ods]),
+                (C.c_size_t * nbg)(*[od.stride(0) if self.nlay > 1 else self.nwav for od in ods]), _hptr(scale),
+                _dptr(optical_depth), _od_type(optical_depth), stride, _lib.AVG[averaging_method],
+                float(flux_weight), float(min_pressure),
+                C.c_void_p(planck_hl_reuse) if planck_hl_reuse else None, C.byref(h)))
+            self.handle = h
+            ctx._children.add(self)
+            return
         check(self.lib.ecckd_gas_create_lw(
             ctx.handle, self.nlay, self.nwav, _hptr(p), _hptr(t), _dptr(wavenumber), _dptr(d_wavenumber),
             _dptr(rank), _dptr(bg_optical_depth) if bg_optical_depth is not None else None,

@@ -220,6 +220,22 @@ k_gas_prep_lw(int nlay, size_t n, size_t src_stride, int method,
 }
 
 
+// The second half of the scatter kernels: the filled tile leaves column by column.  my_rank: the rank of the tile's point
+// `lane`, -1 past the end.
+template <int NLAY, int PARTS, typename T>
+__device__ __forceinline__ void scatter_tile_out(const T (&s_tile)[NLAY][65], int my_rank, size_t npad, T* __restrict__ dst) {
+  constexpr int HP = NLAY / PARTS;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  const size_t part = (size_t)(lane / HP) * npad;
+  const int within = lane % HP;
+  for (int p = wave; p < 64; p += 4) {
+    const int r = __shfl(my_rank, p, 64);
+    if (r < 0) break;
+    if (lane < NLAY) dst[(part + (size_t)r) * HP + within] = s_tile[lane][p];
+  }
+}
+
 // K4 fast path, step 1: transposing scatter.  src is (layer, wavenumber) in ORIGINAL order; the column of wavenumber j goes to
 // its SORTED position rank[j], as PARTS runs of NLAY / PARTS layers: dst[PARTS][npad][NLAY / PARTS] (npad: n rounded up to whole
 // waves).  Reads are coalesced rows through an LDS tile, each point's values leave as one wave store of PARTS contiguous
@@ -229,7 +245,6 @@ template <int NLAY, typename SrcT, int PARTS>
 __global__ void __launch_bounds__(256)
 k_scatter_column_halves(size_t n, size_t npad, size_t src_stride, const int32_t* __restrict__ rank, const SrcT* __restrict__ src,
                         SrcT* __restrict__ dst) {
-  constexpr int HP = NLAY / PARTS;
   __shared__ SrcT s_tile[NLAY][65];
   const size_t j0 = (size_t)blockIdx.x * 64;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -239,15 +254,68 @@ k_scatter_column_halves(size_t n, size_t npad, size_t src_stride, const int32_t*
   }
   // the ranks of the tile's 64 points: one coalesced load per wave, handed out lane by lane below (a load per point inside the
   // loop made every store wait for its own memory latency)
-  const int my_rank = j0 + lane < n ? rank[j0 + lane] : -1;
-  __syncthreads();
-  const size_t part = (size_t)(lane / HP) * npad;
-  const int within = lane % HP;
-  for (int p = wave; p < 64; p += 4) {
-    const int r = __shfl(my_rank, p, 64);
-    if (r < 0) break;
-    if (lane < NLAY) dst[(part + (size_t)r) * HP + within] = s_tile[lane][p];
+  scatter_tile_out<NLAY, PARTS>(s_tile, j0 + lane < n ? rank[j0 + lane] : -1, npad, dst);
+}
+
+// The background of a longwave gas as a list of spectra that are merged on the way (ecckd_gas_create_lw_merged): by value in
+// the kernel arguments, indexed with the (uniform) source counter.
+constexpr int BG_MAX_SOURCES = 16;
+struct BgSources {
+  const void* od[BG_MAX_SOURCES];
+  unsigned long long stride[BG_MAX_SOURCES];
+  int type[BG_MAX_SOURCES];
+};
+
+// k_scatter_column_halves<NLAY, double, PARTS> of the merged background that is never stored: the tile is filled with
+// sum over the sources, in order, of od_s[l][j] * scale[s][l] - the value ecckd_merge_spectrum_dev leaves source after source
+// (read_merged_spectrum.cpp:152-166): the product is rounded, then the sum, the first source assigns.  Written with * and +
+// under `fp contract(off)`: see the comment above merged_point in merge.hip.  A wave takes every fourth layer as above; the
+// loop over its layers is the inner, unrolled one, so the loads of one source are all out before the first is used.
+template <int NLAY, int PARTS>
+__global__ void __launch_bounds__(256)
+k_scatter_merged_halves(size_t n, size_t npad, const int32_t* __restrict__ rank, const BgSources src, int nsrc,
+                        const double* __restrict__ scale /* [nsrc][NLAY] */, double* __restrict__ dst) {
+#pragma clang fp contract(off)
+  constexpr int LPW = (NLAY + 3) / 4;           // layers per wave
+  __shared__ double s_tile[NLAY][65];
+  const size_t j0 = (size_t)blockIdx.x * 64;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const size_t j = j0 + lane;
+  const size_t jj = j < n ? j : n - 1;
+  double tau[LPW];
+#pragma unroll
+  for (int k = 0; k < LPW; ++k) tau[k] = 0.0;
+  for (int s = 0; s < nsrc; ++s) {
+    const size_t stride = (size_t)src.stride[s];
+    const double* __restrict__ sc = scale + (size_t)s * NLAY;
+    double x[LPW];
+    if (src.type[s] == ECCKD_F64) {
+      const double* __restrict__ od = static_cast<const double*>(src.od[s]);
+#pragma unroll
+      for (int k = 0; k < LPW; ++k) {
+        const int l = wave + 4 * k < NLAY ? wave + 4 * k : wave;
+        x[k] = od[(size_t)l * stride + jj];
+      }
+    } else {
+      const float* __restrict__ od = static_cast<const float*>(src.od[s]);
+#pragma unroll
+      for (int k = 0; k < LPW; ++k) {
+        const int l = wave + 4 * k < NLAY ? wave + 4 * k : wave;
+        x[k] = (double)od[(size_t)l * stride + jj];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < LPW; ++k) {
+      const int l = wave + 4 * k < NLAY ? wave + 4 * k : wave;
+      const double v = x[k] * sc[l];
+      tau[k] = s == 0 ? v : tau[k] + v;
+    }
   }
+#pragma unroll
+  for (int k = 0; k < LPW; ++k)
+    if (wave + 4 * k < NLAY) s_tile[wave + 4 * k][lane] = tau[k];
+  scatter_tile_out<NLAY, PARTS>(s_tile, j < n ? rank[j] : -1, npad, dst);
 }
 
 // K4 mirror path (same idea as K5c's, see k_rt_lw_bb_mirror): a pair of waves shares 64 points, the even
@@ -259,7 +327,12 @@ k_scatter_column_halves(size_t n, size_t npad, size_t src_stride, const int32_t*
 // per-lane state of the one-wave version -> two waves per SIMD with half as long dependency chains.
 // REUSE: the Planck matrix of an earlier gas is read instead of evaluated (find_g_points.cpp:970-984 keeps the first
 // gas's matrix for all later gases); its rows are fetched with the other inputs and planck_hl is not written.
-template <int NLAY, typename BgT, typename OdT, bool REUSE>
+// BLK: the background leaves as the sweep reads it, line-blocked (sweep_layout.hpp) - DOUBLE rows into bg_blk [n/16][NLAY][16]
+// instead of bg_od, FLOAT pairs into bg_blk [n/16][NLAY/2][16] instead of bg_pair - and a Planck matrix evaluated here goes
+// to planck_blk [n/16][NLAY+1][16] as well as to the row-major planck_hl (the sums, the fit and the views read that one).  A
+// wave's 64 consecutive ranks are four whole lines of every row.  A DOUBLE background is tested on the way for values that
+// are no floats (the predicate of k_pack_bg32): a lane that met one stores 1 to *not_float.  n is a multiple of 16.
+template <int NLAY, typename BgT, typename OdT, bool REUSE, bool BLK = false>
 __global__ void __launch_bounds__(PREP_THREADS, 2)
 k_gas_prep_lw_mirror(size_t n, int method, const int32_t* __restrict__ ireorder, const double* __restrict__ hk,
                      const double* __restrict__ conv, const double* __restrict__ wn, const double* __restrict__ dwn,
@@ -271,9 +344,13 @@ k_gas_prep_lw_mirror(size_t n, int method, const int32_t* __restrict__ ireorder,
                      double* __restrict__ wave_part /* [3*NLAY+2][nw]: sums over this wave's 64 points of every summable row */,
                      size_t nw,
                      float_x2_store* __restrict__ bg_pair /* FLOAT background only, or NULL: the rows as FLOAT pairs (layers 2p, 2p+1
-                                                             of a point side by side) INSTEAD of the DOUBLE rows bg_od */) {
+                                                             of a point side by side) INSTEAD of the DOUBLE rows bg_od */,
+                     void* __restrict__ bg_blk = nullptr, double* __restrict__ planck_blk = nullptr,
+                     int* __restrict__ not_float = nullptr /* BLK only */) {
   static_assert(NLAY % 2 == 0 && PREP_THREADS == 256, "two wave pairs per block, equal halves");
+  namespace sl = ecckd::sweep_layout;
   constexpr int H = NLAY / 2;
+  constexpr bool BLK_PAIRS = BLK && sizeof(BgT) == 4;     // a FLOAT (or no) background on the blocked path always leaves as pairs
   constexpr bool STAGED = sizeof(OdT) == 4;   // the columns arrive in two runs of H layers, see below (always, on this path)
   __shared__ double s_x[4][64];
   // Row sums over the wave's 64 points, formed while the values are still in registers (they used to be re-read from
@@ -296,6 +373,11 @@ k_gas_prep_lw_mirror(size_t n, int method, const int32_t* __restrict__ ireorder,
   if (live && half == 0) { wn_sorted[i] = w; dwn_sorted[i] = dw; }
   const double freq = ecckd::wn_to_freq(w);
   const double pref = ecckd::planck_pref(dw, freq);
+  // BLK: the byte offset of this lane's point in row 0 of the blocked matrices, one register each (a gas is blocked only
+  // where sl::fits_32bit); row r is r * LINE_BYTES further on
+  const unsigned at_bg = BLK ? (unsigned)sl::point_base(BLK_PAIRS ? H : NLAY, ii) : 0;
+  const unsigned at_pl = BLK && !REUSE ? (unsigned)sl::point_base(NLAY + 1, ii) : 0;
+  const auto blk_row = [](void* base, unsigned at, int r) { return (char*)base + ((size_t)at + (size_t)r * sl::LINE_BYTES); };
   const BgT* bgc = bg_col && !STAGED ? bg_col + ii * NLAY : nullptr;
   const OdT* odc = od_col + (STAGED ? 0 : ii * NLAY);
   const size_t wid = (size_t)blockIdx.x * 2 + pair;          // index of this pair's 64 points among the 64-point groups
@@ -424,9 +506,24 @@ k_gas_prep_lw_mirror(size_t n, int method, const int32_t* __restrict__ ireorder,
     }
   }
   __builtin_amdgcn_s_setprio(0);
+  if (BLK && sizeof(BgT) == 8) {
+    // what k_pack_bg32 asks of every value: it is a float, and not a subnormal one (a lane past the end holds the last point's)
+    bool bad = false;
+#pragma unroll
+    for (int l = 0; l < H; ++l) {
+      const double x = (double)bg_in[l];
+      const float f = (float)x;
+      bad |= !((double)f == x);
+      bad |= f != 0.f && fabsf(f) < 1.17549435e-38f;
+    }
+    if (bad) *not_float = 1;      // every writer writes the same value
+  }
   int lev_near = half ? NLAY : 0;
   double b_near = planck(lev_near);
-  if (!REUSE && live) planck_hl[(size_t)lev_near * n + i] = b_near;
+  if (!REUSE && live) {
+    planck_hl[(size_t)lev_near * n + i] = b_near;
+    if (BLK) *(double*)blk_row(planck_blk, at_pl, lev_near) = b_near;
+  }
   double flux = half ? b_near : 0.0;           // surface: emissivity 1 (radiative_transfer_lw.cpp:52-53)
   f1[0] = flux;
 #pragma unroll
@@ -454,22 +551,26 @@ k_gas_prep_lw_mirror(size_t n, int method, const int32_t* __restrict__ ireorder,
     if (live) {
       const size_t o = (size_t)L * n + i;
       // written once, read by later kernels: streaming stores
-      if (sizeof(BgT) == 4 && bg_pair) {
+      if (BLK_PAIRS || (sizeof(BgT) == 4 && bg_pair)) {
         // the background as the sweep reads it (k_rt_lw_bb_mirror<.., true>): a pair is complete at every second layer of the
         // half column - the even wave has met its layers in the pair's order, the odd wave the other way round; the middle
         // pair of an odd half belongs to both waves, each stores its own float
+        float_x2_store* const pr = BLK_PAIRS ? (float_x2_store*)blk_row(bg_blk, at_bg, L / 2) : &bg_pair[(size_t)(L / 2) * n + i];
         if (l & 1) {
           float_x2_store v;
           v.x = half ? (float)bg_in[l] : (float)bg_in[l - 1];
           v.y = half ? (float)bg_in[l - 1] : (float)bg_in[l];
-          __builtin_nontemporal_store(v, &bg_pair[(size_t)(L / 2) * n + i]);
+          __builtin_nontemporal_store(v, pr);
         } else if (l == H - 1) {
-          ((float*)&bg_pair[(size_t)(L / 2) * n + i])[L & 1] = (float)bg_in[l];
+          ((float*)pr)[L & 1] = (float)bg_in[l];
         }
       } else {
-        __builtin_nontemporal_store(bg, &bg_od[o]);
+        __builtin_nontemporal_store(bg, BLK ? (double*)blk_row(bg_blk, at_bg, L) : &bg_od[o]);
       }
-      if (!REUSE) __builtin_nontemporal_store(b_far, &planck_hl[(size_t)lev_far * n + i]);   // level NLAY/2 is written by both waves with the same bits
+      if (!REUSE) {
+        __builtin_nontemporal_store(b_far, &planck_hl[(size_t)lev_far * n + i]);   // level NLAY/2 is written by both waves with the same bits
+        if (BLK) __builtin_nontemporal_store(b_far, (double*)blk_row(planck_blk, at_pl, lev_far));
+      }
       __builtin_nontemporal_store(m * (half ? b_near : b_far), &w1[o]);          // weight = Planck function at the base of the layer
     }
     push(m * (half ? b_near : b_far));
@@ -930,6 +1031,23 @@ k_unpack_bg32_blocked(int npair, size_t n, const float_x2_store* __restrict__ pa
     const float_x2_store v = at[(size_t)p * sl::LINE_PTS];
     bg_od[(size_t)(2 * p) * n + i] = (double)v.x;
     bg_od[(size_t)(2 * p + 1) * n + i] = (double)v.y;
+  }
+}
+
+// ... and its inverse: the line-blocked FLOAT pairs from the line-blocked DOUBLE rows [n / 16][2 npair][16] that the
+// preparation wrote, once its test has found every value to be a float (ecckd_gas_create_lw): one pass.
+__global__ void __launch_bounds__(256)
+k_pack_bg32_blocked(int npair, size_t n, const double* __restrict__ bg_blk, float_x2_store* __restrict__ pairs) {
+  namespace sl = ecckd::sweep_layout;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double* __restrict__ from = bg_blk + sl::point_base(2 * npair, i) / sl::ELEM_BYTES;
+  float_x2_store* __restrict__ to = pairs + sl::point_base(npair, i) / sl::ELEM_BYTES;
+  for (int p = 0; p < npair; ++p) {
+    float_x2_store v;
+    v.x = (float)from[(size_t)(2 * p) * sl::LINE_PTS];
+    v.y = (float)from[(size_t)(2 * p + 1) * sl::LINE_PTS];
+    to[(size_t)p * sl::LINE_PTS] = v;
   }
 }
 
@@ -2054,34 +2172,46 @@ static int gas_bg_rows(ecckd_gas* g) {
 // DOUBLE rows (one pass, every line read once and stored once), after which the row-major matrices are released; for its
 // duration the gas holds its background twice.  The Planck matrix stays (the sums and the fit read it, and the views); its
 // blocked copy is shared through the context's table by the gases that share the matrix.  ECCKD_RT_ROWMAJOR (read here, when
-// the gas is made): no blocked operands, the row-major sweep - A/B knob and fallback.
+// the gas is made): no blocked operands, the row-major sweep - A/B knob and fallback.  Where the column-staged preparation
+// kernel has written the blocked operands itself (sweep_layout::prep_writes_blocked) there is nothing left to do here.
+static void gas_reblock(ecckd_gas* g, unsigned rows, const void* src, void* dst) {
+  hipLaunchKernelGGL(k_reblock<true>, dim3((unsigned)(((size_t)rows * g->n + 255) / 256)), dim3(256), 0, g->ctx->stream, rows, g->n,
+                     (const unsigned long long*)src, (unsigned long long*)dst);
+}
+
+// g->planck_blk: the blocked copy that the context's table holds of a reused matrix, or a new one, registered.  A new one is
+// filled here from g->planck_hl unless the preparation kernel is about to write it (prep_fills: only a matrix the gas
+// evaluates itself).
+static int gas_planck_blocked(ecckd_gas* g, bool planck_reused, bool prep_fills) {
+  namespace sl = ecckd::sweep_layout;
+  ecckd_ctx* ctx = g->ctx;
+  double* shared = planck_reused ? planck_blk_attach(ctx, g->planck_hl) : nullptr;
+  if (shared) { g->planck_blk = shared; return ECCKD_OK; }
+  void* mine = nullptr;
+  ECCKD_HIP_CHECK(ecckd::dev_malloc(ctx, &mine, (size_t)sl::bytes((unsigned)g->nlay + 1, g->n)));
+  planck_blk_register(ctx, planck_reused ? nullptr : g->planck_hl, mine);      // from here on gas_free lets go of it
+  g->planck_blk = (double*)mine;
+  if (planck_reused || !prep_fills) {
+    gas_reblock(g, (unsigned)g->nlay + 1, g->planck_hl, mine);
+    ECCKD_HIP_CHECK(hipGetLastError());
+  }
+  return ECCKD_OK;
+}
+
 static int gas_block_operands(ecckd_gas* g, bool planck_reused) {
   namespace sl = ecckd::sweep_layout;
   ecckd_ctx* ctx = g->ctx;
   const size_t n = g->n;
-  const unsigned nlay = (unsigned)g->nlay, nhl = nlay + 1;
-  const auto on_line = [](const void* q) { return (uintptr_t)q % sl::LINE_BYTES == 0; };
-  if (!(nlay == 54 || nlay == 30) || !g->chunks_from_line || std::getenv("ECCKD_RT_ROWMAJOR") != nullptr) return ECCKD_OK;
-  if (!sl::whole_lines(n) || !sl::fits_32bit(nhl, n) || !on_line(g->planck_hl) || !on_line(g->bg_od) || !on_line(g->bg_pair)) return ECCKD_OK;
-  const auto reblock = [&](unsigned rows, const void* src, void* dst) {
-    hipLaunchKernelGGL(k_reblock<true>, dim3((unsigned)(((size_t)rows * n + 255) / 256)), dim3(256), 0, ctx->stream, rows, n,
-                       (const unsigned long long*)src, (unsigned long long*)dst);
-  };
-  double* shared = planck_reused ? planck_blk_attach(ctx, g->planck_hl) : nullptr;
-  if (shared) g->planck_blk = shared;
-  else {
-    void* mine = nullptr;
-    ECCKD_HIP_CHECK(ecckd::dev_malloc(ctx, &mine, (size_t)sl::bytes(nhl, n)));
-    planck_blk_register(ctx, planck_reused ? nullptr : g->planck_hl, mine);      // from here on gas_free lets go of it
-    g->planck_blk = (double*)mine;
-    reblock(nhl, g->planck_hl, mine);
-    ECCKD_HIP_CHECK(hipGetLastError());
-  }
+  const unsigned nlay = (unsigned)g->nlay;
+  if (g->bg_blk) return ECCKD_OK;           // the preparation has written them blocked (ecckd_gas_create_lw)
+  if (!sl::gas_can_block(g->nlay, g->chunks_from_line, std::getenv("ECCKD_RT_ROWMAJOR") != nullptr, n)) return ECCKD_OK;
+  if (!sl::on_line(g->planck_hl) || !sl::on_line(g->bg_od) || !sl::on_line(g->bg_pair)) return ECCKD_OK;
+  ECCKD_CHECK(gas_planck_blocked(g, planck_reused, false));
   const bool pairs = g->bg_pair != nullptr;
   const unsigned bg_rows = pairs ? nlay / 2 : nlay;
   void* blocked = nullptr;
   ECCKD_HIP_CHECK(g->alloc(&blocked, (size_t)sl::bytes(bg_rows, n)));
-  reblock(bg_rows, pairs ? (const void*)g->bg_pair : (const void*)g->bg_od, blocked);
+  gas_reblock(g, bg_rows, pairs ? (const void*)g->bg_pair : (const void*)g->bg_od, blocked);
   ECCKD_HIP_CHECK(hipGetLastError());
   ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   g->bg_blk = blocked;
@@ -2100,13 +2230,14 @@ struct Temps {
   ecckd_ctx* ctx;
   void *od_col = nullptr, *bg_col = nullptr;   // the columns of the target and the background, in rank order (scatter_columns)
   void* wave_part = nullptr;                   // per-wave row sums left by K4, combined into the tile sums (gas_sum_rows)
+  void* bg_scale = nullptr;                    // the factors [nsrc][nlay] of a background that the scatter merges
   void drop(void*& q) {                        // the caller has synchronised the stream
     if (q) ecckd::dev_release(ctx, q);
     q = nullptr;
   }
-  void drop_all() { drop(od_col); drop(bg_col); drop(wave_part); }
+  void drop_all() { drop(od_col); drop(bg_col); drop(wave_part); drop(bg_scale); }
   ~Temps() {
-    if (!od_col && !bg_col && !wave_part) return;
+    if (!od_col && !bg_col && !wave_part && !bg_scale) return;
     (void)hipStreamSynchronize(ctx->stream);
     drop_all();
   }
@@ -2194,17 +2325,28 @@ static int invert_rank(ecckd_ctx* ctx, const char* who, size_t nwav, const int32
 
 // The 54-layer columns of the FLOAT target spectrum and of the background (if any) scattered into rank order, in PARTS runs
 // of 54 / PARTS layers, [PARTS][ncol][54 / PARTS] with ncol = nwav rounded up to 64: K4 stages them through LDS.
+// The background: the matrix d_bg_od, or (then d_bg_od is NULL) the nsrc spectra of `merged` with the factors
+// h_bg_scale[nsrc][54], merged as they are scattered: DOUBLE columns, and no merged matrix anywhere.
 template <int PARTS>
 static int scatter_columns(Temps& temps, size_t nwav, size_t src_stride, const int32_t* d_rank, const void* d_od,
-                           const void* d_bg_od, bool bg32) {
+                           const void* d_bg_od, bool bg32, const BgSources* merged = nullptr, int nsrc = 0,
+                           const double* h_bg_scale = nullptr) {
   ecckd_ctx* ctx = temps.ctx;
   const unsigned tblocks = (unsigned)((nwav + 63) / 64);
   const size_t ncol = (size_t)tblocks * 64;
   ECCKD_HIP_CHECK(ecckd::dev_malloc(ctx, &temps.od_col, ncol * 54 * sizeof(float)));
-  if (d_bg_od) ECCKD_HIP_CHECK(ecckd::dev_malloc(ctx, &temps.bg_col, ncol * 54 * (bg32 ? sizeof(float) : sizeof(double))));
+  if (d_bg_od || merged) ECCKD_HIP_CHECK(ecckd::dev_malloc(ctx, &temps.bg_col, ncol * 54 * (bg32 ? sizeof(float) : sizeof(double))));
   hipLaunchKernelGGL((k_scatter_column_halves<54, float, PARTS>), dim3(tblocks), dim3(256), 0, ctx->stream, nwav, ncol, src_stride,
                      d_rank, (const float*)d_od, (float*)temps.od_col);
-  if (d_bg_od && bg32)
+  if (merged) {
+    // the factors go to the device once per gas; the caller's table is pageable: the constructor waits for the stream
+    // before it returns
+    const size_t scale_bytes = (size_t)nsrc * 54 * sizeof(double);
+    ECCKD_HIP_CHECK(ecckd::dev_malloc(ctx, &temps.bg_scale, scale_bytes));
+    ECCKD_HIP_CHECK(hipMemcpyAsync(temps.bg_scale, h_bg_scale, scale_bytes, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL((k_scatter_merged_halves<54, PARTS>), dim3(tblocks), dim3(256), 0, ctx->stream, nwav, ncol, d_rank, *merged,
+                       nsrc, (const double*)temps.bg_scale, (double*)temps.bg_col);
+  } else if (d_bg_od && bg32)
     hipLaunchKernelGGL((k_scatter_column_halves<54, float, PARTS>), dim3(tblocks), dim3(256), 0, ctx->stream, nwav, ncol, src_stride,
                        d_rank, (const float*)d_bg_od, (float*)temps.bg_col);
   else if (d_bg_od)
@@ -2341,25 +2483,24 @@ struct WorkLayout {
   double* part(void* work) const { return (double*)((char*)work + iv_bytes + sums_bytes + fit_bytes); }
 };
 
-}  // namespace
+// The column-staged preparation runs: 54 layers, FLOAT target spectrum (as stored in the CKDMIP files), FLOAT or DOUBLE
+// (merged) background, with or without the Planck matrix of an earlier gas, no log metric.
+static bool lw_fast_path(int nlay, int od_type, int averaging_method) {
+  return nlay == 54 && od_type == ECCKD_F32 && averaging_method != ECCKD_AVG_LOGARITHMIC;
+}
 
-extern "C" {
-
-int ecckd_gas_create_lw(ecckd_ctx* ctx, int nlay, size_t nwav, const double* h_pressure_hl,
-                        const double* h_temperature_hl, const double* d_wavenumber,
-                        const double* d_d_wavenumber, const int32_t* d_rank, const void* d_bg_od,
-                        int bg_type, const void* d_od, int od_type, size_t src_stride,
-                        int averaging_method, double flux_weight, double min_pressure,
-                        const double* d_planck_hl_reuse, ecckd_gas** out) {
-  static const char who[] = "ecckd_gas_create_lw";
-  // total-transmission is shortwave-only (fit_optical_depth_lw has no such branch, find_g_points.cpp:101-104)
-  ECCKD_CHECK(gas_check_args(who, ctx, out, nlay, nwav,
-                             h_pressure_hl && h_temperature_hl && d_wavenumber && d_d_wavenumber && d_rank && d_od, od_type,
-                             d_bg_od != nullptr, bg_type, src_stride, averaging_method, ECCKD_AVG_LOGARITHMIC, h_pressure_hl,
-                             h_temperature_hl));
+// The body of the longwave constructors.  The background is the matrix d_bg_od (or none: NULL), or, on the column-staged
+// path only (lw_fast_path), the nsrc spectra of `merged` with the factors h_bg_scale[nsrc][nlay], which the scatter merges:
+// the gas is the one the DOUBLE matrix of their sum would give.  The arguments are checked.
+static int gas_create_lw(const char* who, ecckd_ctx* ctx, int nlay, size_t nwav, const double* h_pressure_hl,
+                         const double* h_temperature_hl, const double* d_wavenumber, const double* d_d_wavenumber,
+                         const int32_t* d_rank, const void* d_bg_od, int bg_type, const BgSources* merged, int nsrc,
+                         const double* h_bg_scale, const void* d_od, int od_type, size_t src_stride, int averaging_method,
+                         double flux_weight, double min_pressure, const double* d_planck_hl_reuse, ecckd_gas** out) {
+  namespace sl = ecckd::sweep_layout;
   ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
   if ((size_t)nlay * 64 * sizeof(double) > 160 * 1024)
-    return ecckd::fail(ECCKD_PARAMETER_ERROR, "ecckd_gas_create_lw: nlay = %d exceeds the supported maximum (320)", nlay);
+    return ecckd::fail(ECCKD_PARAMETER_ERROR, "%s: nlay = %d exceeds the supported maximum (320)", who, nlay);
 
   GasPtr gas = gas_new(ctx, 0, averaging_method, nlay, nwav, flux_weight, h_pressure_hl);
   ecckd_gas* const g = gas.get();
@@ -2373,10 +2514,29 @@ int ecckd_gas_create_lw(ecckd_ctx* ctx, int nlay, size_t nwav, const double* h_p
   // FLOAT background (or none) on the 54-layer path K4 writes them itself INSTEAD of the DOUBLE rows (which are then made on
   // demand only, gas_bg_rows: 3.1 GB less to write and to hold per gas at 7.2e6 points); otherwise the DOUBLE rows are
   // written and k_pack_bg32 tries to pack them below.  ECCKD_BG64: DOUBLE rows only.
-  const bool want_pairs = (nlay == 54 || nlay == 30) && std::getenv("ECCKD_BG64") == nullptr;
-  const bool pairs_in_k4 = want_pairs && nlay == 54 && od_type == ECCKD_F32 && !is_log && (!d_bg_od || bg_type == ECCKD_F32);
-  if (want_pairs) ECCKD_HIP_CHECK(g->alloc(&g->bg_pair, (size_t)(nlay / 2) * nwav * 2 * sizeof(float)));
-  if (!pairs_in_k4) ECCKD_HIP_CHECK(g->alloc(&g->bg_od, mat));
+  const bool has_bg = d_bg_od || merged;
+  const bool bg32 = d_bg_od && bg_type == ECCKD_F32;
+  const bool fast = lw_fast_path(nlay, od_type, averaging_method);
+  const bool bg64_knob = std::getenv("ECCKD_BG64") != nullptr;
+  const bool want_pairs = (nlay == 54 || nlay == 30) && !bg64_knob;
+  const bool pairs_in_k4 = want_pairs && fast && (!has_bg || bg32);
+  // Where the gas will hold its sweep operands line-blocked (gas_block_operands) and K4's column-staged kernel runs, K4
+  // writes them blocked itself - the background blocked ONLY, FLOAT pairs or DOUBLE rows as above, and the Planck matrix it
+  // evaluates in both layouts - and tests a DOUBLE background for values that are no floats on the way: no row-major
+  // background, no k_pack_bg32 and no k_reblock pass.
+  bool prep_blocks = sl::prep_writes_blocked(nlay, od_type == ECCKD_F32, is_log, bg64_knob, g->chunks_from_line,
+                                             std::getenv("ECCKD_RT_ROWMAJOR") != nullptr, nwav) && sl::on_line(g->planck_hl);
+  if (prep_blocks) {
+    ECCKD_HIP_CHECK(g->alloc(&g->bg_blk, (size_t)sl::bytes(pairs_in_k4 ? nlay / 2 : nlay, nwav)));
+    if (!sl::on_line(g->bg_blk)) { g->give_back(g->bg_blk); prep_blocks = false; }
+  }
+  if (prep_blocks) {
+    g->bg_blk_pairs = pairs_in_k4;
+    ECCKD_CHECK(gas_planck_blocked(g, d_planck_hl_reuse != nullptr, true));
+  } else {
+    if (want_pairs) ECCKD_HIP_CHECK(g->alloc(&g->bg_pair, (size_t)(nlay / 2) * nwav * 2 * sizeof(float)));
+    if (!pairs_in_k4) ECCKD_HIP_CHECK(g->alloc(&g->bg_od, mat));
+  }
   ECCKD_HIP_CHECK(g->alloc(&g->w1, mat));
   if (is_log) {
     ECCKD_HIP_CHECK(g->alloc(&g->w2, mat));
@@ -2407,25 +2567,28 @@ int ecckd_gas_create_lw(ecckd_ctx* ctx, int nlay, size_t nwav, const double* h_p
                        (const BG*)d_bg_od, (const OD*)d_od, d_planck_hl_reuse, g->wn_sorted, g->dwn_sorted,   \
                        g->planck_hl, g->bg_od, g->w1, g->w2, g->cnt, g->hr, g->fds, g->fut);                  \
   } while (0)
-  const bool bg32 = d_bg_od && bg_type == ECCKD_F32;
-  // fast path: 54 layers, FLOAT target spectrum (as stored in the CKDMIP files), FLOAT or DOUBLE (merged) background,
-  // with or without the Planck matrix of an earlier gas, no log metric
-  const bool fast = nlay == 54 && od_type == ECCKD_F32 && !is_log;
   Temps temps{ctx};
   if (fast) {
     // the columns in two runs of 27 layers
-    ECCKD_CHECK(scatter_columns<2>(temps, nwav, src_stride, d_rank, d_od, d_bg_od, bg32));
+    ECCKD_CHECK(scatter_columns<2>(temps, nwav, src_stride, d_rank, d_od, d_bg_od, bg32, merged, nsrc, h_bg_scale));
     const size_t nw64 = (nwav + 63) / 64;
     const unsigned fblocks = (unsigned)((nwav + 127) / 128);
     ECCKD_HIP_CHECK(ecckd::dev_malloc(ctx, &temps.wave_part, (size_t)(3 * 54 + 2) * nw64 * sizeof(double)));
-#define LAUNCH_MIRROR(BG, REUSE)                                                                                              \
-  hipLaunchKernelGGL((k_gas_prep_lw_mirror<54, BG, float, REUSE>), dim3(fblocks), dim3(PREP_THREADS), 0, ctx->stream, nwav,    \
-                     averaging_method, g->ireorder, hkd, convd, d_wavenumber, d_d_wavenumber, (const BG*)temps.bg_col,         \
+#define LAUNCH_MIRROR(BG, REUSE, BLK)                                                                                         \
+  hipLaunchKernelGGL((k_gas_prep_lw_mirror<54, BG, float, REUSE, BLK>), dim3(fblocks), dim3(PREP_THREADS), 0, ctx->stream,     \
+                     nwav, averaging_method, g->ireorder, hkd, convd, d_wavenumber, d_d_wavenumber, (const BG*)temps.bg_col,   \
                      (const float*)temps.od_col, d_planck_hl_reuse, g->wn_sorted, g->dwn_sorted, g->planck_hl, g->bg_od,       \
                      g->w1, g->hr, g->fds, g->fut, (double*)temps.wave_part, nw64,                                             \
-                     pairs_in_k4 ? (float_x2_store*)g->bg_pair : nullptr)
-    if (bg32 || !d_bg_od) { if (d_planck_hl_reuse) LAUNCH_MIRROR(float, true); else LAUNCH_MIRROR(float, false); }
-    else { if (d_planck_hl_reuse) LAUNCH_MIRROR(double, true); else LAUNCH_MIRROR(double, false); }
+                     pairs_in_k4 && !(BLK) ? (float_x2_store*)g->bg_pair : nullptr, (BLK) ? g->bg_blk : nullptr,               \
+                     (BLK) ? g->planck_blk : nullptr, (BLK) ? d_flag + 1 : nullptr)
+#define LAUNCH_MIRROR_BG(BG)                                                                   \
+  do {                                                                                         \
+    if (d_planck_hl_reuse) { if (prep_blocks) LAUNCH_MIRROR(BG, true, true); else LAUNCH_MIRROR(BG, true, false); }   \
+    else { if (prep_blocks) LAUNCH_MIRROR(BG, false, true); else LAUNCH_MIRROR(BG, false, false); }                   \
+  } while (0)
+    if (bg32 || !has_bg) LAUNCH_MIRROR_BG(float);
+    else LAUNCH_MIRROR_BG(double);
+#undef LAUNCH_MIRROR_BG
 #undef LAUNCH_MIRROR
     ECCKD_HIP_CHECK(hipGetLastError());
     ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -2444,7 +2607,7 @@ int ecckd_gas_create_lw(ecckd_ctx* ctx, int nlay, size_t nwav, const double* h_p
   // metric > 0 (:87), which K4 has left in w2.  The per-wave sums go back as soon as they are combined.
   ECCKD_CHECK(gas_sum_rows(g, g->planck_hl + nwav, nwav, temps, temps.wave_part != nullptr));
   // FLOAT pairs from the DOUBLE rows where K4 has not written them itself: kept if every value is a float
-  if (want_pairs && !pairs_in_k4) {
+  if (want_pairs && !pairs_in_k4 && !prep_blocks) {
     hipLaunchKernelGGL(k_pack_bg32, dim3((unsigned)((nwav + 255) / 256)), dim3(256), 0, ctx->stream, nlay / 2, nwav,
                        (const double*)g->bg_od, (float_x2_store*)g->bg_pair, d_flag + 1);
     ECCKD_HIP_CHECK(hipGetLastError());
@@ -2453,9 +2616,89 @@ int ecckd_gas_create_lw(ecckd_ctx* ctx, int nlay, size_t nwav, const double* h_p
   ECCKD_HIP_CHECK(hipMemcpyAsync(&not_float, d_flag + 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   if (want_pairs && !pairs_in_k4 && not_float) g->give_back(g->bg_pair);   // a DOUBLE background with values between the floats: the DOUBLE rows serve
+  if (prep_blocks && !pairs_in_k4 && !not_float) {
+    // K4 met floats only in the blocked DOUBLE rows (rare: say a single unscaled FLOAT spectrum handed over as DOUBLE): the
+    // gas ends where k_pack_bg32 would have left it, with the blocked FLOAT pairs
+    float_x2_store* pairs = nullptr;
+    ECCKD_HIP_CHECK(g->alloc(&pairs, (size_t)sl::bytes(nlay / 2, nwav)));
+    hipLaunchKernelGGL(k_pack_bg32_blocked, dim3((unsigned)((nwav + 255) / 256)), dim3(256), 0, ctx->stream, nlay / 2, nwav,
+                       (const double*)g->bg_blk, pairs);
+    ECCKD_HIP_CHECK(hipGetLastError());
+    ECCKD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    g->give_back(g->bg_blk);
+    g->bg_blk = pairs;
+    g->bg_blk_pairs = true;
+  }
   ECCKD_CHECK(gas_block_operands(g, d_planck_hl_reuse != nullptr));
   *out = gas.release();
   return ECCKD_OK;
+}
+
+// What ecckd_gas_create_lw_merged checks of its list of background spectra, in the words of gas_check_args.
+static int check_bg_sources(const char* who, int nbg, const void* const* d_bg_od, const int* bg_type, const size_t* bg_stride,
+                            const double* h_bg_scale, size_t nwav, BgSources& src) {
+  ECCKD_REQUIRE(nbg >= 0 && nbg <= BG_MAX_SOURCES, "%s: nbg (%d) must be between 0 and %d", who, nbg, BG_MAX_SOURCES);
+  ECCKD_REQUIRE(nbg == 0 || (d_bg_od && bg_type && bg_stride && h_bg_scale), "%s: NULL array argument", who);
+  for (int s = 0; s < BG_MAX_SOURCES; ++s) { src.od[s] = nullptr; src.stride[s] = 0; src.type[s] = ECCKD_F64; }
+  for (int s = 0; s < nbg; ++s) {
+    ECCKD_REQUIRE(d_bg_od[s], "%s: d_bg_od[%d] is NULL", who, s);
+    ECCKD_REQUIRE(bg_type[s] == ECCKD_F32 || bg_type[s] == ECCKD_F64, "%s: bg_type[%d] must be 4 or 8", who, s);
+    ECCKD_REQUIRE(bg_stride[s] >= nwav, "%s: bg_stride[%d] (%zu) < nwav (%zu)", who, s, bg_stride[s], nwav);
+    src.od[s] = d_bg_od[s]; src.stride[s] = bg_stride[s]; src.type[s] = bg_type[s];
+  }
+  return ECCKD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ecckd_gas_create_lw(ecckd_ctx* ctx, int nlay, size_t nwav, const double* h_pressure_hl,
+                        const double* h_temperature_hl, const double* d_wavenumber,
+                        const double* d_d_wavenumber, const int32_t* d_rank, const void* d_bg_od,
+                        int bg_type, const void* d_od, int od_type, size_t src_stride,
+                        int averaging_method, double flux_weight, double min_pressure,
+                        const double* d_planck_hl_reuse, ecckd_gas** out) {
+  static const char who[] = "ecckd_gas_create_lw";
+  // total-transmission is shortwave-only (fit_optical_depth_lw has no such branch, find_g_points.cpp:101-104)
+  ECCKD_CHECK(gas_check_args(who, ctx, out, nlay, nwav,
+                             h_pressure_hl && h_temperature_hl && d_wavenumber && d_d_wavenumber && d_rank && d_od, od_type,
+                             d_bg_od != nullptr, bg_type, src_stride, averaging_method, ECCKD_AVG_LOGARITHMIC, h_pressure_hl,
+                             h_temperature_hl));
+  return gas_create_lw(who, ctx, nlay, nwav, h_pressure_hl, h_temperature_hl, d_wavenumber, d_d_wavenumber, d_rank, d_bg_od,
+                       bg_type, nullptr, 0, nullptr, d_od, od_type, src_stride, averaging_method, flux_weight, min_pressure,
+                       d_planck_hl_reuse, out);
+}
+
+int ecckd_gas_create_lw_merged(ecckd_ctx* ctx, int nlay, size_t nwav, const double* h_pressure_hl,
+                               const double* h_temperature_hl, const double* d_wavenumber,
+                               const double* d_d_wavenumber, const int32_t* d_rank, int nbg,
+                               const void* const* d_bg_od, const int* bg_type, const size_t* bg_stride,
+                               const double* h_bg_scale, const void* d_od, int od_type, size_t src_stride,
+                               int averaging_method, double flux_weight, double min_pressure,
+                               const double* d_planck_hl_reuse, ecckd_gas** out) {
+  static const char who[] = "ecckd_gas_create_lw_merged";
+  ECCKD_CHECK(gas_check_args(who, ctx, out, nlay, nwav,
+                             h_pressure_hl && h_temperature_hl && d_wavenumber && d_d_wavenumber && d_rank && d_od, od_type,
+                             false, 0, src_stride, averaging_method, ECCKD_AVG_LOGARITHMIC, h_pressure_hl, h_temperature_hl));
+  BgSources src;
+  ECCKD_CHECK(check_bg_sources(who, nbg, d_bg_od, bg_type, bg_stride, h_bg_scale, nwav, src));
+  const auto create = [&](const void* d_bg, const BgSources* merged) {
+    return gas_create_lw(who, ctx, nlay, nwav, h_pressure_hl, h_temperature_hl, d_wavenumber, d_d_wavenumber, d_rank, d_bg,
+                         ECCKD_F64, merged, nbg, h_bg_scale, d_od, od_type, src_stride, averaging_method, flux_weight,
+                         min_pressure, d_planck_hl_reuse, out);
+  };
+  if (nbg == 0) return create(nullptr, nullptr);
+  if (lw_fast_path(nlay, od_type, averaging_method)) return create(nullptr, &src);
+  // off the column-staged path: the merged matrix in a temporary (the one-pass merge), the constructor, the temporary back
+  ECCKD_HIP_CHECK(hipSetDevice(ctx->device));
+  void* d_merged = nullptr;
+  ECCKD_HIP_CHECK(ecckd::dev_malloc(ctx, &d_merged, (size_t)nlay * src_stride * sizeof(double)));
+  int rc = ecckd_merge_scenario_dev(ctx, nlay, nwav, nbg, d_bg_od, bg_type, bg_stride, h_bg_scale, (double*)d_merged, src_stride);
+  if (rc == ECCKD_OK) rc = create(d_merged, nullptr);
+  (void)hipStreamSynchronize(ctx->stream);
+  ecckd::dev_release(ctx, d_merged);
+  return rc;
 }
 
 

@@ -66,8 +66,8 @@ struct ecckd_gas {
   bool chunks_from_line = false;
   // longwave, where the aligned mirror sweep runs (nlay 54 or 30, chunks_from_line, rows of whole lines on a line, 32-bit
   // offsets; not with ECCKD_RT_ROWMAJOR set when the gas was made: the A/B knob): the sweep's operands line-blocked
-  // (sweep_layout.hpp).  The background is then held blocked ONLY - bg_od / bg_pair are released, gas_bg_rows rebuilds bg_od on
-  // demand -; the Planck matrix stays row-major for the sums and the views, its blocked copy is shared by the gases that
+  // (sweep_layout.hpp).  The background is then held blocked ONLY - bg_od / bg_pair are released, or were never made where the
+  // preparation kernel wrote the blocked matrix itself (ecckd_gas_create_lw); gas_bg_rows rebuilds bg_od on demand -; the Planck matrix stays row-major for the sums and the views, its blocked copy is shared by the gases that
   // share the matrix (the context's table, planck_blk_*) and is not among `blocks`.
   void* bg_blk = nullptr;       // [n/16][nlay][16] DOUBLE or, bg_blk_pairs, [n/16][nlay/2][16] FLOAT pairs
   bool bg_blk_pairs = false;

@@ -39,5 +39,25 @@ ECCKD_SWEEP_HD inline bool whole_lines(unsigned long long n) { return n > 0 && n
 // Every offset of the matrix fits 32 bits: the sweep keeps a lane's offset in one register.
 ECCKD_SWEEP_HD inline bool fits_32bit(unsigned long long rows, unsigned long long n) { return bytes(rows, n) < (1ULL << 32); }
 
+// An address lies on a line: the sweep's tiles start on a line of every row only if the matrices do.
+inline bool on_line(const void* p) { return (unsigned long long)p % LINE_BYTES == 0; }
+
+// A longwave gas of nlay layers and n points may hold the operands of its mirror sweep blocked: the aligned mirror sweep exists
+// for 54 and 30 layers and needs the chunks counted from a line (not ECCKD_RT_UNALIGNED), rows of whole lines and offsets
+// of 32 bits (the Planck matrix, nlay + 1 rows, is the larger one); ECCKD_RT_ROWMAJOR keeps the row-major matrices.  The
+// bases of the matrices must be on_line as well: the caller knows them.
+inline bool gas_can_block(int nlay, bool chunks_from_line, bool rowmajor_knob, unsigned long long n) {
+  return (nlay == 54 || nlay == 30) && chunks_from_line && !rowmajor_knob && whole_lines(n) &&
+         fits_32bit((unsigned long long)nlay + 1, n);
+}
+
+// The gas preparation writes the blocked operands itself (k_gas_prep_lw_mirror<.., true>, find_g.hip) where its column-staged
+// kernel runs - 54 layers, a FLOAT target spectrum, not the logarithmic method - and the gas can be blocked; with ECCKD_BG64
+// the preparation keeps to the row-major DOUBLE rows, which are blocked by a copy afterwards.
+inline bool prep_writes_blocked(int nlay, bool od_is_float, bool is_log, bool bg64_knob, bool chunks_from_line, bool rowmajor_knob,
+                                unsigned long long n) {
+  return nlay == 54 && od_is_float && !is_log && !bg64_knob && gas_can_block(nlay, chunks_from_line, rowmajor_knob, n);
+}
+
 }  // namespace sweep_layout
 }  // namespace ecckd

@@ -5,8 +5,9 @@ scaling x optical depth over the background files, accumulated in DOUBLE (read_m
 `background_conc` / reference_surface_mole_fraction (:135-141) where the script gives concentrations.
 
 The job per gas, as the reference's gas loop (find_g_points.cpp:655-1266) and the reorder_spectrum run in front of it:
-    merged background (K: ecckd_merge_spectrum_dev)  ->  sorting key + stable sort of the target spectrum (K1 + K3)
-    ->  gas preparation (K4; the first gas's Planck matrix is reused, :529, :970-984)  ->  band search (K5)
+    sorting key + stable sort of the target spectrum (K1 + K3)  ->  gas preparation (K4: the background is merged from its
+    spectra as their columns are brought into rank order, ecckd_gas_create_lw_merged; the first gas's Planck matrix is reused,
+    :529, :970-984)  ->  band search (K5)
 then the overlap of the gases' g points and the merged g-point map (:1452-1483).  bench.py, tools/gases_probe.py and the
 full-size tests drive it through pipeline.find_g_points_resident, gas after gas or with the gases' searches side by side.
 """
@@ -81,21 +82,29 @@ class FsckJob:
     def merged_background(self, gi):
         """read_merged_spectrum for the gas's background_input list: DOUBLE (nlay, nwav) on the device."""
         merged = None
+        for od, sp in self.background_sources(gi):
+            merged = api.merge_spectrum(self.ctx, od, sp, merged)
+        return merged
+
+    def background_sources(self, gi):
+        """The gas's background_input list as api.GasLW takes it: [(spectrum on the device, scaling profile)], the terms of
+        merged_background in its order."""
+        out = []
         for name, conc in self.gases[gi][2]:
             ref = SPECTRA[name][2]
             sp, _ = api.merge_scaling(self.p, conc=conc, reference_surface_vmr=ref if ref is not None else -1.0)
-            merged = api.merge_spectrum(self.ctx, self.od[name], sp, merged)
-        return merged
+            out.append((self.od[name], sp))
+        return out
 
     def load_gas(self, gi):
-        """What find_g_points has of a gas before its preparation: target, merged background, ordering (the gas's
-        reorder_spectrum step, K1 + K3, is part of the job)."""
+        """What find_g_points has of a gas before its preparation: target, the spectra of its background with their scalings
+        (the preparation merges them), ordering (the gas's reorder_spectrum step, K1 + K3, is part of the job)."""
         ctx = self.ctx
         od = self.od[self.gases[gi][1]]
-        bg = self.merged_background(gi)
         key, _ = api.reorder_key_lw(ctx, self.p, self.t_ideal, self.wn, self.dwn, od, 0.5)
         rnk, _ = api.stable_argsort_bands(ctx, key, self.begin, self.end, want_ordered=False)
-        return dict(pressure_hl=self.p, temperature_hl=self.t_file, wn=self.wn, dwn=self.dwn, rank=rnk, od=od, bg=bg,
+        return dict(pressure_hl=self.p, temperature_hl=self.t_file, wn=self.wn, dwn=self.dwn, rank=rnk, od=od,
+                    bg_sources=self.background_sources(gi),
                     sorting_variable=key, band_begin=self.begin, band_end=self.end, min_g_points=np.ones(1, dtype=int),
                     max_g_points=np.full(1, 256))
 
@@ -115,7 +124,8 @@ class FsckJob:
             g = self.load_gas(gi)
             reuse = first.view_ptr("planck_hl")[0] if first is not None else None
             gas, sv, _ = pipeline._prepare_gas(self.ctx, g, "transmission", 0.0, 0.0, reuse, None)
-            g.pop("bg")
+            g.pop("bg", None)
+            g.pop("bg_sources", None)
             first = first or gas
             gases.append(gas)
             self._prepared.append((g, sv))

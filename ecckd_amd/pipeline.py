@@ -481,8 +481,9 @@ def _prepare_gas(ctx, g, averaging_method, flux_weight, min_pressure, planck_reu
     timing = g.setdefault("timing", {})
     t0 = time.perf_counter()
     if sw is None:
+        # the background as the merged matrix "bg", or as the spectra it is merged from, "bg_sources" (api.GasLW)
         gas = api.GasLW(ctx, g["pressure_hl"], g["temperature_hl"], g["wn"], g["dwn"], g["rank"], g["od"], g.get("bg"),
-                        averaging_method, flux_weight, min_pressure, planck_hl_reuse=planck_reuse)
+                        averaging_method, flux_weight, min_pressure, planck_hl_reuse=planck_reuse, bg_sources=g.get("bg_sources"))
         band_albedo = None
     else:
         gas = api.GasSW(ctx, g["pressure_hl"], sw["ssi"], g["rank"], g["od"], g.get("bg"), averaging_method, flux_weight,
@@ -828,7 +829,7 @@ def find_g_points_resident(ctx, names, load_gas, nband, heating_rate_tolerance, 
                     planck_first = api.planck_hl_sorted(ctx, o0["temperature_hl"], o0["wn"], o0["dwn"], o0["rank"])
                 reuse = planck_first.data_ptr()
             gas, sv_sorted, band_albedo = _prepare_gas(ctx, g, averaging_method, flux_weight, min_pressure, reuse, sw)
-            for k in ("od", "bg"):                # the spectra are in the gas's rows now
+            for k in ("od", "bg", "bg_sources"):  # the spectra are in the gas's rows now
                 g.pop(k, None)
             req = _band_requests(g, my_bands[gi], tol, band_albedo)
             prepared[gi] = (g, gas, sv_sorted)

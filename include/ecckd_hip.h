@@ -171,6 +171,23 @@ int ecckd_gas_create_lw(ecckd_ctx* ctx, int nlay, size_t nwav,
                         int averaging_method, double flux_weight, double min_pressure,
                         const double* d_planck_hl_reuse, ecckd_gas** gas);
 
+/* The same gas from a background given as the list of spectra it is merged from (read_merged_spectrum.cpp:152-166)
+ * instead of the merged matrix: nbg spectra d_bg_od[s] (bg_type[s] ECCKD_F32 or ECCKD_F64, row stride bg_stride[s] >= nwav,
+ * ORIGINAL order) with the factors h_bg_scale[nbg][nlay] (ecckd_merge_scaling).  The gas is, array for array and bit for
+ * bit, the one ecckd_gas_create_lw returns for the DOUBLE matrix that ecckd_merge_spectrum_dev leaves after nbg calls
+ * (= ecckd_merge_scenario_dev): product rounded, then the sum, in the order of the list.  With 54 layers, a FLOAT target
+ * and not the logarithmic method the merged matrix is never stored - the spectra are merged as their columns are brought
+ * into rank order -; otherwise it is a temporary of the call.  nbg = 0: no background; at most 16 spectra. */
+int ecckd_gas_create_lw_merged(ecckd_ctx* ctx, int nlay, size_t nwav,
+                               const double* h_pressure_hl, const double* h_temperature_hl,
+                               const double* d_wavenumber, const double* d_d_wavenumber,
+                               const int32_t* d_rank,
+                               int nbg, const void* const* d_bg_od, const int* bg_type,
+                               const size_t* bg_stride, const double* h_bg_scale,
+                               const void* d_od, int od_type, size_t src_stride,
+                               int averaging_method, double flux_weight, double min_pressure,
+                               const double* d_planck_hl_reuse, ecckd_gas** gas);
+
 /* The Planck matrix alone, d_planck_hl[nlay+1][nwav] in the order given by d_rank: bit-identical to the "planck_hl" view
  * of a gas created with the same ordering and temperature profile.  The reference evaluates the matrix for the FIRST gas
  * and reuses it for every later one (find_g_points.cpp:529, :970-984); a process that searches only later gases (the
