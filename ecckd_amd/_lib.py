@@ -193,6 +193,11 @@ SIGNATURES = {
                                                  C.POINTER(C.c_int), _c_double_p, C.c_int, C.c_void_p]),
     "ecckd_gas_optics_fluxes_sw_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.POINTER(C.c_int), _c_double_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p]),
+    "ecckd_gas_optics_fluxes_lw_sky_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.POINTER(C.c_int), _c_double_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "ecckd_gas_optics_fluxes_sw_sky_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.POINTER(C.c_int), _c_double_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p,
+                                                     C.c_void_p]),
     "ecckd_gas_optics_fluxes_geometry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                                    C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     "ecckd_gas_optics_fluxes_plan": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int,
@@ -400,6 +405,12 @@ class FluxOutputs(C.Structure):
     """ecckd_flux_outputs: device pointers of the fused fluxes, None = not wanted."""
     _fields_ = [(n, C.c_void_p) for n in ("flux_dn", "flux_up", "band_flux_dn", "band_flux_up", "spectral_flux_dn", "spectral_flux_up",
                                           "heating_rate", "flux_dn_direct", "band_flux_dn_direct", "spectral_flux_dn_direct")]
+
+
+class FluxSky(C.Structure):
+    """ecckd_flux_sky: device pointers of the cloud layers and the surface of the *_sky_dev fluxes, None = not given."""
+    _fields_ = [(n, C.c_void_p) for n in ("cloud_od", "cloud_ssa", "cloud_asymmetry", "surface_emissivity", "skin_temperature")] + \
+               [("delta_eddington", C.c_int)]
 
 
 class FluxPlan(C.Structure):

@@ -1377,33 +1377,73 @@ class GasOptics:
         self.ctx.synchronize()
         return res
 
+    def _sky(self, ncol, nlay, **given):
+        """The ecckd_flux_sky of the arguments that are not None (device tensors, checked for shape) -> (FluxSky, the tensors it
+        points to), or (None, ()) with none given."""
+        nband = self.nband if self.nband else 1                  # (without iband_per_g the library refuses the band inputs)
+        shapes = dict(cloud_od=(ncol, nlay, nband), cloud_ssa=(ncol, nlay, nband), cloud_asymmetry=(ncol, nlay, nband),
+                      surface_emissivity=(ncol, nband), skin_temperature=(ncol,))
+        sky, keep = _lib.FluxSky(), []
+        for name, a in given.items():
+            if a is not None:
+                keep.append(self._input(a, shapes[name], name))
+                setattr(sky, name, keep[-1].data_ptr())
+        return (sky, keep) if keep else (None, ())
+
     def fluxes_lw(self, pressure_hl, temperature_hl, vmr_fl, nangle=0, temperature_fl=None, gases=None, scalings=None,
-                  bands=False, spectral=False, heating_rate=True, dtype=None):
+                  bands=False, spectral=False, heating_rate=True, dtype=None, cloud_od=None, surface_emissivity=None,
+                  skin_temperature=None):
         """Longwave fluxes and heating rates of device columns in one launch (ecckd_gas_optics_fluxes_lw_dev): the optical
         depths of optical_depth() and the Planck function of planck() fed to the transfer of rt_lw_gpoints(nangle) without
         leaving the kernel.  -> dict of device tensors by run_ckd's names: flux_dn_lw, flux_up_lw [ncol, nlay+1];
         heating_rate_lw [ncol, nlay] (K s-1); bands: band_flux_dn_lw, band_flux_up_lw [ncol, nlay+1, nband]; spectral:
-        spectral_flux_dn_lw, spectral_flux_up_lw [ncol, nlay+1, ng].  Inputs as optical_depth()."""
-        call = lambda ncol, nlay, p, t, tfl, vmr, present, scaling, out_type, o: self.lib.ecckd_gas_optics_fluxes_lw_dev(
-            self.handle, int(nangle), ncol, nlay, p, t, tfl, vmr, present, scaling, out_type, o)
+        spectral_flux_dn_lw, spectral_flux_up_lw [ncol, nlay+1, ng].  Inputs as optical_depth().
+        Under clouds and over a real surface (ecckd_gas_optics_fluxes_lw_sky_dev; device tensors): cloud_od [ncol, nlay, nband],
+        the absorption optical depth of the particulates per band of iband_per_g, joins the gas; surface_emissivity
+        [ncol, nband] (None = 1) and skin_temperature [ncol] (None = temperature_hl[:, nlay]) make the surface Lambertian:
+        up = eps * B(skin) + (1 - eps) * dn.  With none of the three the call is the clear one."""
+        ncol, nlay = pressure_hl.shape[0], pressure_hl.shape[1] - 1
+        sky, _keep = self._sky(ncol, nlay, cloud_od=cloud_od, surface_emissivity=surface_emissivity, skin_temperature=skin_temperature)
+        if sky is None:
+            call = lambda ncol, nlay, p, t, tfl, vmr, present, scaling, out_type, o: self.lib.ecckd_gas_optics_fluxes_lw_dev(
+                self.handle, int(nangle), ncol, nlay, p, t, tfl, vmr, present, scaling, out_type, o)
+        else:
+            call = lambda ncol, nlay, p, t, tfl, vmr, present, scaling, out_type, o: self.lib.ecckd_gas_optics_fluxes_lw_sky_dev(
+                self.handle, int(nangle), ncol, nlay, p, t, tfl, vmr, present, scaling, out_type, o, C.addressof(sky))
         return self._fluxes(False, pressure_hl, temperature_hl, vmr_fl, temperature_fl, gases, scalings, bands, spectral, heating_rate, False,
                             dtype, call)
 
     def fluxes_sw(self, pressure_hl, temperature_hl, vmr_fl, cos_sza, albedo=None, tsi=1361.0, scattering=False,
-                  temperature_fl=None, gases=None, scalings=None, bands=False, spectral=False, heating_rate=True, dtype=None):
+                  temperature_fl=None, gases=None, scalings=None, bands=False, spectral=False, heating_rate=True, dtype=None,
+                  cloud_od=None, cloud_ssa=None, cloud_asymmetry=None, delta_eddington=True):
         """Shortwave fluxes and heating rates of device columns in one launch (ecckd_gas_optics_fluxes_sw_dev).  cos_sza and
         albedo (None = 0) are device tensors [ncol]; a column without sun gets zeros.  scattering=False: the direct beam and its
         reflection, rt_sw_gpoints on optical_depth + rayleigh_optical_depth -> flux_dn_direct_sw, flux_up_sw, heating_rate_sw
         (and band_ / spectral_ forms); scattering=True: the two-stream transfer of rt_sw_gpoints_rayleigh -> flux_dn_sw
-        (direct plus diffuse), flux_up_sw, flux_dn_direct_sw, heating_rate_sw (and band_ / spectral_ forms)."""
-        ncol = pressure_hl.shape[0]
+        (direct plus diffuse), flux_up_sw, flux_dn_direct_sw, heating_rate_sw (and band_ / spectral_ forms).
+        Under clouds (ecckd_gas_optics_fluxes_sw_sky_dev, scattering=True only; device tensors [ncol, nlay, nband], the band of
+        a g point by iband_per_g): cloud_od (extinction), cloud_ssa and cloud_asymmetry of the particulates are mixed into the
+        gas in every layer whose cloud_od is > 0; delta_eddington=True scales the triple in the kernel, False takes it as
+        scaled already.  The values are not validated.  With none of the three the call is the clear one."""
+        ncol, nlay = pressure_hl.shape[0], pressure_hl.shape[1] - 1
+        sky, _keep = self._sky(ncol, nlay, cloud_od=cloud_od, cloud_ssa=cloud_ssa, cloud_asymmetry=cloud_asymmetry)
+        if sky is not None:
+            if not scattering:
+                raise EcckdError(_lib.PARAMETER_ERROR, "fluxes_sw: cloud layers need scattering=True "
+                                 "(ecckd_gas_optics_fluxes_sw_sky_dev is always the two-stream transfer)")
+            sky.delta_eddington = int(delta_eddington)
         if cos_sza is None:
             raise EcckdError(_lib.PARAMETER_ERROR, "fluxes_sw: cos_sza is needed")
         mu0 = self._input(cos_sza, (ncol,), "cos_sza")
         alb = self._input(albedo, (ncol,), "albedo")
-        call = lambda ncol, nlay, p, t, tfl, vmr, present, scaling, out_type, o: self.lib.ecckd_gas_optics_fluxes_sw_dev(
-            self.handle, int(scattering), ncol, nlay, p, t, tfl, vmr, present, scaling, _dptr(mu0), _dptr(alb) if alb is not None else None,
-            float(tsi), out_type, o)
+        if sky is None:
+            call = lambda ncol, nlay, p, t, tfl, vmr, present, scaling, out_type, o: self.lib.ecckd_gas_optics_fluxes_sw_dev(
+                self.handle, int(scattering), ncol, nlay, p, t, tfl, vmr, present, scaling, _dptr(mu0), _dptr(alb) if alb is not None else None,
+                float(tsi), out_type, o)
+        else:
+            call = lambda ncol, nlay, p, t, tfl, vmr, present, scaling, out_type, o: self.lib.ecckd_gas_optics_fluxes_sw_sky_dev(
+                self.handle, ncol, nlay, p, t, tfl, vmr, present, scaling, _dptr(mu0), _dptr(alb) if alb is not None else None,
+                float(tsi), out_type, o, C.addressof(sky))
         return self._fluxes(True, pressure_hl, temperature_hl, vmr_fl, temperature_fl, gases, scalings, bands, spectral, heating_rate,
                             bool(scattering), dtype, call)
 

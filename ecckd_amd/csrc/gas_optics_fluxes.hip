@@ -19,6 +19,10 @@
 // Nothing a column computes depends on the batch, the grid or the column's place in it, and there are no atomics.
 // A, B and the heating rate are compiled without contraction (the bits of the stand-alone calls); C with the default, as
 // lbl_fluxes.hip is.
+// The sky instances (ecckd_gas_optics_fluxes_{lw,sw}_sky_dev with an ecckd_flux_sky that gives something) differ in A and C
+// only: longwave adds the band's cloud optical depth to tau after the clamp and runs every angle down before every angle up
+// from the Lambertian surface (transfer_lw_sky); two-stream takes cloud_layer of lbl_rt.hpp in the layers that have a cloud
+// (transfer_sw_twostream_sky).  Rows, LDS and plan are those of the clear instance of the mode.
 #include "gas_optics_device.hpp"
 #include "lbl_rt.hpp"
 
@@ -26,7 +30,7 @@
 #include <string>
 
 namespace go = ecckd::gas_optics;
-using ecckd::lbl::RayleighLayer; using ecckd::lbl::rayleigh_layer; using ecckd::lbl::rayleigh_up; using ecckd::lbl::rayleigh_down;
+using ecckd::lbl::RayleighLayer; using ecckd::lbl::rayleigh_layer; using ecckd::lbl::cloud_layer; using ecckd::lbl::rayleigh_up; using ecckd::lbl::rayleigh_down;
 
 namespace {
 
@@ -48,6 +52,15 @@ struct FxCall {
   size_t ngroup, block_doubles;
   int ntp, nband, nsec, ncol;
   int cpb, layer_tile, passes, reduce_levels, width;
+};
+
+// what the sky instances read beside it (ecckd_flux_sky); an argument of its own, and an empty one for the clear instances,
+// whose arguments so stay what they were
+template <bool SKY> struct FxSky {};
+template <> struct FxSky<true> {
+  const double *cloud_od, *cloud_ssa, *cloud_asymmetry;   // [ncol][nlay][nband] or NULL
+  const double *surface_emissivity, *skin_temperature;    // [ncol][nband], [ncol] or NULL
+  int delta_eddington, nband;
 };
 
 // The optical depth of one (cell, g) from the cell's entries, as k_gas_optics forms and clamps its total, and the Rayleigh
@@ -153,16 +166,110 @@ __device__ inline void transfer_sw_twostream(int nlay, double mu0, double minus_
   }
 }
 
+// transfer_lw over a Lambertian surface of emissivity eps and Planck function b_skin: every angle's down sweep first, then
+// every angle's up sweep from eps * b_skin + (1 - eps) * dn[nlay] with dn[nlay] the angle-summed flux (optimize.hip's coupling
+// of its angle form; with one angle the reference's own surface line).  The sweeps' expressions and the order in which the
+// angles are added are transfer_lw's.
+__device__ inline void transfer_lw_sky(int nlay, int nsec, const double* sec_wgt, double eps, double b_skin, const double* tau, const double* pl,
+                                       double* fd, double* fu) {
+  constexpr size_t ng = THREADS;
+  for (int l = 0; l <= nlay; ++l) { fd[(size_t)l * ng] = 0.0; fu[(size_t)l * ng] = 0.0; }
+  for (int a = 0; a < nsec; ++a) {
+    const double sec = sec_wgt[a], w = sec_wgt[nsec + a];
+    double f = 0.0;
+    for (int l = 0; l < nlay; ++l) {
+      const double x = tau[(size_t)l * ng];
+      const double e = 1.0 - exp(-sec * x);
+      const double fac = e > 1.0e-5 ? 1.0 - e * (1.0 / sec) / x : 0.5 * e;
+      f = f * (1.0 - e) + pl[(size_t)l * ng] * (e - fac) + pl[(size_t)(l + 1) * ng] * fac;
+      fd[(size_t)(l + 1) * ng] += w * f;
+    }
+  }
+  const double surface = eps * b_skin + (1.0 - eps) * fd[(size_t)nlay * ng];
+  for (int a = 0; a < nsec; ++a) {
+    const double sec = sec_wgt[a], w = sec_wgt[nsec + a];
+    double f = surface;
+    fu[(size_t)nlay * ng] += w * f;
+    for (int l = nlay - 1; l >= 0; --l) {
+      const double x = tau[(size_t)l * ng];
+      const double e = 1.0 - exp(-sec * x);
+      const double fac = e > 1.0e-5 ? 1.0 - e * (1.0 / sec) / x : 0.5 * e;
+      f = f * (1.0 - e) + pl[(size_t)(l + 1) * ng] * (e - fac) + pl[(size_t)l * ng] * fac;
+      fu[(size_t)l * ng] += w * f;
+    }
+  }
+}
+
+// The cloud of one (cell, band) as the layer takes it: false where cloud_od is not > 0 (the clear layer), else the triple,
+// delta-Eddington scaled here where the call asks for it.  Read from the small arrays in each sweep, not kept per thread.
+__device__ inline bool cloud_values(const FxSky<true>& x, size_t i, double& t, double& w, double& a) {
+  t = x.cloud_od[i];
+  if (!(t > 0.0)) return false;
+  w = x.cloud_ssa[i];
+  a = x.cloud_asymmetry[i];
+  if (x.delta_eddington) {
+    const double f = a * a;
+    t = t * (1.0 - w * f);
+    a = a / (1.0 + a);
+    w = w * (1.0 - f) / (1.0 - w * f);
+  }
+  return true;
+}
+
+__device__ inline RayleighLayer sky_layer(const FxSky<true>& x, size_t i, double tau_abs, double tau_ray, double mu0, double minus_sec_sza) {
+  double t, w, a;
+  if (!cloud_values(x, i, t, w, a)) return rayleigh_layer(tau_abs, tau_ray, mu0, minus_sec_sza);
+  return cloud_layer(tau_abs, tau_ray, t, w, a, mu0, minus_sec_sza);
+}
+
+// transfer_sw_twostream with the cloud of the thread's band in the layers that have one; cloud0 = (col * nlay) * nband + band
+// is the thread's first cloud value, the next layer's nband further on
+__device__ inline void transfer_sw_twostream_sky(const FxSky<true>& x, size_t cloud0, int nlay, double mu0, double minus_sec_sza, double albedo,
+                                                 double incoming, const double* tau_abs, const double* tau_ray, double* fdir, double* fd,
+                                                 double* fu) {
+  constexpr size_t ng = THREADS;
+  const size_t nband = (size_t)x.nband;
+  double f = mu0 * incoming;
+  fdir[0] = f;
+  for (int l = 0; l < nlay; ++l) {
+    double t, w, a;
+    if (cloud_values(x, cloud0 + (size_t)l * nband, t, w, a))
+      f = f * exp(minus_sec_sza * (tau_abs[(size_t)l * ng] + tau_ray[(size_t)l * ng] + t));
+    else
+      f = f * exp(minus_sec_sza * (tau_abs[(size_t)l * ng] + tau_ray[(size_t)l * ng]));
+    fdir[(size_t)(l + 1) * ng] = f;
+  }
+  double a = albedo, src = albedo * f;
+  fd[(size_t)nlay * ng] = a;
+  fu[(size_t)nlay * ng] = src;
+  for (int l = nlay - 1; l >= 0; --l) {
+    const RayleighLayer L = sky_layer(x, cloud0 + (size_t)l * nband, tau_abs[(size_t)l * ng], tau_ray[(size_t)l * ng], mu0, minus_sec_sza);
+    rayleigh_up(L, fdir[(size_t)l * ng], a, src, a, src);
+    fd[(size_t)l * ng] = a;
+    fu[(size_t)l * ng] = src;
+  }
+  double diffuse = 0.0, flux_up = src;
+  fd[0] = diffuse + fdir[0];
+  for (int l = 0; l < nlay; ++l) {
+    const RayleighLayer L = sky_layer(x, cloud0 + (size_t)l * nband, tau_abs[(size_t)l * ng], tau_ray[(size_t)l * ng], mu0, minus_sec_sza);
+    rayleigh_down(L, fdir[(size_t)l * ng], fd[(size_t)(l + 1) * ng], fu[(size_t)(l + 1) * ng], diffuse, diffuse, flux_up);
+    fd[(size_t)(l + 1) * ng] = diffuse + fdir[(size_t)(l + 1) * ng];
+    fu[(size_t)(l + 1) * ng] = flux_up;
+  }
+}
+
 // the state rows of a mode (gas_optics_tables.hpp flux_state_rows): which row holds what
 template <int MODE> struct Rows;
 template <> struct Rows<LW> { static constexpr int N = 4, TAU = 0, PL = 1, DN = 2, UP = 3, RAY = -1, DIR = -1; };
 template <> struct Rows<SW_DIRECT> { static constexpr int N = 3, TAU = 0, DN = 1, UP = 2, PL = -1, RAY = -1, DIR = -1; };
 template <> struct Rows<SW_TWOSTREAM> { static constexpr int N = 5, TAU = 0, RAY = 1, DIR = 2, DN = 3, UP = 4, PL = -1; };
 
-template <int MODE, bool F32>
-__global__ __launch_bounds__(THREADS) void k_gas_optics_fluxes(const GoModel m, const GoCall c, const FxCall x) {
+// SKY: the instances of ecckd_gas_optics_fluxes_{lw,sw}_sky_dev (longwave and two-stream; the state rows are the clear ones)
+template <int MODE, bool F32, bool SKY>
+__global__ __launch_bounds__(THREADS) void k_gas_optics_fluxes(const GoModel m, const GoCall c, const FxCall x, const FxSky<SKY> sky) {
   using R = Rows<MODE>;
   static_assert(R::N == go::flux_state_rows(MODE), "state rows");
+  static_assert(!SKY || MODE != SW_DIRECT, "the direct-beam mode has no sky instance");
   extern __shared__ double s_mem[];
   const int nent = m.nent, ng = m.ng, nlay = c.nlay, nhl = nlay + 1;
   const int cpb = x.cpb, LT = x.layer_tile, width = x.width;
@@ -187,6 +294,12 @@ __global__ __launch_bounds__(THREADS) void k_gas_optics_fluxes(const GoModel m, 
       const bool live = ci < ncg && g < (unsigned)ng && (one_pass ? t < (unsigned)cpb * (unsigned)ng : true);
       double* const my = rows + (size_t)pass * pass_doubles + t;  // row r, level l: my[((size_t)r * nhl + l) * THREADS]
       auto row = [&](int r) { return my + (size_t)r * nhl * THREADS; };
+      // (sky) the thread's first cloud value, [col][layer 0][band of g]; the next layer's is nband further on
+      size_t band = 0, cloud0 = 0;
+      if constexpr (SKY) {
+        band = live && x.iband ? (size_t)x.iband[g] : 0;
+        cloud0 = col * (size_t)nlay * (size_t)sky.nband + band;
+      }
       // ---- A: optical depths, a tile of layers at a time
       for (int l0 = 0; l0 < nlay; l0 += LT) {
         const unsigned ln = (unsigned)(nlay - l0 < LT ? nlay - l0 : LT);
@@ -202,6 +315,11 @@ __global__ __launch_bounds__(THREADS) void k_gas_optics_fluxes(const GoModel m, 
             double* tau = row(R::TAU) + (size_t)(l0 + li) * THREADS;
             double* ray = MODE == SW_TWOSTREAM ? row(R::RAY) + (size_t)(l0 + li) * THREADS : nullptr;
             cell_optical_depth<MODE>(m, c.present, s_coef + cl * nent, s_idx + cl * nent, s_moles[cl], g, tau, ray);
+            if constexpr (SKY && MODE == LW)
+              if (sky.cloud_od) {                                 // the absorption optical depth of the band's cloud joins after the clamp
+                const double cloud = sky.cloud_od[cloud0 + (size_t)(l0 + li) * (size_t)sky.nband];
+                if (cloud > 0.0) *tau = *tau + cloud;
+              }
           }
       }
       if (live) {
@@ -211,7 +329,13 @@ __global__ __launch_bounds__(THREADS) void k_gas_optics_fluxes(const GoModel m, 
           double* pl = row(R::PL);
           for (int l = 0; l < nhl; ++l) pl[(size_t)l * THREADS] = planck_value(x.ntp, x.tpl, x.planck, ng, g, T[l]);
           // ---- C
-          transfer_lw(nlay, x.nsec, x.sec_wgt, row(R::TAU), pl, row(R::DN), row(R::UP));
+          if constexpr (SKY) {
+            const double eps = sky.surface_emissivity ? sky.surface_emissivity[col * (size_t)sky.nband + band] : 1.0;
+            const double b_skin = sky.skin_temperature ? planck_value(x.ntp, x.tpl, x.planck, ng, g, sky.skin_temperature[col]) : pl[(size_t)nlay * THREADS];
+            transfer_lw_sky(nlay, x.nsec, x.sec_wgt, eps, b_skin, row(R::TAU), pl, row(R::DN), row(R::UP));
+          } else {
+            transfer_lw(nlay, x.nsec, x.sec_wgt, row(R::TAU), pl, row(R::DN), row(R::UP));
+          }
         } else {
           const double mu0 = x.cos_sza[col], albedo = x.albedo ? x.albedo[col] : 0.0;
           if (!(mu0 > 0.0)) {                                     // no sun: zeros in every output
@@ -223,6 +347,7 @@ __global__ __launch_bounds__(THREADS) void k_gas_optics_fluxes(const GoModel m, 
           } else {
             const double incoming = incoming_value(x.tsi_scaling, x.solar[g]);
             if (MODE == SW_DIRECT) transfer_sw_direct(nlay, mu0, albedo, incoming, row(R::TAU), row(R::DN), row(R::UP));
+            else if constexpr (SKY) transfer_sw_twostream_sky(sky, cloud0, nlay, mu0, -1.0 / mu0, albedo, incoming, row(R::TAU), row(R::RAY), row(R::DIR), row(R::DN), row(R::UP));
             else transfer_sw_twostream(nlay, mu0, -1.0 / mu0, albedo, incoming, row(R::TAU), row(R::RAY), row(R::DIR), row(R::DN), row(R::UP));
           }
         }
@@ -289,12 +414,12 @@ __global__ __launch_bounds__(THREADS) void k_gas_optics_fluxes(const GoModel m, 
   }
 }
 
-template <int MODE, bool F32>
-int launch(ecckd_gas_optics* h, const ecckd_flux_plan& plan, const GoModel& m, const GoCall& c, const FxCall& x) {
-  const auto kernel = k_gas_optics_fluxes<MODE, F32>;
+template <int MODE, bool F32, bool SKY = false>
+int launch(ecckd_gas_optics* h, const ecckd_flux_plan& plan, const GoModel& m, const GoCall& c, const FxCall& x, const FxSky<SKY>& sky = {}) {
+  const auto kernel = k_gas_optics_fluxes<MODE, F32, SKY>;
   if (plan.lds_bytes > 48 * 1024)
     ECCKD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes));
-  hipLaunchKernelGGL(kernel, dim3(plan.grid), dim3(plan.threads), plan.lds_bytes, h->ctx->stream, m, c, x);
+  hipLaunchKernelGGL(kernel, dim3(plan.grid), dim3(plan.threads), plan.lds_bytes, h->ctx->stream, m, c, x, sky);
   ECCKD_HIP_CHECK(hipGetLastError());
   return ECCKD_OK;
 }
@@ -316,7 +441,9 @@ int fluxes(ecckd_gas_optics* h, const go::FluxCallArgs& a, const double* d_press
   int mode = 0;
   unsigned wants = 0;
   ecckd_flux_plan plan{};
+  bool sky = false;
   int rc = go::check_fluxes_call(f, a, present, mode, wants, err);
+  if (rc == ECCKD_OK) rc = go::check_fluxes_sky(f, a, sky, err);
   if (rc == ECCKD_OK)
     rc = go::fluxes_plan(a.ncol, a.nlay, f.ng, f.nent, f.nband, mode, a.nangle, wants, std::max(h->ctx->num_cu, 1), grid_override(), plan, err);
   if (rc != ECCKD_OK) return ecckd::fail(rc, "%s", err.c_str());
@@ -332,7 +459,7 @@ int fluxes(ecckd_gas_optics* h, const go::FluxCallArgs& a, const double* d_press
   x.ntp = f.ntp; x.nband = f.nband; x.ncol = a.ncol;
   if (mode == LW) {
     std::vector<double> sec_wgt;
-    ECCKD_CHECK(ecckd::lbl::lw_angle_table("ecckd_gas_optics_fluxes_lw_dev", a.nangle, &x.nsec, sec_wgt));
+    ECCKD_CHECK(ecckd::lbl::lw_angle_table(a.sky_call ? "ecckd_gas_optics_fluxes_lw_sky_dev" : "ecckd_gas_optics_fluxes_lw_dev", a.nangle, &x.nsec, sec_wgt));
     std::copy(sec_wgt.begin(), sec_wgt.end(), x.sec_wgt);
   } else {
     x.tsi_scaling = go::incoming_scaling(f, tsi);
@@ -346,6 +473,12 @@ int fluxes(ecckd_gas_optics* h, const go::FluxCallArgs& a, const double* d_press
   ECCKD_CHECK(ecckd::carve_scratch(h->ctx, {plan.scratch_bytes}, d));
   x.scratch = (double*)d[0];
   const bool f32 = a.out_type == ECCKD_F32;
+  if (sky) {                                                      // (without a sky pointer the call is the clear call: the clear instance)
+    const FxSky<true> s = {a.sky->cloud_od, a.sky->cloud_ssa, a.sky->cloud_asymmetry, a.sky->surface_emissivity, a.sky->skin_temperature,
+                           a.sky->delta_eddington, f.nband};
+    if (mode == LW) return f32 ? launch<LW, true, true>(h, plan, m, c, x, s) : launch<LW, false, true>(h, plan, m, c, x, s);
+    return f32 ? launch<SW_TWOSTREAM, true, true>(h, plan, m, c, x, s) : launch<SW_TWOSTREAM, false, true>(h, plan, m, c, x, s);
+  }
   if (mode == LW) return f32 ? launch<LW, true>(h, plan, m, c, x) : launch<LW, false>(h, plan, m, c, x);
   if (mode == SW_DIRECT) return f32 ? launch<SW_DIRECT, true>(h, plan, m, c, x) : launch<SW_DIRECT, false>(h, plan, m, c, x);
   return f32 ? launch<SW_TWOSTREAM, true>(h, plan, m, c, x) : launch<SW_TWOSTREAM, false>(h, plan, m, c, x);
@@ -371,6 +504,27 @@ int ecckd_gas_optics_fluxes_sw_dev(ecckd_gas_optics* h, int scattering, int ncol
   ECCKD_REQUIRE(h, "ecckd_gas_optics_fluxes_sw_dev: handle is NULL");
   const go::FluxCallArgs a = {true, 0, scattering, ncol, nlay, d_pressure_hl != nullptr, d_temperature_hl != nullptr, d_vmr_fl != nullptr,
                               d_cos_sza != nullptr, h_gas_present, out_type, out};
+  return fluxes(h, a, d_pressure_hl, d_temperature_hl, d_temperature_fl, d_vmr_fl, h_gas_scaling, d_cos_sza, d_albedo, tsi);
+}
+
+int ecckd_gas_optics_fluxes_lw_sky_dev(ecckd_gas_optics* h, int nangle, int ncol, int nlay, const double* d_pressure_hl,
+                                       const double* d_temperature_hl, const double* d_temperature_fl, const double* d_vmr_fl,
+                                       const int* h_gas_present, const double* h_gas_scaling, int out_type, const ecckd_flux_outputs* out,
+                                       const ecckd_flux_sky* sky) {
+  ECCKD_REQUIRE(h, "ecckd_gas_optics_fluxes_lw_sky_dev: handle is NULL");
+  const go::FluxCallArgs a = {false, nangle, 0, ncol, nlay, d_pressure_hl != nullptr, d_temperature_hl != nullptr, d_vmr_fl != nullptr, false,
+                              h_gas_present, out_type, out, true, sky};
+  return fluxes(h, a, d_pressure_hl, d_temperature_hl, d_temperature_fl, d_vmr_fl, h_gas_scaling, nullptr, nullptr, 0.0);
+}
+
+int ecckd_gas_optics_fluxes_sw_sky_dev(ecckd_gas_optics* h, int ncol, int nlay, const double* d_pressure_hl, const double* d_temperature_hl,
+                                       const double* d_temperature_fl, const double* d_vmr_fl, const int* h_gas_present,
+                                       const double* h_gas_scaling, const double* d_cos_sza, const double* d_albedo, double tsi, int out_type,
+                                       const ecckd_flux_outputs* out, const ecckd_flux_sky* sky) {
+  ECCKD_REQUIRE(h, "ecckd_gas_optics_fluxes_sw_sky_dev: handle is NULL");
+  // (always the two-stream transfer)
+  const go::FluxCallArgs a = {true, 0, 1, ncol, nlay, d_pressure_hl != nullptr, d_temperature_hl != nullptr, d_vmr_fl != nullptr,
+                              d_cos_sza != nullptr, h_gas_present, out_type, out, true, sky};
   return fluxes(h, a, d_pressure_hl, d_temperature_hl, d_temperature_fl, d_vmr_fl, h_gas_scaling, d_cos_sza, d_albedo, tsi);
 }
 

@@ -169,8 +169,13 @@ int fluxes_plan(long long ncol, int nlay, int ng, int nent, int nband, int mode,
   return ECCKD_OK;
 }
 
+static const char* fluxes_entry(const FluxCallArgs& a) {
+  if (a.sky_call) return a.sw_call ? "ecckd_gas_optics_fluxes_sw_sky_dev" : "ecckd_gas_optics_fluxes_lw_sky_dev";
+  return a.sw_call ? "ecckd_gas_optics_fluxes_sw_dev" : "ecckd_gas_optics_fluxes_lw_dev";
+}
+
 int check_fluxes_call(const Flat& f, const FluxCallArgs& a, uint32_t& present_mask, int& mode, unsigned& wants, std::string& err) {
-  const char* who = a.sw_call ? "ecckd_gas_optics_fluxes_sw_dev" : "ecckd_gas_optics_fluxes_lw_dev";
+  const char* who = fluxes_entry(a);
   if (a.sw_call != f.is_sw)
     return refuse(err, "%s: the handle holds a %s model", who, f.is_sw ? "shortwave" : "longwave");
   if (!a.sw_call && (a.nangle < 0 || a.nangle > FLUX_MAX_ANGLES)) return refuse(err, "%s: nangle = %d outside 0..%d", who, a.nangle, FLUX_MAX_ANGLES);
@@ -204,6 +209,33 @@ int check_fluxes_call(const Flat& f, const FluxCallArgs& a, uint32_t& present_ma
   }
   if (a.out_type != ECCKD_F64 && a.out_type != ECCKD_F32)
     return refuse(err, "%s: out_type %d is neither ECCKD_F32 nor ECCKD_F64", who, a.out_type);
+  return ECCKD_OK;
+}
+
+int check_fluxes_sky(const Flat& f, const FluxCallArgs& a, bool& sky_given, std::string& err) {
+  const char* who = fluxes_entry(a);
+  sky_given = false;
+  if (!a.sky) return ECCKD_OK;
+  const ecckd_flux_sky& s = *a.sky;
+  if (s.delta_eddington != 0 && s.delta_eddington != 1)
+    return refuse(err, "%s: sky.delta_eddington must be 0 or 1, not %d", who, s.delta_eddington);
+  if (a.sw_call) {
+    if (s.surface_emissivity) return refuse(err, "%s: sky.surface_emissivity belongs to the longwave call (the shortwave surface is d_albedo)", who);
+    if (s.skin_temperature) return refuse(err, "%s: sky.skin_temperature belongs to the longwave call", who);
+    if (s.cloud_od && !s.cloud_ssa) return refuse(err, "%s: sky.cloud_od is given without sky.cloud_ssa", who);
+    if (s.cloud_od && !s.cloud_asymmetry) return refuse(err, "%s: sky.cloud_od is given without sky.cloud_asymmetry", who);
+    if (s.cloud_ssa && !s.cloud_od) return refuse(err, "%s: sky.cloud_ssa is given without sky.cloud_od", who);
+    if (s.cloud_asymmetry && !s.cloud_od) return refuse(err, "%s: sky.cloud_asymmetry is given without sky.cloud_od", who);
+  } else {
+    if (s.cloud_ssa) return refuse(err, "%s: sky.cloud_ssa belongs to the shortwave call (longwave scattering is not treated)", who);
+    if (s.cloud_asymmetry) return refuse(err, "%s: sky.cloud_asymmetry belongs to the shortwave call (longwave scattering is not treated)", who);
+    if (s.delta_eddington != 0) return refuse(err, "%s: sky.delta_eddington = 1 belongs to the shortwave call", who);
+  }
+  if (f.nband == 0) {
+    const char* band_input = s.cloud_od ? "cloud_od" : (s.surface_emissivity ? "surface_emissivity" : nullptr);
+    if (band_input) return refuse(err, "%s: sky.%s is indexed by band, and the model was created without iband_per_g", who, band_input);
+  }
+  sky_given = s.cloud_od || s.surface_emissivity || s.skin_temperature;
   return ECCKD_OK;
 }
 

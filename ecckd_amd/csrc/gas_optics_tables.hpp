@@ -108,10 +108,15 @@ struct FluxCallArgs {
   const int* gas_present;          // [ngas] or NULL
   int out_type;
   const ecckd_flux_outputs* out;
+  bool sky_call = false;           // ecckd_gas_optics_fluxes_{lw,sw}_sky_dev: the refusals carry that entry's name
+  const ecckd_flux_sky* sky = nullptr;
 };
 // The refusals of the two fused-flux calls, each with its own message; on ECCKD_OK the gases that contribute, the mode and
 // what the outputs ask for (WANT_*).
 int check_fluxes_call(const Flat& f, const FluxCallArgs& a, uint32_t& present_mask, int& mode, unsigned& wants, std::string& err);
+// The refusals the sky argument of the *_sky_dev calls adds (after check_fluxes_call); on ECCKD_OK `sky_given` says whether any
+// of its pointers is set: without one the call is the clear call and runs the clear kernel.
+int check_fluxes_sky(const Flat& f, const FluxCallArgs& a, bool& sky_given, std::string& err);
 
 }  // namespace gas_optics
 }  // namespace ecckd

@@ -110,6 +110,61 @@ __device__ __forceinline__ RayleighLayer rayleigh_layer(double tau_abs, double t
   return L;
 }
 
+// The layer of the resident fluxes under a cloud (gas_optics_fluxes.hip; tests/allsky_ref.py restates it): a particulate of
+// optical depth t, single-scattering albedo ws and asymmetry a (delta-scaled by the caller where that is wanted) mixed into the
+// gas, tau = tau_abs + tau_ray + t, sc = tau_ray + ws t, w = sc / tau, gg = ws t a / sc, under ecRad's shortwave coefficients
+//   fac = 0.75 gg, g1 = 2 - w (1.25 + fac), g2 = w (0.75 - fac), g3 = 0.5 - mu0 fac, g4 = 1 - g3
+// and otherwise rayleigh_layer's closed form, branches and clamps.  g3 and g4 depend on mu0, so cloud_direct forms them, a1 and
+// a2 from the angle it is given: in the resonance treatment every place mu0 occurs takes the shifted angle.
+__device__ __forceinline__ void cloud_direct(double w, double k, double e, double e2, double f, double g1, double g2, double fac, double mu0,
+                                             double tdir, double& rdir, double& tdd) {
+  const double g3 = 0.5 - mu0 * fac, g4 = 1.0 - g3;
+  const double a1 = g1 * g4 + g2 * g3;
+  const double a2 = g1 * g3 + g2 * g4;
+  const double km = k * mu0;
+  const double f2 = w * f / (1.0 - km * km);
+  rdir = f2 * ((1.0 - km) * (a2 + k * g3) - (1.0 + km) * (a2 - k * g3) * e2 - 2.0 * k * e * (g3 - a2 * mu0) * tdir);
+  tdd = f2 * (2.0 * k * e * (g4 + a1 * mu0) - tdir * ((1.0 + km) * (a1 + k * g4) - (1.0 - km) * (a1 - k * g4) * e2));
+}
+
+__device__ __forceinline__ RayleighLayer cloud_layer(double tau_abs, double tau_ray, double t, double ws, double a, double mu0,
+                                                     double minus_sec_sza) {
+  RayleighLayer L;
+  const double tau = tau_abs + tau_ray + t;
+  L.Tdir = exp(minus_sec_sza * tau);
+  const double sc_cloud = ws * t;
+  const double sc = tau_ray + sc_cloud;
+  if (!(sc > 0.0 && tau > 0.0)) {
+    L.R = 0.0; L.T = exp(-2.0 * tau); L.Rdir = 0.0; L.Tdd = 0.0;
+    return L;
+  }
+  const double w = sc / tau;
+  const double gg = sc_cloud * a / sc;
+  const double fac = 0.75 * gg;
+  const double g1 = 2.0 - w * (1.25 + fac), g2 = w * (0.75 - fac);
+  const double k = sqrt(fmax((g1 - g2) * (g1 + g2), 1e-12));
+  const double e = exp(-k * tau);
+  const double e2 = e * e;
+  const double f = 1.0 / (k + g1 + (k - g1) * e2);
+  L.R = g2 * (1.0 - e2) * f;
+  L.T = 2.0 * k * e * f;
+  double rdir, tdd;
+  if (fabs(1.0 - k * mu0) < RAYLEIGH_RESONANCE_H) {
+    const double mu_a = (1.0 - 2.0 * RAYLEIGH_RESONANCE_H) / k, mu_b = (1.0 + 2.0 * RAYLEIGH_RESONANCE_H) / k;
+    double ra, ta, rb, tb;
+    cloud_direct(w, k, e, e2, f, g1, g2, fac, mu_a, exp((-1.0 / mu_a) * tau), ra, ta);
+    cloud_direct(w, k, e, e2, f, g1, g2, fac, mu_b, exp((-1.0 / mu_b) * tau), rb, tb);
+    const double x = (mu0 - mu_a) / (mu_b - mu_a);
+    rdir = ra + (rb - ra) * x;
+    tdd = ta + (tb - ta) * x;
+  } else {
+    cloud_direct(w, k, e, e2, f, g1, g2, fac, mu0, L.Tdir, rdir, tdd);
+  }
+  L.Rdir = fmin(fmax(rdir, 0.0), 1.0 - L.Tdir);
+  L.Tdd = fmin(fmax(tdd, 0.0), 1.0 - L.Tdir - L.Rdir);
+  return L;
+}
+
 // d / d tau_abs of rayleigh_direct at fixed tau_ray, forward mode: every d* argument is the derivative of the argument before
 // it.  mu may itself depend on tau_abs (the shifted angles of the resonance treatment, dmu != 0).
 __device__ __forceinline__ void rayleigh_direct_d(double w, double dw, double k, double dk, double e, double de, double e2, double de2,

@@ -1077,6 +1077,43 @@ int ecckd_gas_optics_fluxes_sw_dev(ecckd_gas_optics* gas_optics, int scattering,
                                    const double* d_temperature_hl, const double* d_temperature_fl, const double* d_vmr_fl,
                                    const int* h_gas_present, const double* h_gas_scaling, const double* d_cos_sza,
                                    const double* d_albedo, double tsi, int out_type, const ecckd_flux_outputs* out);
+/* Resident fluxes under clouds and over a real surface: the two calls above with one more argument.  `sky` == NULL, or a
+ * struct whose pointers are all NULL, runs the kernel of the clear call itself (the same bits); otherwise
+ *   longwave   tau[l][g] = max(gas total, 0) + cloud_od[col][l][band(g)] (a cloud value that is not > 0 adds nothing; the
+ *              absorption optical depth: longwave scattering is not treated).  All angles' down sweeps run first; every angle's
+ *              up sweep starts from the Lambertian surface eps * B_skin + (1 - eps) * dn[nlay] with dn[nlay] the angle-summed
+ *              flux, eps = surface_emissivity[col][band(g)] (NULL = 1) and B_skin the Planck function at skin_temperature[col]
+ *              (NULL = temperature_hl[nlay]); the base of the bottom layer keeps temperature_hl[nlay].
+ *   shortwave  always the two-stream transfer (the model must carry Rayleigh coefficients).  A layer whose cloud_od is > 0
+ *              mixes (od, ssa, asymmetry) of its band into the gas: tau = tau_abs + tau_ray + t', sc = tau_ray + w' t',
+ *              ssa = sc / tau, g = w' t' a' / sc, with ecRad's shortwave coefficients g1 = 2 - ssa (1.25 + 0.75 g),
+ *              g2 = ssa (0.75 - 0.75 g), g3 = 0.5 - 0.75 g mu0, g4 = 1 - g3 in Meador and Weaver's closed form and the adding
+ *              method of the clear call.  delta_eddington = 1: f = a a, t' = t (1 - w f), w' = w (1 - f) / (1 - w f),
+ *              a' = a / (1 + a) formed in the kernel; 0: the inputs are used as they are.  Any other layer is the clear layer.
+ * A g point takes the cloud and surface values of its band, iband_per_g[g]; nband = 1 + max(iband_per_g).  "Cloud" is any
+ * particulate (aerosols are merged by the caller); columns are independent (McICA sub-columns are columns).  The values are
+ * taken as they are: ssa and asymmetry are not validated on the device.
+ * ECCKD_PARAMETER_ERROR, each with its own message, beside the refusals of the clear calls: a band-indexed input (cloud_*,
+ * surface_emissivity) on a model created without iband_per_g; shortwave: cloud_od without cloud_ssa or cloud_asymmetry or
+ * either without cloud_od, surface_emissivity, skin_temperature; longwave: cloud_ssa, cloud_asymmetry, delta_eddington != 0;
+ * delta_eddington outside {0, 1}. */
+typedef struct {
+  const double* cloud_od;            /* [ncol][nlay][nband] device; NULL = no cloud.  SW: extinction; LW: absorption      */
+  const double* cloud_ssa;           /* [ncol][nlay][nband] shortwave only: single-scattering albedo                      */
+  const double* cloud_asymmetry;     /* [ncol][nlay][nband] shortwave only: asymmetry factor                              */
+  const double* surface_emissivity;  /* [ncol][nband] longwave only; NULL = 1                                             */
+  const double* skin_temperature;    /* [ncol] longwave only; NULL = temperature_hl[nlay]                                 */
+  int delta_eddington;               /* shortwave: 1 = scale (od, ssa, g) in the kernel, 0 = they are already scaled       */
+} ecckd_flux_sky;
+int ecckd_gas_optics_fluxes_lw_sky_dev(ecckd_gas_optics* gas_optics, int nangle, int ncol, int nlay, const double* d_pressure_hl,
+                                       const double* d_temperature_hl, const double* d_temperature_fl, const double* d_vmr_fl,
+                                       const int* h_gas_present, const double* h_gas_scaling, int out_type,
+                                       const ecckd_flux_outputs* out, const ecckd_flux_sky* sky);
+int ecckd_gas_optics_fluxes_sw_sky_dev(ecckd_gas_optics* gas_optics, int ncol, int nlay, const double* d_pressure_hl,
+                                       const double* d_temperature_hl, const double* d_temperature_fl, const double* d_vmr_fl,
+                                       const int* h_gas_present, const double* h_gas_scaling, const double* d_cos_sza,
+                                       const double* d_albedo, double tsi, int out_type, const ecckd_flux_outputs* out,
+                                       const ecckd_flux_sky* sky);
 int ecckd_gas_optics_fluxes_geometry(ecckd_gas_optics* gas_optics, int nlay, int mode, int* columns_per_block, int* threads,
                                      int* layer_tile, size_t* scratch_bytes);
 int ecckd_gas_optics_fluxes_plan(long long ncol, int nlay, int ng, int nent, int nband, int mode, int nangle, unsigned wants,
